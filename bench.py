@@ -1,7 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X spectral pipeline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c3|c5] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c3|c5] [--dump-outputs DIR] [--full] [--no-extras]
+
+A plain run sets up, warms up, times the K steps, writes the last step's output if --dump-outputs is given and prints
+the result line: nothing else.  --full adds everything else this file measures and checks: the per-rank comparison with
+the CPU oracle, the collective C5 job, the sustained / two-stream / ring-of-8 windows, the C2 / C4 / file-path side
+measurements, the CPU baseline and the live rocprofv3 traffic and VALU rooflines.  The --no-* options turn single parts of
+--full off again.
+
+--dump-outputs DIR writes what the last timed step computed -- the RGB8 pixels a caller of jpeg_amd_decode_batch receives
+-- as DIR/rgb8_sample.npy (float32, [k, 3], 24 MiB at most): the step's batch viewed as [images * height * width, 3],
+all of it when it has at most 2^21 pixels, otherwise the pixels at the flat indices
+numpy.random.default_rng(20240807).integers(0, images * height * width, 2^21), sorted and made unique.  With --gpus N > 1
+every rank writes DIR/rgb8_sample.rank<r>.npy.  The inputs are seeded, so the same arguments give the same inputs in
+every run.
 
 Metric (BASELINE.json): Mpixels/s of device-resident fused decode
 (dequant + IDCT + 4:2:0 upsample + YCbCr->RGB), and its fraction of the HBM roofline.
@@ -15,12 +28,12 @@ Workload c3 (BASELINE.json configs[2], the configuration the metric is quoted on
 the same per-GPU work at every N, so a 1/2/4/8 curve built from `value` compares like with like.
 The C5 job (configs[4]): ONE job of 4096 independent 1920x1080 images, sharded over the ranks with
 jpeg_amd.dist.shard (contiguous chunks: 512 per GPU at N = 8, all 4096 = 51 GB of coefficients + pixels on the one
-GPU at N = 1) -- strong scaling -- is measured collectively (barrier, max over ranks) at EVERY N right after the
+GPU at N = 1) -- strong scaling -- is measured collectively (barrier, max over ranks) at EVERY N (--full) right after the
 headline and reported as `extra.c5_4096x1080p`; a strong-scaling curve is built from ITS `Mpixels_per_s`.
 `--workload c5` makes that job the headline instead (`value`, "scaling": "strong").
 Every rank proves what it timed: one image of its shard is decoded again on its own, compared with the batch result on
 the device and with the CPU oracle on the host (`per_rank[i].parity_vs_oracle`, `single_equals_batch`), for the
-headline and for the C5 job.
+headline and for the C5 job (both under --full).
 There is no data-path collective in either workload: every rank decodes its own independent images;
 the only collective is an RCCL broadcast of the quantisation tables from rank 0 before the timed
 region.
@@ -63,12 +76,26 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the C2/C4/C5 side measurements")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--traffic", default="live", choices=["live", "file", "none"],
-                    help="roofline.traffic: measured now under rocprofv3 (c3, N = 1), profiles/traffic_latest.json, or null")
-    ap.add_argument("--valu", default="live", choices=["live", "none"],
+    ap.add_argument("--traffic", default=None, choices=["live", "file", "none"],
+                    help="roofline.traffic: measured now under rocprofv3 (c3, N = 1), profiles/traffic_latest.json, or null "
+                         "(default: live with --full, none without)")
+    ap.add_argument("--valu", default=None, choices=["live", "none"],
                     help="roofline.valu / extra.c4_encode_4096.valu: the VALU issue roofline of k_quad420 and k_encode_fused, measured now "
-                         "under rocprofv3 (N = 1), or omitted")
-    return ap.parse_args()
+                         "under rocprofv3 (N = 1), or omitted (default: live with --full, none without)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (see the module docstring); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's RGB8 output to DIR/rgb8_sample.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_parity = args.no_c5_job = args.no_extras = args.no_cpu = True
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "none"
+    if args.valu is None:
+        args.valu = "live" if args.full else "none"
+    return args
 
 
 class DecodeWorkload:
@@ -142,6 +169,11 @@ class DecodeWorkload:
         res["parity_vs_oracle"] = oracle_check(planes, pixels, self.size, quanta_np, threads)
         return res
 
+    def last_output(self):
+        """The pixels of the last step on the device: uint8 [n_images, height * width * 3] (the ring slot it wrote)."""
+        r = (self._step - 1) % self.ring
+        return self.out[r * self.n_images:(r + 1) * self.n_images]
+
     def host_case(self, image=0):
         """Coefficient planes and the pixels the device produced for one image of the LAST step:
         what the cpu_baseline leg decodes again on the host and compares (not timed)."""
@@ -180,6 +212,26 @@ def oracle_check(planes, pixels, size, quanta_np, threads):
     from oracle import oracle as O
     _, rect = O.decode(planes, [quanta_np[0], quanta_np[1], quanta_np[1]], [(2, 2), (1, 1), (1, 1)], tuple(size), threads=threads)
     return bool((O.unpack_rgb8(rect, 3, threads=threads) == pixels.reshape(-1, 3)).all())
+
+
+DUMP_SEED = 20240807
+DUMP_MAX_PIXELS = 1 << 21        # x 3 channels x 4 B: 24 MiB of float32
+
+
+def dump_outputs(wl, directory, rank, world):
+    """--dump-outputs: the pixels the last timed step wrote, every one of them when the step has at most DUMP_MAX_PIXELS,
+    otherwise those at DUMP_MAX_PIXELS flat indices drawn with DUMP_SEED, sorted and made unique (module docstring)."""
+    import numpy as np
+    import torch
+    flat = wl.last_output().reshape(-1, 3)
+    n = flat.shape[0]
+    if n <= DUMP_MAX_PIXELS:
+        idx = np.arange(n)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_PIXELS))
+    sample = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).float().cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rgb8_sample.npy" if world == 1 else f"rgb8_sample.rank{rank}.npy"), sample)
 
 
 def cpu_baseline(J, quanta_np, seconds, device_case=None, encode_case=None):
@@ -422,6 +474,8 @@ def run(args, make_workload=None, backend="nccl", device_kind="cuda"):
         wl.step()
     wall, gpu_ms = time_region(wl, wl.step, args.steps, sync, barrier)
     wall_max = jd.max_over_ranks(wall, dev, dist)
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank, world)
 
     # per-rank record (device, images, times, and the proof of what was timed), gathered on every rank; rank 0 reports it
     mine = {"rank": rank, "device": wl.device_name(), "images_per_step": wl.n_images,
@@ -557,8 +611,9 @@ def run(args, make_workload=None, backend="nccl", device_kind="cuda"):
         }
 
     if rank == 0:
-        result["scaling_curve"] = ("`value` is workload " + workload + " at every N (" + scaling + " scaling); the sharded C5 job is "
-                                   "extra.c5_%dx1080p.Mpixels_per_s at every N (strong scaling)" % args.c5_images)
+        result["scaling_curve"] = "`value` is workload " + workload + " at every N (" + scaling + " scaling)"
+        if c5_job is not None:
+            result["scaling_curve"] += "; the sharded C5 job is extra.c5_%dx1080p.Mpixels_per_s at every N (strong scaling)" % args.c5_images
         checks = [r.get("parity_vs_oracle") for r in per_rank]
         result["parity_vs_oracle"] = None if any(c is None for c in checks) else bool(all(checks))
         if c5_job is not None:

@@ -60,7 +60,7 @@ def main():
     import bench
     from jpeg_amd import dist as jd
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--c5-images", str(n), "--c5-steps", "2",
-                "--no-extras", "--no-cpu"]
+                "--full", "--no-extras", "--no-cpu"]
     args = bench.parse()
     made = {}
 

@@ -1,7 +1,7 @@
 """Worker of tests/test_gpu_rccl_world1.py: a fresh process that initialises torch.distributed with the "nccl" backend
 (= RCCL on ROCm) as a world of ONE on cuda:0 -- TCP store on 127.0.0.1, before any other GPU work -- and drives the
 multi-GPU plumbing through that group: jpeg_amd.dist.broadcast_quanta (the int32-view broadcast of the uint16 tables),
-max_over_ranks (all_reduce MAX), then bench.run() itself with --gpus 1 --dist (barriers, the table broadcast, the C5 job's
+max_over_ranks (all_reduce MAX), then bench.run() itself with --gpus 1 --dist --full (barriers, the table broadcast, the C5 job's
 all_gather_object).  It proves that the backend loads and that the collectives of the path run on this box; it is NOT a
 scaling result.
 usage: python _rccl_worker.py <port> <out.json>"""
@@ -38,7 +38,7 @@ def main():
 
     import bench
     sys.argv = ["bench.py", "--gpus", "1", "--dist", "--steps", "3", "--warmup", "1", "--c5-images", "6", "--c5-steps", "1",
-                "--no-extras", "--no-cpu", "--traffic", "none"]
+                "--full", "--no-extras", "--no-cpu", "--traffic", "none"]
     rec["result"] = bench.run(bench.parse())
     json.dump(rec, open(out, "w"))
 

@@ -3,6 +3,7 @@ GPU sanitizers are not available on the pool): every fixture decoded (1 and 4 th
 again as sequential and as progressive scans, decoded again; then 200 corrupted variants each."""
 import glob
 import os
+import platform
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,5 +30,8 @@ def test_worker_pool_is_clean_under_tsan(tmp_path):
     exe = str(tmp_path / "worker_pool_test")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "jpeg_amd", "csrc"),
                            os.path.join(ROOT, "tests", "cpp", "worker_pool_test.cpp"), "-o", exe, "-lpthread"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    # GCC's ThreadSanitizer expects the executable and its libraries in fixed address windows; a kernel that randomises
+    # mmap with 32 bits (vm.mmap_rnd_bits = 32) can place them outside, and TSan stops before main with "unexpected memory
+    # mapping".  The child runs without address-space randomisation (setarch -R: a personality flag of that process only).
+    r = subprocess.run(["setarch", platform.machine(), "-R", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])

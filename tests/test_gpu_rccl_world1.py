@@ -1,6 +1,6 @@
 """RCCL once: the "nccl" backend of torch.distributed -- RCCL on ROCm -- initialised as a world of one
 on the GPU box, in a fresh child process (a child is started, nothing is re-executed), and the path's collectives driven
-through it: the table broadcast, the max over ranks, bench.run() with --gpus 1 --dist.  Not a scaling result: it shows that
+through it: the table broadcast, the max over ranks, bench.run() with --gpus 1 --dist --full.  Not a scaling result: it shows that
 the int32-view broadcast and the backend work on this box, which no round had executed before."""
 import json
 import os

@@ -38,7 +38,7 @@ c3["c5"] = dict(t["configs"]["c5"], images=4096)     # bench.py --workload c5 sc
 json.dump(c3, open("profiles/traffic_latest.json", "w"), indent=1)
 PY
 for c in c3 c5 c2 c4; do cp $O/$c/kernel_stats.csv profiles/${tag}_${c}_kernel_stats.csv; cp $O/$c/pmc_fetch_size.csv profiles/${tag}_${c}_pmc_fetch_size.csv; cp $O/$c/pmc_write_size.csv profiles/${tag}_${c}_pmc_write_size.csv; done
-python3 bench.py > $O/bench.json 2> $O/bench.log
+python3 bench.py --full > $O/bench.json 2> $O/bench.log
 cp $O/bench.json profiles/${tag}_bench.json
 python3 - <<PY
 # the record has to agree with itself: the profiler's mean duration of the headline kernel against the wall time per step of the bench line

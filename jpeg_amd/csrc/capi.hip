@@ -11,10 +11,7 @@
 #include <new>
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
-#include <functional>
 #include <memory>
-#include <mutex>
 #include <chrono>
 #include <system_error>
 #include <thread>
@@ -36,13 +33,14 @@ struct jpeg_amd_ctx {
     uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
     int qslot = 0;
     int last_hip = 0;
-    // staging of jpeg_amd_decompress_batch, kept between calls: two pinned host slots (the host
-    // threads fill one while the device works from the other) and one device slot
+    // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
+    // host slots (the host threads work in one while the device works from / into the other) and two device slots
     void *file_pinned[2] = {nullptr, nullptr};
-    void *file_device = nullptr;
+    void *file_device = nullptr;                      // both device slots
     size_t file_pinned_bytes = 0, file_device_bytes = 0;
-    hipEvent_t file_done[2] = {nullptr, nullptr};     // chunk's pixels are back in pinned memory
+    hipEvent_t file_done[2] = {nullptr, nullptr};     // chunk's pixels (decode) / first stage of its download (encode) are back
     hipEvent_t file_decoded[2] = {nullptr, nullptr};  // chunk's kernels are done (device -> host copy may start)
+    hipEvent_t file_fetched[2] = {nullptr, nullptr};  // encode: the second stage of the chunk's download is back
     hipStream_t file_d2h = nullptr;                   // downloads overlap the next chunk's uploads (full-duplex PCIe)
     std::unique_ptr<WorkerPool> workers, copiers;     // host threads of the batch file paths: entropy coding; copies out of the pinned slots
     std::vector<std::vector<uint32_t>> records;       // a sparse record per entropy-decoding thread
@@ -158,6 +156,77 @@ int stage_quanta(jpeg_amd_ctx *ctx, const uint16_t *h_quanta, int ntables, const
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// The planes of the staged paths in the context's scratch: n_images images of every plane, `sample_bytes` per sample.
+int scratch_planes(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, size_t sample_bytes, PlaneSetMut *ps)
+{
+    size_t offset[JPEG_AMD_MAX_PLANES], total = 0;
+    for (int p = 0; p < L->nplanes; ++p) {
+        offset[p] = total;
+        total += align256(plane_samples(L, p) * (size_t)n_images * sample_bytes);
+    }
+    JA_TRY(ensure_scratch(ctx, total));
+    *ps = PlaneSetMut{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        ps->ptr[p] = static_cast<uint8_t *>(ctx->scratch) + offset[p];
+        ps->stride[p] = plane_samples(L, p);
+    }
+    return JPEG_AMD_OK;
+}
+
+// A decoded frame's layout: its first `nplanes` components, table c for component c.
+jpeg_amd_layout layout_of_info(const jpeg_amd_frame_info &fi, int nplanes)
+{
+    jpeg_amd_layout L{};
+    L.width = fi.width; L.height = fi.height; L.precision = fi.precision; L.nplanes = nplanes;
+    L.scale_x = fi.scale_x; L.scale_y = fi.scale_y;          // the scale of ALL components (decode.swift:2181-2190)
+    for (int c = 0; c < nplanes; ++c) {
+        L.factor_x[c] = fi.factor_x[c]; L.factor_y[c] = fi.factor_y[c];
+        L.units_x[c] = fi.units_x[c];   L.units_y[c] = fi.units_y[c];
+        L.qi[c] = c;
+    }
+    return L;
+}
+
+// The layout of a frame to be encoded: scale and units from its factors (both written back into the frame), each
+// component's table found by its key.  Precision and component count are the caller's to check.
+int layout_of_frame(jpeg_amd_frame_info *frame, const int32_t *quanta_key, const int32_t *h_quanta_keys, int ntables,
+                    jpeg_amd_layout *L)
+{
+    if (frame->width < 1 || frame->height < 1 || ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
+    const int nc = frame->ncomponents;
+    *L = jpeg_amd_layout{};
+    L->width = frame->width; L->height = frame->height; L->precision = frame->precision; L->nplanes = nc;
+    L->scale_x = L->scale_y = 1;
+    for (int c = 0; c < nc; ++c) {
+        if (frame->factor_x[c] < 1 || frame->factor_y[c] < 1) return JPEG_AMD_EINVAL;
+        L->factor_x[c] = frame->factor_x[c]; L->factor_y[c] = frame->factor_y[c];
+        L->scale_x = std::max(L->scale_x, L->factor_x[c]); L->scale_y = std::max(L->scale_y, L->factor_y[c]);
+        L->qi[c] = -1;
+        for (int t = 0; t < ntables; ++t) if (h_quanta_keys[t] == quanta_key[c]) L->qi[c] = t;
+        if (L->qi[c] < 0) return JPEG_AMD_EINVAL;   // missing quantization table (decode.swift:2527)
+    }
+    JA_TRY(jpeg_amd_layout_units(L));
+    frame->scale_x = L->scale_x; frame->scale_y = L->scale_y;
+    for (int c = 0; c < nc; ++c) { frame->units_x[c] = L->units_x[c]; frame->units_y[c] = L->units_y[c]; }
+    return JPEG_AMD_OK;
+}
+
+// The sparse form of a frame's coefficients in the batch paths (jpeg_amd_jpeg_decode_sparse, k_sparsify): per image a
+// descriptor per block and an arena of 24 entries per block (3/4 of the planes' bytes at most; only what is used travels).
+// Descriptors are 32-bit indices into the arena: a frame whose record would not be addressable that way (25 * blocks >= 2^32:
+// beyond 60 000 x 60 000 4:4:4) travels as planes (ok = false).
+struct SparseBudget {
+    size_t blocks, arena, elems;   // elems: uint32 per image, [descriptors][entries]
+    bool ok;
+};
+SparseBudget sparse_budget(const jpeg_amd_layout &L)
+{
+    size_t blocks = 0;
+    for (int c = 0; c < L.nplanes; ++c) blocks += (size_t)L.units_x[c] * L.units_y[c];
+    const size_t arena = 24 * blocks;
+    return {blocks, arena, blocks + arena, blocks + arena < 0xffffffffull};
+}
+
 // The staging the two batch entry points for files share, kept in the context between calls: two pinned host slots (the host
 // threads work in one while the device works from / into the other), two device slots, two events per slot and a second
 // stream so that uploads and downloads overlap (full-duplex PCIe).
@@ -171,6 +240,7 @@ int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes)
             JA_HIP(ctx, hipHostMalloc(&ctx->file_pinned[i], slot_bytes, hipHostMallocDefault));
             if (!ctx->file_done[i]) JA_HIP(ctx, hipEventCreateWithFlags(&ctx->file_done[i], hipEventDisableTiming));
             if (!ctx->file_decoded[i]) JA_HIP(ctx, hipEventCreateWithFlags(&ctx->file_decoded[i], hipEventDisableTiming));
+            if (!ctx->file_fetched[i]) JA_HIP(ctx, hipEventCreateWithFlags(&ctx->file_fetched[i], hipEventDisableTiming));
         }
         ctx->file_pinned_bytes = slot_bytes;
     }
@@ -321,6 +391,7 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
         if (ctx->file_pinned[i]) (void)hipHostFree(ctx->file_pinned[i]);
         if (ctx->file_done[i]) (void)hipEventDestroy(ctx->file_done[i]);
         if (ctx->file_decoded[i]) (void)hipEventDestroy(ctx->file_decoded[i]);
+        if (ctx->file_fetched[i]) (void)hipEventDestroy(ctx->file_fetched[i]);
     }
     if (ctx->file_d2h) (void)hipStreamDestroy(ctx->file_d2h);
     if (ctx->file_device) (void)hipFree(ctx->file_device);
@@ -515,21 +586,16 @@ int jpeg_amd_decode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
     }
 
     // general path: IDCT every plane into uint8 scratch planes, then upsample + colour.
-    size_t offset[JPEG_AMD_MAX_PLANES], total = 0;
-    for (int p = 0; p < L->nplanes; ++p) {
-        offset[p] = total;
-        total += align256(plane_samples(L, p) * (size_t)n_images);
-    }
-    JA_TRY(ensure_scratch(ctx, total));
+    PlaneSetMut scratch;
+    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint8_t), &scratch));
     PlaneSet ps{};
     for (int p = 0; p < L->nplanes; ++p) {
-        uint8_t *dst = static_cast<uint8_t *>(ctx->scratch) + offset[p];
         JA_HIP(ctx, launch_idct_plane(ctx->stream, n_images, d_coef[p], coef_stride[p],
                                       QuantaRef{d_quanta, quanta_stride}, L->qi[p],
-                                      L->units_x[p], L->units_y[p], L->precision, dst,
-                                      plane_samples(L, p), true));
-        ps.ptr[p] = dst;
-        ps.stride[p] = plane_samples(L, p);
+                                      L->units_x[p], L->units_y[p], L->precision, scratch.ptr[p],
+                                      scratch.stride[p], true));
+        ps.ptr[p] = scratch.ptr[p];
+        ps.stride[p] = scratch.stride[p];
     }
     JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, n_images, *L, ps, true, cosited != 0,
                                         color == JPEG_AMD_COLOR_RGB8 ? PixelKind::RGB8 : PixelKind::YCC8,
@@ -589,19 +655,14 @@ int jpeg_amd_spectral_rectangular_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout
         return JPEG_AMD_OK;
     }
     // staged path (any factors): IDCT every plane into uint16 scratch planes, then upsample + interleave
-    size_t offset[JPEG_AMD_MAX_PLANES], total = 0;
-    for (int p = 0; p < L->nplanes; ++p) {
-        offset[p] = total;
-        total += align256(plane_samples(L, p) * (size_t)n_images * sizeof(uint16_t));
-    }
-    JA_TRY(ensure_scratch(ctx, total));
+    PlaneSetMut scratch;
+    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &scratch));
     PlaneSet ps{};
     for (int p = 0; p < L->nplanes; ++p) {
-        uint8_t *dst = static_cast<uint8_t *>(ctx->scratch) + offset[p];
         JA_HIP(ctx, launch_idct_plane(ctx->stream, n_images, d_coef[p], coef_stride[p], QuantaRef{d_quanta, quanta_stride},
-                                      L->qi[p], L->units_x[p], L->units_y[p], L->precision, dst, plane_samples(L, p), false));
-        ps.ptr[p] = dst;
-        ps.stride[p] = plane_samples(L, p);
+                                      L->qi[p], L->units_x[p], L->units_y[p], L->precision, scratch.ptr[p], scratch.stride[p], false));
+        ps.ptr[p] = scratch.ptr[p];
+        ps.stride[p] = scratch.stride[p];
     }
     JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, n_images, *L, ps, false, cosited != 0, PixelKind::Rect16, d_rect,
                                         rect_stride * sizeof(uint16_t)));
@@ -695,12 +756,8 @@ int jpeg_amd_encode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
 
-    size_t offset[JPEG_AMD_MAX_PLANES], total = 0;
-    for (int p = 0; p < L->nplanes; ++p) {
+    for (int p = 0; p < L->nplanes; ++p)
         if (plane_samples(L, p) && !d_coef[p]) return JPEG_AMD_EINVAL;
-        offset[p] = total;
-        total += align256(plane_samples(L, p) * (size_t)n_images * sizeof(uint16_t));
-    }
     if (fused_encode_supported(*L)) {
         PlaneSetMut cs{};
         for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
@@ -708,12 +765,8 @@ int jpeg_amd_encode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
                                         color == JPEG_AMD_COLOR_RGB8, QuantaRef{d_quanta, quanta_stride}, cs));
         return JPEG_AMD_OK;
     }
-    JA_TRY(ensure_scratch(ctx, total));
-    PlaneSetMut ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        ps.ptr[p] = static_cast<uint8_t *>(ctx->scratch) + offset[p];
-        ps.stride[p] = plane_samples(L, p);
-    }
+    PlaneSetMut ps;
+    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &ps));
     JA_HIP(ctx, launch_decompose(ctx->stream, n_images, *L, d_pixels, pixel_stride,
                                  color == JPEG_AMD_COLOR_RGB8 ? PixelKind::RGB8 : PixelKind::YCC8, ps));
     for (int p = 0; p < L->nplanes; ++p) {
@@ -745,17 +798,8 @@ int jpeg_amd_rectangular_spectral_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout
         return JPEG_AMD_OK;
     }
     // staged path (any factors): decomposed() into uint16 scratch planes, then fdct(quanta:) plane by plane
-    size_t offset[JPEG_AMD_MAX_PLANES], total = 0;
-    for (int p = 0; p < L->nplanes; ++p) {
-        offset[p] = total;
-        total += align256(plane_samples(L, p) * (size_t)n_images * sizeof(uint16_t));
-    }
-    JA_TRY(ensure_scratch(ctx, total));
-    PlaneSetMut ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        ps.ptr[p] = static_cast<uint8_t *>(ctx->scratch) + offset[p];
-        ps.stride[p] = plane_samples(L, p);
-    }
+    PlaneSetMut ps;
+    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &ps));
     JA_HIP(ctx, launch_decompose(ctx->stream, n_images, *L, d_rect, rect_stride * sizeof(uint16_t), PixelKind::Rect16, ps));
     for (int p = 0; p < L->nplanes; ++p) {
         if (plane_samples(L, p) == 0) continue;
@@ -1081,14 +1125,7 @@ try {
     uint16_t quanta[JPEG_AMD_MAX_PLANES][64];
     JA_TRY(jpeg_amd_jpeg_decode_spectral_mt(h_jpeg, nbytes, coef, quanta, &fi, nthreads));
     if (info_out) *info_out = fi;
-    jpeg_amd_layout L{};
-    L.width = fi.width; L.height = fi.height; L.precision = fi.precision; L.nplanes = np;
-    L.scale_x = fi.scale_x; L.scale_y = fi.scale_y;          // the scale of ALL components (decode.swift:2181-2190)
-    for (int c = 0; c < np; ++c) {
-        L.factor_x[c] = fi.factor_x[c]; L.factor_y[c] = fi.factor_y[c];
-        L.units_x[c] = fi.units_x[c];   L.units_y[c] = fi.units_y[c];
-        L.qi[c] = c;
-    }
+    const jpeg_amd_layout L = layout_of_info(fi, np);
     return jpeg_amd_host_spectral_rectangular(ctx, &L, coef, &quanta[0][0], np, cosited, h_rect);
 }
 JA_NOTHROW_TAIL
@@ -1117,33 +1154,21 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
     if (pixel_stride == 0) pixel_stride = npx;
     if (pixel_stride < npx) return JPEG_AMD_EINVAL;
 
-    jpeg_amd_layout L{};
-    L.width = fi.width; L.height = fi.height; L.precision = 8; L.nplanes = nc;
-    L.scale_x = fi.scale_x; L.scale_y = fi.scale_y;
+    const jpeg_amd_layout L = layout_of_info(fi, nc);
     size_t plane[JPEG_AMD_MAX_PLANES] = {};
-    size_t coef_off[JPEG_AMD_MAX_PLANES] = {};
+    for (int c = 0; c < nc; ++c) plane[c] = plane_samples(&L, c);
     const int chunk = std::min(n_images, 32);
-    size_t blocks = 0;
-    for (int c = 0; c < nc; ++c) {
-        L.factor_x[c] = fi.factor_x[c]; L.factor_y[c] = fi.factor_y[c];
-        L.units_x[c] = fi.units_x[c];   L.units_y[c] = fi.units_y[c];
-        L.qi[c] = c;
-        plane[c] = (size_t)64 * fi.units_x[c] * fi.units_y[c];
-        blocks += (size_t)fi.units_x[c] * fi.units_y[c];
-    }
     // Sequential files travel as SPARSE coefficients (jpeg_amd_jpeg_decode_sparse: a descriptor per block + an entry per
     // nonzero coefficient, an eighth of the planes for a typical file) and are expanded on the device; an image that does not
-    // fit its arena, a progressive or a damaged one is decoded into planes as before and uploaded whole.
-    // Arena: 24 entries per block (3/4 of the planes' bytes at most; only what is used is uploaded).
-    const size_t arena = 24 * blocks, sparse_elems = blocks + arena;           // uint32 per image: [descriptors][entries]
-    // descriptors are 32-bit indices into the arena: a frame whose arena would not be addressable that way (24 * blocks + blocks
-    // >= 2^32: beyond 60 000 x 60 000 4:4:4) is decoded into planes
-    const bool sparse_ok = sparse_elems < 0xffffffffull;
+    // fit its arena, a progressive or a damaged one is decoded into planes and uploaded whole, like every image of a frame too
+    // large for 32-bit descriptors (sparse_budget).
+    const SparseBudget sb = sparse_budget(L);
+    const size_t blocks = sb.blocks, arena = sb.arena, sparse_elems = sb.elems;
     // slot layout: [coef plane 0 x chunk][plane 1 x chunk][plane 2 x chunk] [quanta x chunk][skip flags][record offsets][records ...] [pixels x chunk]
     // The middle part goes up in ONE copy per chunk: the tables, the per-image flags, where each image's sparse record
     // [descriptors][entries in use] begins, and the records themselves, packed one behind the other in the order the threads
     // finish (a copy per image is 32 more commands per chunk, and every ~2 000 commands the runtime stops for 30 ms).
-    size_t off = 0;
+    size_t coef_off[JPEG_AMD_MAX_PLANES] = {}, off = 0;
     for (int c = 0; c < nc; ++c) { coef_off[c] = off; off += align256(plane[c] * 2 * chunk); }
     const size_t quanta_off = off;  off += align256((size_t)chunk * kQSlotElems * 2);
     const size_t skip_off = off;    off += align256((size_t)chunk);
@@ -1195,25 +1220,11 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
         return JPEG_AMD_OK;
     };
     struct DrainGuard { decltype(end_drain) &f; ~DrainGuard() { (void)f(); } } drain_guard{end_drain};   // joined on every way out
-    std::vector<int> status_all((size_t)n_images, JPEG_AMD_OK);
-    // The entropy decoding: ONE queue of files for the whole call.  A host thread takes the next file, waits (rarely) until the
-    // pinned slot of the file's chunk is free, and decodes it there; this thread submits a chunk to the device as soon as its
-    // last file is in.  No barrier between chunks on the host threads' side: a thread that is done with its file of chunk k
-    // goes on with chunk k + 1 while a slower one still works on chunk k.
-    // Pinned slot k & 1 is free for chunk k once the kernels of chunk k - 2 are done (its uploads read the slot's coefficient,
-    // sparse and table regions; file_decoded[slot] is recorded behind them).  The helper thread that copies chunk k - 2's
-    // pixels out of the same slot may still be running; it only reads the pixel region, which the decoders do not touch.
-    struct Queue {
-        std::mutex m;
-        std::condition_variable cv;
-        int open_chunks;            // chunks [0, open_chunks) may be decoded
-        std::vector<int> left;      // files of chunk k not decoded yet
-        bool abort = false;
-    } queue;
-    queue.open_chunks = std::min(2, nchunks);
-    queue.left.resize((size_t)nchunks);
-    for (int k = 0; k < nchunks; ++k) queue.left[(size_t)k] = std::min(chunk, n_images - k * chunk);
-    std::atomic<int> next_file{0};
+    // The entropy decoding: ONE queue of files for the whole call (FileQueue), decoded on t_n host threads beside this one, which
+    // directs; this thread submits a chunk to the device as soon as its last file is in.  Chunk j is decoded into pinned slot
+    // j & 1, which is free once the kernels of chunk j - 2 are done (its uploads read the slot's coefficient, sparse and table
+    // regions; file_decoded[slot] is recorded behind them).  The helper thread that copies chunk j - 2's pixels out of the same
+    // slot may still be running; it only reads the pixel region, which the decoders do not touch.
     std::atomic<size_t> packed_end[2];                       // per slot: elements of the records packed so far
     packed_end[0].store(0); packed_end[1].store(0);
     auto decode_file = [&](int file, std::vector<uint32_t> &record) -> int {
@@ -1240,7 +1251,7 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
         // descriptor array holds and never writes past the arena, so a file of another geometry is caught afterwards.
         // (spare threads only help a file that has restart intervals; such a file is decoded into planes on `inner` threads)
         bool sparse_done = false;
-        if ((inner == 1 || fi.restart_interval == 0) && sparse_ok) {
+        if ((inner == 1 || fi.restart_interval == 0) && sb.ok) {
             if (record.size() < sparse_elems) record.resize(sparse_elems);      // (this thread's; kept in the context between calls, trimmed on the way out when huge)
             size_t n = 0;
             const int ss = jpeg_amd_jpeg_decode_sparse(h_jpeg[file], nbytes[file], record.data(), blocks, record.data() + blocks, arena, &n, quanta, &f);
@@ -1265,79 +1276,27 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
             st = jpeg_amd_jpeg_decode_spectral_mt(h_jpeg[file], nbytes[file], planes, quanta, nullptr, inner > 1 && auto_threads ? 0 : inner);
         return st;
     };
-    auto worker = [&](std::vector<uint32_t> &record) {
-        for (;;) {
-            const int file = next_file.fetch_add(1);
-            if (file >= n_images) return;
-            const int k = file / chunk;
-            {
-                std::unique_lock<std::mutex> g(queue.m);
-                queue.cv.wait(g, [&] { return queue.abort || queue.open_chunks > k; });
-                if (queue.abort) return;
-            }
-            int st;
-            try { st = decode_file(file, record); } catch (...) { st = JPEG_AMD_ENOMEM; }
-            status_all[(size_t)file] = st;
-            std::lock_guard<std::mutex> g(queue.m);
-            if (--queue.left[(size_t)k] == 0) queue.cv.notify_all();
-        }
-    };
     const int t_n = std::min(nthreads, n_images);
-    WorkerPool &pool = pool_with(ctx->workers, t_n + 1);     // t_n threads beside this one, which only directs
-    if (ctx->records.size() < (size_t)t_n) ctx->records.resize((size_t)t_n);
-    struct Stop {             // on every way out: tell the threads to stop, wait for them
-        Queue &q; WorkerPool &p;
-        ~Stop() { { std::lock_guard<std::mutex> g(q.m); q.abort = true; } q.cv.notify_all(); p.finish(); }
-    } stop{queue, pool};
-    // Not one helper thread to be had (thread creation failed when the pool was made): no parallel region; this thread decodes
-    // every chunk itself, in front of the chunk's submission -- synchronous, slower, but any number of chunks goes through.
-    const bool inline_decode = pool.size() < 2;
-    if (inline_decode && ctx->records.empty()) ctx->records.resize(1);
-    if (!inline_decode) pool.begin(t_n, [&](int index) { worker(ctx->records[(size_t)index]); }, t_n + 1);
-    // The threads' sparse records stay in the context between calls (a batch of 1080p files: 5 MB per thread); a call on huge
-    // frames leaves several hundred MB per thread behind, which is given back on the way out.
-    struct Trim {
-        std::vector<std::vector<uint32_t>> &r;
-        ~Trim() { for (auto &v : r) if (v.capacity() > ((size_t)16 << 20)) std::vector<uint32_t>().swap(v); }
-    } trim{ctx->records};
+    // (the threads' sparse records stay in the context between calls -- a batch of 1080p files: 5 MB per thread -- unless huge)
+    FileQueue queue(pool_with(ctx->workers, t_n + 1), ctx->records, n_images, chunk, t_n, [&](int file, std::vector<uint32_t> &record) {
+        try { return decode_file(file, record); } catch (...) { return (int)JPEG_AMD_ENOMEM; }
+    }, (size_t)16 << 20);
     for (int k = 0; k < nchunks && result == JPEG_AMD_OK; ++k) {
         const int slot = k & 1, base = k * chunk, m = std::min(chunk, n_images - base);
         char *host = static_cast<char *>(ctx->file_pinned[slot]);
         const uint8_t *skip = reinterpret_cast<const uint8_t *>(host + skip_off);
-        if (inline_decode) {
-            // pinned slot `slot` is free once the uploads of chunk k - 2 have read it
-            if (k >= 2) {
-                const hipError_t w = wait_event(ctx->file_decoded[slot]);
-                if (w != hipSuccess) { ctx->last_hip = (int)w; result = JPEG_AMD_EHIP; break; }
-                packed_end[slot].store(0);
-            }
-            for (int i = 0; i < m; ++i) {
-                int st;
-                try { st = decode_file(base + i, ctx->records[0]); } catch (...) { st = JPEG_AMD_ENOMEM; }
-                status_all[(size_t)(base + i)] = st;
-            }
-            std::lock_guard<std::mutex> g(queue.m);
-            queue.left[(size_t)k] = 0;
-        } else {
         // (like every failure inside this loop it leaves through the common tail below, which waits for both streams)
-        // While the threads are in chunk k: chunk k + 1 goes into the pinned slot of chunk k - 1, which is free when that chunk's
-        // kernels are done (submitted at the end of the last iteration) -- wait for them here, where this thread has nothing
-        // else to do, and open the chunk: a thread that is through with chunk k goes straight on.
-        if (k >= 1 && k + 1 < nchunks) {
-            const hipError_t w = wait_event(ctx->file_decoded[(k - 1) & 1]);
+        // With threads, chunk k + 1 is opened while they are in chunk k: a thread that is through with chunk k goes straight on,
+        // and this thread waits for chunk k - 1's kernels here, where it has nothing else to do.  Without, this thread decodes
+        // chunk k itself (in wait(k)), in front of the chunk's submission.
+        const int j = queue.threaded() ? k + 1 : k;
+        if (j >= 2 && j < nchunks) {
+            const hipError_t w = wait_event(ctx->file_decoded[j & 1]);
             if (w != hipSuccess) { ctx->last_hip = (int)w; result = JPEG_AMD_EHIP; break; }
+            packed_end[j & 1].store(0);                       // (chunks 0 and 1 start from the initial zeros)
         }
-        if (k + 1 < nchunks) {
-            if (k >= 1) packed_end[(k + 1) & 1].store(0);     // (chunks 0 and 1 start from the initial zeros)
-            { std::lock_guard<std::mutex> g(queue.m); queue.open_chunks = std::max(queue.open_chunks, k + 2); }
-            queue.cv.notify_all();
-        }
-        {
-            std::unique_lock<std::mutex> g(queue.m);
-            queue.cv.wait(g, [&] { return queue.left[(size_t)k] == 0; });          // chunk k is decoded
-        }
-        }   // (!inline_decode)
-        for (int i = 0; i < m; ++i) if (status_all[(size_t)(base + i)] != JPEG_AMD_OK) result = status_all[(size_t)(base + i)];
+        queue.open(std::min(j + 1, nchunks));
+        result = queue.wait(k);
         { const int ds = end_drain(); if (ds != JPEG_AMD_OK) result = ds; }   // chunk k - 1 is out of its pinned slot: chunk k + 1's download may land there
         // (downloads that go straight into the caller's buffer are not waited for by a copy out: the device slot's pixels of
         // chunk k - 2 must have left before chunk k's kernels write there)
@@ -1354,8 +1313,6 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
             char *dev = static_cast<char *>(ctx->file_device) + (size_t)slot * slot_bytes;
             int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
             for (int c = 0; c < nc; ++c) d_coef[c] = reinterpret_cast<int16_t *>(dev + coef_off[c]);
-            size_t stride[JPEG_AMD_MAX_PLANES] = {};
-            for (int c = 0; c < nc; ++c) stride[c] = plane[c];
             bool any_sparse = false;
             for (int i = 0; i < m; ++i) {
                 any_sparse = any_sparse || !skip[i];
@@ -1368,12 +1325,12 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
             JA_HIP(ctx, hipMemcpyAsync(dev + quanta_off, host + quanta_off, sparse_off - quanta_off + packed_end[slot].load() * 4, hipMemcpyHostToDevice, ctx->stream));
             if (any_sparse) {
                 PlaneSetMut cs{};
-                for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = stride[c]; }
+                for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = plane[c]; }
                 JA_HIP(ctx, launch_expand_sparse(ctx->stream, m, L, reinterpret_cast<const uint32_t *>(dev + sparse_off), 0, nullptr, 0,
                                                  reinterpret_cast<const uint8_t *>(dev + skip_off), cs, reinterpret_cast<const uint64_t *>(dev + where_off)));
             }
             uint8_t *d_px = to_host ? reinterpret_cast<uint8_t *>(dev + px_off) : d_pixels_out + (size_t)base * pixel_stride;
-            JA_TRY(jpeg_amd_decode_batch(ctx, &L, m, d_coef, stride, reinterpret_cast<const uint16_t *>(dev + quanta_off), kQSlotElems,
+            JA_TRY(jpeg_amd_decode_batch(ctx, &L, m, d_coef, plane, reinterpret_cast<const uint16_t *>(dev + quanta_off), kQSlotElems,
                                          JPEG_AMD_MAX_PLANES, cosited, color, d_px, to_host ? npx : pixel_stride));
             JA_HIP(ctx, hipEventRecord(ctx->file_decoded[slot], ctx->stream));
             if (!to_host) {                                  // the pixels stay where they are: done when the kernels are
@@ -1435,26 +1392,12 @@ try {
     const int nc = frame->ncomponents;
     // JPEG.Common: 8-bit, arity 1 or 3 (jpeg.swift:357-424)
     if (frame->precision != 8 || (nc != 1 && nc != 3)) return JPEG_AMD_ENOSUP;
-    if (frame->width < 1 || frame->height < 1 || ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
-
-    jpeg_amd_layout L{};
-    L.width = frame->width; L.height = frame->height; L.precision = 8; L.nplanes = nc;
-    L.scale_x = L.scale_y = 1;
-    for (int c = 0; c < nc; ++c) {
-        if (frame->factor_x[c] < 1 || frame->factor_y[c] < 1) return JPEG_AMD_EINVAL;
-        L.factor_x[c] = frame->factor_x[c]; L.factor_y[c] = frame->factor_y[c];
-        L.scale_x = std::max(L.scale_x, L.factor_x[c]); L.scale_y = std::max(L.scale_y, L.factor_y[c]);
-        L.qi[c] = -1;
-        for (int t = 0; t < ntables; ++t) if (h_quanta_keys[t] == quanta_key[c]) L.qi[c] = t;
-        if (L.qi[c] < 0) return JPEG_AMD_EINVAL;   // missing quantization table (decode.swift:2527)
-    }
-    JA_TRY(jpeg_amd_layout_units(&L));
-    frame->scale_x = L.scale_x; frame->scale_y = L.scale_y;
+    jpeg_amd_layout L;
+    JA_TRY(layout_of_frame(frame, quanta_key, h_quanta_keys, ntables, &L));
     std::vector<std::vector<int16_t>> planes((size_t)nc);
     int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
     for (int c = 0; c < nc; ++c) {
-        frame->units_x[c] = L.units_x[c]; frame->units_y[c] = L.units_y[c];
-        planes[c].resize((size_t)64 * L.units_x[c] * L.units_y[c]);
+        planes[c].resize(plane_samples(&L, c));
         coef[c] = planes[c].data();
     }
     JA_TRY(jpeg_amd_host_encode(ctx, &L, h_pixels, color, h_quanta, ntables, coef));
@@ -1475,25 +1418,12 @@ try {
     if (!frame || !h_rect || !quanta_key || !h_quanta || !h_quanta_keys || !scans || !nbytes) return JPEG_AMD_EINVAL;
     const int nc = frame->ncomponents;
     if (nc < 1 || nc > JPEG_AMD_MAX_PLANES || frame->precision < 1 || frame->precision > 16) return JPEG_AMD_ENOSUP;
-    if (frame->width < 1 || frame->height < 1 || ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
-    jpeg_amd_layout L{};
-    L.width = frame->width; L.height = frame->height; L.precision = frame->precision; L.nplanes = nc;
-    L.scale_x = L.scale_y = 1;
-    for (int c = 0; c < nc; ++c) {
-        if (frame->factor_x[c] < 1 || frame->factor_y[c] < 1) return JPEG_AMD_EINVAL;
-        L.factor_x[c] = frame->factor_x[c]; L.factor_y[c] = frame->factor_y[c];
-        L.scale_x = std::max(L.scale_x, L.factor_x[c]); L.scale_y = std::max(L.scale_y, L.factor_y[c]);
-        L.qi[c] = -1;
-        for (int t = 0; t < ntables; ++t) if (h_quanta_keys[t] == quanta_key[c]) L.qi[c] = t;
-        if (L.qi[c] < 0) return JPEG_AMD_EINVAL;   // missing quantization table (decode.swift:2527)
-    }
-    JA_TRY(jpeg_amd_layout_units(&L));
-    frame->scale_x = L.scale_x; frame->scale_y = L.scale_y;
+    jpeg_amd_layout L;
+    JA_TRY(layout_of_frame(frame, quanta_key, h_quanta_keys, ntables, &L));
     std::vector<std::vector<int16_t>> planes((size_t)nc);
     int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
     for (int c = 0; c < nc; ++c) {
-        frame->units_x[c] = L.units_x[c]; frame->units_y[c] = L.units_y[c];
-        planes[c].resize((size_t)64 * L.units_x[c] * L.units_y[c]);
+        planes[c].resize(plane_samples(&L, c));
         coef[c] = planes[c].data();
     }
     JA_TRY(jpeg_amd_host_rectangular_spectral(ctx, &L, h_rect, h_quanta, ntables, coef));
@@ -1521,29 +1451,13 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
     if (n_images == 0) return JPEG_AMD_OK;
     const int nc = frame->ncomponents;
     if (frame->precision != 8 || (nc != 1 && nc != 3)) return JPEG_AMD_ENOSUP;
-    if (frame->width < 1 || frame->height < 1 || ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
     const size_t npx = (size_t)frame->width * frame->height * 3;
     if (pixel_stride == 0) pixel_stride = npx;
     if (pixel_stride < npx) return JPEG_AMD_EINVAL;
-
-    jpeg_amd_layout L{};
-    L.width = frame->width; L.height = frame->height; L.precision = 8; L.nplanes = nc;
-    L.scale_x = L.scale_y = 1;
-    for (int c = 0; c < nc; ++c) {
-        if (frame->factor_x[c] < 1 || frame->factor_y[c] < 1) return JPEG_AMD_EINVAL;
-        L.factor_x[c] = frame->factor_x[c]; L.factor_y[c] = frame->factor_y[c];
-        L.scale_x = std::max(L.scale_x, L.factor_x[c]); L.scale_y = std::max(L.scale_y, L.factor_y[c]);
-        L.qi[c] = -1;
-        for (int t = 0; t < ntables; ++t) if (h_quanta_keys[t] == quanta_key[c]) L.qi[c] = t;
-        if (L.qi[c] < 0) return JPEG_AMD_EINVAL;
-    }
-    JA_TRY(jpeg_amd_layout_units(&L));
-    frame->scale_x = L.scale_x; frame->scale_y = L.scale_y;
-    size_t plane[JPEG_AMD_MAX_PLANES] = {}, stride[JPEG_AMD_MAX_PLANES] = {};
-    for (int c = 0; c < nc; ++c) {
-        frame->units_x[c] = L.units_x[c]; frame->units_y[c] = L.units_y[c];
-        plane[c] = stride[c] = (size_t)64 * L.units_x[c] * L.units_y[c];
-    }
+    jpeg_amd_layout L;
+    JA_TRY(layout_of_frame(frame, quanta_key, h_quanta_keys, ntables, &L));
+    size_t plane[JPEG_AMD_MAX_PLANES] = {};
+    for (int c = 0; c < nc; ++c) plane[c] = plane_samples(&L, c);
     const int chunk = std::min(n_images, 32);
     if (nthreads <= 0) nthreads = default_host_threads();
     nthreads = std::max(1, nthreads);
@@ -1553,13 +1467,10 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
     // Sequential scans: the coefficients come down as SPARSE entries (k_sparsify: a descriptor per block + an entry per
     // nonzero coefficient, an eighth of the planes for a typical picture) and go to the writer in that form
     // (jpeg_amd_jpeg_encode_sparse); a picture whose entries do not fit its arena comes down as planes, like every picture of a
-    // progressive frame.  Arena: 24 entries per block.
-    size_t blocks = 0;
-    for (int c = 0; c < nc; ++c) blocks += (size_t)L.units_x[c] * L.units_y[c];
-    const size_t arena = 24 * blocks, sparse_elems = blocks + arena;           // uint32 per image: [descriptors][entries]
-    // descriptors are 32-bit indices into the arena: a frame whose arena would not be addressable that way (24 * blocks + blocks
-    // >= 2^32: beyond 60 000 x 60 000 4:4:4) comes down as planes
-    const bool sparse_down = frame->process != 2 && sparse_elems < 0xffffffffull;
+    // progressive frame, or of a frame too large for 32-bit descriptors (sparse_budget).
+    const SparseBudget sb = sparse_budget(L);
+    const size_t blocks = sb.blocks, arena = sb.arena, sparse_elems = sb.elems;
+    const bool sparse_down = frame->process != 2 && sb.ok;
     // slot layout (pinned and device alike): [pixels x chunk][coef plane 0 x chunk][plane 1 x chunk][plane 2 x chunk][sparse x chunk][counts]
     size_t coef_off[JPEG_AMD_MAX_PLANES] = {};
     size_t off = align256(npx * chunk);
@@ -1568,10 +1479,6 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
     const size_t count_off = off;   off += align256((size_t)chunk * 4);
     const size_t slot_bytes = off;
     JA_TRY(ensure_file_staging(ctx, slot_bytes));
-    // (a third event per slot, for this call: the second stage of a chunk's download is complete)
-    hipEvent_t fetched[2] = {nullptr, nullptr};
-    struct Events { hipEvent_t *e; ~Events() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } events{fetched};
-    for (int i = 0; i < 2; ++i) JA_HIP(ctx, hipEventCreateWithFlags(&fetched[i], hipEventDisableTiming));
 
     const int nchunks = (n_images + chunk - 1) / chunk;
     // a caller whose pixels are page-locked gets them uploaded from where they are: nothing to stage
@@ -1594,10 +1501,10 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
         else
             for (int i = 0; i < m; ++i)
                 JA_HIP(ctx, hipMemcpyAsync(dev + npx * i, h_pixels + ((size_t)k * chunk + i) * pixel_stride, npx, hipMemcpyHostToDevice, ctx->stream));
-        JA_TRY(jpeg_amd_encode_batch(ctx, &L, m, d_px, d_px_stride, color, d_q, 0, ntables, d_coef, stride));
+        JA_TRY(jpeg_amd_encode_batch(ctx, &L, m, d_px, d_px_stride, color, d_q, 0, ntables, d_coef, plane));
         if (sparse_down) {
             PlaneSet cs{};
-            for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = stride[c]; }
+            for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = plane[c]; }
             uint32_t *sp = reinterpret_cast<uint32_t *>(dev + sparse_off);
             JA_HIP(ctx, launch_sparsify(ctx->stream, m, L, cs, sp, sparse_elems, sp + blocks, sparse_elems, (uint32_t)arena,
                                         reinterpret_cast<uint32_t *>(dev + count_off)));
@@ -1632,7 +1539,7 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
                 }
             }
         }
-        JA_HIP(ctx, hipEventRecord(fetched[slot], ctx->file_d2h));
+        JA_HIP(ctx, hipEventRecord(ctx->file_fetched[slot], ctx->file_d2h));
         return JPEG_AMD_OK;
     };
     // One parallel region of the host threads: the files of chunk `code` are written from what came down into its pinned slot
@@ -1647,7 +1554,7 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
         char *stage_host = nullptr;
         if (code >= 0) {
             m_code = std::min(chunk, n_images - code * chunk);
-            JA_HIP(ctx, wait_event(fetched[code & 1]));
+            JA_HIP(ctx, wait_event(ctx->file_fetched[code & 1]));
             down = static_cast<const char *>(ctx->file_pinned[code & 1]);
         }
         if (stage < nchunks && !direct_in) {

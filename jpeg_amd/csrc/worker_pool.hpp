@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cstdint>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -94,6 +95,90 @@ private:
     bool open_ = false;
     unsigned long generation_ = 0;
     bool stop_ = false;
+};
+
+// The host-thread side of a batch decode (jpeg_amd_decompress_batch): `files` files in chunks of `chunk`, drawn from ONE
+// counter for the whole call by `threads` threads of the pool, each with its own record (records[index], kept by the caller
+// between calls).  No barrier between chunks: a thread that is done with its file of chunk k goes on with chunk k + 1 while a
+// slower one still works on chunk k -- but a file is not started before its chunk is opened.  The calling thread directs:
+// open(j) lets chunks [0, j) be decoded, wait(k) returns once chunk k is.  A pool without a helper thread decodes nothing by
+// itself: wait(k) decodes chunk k on the calling thread.  decode(file, record) returns 0 or an error status and does not throw.
+class FileQueue {
+public:
+    using Decode = std::function<int(int, std::vector<uint32_t> &)>;
+    FileQueue(WorkerPool &pool, std::vector<std::vector<uint32_t>> &records, int files, int chunk, int threads, Decode decode,
+              size_t trim_above)
+        : pool_(pool), records_(records), decode_(std::move(decode)), files_(files), chunk_(chunk), trim_above_(trim_above),
+          inline_(pool.size() < 2), status_((size_t)files, 0), left_((size_t)((files + chunk - 1) / chunk))
+    {
+        for (size_t k = 0; k < left_.size(); ++k) left_[k] = std::min(chunk, files - (int)k * chunk);
+        if (records_.size() < (size_t)std::max(1, threads)) records_.resize((size_t)std::max(1, threads));
+        if (!inline_) pool_.begin(threads, [this](int index) { work(records_[(size_t)index]); }, threads + 1);
+    }
+    // Every way out of a call comes through here, a failed chunk included, while threads may still be decoding later chunks into
+    // their records: they are stopped and joined BEFORE the records a call on huge frames left behind (hundreds of MB each) are
+    // trimmed -- never the other way round.
+    ~FileQueue()
+    {
+        { std::lock_guard<std::mutex> g(m_); abort_ = true; }
+        cv_.notify_all();
+        pool_.finish();
+        for (std::vector<uint32_t> &r : records_)
+            if (r.capacity() > trim_above_) std::vector<uint32_t>().swap(r);
+    }
+    bool threaded() const { return !inline_; }
+    void open(int chunks)
+    {
+        { std::lock_guard<std::mutex> g(m_); open_ = std::max(open_, chunks); }
+        cv_.notify_all();
+    }
+    // chunk k must have been opened; returns the status of its last failing file (0: every file decoded)
+    int wait(int k)
+    {
+        const int end = std::min(files_, (k + 1) * chunk_);
+        if (inline_)
+            while (next_.load() < end) run(next_.fetch_add(1), records_[0]);
+        std::unique_lock<std::mutex> g(m_);
+        cv_.wait(g, [&] { return left_[(size_t)k] == 0; });
+        int st = 0;
+        for (int file = k * chunk_; file < end; ++file)
+            if (status_[(size_t)file] != 0) st = status_[(size_t)file];
+        return st;
+    }
+
+private:
+    void run(int file, std::vector<uint32_t> &record)
+    {
+        status_[(size_t)file] = decode_(file, record);
+        std::lock_guard<std::mutex> g(m_);
+        if (--left_[(size_t)(file / chunk_)] == 0) cv_.notify_all();
+    }
+    void work(std::vector<uint32_t> &record)
+    {
+        for (;;) {
+            const int file = next_.fetch_add(1);
+            if (file >= files_) return;
+            {
+                std::unique_lock<std::mutex> g(m_);
+                cv_.wait(g, [&] { return abort_ || open_ > file / chunk_; });
+                if (abort_) return;
+            }
+            run(file, record);
+        }
+    }
+    WorkerPool &pool_;
+    std::vector<std::vector<uint32_t>> &records_;
+    const Decode decode_;
+    const int files_, chunk_;
+    const size_t trim_above_;
+    const bool inline_;
+    std::vector<int> status_;        // per file, read by wait() once the file's chunk is complete
+    std::mutex m_;
+    std::condition_variable cv_;
+    std::vector<int> left_;          // files of chunk k not decoded yet
+    std::atomic<int> next_{0};
+    int open_ = 0;
+    bool abort_ = false;
 };
 
 }  // namespace jpeg_amd

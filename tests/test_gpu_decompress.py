@@ -299,6 +299,32 @@ def test_a_bad_file_in_the_middle_of_a_batch_fails_the_call_and_leaves_the_conte
             assert G.sha(out[i * w * h * 3:(i + 1) * w * h * 3]) == G.entry(name)["gold"]["rgb_sha256"]
 
 
+@pytest.mark.timeout(120)
+def test_a_file_of_another_geometry_in_chunk_0_fails_the_call_and_the_context_decodes_the_next_batch(ctx):
+    """70 files = three chunks on 5 threads, the 4th of another geometry: the call fails in chunk 0 while the threads may already
+    be decoding chunk 1 (they are stopped and joined before the call returns its error), and the same context then decodes the
+    clean batch right."""
+    import jpeg_amd as J
+    lib = _lib.lib()
+    names = ["color-sequential-1.jpg", "color-progressive-1.jpg", "color-sequential-restart.jpg"]
+    names = [n for n in names if (G.entry(n)["width"], G.entry(n)["height"]) == (G.entry(names[0])["width"], G.entry(names[0])["height"])]
+    files = [np.fromfile(G.path(G.entry(n)["file"]), np.uint8) for n in names]
+    other = np.fromfile(G.path(G.entry("karlie-2019.jpg")["file"]), np.uint8)
+    n = 70
+    batch = [files[i % len(files)] for i in range(n)]
+    w, h = G.entry(names[0])["width"], G.entry(names[0])["height"]
+    out = np.zeros(n * w * h * 3, np.uint8)
+    def call(batch):
+        ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in batch])
+        sizes = (C.c_size_t * n)(*[f.size for f in batch])
+        return lib.jpeg_amd_decompress_batch(ctx.handle, ptrs, sizes, n, 5, 0, J.RGB.code, out.ctypes.data, 0, None)
+    assert call([other if i == 3 else f for i, f in enumerate(batch)]) == _lib.EINVAL
+    out[:] = 0
+    assert call(batch) == 0
+    for i in range(n):
+        assert G.sha(out[i * w * h * 3:(i + 1) * w * h * 3]) == G.entry(names[i % len(names)])["gold"]["rgb_sha256"], i
+
+
 def test_decompress_batch_without_a_single_helper_thread():
     """a process that cannot start one more thread (RLIMIT_NPROC reached) used to get ENOMEM for batches of more than
     two chunks; now the calling thread decodes every chunk itself in front of its submission.  In a fresh interpreter: context

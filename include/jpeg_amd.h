@@ -452,6 +452,84 @@ int jpeg_amd_compress_batch_device(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame
                             int nscans, const jpeg_amd_metadata *metadata, int nmetadata, int nthreads,
                             uint8_t *h_out, size_t out_stride, size_t nbytes[]);
 
+/* ---- lossless spectral transforms: rotate, flip, crop, requantise --------------------------------
+ * Editing JPEG.Data.Spectral directly, as examples/rotate/main.swift (lossless 90 / 180 / 270 degree rotations) and
+ * examples/recompress/main.swift:40-61 (new quantisation tables without going back to pixels) do.
+ *
+ * op: three bits applied in this order -- TRANSPOSE (across the main diagonal), then FLIP_H (mirror left-right), then
+ * FLIP_V (mirror top-bottom).  The 8 results are the dihedral group; the reference's rotations are
+ *   "ii"  = ROT_CCW = reflectVertical(transpose)    (90 degrees counter-clockwise, np.rot90(k=1))
+ *   "iii" = ROT_180 = reflectVertical(reflectHorizontal)
+ *   "iv"  = ROT_CW  = reflectHorizontal(transpose).
+ * Inside a block (the example's Block.transform): output zigzag index z takes sign(z) * in[m(z)]; a transpose swaps the
+ * frequencies (k, h), a horizontal mirror negates odd k, a vertical mirror negates odd h.  Tables: q_out[z] = q_in[m(z)].
+ * Block grid (the example's matrix / offset): block (x, y) of a plane goes to its transposed and / or mirrored position
+ * among that plane's units.
+ * Region (optional, source pixels, applied BEFORE the op): x, y multiples of 8 * scale_x, 8 * scale_y and inside the image,
+ * width, height > 0; it may reach past the image, and the blocks it adds are zero -- with x = y = 0 it is exactly
+ * Spectral.set(width:) / set(height:) (decode.swift:2443-2500).
+ * Trim (the example's rule): after the region, a partial-MCU edge the op would move to the top or left is cut to whole MCUs
+ * -- a mirrored source x (FLIP_H without TRANSPOSE, FLIP_V with it: ROT_CCW, ROT_180) trims the width, a mirrored source y
+ * (FLIP_V without TRANSPOSE, FLIP_H with it: ROT_CW, ROT_180) the height.  Partial edges that stay right / bottom are kept.
+ * Layout: a transposing op swaps factor_x / factor_y of every plane and scale_x / scale_y (4:2:2 becomes 4:4:0); units are
+ * recomputed as in jpeg_amd_layout_units.
+ * Requantisation (optional; new tables in OUTPUT orientation), examples/recompress/main.swift:52-56:
+ *   v = Int16(q_in[m(z)]) * sign(z) * in[m(z)];  r = Double(v) / Double(q_out[z]);  out = Int16(r + 0.3 * (r < 0 ? -1 : 1))
+ * (truncation toward zero).  Where the reference traps the call fails with EINVAL: q_in > 32767, an Int16 product that
+ * overflows (a negated -32768 included, which also holds without requantisation), q_out = 0.  Without requantisation the
+ * coefficients are copied exactly. */
+#define JPEG_AMD_XFORM_TRANSPOSE 1
+#define JPEG_AMD_XFORM_FLIP_H    2
+#define JPEG_AMD_XFORM_FLIP_V    4
+#define JPEG_AMD_XFORM_NONE       0
+#define JPEG_AMD_XFORM_ROT_CCW    (JPEG_AMD_XFORM_TRANSPOSE | JPEG_AMD_XFORM_FLIP_V)   /* "ii"  */
+#define JPEG_AMD_XFORM_ROT_180    (JPEG_AMD_XFORM_FLIP_H | JPEG_AMD_XFORM_FLIP_V)      /* "iii" */
+#define JPEG_AMD_XFORM_ROT_CW     (JPEG_AMD_XFORM_TRANSPOSE | JPEG_AMD_XFORM_FLIP_H)   /* "iv"  */
+#define JPEG_AMD_XFORM_TRANSVERSE 7
+
+typedef struct jpeg_amd_region {
+    int32_t x, y, width, height;              /* source pixels */
+} jpeg_amd_region;
+
+/* The output geometry of `op` and `region` (NULL = the whole image) applied to `in`; qi is carried over.  EINVAL for an
+ * unaligned or outside origin, a zero size, or a trim that leaves nothing.  Host only. */
+int jpeg_amd_transform_layout(const jpeg_amd_layout *in, int op, const jpeg_amd_region *region, jpeg_amd_layout *out);
+/* q_out[z] = q_in[m(z)].  Host only. */
+int jpeg_amd_transform_quanta(int op, const uint16_t in[64], uint16_t out[64]);
+/* One launch for every plane of n_images images of layout in_layout: image i of plane p reads d_coef_in[p] +
+ * i * in_stride[p] and writes d_coef_out[p] + i * out_stride[p] (int16 elements; the output planes are sized by
+ * jpeg_amd_transform_layout).  d_quanta: DEVICE tables [..][ntables][64], image i at i * quanta_stride; plane p uses
+ * table in_layout->qi[p].  d_quanta_out: NULL = no requantisation, else the new tables, output orientation, same layout
+ * and strides.  d_overflow (optional): a device int32 the kernel sets to 1 where the reference would trap (it is not
+ * cleared here).  Asynchronous on the ctx stream. */
+int jpeg_amd_spectral_transform_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *in_layout, int n_images, int op,
+                                      const jpeg_amd_region *region, const int16_t *const d_coef_in[],
+                                      const size_t in_stride[], const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                      const uint16_t *d_quanta_out, int16_t *const d_coef_out[], const size_t out_stride[],
+                                      int32_t *d_overflow);
+/* single image, host tables (h_quanta_out NULL = no requantisation); synchronises, EINVAL where the reference would trap */
+int jpeg_amd_spectral_transform(jpeg_amd_ctx *ctx, const jpeg_amd_layout *in_layout, int op, const jpeg_amd_region *region,
+                                const int16_t *const d_coef_in[], const uint16_t *h_quanta, int ntables,
+                                const uint16_t *h_quanta_out, int16_t *const d_coef_out[]);
+
+/* The script of a JPEG file, as its writer laid it out: the scans in order (*nscans of them; scans == NULL only counts,
+ * otherwise scan_capacity must hold them all), each component's quantisation-table key (the index, in file order, of the
+ * DQT table definition its frame selector points at when its first scan starts -- the inverse of JPEG.Layout's slot
+ * allocation, jpeg.swift:1383-1442) and the APPn / COM segments in front of the frame header (*nmetadata of them, kind 1 /
+ * 2, `data` pointing INTO h_jpeg; NULL / capacity as for scans).  What jpeg_amd_jpeg_encode_spectral takes to write the
+ * file again.  Host only. */
+int jpeg_amd_jpeg_script(const uint8_t *h_jpeg, size_t nbytes, jpeg_amd_scan *scans, int scan_capacity, int *nscans,
+                         int32_t quanta_key[JPEG_AMD_MAX_PLANES], jpeg_amd_metadata *metadata, int metadata_capacity,
+                         int *nmetadata);
+/* File to file: entropy decoding on the host (restart intervals on `nthreads` threads, <= 0: all cores), the transform on
+ * the GPU, and the host writer keeping the input's process, component ids, scan script, table keys, restart interval and
+ * metadata segments verbatim and in order.  Every component of the frame is transformed.  h_requant: NULL or
+ * [ncomponents][64] in output orientation (components that share a key must get equal tables).  h_out == NULL only sizes
+ * the output (*nbytes_out); out_info (optional) receives the output frame. */
+int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int op, const jpeg_amd_region *region,
+                       const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
+                       jpeg_amd_frame_info *out_info);
+
 #ifdef __cplusplus
 }
 #endif

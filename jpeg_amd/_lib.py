@@ -107,7 +107,25 @@ SIGNATURES = {
                                           C.c_int, _p, C.c_size_t, _p]),
     "jpeg_amd_compress_batch_device": (C.c_int, [_p, _p, _p, C.c_size_t, C.c_int, C.c_int, _p, _p, _p, C.c_int, _p, C.c_int, _p, C.c_int,
                                                  C.c_int, _p, C.c_size_t, _p]),
+    "jpeg_amd_transform_layout": (C.c_int, [_L, C.c_int, _p, _L]),
+    "jpeg_amd_transform_quanta": (C.c_int, [C.c_int, _p, _p]),
+    "jpeg_amd_spectral_transform_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _p, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp,
+                                                    _p]),
+    "jpeg_amd_spectral_transform": (C.c_int, [_p, _L, C.c_int, _p, _pp, _p, C.c_int, _p, _pp]),
+    "jpeg_amd_jpeg_script": (C.c_int, [_p, C.c_size_t, _p, C.c_int, _p, _p, _p, C.c_int, _p]),
+    "jpeg_amd_transform": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, _p, C.c_int, _p, C.c_size_t, _p, _p]),
 }
+
+
+class Region(C.Structure):
+    """struct jpeg_amd_region"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+# JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V
+XFORM_TRANSPOSE, XFORM_FLIP_H, XFORM_FLIP_V = 1, 2, 4
+XFORM = {"none": 0, "transpose": 1, "flip_h": 2, "flip_v": 4, "rot_180": 6, "rot_ccw": 5, "rot_cw": 3, "transverse": 7,
+         "ii": 5, "iii": 6, "iv": 3}
 
 
 class FrameInfo(C.Structure):

@@ -286,6 +286,56 @@ class Spectral:
                 f.write(data)
         return data
 
+    def transform(self, op, region=None, requantize=None) -> "Spectral":
+        """Lossless rotate / flip / crop / requantise, device to device (jpeg_amd_spectral_transform_batch; the contract is in
+        include/jpeg_amd.h): what examples/rotate/main.swift and examples/recompress/main.swift do to a Spectral.
+        op: a JPEG_AMD_XFORM_* value or name ("rot_ccw", "flip_h", ...; the reference's "ii", "iii", "iv").
+        region: (x, y, width, height) in source pixels, applied before the op.  requantize: the new tables in OUTPUT
+        orientation, {quanta key: 64 values} or one per entry of self.quanta; None keeps the coefficients exactly."""
+        torch = _torch()
+        op = _xform_op(op)
+        L = self._layout()
+        out = _lib.Layout()
+        reg = _region(region)
+        lib = _lib.lib()
+        _lib.check(lib.jpeg_amd_transform_layout(C.byref(L), op, reg, C.byref(out)), "jpeg_amd_transform_layout")
+        T = op & _lib.XFORM_TRANSPOSE
+        comps = {k: Component((c.factor[1], c.factor[0]) if T else c.factor, c.qi) for k, c in self.layout.components.items()}
+        layout = Layout(self.layout.format, comps)
+        planes = [self.ctx.empty(64 * out.units_x[p] * out.units_y[p], torch.int16).view(out.units_y[p], out.units_x[p], 64)
+                  for p in range(self.layout.count)]
+        n = len(self.quanta)
+        if requantize is None:
+            quanta = [transform_quanta(op, t) for t in self.quanta]
+        elif isinstance(requantize, dict):
+            quanta = [transform_quanta(op, t) for t in self.quanta]
+            for p, comp in enumerate(self.layout.planes):
+                quanta[self.q[p]] = np.asarray(requantize[comp.qi], np.uint16).reshape(64)
+        else:
+            quanta = [np.asarray(t, np.uint16).reshape(64) for t in requantize]
+            if len(quanta) != n:
+                raise ValueError("requantize: one table per entry of self.quanta")
+        d_q = self.ctx.upload(np.stack(self.quanta).astype(np.uint16))
+        d_qo = self.ctx.upload(np.stack(quanta).astype(np.uint16)) if requantize is not None else None
+        flag = torch.zeros(1, dtype=torch.int32, device=self.ctx.torch_device)
+        zero = _lib.size_array([0] * MAX_PLANES)
+        _lib.check(lib.jpeg_amd_spectral_transform_batch(
+            self.ctx.handle, C.byref(L), 1, op, reg, _ptrs(self.planes), zero, d_q.data_ptr(), 0, n,
+            d_qo.data_ptr() if d_qo is not None else None, _ptrs(planes), zero, flag.data_ptr()),
+            "jpeg_amd_spectral_transform_batch", self.ctx.handle)
+        if int(flag.item()):
+            raise _lib.JpegAmdError(_lib.EINVAL, "Spectral.transform: a coefficient the reference would trap on "
+                                                 "(Int16 overflow, q_in > 32767 or q_out = 0)")
+        return Spectral(self.ctx, (out.width, out.height), layout, planes, quanta, self.q)
+
+    def set(self, width: Optional[int] = None, height: Optional[int] = None) -> None:
+        """Spectral.set(width:) / set(height:) (decode.swift:2443-2500), in place: the image is cropped or grows from its
+        top left corner; new blocks are zero."""
+        w = self.size[0] if width is None else int(width)
+        h = self.size[1] if height is None else int(height)
+        t = self.transform(0, (0, 0, w, h))
+        self.size, self.planes = t.size, t.planes
+
     @classmethod
     def decompress(cls, ctx: Context, source, scans: int = 0) -> "Spectral":
         """Spectral.decompress(stream:) / decompress(path:) -- decode.swift:3728, os.swift:309.
@@ -395,6 +445,66 @@ def _decode_spectral(data: np.ndarray, scans: int = 0):
         data.ctypes.data, data.size, _lib.ptr_array([p.ctypes.data for p in planes]), quanta.ctypes.data, None, 0, scans),
         "jpeg_amd_jpeg_decode_spectral_partial")
     return info, planes, quanta
+
+
+def _xform_op(op) -> int:
+    """JPEG_AMD_XFORM_* value or name ("none", "transpose", "flip_h", "flip_v", "rot_180", "rot_ccw", "rot_cw",
+    "transverse"; the reference's rotations "ii", "iii", "iv")."""
+    if isinstance(op, str):
+        key = op.lower()
+        if key not in _lib.XFORM:
+            raise ValueError(f"unknown transform {op!r}")
+        return _lib.XFORM[key]
+    op = int(op)
+    if not 0 <= op <= 7:
+        raise ValueError(f"transform op {op} is not in 0 .. 7")
+    return op
+
+
+def _region(region):
+    if region is None:
+        return None
+    r = _lib.Region()
+    r.x, r.y, r.width, r.height = (int(v) for v in region)
+    return C.byref(r)
+
+
+def transform_quanta(op, table) -> np.ndarray:
+    """q_out[z] = q_in[m(z)] (jpeg_amd_transform_quanta)."""
+    t = np.ascontiguousarray(np.asarray(table, np.uint16).reshape(64))
+    out = np.empty(64, np.uint16)
+    _lib.check(_lib.lib().jpeg_amd_transform_quanta(_xform_op(op), t.ctypes.data, out.ctypes.data), "jpeg_amd_transform_quanta")
+    return out
+
+
+def transform(source, op, region=None, requantize=None, threads: int = 0, path=None, ctx: Optional[Context] = None) -> bytes:
+    """JPEG file -> JPEG file, losslessly rotated / flipped / cropped (and optionally requantised) in the coefficient domain
+    (jpeg_amd_transform): the input's process, scan script, table keys, restart interval and metadata segments are kept.
+    requantize: None or one table of 64 values per frame component, output orientation."""
+    ctx = ctx or default_context()
+    data = _file_bytes(source)
+    reg = _region(region)
+    rq = None
+    if requantize is not None:
+        rq = np.ascontiguousarray(np.stack([np.asarray(t, np.uint16).reshape(64) for t in requantize]))
+    lib = _lib.lib()
+    n = C.c_size_t()
+    cap = 2 * data.size + (1 << 20)
+    for _ in range(2):
+        out = np.empty(cap, np.uint8)
+        st = lib.jpeg_amd_transform(ctx.handle, data.ctypes.data, data.size, _xform_op(op), reg,
+                                    rq.ctypes.data if rq is not None else None, int(threads), out.ctypes.data, out.size,
+                                    C.byref(n), None)
+        if st == _lib.EINVAL and n.value > cap:
+            cap = n.value
+            continue
+        break
+    _lib.check(st, "jpeg_amd_transform", ctx.handle)
+    b = out[:n.value].tobytes()
+    if path is not None:
+        with open(path, "wb") as f:
+            f.write(b)
+    return b
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "transform.hpp"
 #include "worker_pool.hpp"
 
 using namespace jpeg_amd;
@@ -31,6 +32,7 @@ struct jpeg_amd_ctx {
     size_t scratch_bytes = 0;
     uint16_t *d_qstage = nullptr;  // ring of staged host tables
     uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
+    int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -387,6 +389,7 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
+    if (ctx->d_flag) (void)hipFree(ctx->d_flag);
     for (int i = 0; i < 2; ++i) {
         if (ctx->file_pinned[i]) (void)hipHostFree(ctx->file_pinned[i]);
         if (ctx->file_done[i]) (void)hipEventDestroy(ctx->file_done[i]);
@@ -1626,6 +1629,199 @@ try {
     if (!d_pixels) return JPEG_AMD_EINVAL;
     return compress_batch_impl(ctx, frame, nullptr, d_pixels, pixel_stride, n_images, color, quanta_key, h_quanta, h_quanta_keys, ntables,
                                scans, nscans, metadata, nmetadata, nthreads, h_out, out_stride, nbytes);
+}
+JA_NOTHROW_TAIL
+
+// ---- lossless spectral transforms: rotate, flip, crop, requantise (examples/rotate, examples/recompress) ------------------
+namespace {
+
+// whether the op mirrors the SOURCE's x / y axis (FLIP_H / FLIP_V act in the output frame, after the transpose)
+bool mirrors_source_x(int op) { return (op & JPEG_AMD_XFORM_TRANSPOSE) ? (op & JPEG_AMD_XFORM_FLIP_V) : (op & JPEG_AMD_XFORM_FLIP_H); }
+bool mirrors_source_y(int op) { return (op & JPEG_AMD_XFORM_TRANSPOSE) ? (op & JPEG_AMD_XFORM_FLIP_H) : (op & JPEG_AMD_XFORM_FLIP_V); }
+
+// The output layout and, per plane, the region's origin in that plane's blocks.
+struct TransformPlan {
+    jpeg_amd_layout out;
+    int ox[JPEG_AMD_MAX_PLANES], oy[JPEG_AMD_MAX_PLANES];
+};
+
+int plan_transform(const jpeg_amd_layout *in, int op, const jpeg_amd_region *region, TransformPlan *tp)
+{
+    JA_TRY(check_layout(in, -1));
+    if (op < 0 || op > 7) return JPEG_AMD_EINVAL;
+    const jpeg_amd_region r = region ? *region : jpeg_amd_region{0, 0, in->width, in->height};
+    const int mx = 8 * in->scale_x, my = 8 * in->scale_y;
+    if (r.x < 0 || r.y < 0 || r.x >= in->width || r.y >= in->height || r.x % mx || r.y % my) return JPEG_AMD_EINVAL;
+    if (r.width <= 0 || r.height <= 0) return JPEG_AMD_EINVAL;
+    // Spectral.set(width:) / set(height:) from the region's origin, then the example's trim of the edges that the op moves
+    // to the top or left (examples/rotate/main.swift: set(width: size.x - size.x % (8 * scale.x)))
+    jpeg_amd_layout c = *in;
+    c.width = r.width;
+    c.height = r.height;
+    if (mirrors_source_x(op)) c.width -= c.width % mx;
+    if (mirrors_source_y(op)) c.height -= c.height % my;
+    if (c.width <= 0 || c.height <= 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout o = c;
+    if (op & JPEG_AMD_XFORM_TRANSPOSE) {
+        o.width = c.height; o.height = c.width;
+        o.scale_x = c.scale_y; o.scale_y = c.scale_x;
+        for (int p = 0; p < c.nplanes; ++p) { o.factor_x[p] = c.factor_y[p]; o.factor_y[p] = c.factor_x[p]; }
+    }
+    JA_TRY(jpeg_amd_layout_units(&o));
+    for (int p = 0; p < c.nplanes; ++p) {
+        if ((long long)o.units_x[p] * o.units_y[p] > (1LL << 30)) return JPEG_AMD_EINVAL;
+        tp->ox[p] = r.x / mx * in->factor_x[p];
+        tp->oy[p] = r.y / my * in->factor_y[p];
+    }
+    tp->out = o;
+    return JPEG_AMD_OK;
+}
+
+}  // namespace
+
+int jpeg_amd_transform_layout(const jpeg_amd_layout *in, int op, const jpeg_amd_region *region, jpeg_amd_layout *out)
+{
+    if (!in || !out) return JPEG_AMD_EINVAL;
+    TransformPlan tp;
+    JA_TRY(plan_transform(in, op, region, &tp));
+    *out = tp.out;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_transform_quanta(int op, const uint16_t in[64], uint16_t out[64])
+{
+    if (!in || !out || op < 0 || op > 7) return JPEG_AMD_EINVAL;
+    uint16_t t[64];
+    for (int z = 0; z < 64; ++z) t[z] = in[xform_source(op, z)];
+    std::memcpy(out, t, sizeof t);
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_spectral_transform_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, int op,
+                                      const jpeg_amd_region *region, const int16_t *const d_coef_in[], const size_t in_stride[],
+                                      const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                      const uint16_t *d_quanta_out, int16_t *const d_coef_out[], const size_t out_stride[],
+                                      int32_t *d_overflow)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, d_quanta_out ? ntables : -1));
+    if (d_quanta_out && (ntables < 1 || ntables > JPEG_AMD_MAX_PLANES)) return JPEG_AMD_EINVAL;
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    TransformPlan tp;
+    JA_TRY(plan_transform(L, op, region, &tp));
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef_in || !in_stride || !d_coef_out || !out_stride || (d_quanta_out && !d_quanta)) return JPEG_AMD_EINVAL;
+    PlaneSet cin{};
+    PlaneSetMut cout{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        if (!d_coef_out[p] || (!d_coef_in[p] && plane_samples(L, p) != 0)) return JPEG_AMD_EINVAL;
+        cin.ptr[p] = d_coef_in[p]; cin.stride[p] = in_stride[p];
+        cout.ptr[p] = d_coef_out[p]; cout.stride[p] = out_stride[p];
+    }
+    JA_HIP(ctx, launch_transform(ctx->stream, n_images, op, *L, tp.out, tp.ox, tp.oy, cin, QuantaRef{d_quanta, quanta_stride},
+                                 d_quanta_out, cout, d_overflow));
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_spectral_transform(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int op, const jpeg_amd_region *region,
+                                const int16_t *const d_coef_in[], const uint16_t *h_quanta, int ntables,
+                                const uint16_t *h_quanta_out, int16_t *const d_coef_out[])
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    const uint16_t *d_q = nullptr, *d_qo = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    if (h_quanta_out) JA_TRY(stage_quanta(ctx, h_quanta_out, ntables, &d_qo));
+    if (!ctx->d_flag) JA_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_flag), 256));
+    JA_HIP(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(int32_t), ctx->stream));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    JA_TRY(jpeg_amd_spectral_transform_batch(ctx, L, 1, op, region, d_coef_in, zero, d_q, 0, ntables, d_qo, d_coef_out, zero,
+                                             ctx->d_flag));
+    int32_t flag = 0;
+    JA_HIP(ctx, hipMemcpyAsync(&flag, ctx->d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return flag ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
+}
+
+// File to file: host entropy decoding, the transform on the device, the host writer with the input's script.
+int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int op, const jpeg_amd_region *region,
+                       const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
+                       jpeg_amd_frame_info *out_info)
+try {
+    JA_TRY(bind(ctx));
+    if (!h_jpeg || !nbytes_out || op < 0 || op > 7) return JPEG_AMD_EINVAL;
+    jpeg_amd_frame_info fi;
+    JA_TRY(jpeg_amd_jpeg_inspect(h_jpeg, nbytes, &fi));
+    const int nc = fi.ncomponents;
+    if (nc < 1 || nc > JPEG_AMD_MAX_PLANES) return JPEG_AMD_ENOSUP;
+    // the script: scans, table keys, metadata segments (pointing into h_jpeg)
+    int nscans = 0, nmeta = 0;
+    int32_t keys[JPEG_AMD_MAX_PLANES] = {};
+    JA_TRY(jpeg_amd_jpeg_script(h_jpeg, nbytes, nullptr, 0, &nscans, keys, nullptr, 0, &nmeta));
+    std::vector<jpeg_amd_scan> scans((size_t)std::max(nscans, 1));
+    std::vector<jpeg_amd_metadata> meta((size_t)std::max(nmeta, 1));
+    JA_TRY(jpeg_amd_jpeg_script(h_jpeg, nbytes, scans.data(), nscans, &nscans, keys, meta.data(), nmeta, &nmeta));
+    // entropy decoding on the host
+    std::vector<std::vector<int16_t>> planes((size_t)nc);
+    int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+    for (int c = 0; c < nc; ++c) {
+        planes[c].resize((size_t)64 * fi.units_x[c] * fi.units_y[c]);
+        coef[c] = planes[c].data();
+    }
+    uint16_t quanta[JPEG_AMD_MAX_PLANES][64];
+    JA_TRY(jpeg_amd_jpeg_decode_spectral_mt(h_jpeg, nbytes, coef, quanta, &fi, nthreads));
+    const jpeg_amd_layout L = layout_of_info(fi, nc);
+    TransformPlan tp;
+    JA_TRY(plan_transform(&L, op, region, &tp));
+    const jpeg_amd_layout &O = tp.out;
+    // components that share a key share a table, in the file and after requantisation
+    if (h_requant)
+        for (int c = 0; c < nc; ++c)
+            for (int d = 0; d < c; ++d)
+                if (keys[c] == keys[d] && std::memcmp(h_requant + 64 * c, h_requant + 64 * d, 64 * sizeof(uint16_t)))
+                    return JPEG_AMD_EINVAL;
+    // the device: upload, transform, download
+    std::vector<std::vector<int16_t>> outp((size_t)nc);
+    int16_t *ocoef[JPEG_AMD_MAX_PLANES] = {};
+    for (int c = 0; c < nc; ++c) {
+        outp[c].resize(plane_samples(&O, c));
+        ocoef[c] = outp[c].data();
+    }
+    {
+        DeviceBag bag(ctx);
+        const int16_t *d_in[JPEG_AMD_MAX_PLANES] = {};
+        int16_t *d_out[JPEG_AMD_MAX_PLANES] = {};
+        for (int c = 0; c < nc; ++c) {
+            JA_TRY(bag.upload(coef[c], plane_samples(&L, c) * 2, (void **)&d_in[c]));
+            JA_TRY(bag.alloc(plane_samples(&O, c) * 2, (void **)&d_out[c]));
+        }
+        JA_TRY(jpeg_amd_spectral_transform(ctx, &L, op, region, d_in, &quanta[0][0], nc, h_requant, d_out));
+        for (int c = 0; c < nc; ++c) JA_TRY(bag.download(ocoef[c], d_out[c], plane_samples(&O, c) * 2));
+        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // one table per distinct key, ascending, in output orientation
+    std::vector<int32_t> tkeys;
+    std::vector<uint16_t> tables;
+    for (int c = 0; c < nc; ++c)
+        if (std::find(tkeys.begin(), tkeys.end(), keys[c]) == tkeys.end()) tkeys.push_back(keys[c]);
+    std::sort(tkeys.begin(), tkeys.end());
+    for (int32_t k : tkeys) {
+        const int c = (int)(std::find(keys, keys + nc, k) - keys);
+        uint16_t t[64];
+        if (h_requant) std::memcpy(t, h_requant + 64 * c, sizeof t);
+        else JA_TRY(jpeg_amd_transform_quanta(op, quanta[c], t));
+        tables.insert(tables.end(), t, t + 64);
+    }
+    jpeg_amd_frame_info of = fi;
+    of.width = O.width; of.height = O.height;
+    of.scale_x = O.scale_x; of.scale_y = O.scale_y;
+    for (int c = 0; c < nc; ++c) {
+        of.factor_x[c] = O.factor_x[c]; of.factor_y[c] = O.factor_y[c];
+        of.units_x[c] = O.units_x[c];   of.units_y[c] = O.units_y[c];
+    }
+    if (out_info) *out_info = of;
+    return jpeg_amd_jpeg_encode_spectral(&of, keys, ocoef, tables.data(), tkeys.data(), (int)tkeys.size(), scans.data(), nscans,
+                                         meta.data(), nmeta, h_out, capacity, nbytes_out);
 }
 JA_NOTHROW_TAIL
 

@@ -1083,6 +1083,109 @@ int jpeg_amd_jpeg_inspect(const uint8_t *data, size_t nbytes, jpeg_amd_frame_inf
     JA_NOTHROW_END
 }
 
+// The writer's script of a file (what jpeg_amd_jpeg_encode_spectral takes to write it again): a marker walk that decodes no
+// entropy-coded data.  Table keys: every DQT table DEFINITION is a key, numbered in file order; a component's key is the
+// definition its frame selector points at when its first scan starts (the inverse of JPEG.Layout's slot allocation,
+// jpeg.swift:1383-1442).  Metadata: the APPn / COM segments in front of the frame header.
+int jpeg_amd_jpeg_script(const uint8_t *data, size_t nbytes, jpeg_amd_scan *scans, int scan_capacity, int *nscans,
+                         int32_t quanta_key[JPEG_AMD_MAX_PLANES], jpeg_amd_metadata *metadata, int metadata_capacity,
+                         int *nmetadata)
+{
+    if (!data || !nscans || !quanta_key || !nmetadata || scan_capacity < 0 || metadata_capacity < 0) return JPEG_AMD_EINVAL;
+    if (nbytes < 4 || data[0] != 0xff || data[1] != 0xd8) return JPEG_AMD_EINVAL;
+    int ids[JPEG_AMD_MAX_PLANES], tq[JPEG_AMD_MAX_PLANES], key[JPEG_AMD_MAX_PLANES];
+    int slot_key[4] = {-1, -1, -1, -1};
+    int ncomp = 0, ndefs = 0, ns_total = 0, nm = 0, process = -1;
+    size_t pos = 2;
+    while (pos + 1 < nbytes) {
+        if (data[pos] != 0xff) return JPEG_AMD_EINVAL;
+        while (pos + 1 < nbytes && data[pos + 1] == 0xff) ++pos;      // fill bytes
+        if (pos + 1 >= nbytes) break;
+        const int m = data[pos + 1];
+        pos += 2;
+        if (m == 0xd9) break;                                            // EOI
+        if (m == 0x01 || (m >= 0xd0 && m <= 0xd7)) continue;
+        if (pos + 2 > nbytes) return JPEG_AMD_EINVAL;
+        const size_t seglen = ((size_t)data[pos] << 8) | data[pos + 1];
+        if (seglen < 2 || pos + seglen > nbytes) return JPEG_AMD_EINVAL;
+        const uint8_t *s = data + pos + 2;
+        const size_t len = seglen - 2;
+        pos += seglen;
+        if (process < 0 && ((m >= 0xe0 && m <= 0xef) || m == 0xfe)) {
+            if (metadata && nm < metadata_capacity) {
+                jpeg_amd_metadata &md = metadata[nm];
+                md = jpeg_amd_metadata{};
+                md.kind = m == 0xfe ? 2 : 1;
+                md.app = m == 0xfe ? 0 : m - 0xe0;
+                md.data = s;
+                md.size = len;
+            }
+            ++nm;
+        } else if (m == 0xc0 || m == 0xc1 || m == 0xc2) {
+            if (process >= 0 || len < 6) return JPEG_AMD_EINVAL;
+            process = m - 0xc0;
+            ncomp = s[5];
+            if (ncomp < 1 || ncomp > JPEG_AMD_MAX_PLANES || len < 6 + 3 * (size_t)ncomp) return JPEG_AMD_ENOSUP;
+            for (int c = 0; c < ncomp; ++c) {
+                ids[c] = s[6 + 3 * c];
+                tq[c] = s[8 + 3 * c] & 3;
+                key[c] = -1;
+            }
+        } else if (m == 0xdb) {
+            size_t i = 0;
+            while (i < len) {
+                const int pq = s[i] >> 4, slot = s[i] & 15;
+                if (pq > 1 || slot > 3 || i + 1 + (pq ? 128 : 64) > len) return JPEG_AMD_EINVAL;
+                slot_key[slot] = ndefs++;
+                i += 1 + (pq ? 128 : 64);
+            }
+        } else if (m == 0xda) {
+            if (process < 0 || len < 1) return JPEG_AMD_EINVAL;
+            const int ns = s[0];
+            if (ns < 1 || ns > ncomp || len < 4 + 2 * (size_t)ns) return JPEG_AMD_EINVAL;
+            jpeg_amd_scan sc{};
+            sc.ncomponents = ns;
+            for (int k = 0; k < ns; ++k) {
+                int c = 0;
+                while (c < ncomp && ids[c] != s[1 + 2 * k]) ++c;
+                if (c == ncomp) return JPEG_AMD_EINVAL;
+                if (key[c] < 0) {
+                    if (slot_key[tq[c]] < 0) return JPEG_AMD_EINVAL;    // no table defined for the component yet
+                    key[c] = slot_key[tq[c]];
+                }
+                // ascending plane order (insertion)
+                int j = k;
+                while (j > 0 && sc.component[j - 1] > c) {
+                    sc.component[j] = sc.component[j - 1]; sc.dc[j] = sc.dc[j - 1]; sc.ac[j] = sc.ac[j - 1];
+                    --j;
+                }
+                sc.component[j] = c;
+                sc.dc[j] = s[2 + 2 * k] >> 4;
+                sc.ac[j] = s[2 + 2 * k] & 15;
+            }
+            if (process == 2) {
+                const int ss = s[1 + 2 * ns], se = s[2 + 2 * ns], ah = s[3 + 2 * ns] >> 4, al = s[3 + 2 * ns] & 15;
+                sc.band_lo = ss; sc.band_hi = se + 1; sc.bit = al; sc.refine = ah ? 1 : 0;
+            }
+            if (scans && ns_total < scan_capacity) scans[ns_total] = sc;
+            ++ns_total;
+            // the entropy-coded segment runs to the next marker that is not RSTn / stuffing
+            while (pos + 1 < nbytes && !(data[pos] == 0xff && data[pos + 1] != 0x00 && !(data[pos + 1] >= 0xd0 && data[pos + 1] <= 0xd7)))
+                ++pos;
+            if (pos + 1 >= nbytes) break;
+        }
+    }
+    if (process < 0 || ns_total == 0) return JPEG_AMD_EINVAL;
+    for (int c = 0; c < ncomp; ++c) {
+        if (key[c] < 0) return JPEG_AMD_EINVAL;                          // a component no scan reaches
+        quanta_key[c] = key[c];
+    }
+    *nscans = ns_total;
+    *nmetadata = nm;
+    if ((scans && ns_total > scan_capacity) || (metadata && nm > metadata_capacity)) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
 int jpeg_amd_jpeg_decode_spectral(const uint8_t *data, size_t nbytes, int16_t *const h_coef[],
                                   uint16_t h_quanta[][64], jpeg_amd_frame_info *info)
 {

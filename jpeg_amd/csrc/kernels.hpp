@@ -101,6 +101,15 @@ bool       generic_fused_supported(const jpeg_amd_layout &layout);
 hipError_t launch_generic_fused(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef,
                                 QuantaRef q, bool cosited, uint32_t *d_walk_counter, uint16_t *d_rect, size_t rect_stride);
 
+// ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
+// Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
+// maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,
+// else requantise (q's tables -> these, same strides, plane p's table in.qi[p]).  d_overflow: optional, set to 1 where the
+// reference would trap.
+hipError_t launch_transform(hipStream_t stream, int n_images, int op, const jpeg_amd_layout &in, const jpeg_amd_layout &out,
+                            const int *ox, const int *oy, const PlaneSet &coef_in, QuantaRef q, const uint16_t *d_quanta_out,
+                            const PlaneSetMut &coef_out, int32_t *d_overflow);
+
 // ---- encode -------------------------------------------------------------------------
 // a13: Rectangular.pack
 hipError_t launch_pack(hipStream_t stream, const uint8_t *d_pixels, size_t npixels,

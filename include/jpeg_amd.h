@@ -530,6 +530,35 @@ int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, 
                        const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
                        jpeg_amd_frame_info *out_info);
 
+/* ---- region decode: the pixels of a rectangle ----------------------------------------------------
+ * == jpeg_amd_decode_batch(...) of the same arguments, then image i cropped to regions[i], bit for bit
+ * (decode.swift:4154-4165, 4182-4276, 4291-4298).  Regions are in PIXELS, any alignment: x, y >= 0, width, height > 0,
+ * x + width <= W, y + height <= H.  Output image i at d_pixels + i * pixel_stride: region.height rows of region.width * 3
+ * bytes, no padding between rows; pixel_stride >= 3 * width_i * height_i for every i (any value, 0 included, when
+ * n_images == 1).  h_regions is a HOST array of n_images regions; the call copies it before it returns, as it copies host
+ * tables.  Every region is validated before anything is enqueued: on EINVAL nothing is written.  Argument rules as
+ * jpeg_amd_decode_batch: 8-bit only (else ENOSUP), 1 or 3 planes, at most 65 535 images, n_images == 0 is OK.
+ * Cost: for the layouts of the fused decode (y8; ycc8 with full-factor luma and chroma at 1x or 2x per axis, centred) one
+ * launch that reads only the blocks of each region's window (jpeg_amd_region_window) and writes only region pixels.  Other
+ * layouts (cosited, factors 3 or 4, ...) decode the whole images into context scratch and crop: correct, but as costly as a
+ * full decode.  A call whose regions are all whole images is jpeg_amd_decode_batch. */
+int jpeg_amd_decode_region_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_region *h_regions,
+                                 uint8_t *d_pixels, size_t pixel_stride);
+/* single image, host tables */
+int jpeg_amd_decode_region(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_region *region, uint8_t *d_pixels);
+/* Host only.  windows[p] (in BLOCKS of plane p, for p < nplanes; the rest are zeroed): the smallest block rectangle that
+ * holds every sample of plane p the reference reads for some pixel of `region` -- for an upsampled plane both neighbours
+ * i and min(i + 1, 8 * units - 1) of the interleave index formula (decode.swift:4182-4276; oracle/jpeg_oracle.c
+ * orc_interleave_rows), zero-weight reads included; for a plane at full factor, or a single-plane image, the sample under
+ * the pixel.  EINVAL for a region outside the image, or a layout whose planes do not cover it. */
+int jpeg_amd_region_window(const jpeg_amd_layout *layout, int cosited, const jpeg_amd_region *region,
+                           jpeg_amd_region windows[JPEG_AMD_MAX_PLANES]);
+
 #ifdef __cplusplus
 }
 #endif

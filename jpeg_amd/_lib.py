@@ -114,6 +114,10 @@ SIGNATURES = {
     "jpeg_amd_spectral_transform": (C.c_int, [_p, _L, C.c_int, _p, _pp, _p, C.c_int, _p, _pp]),
     "jpeg_amd_jpeg_script": (C.c_int, [_p, C.c_size_t, _p, C.c_int, _p, _p, _p, C.c_int, _p]),
     "jpeg_amd_transform": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, _p, C.c_int, _p, C.c_size_t, _p, _p]),
+    "jpeg_amd_decode_region_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, _p,
+                                               C.c_size_t]),
+    "jpeg_amd_decode_region": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "jpeg_amd_region_window": (C.c_int, [_L, C.c_int, _p, _p]),
 }
 
 

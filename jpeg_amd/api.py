@@ -234,12 +234,21 @@ class Spectral:
             "jpeg_amd_spectral_rectangular", self.ctx.handle)
         return Rectangular(self.ctx, self.size, self.layout, out.view(H, W, self.layout.count))
 
-    def decode(self, color=RGB, cosite: bool = False):
-        """Fused idct().interleaved(cosite:).unpack(as:) -> uint8 tensor [H*W, 3]."""
+    def decode(self, color=RGB, cosite: bool = False, region=None):
+        """Fused idct().interleaved(cosite:).unpack(as:) -> uint8 tensor [H*W, 3].  region (x, y, width, height) in pixels,
+        any alignment: the same decode cropped to it, bit for bit, as [height*width, 3] (jpeg_amd_decode_region)."""
         torch = _torch()
         L = self._layout()
-        out = self.ctx.empty(self.size[0] * self.size[1] * 3, torch.uint8)
         qarr, qptr = _quanta_array(self.quanta)
+        if region is not None:
+            reg = _region(region)
+            r = reg._obj
+            out = self.ctx.empty(max(r.width, 0) * max(r.height, 0) * 3, torch.uint8)
+            _lib.check(_lib.lib().jpeg_amd_decode_region(
+                self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
+                1 if cosite else 0, color.code, reg, out.data_ptr()), "jpeg_amd_decode_region", self.ctx.handle)
+            return out.view(-1, 3)
+        out = self.ctx.empty(self.size[0] * self.size[1] * 3, torch.uint8)
         _lib.check(_lib.lib().jpeg_amd_decode(
             self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
             1 if cosite else 0, color.code, out.data_ptr()), "jpeg_amd_decode", self.ctx.handle)
@@ -505,6 +514,49 @@ def transform(source, op, region=None, requantize=None, threads: int = 0, path=N
         with open(path, "wb") as f:
             f.write(b)
     return b
+
+
+def region_window(size, layout: Layout, region, cosite: bool = False, units=None) -> List[Tuple[int, int, int, int]]:
+    """The block window (x, y, width, height in blocks) of every plane that the pixels of `region` read
+    (jpeg_amd_region_window): what a caller uploads to decode that region."""
+    L = layout.c_layout(size, units)
+    w = (_lib.Region * MAX_PLANES)()
+    _lib.check(_lib.lib().jpeg_amd_region_window(C.byref(L), 1 if cosite else 0, _region(region), w), "jpeg_amd_region_window")
+    return [(w[p].x, w[p].y, w[p].width, w[p].height) for p in range(layout.count)]
+
+
+def decode_regions(ctx: Context, size, layout: Layout, planes, quanta, regions, q: Optional[Sequence[int]] = None, color=RGB,
+                   cosite: bool = False):
+    """Decode n images of one layout, each cropped to its own region, in one call (jpeg_amd_decode_region_batch).
+    planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or device); regions: [n, 4] of (x, y, width,
+    height) in pixels.  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+    torch = _torch()
+    regs = np.ascontiguousarray(np.asarray(regions, np.int32).reshape(-1, 4))
+    n = regs.shape[0]
+    q = list(q) if q is not None else _dedupe_q(layout)
+    planes = list(planes)
+    if len(planes) != layout.count or len(q) != layout.count:
+        raise ValueError("plane count does not match layout")
+    for p in planes:
+        if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
+            raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
+    units = [(int(p.shape[2]), int(p.shape[1])) for p in planes]
+    if isinstance(quanta, np.ndarray):
+        quanta = ctx.upload(np.asarray(quanta, np.uint16))
+    if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
+        raise ValueError("quanta: [n, ntables, 64]")
+    L = layout.c_layout(size, units, q)
+    areas = [3 * int(w) * int(h) for w, h in regs[:, 2:4]] if n else [0]
+    stride = max(max(areas), 0)
+    out = ctx.empty(n * stride, torch.uint8)
+    h_regions = (_lib.Region * max(n, 1))()
+    for i, (x, y, w, h) in enumerate(regs.tolist()):
+        h_regions[i].x, h_regions[i].y, h_regions[i].width, h_regions[i].height = x, y, w, h
+    _lib.check(_lib.lib().jpeg_amd_decode_region_batch(
+        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() for p in planes]), quanta.data_ptr(),
+        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_regions, out.data_ptr(), stride),
+        "jpeg_amd_decode_region_batch", ctx.handle)
+    return [out[i * stride:i * stride + areas[i]].view(int(regs[i, 3]), int(regs[i, 2]), 3) for i in range(n)]
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

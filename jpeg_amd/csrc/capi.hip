@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "region.hpp"
 #include "transform.hpp"
 #include "worker_pool.hpp"
 
@@ -33,6 +34,8 @@ struct jpeg_amd_ctx {
     uint16_t *d_qstage = nullptr;  // ring of staged host tables
     uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
     int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
+    void *d_region = nullptr;      // staged regions + tile prefix of jpeg_amd_decode_region_batch (grown on demand)
+    size_t region_bytes = 0;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -157,6 +160,14 @@ int stage_quanta(jpeg_amd_ctx *ctx, const uint16_t *h_quanta, int ntables, const
 }
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Bytes of scratch_planes's planes: they take [0, this) of the scratch.
+size_t scratch_planes_bytes(const jpeg_amd_layout *L, int n_images, size_t sample_bytes)
+{
+    size_t total = 0;
+    for (int p = 0; p < L->nplanes; ++p) total += align256(plane_samples(L, p) * (size_t)n_images * sample_bytes);
+    return total;
+}
 
 // The planes of the staged paths in the context's scratch: n_images images of every plane, `sample_bytes` per sample.
 int scratch_planes(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, size_t sample_bytes, PlaneSetMut *ps)
@@ -387,6 +398,7 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     ctx->workers.reset();
     ctx->copiers.reset();
     if (ctx->scratch) (void)hipFree(ctx->scratch);
+    if (ctx->d_region) (void)hipFree(ctx->d_region);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
     if (ctx->d_flag) (void)hipFree(ctx->d_flag);
@@ -617,6 +629,153 @@ int jpeg_amd_decode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *
     const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
     return jpeg_amd_decode_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color,
                                  d_pixels, 0);
+}
+
+namespace {
+
+// A pixel region of jpeg_amd_decode_region_batch / jpeg_amd_region_window: inside the image, not empty.
+int check_region(const jpeg_amd_layout *L, const jpeg_amd_region &r)
+{
+    if (r.x < 0 || r.y < 0 || r.width <= 0 || r.height <= 0) return JPEG_AMD_EINVAL;
+    if ((long long)r.x + r.width > L->width || (long long)r.y + r.height > L->height) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+bool whole_image(const jpeg_amd_layout *L, const jpeg_amd_region &r)
+{
+    return r.x == 0 && r.y == 0 && r.width == L->width && r.height == L->height;
+}
+
+// The regions (int32 [n][4]) and their tile prefix (uint32 [n + 1]) in the context's region buffer, one copy from a host
+// buffer (pageable, so the copy has taken it when the call returns -- as stage_quanta).  Returns the workgroup count.
+int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int32_t **d_regions, const uint32_t **d_tiles,
+                  uint32_t *nwg)
+{
+    const size_t bytes = (size_t)16 * n + 4 * ((size_t)n + 1);
+    std::vector<uint32_t> buf(bytes / 4);
+    uint32_t acc = 0;
+    for (int i = 0; i < n; ++i) {
+        std::memcpy(&buf[4 * (size_t)i], &h[i], 16);
+        buf[4 * (size_t)n + i] = acc;
+        acc += region_tiles(h[i]);
+    }
+    buf[4 * (size_t)n + n] = acc;
+    if (bytes > ctx->region_bytes) {
+        if (ctx->d_region) {
+            JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still read it
+            JA_HIP(ctx, hipFree(ctx->d_region));
+            ctx->d_region = nullptr;
+            ctx->region_bytes = 0;
+        }
+        const size_t want = bytes + bytes / 8 + 4096;
+        JA_HIP(ctx, hipMalloc(&ctx->d_region, want));
+        ctx->region_bytes = want;
+    }
+    JA_HIP(ctx, hipMemcpyAsync(ctx->d_region, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_regions = static_cast<const int32_t *>(ctx->d_region);
+    *d_tiles = reinterpret_cast<const uint32_t *>(static_cast<const int32_t *>(ctx->d_region) + 4 * (size_t)n);
+    *nwg = acc;
+    return JPEG_AMD_OK;
+}
+
+constexpr size_t kRegionFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's whole-image decodes
+
+}  // namespace
+
+int jpeg_amd_decode_region_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_region *h_regions,
+                                 uint8_t *d_pixels, size_t pixel_stride)
+try {
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (L->nplanes != 1 && L->nplanes != 3) return JPEG_AMD_EINVAL;
+    if (L->precision != 8) return JPEG_AMD_ENOSUP;
+    if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_regions) return JPEG_AMD_EINVAL;
+    for (int p = 0; p < L->nplanes; ++p)
+        if (!d_coef[p]) return JPEG_AMD_EINVAL;
+    bool whole = true;
+    size_t max_bytes = 0;
+    for (int i = 0; i < n_images; ++i) {
+        JA_TRY(check_region(L, h_regions[i]));
+        const size_t bytes = (size_t)3 * h_regions[i].width * h_regions[i].height;
+        if (n_images > 1 && pixel_stride < bytes) return JPEG_AMD_EINVAL;
+        max_bytes = std::max(max_bytes, bytes);
+        whole = whole && whole_image(L, h_regions[i]);
+    }
+    if (whole)
+        return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                     d_pixels, pixel_stride);
+
+    const int32_t *d_regions = nullptr;
+    const uint32_t *d_tiles = nullptr;
+    uint32_t nwg = 0;
+    if (fused_decode_supported(*L, cosited != 0)) {
+        JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
+        PlaneSet cs{};
+        for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
+        JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride},
+                                         color == JPEG_AMD_COLOR_RGB8, d_tiles, d_regions, nwg, d_pixels, pixel_stride));
+        return JPEG_AMD_OK;
+    }
+
+    // fallback: whole images into scratch behind the staged path's planes, then one crop launch, chunk by chunk
+    const size_t full = (size_t)3 * L->width * L->height;
+    const size_t per_image = full + scratch_planes_bytes(L, 1, sizeof(uint8_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kRegionFallbackBytes / per_image));
+    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
+    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full * chunk)));
+    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;   // decode_batch's planes stay below it
+    JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
+    for (int i0 = 0; i0 < n_images; i0 += chunk) {
+        const int m = std::min(chunk, n_images - i0);
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
+        JA_TRY(jpeg_amd_decode_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
+                                     cosited, color, d_full, full));
+        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, L->width, d_regions + 4 * (size_t)i0, max_bytes,
+                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+    }
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_region(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_region *region, uint8_t *d_pixels)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (!region) return JPEG_AMD_EINVAL;
+    JA_TRY(check_region(L, *region));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    return jpeg_amd_decode_region_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, region, d_pixels, 0);
+}
+
+int jpeg_amd_region_window(const jpeg_amd_layout *L, int cosited, const jpeg_amd_region *region,
+                           jpeg_amd_region windows[JPEG_AMD_MAX_PLANES])
+{
+    if (!region || !windows) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_region(L, *region));
+    const jpeg_amd_region &r = *region;
+    for (int p = 0; p < JPEG_AMD_MAX_PLANES; ++p) {
+        windows[p] = jpeg_amd_region{0, 0, 0, 0};
+        if (p >= L->nplanes) continue;
+        int32_t x0, x1, y0, y1;
+        axis_span(region_axis(*L, p, cosited != 0, false), r.x, r.x + r.width - 1, x0, x1);
+        axis_span(region_axis(*L, p, cosited != 0, true), r.y, r.y + r.height - 1, y0, y1);
+        windows[p] = jpeg_amd_region{x0 >> 3, y0 >> 3, (x1 >> 3) - (x0 >> 3) + 1, (y1 >> 3) - (y0 >> 3) + 1};
+    }
+    return JPEG_AMD_OK;
 }
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,

@@ -101,6 +101,19 @@ bool       generic_fused_supported(const jpeg_amd_layout &layout);
 hipError_t launch_generic_fused(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef,
                                 QuantaRef q, bool cosited, uint32_t *d_walk_counter, uint16_t *d_rect, size_t rect_stride);
 
+// ---- region decode (kernels_region.hip) -----------------------------------------------
+// The layouts of fused_decode_supported: n_images images, image i cut to its rectangle in ONE launch of nwg workgroups.
+// d_regions: int32 [n][4] (x, y, width, height); d_tiles: uint32 [n + 1], the prefix of region_tiles over the images
+// (d_tiles[n] == nwg).  Image i's rows of width * 3 bytes, unpadded, at d_pixels + i * pixel_stride.
+uint32_t   region_tiles(const jpeg_amd_region &region);
+hipError_t launch_region_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef, QuantaRef q,
+                                bool rgb, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
+                                uint8_t *d_pixels, size_t pixel_stride);
+// Any layout: whole decoded images (width x height x 3 bytes, full_stride apart) cut to their rectangles.  max_bytes: the
+// largest rectangle's byte count.
+hipError_t launch_region_crop(hipStream_t stream, int n_images, const uint8_t *d_full, size_t full_stride, int width,
+                              const int32_t *d_regions, size_t max_bytes, uint8_t *d_pixels, size_t pixel_stride);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

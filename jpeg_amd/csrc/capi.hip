@@ -17,8 +17,8 @@
 #include <thread>
 #include <vector>
 
+#include "interleave.hpp"
 #include "kernels.hpp"
-#include "region.hpp"
 #include "transform.hpp"
 #include "worker_pool.hpp"
 
@@ -110,17 +110,14 @@ int check_layout(const jpeg_amd_layout *L, int ntables)
 int check_planes_cover_image(const jpeg_amd_layout *L)
 {
     for (int p = 0; p < L->nplanes; ++p) {
-        const bool direct = L->nplanes == 1 ||
-                            (L->factor_x[p] == L->scale_x && L->factor_y[p] == L->scale_y);
-        if (direct) {
+        if (plane_is_direct(*L, p)) {
             if (8 * L->units_x[p] < L->width || 8 * L->units_y[p] < L->height) return JPEG_AMD_EINVAL;
         } else {
-            // bilinear: the sample index of the last pixel, i = (a + b (size - 1)) / c (decode.swift:4223-4246; its
-            // neighbour i + 1 is clamped to the plane, i itself is not), must lie inside the plane.  The cosited form
-            // i = factor (size - 1) / scale is the larger of the two.
+            // bilinear: the sample index of the last pixel (decode.swift:4223-4246; its neighbour i + 1 is clamped to the
+            // plane, i itself is not) must lie inside the plane.  The cosited form is the larger of the two.
             if (L->units_x[p] < 1 || L->units_y[p] < 1) return JPEG_AMD_EINVAL;
-            const long long ix = (long long)L->factor_x[p] * (L->width - 1) / L->scale_x;
-            const long long iy = (long long)L->factor_y[p] * (L->height - 1) / L->scale_y;
+            const long long ix = axis_index(interleave_axis(*L, p, true, false), L->width - 1);
+            const long long iy = axis_index(interleave_axis(*L, p, true, true), L->height - 1);
             if (ix >= 8LL * L->units_x[p] || iy >= 8LL * L->units_y[p]) return JPEG_AMD_EINVAL;
         }
     }
@@ -182,6 +179,65 @@ int scratch_planes(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, si
     for (int p = 0; p < L->nplanes; ++p) {
         ps->ptr[p] = static_cast<uint8_t *>(ctx->scratch) + offset[p];
         ps->stride[p] = plane_samples(L, p);
+    }
+    return JPEG_AMD_OK;
+}
+
+// The ABI's per-plane pointer (and stride: nullptr = one image) arrays as a PlaneSet / PlaneSetMut.  Decode inputs
+// (need_all) reject any null plane pointer, encode outputs only where the plane has samples.
+template <typename Set, typename T>
+int plane_set(const jpeg_amd_layout *L, T *const d_planes[], const size_t stride[], bool need_all, Set *ps)
+{
+    *ps = Set{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        if (!d_planes[p] && (need_all || plane_samples(L, p))) return JPEG_AMD_EINVAL;
+        ps->ptr[p] = d_planes[p];
+        ps->stride[p] = stride ? stride[p] : 0;
+    }
+    return JPEG_AMD_OK;
+}
+
+// What the batch entry points of the built-in 8-bit colour formats require, in the order that decides the status of a
+// call that is wrong twice (EINVAL against ENOSUP).
+int check_batch8(const jpeg_amd_layout *L, int n_images, jpeg_amd_color color)
+{
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (L->nplanes != 1 && L->nplanes != 3) return JPEG_AMD_EINVAL;   // built-in colour formats
+    if (L->precision != 8) return JPEG_AMD_ENOSUP;                   // JPEG.Common is 8-bit
+    if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// The staged decode (any factors): IDCT every plane into scratch planes of bytes or halfwords, then upsample + interleave
+// (+ colour) into `kind` pixels.
+int staged_decode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const PlaneSet &coef, QuantaRef q, bool cosited,
+                  bool planes_u8, PixelKind kind, void *d_out, size_t out_stride_bytes)
+{
+    PlaneSetMut scratch;
+    JA_TRY(scratch_planes(ctx, L, n_images, planes_u8 ? sizeof(uint8_t) : sizeof(uint16_t), &scratch));
+    PlaneSet ps{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        JA_HIP(ctx, launch_idct_plane(ctx->stream, n_images, static_cast<const int16_t *>(coef.ptr[p]), coef.stride[p], q, L->qi[p],
+                                      L->units_x[p], L->units_y[p], L->precision, scratch.ptr[p], scratch.stride[p], planes_u8));
+        ps.ptr[p] = scratch.ptr[p];
+        ps.stride[p] = scratch.stride[p];
+    }
+    JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, n_images, *L, ps, planes_u8, cosited, kind, d_out, out_stride_bytes));
+    return JPEG_AMD_OK;
+}
+
+// The staged encode (any factors): decomposed() into uint16 scratch planes, then fdct(quanta:) plane by plane.
+int staged_encode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const void *d_in, size_t in_stride_bytes,
+                  PixelKind kind, QuantaRef q, const PlaneSetMut &coef)
+{
+    PlaneSetMut ps;
+    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &ps));
+    JA_HIP(ctx, launch_decompose(ctx->stream, n_images, *L, d_in, in_stride_bytes, kind, ps));
+    for (int p = 0; p < L->nplanes; ++p) {
+        if (plane_samples(L, p) == 0) continue;
+        JA_HIP(ctx, launch_fdct_plane(ctx->stream, n_images, static_cast<const uint16_t *>(ps.ptr[p]), ps.stride[p], q, L->qi[p],
+                                      L->units_x[p], L->units_y[p], L->precision, static_cast<int16_t *>(coef.ptr[p]),
+                                      coef.stride[p]));
     }
     return JPEG_AMD_OK;
 }
@@ -552,11 +608,8 @@ int jpeg_amd_planar_interleaved(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L,
     JA_TRY(check_layout(L, -1));
     JA_TRY(check_planes_cover_image(L));
     if (!d_planes || !d_rect) return JPEG_AMD_EINVAL;
-    PlaneSet ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (!d_planes[p]) return JPEG_AMD_EINVAL;
-        ps.ptr[p] = d_planes[p];
-    }
+    PlaneSet ps;
+    JA_TRY(plane_set(L, d_planes, nullptr, true, &ps));
     JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, 1, *L, ps, false, cosited != 0,
                                         PixelKind::Rect16, d_rect, 0));
     return JPEG_AMD_OK;
@@ -583,39 +636,18 @@ int jpeg_amd_decode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
     JA_TRY(bind(ctx));
     JA_TRY(check_layout(L, ntables));
     JA_TRY(check_planes_cover_image(L));
-    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    if (L->nplanes != 1 && L->nplanes != 3) return JPEG_AMD_EINVAL;   // built-in colour formats
-    if (L->precision != 8) return JPEG_AMD_ENOSUP;                   // JPEG.Common is 8-bit
-    if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
+    JA_TRY(check_batch8(L, n_images, color));
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
-    for (int p = 0; p < L->nplanes; ++p)
-        if (!d_coef[p]) return JPEG_AMD_EINVAL;
-
+    PlaneSet cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+    const QuantaRef q{d_quanta, quanta_stride};
+    const bool rgb = color == JPEG_AMD_COLOR_RGB8;
     if (fused_decode_supported(*L, cosited != 0)) {
-        PlaneSet cs{};
-        for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
-        JA_HIP(ctx, launch_fused_decode(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride},
-                                        color == JPEG_AMD_COLOR_RGB8, ctx->d_walk, d_pixels, pixel_stride));
+        JA_HIP(ctx, launch_fused_decode(ctx->stream, n_images, *L, cs, q, rgb, ctx->d_walk, d_pixels, pixel_stride));
         return JPEG_AMD_OK;
     }
-
-    // general path: IDCT every plane into uint8 scratch planes, then upsample + colour.
-    PlaneSetMut scratch;
-    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint8_t), &scratch));
-    PlaneSet ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        JA_HIP(ctx, launch_idct_plane(ctx->stream, n_images, d_coef[p], coef_stride[p],
-                                      QuantaRef{d_quanta, quanta_stride}, L->qi[p],
-                                      L->units_x[p], L->units_y[p], L->precision, scratch.ptr[p],
-                                      scratch.stride[p], true));
-        ps.ptr[p] = scratch.ptr[p];
-        ps.stride[p] = scratch.stride[p];
-    }
-    JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, n_images, *L, ps, true, cosited != 0,
-                                        color == JPEG_AMD_COLOR_RGB8 ? PixelKind::RGB8 : PixelKind::YCC8,
-                                        d_pixels, pixel_stride));
-    return JPEG_AMD_OK;
+    return staged_decode(ctx, L, n_images, cs, q, cosited != 0, true, rgb ? PixelKind::RGB8 : PixelKind::YCC8, d_pixels, pixel_stride);
 }
 
 int jpeg_amd_decode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
@@ -691,14 +723,11 @@ try {
     JA_TRY(bind(ctx));
     JA_TRY(check_layout(L, ntables));
     JA_TRY(check_planes_cover_image(L));
-    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    if (L->nplanes != 1 && L->nplanes != 3) return JPEG_AMD_EINVAL;
-    if (L->precision != 8) return JPEG_AMD_ENOSUP;
-    if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
+    JA_TRY(check_batch8(L, n_images, color));
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_regions) return JPEG_AMD_EINVAL;
-    for (int p = 0; p < L->nplanes; ++p)
-        if (!d_coef[p]) return JPEG_AMD_EINVAL;
+    PlaneSet cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
     bool whole = true;
     size_t max_bytes = 0;
     for (int i = 0; i < n_images; ++i) {
@@ -717,8 +746,6 @@ try {
     uint32_t nwg = 0;
     if (fused_decode_supported(*L, cosited != 0)) {
         JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
-        PlaneSet cs{};
-        for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
         JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride},
                                          color == JPEG_AMD_COLOR_RGB8, d_tiles, d_regions, nwg, d_pixels, pixel_stride));
         return JPEG_AMD_OK;
@@ -771,8 +798,8 @@ int jpeg_amd_region_window(const jpeg_amd_layout *L, int cosited, const jpeg_amd
         windows[p] = jpeg_amd_region{0, 0, 0, 0};
         if (p >= L->nplanes) continue;
         int32_t x0, x1, y0, y1;
-        axis_span(region_axis(*L, p, cosited != 0, false), r.x, r.x + r.width - 1, x0, x1);
-        axis_span(region_axis(*L, p, cosited != 0, true), r.y, r.y + r.height - 1, y0, y1);
+        axis_span(interleave_axis(*L, p, cosited != 0, false), r.x, r.x + r.width - 1, x0, x1);
+        axis_span(interleave_axis(*L, p, cosited != 0, true), r.y, r.y + r.height - 1, y0, y1);
         windows[p] = jpeg_amd_region{x0 >> 3, y0 >> 3, (x1 >> 3) - (x0 >> 3) + 1, (y1 >> 3) - (y0 >> 3) + 1};
     }
     return JPEG_AMD_OK;
@@ -787,11 +814,8 @@ int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, 
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_desc || !d_entries || !d_coef || !coef_stride) return JPEG_AMD_EINVAL;
-    PlaneSetMut cs{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (!d_coef[p]) return JPEG_AMD_EINVAL;
-        cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p];
-    }
+    PlaneSetMut cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
     JA_HIP(ctx, launch_expand_sparse(ctx->stream, n_images, *L, d_desc, desc_stride, d_entries, entries_stride, d_skip, cs));
     return JPEG_AMD_OK;
 }
@@ -807,28 +831,15 @@ int jpeg_amd_spectral_rectangular_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef || !coef_stride || !d_quanta || !d_rect) return JPEG_AMD_EINVAL;
-    for (int p = 0; p < L->nplanes; ++p)
-        if (!d_coef[p]) return JPEG_AMD_EINVAL;
-    PlaneSet cs{};
-    for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
+    PlaneSet cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+    const QuantaRef q{d_quanta, quanta_stride};
     if (generic_fused_supported(*L)) {
-        JA_HIP(ctx, launch_generic_fused(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride}, cosited != 0,
+        JA_HIP(ctx, launch_generic_fused(ctx->stream, n_images, *L, cs, q, cosited != 0,
                                          ctx->d_walk ? ctx->d_walk + 16 : nullptr, d_rect, rect_stride));   // (dword 16: the 4:2:0 walk owns dword 0)
         return JPEG_AMD_OK;
     }
-    // staged path (any factors): IDCT every plane into uint16 scratch planes, then upsample + interleave
-    PlaneSetMut scratch;
-    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &scratch));
-    PlaneSet ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        JA_HIP(ctx, launch_idct_plane(ctx->stream, n_images, d_coef[p], coef_stride[p], QuantaRef{d_quanta, quanta_stride},
-                                      L->qi[p], L->units_x[p], L->units_y[p], L->precision, scratch.ptr[p], scratch.stride[p], false));
-        ps.ptr[p] = scratch.ptr[p];
-        ps.stride[p] = scratch.stride[p];
-    }
-    JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, n_images, *L, ps, false, cosited != 0, PixelKind::Rect16, d_rect,
-                                        rect_stride * sizeof(uint16_t)));
-    return JPEG_AMD_OK;
+    return staged_decode(ctx, L, n_images, cs, q, cosited != 0, false, PixelKind::Rect16, d_rect, rect_stride * sizeof(uint16_t));
 }
 
 int jpeg_amd_spectral_rectangular(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
@@ -862,11 +873,8 @@ int jpeg_amd_rectangular_decomposed(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L,
     JA_TRY(bind(ctx));
     JA_TRY(check_layout(L, -1));
     if (!d_rect || !d_planes) return JPEG_AMD_EINVAL;
-    PlaneSetMut ps{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (plane_samples(L, p) && !d_planes[p]) return JPEG_AMD_EINVAL;
-        ps.ptr[p] = d_planes[p];
-    }
+    PlaneSetMut ps;
+    JA_TRY(plane_set(L, d_planes, nullptr, false, &ps));
     JA_HIP(ctx, launch_decompose(ctx->stream, 1, *L, d_rect, 0, PixelKind::Rect16, ps));
     return JPEG_AMD_OK;
 }
@@ -911,34 +919,18 @@ int jpeg_amd_encode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
 {
     JA_TRY(bind(ctx));
     JA_TRY(check_layout(L, ntables));
-    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    if (L->nplanes != 1 && L->nplanes != 3) return JPEG_AMD_EINVAL;
-    if (L->precision != 8) return JPEG_AMD_ENOSUP;
-    if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
+    JA_TRY(check_batch8(L, n_images, color));
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
-
-    for (int p = 0; p < L->nplanes; ++p)
-        if (plane_samples(L, p) && !d_coef[p]) return JPEG_AMD_EINVAL;
+    PlaneSetMut cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, false, &cs));
+    const QuantaRef q{d_quanta, quanta_stride};
+    const bool rgb = color == JPEG_AMD_COLOR_RGB8;
     if (fused_encode_supported(*L)) {
-        PlaneSetMut cs{};
-        for (int p = 0; p < L->nplanes; ++p) { cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p]; }
-        JA_HIP(ctx, launch_fused_encode(ctx->stream, n_images, *L, d_pixels, pixel_stride,
-                                        color == JPEG_AMD_COLOR_RGB8, QuantaRef{d_quanta, quanta_stride}, cs));
+        JA_HIP(ctx, launch_fused_encode(ctx->stream, n_images, *L, d_pixels, pixel_stride, rgb, q, cs));
         return JPEG_AMD_OK;
     }
-    PlaneSetMut ps;
-    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &ps));
-    JA_HIP(ctx, launch_decompose(ctx->stream, n_images, *L, d_pixels, pixel_stride,
-                                 color == JPEG_AMD_COLOR_RGB8 ? PixelKind::RGB8 : PixelKind::YCC8, ps));
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (plane_samples(L, p) == 0) continue;
-        JA_HIP(ctx, launch_fdct_plane(ctx->stream, n_images, static_cast<const uint16_t *>(ps.ptr[p]),
-                                      ps.stride[p], QuantaRef{d_quanta, quanta_stride}, L->qi[p],
-                                      L->units_x[p], L->units_y[p], L->precision, d_coef[p],
-                                      coef_stride[p]));
-    }
-    return JPEG_AMD_OK;
+    return staged_encode(ctx, L, n_images, d_pixels, pixel_stride, rgb ? PixelKind::RGB8 : PixelKind::YCC8, q, cs);
 }
 
 int jpeg_amd_rectangular_spectral_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint16_t *d_rect,
@@ -950,26 +942,14 @@ int jpeg_amd_rectangular_spectral_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_rect || !d_quanta || !d_coef || !coef_stride) return JPEG_AMD_EINVAL;
-    PlaneSetMut cs{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (plane_samples(L, p) && !d_coef[p]) return JPEG_AMD_EINVAL;
-        cs.ptr[p] = d_coef[p]; cs.stride[p] = coef_stride[p];
-    }
+    PlaneSetMut cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, false, &cs));
+    const QuantaRef q{d_quanta, quanta_stride};
     if (generic_encode_supported(*L)) {
-        JA_HIP(ctx, launch_generic_encode(ctx->stream, n_images, *L, d_rect, rect_stride, QuantaRef{d_quanta, quanta_stride}, cs));
+        JA_HIP(ctx, launch_generic_encode(ctx->stream, n_images, *L, d_rect, rect_stride, q, cs));
         return JPEG_AMD_OK;
     }
-    // staged path (any factors): decomposed() into uint16 scratch planes, then fdct(quanta:) plane by plane
-    PlaneSetMut ps;
-    JA_TRY(scratch_planes(ctx, L, n_images, sizeof(uint16_t), &ps));
-    JA_HIP(ctx, launch_decompose(ctx->stream, n_images, *L, d_rect, rect_stride * sizeof(uint16_t), PixelKind::Rect16, ps));
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (plane_samples(L, p) == 0) continue;
-        JA_HIP(ctx, launch_fdct_plane(ctx->stream, n_images, static_cast<const uint16_t *>(ps.ptr[p]), ps.stride[p],
-                                      QuantaRef{d_quanta, quanta_stride}, L->qi[p], L->units_x[p], L->units_y[p], L->precision,
-                                      d_coef[p], coef_stride[p]));
-    }
-    return JPEG_AMD_OK;
+    return staged_encode(ctx, L, n_images, d_rect, rect_stride * sizeof(uint16_t), PixelKind::Rect16, q, cs);
 }
 
 int jpeg_amd_rectangular_spectral(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const uint16_t *d_rect,

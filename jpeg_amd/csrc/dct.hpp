@@ -384,4 +384,35 @@ __device__ __forceinline__ float round_half_away(float v)
     return r + __builtin_truncf(d + d);
 }
 
+// One block's 64 coefficients (128 bytes, 16-byte aligned) as eight 16-byte loads into 32 packed dwords.
+__device__ __forceinline__ void load_block(const int16_t *src, uint32_t (&w)[32])
+{
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint4 v = s[i];
+        w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+}
+
+// One row of eight samples, clamp_trunc'ed and packed to bytes or halfwords (T), in ONE store (dst aligned to 8 sizeof(T)).
+template <typename T>
+__device__ __forceinline__ void store_sample_row(T *dst, const float *g, float limit)
+{
+    uint32_t s[8];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) s[x] = clamp_trunc(g[x], limit);
+    if constexpr (sizeof(T) == 2) {
+        uint4 v;
+        v.x = s[0] | (s[1] << 16); v.y = s[2] | (s[3] << 16);
+        v.z = s[4] | (s[5] << 16); v.w = s[6] | (s[7] << 16);
+        *reinterpret_cast<uint4 *>(dst) = v;
+    } else {
+        uint2 v;
+        v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
+        v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
+        *reinterpret_cast<uint2 *>(dst) = v;
+    }
+}
+
 }  // namespace jpeg_amd

@@ -29,6 +29,7 @@
 
 #include "dct.hpp"
 #include "fused_common.hpp"
+#include "interleave.hpp"
 #include "kernels.hpp"
 #include "quantise.hpp"
 
@@ -378,7 +379,7 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
                     if (kind == 0) pixels(std::integral_constant<int, 0>{});
                     else if (kind == 1) pixels(std::integral_constant<int, 1>{});
                     else pixels(std::integral_constant<int, 2>{});
-                } else
+                } else   // the literal filter: interleave.hpp's axis_index / axis_fraction / bilinear_sample, specialised
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int x = xb + i;
@@ -771,7 +772,7 @@ int tile_blocks(const jpeg_amd_layout &L, int th)
 {
     int n = 0;
     for (int p = 0; p < L.nplanes; ++p) {
-        const bool direct = L.nplanes == 1 || (L.factor_x[p] == L.scale_x && L.factor_y[p] == L.scale_y);
+        const bool direct = plane_is_direct(L, p);
         n += axis_blocks(direct, L.factor_x[p], L.scale_x, GTW) * axis_blocks(direct, L.factor_y[p], L.scale_y, th);
     }
     return n;
@@ -805,13 +806,9 @@ hipError_t launch_generic_fused(hipStream_t stream, int n_images, const jpeg_amd
         P.coef = static_cast<const int16_t *>(coef.ptr[p]); P.stride = coef.stride[p];
         P.ux = L.units_x[p]; P.uy = L.units_y[p]; P.qi = L.qi[p];
         P.rx = L.scale_x / L.factor_x[p]; P.ry = L.scale_y / L.factor_y[p];
-        P.direct = (L.nplanes == 1) || (L.factor_x[p] == L.scale_x && L.factor_y[p] == L.scale_y);
-        if (cosited) {  // decode.swift:4223-4234
-            P.ax = 0; P.ay = 0; P.bx = L.factor_x[p]; P.by = L.factor_y[p]; P.cx = L.scale_x; P.cy = L.scale_y;
-        } else {
-            P.ax = L.factor_x[p] - L.scale_x; P.ay = L.factor_y[p] - L.scale_y;
-            P.bx = 2 * L.factor_x[p]; P.by = 2 * L.factor_y[p]; P.cx = 2 * L.scale_x; P.cy = 2 * L.scale_y;
-        }
+        const InterleaveAxis mx = interleave_axis(L, p, cosited, false), my = interleave_axis(L, p, cosited, true);
+        P.direct = mx.direct;
+        P.ax = mx.a; P.bx = mx.b; P.cx = mx.c; P.ay = my.a; P.by = my.b; P.cy = my.c;
         auto log2_of = [](int c) { return c == 1 ? 0 : c == 2 ? 1 : c == 4 ? 2 : c == 8 ? 3 : -1; };
         P.lgx = log2_of(P.cx); P.lgy = log2_of(P.cy);
         P.mx = (uint32_t)((0x100000000ull + (uint64_t)P.cx - 1) / (uint64_t)P.cx); P.my = (uint32_t)((0x100000000ull + (uint64_t)P.cy - 1) / (uint64_t)P.cy);

@@ -10,8 +10,8 @@
 // workgroup
 //   1. modulates the image's tables into LDS and writes the per-column / per-row interleave maps of its chroma planes
 //      (the sample pair and the fraction of decode.swift:4240-4251, tile-local);
-//   2. transforms every block of every plane that the tile's pixels read -- the window of region.hpp, the chroma halo
-//      included, clamped at the chroma plane's padded edge -- one block per work-item into byte samples in LDS;
+//   2. transforms every block of every plane that the tile's pixels read -- axis_span of interleave.hpp, the chroma
+//      halo included, clamped at the chroma plane's padded edge -- one block per work-item into byte samples in LDS;
 //   3. writes the tile's pixels: upsample from LDS, colour, three byte stores per pixel (the rows of a region have any
 //      length and any alignment).
 // Layouts: those of fused_decode_supported (y8; ycc8 with full-factor luma and 1x1 chroma at scale 1 or 2 per axis, centred).
@@ -21,8 +21,8 @@
 
 #include "dct.hpp"
 #include "fused_common.hpp"
+#include "interleave.hpp"
 #include "kernels.hpp"
-#include "region.hpp"
 
 namespace jpeg_amd {
 
@@ -41,7 +41,7 @@ struct RegionArgs {
     const int16_t *coef[3];
     size_t coef_stride[3];        // int16 elements between images
     int ux[3], qi[3];
-    RegionAxis ax[3], ay[3];
+    InterleaveAxis ax[3], ay[3];
     const uint16_t *quanta;
     size_t quanta_stride;         // uint16 elements between images' table sets
     const uint32_t *tiles;        // [n + 1]: first workgroup of image i; tiles[n] = the grid
@@ -96,27 +96,17 @@ __global__ __launch_bounds__(kThreads) void k_region_decode(RegionArgs a)
     }
     if constexpr (NP == 3) {
         // interleave maps of the chroma planes, decode.swift:4240-4251 (tile-local sample indices)
-        const RegionAxis &mx = a.ax[1], &my = a.ay[1];
+        const InterleaveAxis &mx = a.ax[1], &my = a.ay[1];
         if (t < kTileW && t < px1 - px0) {
             const int x = px0 + t, i = axis_index(mx, x), j = axis_neighbour(mx, x);
-            float f = 0.0f;
-            if (!mx.direct) {
-                const int64_t n = (int64_t)mx.a + (int64_t)mx.b * x;
-                f = fmaxf(0.0f, fminf((float)(int)(n - (int64_t)i * mx.c) / (float)mx.c, 1.0f));
-            }
             colmap[t] = (uint32_t)(i - 8 * wx0[1]) | (uint32_t)(j - 8 * wx0[1]) << 16;
-            colt[t] = f;
+            colt[t] = axis_fraction(mx, x);
         }
         const int u = t - kTileW;
         if (u >= 0 && u < kTileH && u < py1 - py0) {
             const int y = py0 + u, i = axis_index(my, y), j = axis_neighbour(my, y);
-            float f = 0.0f;
-            if (!my.direct) {
-                const int64_t n = (int64_t)my.a + (int64_t)my.b * y;
-                f = fmaxf(0.0f, fminf((float)(int)(n - (int64_t)i * my.c) / (float)my.c, 1.0f));
-            }
             rowmap[u] = (uint32_t)(i - 8 * wy0[1]) | (uint32_t)(j - 8 * wy0[1]) << 16;
-            rowt[u] = f;
+            rowt[u] = axis_fraction(my, y);
         }
     }
     __syncthreads();
@@ -135,32 +125,18 @@ __global__ __launch_bounds__(kThreads) void k_region_decode(RegionArgs a)
         for (int s = 0; s + 1 < NP; ++s)
             if (p == s && k >= nblk[s]) { k -= nblk[s]; p = s + 1; }
         const int ly = k / wbx[p], lx = k - ly * wbx[p];
-        const uint4 *src = reinterpret_cast<const uint4 *>(
-            a.coef[p] + (size_t)img * a.coef_stride[p] + (size_t)64 * ((size_t)(wy0[p] + ly) * a.ux[p] + wx0[p] + lx));
         uint32_t w[32];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint4 v = src[i];
-            w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
+        load_block(a.coef[p] + (size_t)img * a.coef_stride[p] + (size_t)64 * ((size_t)(wy0[p] + ly) * a.ux[p] + wx0[p] + lx), w);
         float g[64];
         idct_block(w, &sq[p][0], 128.5f, g);                 // level 2^7 + 1/2 (decode.swift:4110-4111)
         const int pitch = 8 * wbx[p];
         uint8_t *dst = smp + base[p] + 8 * ly * pitch + 8 * lx;
 #pragma unroll
-        for (int y = 0; y < 8; ++y) {
-            uint32_t s[8];
-#pragma unroll
-            for (int x = 0; x < 8; ++x) s[x] = clamp_trunc(g[8 * y + x], 255.0f);
-            uint2 v;
-            v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-            v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
-            *reinterpret_cast<uint2 *>(dst + y * pitch) = v;
-        }
+        for (int y = 0; y < 8; ++y) store_sample_row(dst + y * pitch, g + 8 * y, 255.0f);
     }
     __syncthreads();
 
-    // the tile's pixels: Planar.interleaved + Rectangular.unpack(as:), literal arithmetic (region.hpp)
+    // the tile's pixels: Planar.interleaved + Rectangular.unpack(as:), literal arithmetic (interleave.hpp)
     const int tw = px1 - px0, th = py1 - py0;
     FastDiv dw;
     dw.set((uint32_t)tw);
@@ -183,12 +159,12 @@ __global__ __launch_bounds__(kThreads) void k_region_decode(RegionArgs a)
                 cr = s2[i1 + i0];
             } else {
                 const float fx = colt[c], fy = rowt[rr];
-                cb = bilinear_literal((float)s1[i1 + i0], (float)s1[i1 + j0], (float)s1[j1 + i0], (float)s1[j1 + j0], fx, fy);
-                cr = bilinear_literal((float)s2[i1 + i0], (float)s2[i1 + j0], (float)s2[j1 + i0], (float)s2[j1 + j0], fx, fy);
+                cb = bilinear_sample((float)s1[i1 + i0], (float)s1[i1 + j0], (float)s1[j1 + i0], (float)s1[j1 + j0], fx, fy);
+                cr = bilinear_sample((float)s2[i1 + i0], (float)s2[i1 + j0], (float)s2[j1 + i0], (float)s2[j1 + j0], fx, fy);
             }
         }
         uint32_t o0 = yv, o1 = cb, o2 = cr;
-        if constexpr (RGB) ycc_to_rgb_literal(yv, cb, cr, o0, o1, o2);
+        if constexpr (RGB) ycc_to_rgb((float)yv, (float)cb, (float)cr, o0, o1, o2);
         uint8_t *o = out + rr * row_bytes + 3 * c;
         o[0] = (uint8_t)o0; o[1] = (uint8_t)o1; o[2] = (uint8_t)o2;
     }
@@ -223,8 +199,8 @@ hipError_t launch_region_decode(hipStream_t stream, int n_images, const jpeg_amd
         a.coef_stride[p] = coef.stride[p];
         a.ux[p] = L.units_x[p];
         a.qi[p] = L.qi[p];
-        a.ax[p] = region_axis(L, p, false, false);
-        a.ay[p] = region_axis(L, p, false, true);
+        a.ax[p] = interleave_axis(L, p, false, false);
+        a.ay[p] = interleave_axis(L, p, false, true);
     }
     a.quanta = q.d_quanta;
     a.quanta_stride = q.image_stride;

@@ -15,6 +15,7 @@
 #pragma clang fp contract(off)
 
 #include "dct.hpp"
+#include "interleave.hpp"
 #include "kernels.hpp"
 
 namespace jpeg_amd {
@@ -53,13 +54,8 @@ __global__ __launch_bounds__(kThreads) void k_idct_plane(
     if (b >= nblocks) return;
     const int by = b / ux, bx = b - by * ux;
 
-    const uint4 *src = reinterpret_cast<const uint4 *>(coef + img * coef_stride + (size_t)64 * b);
     uint32_t w[32];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint4 v = src[i];
-        w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
+    load_block(coef + img * coef_stride + (size_t)64 * b, w);
 
     float g[64];
     idct_block(w, sq, level, g);
@@ -67,50 +63,7 @@ __global__ __launch_bounds__(kThreads) void k_idct_plane(
     const size_t pitch = (size_t)8 * ux;
     OutT *dst = out + img * out_stride + (size_t)8 * by * pitch + 8 * bx;
 #pragma unroll
-    for (int y = 0; y < 8; ++y) {
-        uint32_t s[8];
-#pragma unroll
-        for (int x = 0; x < 8; ++x) s[x] = clamp_trunc(g[8 * y + x], limit);
-        if constexpr (sizeof(OutT) == 2) {
-            uint4 v;
-            v.x = s[0] | (s[1] << 16); v.y = s[2] | (s[3] << 16);
-            v.z = s[4] | (s[5] << 16); v.w = s[6] | (s[7] << 16);
-            *reinterpret_cast<uint4 *>(dst + y * pitch) = v;
-        } else {
-            uint2 v;
-            v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-            v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
-            *reinterpret_cast<uint2 *>(dst + y * pitch) = v;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// colour math  jpeg.swift:441-453 (YCbCr.rgb), :463-478 (RGB.ycc), :343-354 (clamp)
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t clamp_u8(float v)
-{
-    return (uint32_t)__builtin_amdgcn_fmed3f(v, 0.0f, 255.0f);
-}
-
-// x = (Float(y) + m_cb * (Float(cb) - 128)) + m_cr * (Float(cr) - 128); the two `0.0 * c`
-// products only add a signed zero, which cannot change any sum here.
-__device__ __forceinline__ void ycc_to_rgb(float y, float cb, float cr, uint32_t &r,
-                                           uint32_t &g, uint32_t &b)
-{
-    const float pb = cb - 128.0f;
-    const float pr = cr - 128.0f;
-    r = clamp_u8(y + 1.40200f * pr);
-    g = clamp_u8((y + -0.34414f * pb) + -0.71414f * pr);
-    b = clamp_u8(y + 1.77200f * pb);
-}
-
-// x = ((m0 + m_r * r) + m_g * g) + m_b * b; for Y m0 = 0 and `0 + x` is exact.
-__device__ __forceinline__ uint32_t rgb_to_ycc_component(int p, float r, float g, float b)
-{
-    if (p == 0) return clamp_u8((0.2990f * r + 0.5870f * g) + 0.1140f * b);
-    if (p == 1) return clamp_u8(((128.0f + -0.1687f * r) + -0.3313f * g) + 0.5000f * b);
-    return clamp_u8(((128.0f + 0.5000f * r) + -0.4187f * g) + -0.0813f * b);
+    for (int y = 0; y < 8; ++y) store_sample_row(dst + y * pitch, g + 8 * y, limit);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -119,33 +72,21 @@ __device__ __forceinline__ uint32_t rgb_to_ycc_component(int p, float r, float g
 struct UpsampleArgs {
     const void *plane[JPEG_AMD_MAX_PLANES];
     size_t stride[JPEG_AMD_MAX_PLANES];  // elements between images
-    int pw[JPEG_AMD_MAX_PLANES], ph[JPEG_AMD_MAX_PLANES];
-    int ax[JPEG_AMD_MAX_PLANES], bx[JPEG_AMD_MAX_PLANES], cx[JPEG_AMD_MAX_PLANES];
-    int ay[JPEG_AMD_MAX_PLANES], by[JPEG_AMD_MAX_PLANES], cy[JPEG_AMD_MAX_PLANES];
-    int direct[JPEG_AMD_MAX_PLANES];  // factor == scale, or single-plane image: crop copy
+    InterleaveAxis ax[JPEG_AMD_MAX_PLANES], ay[JPEG_AMD_MAX_PLANES];
     int count, W, H;
 };
 
+// One sample of plane p at pixel (x, y).  The map is formed in 32 bits (interleave.hpp states the bound): 64-bit
+// divisions per axis, plane and pixel would be most of this kernel.
 template <typename T>
 __device__ __forceinline__ uint32_t upsampled(const UpsampleArgs &a, int p, int img, int x, int y)
 {
     const T *plane = static_cast<const T *>(a.plane[p]) + img * a.stride[p];
-    const size_t pw = a.pw[p];
-    if (a.direct[p]) return plane[x + pw * y];  // :4192, :4212
-
-    // :4240-4241  quotientAndRemainder truncates toward zero, like C's / and %
-    const int nx = a.ax[p] + a.bx[p] * x, ny = a.ay[p] + a.by[p] * y;
-    const int ix = nx / a.cx[p], fx = nx - ix * a.cx[p];
-    const int iy = ny / a.cy[p], fy = ny - iy * a.cy[p];
-    const int jx = min(ix + 1, a.pw[p] - 1);  // :4245-4246 clamps to the PADDED plane
-    const int jy = min(iy + 1, a.ph[p] - 1);
-    const float tx = fmaxf(0.0f, fminf((float)fx / (float)a.cx[p], 1.0f));  // :4250-4251
-    const float ty = fmaxf(0.0f, fminf((float)fy / (float)a.cy[p], 1.0f));
-    const float u00 = (float)plane[ix + pw * iy], u01 = (float)plane[jx + pw * iy];
-    const float u10 = (float)plane[ix + pw * jy], u11 = (float)plane[jx + pw * jy];
-    const float v0 = u00 * (1.0f - tx) + u01 * tx;  // :4260-4261
-    const float v1 = u10 * (1.0f - tx) + u11 * tx;
-    return (uint32_t)round_half_away(v0 * (1.0f - ty) + v1 * ty);  // :4264
+    const size_t pw = a.ax[p].last + 1;            // the padded plane's pitch, 8 units (summed as int, then widened)
+    if (a.ax[p].direct) return plane[x + pw * y];  // :4192, :4212
+    const AxisTap cx = interpolated_tap<int32_t>(a.ax[p], x), cy = interpolated_tap<int32_t>(a.ay[p], y);
+    return bilinear_sample((float)plane[cx.i + pw * cy.i], (float)plane[cx.j + pw * cy.i],
+                           (float)plane[cx.i + pw * cy.j], (float)plane[cx.j + pw * cy.j], cx.t, cy.t);
 }
 
 template <typename T, PixelKind KIND>
@@ -376,12 +317,7 @@ __global__ __launch_bounds__(kThreads) void k_sparsify(SparsifyArgs a)
 #pragma unroll
         for (int q = 1; q < JPEG_AMD_MAX_PLANES; ++q)
             if (p == q) { src = a.coef[q]; stride = a.coef_stride[q]; first = a.first[q]; }
-        const uint4 *blk = reinterpret_cast<const uint4 *>(src + img * stride + (size_t)(b - first) * 64);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint4 v = blk[i];
-            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
+        load_block(src + img * stride + (size_t)(b - first) * 64, w);
         count = 1;                                              // the DC, zero or not
         if (w[0] >> 16) ++count;
 #pragma unroll
@@ -546,19 +482,8 @@ hipError_t launch_planar_to_pixels(hipStream_t stream, int n_images,
     for (int p = 0; p < L.nplanes; ++p) {
         a.plane[p] = planes.ptr[p];
         a.stride[p] = planes.stride[p];
-        a.pw[p] = 8 * L.units_x[p];
-        a.ph[p] = 8 * L.units_y[p];
-        a.direct[p] = (L.nplanes == 1) ||
-                      (L.factor_x[p] == L.scale_x && L.factor_y[p] == L.scale_y);
-        if (cosited) {  // decode.swift:4223-4234
-            a.ax[p] = 0; a.ay[p] = 0;
-            a.bx[p] = L.factor_x[p]; a.by[p] = L.factor_y[p];
-            a.cx[p] = L.scale_x;     a.cy[p] = L.scale_y;
-        } else {
-            a.ax[p] = L.factor_x[p] - L.scale_x; a.ay[p] = L.factor_y[p] - L.scale_y;
-            a.bx[p] = 2 * L.factor_x[p];         a.by[p] = 2 * L.factor_y[p];
-            a.cx[p] = 2 * L.scale_x;             a.cy[p] = 2 * L.scale_y;
-        }
+        a.ax[p] = interleave_axis(L, p, cosited, false);
+        a.ay[p] = interleave_axis(L, p, cosited, true);
     }
     const dim3 grid(blocks_for((size_t)L.width * L.height), n_images);
 #define JA_LAUNCH(T, K) \

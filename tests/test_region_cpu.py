@@ -140,6 +140,64 @@ def test_window_of_a_420_region_holds_the_chroma_halo():
     assert w[1] == w[2] == _brute(L, 0, (1237, 901, 64, 64))[1]
 
 
+def _planes_cover_image(L):
+    """The rule Planar.interleaved puts on the planes (decode.swift:4190-4246), restated: a direct plane is copied up to the
+    image size; any other plane is read at the last pixel's sample, whose cosited index factor (size - 1) / scale is the
+    larger of the two maps' (the neighbour is clamped to the plane, the sample itself is not)."""
+    for p in range(L.nplanes):
+        fx, fy, ux, uy = L.factor_x[p], L.factor_y[p], L.units_x[p], L.units_y[p]
+        if L.nplanes == 1 or (fx == L.scale_x and fy == L.scale_y):
+            ok = 8 * ux >= L.width and 8 * uy >= L.height
+        else:
+            ok = ux >= 1 and uy >= 1 and fx * (L.width - 1) // L.scale_x < 8 * ux and fy * (L.height - 1) // L.scale_y < 8 * uy
+        if not ok:
+            return False
+    return True
+
+
+def _check_cover(L):
+    """Every plane's units as computed, one fewer and one more, per axis: accept / reject as the rule says."""
+    lib, r, w = _lib.lib(), _lib.Region(0, 0, 1, 1), (_lib.Region * _lib.MAX_PLANES)()
+    accepted = 0
+    for p in range(L.nplanes):
+        ux, uy = L.units_x[p], L.units_y[p]
+        try:
+            for dx in (-1, 0, 1):
+                for dy in (-1, 0, 1):
+                    L.units_x[p], L.units_y[p] = ux + dx, uy + dy
+                    want = 0 if _planes_cover_image(L) else _lib.EINVAL
+                    for cosited in (0, 1):
+                        st = lib.jpeg_amd_region_window(C.byref(L), cosited, C.byref(r), w)
+                        assert st == want, (L.width, L.height, p, dx, dy, cosited, list(L.factor_x), list(L.factor_y),
+                                            L.scale_x, L.scale_y)
+                    accepted += want == 0
+        finally:
+            L.units_x[p], L.units_y[p] = ux, uy
+    return accepted
+
+
+def test_planes_must_cover_the_image():
+    rng = np.random.default_rng(4190)
+    accepted = total = 0
+    layouts = []
+    for it in range(600):                     # the layouts of test_window_of_random_layouts
+        n = 1 if rng.random() < 0.3 else 3
+        factors = [(int(rng.integers(1, 5)), int(rng.integers(1, 5))) for _ in range(n)]
+        scale = None
+        if n == 3 and rng.random() < 0.2:
+            scale = (max(max(f[0] for f in factors), int(rng.integers(1, 5))),
+                     max(max(f[1] for f in factors), int(rng.integers(1, 5))))
+        layouts.append(_layout(int(rng.integers(1, 301)), int(rng.integers(1, 301)), factors, scale))
+    for W, H in ((17, 33), (31, 15), (47, 1), (1, 47), (161, 97), (8, 8), (16, 16), (9, 9)):   # ... and of the edge test
+        for factors in ([(2, 2), (1, 1), (1, 1)], [(2, 1), (1, 1), (1, 1)], [(1, 2), (1, 1), (1, 1)], [(1, 1)] * 3,
+                        [(4, 2), (1, 1), (2, 1)], [(1, 1)]):
+            layouts.append(_layout(W, H, factors))
+    for L in layouts:
+        accepted += _check_cover(L)
+        total += 9 * L.nplanes
+    assert 0 < accepted < total               # the sweep sees both answers
+
+
 def test_python_wrapper():
     layout = J.Layout("ycc8", {1: ((2, 2), 0), 2: ((1, 1), 1), 3: ((1, 1), 1)})
     got = J.region_window((100, 60), layout, (17, 9, 30, 20))

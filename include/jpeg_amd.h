@@ -559,6 +559,70 @@ int jpeg_amd_decode_region(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, con
 int jpeg_amd_region_window(const jpeg_amd_layout *layout, int cosited, const jpeg_amd_region *region,
                            jpeg_amd_region windows[JPEG_AMD_MAX_PLANES]);
 
+/* ---- scaled decode: 1/2, 1/4 and 1/8 size pixels straight from the coefficients -------------------
+ * The reference has no scaled decode; this is its own transform with the odd half and the upper coefficients deleted,
+ * followed by its own interleave and colour stage.  THE CONTRACT (the one statement of it):
+ *
+ * denom in {1, 2, 4, 8}, N = 8 / denom.  The image becomes (W', H') = (ceil(W N / 8), ceil(H N / 8)) pixels; plane p
+ * becomes N units_x[p] x N units_y[p] samples, N x N per block.
+ *
+ * Table, for k, h < N:  q_N[h][k] = (rN[k] * rN[h]) * (0x1p-3 * Float(Q[z(k, h)])), left-associative like
+ * Spectral.Plane.modulate (decode.swift:3984-4017), with rN[i] = r[8 i / N] of the reference's vector:
+ * r4 = {1, 1.306562965, 1, 0.541196100}, r2 = {1, 1}, r1 = {1}.  The scale stays 0x1p-3 for every N: the N / 8 of the
+ * size change and the 1 / N of the N-point transform cancel against the reference's 1 / 8.
+ *
+ * Butterfly over the inputs h[0 .. N-1] along the transformed axis; every statement is ONE binary32 operation, nothing
+ * is contracted:
+ *   N = 4 (idct8's even half, decode.swift:4042-4093, with h[0], h[1], h[2], h[3] in the places of its h0, h2, h4, h6):
+ *     e = shift + h[0];  a0 = e + h[2];  a1 = e - h[2];  b = h[1] + h[3];  c = 1.414213562 * (h[1] - h[3]) - b;
+ *     g = (a0 + b, a1 + c, a1 - c, a0 - b)
+ *   N = 2:  e = shift + h[0];  g = (e + h[1], e - h[1])
+ *   N = 1:  g = (shift + h[0])
+ *
+ * Passes, as Spectral.Plane.idct (decode.swift:4101-4133): the first over the vertical frequency of each column k < N
+ * with no shift, the second over the horizontal frequency of each row with shift = level = 2^(P-1) + 0.5; then clamp to
+ * [0, 2^P - 1] and truncate.  Coefficients with k >= N or h >= N are not read.  Against the textbook form -- (N / 8) x
+ * the orthonormal N-point 2-D IDCT of the top-left N x N dequantised coefficients, plus level, clamped, truncated -- a
+ * sample differs by at most one level, and only where that value lies at an integer boundary.
+ *
+ * Interleave and colour: Planar.interleaved(cosite:) and Rectangular.unpack(as:) (decode.swift:4182-4276,
+ * jpeg.swift:343-354, 441-478) unchanged, at the image size (W', H'), with the padded plane's edge last = N units - 1 in
+ * the place of 8 units - 1: direct planes, the centred and cosited (a, b, c), the fraction clamp, the two-step bilinear
+ * sum, .rounded(), YCbCr.rgb and the clamping byte conversion are the reference's.  Pixel W' - 1 never indexes past
+ * N units - 1 where units = ceil(W f / (8 s)):  W' - 1 < W N / 8, so its cosited index f (W' - 1) / s < N W f / (8 s) <=
+ * N units; the centred index (f - s + 2 f t) / (2 s) = f t / s + (f - s) / (2 s) <= f t / s is no larger (f <= s).  A
+ * direct plane reads sample t <= W' - 1 <= N units - 1 because 8 units >= W.  (Planes given with other units must cover
+ * the scaled image in the same sense, else EINVAL.)
+ *
+ * denom == 1 is jpeg_amd_decode_batch itself: the same call, the same bytes.  Everything else follows
+ * jpeg_amd_decode_batch: 8-bit only (else ENOSUP), 1 or 3 planes, at most 65 535 images, n_images == 0 is OK; everything
+ * is validated before anything is enqueued and on EINVAL nothing is written.  Any other denom is EINVAL.
+ * Image i at d_pixels + i * pixel_stride: H' rows of 3 W' bytes; pixel_stride >= 3 W' H' (any value, 0 included, when
+ * n_images == 1); bytes in the stride gaps are left alone.
+ * Cost: the layouts of the fused decode (y8; ycc8 with full-factor luma and chroma at 1x or 2x per axis, centred) take
+ * one launch that fetches only the head of each block (half of it at denom 2, 16 bytes at denom 4, 2 bytes at denom 8).
+ * Other layouts (cosited, factors 3 or 4, ...) transform every plane into context scratch, padded to whole blocks by edge
+ * replication, and run the staged interleave kernel under jpeg_amd_scaled_layout's layout. */
+int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, int denom,
+                                 uint8_t *d_pixels, size_t pixel_stride);
+/* single image, host tables */
+int jpeg_amd_decode_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color, int denom,
+                           uint8_t *d_pixels);
+/* Host only.  The layout of the scaled image as the staged calls see it: (W', H'), the same precision, factors, scale and
+ * tables, units ceil(N units / 8) -- the scaled planes padded to whole 8 x 8 blocks.  Padded by EDGE REPLICATION (sample
+ * (x, y) of the padding = sample (min(x, N units_x - 1), min(y, N units_y - 1))) they give, through
+ * jpeg_amd_planar_interleaved and jpeg_amd_rectangular_unpack under this layout, the contract's pixels: replication makes
+ * min(i + 1, 8 units' - 1) read the value min(i + 1, N units - 1) reads.  EINVAL for a denom not in {1, 2, 4, 8}. */
+int jpeg_amd_scaled_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out);
+/* The staged form of the transform alone (single image, host tables, any precision): d_planes[p] is the scaled plane p
+ * as uint16 [8 units_y'][8 units_x'] under jpeg_amd_scaled_layout's units, edge-replicated as described there. */
+int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                                  const uint16_t *h_quanta, int ntables, int denom, uint16_t *const d_planes[]);
+
 #ifdef __cplusplus
 }
 #endif

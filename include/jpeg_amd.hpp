@@ -302,6 +302,18 @@ class spectral {
                               cosite ? 1 : 0, (jpeg_amd_color)target, px.data()), "jpeg_amd_decode");
         return px.host();
     }
+    /// the image at 1 / denom size (denom 1 | 2 | 4 | 8) straight from the coefficients: H' * W' colours of 3 bytes,
+    /// (W', H') = (ceil(W N / 8), ceil(H N / 8)), N = 8 / denom (jpeg_amd.h, "scaled decode")
+    std::vector<uint8_t> decode_scaled(color target, int denom, bool cosite = false) const
+    {
+        jpeg_amd_layout l = lay.c_layout(size, units, q), s;
+        check(jpeg_amd_scaled_layout(&l, denom, &s), "jpeg_amd_scaled_layout");
+        device_array<uint8_t> px(*ctx, (size_t)3 * s.width * s.height);
+        auto in = detail::pointers(planes);
+        check(jpeg_amd_decode_scaled(ctx->handle(), &l, const_cast<const int16_t *const *>(in.data()), tables.data(), ntables(),
+                                     cosite ? 1 : 0, (jpeg_amd_color)target, denom, px.data()), "jpeg_amd_decode_scaled");
+        return px.host();
+    }
 
     /// Spectral.decompress(stream:) (decode.swift:3728): a JPEG file's bytes -> coefficient planes
     /// in HBM; the entropy decoding runs on the host inside the library.  Component c gets quanta

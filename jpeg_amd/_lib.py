@@ -118,6 +118,11 @@ SIGNATURES = {
                                                C.c_size_t]),
     "jpeg_amd_decode_region": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
     "jpeg_amd_region_window": (C.c_int, [_L, C.c_int, _p, _p]),
+    "jpeg_amd_decode_scaled_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _p,
+                                               C.c_size_t]),
+    "jpeg_amd_decode_scaled": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
+    "jpeg_amd_scaled_layout": (C.c_int, [_L, C.c_int, _L]),
+    "jpeg_amd_spectral_idct_scaled": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, _pp]),
 }
 
 

@@ -234,12 +234,23 @@ class Spectral:
             "jpeg_amd_spectral_rectangular", self.ctx.handle)
         return Rectangular(self.ctx, self.size, self.layout, out.view(H, W, self.layout.count))
 
-    def decode(self, color=RGB, cosite: bool = False, region=None):
+    def decode(self, color=RGB, cosite: bool = False, region=None, scale: int = 1):
         """Fused idct().interleaved(cosite:).unpack(as:) -> uint8 tensor [H*W, 3].  region (x, y, width, height) in pixels,
-        any alignment: the same decode cropped to it, bit for bit, as [height*width, 3] (jpeg_amd_decode_region)."""
+        any alignment: the same decode cropped to it, bit for bit, as [height*width, 3] (jpeg_amd_decode_region).
+        scale: the scale denominator 1 | 2 | 4 | 8: the image at 1/scale size straight from the coefficients, as
+        [H'*W', 3] with (W', H') = scaled_size(size, scale) (jpeg_amd_decode_scaled).  Not together with region."""
         torch = _torch()
         L = self._layout()
         qarr, qptr = _quanta_array(self.quanta)
+        if scale != 1:
+            if region is not None:
+                raise ValueError("region together with scale != 1 is out of scope")
+            w, h = scaled_size(self.size, scale)
+            out = self.ctx.empty(w * h * 3, torch.uint8)
+            _lib.check(_lib.lib().jpeg_amd_decode_scaled(
+                self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
+                1 if cosite else 0, color.code, int(scale), out.data_ptr()), "jpeg_amd_decode_scaled", self.ctx.handle)
+            return out.view(-1, 3)
         if region is not None:
             reg = _region(region)
             r = reg._obj
@@ -557,6 +568,43 @@ def decode_regions(ctx: Context, size, layout: Layout, planes, quanta, regions, 
         int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_regions, out.data_ptr(), stride),
         "jpeg_amd_decode_region_batch", ctx.handle)
     return [out[i * stride:i * stride + areas[i]].view(int(regs[i, 3]), int(regs[i, 2]), 3) for i in range(n)]
+
+
+def scaled_size(size, denom: int) -> Tuple[int, int]:
+    """(W', H') = (ceil(W N / 8), ceil(H N / 8)), N = 8 / denom: the size of a scaled decode (jpeg_amd_scaled_layout)."""
+    if denom not in (1, 2, 4, 8):
+        raise ValueError("denom: 1, 2, 4 or 8")
+    n = 8 // denom
+    return (int(size[0]) * n + 7) // 8, (int(size[1]) * n + 7) // 8
+
+
+def decode_scaled(ctx: Context, size, layout: Layout, planes, quanta, denom: int, q: Optional[Sequence[int]] = None, color=RGB,
+                  cosite: bool = False):
+    """Decode n images of one layout at 1/denom size in one call (jpeg_amd_decode_scaled_batch).  planes[p]: device int16
+    [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or device).  Returns one uint8 tensor [n, H', W', 3]."""
+    torch = _torch()
+    q = list(q) if q is not None else _dedupe_q(layout)
+    planes = list(planes)
+    if len(planes) != layout.count or len(q) != layout.count:
+        raise ValueError("plane count does not match layout")
+    n = int(planes[0].shape[0]) if planes and planes[0].dim() == 4 else -1
+    for p in planes:
+        if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
+            raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
+    units = [(int(p.shape[2]), int(p.shape[1])) for p in planes]
+    if isinstance(quanta, np.ndarray):
+        quanta = ctx.upload(np.asarray(quanta, np.uint16))
+    if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
+        raise ValueError("quanta: [n, ntables, 64]")
+    w, h = scaled_size(size, denom)
+    L = layout.c_layout(size, units, q)
+    stride = 3 * w * h
+    out = ctx.empty(n * stride, torch.uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_scaled_batch(
+        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
+        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, int(denom), out.data_ptr(), stride),
+        "jpeg_amd_decode_scaled_batch", ctx.handle)
+    return out.view(n, h, w, 3)
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

@@ -805,6 +805,132 @@ int jpeg_amd_region_window(const jpeg_amd_layout *L, int cosited, const jpeg_amd
     return JPEG_AMD_OK;
 }
 
+namespace {
+
+// N = 8 / denom for a denom of the contract, else 0.
+int scaled_n(int denom) { return denom == 1 || denom == 2 || denom == 4 || denom == 8 ? 8 / denom : 0; }
+
+// The planes, N x N samples per block, must cover the scaled image as check_planes_cover_image asks of the full-size one:
+// with units = ceil(size factor / (8 scale)) they always do (include/jpeg_amd.h has the proof); units given by hand may not.
+int check_planes_cover_scaled(const jpeg_amd_layout *L, const jpeg_amd_layout *S, int n)
+{
+    for (int p = 0; p < L->nplanes; ++p) {
+        const long long sx = (long long)n * L->units_x[p], sy = (long long)n * L->units_y[p];
+        if (plane_is_direct(*L, p)) {
+            if (sx < S->width || sy < S->height) return JPEG_AMD_EINVAL;
+        } else {
+            if (sx < 1 || sy < 1) return JPEG_AMD_EINVAL;
+            if (axis_index(interleave_axis(*L, p, true, false), S->width - 1) >= sx) return JPEG_AMD_EINVAL;
+            if (axis_index(interleave_axis(*L, p, true, true), S->height - 1) >= sy) return JPEG_AMD_EINVAL;
+        }
+    }
+    return JPEG_AMD_OK;
+}
+
+constexpr size_t kScaledFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's planes
+
+}  // namespace
+
+int jpeg_amd_scaled_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out)
+{
+    if (!out) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(in, -1));
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout s = *in;
+    s.width = (int32_t)(((long long)in->width * n + 7) / 8);
+    s.height = (int32_t)(((long long)in->height * n + 7) / 8);
+    for (int p = 0; p < in->nplanes; ++p) {
+        s.units_x[p] = (int32_t)(((long long)in->units_x[p] * n + 7) / 8);
+        s.units_y[p] = (int32_t)(((long long)in->units_y[p] * n + 7) / 8);
+    }
+    *out = s;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, int denom,
+                                 uint8_t *d_pixels, size_t pixel_stride)
+{
+    if (denom == 1)
+        return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                     d_pixels, pixel_stride);
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, n_images, color));
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(jpeg_amd_scaled_layout(L, denom, &S));
+    JA_TRY(check_planes_cover_scaled(L, &S, n));
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
+    if (n_images > 1 && pixel_stride < (size_t)3 * S.width * S.height) return JPEG_AMD_EINVAL;
+    PlaneSet cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+    const QuantaRef q{d_quanta, quanta_stride};
+    const bool rgb = color == JPEG_AMD_COLOR_RGB8;
+    if (fused_decode_supported(*L, cosited != 0)) {
+        JA_HIP(ctx, launch_scaled_decode(ctx->stream, n_images, *L, n, S.width, S.height, cs, q, rgb, d_pixels, pixel_stride));
+        return JPEG_AMD_OK;
+    }
+
+    // fallback: every plane N x N per block into byte planes in scratch, padded to S's whole blocks by edge replication, then
+    // the staged interleave + colour kernel under S, chunk by chunk
+    const size_t per_image = std::max<size_t>(1, scratch_planes_bytes(&S, 1, sizeof(uint8_t)));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kScaledFallbackBytes / per_image));
+    PlaneSetMut scratch;
+    JA_TRY(scratch_planes(ctx, &S, chunk, sizeof(uint8_t), &scratch));
+    for (int i0 = 0; i0 < n_images; i0 += chunk) {
+        const int m = std::min(chunk, n_images - i0);
+        PlaneSet ps{};
+        for (int p = 0; p < L->nplanes; ++p) {
+            JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, m, static_cast<const int16_t *>(cs.ptr[p]) + (size_t)i0 * cs.stride[p],
+                                                 cs.stride[p], QuantaRef{d_quanta + (size_t)i0 * quanta_stride, quanta_stride}, L->qi[p],
+                                                 L->units_x[p], L->units_y[p], n, L->precision, scratch.ptr[p], scratch.stride[p], true));
+            ps.ptr[p] = scratch.ptr[p];
+            ps.stride[p] = scratch.stride[p];
+        }
+        JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, m, S, ps, true, cosited != 0, rgb ? PixelKind::RGB8 : PixelKind::YCC8,
+                                            d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+    }
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_decode_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color, int denom,
+                           uint8_t *d_pixels)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (scaled_n(denom) == 0) return JPEG_AMD_EINVAL;
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    return jpeg_amd_decode_scaled_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, denom, d_pixels, 0);
+}
+
+int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                                  const uint16_t *h_quanta, int ntables, int denom, uint16_t *const d_planes[])
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (denom == 1) return jpeg_amd_spectral_idct(ctx, L, d_coef, h_quanta, ntables, d_planes);
+    const int n = scaled_n(denom);
+    if (n == 0 || !d_coef || !d_planes) return JPEG_AMD_EINVAL;
+    for (int p = 0; p < L->nplanes; ++p)
+        if (plane_samples(L, p) != 0 && (!d_coef[p] || !d_planes[p])) return JPEG_AMD_EINVAL;
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    for (int p = 0; p < L->nplanes; ++p)
+        JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, 1, d_coef[p], 0, QuantaRef{d_q, 0}, L->qi[p], L->units_x[p], L->units_y[p], n,
+                                             L->precision, d_planes[p], 0, false));
+    return JPEG_AMD_OK;
+}
+
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,
                                    size_t desc_stride, const uint32_t *d_entries, size_t entries_stride, const uint8_t *d_skip,
                                    int16_t *const d_coef[], const size_t coef_stride[])

@@ -172,6 +172,95 @@ __device__ __forceinline__ void idct_block(const uint32_t (&w)[32], QPtr q, floa
     }
 }
 
+// ---- scaled decode: N x N samples per block, N = 8 / denom in {4, 2, 1} (include/jpeg_amd.h, "scaled decode") ------------
+// The reference's own transform with the odd half and the upper coefficients deleted: idct8's even half IS a 4-point
+// AAN butterfly with the factors r[0], r[2], r[4], r[6], and so on down to N = 1.
+
+// q_N[h][k] = (rN[k] * rN[h]) * (0x1p-3 * Float(Q[z(k, h)])) with rN[i] = r[8 i / N]: modulate_entry at the kept
+// frequencies' places in r.  `quantum` is Q[z(k, h)] of the TRUE (k, h).
+template <int N>
+__host__ __device__ inline float modulate_entry_scaled(int k, int h, uint16_t quantum)
+{
+    return modulate_entry((8 / N) * k, (8 / N) * h, 0.125f, quantum);
+}
+
+// The reduced butterflies.  N = 4: idct8 with h[0], h[1], h[2], h[3] in the places of its h0, h2, h4, h6 and the odd half
+// gone; N = 2: e +- h[1]; N = 1: e.  SHIFTED as in idct8.
+template <int N, bool SHIFTED>
+__device__ __forceinline__ void idct_scaled(const float (&h)[N], float shift, float (&g)[N])
+{
+    static_assert(N == 4 || N == 2 || N == 1, "N = 8 / denom");
+    const float e = SHIFTED ? shift + h[0] : h[0];
+    if constexpr (N == 4) {
+        const float a0 = e + h[2];
+        const float a1 = e - h[2];
+        const float b  = h[1] + h[3];
+        const float c  = 1.414213562f * (h[1] - h[3]) - b;
+        g[0] = a0 + b;
+        g[1] = a1 + c;
+        g[2] = a1 - c;
+        g[3] = a0 - b;
+    } else if constexpr (N == 2) {
+        g[0] = e + h[1];
+        g[1] = e - h[1];
+    } else {
+        g[0] = e;
+    }
+}
+
+// The head of a block that holds every coefficient with k, h < N: zigzag indices <= 24 (N = 4: four 16-byte loads, half
+// the block), <= 4 (N = 2: one 16-byte load), 0 (N = 1: one 2-byte load).  Packed dwords as load_block's.
+template <int N> constexpr int scaled_head_words() { return N == 4 ? 16 : N == 2 ? 4 : 1; }
+
+template <int N>
+__device__ __forceinline__ void load_block_head(const int16_t *src, uint32_t (&w)[scaled_head_words<N>()])
+{
+    static_assert(zigzag_of(3, 3) == 24 && zigzag_of(1, 1) == 4 && zigzag_of(0, 0) == 0, "the heads' last zigzag indices");
+    if constexpr (N == 1) {
+        w[0] = (uint32_t)(uint16_t)src[0];
+    } else {
+        const uint4 *s = reinterpret_cast<const uint4 *>(src);
+#pragma unroll
+        for (int i = 0; i < scaled_head_words<N>() / 4; ++i) {
+            const uint4 v = s[i];
+            w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+    }
+}
+
+// idct_block for N x N: first pass over the vertical frequency of each column k < N (no shift), second over the
+// horizontal frequency of each row (shift = level).  q: modulated table q[N * h + k] (modulate_entry_scaled);
+// g[N * y + x]: samples before the clamp.  Coefficients with k >= N or h >= N are not read.
+template <int N, typename QPtr>
+__device__ __forceinline__ void idct_block_scaled(const uint32_t (&w)[scaled_head_words<N>()], QPtr q, float level,
+                                                  float (&g)[N * N])
+{
+    float f[N * N];  // f[N * k + y]
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float h[N], res[N];
+#pragma unroll
+        for (int hh = 0; hh < N; ++hh) {
+            const int z = zigzag_of(k, hh);
+            const int32_t word = (int32_t)w[z >> 1];
+            const int32_t c = (z & 1) ? (word >> 16) : (int32_t)(int16_t)word;
+            h[hh] = q[N * hh + k] * (float)c;
+        }
+        idct_scaled<N, false>(h, 0.0f, res);
+#pragma unroll
+        for (int y = 0; y < N; ++y) f[N * k + y] = res[y];
+    }
+#pragma unroll
+    for (int y = 0; y < N; ++y) {
+        float r[N], res[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) r[k] = f[N * k + y];
+        idct_scaled<N, true>(r, level, res);
+#pragma unroll
+        for (int x = 0; x < N; ++x) g[N * y + x] = res[x];
+    }
+}
+
 // The same two passes, split so that a kernel can interleave other work between them and
 // produce output rows one at a time (idct_block == idct_pass1 + 8 x idct_pass2_row).
 template <typename QPtr>

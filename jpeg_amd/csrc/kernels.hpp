@@ -114,6 +114,17 @@ hipError_t launch_region_decode(hipStream_t stream, int n_images, const jpeg_amd
 hipError_t launch_region_crop(hipStream_t stream, int n_images, const uint8_t *d_full, size_t full_stride, int width,
                               const int32_t *d_regions, size_t max_bytes, uint8_t *d_pixels, size_t pixel_stride);
 
+// ---- scaled decode (kernels_scaled.hip) ------------------------------------------------
+// n = 8 / denom in {4, 2, 1}; `layout` is the FULL-SIZE image's, width x height the scaled image's (W', H').
+// The layouts of fused_decode_supported: n_images images in ONE launch (k_scaled_decode).  Image i's rows of width * 3
+// bytes, unpadded, at d_pixels + i * pixel_stride.
+hipError_t launch_scaled_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, int n, int width, int height,
+                                const PlaneSet &coef, QuantaRef q, bool rgb, uint8_t *d_pixels, size_t pixel_stride);
+// Any layout: one plane (ux x uy blocks) into n x n samples per block, uint16 or uint8, in a plane of ceil(n ux / 8) x
+// ceil(n uy / 8) whole blocks whose padding repeats the edge samples (k_idct_scaled).
+hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int16_t *d_coef, size_t coef_stride, QuantaRef q,
+                                    int qi, int ux, int uy, int n, int precision, void *d_plane, size_t plane_stride, bool out_u8);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

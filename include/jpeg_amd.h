@@ -623,6 +623,59 @@ int jpeg_amd_scaled_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout
 int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
                                   const uint16_t *h_quanta, int ntables, int denom, uint16_t *const d_planes[]);
 
+/* ---- view decode: a rectangle of the scaled image, a denominator and a rectangle per image ----------
+ * A view is a denominator and a rectangle in pixels of the image that denominator gives. */
+typedef struct jpeg_amd_view {
+    int32_t denom;
+    jpeg_amd_region region;
+} jpeg_amd_view;
+
+/* Image i of the output is THE IMAGE THAT jpeg_amd_decode_scaled_batch DEFINES FOR views[i].denom, CROPPED TO
+ * views[i].region, bit for bit.  Nothing is defined here arithmetically: the scaled contract above (tables, reduced
+ * butterflies, last = N units - 1, the reference's interleave and colour stage at size (W', H')) is the contract.  For
+ * denom == 1 that image is jpeg_amd_decode_batch's, and the view is exactly a region of jpeg_amd_decode_region_batch.
+ *
+ * denom in {1, 2, 4, 8}, N = 8 / denom, else EINVAL.  The region is in pixels of the scaled image (W', H') =
+ * (ceil(W N / 8), ceil(H N / 8)), any alignment: x, y >= 0, width, height > 0, x + width <= W', y + height <= H', else
+ * EINVAL.  Output image i at d_pixels + i * pixel_stride: region.height rows of region.width * 3 bytes, no padding between
+ * rows; pixel_stride >= 3 * width_i * height_i for every i (any value, 0 included, when n_images == 1); bytes in the stride
+ * gaps are left alone.  h_views is a HOST array of n_images views, any mix of denominators; the call copies it before it
+ * returns, as h_regions.  Every view is validated before anything is enqueued: on EINVAL nothing is written and the context
+ * stays usable.  Everything else as jpeg_amd_decode_batch: 8-bit only (else ENOSUP), 1 or 3 planes, at most 65 535 images,
+ * n_images == 0 is OK.
+ * Cost: for the layouts of the fused decode (y8; ycc8 with full-factor luma and chroma at 1x or 2x per axis, centred) one
+ * launch per distinct denominator of the call, four at most, each over the images of that denominator; a view reads only
+ * the heads of the blocks of its window (jpeg_amd_view_window) and writes only its pixels.  Other layouts (cosited, factors
+ * 3 or 4, ...) decode the WHOLE scaled images into context scratch -- run by run of consecutive images of one denominator,
+ * in chunks of at most 1 GiB -- and crop: correct, but as costly as the scaled decode of every image.  A call whose views
+ * are all whole images at one denominator is jpeg_amd_decode_scaled_batch (jpeg_amd_decode_batch at denominator 1); one
+ * whose denominators are all 1 is jpeg_amd_decode_region_batch. */
+int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                               const int16_t *const d_coef[], const size_t coef_stride[],
+                               const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                               int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                               uint8_t *d_pixels, size_t pixel_stride);
+/* single image, host tables */
+int jpeg_amd_decode_view(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                         const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                         const jpeg_amd_view *view, uint8_t *d_pixels);
+/* Host only.  jpeg_amd_region_window for a view: windows[p] (in BLOCKS of plane p, for p < nplanes; the rest are zeroed)
+ * is the smallest block rectangle that holds every sample of the scaled plane p -- N x N per block -- that the contract
+ * reads for some pixel of `region` of the image at `denom`: N in the place of 8, N units - 1 as the padded edge,
+ * zero-weight neighbours included.  At denom 1 it is jpeg_amd_region_window.  EINVAL for a denom not in {1, 2, 4, 8}, a
+ * region outside (W', H'), or a layout whose planes do not cover the scaled image. */
+int jpeg_amd_view_window(const jpeg_amd_layout *layout, int cosited, int denom, const jpeg_amd_region *region,
+                         jpeg_amd_region windows[JPEG_AMD_MAX_PLANES]);
+/* Host only.  The smallest rectangle of the image at `denom` that covers `source_region`, a rectangle in pixels of the
+ * full-size image (scaled pixel x' stands for the source pixels [8 x' / N, 8 (x' + 1) / N)):  x' = floor(x N / 8),
+ * x1' = min(W', ceil((x + width) N / 8)), the same for y.  EINVAL for a source rectangle outside the image. */
+int jpeg_amd_view_of_source(const jpeg_amd_layout *layout, int denom, const jpeg_amd_region *source_region,
+                            jpeg_amd_region *region);
+/* Host only, pure.  The largest denom in {8, 4, 2, 1} with floor(src_w N / 8) >= want_w and floor(src_h N / 8) >= want_h
+ * (N = 8 / denom), 1 if none: the cheapest reduction of a src_w x src_h source rectangle that still needs no upscaling
+ * to reach want_w x want_h. */
+int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t want_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -314,6 +314,18 @@ class spectral {
                                      cosite ? 1 : 0, (jpeg_amd_color)target, denom, px.data()), "jpeg_amd_decode_scaled");
         return px.host();
     }
+    /// decode_scaled(target, view.denom, cosite) cropped to view.region, a rectangle in pixels of that scaled image, bit for
+    /// bit: region.height * region.width colours of 3 bytes (jpeg_amd.h, "view decode")
+    std::vector<uint8_t> decode_view(color target, const jpeg_amd_view &view, bool cosite = false) const
+    {
+        jpeg_amd_layout l = lay.c_layout(size, units, q);
+        const size_t w = view.region.width > 0 ? view.region.width : 0, h = view.region.height > 0 ? view.region.height : 0;
+        device_array<uint8_t> px(*ctx, 3 * w * h);
+        auto in = detail::pointers(planes);
+        check(jpeg_amd_decode_view(ctx->handle(), &l, const_cast<const int16_t *const *>(in.data()), tables.data(), ntables(),
+                                   cosite ? 1 : 0, (jpeg_amd_color)target, &view, px.data()), "jpeg_amd_decode_view");
+        return px.host();
+    }
 
     /// Spectral.decompress(stream:) (decode.swift:3728): a JPEG file's bytes -> coefficient planes
     /// in HBM; the entropy decoding runs on the host inside the library.  Component c gets quanta

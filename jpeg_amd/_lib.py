@@ -123,12 +123,23 @@ SIGNATURES = {
     "jpeg_amd_decode_scaled": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     "jpeg_amd_scaled_layout": (C.c_int, [_L, C.c_int, _L]),
     "jpeg_amd_spectral_idct_scaled": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, _pp]),
+    "jpeg_amd_decode_view_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, _p,
+                                             C.c_size_t]),
+    "jpeg_amd_decode_view": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "jpeg_amd_view_window": (C.c_int, [_L, C.c_int, C.c_int, _p, _p]),
+    "jpeg_amd_view_of_source": (C.c_int, [_L, C.c_int, _p, _p]),
+    "jpeg_amd_view_denom": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 
 class Region(C.Structure):
     """struct jpeg_amd_region"""
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class View(C.Structure):
+    """struct jpeg_amd_view"""
+    _fields_ = [("denom", C.c_int32), ("region", Region)]
 
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V

@@ -238,13 +238,14 @@ class Spectral:
         """Fused idct().interleaved(cosite:).unpack(as:) -> uint8 tensor [H*W, 3].  region (x, y, width, height) in pixels,
         any alignment: the same decode cropped to it, bit for bit, as [height*width, 3] (jpeg_amd_decode_region).
         scale: the scale denominator 1 | 2 | 4 | 8: the image at 1/scale size straight from the coefficients, as
-        [H'*W', 3] with (W', H') = scaled_size(size, scale) (jpeg_amd_decode_scaled).  Not together with region."""
+        [H'*W', 3] with (W', H') = scaled_size(size, scale) (jpeg_amd_decode_scaled).  Not together with region: a region of
+        the scaled image is Spectral.view."""
         torch = _torch()
         L = self._layout()
         qarr, qptr = _quanta_array(self.quanta)
         if scale != 1:
             if region is not None:
-                raise ValueError("region together with scale != 1 is out of scope")
+                raise ValueError("region together with scale != 1: use Spectral.view")
             w, h = scaled_size(self.size, scale)
             out = self.ctx.empty(w * h * 3, torch.uint8)
             _lib.check(_lib.lib().jpeg_amd_decode_scaled(
@@ -264,6 +265,21 @@ class Spectral:
             self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
             1 if cosite else 0, color.code, out.data_ptr()), "jpeg_amd_decode", self.ctx.handle)
         return out.view(-1, 3)
+
+    def view(self, region, scale: int, color=RGB, cosite: bool = False):
+        """The image at 1/scale size (scale 1 | 2 | 4 | 8, as decode(scale=)) cropped to region (x, y, width, height) in
+        pixels of THAT image, any alignment, bit for bit, as uint8 [height, width, 3] (jpeg_amd_decode_view).  view_of_source
+        turns a rectangle of the full-size image into such a region, view_denom picks the scale for a target size."""
+        torch = _torch()
+        L = self._layout()
+        qarr, qptr = _quanta_array(self.quanta)
+        v = _view(scale, region)
+        w, h = max(v.region.width, 0), max(v.region.height, 0)
+        out = self.ctx.empty(w * h * 3, torch.uint8)
+        _lib.check(_lib.lib().jpeg_amd_decode_view(
+            self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
+            1 if cosite else 0, color.code, C.byref(v), out.data_ptr()), "jpeg_amd_decode_view", self.ctx.handle)
+        return out.view(h, w, 3)
 
     def host_planes(self) -> List[np.ndarray]:
         return [p.cpu().numpy() for p in self.planes]
@@ -489,6 +505,13 @@ def _region(region):
     return C.byref(r)
 
 
+def _view(denom, region) -> "_lib.View":
+    v = _lib.View()
+    v.denom = int(denom)
+    v.region.x, v.region.y, v.region.width, v.region.height = (int(t) for t in region)
+    return v
+
+
 def transform_quanta(op, table) -> np.ndarray:
     """q_out[z] = q_in[m(z)] (jpeg_amd_transform_quanta)."""
     t = np.ascontiguousarray(np.asarray(table, np.uint16).reshape(64))
@@ -605,6 +628,66 @@ def decode_scaled(ctx: Context, size, layout: Layout, planes, quanta, denom: int
         int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, int(denom), out.data_ptr(), stride),
         "jpeg_amd_decode_scaled_batch", ctx.handle)
     return out.view(n, h, w, 3)
+
+
+def view_window(size, layout: Layout, denom: int, region, cosite: bool = False, units=None) -> List[Tuple[int, int, int, int]]:
+    """region_window for a view: the block window of every plane that the pixels of `region` of the image at 1/denom size
+    read (jpeg_amd_view_window); of each block only the head of the scaled decode."""
+    L = layout.c_layout(size, units)
+    w = (_lib.Region * MAX_PLANES)()
+    _lib.check(_lib.lib().jpeg_amd_view_window(C.byref(L), 1 if cosite else 0, int(denom), _region(region), w), "jpeg_amd_view_window")
+    return [(w[p].x, w[p].y, w[p].width, w[p].height) for p in range(layout.count)]
+
+
+def view_of_source(size, denom: int, source_region) -> Tuple[int, int, int, int]:
+    """The smallest rectangle of the image at 1/denom size that covers `source_region`, a rectangle in pixels of the
+    full-size image (jpeg_amd_view_of_source)."""
+    L = _lib.Layout()
+    L.width, L.height, L.precision, L.nplanes = int(size[0]), int(size[1]), 8, 1
+    L.scale_x = L.scale_y = L.factor_x[0] = L.factor_y[0] = 1
+    r = _lib.Region()
+    _lib.check(_lib.lib().jpeg_amd_view_of_source(C.byref(L), int(denom), _region(source_region), C.byref(r)), "jpeg_amd_view_of_source")
+    return r.x, r.y, r.width, r.height
+
+
+def view_denom(source_size, want_size) -> int:
+    """The largest denominator in (8, 4, 2, 1) at which a source rectangle of source_size (w, h) is still at least
+    want_size (w, h): the cheapest view that needs no upscaling (jpeg_amd_view_denom)."""
+    return int(_lib.lib().jpeg_amd_view_denom(int(source_size[0]), int(source_size[1]), int(want_size[0]), int(want_size[1])))
+
+
+def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: Optional[Sequence[int]] = None, color=RGB,
+                 cosite: bool = False):
+    """Decode n images of one layout, each at its own denominator and cropped to its own rectangle of that scaled image, in
+    one call (jpeg_amd_decode_view_batch).  planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or
+    device); views: [n, 5] of (denom, x, y, width, height).  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+    torch = _torch()
+    vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
+    n = vs.shape[0]
+    q = list(q) if q is not None else _dedupe_q(layout)
+    planes = list(planes)
+    if len(planes) != layout.count or len(q) != layout.count:
+        raise ValueError("plane count does not match layout")
+    for p in planes:
+        if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
+            raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
+    units = [(int(p.shape[2]), int(p.shape[1])) for p in planes]
+    if isinstance(quanta, np.ndarray):
+        quanta = ctx.upload(np.asarray(quanta, np.uint16))
+    if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
+        raise ValueError("quanta: [n, ntables, 64]")
+    L = layout.c_layout(size, units, q)
+    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
+    stride = max(areas)
+    out = ctx.empty(n * stride, torch.uint8)
+    h_views = (_lib.View * max(n, 1))()
+    for i, row in enumerate(vs.tolist()):
+        h_views[i] = _view(row[0], row[1:])
+    _lib.check(_lib.lib().jpeg_amd_decode_view_batch(
+        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
+        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, out.data_ptr(), stride),
+        "jpeg_amd_decode_view_batch", ctx.handle)
+    return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

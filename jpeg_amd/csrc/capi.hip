@@ -34,7 +34,7 @@ struct jpeg_amd_ctx {
     uint16_t *d_qstage = nullptr;  // ring of staged host tables
     uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
     int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
-    void *d_region = nullptr;      // staged regions + tile prefix of jpeg_amd_decode_region_batch (grown on demand)
+    void *d_region = nullptr;      // staged regions + tile prefix of jpeg_amd_decode_region_batch / _view_batch (grown on demand)
     size_t region_bytes = 0;
     int qslot = 0;
     int last_hip = 0;
@@ -678,6 +678,26 @@ bool whole_image(const jpeg_amd_layout *L, const jpeg_amd_region &r)
     return r.x == 0 && r.y == 0 && r.width == L->width && r.height == L->height;
 }
 
+// `buf` into the context's region buffer (grown on demand), one copy from a host buffer (pageable, so the copy has taken
+// it when the call returns -- as stage_quanta).
+int upload_regions(jpeg_amd_ctx *ctx, const std::vector<uint32_t> &buf)
+{
+    const size_t bytes = 4 * buf.size();
+    if (bytes > ctx->region_bytes) {
+        if (ctx->d_region) {
+            JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still read it
+            JA_HIP(ctx, hipFree(ctx->d_region));
+            ctx->d_region = nullptr;
+            ctx->region_bytes = 0;
+        }
+        const size_t want = bytes + bytes / 8 + 4096;
+        JA_HIP(ctx, hipMalloc(&ctx->d_region, want));
+        ctx->region_bytes = want;
+    }
+    JA_HIP(ctx, hipMemcpyAsync(ctx->d_region, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    return JPEG_AMD_OK;
+}
+
 // The regions (int32 [n][4]) and their tile prefix (uint32 [n + 1]) in the context's region buffer, one copy from a host
 // buffer (pageable, so the copy has taken it when the call returns -- as stage_quanta).  Returns the workgroup count.
 int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int32_t **d_regions, const uint32_t **d_tiles,
@@ -692,18 +712,7 @@ int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int3
         acc += region_tiles(h[i]);
     }
     buf[4 * (size_t)n + n] = acc;
-    if (bytes > ctx->region_bytes) {
-        if (ctx->d_region) {
-            JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still read it
-            JA_HIP(ctx, hipFree(ctx->d_region));
-            ctx->d_region = nullptr;
-            ctx->region_bytes = 0;
-        }
-        const size_t want = bytes + bytes / 8 + 4096;
-        JA_HIP(ctx, hipMalloc(&ctx->d_region, want));
-        ctx->region_bytes = want;
-    }
-    JA_HIP(ctx, hipMemcpyAsync(ctx->d_region, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(upload_regions(ctx, buf));
     *d_regions = static_cast<const int32_t *>(ctx->d_region);
     *d_tiles = reinterpret_cast<const uint32_t *>(static_cast<const int32_t *>(ctx->d_region) + 4 * (size_t)n);
     *nwg = acc;
@@ -929,6 +938,201 @@ int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, c
         JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, 1, d_coef[p], 0, QuantaRef{d_q, 0}, L->qi[p], L->units_x[p], L->units_y[p], n,
                                              L->precision, d_planes[p], 0, false));
     return JPEG_AMD_OK;
+}
+
+namespace {
+
+constexpr int kViewDenoms = 4;   // slot k: denom 1 << k
+int view_slot(int denom) { return denom == 1 ? 0 : denom == 2 ? 1 : denom == 4 ? 2 : denom == 8 ? 3 : -1; }
+
+// The image at `denom` as the scaled contract defines it: *S is jpeg_amd_scaled_layout's, and the planes cover it.
+int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
+{
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    JA_TRY(jpeg_amd_scaled_layout(L, denom, S));
+    return denom == 1 ? JPEG_AMD_OK : check_planes_cover_scaled(L, S, n);
+}
+
+constexpr size_t kViewFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's whole-image decodes
+
+}  // namespace
+
+int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                               const int16_t *const d_coef[], const size_t coef_stride[],
+                               const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                               int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                               uint8_t *d_pixels, size_t pixel_stride)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, n_images, color));
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    if (n_images > 0) {
+        if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_views) return JPEG_AMD_EINVAL;
+        JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+        for (int i = 0; i < n_images; ++i) {
+            const int k = view_slot(h_views[i].denom);
+            if (k < 0) return JPEG_AMD_EINVAL;
+            if (count[k]++ == 0) JA_TRY(scaled_image(L, h_views[i].denom, &S[k]));
+            const jpeg_amd_region &r = h_views[i].region;
+            JA_TRY(check_region(&S[k], r));
+            if (n_images > 1 && pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
+            whole = whole && whole_image(&S[k], r);
+        }
+    }
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+
+    const int denom0 = h_views[0].denom;
+    if (whole && count[view_slot(denom0)] == n_images)
+        return jpeg_amd_decode_scaled_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            denom0, d_pixels, pixel_stride);
+    if (count[0] == n_images) {   // every view a region of the full-size image
+        std::vector<jpeg_amd_region> regions((size_t)n_images);
+        for (int i = 0; i < n_images; ++i) regions[(size_t)i] = h_views[i].region;
+        return jpeg_amd_decode_region_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            regions.data(), d_pixels, pixel_stride);
+    }
+
+    const size_t n = (size_t)n_images;
+    if (fused_decode_supported(*L, cosited != 0)) {
+        // staged in one copy: the rectangles [n][4], then per denominator of the call its index list [m] and tile prefix [m + 1]
+        std::vector<uint32_t> buf(4 * n);
+        for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
+        size_t at[kViewDenoms];
+        uint32_t nwg[kViewDenoms];
+        for (int k = 0; k < kViewDenoms; ++k) {
+            at[k] = buf.size();
+            nwg[k] = 0;
+            if (count[k] == 0) continue;
+            for (size_t i = 0; i < n; ++i)
+                if (view_slot(h_views[i].denom) == k) buf.push_back((uint32_t)i);
+            uint64_t acc = 0;
+            for (size_t i = 0; i < n; ++i) {
+                if (view_slot(h_views[i].denom) != k) continue;
+                buf.push_back((uint32_t)acc);
+                acc += view_tiles(8 >> k, h_views[i].region);
+            }
+            if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
+            buf.push_back((uint32_t)acc);
+            nwg[k] = (uint32_t)acc;
+        }
+        JA_TRY(upload_regions(ctx, buf));
+        const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->d_region);
+        for (int k = 0; k < kViewDenoms; ++k) {
+            if (count[k] == 0) continue;
+            JA_HIP(ctx, launch_view_decode(ctx->stream, count[k], *L, 8 >> k, cs, QuantaRef{d_quanta, quanta_stride},
+                                           color == JPEG_AMD_COLOR_RGB8, d_buf + at[k], d_buf + at[k] + count[k],
+                                           reinterpret_cast<const int32_t *>(d_buf), nwg[k], d_pixels, pixel_stride));
+        }
+        return JPEG_AMD_OK;
+    }
+
+    // fallback: the whole scaled images of a run of consecutive images of one denominator into scratch behind the staged
+    // paths' planes (S's planes are no larger than L's), then one crop launch; a run is at most a chunk
+    size_t full_max = 0;
+    for (int k = 0; k < kViewDenoms; ++k)
+        if (count[k]) full_max = std::max(full_max, (size_t)3 * S[k].width * S[k].height);
+    const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kViewFallbackBytes / per_image));
+    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
+    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full_max * chunk)));
+    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;
+    std::vector<uint32_t> buf(4 * n);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
+    JA_TRY(upload_regions(ctx, buf));
+    const int32_t *d_regions = static_cast<const int32_t *>(ctx->d_region);
+    for (int i0 = 0; i0 < n_images;) {
+        const int denom = h_views[i0].denom;
+        const jpeg_amd_layout &Sd = S[view_slot(denom)];
+        int m = 0;
+        size_t max_bytes = 0;
+        for (; i0 + m < n_images && m < chunk && h_views[i0 + m].denom == denom; ++m)
+            max_bytes = std::max(max_bytes, (size_t)3 * h_views[i0 + m].region.width * h_views[i0 + m].region.height);
+        const size_t full = (size_t)3 * Sd.width * Sd.height;
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
+        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
+                                            cosited, color, denom, d_full, full));
+        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes,
+                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+        i0 += m;
+    }
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_view(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                         const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                         const jpeg_amd_view *view, uint8_t *d_pixels)
+{
+    // as the batch call: what can be refused is refused before a table is staged
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, 1, color));
+    if (!view) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, view->denom, &S));
+    JA_TRY(check_region(&S, view->region));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    return jpeg_amd_decode_view_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, view, d_pixels, 0);
+}
+
+int jpeg_amd_view_window(const jpeg_amd_layout *L, int cosited, int denom, const jpeg_amd_region *region,
+                         jpeg_amd_region windows[JPEG_AMD_MAX_PLANES])
+{
+    if (!region || !windows) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    JA_TRY(check_planes_cover_image(L));
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, denom, &S));
+    JA_TRY(check_region(&S, *region));
+    const jpeg_amd_region &r = *region;
+    const int32_t n = scaled_n(denom);
+    for (int p = 0; p < JPEG_AMD_MAX_PLANES; ++p) {
+        windows[p] = jpeg_amd_region{0, 0, 0, 0};
+        if (p >= L->nplanes) continue;
+        InterleaveAxis mx = interleave_axis(*L, p, cosited != 0, false), my = interleave_axis(*L, p, cosited != 0, true);
+        mx.last = n * L->units_x[p] - 1;   // the scaled plane's padded edge
+        my.last = n * L->units_y[p] - 1;
+        int32_t x0, x1, y0, y1;
+        axis_span(mx, r.x, r.x + r.width - 1, x0, x1);
+        axis_span(my, r.y, r.y + r.height - 1, y0, y1);
+        windows[p] = jpeg_amd_region{x0 / n, y0 / n, x1 / n - x0 / n + 1, y1 / n - y0 / n + 1};
+    }
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_view_of_source(const jpeg_amd_layout *L, int denom, const jpeg_amd_region *source_region, jpeg_amd_region *region)
+{
+    if (!source_region || !region) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    const long long n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    JA_TRY(check_region(L, *source_region));
+    const jpeg_amd_region &s = *source_region;
+    const long long w1 = ((long long)L->width * n + 7) / 8, h1 = ((long long)L->height * n + 7) / 8;
+    const long long x0 = s.x * n / 8, x1 = std::min(w1, (((long long)s.x + s.width) * n + 7) / 8);
+    const long long y0 = s.y * n / 8, y1 = std::min(h1, (((long long)s.y + s.height) * n + 7) / 8);
+    *region = jpeg_amd_region{(int32_t)x0, (int32_t)y0, (int32_t)(x1 - x0), (int32_t)(y1 - y0)};
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t want_h)
+{
+    for (int denom = 8; denom > 1; denom /= 2) {
+        const long long n = 8 / denom;
+        if (src_w * n / 8 >= want_w && src_h * n / 8 >= want_h) return denom;
+    }
+    return 1;
 }
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,

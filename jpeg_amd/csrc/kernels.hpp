@@ -125,6 +125,17 @@ hipError_t launch_scaled_decode(hipStream_t stream, int n_images, const jpeg_amd
 hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int16_t *d_coef, size_t coef_stride, QuantaRef q,
                                     int qi, int ux, int uy, int n, int precision, void *d_plane, size_t plane_stride, bool out_u8);
 
+// ---- view decode (kernels_view.hip) ------------------------------------------------------
+// The layouts of fused_decode_supported, n = 8 / denom in {8, 4, 2, 1}: the n_images images of a call that share n, each cut
+// to its rectangle of the scaled image, in ONE launch of nwg workgroups (k_view_decode).  d_index: uint32 [n_images], the
+// launch's image i is image d_index[i] of the call -- which is where its coefficients, tables, rectangle (d_regions: int32
+// [images of the call][4]) and pixels are; d_tiles: uint32 [n_images + 1], the prefix of view_tiles over the launch's images
+// (d_tiles[n_images] == nwg).
+uint32_t   view_tiles(int n, const jpeg_amd_region &region);
+hipError_t launch_view_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, int n, const PlaneSet &coef, QuantaRef q,
+                              bool rgb, const uint32_t *d_index, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
+                              uint8_t *d_pixels, size_t pixel_stride);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

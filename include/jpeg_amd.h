@@ -676,6 +676,53 @@ int jpeg_amd_view_of_source(const jpeg_amd_layout *layout, int denom, const jpeg
  * to reach want_w x want_h. */
 int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t want_h);
 
+/* ---- resized decode: views resampled to one fixed size ------------------------------------------------
+ * The reference has no resize; this is the conventional bilinear filter with half-pixel centres.  THE CONTRACT (the one
+ * statement of it), every statement ONE binary32 operation, nothing contracted:
+ *
+ * A source image is w x h pixels of 3 bytes, the target out_w x out_h.  Per axis, here x for output column j:
+ *   kx = (float)w / (float)out_w               divided ON THE HOST, handed to the kernel per image: the kernel holds no
+ *                                              division and nothing depends on a device division mode
+ *   sx = ((float)j + 0.5f) * kx - 0.5f;  sx = max(sx, 0.0f)
+ *   x0 = min((int)sx, w - 1);  x1 = min(x0 + 1, w - 1);  fx = sx - (float)x0
+ * and y0, y1, fy from ky = (float)h / (float)out_h and the output row likewise.  Per channel, with a, b, c, d the bytes at
+ * (y0, x0), (y0, x1), (y1, x0), (y1, x1) converted to float -- the horizontal pass first, then the vertical pass:
+ *   top = a + fx * (b - a);  bot = c + fx * (d - c);  v = top + fy * (bot - top)
+ *   out = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
+ * There is no antialiasing filter: with a denominator from jpeg_amd_view_denom what is left to reduce is below 2 per axis
+ * unless the source is more than 8 times the target.  out_w == w and out_h == h give the source bytes (sx = j, fx = 0).
+ * Upscaling is the same formula. */
+typedef struct jpeg_amd_extent {
+    int32_t width, height;
+} jpeg_amd_extent;
+
+/* The resample alone, pixels to pixels, one launch.  Source image i is h_extents[i].height rows of 3 * width bytes, no
+ * padding between rows, at d_src + i * src_stride; output image i is out_h rows of 3 * out_w bytes at d_dst + i * dst_stride.
+ * src_stride >= 3 * width_i * height_i for every i and dst_stride >= 3 * out_w * out_h (any value, 0 included, when
+ * n_images == 1); bytes in the stride gaps are left alone.  The source and the output must not overlap.  h_extents is a HOST
+ * array of n_images extents; the call copies it before it returns.  Everything is validated before anything is enqueued: on
+ * EINVAL -- out_w or out_h < 1 or above 2^30, a width or height < 1, a stride that is too small, more than 65 535 images, a
+ * null pointer -- nothing is written and the context stays usable.  n_images == 0 is OK. */
+int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride);
+
+/* Image i of the output is THE IMAGE THAT jpeg_amd_decode_view_batch DEFINES FOR h_views[i], RESAMPLED to out_w x out_h by
+ * the contract above; nothing else is defined here arithmetically.  Output and its stride as in jpeg_amd_resize_batch,
+ * every other argument as in jpeg_amd_decode_view_batch, and whatever either refuses is refused here -- before anything is
+ * enqueued, nothing written, the context usable (8-bit only, else ENOSUP; n_images == 0 is OK).
+ * Cost: jpeg_amd_decode_view_batch, as it stands, into a buffer of the context (each view compact, the views of a chunk at
+ * a stride of the chunk's largest, chunks of consecutive images of at most 1 GiB), then ONE resample launch per chunk.
+ * Every layout of the view call works, its fallback layouts included. */
+int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                  const int16_t *const d_coef[], const size_t coef_stride[],
+                                  const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                  int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                  int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride);
+/* single image, host tables */
+int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                            const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                            const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -326,6 +326,18 @@ class spectral {
                                    cosite ? 1 : 0, (jpeg_amd_color)target, &view, px.data()), "jpeg_amd_decode_view");
         return px.host();
     }
+    /// decode_view(target, view, cosite) bilinearly resampled to out_w x out_h: out_h * out_w colours of 3 bytes
+    /// (jpeg_amd.h, "resized decode", holds the filter's contract)
+    std::vector<uint8_t> decode_resized(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h, bool cosite = false) const
+    {
+        jpeg_amd_layout l = lay.c_layout(size, units, q);
+        const size_t w = out_w > 0 ? out_w : 0, h = out_h > 0 ? out_h : 0;
+        device_array<uint8_t> px(*ctx, 3 * w * h);
+        auto in = detail::pointers(planes);
+        check(jpeg_amd_decode_resized(ctx->handle(), &l, const_cast<const int16_t *const *>(in.data()), tables.data(), ntables(),
+                                      cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, px.data()), "jpeg_amd_decode_resized");
+        return px.host();
+    }
 
     /// Spectral.decompress(stream:) (decode.swift:3728): a JPEG file's bytes -> coefficient planes
     /// in HBM; the entropy decoding runs on the host inside the library.  Component c gets quanta

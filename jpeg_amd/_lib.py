@@ -129,6 +129,10 @@ SIGNATURES = {
     "jpeg_amd_view_window": (C.c_int, [_L, C.c_int, C.c_int, _p, _p]),
     "jpeg_amd_view_of_source": (C.c_int, [_L, C.c_int, _p, _p]),
     "jpeg_amd_view_denom": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "jpeg_amd_resize_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, _p, C.c_size_t]),
+    "jpeg_amd_decode_resized_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, C.c_int32,
+                                                C.c_int32, _p, C.c_size_t]),
+    "jpeg_amd_decode_resized": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p]),
 }
 
 
@@ -140,6 +144,11 @@ class Region(C.Structure):
 class View(C.Structure):
     """struct jpeg_amd_view"""
     _fields_ = [("denom", C.c_int32), ("region", Region)]
+
+
+class Extent(C.Structure):
+    """struct jpeg_amd_extent"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32)]
 
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V

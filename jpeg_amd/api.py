@@ -266,14 +266,22 @@ class Spectral:
             1 if cosite else 0, color.code, out.data_ptr()), "jpeg_amd_decode", self.ctx.handle)
         return out.view(-1, 3)
 
-    def view(self, region, scale: int, color=RGB, cosite: bool = False):
+    def view(self, region, scale: int, color=RGB, cosite: bool = False, size=None):
         """The image at 1/scale size (scale 1 | 2 | 4 | 8, as decode(scale=)) cropped to region (x, y, width, height) in
         pixels of THAT image, any alignment, bit for bit, as uint8 [height, width, 3] (jpeg_amd_decode_view).  view_of_source
-        turns a rectangle of the full-size image into such a region, view_denom picks the scale for a target size."""
+        turns a rectangle of the full-size image into such a region, view_denom picks the scale for a target size.
+        size (Wt, Ht): that view bilinearly resampled to Wt x Ht, as uint8 [Ht, Wt, 3] (jpeg_amd_decode_resized)."""
         torch = _torch()
         L = self._layout()
         qarr, qptr = _quanta_array(self.quanta)
         v = _view(scale, region)
+        if size is not None:
+            wt, ht = int(size[0]), int(size[1])
+            out = self.ctx.empty(max(wt, 0) * max(ht, 0) * 3, torch.uint8)
+            _lib.check(_lib.lib().jpeg_amd_decode_resized(
+                self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
+                1 if cosite else 0, color.code, C.byref(v), wt, ht, out.data_ptr()), "jpeg_amd_decode_resized", self.ctx.handle)
+            return out.view(ht, wt, 3)
         w, h = max(v.region.width, 0), max(v.region.height, 0)
         out = self.ctx.empty(w * h * 3, torch.uint8)
         _lib.check(_lib.lib().jpeg_amd_decode_view(
@@ -656,11 +664,8 @@ def view_denom(source_size, want_size) -> int:
     return int(_lib.lib().jpeg_amd_view_denom(int(source_size[0]), int(source_size[1]), int(want_size[0]), int(want_size[1])))
 
 
-def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: Optional[Sequence[int]] = None, color=RGB,
-                 cosite: bool = False):
-    """Decode n images of one layout, each at its own denominator and cropped to its own rectangle of that scaled image, in
-    one call (jpeg_amd_decode_view_batch).  planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or
-    device); views: [n, 5] of (denom, x, y, width, height).  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+def _view_batch_args(ctx: Context, size, layout: Layout, planes, quanta, views, q):
+    """The arguments decode_views and decode_resized share: (vs [n, 5], planes, quanta on the device, c layout, c views)."""
     torch = _torch()
     vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
     n = vs.shape[0]
@@ -677,17 +682,83 @@ def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: O
     if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
         raise ValueError("quanta: [n, ntables, 64]")
     L = layout.c_layout(size, units, q)
-    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
-    stride = max(areas)
-    out = ctx.empty(n * stride, torch.uint8)
     h_views = (_lib.View * max(n, 1))()
     for i, row in enumerate(vs.tolist()):
         h_views[i] = _view(row[0], row[1:])
+    return vs, planes, quanta, L, h_views
+
+
+def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: Optional[Sequence[int]] = None, color=RGB,
+                 cosite: bool = False):
+    """Decode n images of one layout, each at its own denominator and cropped to its own rectangle of that scaled image, in
+    one call (jpeg_amd_decode_view_batch).  planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or
+    device); views: [n, 5] of (denom, x, y, width, height).  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+    torch = _torch()
+    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    n = vs.shape[0]
+    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
+    stride = max(areas)
+    out = ctx.empty(n * stride, torch.uint8)
     _lib.check(_lib.lib().jpeg_amd_decode_view_batch(
         ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
         int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, out.data_ptr(), stride),
         "jpeg_amd_decode_view_batch", ctx.handle)
     return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
+
+
+def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, q: Optional[Sequence[int]] = None,
+                   color=RGB, cosite: bool = False):
+    """decode_views with every image bilinearly resampled to out_size (Wt, Ht), in one call
+    (jpeg_amd_decode_resized_batch; include/jpeg_amd.h holds the filter's contract).  Arguments as decode_views.  Returns one
+    uint8 tensor [n, Ht, Wt, 3]."""
+    torch = _torch()
+    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    n = vs.shape[0]
+    wt, ht = int(out_size[0]), int(out_size[1])
+    stride = 3 * max(wt, 0) * max(ht, 0)
+    out = ctx.empty(n * stride, torch.uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(
+        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
+        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, wt, ht, out.data_ptr(), stride),
+        "jpeg_amd_decode_resized_batch", ctx.handle)
+    return out.view(n, ht, wt, 3)
+
+
+def decode_crops_resized(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size,
+                         q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+    """The data-loader call: per image a rectangle (x, y, width, height) of the FULL-SIZE image, decoded at the cheapest
+    denominator that is still no smaller than out_size -- view_denom((width, height), out_size), then view_of_source -- and
+    resampled to out_size (Wt, Ht) by decode_resized.  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
+    [n, 5] of (denom, x, y, width, height))."""
+    regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
+    views = np.empty((regs.shape[0], 5), np.int32)
+    for i, r in enumerate(regs.tolist()):
+        denom = view_denom(r[2:], out_size)
+        views[i] = (denom,) + view_of_source(size, denom, r)
+    return decode_resized(ctx, size, layout, planes, quanta, views, out_size, q=q, color=color, cosite=cosite), views
+
+
+def resize(ctx: Context, images, out_size):
+    """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
+    (jpeg_amd_resize_batch).  The images are packed into one allocation first (torch copies).  Returns uint8 [n, Ht, Wt, 3]."""
+    torch = _torch()
+    images = list(images)
+    n = len(images)
+    for im in images:
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError("images: uint8 device tensors [h, w, 3]")
+    wt, ht = int(out_size[0]), int(out_size[1])
+    src_stride = max([int(im.numel()) for im in images] or [0])
+    src = ctx.empty(n * src_stride, torch.uint8)
+    extents = (_lib.Extent * max(n, 1))()
+    for i, im in enumerate(images):
+        src[i * src_stride:i * src_stride + im.numel()].copy_(im.reshape(-1))
+        extents[i].width, extents[i].height = int(im.shape[1]), int(im.shape[0])
+    stride = 3 * max(wt, 0) * max(ht, 0)
+    out = ctx.empty(n * stride, torch.uint8)
+    _lib.check(_lib.lib().jpeg_amd_resize_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, out.data_ptr(), stride),
+               "jpeg_amd_resize_batch", ctx.handle)
+    return out.view(n, ht, wt, 3)
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

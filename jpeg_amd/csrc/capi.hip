@@ -36,6 +36,10 @@ struct jpeg_amd_ctx {
     int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
     void *d_region = nullptr;      // staged regions + tile prefix of jpeg_amd_decode_region_batch / _view_batch (grown on demand)
     size_t region_bytes = 0;
+    // jpeg_amd_decode_resized_batch / jpeg_amd_resize_batch: the decoded views of a chunk and the resample's per-image records.
+    // Buffers of their own: the view call in between regrows `scratch` and overwrites `d_region`.
+    void *d_resize_src = nullptr, *d_resize_rec = nullptr;
+    size_t resize_src_bytes = 0, resize_rec_bytes = 0;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -455,6 +459,8 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     ctx->copiers.reset();
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_region) (void)hipFree(ctx->d_region);
+    if (ctx->d_resize_src) (void)hipFree(ctx->d_resize_src);
+    if (ctx->d_resize_rec) (void)hipFree(ctx->d_resize_rec);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
     if (ctx->d_flag) (void)hipFree(ctx->d_flag);
@@ -956,6 +962,30 @@ int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
 
 constexpr size_t kViewFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's whole-image decodes
 
+// Every argument of jpeg_amd_decode_view_batch but the context, in the order that decides the status of a call that is wrong
+// twice.  S[k] / count[k]: the scaled image and the number of views of denominator 1 << k; *whole: every view a whole image.
+int check_views(const jpeg_amd_layout *L, int n_images, const int16_t *const d_coef[], const size_t coef_stride[],
+                const uint16_t *d_quanta, int ntables, jpeg_amd_color color, const jpeg_amd_view *h_views, const uint8_t *d_pixels,
+                size_t pixel_stride, jpeg_amd_layout S[kViewDenoms], int count[kViewDenoms], bool *whole, PlaneSet *cs)
+{
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, n_images, color));
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_views) return JPEG_AMD_EINVAL;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, cs));
+    for (int i = 0; i < n_images; ++i) {
+        const int k = view_slot(h_views[i].denom);
+        if (k < 0) return JPEG_AMD_EINVAL;
+        if (count[k]++ == 0) JA_TRY(scaled_image(L, h_views[i].denom, &S[k]));
+        const jpeg_amd_region &r = h_views[i].region;
+        JA_TRY(check_region(&S[k], r));
+        if (n_images > 1 && pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
+        *whole = *whole && whole_image(&S[k], r);
+    }
+    return JPEG_AMD_OK;
+}
+
 }  // namespace
 
 int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
@@ -965,26 +995,12 @@ int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int 
                                uint8_t *d_pixels, size_t pixel_stride)
 try {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, n_images, color));
     jpeg_amd_layout S[kViewDenoms];
     int count[kViewDenoms] = {0, 0, 0, 0};
     bool whole = true;
     PlaneSet cs{};
-    if (n_images > 0) {
-        if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_views) return JPEG_AMD_EINVAL;
-        JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
-        for (int i = 0; i < n_images; ++i) {
-            const int k = view_slot(h_views[i].denom);
-            if (k < 0) return JPEG_AMD_EINVAL;
-            if (count[k]++ == 0) JA_TRY(scaled_image(L, h_views[i].denom, &S[k]));
-            const jpeg_amd_region &r = h_views[i].region;
-            JA_TRY(check_region(&S[k], r));
-            if (n_images > 1 && pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
-            whole = whole && whole_image(&S[k], r);
-        }
-    }
+    JA_TRY(check_views(L, n_images, d_coef, coef_stride, d_quanta, ntables, color, h_views, d_pixels, pixel_stride, S, count, &whole,
+                       &cs));
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
 
@@ -1133,6 +1149,155 @@ int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t wa
         if (src_w * n / 8 >= want_w && src_h * n / 8 >= want_h) return denom;
     }
     return 1;
+}
+
+namespace {
+
+constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of jpeg_amd_decode_resized_batch
+
+// One of the context's resample buffers, grown as upload_regions grows the region buffer.
+int ensure_buffer(jpeg_amd_ctx *ctx, void **buf, size_t *have, size_t bytes)
+{
+    if (bytes <= *have) return JPEG_AMD_OK;
+    if (*buf) {
+        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still use it
+        JA_HIP(ctx, hipFree(*buf));
+        *buf = nullptr;
+        *have = 0;
+    }
+    const size_t want = bytes + bytes / 8 + 4096;
+    JA_HIP(ctx, hipMalloc(buf, want));
+    *have = want;
+    return JPEG_AMD_OK;
+}
+
+// The scale factors of the contract: divided here, in binary32, never on the device.
+ResizeRecord resize_record(uint64_t offset, int32_t w, int32_t h, int32_t out_w, int32_t out_h)
+{
+    return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h};
+}
+
+// The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
+// returns -- as stage_quanta).
+int upload_records(jpeg_amd_ctx *ctx, const std::vector<ResizeRecord> &rec)
+{
+    const size_t bytes = rec.size() * sizeof(ResizeRecord);
+    JA_TRY(ensure_buffer(ctx, &ctx->d_resize_rec, &ctx->resize_rec_bytes, bytes));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->d_resize_rec, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    return JPEG_AMD_OK;
+}
+
+// What both resample calls require of the output.
+int check_resize_target(int n_images, int32_t out_w, int32_t out_h, const uint8_t *d_dst, size_t dst_stride)
+{
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
+    if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
+    if (n_images > 1 && dst_stride < (size_t)3 * out_w * out_h) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+}  // namespace
+
+int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    JA_TRY(check_resize_target(n_images, out_w, out_h, d_dst, dst_stride));
+    std::vector<ResizeRecord> rec((size_t)n_images);
+    if (n_images > 0) {
+        if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
+        for (int i = 0; i < n_images; ++i) {
+            const jpeg_amd_extent &e = h_extents[i];
+            if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
+            if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
+            rec[(size_t)i] = resize_record((uint64_t)i * src_stride, e.width, e.height, out_w, out_h);
+        }
+    }
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+    JA_TRY(upload_records(ctx, rec));
+    JA_HIP(ctx, launch_resize_bilinear(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->d_resize_rec), out_w,
+                                       out_h, d_dst, dst_stride));
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                  const int16_t *const d_coef[], const size_t coef_stride[],
+                                  const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                  int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                  int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
+    // ours and always large enough)
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(L, n_images, d_coef, coef_stride, d_quanta, ntables, color, h_views, d_pixels, ~(size_t)0, S, count, &whole,
+                       &cs));
+    JA_TRY(check_resize_target(n_images, out_w, out_h, d_pixels, pixel_stride));
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+
+    // chunks of consecutive images: m images at a stride of the chunk's largest view, at most kResizeChunkBytes in all
+    struct Chunk { int i0, m; size_t stride; };
+    std::vector<Chunk> chunks;
+    std::vector<ResizeRecord> rec((size_t)n_images);
+    size_t need = 0;
+    for (int i0 = 0; i0 < n_images;) {
+        int m = 0;
+        size_t stride = 0;
+        for (; i0 + m < n_images; ++m) {
+            const jpeg_amd_region &r = h_views[i0 + m].region;
+            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
+            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
+            stride = s;
+        }
+        for (int j = 0; j < m; ++j) {
+            const jpeg_amd_region &r = h_views[i0 + j].region;
+            rec[(size_t)(i0 + j)] = resize_record((uint64_t)j * stride, r.width, r.height, out_w, out_h);
+        }
+        chunks.push_back(Chunk{i0, m, stride});
+        need = std::max(need, stride * (size_t)m);
+        i0 += m;
+    }
+    JA_TRY(ensure_buffer(ctx, &ctx->d_resize_src, &ctx->resize_src_bytes, need));
+    JA_TRY(upload_records(ctx, rec));
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->d_resize_src);
+    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->d_resize_rec);
+    for (const Chunk &c : chunks) {
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)c.i0 * coef_stride[p];
+        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, c.m, coef, coef_stride, d_quanta + (size_t)c.i0 * quanta_stride, quanta_stride,
+                                          ntables, cosited, color, h_views + c.i0, d_views, c.stride));
+        JA_HIP(ctx, launch_resize_bilinear(ctx->stream, c.m, d_views, d_rec + c.i0, out_w, out_h,
+                                           d_pixels + (size_t)c.i0 * pixel_stride, pixel_stride));
+    }
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                            const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                            const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels)
+{
+    // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, 1, color));
+    if (!view) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, view->denom, &S));
+    JA_TRY(check_region(&S, view->region));
+    JA_TRY(check_resize_target(1, out_w, out_h, d_pixels, 0));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    return jpeg_amd_decode_resized_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, view, out_w, out_h, d_pixels, 0);
 }
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,

@@ -136,6 +136,20 @@ hipError_t launch_view_decode(hipStream_t stream, int n_images, const jpeg_amd_l
                               bool rgb, const uint32_t *d_index, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
                               uint8_t *d_pixels, size_t pixel_stride);
 
+// ---- bilinear resample (kernels_resize.hip) ------------------------------------------------
+// n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h by the contract of include/jpeg_amd.h
+// ("resized decode") in ONE launch (k_resize_bilinear).  d_records: one ResizeRecord per image -- the image's first byte at
+// d_src + offset, its extent, and the scale factors, divided on the host.  Output image i at d_dst + i * dst_stride.
+struct ResizeRecord {
+    uint64_t offset;   // bytes from d_src
+    int32_t  w, h;     // > 0
+    float    kx, ky;   // (float)w / (float)out_w, (float)h / (float)out_h
+};
+constexpr int kResizeMaxSide = 1 << 30;          // of the output: the kernel's pixel indices are int
+uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the launch's grid.x, which holds 2^31 - 1 at most
+hipError_t launch_resize_bilinear(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
+                                  int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

@@ -725,7 +725,51 @@ int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int3
     return JPEG_AMD_OK;
 }
 
-constexpr size_t kRegionFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's whole-image decodes
+constexpr size_t kFallbackChunkBytes = (size_t)1 << 30;   // scratch per chunk of a fallback's whole-image decodes or planes
+
+constexpr int kViewDenoms = 4;   // slot k: denom 1 << k
+int view_slot(int denom) { return denom == 1 ? 0 : denom == 2 ? 1 : denom == 4 ? 2 : denom == 8 ? 3 : -1; }
+
+// The region and the view call's fallback for the layouts without a tile kernel: the whole scaled images of a run of
+// consecutive images of one denominator into scratch behind the staged paths' planes (S's planes are no larger than L's),
+// then one crop launch; a run is at most a chunk.  S[k]: the image at denominator 1 << k, for every k among the views.
+int crop_fallback(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const int16_t *const d_coef[], const size_t coef_stride[],
+                  const uint16_t *d_quanta, size_t quanta_stride, int ntables, int cosited, jpeg_amd_color color,
+                  const jpeg_amd_view *h_views, const jpeg_amd_layout S[kViewDenoms], uint8_t *d_pixels, size_t pixel_stride)
+{
+    const size_t n = (size_t)n_images;
+    size_t full_max = 0;
+    std::vector<uint32_t> buf(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const jpeg_amd_layout &Si = S[view_slot(h_views[i].denom)];
+        full_max = std::max(full_max, (size_t)3 * Si.width * Si.height);
+        std::memcpy(&buf[4 * i], &h_views[i].region, 16);
+    }
+    const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kFallbackChunkBytes / per_image));
+    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
+    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full_max * chunk)));
+    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;   // the staged paths' planes stay below it
+    JA_TRY(upload_regions(ctx, buf));
+    const int32_t *d_regions = static_cast<const int32_t *>(ctx->d_region);
+    for (int i0 = 0; i0 < n_images;) {
+        const int denom = h_views[i0].denom;
+        const jpeg_amd_layout &Sd = S[view_slot(denom)];
+        int m = 0;
+        size_t max_bytes = 0;
+        for (; i0 + m < n_images && m < chunk && h_views[i0 + m].denom == denom; ++m)
+            max_bytes = std::max(max_bytes, (size_t)3 * h_views[i0 + m].region.width * h_views[i0 + m].region.height);
+        const size_t full = (size_t)3 * Sd.width * Sd.height;
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
+        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
+                                            cosited, color, denom, d_full, full));
+        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes,
+                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+        i0 += m;
+    }
+    return JPEG_AMD_OK;
+}
 
 }  // namespace
 
@@ -744,46 +788,31 @@ try {
     PlaneSet cs;
     JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
     bool whole = true;
-    size_t max_bytes = 0;
     for (int i = 0; i < n_images; ++i) {
         JA_TRY(check_region(L, h_regions[i]));
-        const size_t bytes = (size_t)3 * h_regions[i].width * h_regions[i].height;
-        if (n_images > 1 && pixel_stride < bytes) return JPEG_AMD_EINVAL;
-        max_bytes = std::max(max_bytes, bytes);
+        if (n_images > 1 && pixel_stride < (size_t)3 * h_regions[i].width * h_regions[i].height) return JPEG_AMD_EINVAL;
         whole = whole && whole_image(L, h_regions[i]);
     }
     if (whole)
         return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
                                      d_pixels, pixel_stride);
 
-    const int32_t *d_regions = nullptr;
-    const uint32_t *d_tiles = nullptr;
-    uint32_t nwg = 0;
     if (fused_decode_supported(*L, cosited != 0)) {
+        const int32_t *d_regions = nullptr;
+        const uint32_t *d_tiles = nullptr;
+        uint32_t nwg = 0;
         JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
         JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride},
                                          color == JPEG_AMD_COLOR_RGB8, d_tiles, d_regions, nwg, d_pixels, pixel_stride));
         return JPEG_AMD_OK;
     }
 
-    // fallback: whole images into scratch behind the staged path's planes, then one crop launch, chunk by chunk
-    const size_t full = (size_t)3 * L->width * L->height;
-    const size_t per_image = full + scratch_planes_bytes(L, 1, sizeof(uint8_t));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kRegionFallbackBytes / per_image));
-    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
-    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full * chunk)));
-    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;   // decode_batch's planes stay below it
-    JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
-    for (int i0 = 0; i0 < n_images; i0 += chunk) {
-        const int m = std::min(chunk, n_images - i0);
-        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
-        JA_TRY(jpeg_amd_decode_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
-                                     cosited, color, d_full, full));
-        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, L->width, d_regions + 4 * (size_t)i0, max_bytes,
-                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
-    }
-    return JPEG_AMD_OK;
+    // the crop fallback at denominator 1, where the scaled image is the image
+    std::vector<jpeg_amd_view> views((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) views[(size_t)i] = jpeg_amd_view{1, h_regions[i]};
+    const jpeg_amd_layout S[kViewDenoms] = {*L};
+    return crop_fallback(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, views.data(), S,
+                         d_pixels, pixel_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -842,8 +871,6 @@ int check_planes_cover_scaled(const jpeg_amd_layout *L, const jpeg_amd_layout *S
     return JPEG_AMD_OK;
 }
 
-constexpr size_t kScaledFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's planes
-
 }  // namespace
 
 int jpeg_amd_scaled_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out)
@@ -896,7 +923,7 @@ int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
     // fallback: every plane N x N per block into byte planes in scratch, padded to S's whole blocks by edge replication, then
     // the staged interleave + colour kernel under S, chunk by chunk
     const size_t per_image = std::max<size_t>(1, scratch_planes_bytes(&S, 1, sizeof(uint8_t)));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kScaledFallbackBytes / per_image));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kFallbackChunkBytes / per_image));
     PlaneSetMut scratch;
     JA_TRY(scratch_planes(ctx, &S, chunk, sizeof(uint8_t), &scratch));
     for (int i0 = 0; i0 < n_images; i0 += chunk) {
@@ -948,9 +975,6 @@ int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, c
 
 namespace {
 
-constexpr int kViewDenoms = 4;   // slot k: denom 1 << k
-int view_slot(int denom) { return denom == 1 ? 0 : denom == 2 ? 1 : denom == 4 ? 2 : denom == 8 ? 3 : -1; }
-
 // The image at `denom` as the scaled contract defines it: *S is jpeg_amd_scaled_layout's, and the planes cover it.
 int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
 {
@@ -959,8 +983,6 @@ int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
     JA_TRY(jpeg_amd_scaled_layout(L, denom, S));
     return denom == 1 ? JPEG_AMD_OK : check_planes_cover_scaled(L, S, n);
 }
-
-constexpr size_t kViewFallbackBytes = (size_t)1 << 30;   // scratch per chunk of the fallback's whole-image decodes
 
 // Every argument of jpeg_amd_decode_view_batch but the context, in the order that decides the status of a call that is wrong
 // twice.  S[k] / count[k]: the scaled image and the number of views of denominator 1 << k; *whole: every view a whole image.
@@ -1049,37 +1071,8 @@ try {
         return JPEG_AMD_OK;
     }
 
-    // fallback: the whole scaled images of a run of consecutive images of one denominator into scratch behind the staged
-    // paths' planes (S's planes are no larger than L's), then one crop launch; a run is at most a chunk
-    size_t full_max = 0;
-    for (int k = 0; k < kViewDenoms; ++k)
-        if (count[k]) full_max = std::max(full_max, (size_t)3 * S[k].width * S[k].height);
-    const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kViewFallbackBytes / per_image));
-    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
-    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full_max * chunk)));
-    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;
-    std::vector<uint32_t> buf(4 * n);
-    for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
-    JA_TRY(upload_regions(ctx, buf));
-    const int32_t *d_regions = static_cast<const int32_t *>(ctx->d_region);
-    for (int i0 = 0; i0 < n_images;) {
-        const int denom = h_views[i0].denom;
-        const jpeg_amd_layout &Sd = S[view_slot(denom)];
-        int m = 0;
-        size_t max_bytes = 0;
-        for (; i0 + m < n_images && m < chunk && h_views[i0 + m].denom == denom; ++m)
-            max_bytes = std::max(max_bytes, (size_t)3 * h_views[i0 + m].region.width * h_views[i0 + m].region.height);
-        const size_t full = (size_t)3 * Sd.width * Sd.height;
-        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
-        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
-                                            cosited, color, denom, d_full, full));
-        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes,
-                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
-        i0 += m;
-    }
-    return JPEG_AMD_OK;
+    return crop_fallback(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, h_views, S, d_pixels,
+                         pixel_stride);
 }
 JA_NOTHROW_TAIL
 

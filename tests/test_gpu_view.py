@@ -228,6 +228,31 @@ def test_views_equal_the_existing_calls(ctx, torch, name):
             assert i == n - 1 or (mixed[i] == want[i]).all(), (name, color, i)
 
 
+@pytest.mark.parametrize("name", ["y8", "444", "420", "422"])
+def test_the_two_full_size_kernels_agree_across_their_tile_seams(ctx, torch, name):
+    """k_region_decode (128 x 64 tiles) and k_view_decode<8> (128 x 32) run one tile body.  The rectangle's tile grid is
+    anchored at (8, 8): it crosses x = 136 and 264, and y = 40, 72 and 104 of the view kernel, y = 72 of the region kernel."""
+    size, r = (300, 150), (13, 11, 270, 120)
+    L = _layout(size[0], size[1], FUSED[name])
+    planes, dq, ntables = _synthetic(ctx, torch, L, 2, 77)
+    ph = [p.cpu().numpy() for p in planes]
+    qh = dq.cpu().numpy().astype(np.uint16)
+    want = _reference(L, ph, qh, 0, 1, 0)
+    area = 3 * r[2] * r[3]
+    for color in COLORS:
+        out = torch.full((area + 16,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
+        assert _lib.lib().jpeg_amd_decode_region_batch(
+            ctx.handle, C.byref(L), 1, _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(_strides(L)), dq.data_ptr(),
+            ntables * 64, ntables, 0, color, (_lib.Region * 1)(_lib.Region(*r)), out.data_ptr(), area) == 0
+        out = out.cpu().numpy()
+        assert (out[area:] == SENTINEL).all()
+        region = out[:area].reshape(r[3], r[2], 3)
+        alone = _view_batch(ctx, torch, L, planes, dq, ntables, 0, color, [(1, r)], gap=16)[0]
+        mixed = _view_batch(ctx, torch, L, planes, dq, ntables, 0, color, [(1, r), (2, (1, 1, 9, 5))], gap=16)[0]
+        for how, got in (("region call", region), ("view alone", alone), ("mixed call", mixed)):
+            assert (got == _crop(want[color], r)).all(), (name, color, how)
+
+
 # ---- 4. unread coefficients do not matter -------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("denom", [4, 2])

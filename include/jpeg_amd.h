@@ -723,6 +723,66 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, co
                             const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
                             const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels);
 
+/* ---- spectral reduce: a Spectral at 1/2, 1/4 or 1/8 size, coefficients in and coefficients out ----------
+ * JPEG in, smaller JPEG out, without pixels in between: no interleave, no colour conversion and no second generation of
+ * chroma rounding, so every layout, plane count and precision is served alike.  It composes two contracts that are stated
+ * elsewhere and defines no arithmetic of its own.  THE CONTRACT (the one statement of it):
+ *
+ * denom in {2, 4, 8}, N = 8 / denom.  Any other value is EINVAL -- 1 included: requantising at full size is
+ * jpeg_amd_spectral_transform's job.
+ *
+ * Scaled samples.  For plane p of units (ux, uy) and table Q_in, S_p is the N uy x N ux sample array that the
+ * scaled-decode contract above defines: the table q_N, the reduced butterflies, the two passes, clamp to [0, 2^P - 1] and
+ * truncate at the layout's precision P.  Coefficients with k >= N or h >= N are not read.
+ *
+ * Output geometry (jpeg_amd_reduce_layout).  (W', H') = (ceil(W N / 8), ceil(H N / 8)); precision, factors, scale and qi
+ * are the input's; the units are recomputed exactly as jpeg_amd_layout_units does for (W', H') -- what any reader of the
+ * output file derives from its header.  Where every factor divides the scale these are jpeg_amd_scaled_layout's
+ * ceil(N units / 8); for a factor that does not divide the scale they can be one larger (factor 3 in scale 4, width 21,
+ * N = 4: 2 against 1).  The replication rule covers both.
+ *
+ * Output samples.  Plane p of the output is 8 uy' x 8 ux' samples; sample (x, y) is S_p(min(x, N ux - 1), min(y, N uy - 1)):
+ * edge replication, the rule jpeg_amd_scaled_layout documents.
+ *
+ * Output coefficients.  Spectral.Plane.fdct(_:quanta:precision:) (encode.swift:199-248) of that plane with table Q_out:
+ * load(limit:), fdct8x8, the x8 modulated table, the quotient rounded half away from zero -- exactly what
+ * jpeg_amd_planar_fdct computes (oracle/: fdct_plane).  Q_out is given per table index like Q_in; NULL means Q_in.
+ *
+ * The quantiser is the literal binary32 division of the staged FDCT kernel (the only other form the contract admits is the
+ * fused encoder's reciprocal-plus-correction inside the range tools/verify_div16.hip proved: every 16-bit divisor,
+ * numerators below 2^25).  A quotient that does not fit int16 behaves as in jpeg_amd_planar_fdct; nothing new is defined
+ * for it.  A zero in a HOST-supplied output table (NULL = the input tables) is EINVAL; the batch entry takes DEVICE tables,
+ * like jpeg_amd_encode_batch, and validates what that call validates.
+ *
+ * Cost: one launch for every plane of every image; it reads only the block heads the scaled decode reads (half a block at
+ * denom 2, 16 bytes at denom 4, 2 bytes at denom 8) and writes 1/4, 1/16 or 1/64 of the input's bytes. */
+
+/* Host only.  The output geometry above; EINVAL for a denom not in {2, 4, 8} or an invalid layout. */
+int jpeg_amd_reduce_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out);
+/* n_images images of layout in_layout: image i of plane p reads d_coef_in[p] + i * in_stride[p] and writes d_coef_out[p] +
+ * i * out_stride[p] (int16 elements; the output planes are sized by jpeg_amd_reduce_layout; int16 elements in the stride gaps
+ * are left alone).  Plane pointers are multiples of 16 bytes and, for more than one image, strides multiples of 8 elements, else
+ * EINVAL: every block starts on a 16-byte boundary.  Every plane of in_layout has at least one block.  d_quanta: DEVICE tables [..][ntables][64], image i at
+ * i * quanta_stride, plane p uses table in_layout->qi[p]; d_quanta_out: NULL = d_quanta, else the output tables, same layout
+ * and strides.  At most 65 535 images, n_images == 0 is OK.  Everything is validated before anything is enqueued: on EINVAL
+ * nothing is written and the context stays usable.  Asynchronous on the ctx stream. */
+int jpeg_amd_spectral_reduce_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *in_layout, int n_images, int denom,
+                                   const int16_t *const d_coef_in[], const size_t in_stride[],
+                                   const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                   const uint16_t *d_quanta_out, int16_t *const d_coef_out[], const size_t out_stride[]);
+/* single image, host tables (h_quanta_out NULL = h_quanta); synchronises */
+int jpeg_amd_spectral_reduce(jpeg_amd_ctx *ctx, const jpeg_amd_layout *in_layout, int denom,
+                             const int16_t *const d_coef_in[], const uint16_t *h_quanta, int ntables,
+                             const uint16_t *h_quanta_out, int16_t *const d_coef_out[]);
+/* File to file, built like jpeg_amd_transform: entropy decoding on the host (restart intervals on `nthreads` threads, <= 0:
+ * all cores), ONE reduce launch on the GPU, and the host writer keeping the input's process, component ids, scan script,
+ * table keys, restart interval and metadata segments verbatim and in order.  Every component of the frame is reduced.
+ * h_requant: NULL (the file's own tables) or [ncomponents][64], the output tables (components that share a key must get
+ * equal tables, else EINVAL).  h_out == NULL only sizes the output (*nbytes_out); out_info (optional) receives the output
+ * frame. */
+int jpeg_amd_reduce(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int denom, const uint16_t *h_requant,
+                    int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out, jpeg_amd_frame_info *out_info);
+
 #ifdef __cplusplus
 }
 #endif

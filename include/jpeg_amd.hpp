@@ -339,6 +339,25 @@ class spectral {
         return px.host();
     }
 
+    /// this image at 1 / denom size (denom 2 | 4 | 8), coefficients to coefficients in one launch: every plane's scaled
+    /// samples through Spectral.Plane.fdct with the same tables (jpeg_amd.h, "spectral reduce")
+    spectral reduce(int denom) const
+    {
+        jpeg_amd_layout l = lay.c_layout(size, units, q), o;
+        check(jpeg_amd_reduce_layout(&l, denom, &o), "jpeg_amd_reduce_layout");
+        std::vector<size2> ou;
+        std::vector<device_array<int16_t>> out;
+        for (int p = 0; p < l.nplanes; ++p) {
+            ou.push_back({o.units_x[p], o.units_y[p]});
+            out.emplace_back(*ctx, (size_t)64 * o.units_x[p] * o.units_y[p]);
+        }
+        auto in = detail::pointers(planes);
+        auto op = detail::pointers(out);
+        check(jpeg_amd_spectral_reduce(ctx->handle(), &l, denom, const_cast<const int16_t *const *>(in.data()), tables.data(),
+                                       ntables(), nullptr, op.data()), "jpeg_amd_spectral_reduce");
+        return spectral(*ctx, {o.width, o.height}, lay, std::move(ou), std::move(out), tables, q);
+    }
+
     /// Spectral.decompress(stream:) (decode.swift:3728): a JPEG file's bytes -> coefficient planes
     /// in HBM; the entropy decoding runs on the host inside the library.  Component c gets quanta
     /// key c.  `ids` (optional) receives the component identifiers of the frame header.

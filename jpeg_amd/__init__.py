@@ -9,11 +9,11 @@ from ._lib import JpegAmdError, LIB_PATH  # noqa: F401
 from .api import (  # noqa: F401
     RGB, YCbCr, Component, Context, Layout, Planar, Rectangular, Scan, Spectral,
     compression_quanta, decode_crops_resized, decode_regions, decode_resized, decode_scaled, decode_views, default_context, inspect,
-    region_window, resize, scaled_size, transform, transform_quanta, view_denom, view_of_source, view_window,
+    reduce, reduce_layout, region_window, resize, scaled_size, transform, transform_quanta, view_denom, view_of_source, view_window,
 )
 
 __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangular",
            "Scan", "Spectral", "JpegAmdError", "compression_quanta", "decode_crops_resized", "decode_regions", "decode_resized",
-           "decode_scaled", "decode_views", "default_context", "inspect", "region_window", "resize", "scaled_size",
+           "decode_scaled", "decode_views", "default_context", "inspect", "reduce", "reduce_layout", "region_window", "resize", "scaled_size",
            "transform", "transform_quanta", "view_denom",
            "view_of_source", "view_window"]

@@ -133,6 +133,10 @@ SIGNATURES = {
     "jpeg_amd_decode_resized_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, C.c_int32,
                                                 C.c_int32, _p, C.c_size_t]),
     "jpeg_amd_decode_resized": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p]),
+    "jpeg_amd_reduce_layout": (C.c_int, [_L, C.c_int, _L]),
+    "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
+    "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
+    "jpeg_amd_reduce": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.c_int, _p, C.c_size_t, _p, _p]),
 }
 
 

@@ -372,6 +372,38 @@ class Spectral:
                                                  "(Int16 overflow, q_in > 32767 or q_out = 0)")
         return Spectral(self.ctx, (out.width, out.height), layout, planes, quanta, self.q)
 
+    def reduce(self, denom: int, quanta=None) -> "Spectral":
+        """This image at 1/denom size (denom 2 | 4 | 8), coefficients to coefficients, device to device, in one launch
+        (jpeg_amd_spectral_reduce_batch; the contract is in include/jpeg_amd.h, "spectral reduce"): every plane's scaled-decode
+        samples through Spectral.Plane.fdct -- no interleave and no colour conversion, any layout and precision.
+        quanta: the output tables, {quanta key: 64 values} or one per entry of self.quanta; None keeps the input's."""
+        torch = _torch()
+        L = self._layout()
+        out = _lib.Layout()
+        lib = _lib.lib()
+        _lib.check(lib.jpeg_amd_reduce_layout(C.byref(L), int(denom), C.byref(out)), "jpeg_amd_reduce_layout")
+        n = len(self.quanta)
+        tables = [np.asarray(t, np.uint16).reshape(64) for t in self.quanta]
+        if isinstance(quanta, dict):
+            for p, comp in enumerate(self.layout.planes):
+                tables[self.q[p]] = np.asarray(quanta[comp.qi], np.uint16).reshape(64)
+        elif quanta is not None:
+            tables = [np.asarray(t, np.uint16).reshape(64) for t in quanta]
+            if len(tables) != n:
+                raise ValueError("quanta: one table per entry of self.quanta")
+        if any((tables[t] == 0).any() for t in set(self.q)):
+            raise _lib.JpegAmdError(_lib.EINVAL, "Spectral.reduce: a zero in an output table")
+        planes = [self.ctx.empty(64 * out.units_x[p] * out.units_y[p], torch.int16).view(out.units_y[p], out.units_x[p], 64)
+                  for p in range(self.layout.count)]
+        d_q = self.ctx.upload(np.stack(self.quanta).astype(np.uint16))
+        d_qo = self.ctx.upload(np.stack(tables).astype(np.uint16)) if quanta is not None else None
+        zero = _lib.size_array([0] * MAX_PLANES)
+        _lib.check(lib.jpeg_amd_spectral_reduce_batch(
+            self.ctx.handle, C.byref(L), 1, int(denom), _ptrs(self.planes), zero, d_q.data_ptr(), 0, n,
+            d_qo.data_ptr() if d_qo is not None else None, _ptrs(planes), zero),
+            "jpeg_amd_spectral_reduce_batch", self.ctx.handle)
+        return Spectral(self.ctx, (out.width, out.height), self.layout, planes, tables, self.q)
+
     def set(self, width: Optional[int] = None, height: Optional[int] = None) -> None:
         """Spectral.set(width:) / set(height:) (decode.swift:2443-2500), in place: the image is cropped or grows from its
         top left corner; new blocks are zero."""
@@ -551,6 +583,43 @@ def transform(source, op, region=None, requantize=None, threads: int = 0, path=N
             continue
         break
     _lib.check(st, "jpeg_amd_transform", ctx.handle)
+    b = out[:n.value].tobytes()
+    if path is not None:
+        with open(path, "wb") as f:
+            f.write(b)
+    return b
+
+
+def reduce_layout(size, layout: Layout, denom: int, units=None) -> Tuple[Tuple[int, int], List[Tuple[int, int]]]:
+    """((W', H'), [(units_x, units_y) per plane]) of the image at 1/denom size as Spectral.reduce / reduce give it
+    (jpeg_amd_reduce_layout): the units are recomputed from (W', H'), as a reader of the output file does."""
+    L = layout.c_layout(size, units)
+    out = _lib.Layout()
+    _lib.check(_lib.lib().jpeg_amd_reduce_layout(C.byref(L), int(denom), C.byref(out)), "jpeg_amd_reduce_layout")
+    return (out.width, out.height), [(out.units_x[p], out.units_y[p]) for p in range(layout.count)]
+
+
+def reduce(source, denom: int, requantize=None, threads: int = 0, path=None, ctx: Optional[Context] = None) -> bytes:
+    """JPEG file -> JPEG file at 1/denom size (denom 2 | 4 | 8) in the coefficient domain (jpeg_amd_reduce): the input's
+    process, scan script, table keys, restart interval and metadata segments are kept.
+    requantize: None (the file's own tables) or one output table of 64 values per frame component."""
+    ctx = ctx or default_context()
+    data = _file_bytes(source)
+    rq = None
+    if requantize is not None:
+        rq = np.ascontiguousarray(np.stack([np.asarray(t, np.uint16).reshape(64) for t in requantize]))
+    lib = _lib.lib()
+    n = C.c_size_t()
+    cap = 2 * data.size + (1 << 16)                  # one pass: a smaller image of the same script fits; else once more
+    for _ in range(2):
+        out = np.empty(cap, np.uint8)
+        st = lib.jpeg_amd_reduce(ctx.handle, data.ctypes.data, data.size, int(denom), rq.ctypes.data if rq is not None else None,
+                                 int(threads), out.ctypes.data, out.size, C.byref(n), None)
+        if st == _lib.EINVAL and n.value > cap:
+            cap = n.value
+            continue
+        break
+    _lib.check(st, "jpeg_amd_reduce", ctx.handle)
     b = out[:n.value].tobytes()
     if path is not None:
         with open(path, "wb") as f:

@@ -2370,13 +2370,17 @@ int jpeg_amd_spectral_transform(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int
     return flag ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
 }
 
-// File to file: host entropy decoding, the transform on the device, the host writer with the input's script.
-int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int op, const jpeg_amd_region *region,
-                       const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
-                       jpeg_amd_frame_info *out_info)
-try {
-    JA_TRY(bind(ctx));
-    if (!h_jpeg || !nbytes_out || op < 0 || op > 7) return JPEG_AMD_EINVAL;
+// ---- file to file in the coefficient domain: what jpeg_amd_transform and jpeg_amd_reduce share ---------------------------
+namespace {
+extern "C++" {
+
+// Host entropy decoding, one device step on the planes, the host writer with the input's script (scans, table keys, restart
+// interval, metadata segments).  plan(L, &O): the output layout; device(L, d_in, quanta, nc, d_out): the step, synchronised on
+// return; table(c, quanta[c], t): the output table of component c when h_requant is NULL.
+template <typename Plan, typename Device, typename Table>
+int file_to_file(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, const uint16_t *h_requant, int nthreads, Plan plan,
+                 Device device, Table table, uint8_t *h_out, size_t capacity, size_t *nbytes_out, jpeg_amd_frame_info *out_info)
+{
     jpeg_amd_frame_info fi;
     JA_TRY(jpeg_amd_jpeg_inspect(h_jpeg, nbytes, &fi));
     const int nc = fi.ncomponents;
@@ -2398,16 +2402,15 @@ try {
     uint16_t quanta[JPEG_AMD_MAX_PLANES][64];
     JA_TRY(jpeg_amd_jpeg_decode_spectral_mt(h_jpeg, nbytes, coef, quanta, &fi, nthreads));
     const jpeg_amd_layout L = layout_of_info(fi, nc);
-    TransformPlan tp;
-    JA_TRY(plan_transform(&L, op, region, &tp));
-    const jpeg_amd_layout &O = tp.out;
+    jpeg_amd_layout O;
+    JA_TRY(plan(L, &O));
     // components that share a key share a table, in the file and after requantisation
     if (h_requant)
         for (int c = 0; c < nc; ++c)
             for (int d = 0; d < c; ++d)
                 if (keys[c] == keys[d] && std::memcmp(h_requant + 64 * c, h_requant + 64 * d, 64 * sizeof(uint16_t)))
                     return JPEG_AMD_EINVAL;
-    // the device: upload, transform, download
+    // the device: upload, the step, download
     std::vector<std::vector<int16_t>> outp((size_t)nc);
     int16_t *ocoef[JPEG_AMD_MAX_PLANES] = {};
     for (int c = 0; c < nc; ++c) {
@@ -2422,11 +2425,11 @@ try {
             JA_TRY(bag.upload(coef[c], plane_samples(&L, c) * 2, (void **)&d_in[c]));
             JA_TRY(bag.alloc(plane_samples(&O, c) * 2, (void **)&d_out[c]));
         }
-        JA_TRY(jpeg_amd_spectral_transform(ctx, &L, op, region, d_in, &quanta[0][0], nc, h_requant, d_out));
+        JA_TRY(device(L, d_in, &quanta[0][0], nc, d_out));
         for (int c = 0; c < nc; ++c) JA_TRY(bag.download(ocoef[c], d_out[c], plane_samples(&O, c) * 2));
         JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    // one table per distinct key, ascending, in output orientation
+    // one table per distinct key, ascending
     std::vector<int32_t> tkeys;
     std::vector<uint16_t> tables;
     for (int c = 0; c < nc; ++c)
@@ -2436,7 +2439,7 @@ try {
         const int c = (int)(std::find(keys, keys + nc, k) - keys);
         uint16_t t[64];
         if (h_requant) std::memcpy(t, h_requant + 64 * c, sizeof t);
-        else JA_TRY(jpeg_amd_transform_quanta(op, quanta[c], t));
+        else JA_TRY(table(c, quanta[c], t));
         tables.insert(tables.end(), t, t + 64);
     }
     jpeg_amd_frame_info of = fi;
@@ -2449,6 +2452,126 @@ try {
     if (out_info) *out_info = of;
     return jpeg_amd_jpeg_encode_spectral(&of, keys, ocoef, tables.data(), tkeys.data(), (int)tkeys.size(), scans.data(), nscans,
                                          meta.data(), nmeta, h_out, capacity, nbytes_out);
+}
+
+}  // extern "C++"
+}  // namespace
+
+// File to file: host entropy decoding, the transform on the device, the host writer with the input's script; the tables in
+// output orientation.
+int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int op, const jpeg_amd_region *region,
+                       const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
+                       jpeg_amd_frame_info *out_info)
+try {
+    JA_TRY(bind(ctx));
+    if (!h_jpeg || !nbytes_out || op < 0 || op > 7) return JPEG_AMD_EINVAL;
+    return file_to_file(
+        ctx, h_jpeg, nbytes, h_requant, nthreads,
+        [&](const jpeg_amd_layout &L, jpeg_amd_layout *O) { return jpeg_amd_transform_layout(&L, op, region, O); },
+        [&](const jpeg_amd_layout &L, const int16_t *const d_in[], const uint16_t *quanta, int nc, int16_t *const d_out[]) {
+            return jpeg_amd_spectral_transform(ctx, &L, op, region, d_in, quanta, nc, h_requant, d_out);
+        },
+        [&](int, const uint16_t *q, uint16_t *t) { return jpeg_amd_transform_quanta(op, q, t); },
+        h_out, capacity, nbytes_out, out_info);
+}
+JA_NOTHROW_TAIL
+
+// ---- spectral reduce: 1/2, 1/4, 1/8 size, coefficients in and out (include/jpeg_amd.h, "spectral reduce") ---------------
+namespace {
+
+// N = 8 / denom for a denom of the reduce contract, else 0.
+int reduce_n(int denom) { return denom == 2 || denom == 4 || denom == 8 ? 8 / denom : 0; }
+
+// A zero divisor among the tables the planes of L use.
+bool has_zero_quantum(const jpeg_amd_layout *L, const uint16_t *h_tables)
+{
+    for (int p = 0; p < L->nplanes; ++p)
+        for (int z = 0; z < 64; ++z)
+            if (h_tables[64 * L->qi[p] + z] == 0) return true;
+    return false;
+}
+
+}  // namespace
+
+int jpeg_amd_reduce_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out)
+{
+    if (!out) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(in, -1));
+    const int n = reduce_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout r = *in;
+    r.width = (int32_t)(((long long)in->width * n + 7) / 8);
+    r.height = (int32_t)(((long long)in->height * n + 7) / 8);
+    JA_TRY(jpeg_amd_layout_units(&r));
+    *out = r;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_spectral_reduce_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, int denom,
+                                   const int16_t *const d_coef_in[], const size_t in_stride[],
+                                   const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                   const uint16_t *d_quanta_out, int16_t *const d_coef_out[], const size_t out_stride[])
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    const int n = reduce_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout O;
+    JA_TRY(jpeg_amd_reduce_layout(L, denom, &O));
+    for (int p = 0; p < L->nplanes; ++p)
+        if (plane_samples(L, p) == 0) return JPEG_AMD_EINVAL;      // no block whose edge could be replicated
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef_in || !in_stride || !d_coef_out || !out_stride || !d_quanta) return JPEG_AMD_EINVAL;
+    PlaneSet cin{};
+    PlaneSetMut cout{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        if (!d_coef_in[p] || !d_coef_out[p]) return JPEG_AMD_EINVAL;
+        if (n_images > 1 && out_stride[p] < plane_samples(&O, p)) return JPEG_AMD_EINVAL;      // the images' outputs would overlap
+        // the kernel loads and stores 16-byte pieces: every block of every image starts on a 16-byte boundary
+        if (reinterpret_cast<uintptr_t>(d_coef_in[p]) % 16 || reinterpret_cast<uintptr_t>(d_coef_out[p]) % 16) return JPEG_AMD_EINVAL;
+        if (n_images > 1 && (in_stride[p] % 8 || out_stride[p] % 8)) return JPEG_AMD_EINVAL;
+        cin.ptr[p] = d_coef_in[p]; cin.stride[p] = in_stride[p];
+        cout.ptr[p] = d_coef_out[p]; cout.stride[p] = out_stride[p];
+    }
+    JA_HIP(ctx, launch_spectral_reduce(ctx->stream, n_images, n, *L, O, cin, QuantaRef{d_quanta, quanta_stride}, d_quanta_out, cout));
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_spectral_reduce(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int denom, const int16_t *const d_coef_in[],
+                             const uint16_t *h_quanta, int ntables, const uint16_t *h_quanta_out, int16_t *const d_coef_out[])
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (reduce_n(denom) == 0 || !h_quanta || ntables < 1 || ntables > JPEG_AMD_MAX_PLANES) return JPEG_AMD_EINVAL;
+    if (has_zero_quantum(L, h_quanta_out ? h_quanta_out : h_quanta)) return JPEG_AMD_EINVAL;
+    if (!d_coef_in || !d_coef_out) return JPEG_AMD_EINVAL;
+    for (int p = 0; p < L->nplanes; ++p)
+        if (plane_samples(L, p) == 0 || !d_coef_in[p] || !d_coef_out[p]) return JPEG_AMD_EINVAL;
+    const uint16_t *d_q = nullptr, *d_qo = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    if (h_quanta_out) JA_TRY(stage_quanta(ctx, h_quanta_out, ntables, &d_qo));
+    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+    JA_TRY(jpeg_amd_spectral_reduce_batch(ctx, L, 1, denom, d_coef_in, zero, d_q, 0, ntables, d_qo, d_coef_out, zero));
+    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return JPEG_AMD_OK;
+}
+
+// File to file: host entropy decoding, one reduce launch on the device, the host writer with the input's script.
+int jpeg_amd_reduce(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int denom, const uint16_t *h_requant,
+                    int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out, jpeg_amd_frame_info *out_info)
+try {
+    JA_TRY(bind(ctx));
+    if (!h_jpeg || !nbytes_out || reduce_n(denom) == 0) return JPEG_AMD_EINVAL;
+    return file_to_file(
+        ctx, h_jpeg, nbytes, h_requant, nthreads,
+        [&](const jpeg_amd_layout &L, jpeg_amd_layout *O) { return jpeg_amd_reduce_layout(&L, denom, O); },
+        [&](const jpeg_amd_layout &L, const int16_t *const d_in[], const uint16_t *quanta, int nc, int16_t *const d_out[]) {
+            return jpeg_amd_spectral_reduce(ctx, &L, denom, d_in, quanta, nc, h_requant, d_out);
+        },
+        [&](int, const uint16_t *q, uint16_t *t) { std::memcpy(t, q, 64 * sizeof(uint16_t)); return (int)JPEG_AMD_OK; },
+        h_out, capacity, nbytes_out, out_info);
 }
 JA_NOTHROW_TAIL
 

@@ -159,6 +159,14 @@ hipError_t launch_transform(hipStream_t stream, int n_images, int op, const jpeg
                             const int *ox, const int *oy, const PlaneSet &coef_in, QuantaRef q, const uint16_t *d_quanta_out,
                             const PlaneSetMut &coef_out, int32_t *d_overflow);
 
+// ---- spectral reduce (kernels_reduce.hip) ------------------------------------------------
+// n = 8 / denom in {4, 2, 1}.  Every plane of n_images images in one launch (k_spectral_reduce): plane p of `out`
+// (jpeg_amd_reduce_layout's) is Spectral.Plane.fdct of the scaled-decode samples of plane p of `in`, edge-replicated to out's
+// whole blocks.  d_quanta_out: nullptr = q's tables, else the output tables (same strides, plane p's table in.qi[p]).  Every
+// plane of `in` has at least one block.
+hipError_t launch_spectral_reduce(hipStream_t stream, int n_images, int n, const jpeg_amd_layout &in, const jpeg_amd_layout &out,
+                                  const PlaneSet &coef_in, QuantaRef q, const uint16_t *d_quanta_out, const PlaneSetMut &coef_out);
+
 // ---- encode -------------------------------------------------------------------------
 // a13: Rectangular.pack
 hipError_t launch_pack(hipStream_t stream, const uint8_t *d_pixels, size_t npixels,

@@ -15,6 +15,7 @@
 //   additions (no counterpart in the reference: the three decode stages in one PCIe round trip)
 //   Spectral.decode(as:cosite:)  for JPEG.RGB / JPEG.YCbCr  = idct().interleaved(cosite:).unpack(as:)
 //   AMD.withDevice(_:_:) / AMD.device / AMD.deviceCount      which GPU a thread's calls run on
+//   AMD.reduce(file:denom:capacity:)                         JPEG file -> JPEG file at 1/2, 1/4, 1/8 size (jpeg_amd_reduce)
 //   overloads (the reference's generic definition stays for every other JPEG.Color conformance)
 //   Rectangular.unpack(as:)  for JPEG.RGB / JPEG.YCbCr    decode.swift:4291-4298
 //   Rectangular.pack(size:layout:metadata:pixels:)  same  encode.swift:453-464
@@ -176,6 +177,12 @@ enum AMD
             return taken.withUnsafeMutableBufferPointer{ go(i + 1, acc + [$0.baseAddress], &arrays) }
         }
         return go(0, [], &arrays)
+    }
+
+    /// A JPEG file's bytes at 1 / denom size (denom 2, 4 or 8), coefficients to coefficients: jpeg_amd_reduce, forwarded.
+    static func reduce(file:[UInt8], denom:Int32, capacity:Int) -> [UInt8]
+    {
+        .init(unsafeUninitializedCapacity: capacity){ out, count in Self.withContext{ Self.check(jpeg_amd_reduce($0, file, file.count, denom, nil, 0, out.baseAddress, capacity, &count, nil), "jpeg_amd_reduce") } }
     }
 
     /// [table][64] in zigzag order (decode.swift:1289-1326), the form the C ABI takes tables in

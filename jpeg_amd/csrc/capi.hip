@@ -24,22 +24,25 @@
 
 using namespace jpeg_amd;
 
+// Device memory a context keeps between calls and grows on demand (ensure_buffer).
+struct DeviceBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
 struct jpeg_amd_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DeviceBuffer scratch;          // the planes of the staged paths, the whole images of the fallbacks
     uint16_t *d_qstage = nullptr;  // ring of staged host tables
     uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
     int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
-    void *d_region = nullptr;      // staged regions + tile prefix of jpeg_amd_decode_region_batch / _view_batch (grown on demand)
-    size_t region_bytes = 0;
+    DeviceBuffer region;           // staged regions + tile prefix of jpeg_amd_decode_region_batch / _view_batch
     // jpeg_amd_decode_resized_batch / jpeg_amd_resize_batch: the decoded views of a chunk and the resample's per-image records.
-    // Buffers of their own: the view call in between regrows `scratch` and overwrites `d_region`.
-    void *d_resize_src = nullptr, *d_resize_rec = nullptr;
-    size_t resize_src_bytes = 0, resize_rec_bytes = 0;
+    // Buffers of their own: the view call in between regrows `scratch` and overwrites `region`.
+    DeviceBuffer resize_src, resize_rec;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -133,18 +136,20 @@ size_t plane_samples(const jpeg_amd_layout *L, int p)
     return (size_t)64 * L->units_x[p] * L->units_y[p];
 }
 
-int ensure_scratch(jpeg_amd_ctx *ctx, size_t bytes)
+// One of the context's buffers with room for `bytes`, grown with an eighth to spare.  The one place that frees such a
+// buffer between calls: the previous call's kernels may still use it, so the stream is synchronised first.
+// (C linkage, as the helpers inside the extern "C" block have: the library's dynamic symbol list keeps the name.)
+extern "C" int ensure_buffer(jpeg_amd_ctx *ctx, DeviceBuffer &buf, size_t bytes)
 {
-    if (bytes <= ctx->scratch_bytes) return JPEG_AMD_OK;
-    if (ctx->scratch) {
+    if (bytes <= buf.bytes) return JPEG_AMD_OK;
+    if (buf.ptr) {
         JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        JA_HIP(ctx, hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
+        JA_HIP(ctx, hipFree(buf.ptr));
+        buf = DeviceBuffer{};
     }
     const size_t want = bytes + bytes / 8 + 4096;
-    JA_HIP(ctx, hipMalloc(&ctx->scratch, want));
-    ctx->scratch_bytes = want;
+    JA_HIP(ctx, hipMalloc(&buf.ptr, want));
+    buf.bytes = want;
     return JPEG_AMD_OK;
 }
 
@@ -159,6 +164,9 @@ int stage_quanta(jpeg_amd_ctx *ctx, const uint16_t *h_quanta, int ntables, const
     *d_out = slot;
     return JPEG_AMD_OK;
 }
+
+// The single-image forms are their batch forms with one image, staged tables and these strides.
+constexpr size_t kOneImage[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
@@ -178,10 +186,10 @@ int scratch_planes(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, si
         offset[p] = total;
         total += align256(plane_samples(L, p) * (size_t)n_images * sample_bytes);
     }
-    JA_TRY(ensure_scratch(ctx, total));
+    JA_TRY(ensure_buffer(ctx, ctx->scratch, total));
     *ps = PlaneSetMut{};
     for (int p = 0; p < L->nplanes; ++p) {
-        ps->ptr[p] = static_cast<uint8_t *>(ctx->scratch) + offset[p];
+        ps->ptr[p] = static_cast<uint8_t *>(ctx->scratch.ptr) + offset[p];
         ps->stride[p] = plane_samples(L, p);
     }
     return JPEG_AMD_OK;
@@ -211,6 +219,45 @@ int check_batch8(const jpeg_amd_layout *L, int n_images, jpeg_amd_color color)
     if (color != JPEG_AMD_COLOR_YCC8 && color != JPEG_AMD_COLOR_RGB8) return JPEG_AMD_EINVAL;
     return JPEG_AMD_OK;
 }
+
+// The arguments the batch decode entry points (whole, region, scaled, view, resized) share, as the caller gave them.
+struct DecodeCall {
+    const jpeg_amd_layout *L;
+    int n_images;
+    const int16_t *const *d_coef;
+    const size_t *coef_stride;
+    const uint16_t *d_quanta;
+    size_t quanta_stride;
+    int ntables, cosited;
+    jpeg_amd_color color;
+    uint8_t *d_pixels;
+    size_t pixel_stride;
+
+    // What is judged before the image count may end the call, in the order that decides the status of a call that is wrong
+    // twice.  The context is no part of it: every entry point binds where it always did.
+    int check() const
+    {
+        JA_TRY(check_layout(L, ntables));
+        JA_TRY(check_planes_cover_image(L));
+        return check_batch8(L, n_images, color);
+    }
+    // ... and of a call with images: no null pointer (per_image: the entry point's regions or views are there, where it
+    // has any) and the coefficient planes as a PlaneSet.
+    int planes(PlaneSet *cs, bool per_image = true) const
+    {
+        if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !per_image) return JPEG_AMD_EINVAL;
+        return plane_set(L, d_coef, coef_stride, true, cs);
+    }
+    // Images [i0, i0 + m) of this call; `coef` is the caller's room for their plane pointers.
+    DecodeCall images(int i0, int m, const int16_t *coef[JPEG_AMD_MAX_PLANES]) const
+    {
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
+        return DecodeCall{L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables, cosited, color,
+                          d_pixels + (size_t)i0 * pixel_stride, pixel_stride};
+    }
+    QuantaRef quanta() const { return QuantaRef{d_quanta, quanta_stride}; }
+    bool rgb() const { return color == JPEG_AMD_COLOR_RGB8; }
+};
 
 // The staged decode (any factors): IDCT every plane into scratch planes of bytes or halfwords, then upsample + interleave
 // (+ colour) into `kind` pixels.
@@ -457,10 +504,8 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->workers.reset();
     ctx->copiers.reset();
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->d_region) (void)hipFree(ctx->d_region);
-    if (ctx->d_resize_src) (void)hipFree(ctx->d_resize_src);
-    if (ctx->d_resize_rec) (void)hipFree(ctx->d_resize_rec);
+    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec})
+        if (buf->ptr) (void)hipFree(buf->ptr);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
     if (ctx->d_flag) (void)hipFree(ctx->d_flag);
@@ -639,16 +684,14 @@ int jpeg_amd_decode_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_ima
                           int cosited, jpeg_amd_color color, uint8_t *d_pixels,
                           size_t pixel_stride)
 {
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
     JA_TRY(bind(ctx));
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, n_images, color));
+    JA_TRY(c.check());
     if (n_images == 0) return JPEG_AMD_OK;
-    if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
     PlaneSet cs;
-    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
-    const QuantaRef q{d_quanta, quanta_stride};
-    const bool rgb = color == JPEG_AMD_COLOR_RGB8;
+    JA_TRY(c.planes(&cs));
+    const QuantaRef q = c.quanta();
+    const bool rgb = c.rgb();
     if (fused_decode_supported(*L, cosited != 0)) {
         JA_HIP(ctx, launch_fused_decode(ctx->stream, n_images, *L, cs, q, rgb, ctx->d_walk, d_pixels, pixel_stride));
         return JPEG_AMD_OK;
@@ -664,9 +707,7 @@ int jpeg_amd_decode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *
     JA_TRY(check_layout(L, ntables));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_decode_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color,
-                                 d_pixels, 0);
+    return jpeg_amd_decode_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, d_pixels, 0);
 }
 
 namespace {
@@ -689,18 +730,8 @@ bool whole_image(const jpeg_amd_layout *L, const jpeg_amd_region &r)
 int upload_regions(jpeg_amd_ctx *ctx, const std::vector<uint32_t> &buf)
 {
     const size_t bytes = 4 * buf.size();
-    if (bytes > ctx->region_bytes) {
-        if (ctx->d_region) {
-            JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still read it
-            JA_HIP(ctx, hipFree(ctx->d_region));
-            ctx->d_region = nullptr;
-            ctx->region_bytes = 0;
-        }
-        const size_t want = bytes + bytes / 8 + 4096;
-        JA_HIP(ctx, hipMalloc(&ctx->d_region, want));
-        ctx->region_bytes = want;
-    }
-    JA_HIP(ctx, hipMemcpyAsync(ctx->d_region, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(ensure_buffer(ctx, ctx->region, bytes));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->region.ptr, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
     return JPEG_AMD_OK;
 }
 
@@ -719,8 +750,8 @@ int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int3
     }
     buf[4 * (size_t)n + n] = acc;
     JA_TRY(upload_regions(ctx, buf));
-    *d_regions = static_cast<const int32_t *>(ctx->d_region);
-    *d_tiles = reinterpret_cast<const uint32_t *>(static_cast<const int32_t *>(ctx->d_region) + 4 * (size_t)n);
+    *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
+    *d_tiles = reinterpret_cast<const uint32_t *>(*d_regions + 4 * (size_t)n);
     *nwg = acc;
     return JPEG_AMD_OK;
 }
@@ -733,10 +764,10 @@ int view_slot(int denom) { return denom == 1 ? 0 : denom == 2 ? 1 : denom == 4 ?
 // The region and the view call's fallback for the layouts without a tile kernel: the whole scaled images of a run of
 // consecutive images of one denominator into scratch behind the staged paths' planes (S's planes are no larger than L's),
 // then one crop launch; a run is at most a chunk.  S[k]: the image at denominator 1 << k, for every k among the views.
-int crop_fallback(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const int16_t *const d_coef[], const size_t coef_stride[],
-                  const uint16_t *d_quanta, size_t quanta_stride, int ntables, int cosited, jpeg_amd_color color,
-                  const jpeg_amd_view *h_views, const jpeg_amd_layout S[kViewDenoms], uint8_t *d_pixels, size_t pixel_stride)
+int crop_fallback(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, const jpeg_amd_layout S[kViewDenoms])
 {
+    const jpeg_amd_layout *L = c.L;
+    const int n_images = c.n_images;
     const size_t n = (size_t)n_images;
     size_t full_max = 0;
     std::vector<uint32_t> buf(4 * n);
@@ -748,10 +779,10 @@ int crop_fallback(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, con
     const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kFallbackChunkBytes / per_image));
     const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
-    JA_TRY(ensure_scratch(ctx, planes_bytes + align256(full_max * chunk)));
-    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch) + planes_bytes;   // the staged paths' planes stay below it
+    JA_TRY(ensure_buffer(ctx, ctx->scratch, planes_bytes + align256(full_max * chunk)));
+    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch.ptr) + planes_bytes;   // the staged paths' planes stay below it
     JA_TRY(upload_regions(ctx, buf));
-    const int32_t *d_regions = static_cast<const int32_t *>(ctx->d_region);
+    const int32_t *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
     for (int i0 = 0; i0 < n_images;) {
         const int denom = h_views[i0].denom;
         const jpeg_amd_layout &Sd = S[view_slot(denom)];
@@ -761,11 +792,11 @@ int crop_fallback(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, con
             max_bytes = std::max(max_bytes, (size_t)3 * h_views[i0 + m].region.width * h_views[i0 + m].region.height);
         const size_t full = (size_t)3 * Sd.width * Sd.height;
         const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
-        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables,
-                                            cosited, color, denom, d_full, full));
-        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes,
-                                       d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+        const DecodeCall run = c.images(i0, m, coef);
+        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, c.coef_stride, run.d_quanta, c.quanta_stride, c.ntables, c.cosited, c.color,
+                                            denom, d_full, full));
+        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes, run.d_pixels,
+                                       c.pixel_stride));
         i0 += m;
     }
     return JPEG_AMD_OK;
@@ -779,14 +810,12 @@ int jpeg_amd_decode_region_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
                                  int cosited, jpeg_amd_color color, const jpeg_amd_region *h_regions,
                                  uint8_t *d_pixels, size_t pixel_stride)
 try {
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
     JA_TRY(bind(ctx));
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, n_images, color));
+    JA_TRY(c.check());
     if (n_images == 0) return JPEG_AMD_OK;
-    if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_regions) return JPEG_AMD_EINVAL;
     PlaneSet cs;
-    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+    JA_TRY(c.planes(&cs, h_regions != nullptr));
     bool whole = true;
     for (int i = 0; i < n_images; ++i) {
         JA_TRY(check_region(L, h_regions[i]));
@@ -802,8 +831,8 @@ try {
         const uint32_t *d_tiles = nullptr;
         uint32_t nwg = 0;
         JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
-        JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, QuantaRef{d_quanta, quanta_stride},
-                                         color == JPEG_AMD_COLOR_RGB8, d_tiles, d_regions, nwg, d_pixels, pixel_stride));
+        JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, c.quanta(), c.rgb(), d_tiles, d_regions, nwg, d_pixels,
+                                         pixel_stride));
         return JPEG_AMD_OK;
     }
 
@@ -811,8 +840,7 @@ try {
     std::vector<jpeg_amd_view> views((size_t)n_images);
     for (int i = 0; i < n_images; ++i) views[(size_t)i] = jpeg_amd_view{1, h_regions[i]};
     const jpeg_amd_layout S[kViewDenoms] = {*L};
-    return crop_fallback(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, views.data(), S,
-                         d_pixels, pixel_stride);
+    return crop_fallback(ctx, c, views.data(), S);
 }
 JA_NOTHROW_TAIL
 
@@ -826,8 +854,7 @@ int jpeg_amd_decode_region(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
     JA_TRY(check_region(L, *region));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_decode_region_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, region, d_pixels, 0);
+    return jpeg_amd_decode_region_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, region, d_pixels, 0);
 }
 
 int jpeg_amd_region_window(const jpeg_amd_layout *L, int cosited, const jpeg_amd_region *region,
@@ -899,22 +926,20 @@ int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
     if (denom == 1)
         return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
                                      d_pixels, pixel_stride);
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
     JA_TRY(bind(ctx));
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, n_images, color));
+    JA_TRY(c.check());
     const int n = scaled_n(denom);
     if (n == 0) return JPEG_AMD_EINVAL;
     jpeg_amd_layout S;
     JA_TRY(jpeg_amd_scaled_layout(L, denom, &S));
     JA_TRY(check_planes_cover_scaled(L, &S, n));
     if (n_images == 0) return JPEG_AMD_OK;
-    if (!d_coef || !coef_stride || !d_quanta || !d_pixels) return JPEG_AMD_EINVAL;
-    if (n_images > 1 && pixel_stride < (size_t)3 * S.width * S.height) return JPEG_AMD_EINVAL;
     PlaneSet cs;
-    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
-    const QuantaRef q{d_quanta, quanta_stride};
-    const bool rgb = color == JPEG_AMD_COLOR_RGB8;
+    JA_TRY(c.planes(&cs));
+    if (n_images > 1 && pixel_stride < (size_t)3 * S.width * S.height) return JPEG_AMD_EINVAL;
+    const QuantaRef q = c.quanta();
+    const bool rgb = c.rgb();
     if (fused_decode_supported(*L, cosited != 0)) {
         JA_HIP(ctx, launch_scaled_decode(ctx->stream, n_images, *L, n, S.width, S.height, cs, q, rgb, d_pixels, pixel_stride));
         return JPEG_AMD_OK;
@@ -928,16 +953,17 @@ int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
     JA_TRY(scratch_planes(ctx, &S, chunk, sizeof(uint8_t), &scratch));
     for (int i0 = 0; i0 < n_images; i0 += chunk) {
         const int m = std::min(chunk, n_images - i0);
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall part = c.images(i0, m, coef);
         PlaneSet ps{};
         for (int p = 0; p < L->nplanes; ++p) {
-            JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, m, static_cast<const int16_t *>(cs.ptr[p]) + (size_t)i0 * cs.stride[p],
-                                                 cs.stride[p], QuantaRef{d_quanta + (size_t)i0 * quanta_stride, quanta_stride}, L->qi[p],
-                                                 L->units_x[p], L->units_y[p], n, L->precision, scratch.ptr[p], scratch.stride[p], true));
+            JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, m, coef[p], coef_stride[p], part.quanta(), L->qi[p], L->units_x[p],
+                                                 L->units_y[p], n, L->precision, scratch.ptr[p], scratch.stride[p], true));
             ps.ptr[p] = scratch.ptr[p];
             ps.stride[p] = scratch.stride[p];
         }
         JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, m, S, ps, true, cosited != 0, rgb ? PixelKind::RGB8 : PixelKind::YCC8,
-                                            d_pixels + (size_t)i0 * pixel_stride, pixel_stride));
+                                            part.d_pixels, pixel_stride));
     }
     return JPEG_AMD_OK;
 }
@@ -951,8 +977,7 @@ int jpeg_amd_decode_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
     if (scaled_n(denom) == 0) return JPEG_AMD_EINVAL;
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_decode_scaled_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, denom, d_pixels, 0);
+    return jpeg_amd_decode_scaled_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, denom, d_pixels, 0);
 }
 
 int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
@@ -986,26 +1011,37 @@ int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
 
 // Every argument of jpeg_amd_decode_view_batch but the context, in the order that decides the status of a call that is wrong
 // twice.  S[k] / count[k]: the scaled image and the number of views of denominator 1 << k; *whole: every view a whole image.
-int check_views(const jpeg_amd_layout *L, int n_images, const int16_t *const d_coef[], const size_t coef_stride[],
-                const uint16_t *d_quanta, int ntables, jpeg_amd_color color, const jpeg_amd_view *h_views, const uint8_t *d_pixels,
-                size_t pixel_stride, jpeg_amd_layout S[kViewDenoms], int count[kViewDenoms], bool *whole, PlaneSet *cs)
+int check_views(const DecodeCall &c, const jpeg_amd_view *h_views, jpeg_amd_layout S[kViewDenoms], int count[kViewDenoms], bool *whole,
+                PlaneSet *cs)
 {
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, n_images, color));
+    const jpeg_amd_layout *L = c.L;
+    const int n_images = c.n_images;
+    JA_TRY(c.check());
     if (n_images == 0) return JPEG_AMD_OK;
-    if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !h_views) return JPEG_AMD_EINVAL;
-    JA_TRY(plane_set(L, d_coef, coef_stride, true, cs));
+    JA_TRY(c.planes(cs, h_views != nullptr));
     for (int i = 0; i < n_images; ++i) {
         const int k = view_slot(h_views[i].denom);
         if (k < 0) return JPEG_AMD_EINVAL;
         if (count[k]++ == 0) JA_TRY(scaled_image(L, h_views[i].denom, &S[k]));
         const jpeg_amd_region &r = h_views[i].region;
         JA_TRY(check_region(&S[k], r));
-        if (n_images > 1 && pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
+        if (n_images > 1 && c.pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
         *whole = *whole && whole_image(&S[k], r);
     }
     return JPEG_AMD_OK;
+}
+
+// What jpeg_amd_decode_view and jpeg_amd_decode_resized refuse before a table is staged: check_views for their one view.
+// (C++ linkage: a function of an unnamed namespace inside the extern "C" block is exported under its plain name.)
+extern "C++" int check_one_view(const jpeg_amd_layout *L, int ntables, jpeg_amd_color color, const jpeg_amd_view *view)
+{
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, 1, color));
+    if (!view) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, view->denom, &S));
+    return check_region(&S, view->region);
 }
 
 }  // namespace
@@ -1017,12 +1053,12 @@ int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int 
                                uint8_t *d_pixels, size_t pixel_stride)
 try {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
     jpeg_amd_layout S[kViewDenoms];
     int count[kViewDenoms] = {0, 0, 0, 0};
     bool whole = true;
     PlaneSet cs{};
-    JA_TRY(check_views(L, n_images, d_coef, coef_stride, d_quanta, ntables, color, h_views, d_pixels, pixel_stride, S, count, &whole,
-                       &cs));
+    JA_TRY(check_views(c, h_views, S, count, &whole, &cs));
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
 
@@ -1061,18 +1097,17 @@ try {
             nwg[k] = (uint32_t)acc;
         }
         JA_TRY(upload_regions(ctx, buf));
-        const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->d_region);
+        const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->region.ptr);
         for (int k = 0; k < kViewDenoms; ++k) {
             if (count[k] == 0) continue;
-            JA_HIP(ctx, launch_view_decode(ctx->stream, count[k], *L, 8 >> k, cs, QuantaRef{d_quanta, quanta_stride},
-                                           color == JPEG_AMD_COLOR_RGB8, d_buf + at[k], d_buf + at[k] + count[k],
-                                           reinterpret_cast<const int32_t *>(d_buf), nwg[k], d_pixels, pixel_stride));
+            JA_HIP(ctx, launch_view_decode(ctx->stream, count[k], *L, 8 >> k, cs, c.quanta(), c.rgb(), d_buf + at[k],
+                                           d_buf + at[k] + count[k], reinterpret_cast<const int32_t *>(d_buf), nwg[k], d_pixels,
+                                           pixel_stride));
         }
         return JPEG_AMD_OK;
     }
 
-    return crop_fallback(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, h_views, S, d_pixels,
-                         pixel_stride);
+    return crop_fallback(ctx, c, h_views, S);
 }
 JA_NOTHROW_TAIL
 
@@ -1081,18 +1116,11 @@ int jpeg_amd_decode_view(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int1
                          const jpeg_amd_view *view, uint8_t *d_pixels)
 {
     // as the batch call: what can be refused is refused before a table is staged
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, 1, color));
-    if (!view) return JPEG_AMD_EINVAL;
-    jpeg_amd_layout S;
-    JA_TRY(scaled_image(L, view->denom, &S));
-    JA_TRY(check_region(&S, view->region));
+    JA_TRY(check_one_view(L, ntables, color, view));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_decode_view_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, view, d_pixels, 0);
+    return jpeg_amd_decode_view_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, d_pixels, 0);
 }
 
 int jpeg_amd_view_window(const jpeg_amd_layout *L, int cosited, int denom, const jpeg_amd_region *region,
@@ -1148,22 +1176,6 @@ namespace {
 
 constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of jpeg_amd_decode_resized_batch
 
-// One of the context's resample buffers, grown as upload_regions grows the region buffer.
-int ensure_buffer(jpeg_amd_ctx *ctx, void **buf, size_t *have, size_t bytes)
-{
-    if (bytes <= *have) return JPEG_AMD_OK;
-    if (*buf) {
-        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the previous call's kernels may still use it
-        JA_HIP(ctx, hipFree(*buf));
-        *buf = nullptr;
-        *have = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 4096;
-    JA_HIP(ctx, hipMalloc(buf, want));
-    *have = want;
-    return JPEG_AMD_OK;
-}
-
 // The scale factors of the contract: divided here, in binary32, never on the device.
 ResizeRecord resize_record(uint64_t offset, int32_t w, int32_t h, int32_t out_w, int32_t out_h)
 {
@@ -1175,8 +1187,8 @@ ResizeRecord resize_record(uint64_t offset, int32_t w, int32_t h, int32_t out_w,
 int upload_records(jpeg_amd_ctx *ctx, const std::vector<ResizeRecord> &rec)
 {
     const size_t bytes = rec.size() * sizeof(ResizeRecord);
-    JA_TRY(ensure_buffer(ctx, &ctx->d_resize_rec, &ctx->resize_rec_bytes, bytes));
-    JA_HIP(ctx, hipMemcpyAsync(ctx->d_resize_rec, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(ensure_buffer(ctx, ctx->resize_rec, bytes));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->resize_rec.ptr, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
     return JPEG_AMD_OK;
 }
 
@@ -1211,7 +1223,7 @@ try {
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
     JA_TRY(upload_records(ctx, rec));
-    JA_HIP(ctx, launch_resize_bilinear(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->d_resize_rec), out_w,
+    JA_HIP(ctx, launch_resize_bilinear(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), out_w,
                                        out_h, d_dst, dst_stride));
     return JPEG_AMD_OK;
 }
@@ -1225,12 +1237,14 @@ int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, i
 try {
     // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
     // ours and always large enough)
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
+    DecodeCall views = c;
+    views.pixel_stride = ~(size_t)0;
     jpeg_amd_layout S[kViewDenoms];
     int count[kViewDenoms] = {0, 0, 0, 0};
     bool whole = true;
     PlaneSet cs{};
-    JA_TRY(check_views(L, n_images, d_coef, coef_stride, d_quanta, ntables, color, h_views, d_pixels, ~(size_t)0, S, count, &whole,
-                       &cs));
+    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
     JA_TRY(check_resize_target(n_images, out_w, out_h, d_pixels, pixel_stride));
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
@@ -1257,17 +1271,16 @@ try {
         need = std::max(need, stride * (size_t)m);
         i0 += m;
     }
-    JA_TRY(ensure_buffer(ctx, &ctx->d_resize_src, &ctx->resize_src_bytes, need));
+    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
     JA_TRY(upload_records(ctx, rec));
-    uint8_t *d_views = static_cast<uint8_t *>(ctx->d_resize_src);
-    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->d_resize_rec);
-    for (const Chunk &c : chunks) {
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
+    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
+    for (const Chunk &k : chunks) {
         const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)c.i0 * coef_stride[p];
-        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, c.m, coef, coef_stride, d_quanta + (size_t)c.i0 * quanta_stride, quanta_stride,
-                                          ntables, cosited, color, h_views + c.i0, d_views, c.stride));
-        JA_HIP(ctx, launch_resize_bilinear(ctx->stream, c.m, d_views, d_rec + c.i0, out_w, out_h,
-                                           d_pixels + (size_t)c.i0 * pixel_stride, pixel_stride));
+        const DecodeCall part = c.images(k.i0, k.m, coef);
+        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, k.m, coef, coef_stride, part.d_quanta, quanta_stride, ntables, cosited, color,
+                                          h_views + k.i0, d_views, k.stride));
+        JA_HIP(ctx, launch_resize_bilinear(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, part.d_pixels, pixel_stride));
     }
     return JPEG_AMD_OK;
 }
@@ -1278,19 +1291,13 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const i
                             const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels)
 {
     // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
-    JA_TRY(check_layout(L, ntables));
-    JA_TRY(check_planes_cover_image(L));
-    JA_TRY(check_batch8(L, 1, color));
-    if (!view) return JPEG_AMD_EINVAL;
-    jpeg_amd_layout S;
-    JA_TRY(scaled_image(L, view->denom, &S));
-    JA_TRY(check_region(&S, view->region));
+    JA_TRY(check_one_view(L, ntables, color, view));
     JA_TRY(check_resize_target(1, out_w, out_h, d_pixels, 0));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_decode_resized_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, color, view, out_w, out_h, d_pixels, 0);
+    return jpeg_amd_decode_resized_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, d_pixels,
+                                         0);
 }
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,
@@ -1337,8 +1344,7 @@ int jpeg_amd_spectral_rectangular(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, c
     JA_TRY(check_layout(L, ntables));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_spectral_rectangular_batch(ctx, L, 1, d_coef, zero, d_q, 0, ntables, cosited, d_rect, 0);
+    return jpeg_amd_spectral_rectangular_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, d_rect, 0);
 }
 
 // ---- encode stages ----------------------------------------------------------------------
@@ -1447,8 +1453,7 @@ int jpeg_amd_rectangular_spectral(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, c
     JA_TRY(check_layout(L, ntables));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_rectangular_spectral_batch(ctx, L, 1, d_rect, 0, d_q, 0, ntables, d_coef, zero);
+    return jpeg_amd_rectangular_spectral_batch(ctx, L, 1, d_rect, 0, d_q, 0, ntables, d_coef, kOneImage);
 }
 
 int jpeg_amd_encode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const uint8_t *d_pixels,
@@ -1459,16 +1464,16 @@ int jpeg_amd_encode(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const uint8_t *
     JA_TRY(check_layout(L, ntables));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    return jpeg_amd_encode_batch(ctx, L, 1, d_pixels, 0, color, d_q, 0, ntables, d_coef, zero);
+    return jpeg_amd_encode_batch(ctx, L, 1, d_pixels, 0, color, d_q, 0, ntables, d_coef, kOneImage);
 }
 
 // ---- host-buffer conveniences -------------------------------------------------------------
 
 namespace {
 
-// Small RAII bag of device buffers for the host wrappers.
-struct DeviceBag {
+// Small RAII bag of device buffers for the host wrappers: single buffers, or every plane of a layout (T: the 16-bit sample;
+// a plane without samples gets the 16 bytes of an empty buffer and no copy).  (C++ linkage for the member templates.)
+extern "C++" struct DeviceBag {
     jpeg_amd_ctx *ctx;
     std::vector<void *> ptrs;
     explicit DeviceBag(jpeg_amd_ctx *c) : ctx(c) {}
@@ -1501,6 +1506,30 @@ struct DeviceBag {
         JA_HIP(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return JPEG_AMD_OK;
     }
+    template <typename T>
+    int alloc_planes(const jpeg_amd_layout *L, T *d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(alloc(plane_samples(L, p) * sizeof(T), (void **)&d[p]));
+        return JPEG_AMD_OK;
+    }
+    template <typename T>
+    int upload_planes(const jpeg_amd_layout *L, const T *const h[], const T *d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(upload(h[p], plane_samples(L, p) * sizeof(T), (void **)&d[p]));
+        return JPEG_AMD_OK;
+    }
+    template <typename T>
+    int download_planes(const jpeg_amd_layout *L, T *const h[], T *const d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(download(h[p], d[p], plane_samples(L, p) * sizeof(T)));
+        return JPEG_AMD_OK;
+    }
+    // the downloads have arrived in the caller's memory
+    int finish()
+    {
+        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return JPEG_AMD_OK;
+    }
 };
 
 size_t rect_samples(const jpeg_amd_layout *L) { return (size_t)L->width * L->height * L->nplanes; }
@@ -1517,16 +1546,11 @@ try {
     DeviceBag bag(ctx);
     const int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
     uint16_t *d_planes[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p) {
-        const size_t n = plane_samples(L, p);
-        JA_TRY(bag.upload(h_coef[p], n * 2, (void **)&d_coef[p]));
-        JA_TRY(bag.alloc(n * 2, (void **)&d_planes[p]));
-    }
+    JA_TRY(bag.upload_planes(L, h_coef, d_coef));
+    JA_TRY(bag.alloc_planes(L, d_planes));
     JA_TRY(jpeg_amd_spectral_idct(ctx, L, d_coef, h_quanta, ntables, d_planes));
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.download(h_planes[p], d_planes[p], plane_samples(L, p) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    JA_TRY(bag.download_planes(L, h_planes, d_planes));
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1539,14 +1563,12 @@ try {
     if (!h_planes || !h_rect) return JPEG_AMD_EINVAL;
     DeviceBag bag(ctx);
     const uint16_t *d_planes[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.upload(h_planes[p], plane_samples(L, p) * 2, (void **)&d_planes[p]));
+    JA_TRY(bag.upload_planes(L, h_planes, d_planes));
     uint16_t *d_rect = nullptr;
     JA_TRY(bag.alloc(rect_samples(L) * 2, (void **)&d_rect));
     JA_TRY(jpeg_amd_planar_interleaved(ctx, L, d_planes, cosited, d_rect));
     JA_TRY(bag.download(h_rect, d_rect, rect_samples(L) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1562,8 +1584,7 @@ try {
     JA_TRY(bag.alloc(npixels * 3, (void **)&d_px));
     JA_TRY(jpeg_amd_rectangular_unpack(ctx, d_rect, npixels, nplanes, color, d_px));
     JA_TRY(bag.download(h_pixels, d_px, npixels * 3));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1576,15 +1597,13 @@ try {
     if (!h_coef || !h_pixels) return JPEG_AMD_EINVAL;
     DeviceBag bag(ctx);
     const int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.upload(h_coef[p], plane_samples(L, p) * 2, (void **)&d_coef[p]));
+    JA_TRY(bag.upload_planes(L, h_coef, d_coef));
     uint8_t *d_px = nullptr;
     const size_t nbytes = (size_t)L->width * L->height * 3;
     JA_TRY(bag.alloc(nbytes, (void **)&d_px));
     JA_TRY(jpeg_amd_decode(ctx, L, d_coef, h_quanta, ntables, cosited, color, d_px));
     JA_TRY(bag.download(h_pixels, d_px, nbytes));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1597,14 +1616,12 @@ try {
     if (!h_coef || !h_rect) return JPEG_AMD_EINVAL;
     DeviceBag bag(ctx);
     const int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.upload(h_coef[p], plane_samples(L, p) * 2, (void **)&d_coef[p]));
+    JA_TRY(bag.upload_planes(L, h_coef, d_coef));
     uint16_t *d_rect = nullptr;
     JA_TRY(bag.alloc(rect_samples(L) * 2, (void **)&d_rect));
     JA_TRY(jpeg_amd_spectral_rectangular(ctx, L, d_coef, h_quanta, ntables, cosited, d_rect));
     JA_TRY(bag.download(h_rect, d_rect, rect_samples(L) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1618,11 +1635,10 @@ try {
     uint16_t *d_rect = nullptr;
     JA_TRY(bag.upload(h_rect, rect_samples(L) * 2, (void **)&d_rect));
     int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p) JA_TRY(bag.alloc(plane_samples(L, p) * 2, (void **)&d_coef[p]));
+    JA_TRY(bag.alloc_planes(L, d_coef));
     JA_TRY(jpeg_amd_rectangular_spectral(ctx, L, d_rect, h_quanta, ntables, d_coef));
-    for (int p = 0; p < L->nplanes; ++p) JA_TRY(bag.download(h_coef[p], d_coef[p], plane_samples(L, p) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    JA_TRY(bag.download_planes(L, h_coef, d_coef));
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1638,8 +1654,7 @@ try {
     JA_TRY(bag.alloc(npixels * nplanes * 2, (void **)&d_rect));
     JA_TRY(jpeg_amd_rectangular_pack(ctx, d_px, npixels, nplanes, color, d_rect));
     JA_TRY(bag.download(h_rect, d_rect, npixels * nplanes * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1653,13 +1668,10 @@ try {
     uint16_t *d_rect = nullptr;
     JA_TRY(bag.upload(h_rect, rect_samples(L) * 2, (void **)&d_rect));
     uint16_t *d_planes[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.alloc(plane_samples(L, p) * 2, (void **)&d_planes[p]));
+    JA_TRY(bag.alloc_planes(L, d_planes));
     JA_TRY(jpeg_amd_rectangular_decomposed(ctx, L, d_rect, d_planes));
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.download(h_planes[p], d_planes[p], plane_samples(L, p) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    JA_TRY(bag.download_planes(L, h_planes, d_planes));
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1673,16 +1685,11 @@ try {
     DeviceBag bag(ctx);
     const uint16_t *d_planes[JPEG_AMD_MAX_PLANES] = {};
     int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p) {
-        const size_t n = plane_samples(L, p);
-        JA_TRY(bag.upload(h_planes[p], n * 2, (void **)&d_planes[p]));
-        JA_TRY(bag.alloc(n * 2, (void **)&d_coef[p]));
-    }
+    JA_TRY(bag.upload_planes(L, h_planes, d_planes));
+    JA_TRY(bag.alloc_planes(L, d_coef));
     JA_TRY(jpeg_amd_planar_fdct(ctx, L, d_planes, h_quanta, ntables, d_coef));
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.download(h_coef[p], d_coef[p], plane_samples(L, p) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    JA_TRY(bag.download_planes(L, h_coef, d_coef));
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -1697,13 +1704,10 @@ try {
     uint8_t *d_px = nullptr;
     JA_TRY(bag.upload(h_pixels, (size_t)L->width * L->height * 3, (void **)&d_px));
     int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.alloc(plane_samples(L, p) * 2, (void **)&d_coef[p]));
+    JA_TRY(bag.alloc_planes(L, d_coef));
     JA_TRY(jpeg_amd_encode(ctx, L, d_px, color, h_quanta, ntables, d_coef));
-    for (int p = 0; p < L->nplanes; ++p)
-        JA_TRY(bag.download(h_coef[p], d_coef[p], plane_samples(L, p) * 2));
-    JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JPEG_AMD_OK;
+    JA_TRY(bag.download_planes(L, h_coef, d_coef));
+    return bag.finish();
 }
 JA_NOTHROW_TAIL
 
@@ -2338,13 +2342,10 @@ int jpeg_amd_spectral_transform_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *
     JA_TRY(plan_transform(L, op, region, &tp));
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef_in || !in_stride || !d_coef_out || !out_stride || (d_quanta_out && !d_quanta)) return JPEG_AMD_EINVAL;
-    PlaneSet cin{};
-    PlaneSetMut cout{};
-    for (int p = 0; p < L->nplanes; ++p) {
-        if (!d_coef_out[p] || (!d_coef_in[p] && plane_samples(L, p) != 0)) return JPEG_AMD_EINVAL;
-        cin.ptr[p] = d_coef_in[p]; cin.stride[p] = in_stride[p];
-        cout.ptr[p] = d_coef_out[p]; cout.stride[p] = out_stride[p];
-    }
+    PlaneSet cin;
+    PlaneSetMut cout;
+    JA_TRY(plane_set(L, d_coef_in, in_stride, false, &cin));
+    JA_TRY(plane_set(L, d_coef_out, out_stride, true, &cout));
     JA_HIP(ctx, launch_transform(ctx->stream, n_images, op, *L, tp.out, tp.ox, tp.oy, cin, QuantaRef{d_quanta, quanta_stride},
                                  d_quanta_out, cout, d_overflow));
     return JPEG_AMD_OK;
@@ -2361,8 +2362,7 @@ int jpeg_amd_spectral_transform(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int
     if (h_quanta_out) JA_TRY(stage_quanta(ctx, h_quanta_out, ntables, &d_qo));
     if (!ctx->d_flag) JA_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_flag), 256));
     JA_HIP(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(int32_t), ctx->stream));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    JA_TRY(jpeg_amd_spectral_transform_batch(ctx, L, 1, op, region, d_coef_in, zero, d_q, 0, ntables, d_qo, d_coef_out, zero,
+    JA_TRY(jpeg_amd_spectral_transform_batch(ctx, L, 1, op, region, d_coef_in, kOneImage, d_q, 0, ntables, d_qo, d_coef_out, kOneImage,
                                              ctx->d_flag));
     int32_t flag = 0;
     JA_HIP(ctx, hipMemcpyAsync(&flag, ctx->d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
@@ -2421,13 +2421,11 @@ int file_to_file(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, const 
         DeviceBag bag(ctx);
         const int16_t *d_in[JPEG_AMD_MAX_PLANES] = {};
         int16_t *d_out[JPEG_AMD_MAX_PLANES] = {};
-        for (int c = 0; c < nc; ++c) {
-            JA_TRY(bag.upload(coef[c], plane_samples(&L, c) * 2, (void **)&d_in[c]));
-            JA_TRY(bag.alloc(plane_samples(&O, c) * 2, (void **)&d_out[c]));
-        }
+        JA_TRY(bag.upload_planes<int16_t>(&L, coef, d_in));
+        JA_TRY(bag.alloc_planes(&O, d_out));
         JA_TRY(device(L, d_in, &quanta[0][0], nc, d_out));
-        for (int c = 0; c < nc; ++c) JA_TRY(bag.download(ocoef[c], d_out[c], plane_samples(&O, c) * 2));
-        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        JA_TRY(bag.download_planes(&O, ocoef, d_out));
+        JA_TRY(bag.finish());
     }
     // one table per distinct key, ascending
     std::vector<int32_t> tkeys;
@@ -2524,16 +2522,15 @@ int jpeg_amd_spectral_reduce_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, 
         if (plane_samples(L, p) == 0) return JPEG_AMD_EINVAL;      // no block whose edge could be replicated
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_coef_in || !in_stride || !d_coef_out || !out_stride || !d_quanta) return JPEG_AMD_EINVAL;
-    PlaneSet cin{};
-    PlaneSetMut cout{};
+    PlaneSet cin;
+    PlaneSetMut cout;
+    JA_TRY(plane_set(L, d_coef_in, in_stride, true, &cin));
+    JA_TRY(plane_set(L, d_coef_out, out_stride, true, &cout));
     for (int p = 0; p < L->nplanes; ++p) {
-        if (!d_coef_in[p] || !d_coef_out[p]) return JPEG_AMD_EINVAL;
         if (n_images > 1 && out_stride[p] < plane_samples(&O, p)) return JPEG_AMD_EINVAL;      // the images' outputs would overlap
         // the kernel loads and stores 16-byte pieces: every block of every image starts on a 16-byte boundary
         if (reinterpret_cast<uintptr_t>(d_coef_in[p]) % 16 || reinterpret_cast<uintptr_t>(d_coef_out[p]) % 16) return JPEG_AMD_EINVAL;
         if (n_images > 1 && (in_stride[p] % 8 || out_stride[p] % 8)) return JPEG_AMD_EINVAL;
-        cin.ptr[p] = d_coef_in[p]; cin.stride[p] = in_stride[p];
-        cout.ptr[p] = d_coef_out[p]; cout.stride[p] = out_stride[p];
     }
     JA_HIP(ctx, launch_spectral_reduce(ctx->stream, n_images, n, *L, O, cin, QuantaRef{d_quanta, quanta_stride}, d_quanta_out, cout));
     return JPEG_AMD_OK;
@@ -2552,8 +2549,7 @@ int jpeg_amd_spectral_reduce(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int de
     const uint16_t *d_q = nullptr, *d_qo = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
     if (h_quanta_out) JA_TRY(stage_quanta(ctx, h_quanta_out, ntables, &d_qo));
-    const size_t zero[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
-    JA_TRY(jpeg_amd_spectral_reduce_batch(ctx, L, 1, denom, d_coef_in, zero, d_q, 0, ntables, d_qo, d_coef_out, zero));
+    JA_TRY(jpeg_amd_spectral_reduce_batch(ctx, L, 1, denom, d_coef_in, kOneImage, d_q, 0, ntables, d_qo, d_coef_out, kOneImage));
     JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JPEG_AMD_OK;
 }

@@ -1,0 +1,144 @@
+"""The status of a refused call, entry point by entry point -- no GPU.  Every entry point that takes a context and device
+pointers is called with a NULL context (bind then returns EINVAL before any HIP call) under a small table of argument sets,
+one of them valid and the others wrong in one more way.  Most entry points look at the context first and so answer EINVAL
+whatever else is wrong; the view, resized and resize calls judge everything else first, and there the layout's verdict
+(ENOSUP for 12 bits) comes through.  The expected statuses are not reasoned out: they are what the library returned before
+the argument handling of capi.hip was gathered into one record, so a change of the order of checks shows here."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from jpeg_amd import _lib
+
+EINVAL, ENOSUP = -1, -5                                            # JPEG_AMD_EINVAL, JPEG_AMD_ENOSUP, as literals
+CASES = ("valid", "null layout", "12-bit layout", "two planes", "n_images = -1", "bad denominator or empty region")
+
+
+def _layout(factors, precision=8):
+    L = _lib.Layout()
+    L.width, L.height, L.precision, L.nplanes = 16, 16, precision, len(factors)
+    L.scale_x, L.scale_y = max(f[0] for f in factors), max(f[1] for f in factors)
+    for p, (fx, fy) in enumerate(factors):
+        L.factor_x[p], L.factor_y[p] = fx, fy
+        L.qi[p] = min(p, 1)
+    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
+    return L
+
+
+class Args:
+    """One argument set: a 16 x 16 4:2:0 layout and made-up non-null pointers (a host buffer stands in for the device's:
+    a refused call reads none of them), then the case's one change."""
+
+    def __init__(self, case):
+        f420 = [(2, 2), (1, 1), (1, 1)]
+        self.layout = _layout(f420[:2] if case == "two planes" else f420, 12 if case == "12-bit layout" else 8)
+        self.L = None if case == "null layout" else C.byref(self.layout)
+        self.precision = self.layout.precision
+        self.nplanes = self.layout.nplanes
+        self.n = -1 if case == "n_images = -1" else 1
+        bad = case == "bad denominator or empty region"
+        self.denom = 3 if bad else 2
+        self.buf = np.zeros(1024, np.uint16)
+        self.p = self.buf.ctypes.data                              # any pointer: tables, pixels, planes
+        self.pp = _lib.ptr_array([self.p] * 4)
+        self.sz = _lib.size_array([1024] * 4)
+        self.region = _lib.Region(0, 0, 0 if bad else 4, 4)
+        self.view = _lib.View(self.denom, _lib.Region(0, 0, 4, 4))
+        self.extent = _lib.Extent(4, 4)
+        self.r, self.v, self.e = C.byref(self.region), C.byref(self.view), C.byref(self.extent)
+
+
+RGB = _lib.COLOR_RGB8
+# name -> the arguments behind the context, from an Args
+CALLS = {
+    "jpeg_amd_decode_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.p, 768),
+    "jpeg_amd_decode": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.p),
+    "jpeg_amd_decode_region_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.r, a.p, 768),
+    "jpeg_amd_decode_region": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.r, a.p),
+    "jpeg_amd_decode_scaled_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.denom, a.p, 768),
+    "jpeg_amd_decode_scaled": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.denom, a.p),
+    "jpeg_amd_decode_view_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, a.p, 768),
+    "jpeg_amd_decode_view": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, a.p),
+    "jpeg_amd_decode_resized_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.p, 768),
+    "jpeg_amd_decode_resized": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 8, 8, a.p),
+    "jpeg_amd_resize_batch": lambda a: (a.n, a.p, 48, a.e, 8, 8, a.p, 192),
+    "jpeg_amd_encode_batch": lambda a: (a.L, a.n, a.p, 768, RGB, a.p, 64, 2, a.pp, a.sz),
+    "jpeg_amd_encode": lambda a: (a.L, a.p, RGB, a.p, 2, a.pp),
+    "jpeg_amd_spectral_rectangular_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, a.p, 768),
+    "jpeg_amd_spectral_rectangular": lambda a: (a.L, a.pp, a.p, 2, 0, a.p),
+    "jpeg_amd_rectangular_spectral_batch": lambda a: (a.L, a.n, a.p, 768, a.p, 64, 2, a.pp, a.sz),
+    "jpeg_amd_rectangular_spectral": lambda a: (a.L, a.p, a.p, 2, a.pp),
+    "jpeg_amd_spectral_transform_batch": lambda a: (a.L, a.n, 0, a.r, a.pp, a.sz, a.p, 64, 2, None, a.pp, a.sz, None),
+    "jpeg_amd_spectral_transform": lambda a: (a.L, 0, a.r, a.pp, a.p, 2, None, a.pp),
+    "jpeg_amd_spectral_reduce_batch": lambda a: (a.L, a.n, a.denom, a.pp, a.sz, a.p, 64, 2, None, a.pp, a.sz),
+    "jpeg_amd_spectral_reduce": lambda a: (a.L, a.denom, a.pp, a.p, 2, None, a.pp),
+    "jpeg_amd_spectral_expand_batch": lambda a: (a.L, a.n, a.p, 64, a.p, 64, None, a.pp, a.sz),
+    # the stages
+    "jpeg_amd_idct_plane": lambda a: (a.p, 2, 2, a.p, a.precision, a.p),
+    "jpeg_amd_spectral_idct": lambda a: (a.L, a.pp, a.p, 2, a.pp),
+    "jpeg_amd_spectral_idct_scaled": lambda a: (a.L, a.pp, a.p, 2, a.denom, a.pp),
+    "jpeg_amd_planar_interleaved": lambda a: (a.L, a.pp, 0, a.p),
+    "jpeg_amd_rectangular_unpack": lambda a: (a.p, 256, a.nplanes, RGB, a.p),
+    "jpeg_amd_rectangular_pack": lambda a: (a.p, 256, a.nplanes, RGB, a.p),
+    "jpeg_amd_rectangular_decomposed": lambda a: (a.L, a.p, a.pp),
+    "jpeg_amd_fdct_plane": lambda a: (a.p, 2, 2, a.p, a.precision, a.p),
+    "jpeg_amd_planar_fdct": lambda a: (a.L, a.pp, a.p, 2, a.pp),
+}
+
+# The statuses of the library before the change, in the order of CASES; a case that changes no argument of the call is left out
+# of it (None).
+_ = None
+BIND_FIRST = (EINVAL,) * 6
+EXPECTED = {
+    "jpeg_amd_decode_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_decode": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_decode_region_batch": BIND_FIRST,
+    "jpeg_amd_decode_region": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
+    "jpeg_amd_decode_scaled_batch": BIND_FIRST,
+    "jpeg_amd_decode_scaled": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
+    "jpeg_amd_decode_view_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_view": (EINVAL, EINVAL, ENOSUP, EINVAL, _, EINVAL),
+    "jpeg_amd_decode_resized_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_resized": (EINVAL, EINVAL, ENOSUP, EINVAL, _, EINVAL),
+    "jpeg_amd_resize_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_encode_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_encode": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_spectral_rectangular_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_spectral_rectangular": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_rectangular_spectral_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_rectangular_spectral": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_spectral_transform_batch": BIND_FIRST,
+    "jpeg_amd_spectral_transform": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
+    "jpeg_amd_spectral_reduce_batch": BIND_FIRST,
+    "jpeg_amd_spectral_reduce": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
+    "jpeg_amd_spectral_expand_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_idct_plane": (EINVAL, _, EINVAL, _, _, _),
+    "jpeg_amd_spectral_idct": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_spectral_idct_scaled": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
+    "jpeg_amd_planar_interleaved": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_rectangular_unpack": (EINVAL, _, _, EINVAL, _, _),
+    "jpeg_amd_rectangular_pack": (EINVAL, _, _, EINVAL, _, _),
+    "jpeg_amd_rectangular_decomposed": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+    "jpeg_amd_fdct_plane": (EINVAL, _, EINVAL, _, _, _),
+    "jpeg_amd_planar_fdct": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
+}
+
+
+assert set(CALLS) == set(EXPECTED)
+
+
+def statuses(name):
+    """The status of `name` with a NULL context under every case that applies to it."""
+    fn = getattr(_lib.lib(), name)
+    out = []
+    for case, want in zip(CASES, EXPECTED[name]):
+        a = Args(case)
+        out.append(None if want is None else fn(None, *CALLS[name](a)))
+    return tuple(out)
+
+
+@pytest.mark.parametrize("name", sorted(CALLS))
+def test_status_of_a_refused_call(name):
+    assert statuses(name) == EXPECTED[name]
+

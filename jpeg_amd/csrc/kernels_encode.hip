@@ -88,7 +88,8 @@ __device__ __forceinline__ void rgb_to_ycc(float r, float g, float b, float &y, 
 // step) and  n = trunc(y1 + copysign(pred(0.5), y1)).  tools/verify_div.hip proves by exhaustion
 // on the GPU that n equals the reference's integer for EVERY float numerator below 2^17 and
 // EVERY divisor an 8-bit quantisation table can produce (7140 divisors x 1.2e9 numerators,
-// profiles/r01_verify_div.txt); the fused kernel only runs for 8-bit formats.
+// profiles/r01_verify_div.txt); the fused kernel only runs for 8-bit formats.  That proof runs a copy of the formula; the
+// kernel as built is held to it by tests/test_gpu_quantiser.py, on exact ties H = 4 Q m under every Q = 1 .. 255.
 __device__ __forceinline__ void fdct_quantise(const float (&g)[64], const float *q, const float *rq,
                                               uint32_t (&w)[32])
 {

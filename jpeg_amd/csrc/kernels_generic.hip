@@ -712,7 +712,8 @@ __global__ __launch_bounds__(NT, (GEH == 64 ? 2 : 4)) void k_generic_encode(GenE
                     // trunc(y1 + copysign(pred(1/2), y1)): tools/verify_div16.hip proves by exhaustion on the GPU that the stored
                     // integer equals the reference's for EVERY divisor a 16-bit table can produce (Q = 1 .. 65535, all 64
                     // positions: 1.8 M divisors) and EVERY float numerator below 2^25 -- more than the FDCT of 16-bit samples
-                    // reaches (profiles/r06_verify_div16.txt).  Three operations instead of the ten of a true division.
+                    // reaches (profiles/r06_verify_div16.txt).  Three operations instead of the ten of a true division.  (The proof
+                    // runs a copy of the formula; tests/test_gpu_quantiser.py holds THIS kernel to it on exact ties at 8, 12, 16 bits.)
                     const float qq = sq[p][8 * h + k], rr = sr[p][8 * h + k];
                     const float y0 = res[h] * rr;
                     const float e1 = __builtin_fmaf(-y0, qq, res[h]);

@@ -723,6 +723,64 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, co
                             const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
                             const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels);
 
+/* ---- tensor output: resized views as normalised float tensors (CHW / HWC, horizontal flip) ------------
+ * The tail every training loop runs on a resized batch -- flip, permute, convert, subtract mean, divide by std, cast -- in
+ * the resample's own launch.  THE CONTRACT (the one statement of it): the tensor output defines no resample arithmetic of
+ * its own.  Let u(i, y, x, c) be the byte that jpeg_amd_resize_batch (or jpeg_amd_decode_resized_batch) defines for image i,
+ * row y, column x, channel c.  The element stored for (i, c, y, x) is
+ *   xs = flip[i] ? out_w - 1 - x : x            the RESAMPLED image mirrored; NOT a mirrored source rectangle
+ *   t  = (float)u(i, y, xs, c) - mean[c]        one binary32 operation
+ *   v  = t * scale[c]                           one binary32 operation, nothing contracted
+ *   element = v                                 JPEG_AMD_F32
+ *           | v rounded to binary16             JPEG_AMD_F16, round to nearest even
+ *           | v rounded to bfloat16             JPEG_AMD_BF16, round to nearest even: with `bits` the binary32 pattern of v,
+ *                                               (bits + 0x7fff + ((bits >> 16) & 1)) >> 16
+ * mean is in BYTE units (255 * 0.485, say) and scale is what the caller wants multiplied (1 / (255 * 0.229)), both rounded
+ * to binary32 by the caller: the kernel holds no division.  There are always three channels, like the byte calls (grey
+ * layouts give three equal bytes there), and `color` passes through unchanged.
+ * Layouts, in ELEMENTS, image i at d_dst + i * dst_stride elements:
+ *   JPEG_AMD_TENSOR_HWC   element (y * out_w + x) * 3 + c
+ *   JPEG_AMD_TENSOR_CHW   element (c * out_h + y) * out_w + x
+ * Elements in the stride gaps are left alone. */
+enum { JPEG_AMD_F32 = 0, JPEG_AMD_F16 = 1, JPEG_AMD_BF16 = 2 };
+enum { JPEG_AMD_TENSOR_HWC = 0, JPEG_AMD_TENSOR_CHW = 1 };
+typedef struct jpeg_amd_tensor_spec {
+    int32_t dtype;    /* JPEG_AMD_F32 | JPEG_AMD_F16 | JPEG_AMD_BF16 */
+    int32_t layout;   /* JPEG_AMD_TENSOR_HWC | JPEG_AMD_TENSOR_CHW */
+    float mean[3], scale[3];
+} jpeg_amd_tensor_spec;
+
+/* Host only, pure.  *elem_bytes = the element size (4, 2, 2) and *image_elems = 3 * out_w * out_h (either pointer may be
+ * NULL).  EINVAL for a NULL spec, an unknown dtype or layout, a mean or scale that is not finite, or an out_w / out_h that
+ * jpeg_amd_resize_batch refuses. */
+int jpeg_amd_tensor_extent(const jpeg_amd_tensor_spec *spec, int32_t out_w, int32_t out_h, size_t *elem_bytes,
+                           size_t *image_elems);
+/* The resample and the output stage alone, one launch.  Sources, src_stride, h_extents, out_w and out_h as in
+ * jpeg_amd_resize_batch.  h_flip: a HOST array of n_images bytes, nonzero = mirror image i; NULL = none.  spec and h_flip are
+ * copied before the call returns.  d_dst is aligned to the element size; dst_stride, in elements, >= 3 * out_w * out_h (any
+ * value, 0 included, when n_images == 1).  Everything is validated before anything is enqueued: on EINVAL -- what
+ * jpeg_amd_tensor_extent refuses, a misaligned d_dst, a stride that is too small, a null pointer, and whatever
+ * jpeg_amd_resize_batch refuses -- nothing is written and the context stays usable.  n_images == 0 is OK. */
+int jpeg_amd_resize_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride);
+/* Views to tensor: every argument up to out_h as in jpeg_amd_decode_resized_batch, spec, h_flip, d_dst and dst_stride as
+ * above; whatever either refuses is refused here, before anything is enqueued.
+ * Cost: exactly jpeg_amd_decode_resized_batch's route -- jpeg_amd_decode_view_batch, as it stands, into the context's
+ * buffer in chunks of at most 1 GiB, then ONE launch per chunk that resamples and writes the elements.  Every layout of the
+ * view call works, its fallback layouts included. */
+int jpeg_amd_decode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                 int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                 void *d_dst, size_t dst_stride);
+/* single image, host tables; flip: nonzero = mirrored */
+int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_view *view, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
+                           int flip, void *d_dst);
+
 /* ---- spectral reduce: a Spectral at 1/2, 1/4 or 1/8 size, coefficients in and coefficients out ----------
  * JPEG in, smaller JPEG out, without pixels in between: no interleave, no colour conversion and no second generation of
  * chroma rounding, so every layout, plane count and precision is served alike.  It composes two contracts that are stated

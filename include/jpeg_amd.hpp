@@ -338,6 +338,21 @@ class spectral {
                                       cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, px.data()), "jpeg_amd_decode_resized");
         return px.host();
     }
+    /// decode_resized(target, view, out_w, out_h, cosite) through the output stage of `spec`, mirrored along x if `flip`:
+    /// the raw bytes of the 3 * out_w * out_h elements in spec's dtype and layout (jpeg_amd.h, "tensor output")
+    std::vector<uint8_t> decode_tensor(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h,
+                                       const jpeg_amd_tensor_spec &spec, bool flip = false, bool cosite = false) const
+    {
+        jpeg_amd_layout l = lay.c_layout(size, units, q);
+        size_t elem_bytes = 0, elems = 0;
+        check(jpeg_amd_tensor_extent(&spec, out_w, out_h, &elem_bytes, &elems), "jpeg_amd_tensor_extent");
+        device_array<uint8_t> px(*ctx, elem_bytes * elems);
+        auto in = detail::pointers(planes);
+        check(jpeg_amd_decode_tensor(ctx->handle(), &l, const_cast<const int16_t *const *>(in.data()), tables.data(), ntables(),
+                                     cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, &spec, flip ? 1 : 0, px.data()),
+              "jpeg_amd_decode_tensor");
+        return px.host();
+    }
 
     /// this image at 1 / denom size (denom 2 | 4 | 8), coefficients to coefficients in one launch: every plane's scaled
     /// samples through Spectral.Plane.fdct with the same tables (jpeg_amd.h, "spectral reduce")

@@ -133,6 +133,11 @@ SIGNATURES = {
     "jpeg_amd_decode_resized_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, C.c_int32,
                                                 C.c_int32, _p, C.c_size_t]),
     "jpeg_amd_decode_resized": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p]),
+    "jpeg_amd_tensor_extent": (C.c_int, [_p, C.c_int32, C.c_int32, _szp, _szp]),
+    "jpeg_amd_resize_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, C.c_int32,
+                                               C.c_int32, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, C.c_int, _p]),
     "jpeg_amd_reduce_layout": (C.c_int, [_L, C.c_int, _L]),
     "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
     "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
@@ -154,6 +159,14 @@ class Extent(C.Structure):
     """struct jpeg_amd_extent"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)]
 
+
+class TensorSpec(C.Structure):
+    """struct jpeg_amd_tensor_spec"""
+    _fields_ = [("dtype", C.c_int32), ("layout", C.c_int32), ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
+F32, F16, BF16 = 0, 1, 2                # JPEG_AMD_F32 ...
+TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V
 XFORM_TRANSPOSE, XFORM_FLIP_H, XFORM_FLIP_V = 1, 2, 4

@@ -793,18 +793,40 @@ def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     return out.view(n, ht, wt, 3)
 
 
+def _crop_views(size, source_regions, out_size) -> np.ndarray:
+    """The views of decode_crops_resized / decode_crops_tensor: int32 [n, 5] of (denom, x, y, width, height)."""
+    regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
+    views = np.empty((regs.shape[0], 5), np.int32)
+    for i, r in enumerate(regs.tolist()):
+        denom = view_denom(r[2:], out_size)
+        views[i] = (denom,) + view_of_source(size, denom, r)
+    return views
+
+
 def decode_crops_resized(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size,
                          q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
     """The data-loader call: per image a rectangle (x, y, width, height) of the FULL-SIZE image, decoded at the cheapest
     denominator that is still no smaller than out_size -- view_denom((width, height), out_size), then view_of_source -- and
     resampled to out_size (Wt, Ht) by decode_resized.  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
     [n, 5] of (denom, x, y, width, height))."""
-    regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
-    views = np.empty((regs.shape[0], 5), np.int32)
-    for i, r in enumerate(regs.tolist()):
-        denom = view_denom(r[2:], out_size)
-        views[i] = (denom,) + view_of_source(size, denom, r)
+    views = _crop_views(size, source_regions, out_size)
     return decode_resized(ctx, size, layout, planes, quanta, views, out_size, q=q, color=color, cosite=cosite), views
+
+
+def _pack_images(ctx: Context, images):
+    """Device uint8 images [h_i, w_i, 3] packed into one allocation (torch copies) -> (it, its stride, the extents)."""
+    torch = _torch()
+    n = len(images)
+    for im in images:
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError("images: uint8 device tensors [h, w, 3]")
+    src_stride = max([int(im.numel()) for im in images] or [0])
+    src = ctx.empty(n * src_stride, torch.uint8)
+    extents = (_lib.Extent * max(n, 1))()
+    for i, im in enumerate(images):
+        src[i * src_stride:i * src_stride + im.numel()].copy_(im.reshape(-1))
+        extents[i].width, extents[i].height = int(im.shape[1]), int(im.shape[0])
+    return src, src_stride, extents
 
 
 def resize(ctx: Context, images, out_size):
@@ -813,21 +835,87 @@ def resize(ctx: Context, images, out_size):
     torch = _torch()
     images = list(images)
     n = len(images)
-    for im in images:
-        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
-            raise ValueError("images: uint8 device tensors [h, w, 3]")
+    src, src_stride, extents = _pack_images(ctx, images)
     wt, ht = int(out_size[0]), int(out_size[1])
-    src_stride = max([int(im.numel()) for im in images] or [0])
-    src = ctx.empty(n * src_stride, torch.uint8)
-    extents = (_lib.Extent * max(n, 1))()
-    for i, im in enumerate(images):
-        src[i * src_stride:i * src_stride + im.numel()].copy_(im.reshape(-1))
-        extents[i].width, extents[i].height = int(im.shape[1]), int(im.shape[0])
     stride = 3 * max(wt, 0) * max(ht, 0)
     out = ctx.empty(n * stride, torch.uint8)
     _lib.check(_lib.lib().jpeg_amd_resize_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, out.data_ptr(), stride),
                "jpeg_amd_resize_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
+
+
+def tensor_spec(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.TensorSpec:
+    """The output stage of the tensor calls (struct jpeg_amd_tensor_spec) from the torchvision convention: mean and std per
+    channel in 0 ... 1 units give mean_b = float32(255 mean) and scale = float32(1 / (255 std)), each computed in float64 and
+    rounded once; element = (byte - mean_b) * scale.  mean=None: mean_b = 0; std=None: scale = 1 (both None: the bytes
+    themselves as floats).  dtype: torch.float32, torch.float16 (the default) or torch.bfloat16; layout: "chw" or "hwc"."""
+    torch = _torch()
+    dtype = torch.float16 if dtype is None else dtype
+    codes = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+    layouts = {"hwc": _lib.TENSOR_HWC, "chw": _lib.TENSOR_CHW}
+    if dtype not in codes or str(layout).lower() not in layouts:
+        raise ValueError("tensor_spec: dtype float32 / float16 / bfloat16, layout 'chw' / 'hwc'")
+    spec = _lib.TensorSpec()
+    spec.dtype, spec.layout = codes[dtype], layouts[str(layout).lower()]
+    for c in range(3):
+        spec.mean[c] = 0.0 if mean is None else float(np.float32(255.0 * float(mean[c])))
+        spec.scale[c] = 1.0 if std is None else float(np.float32(1.0 / (255.0 * float(std[c]))))
+    return spec
+
+
+def _tensor_out(ctx: Context, n: int, out_size, spec: _lib.TensorSpec, flips):
+    """-> (wt, ht, the output tensor [n * 3 wt ht], its stride in elements, the flip bytes or None)."""
+    torch = _torch()
+    wt, ht = int(out_size[0]), int(out_size[1])
+    dtype = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}.get(spec.dtype, torch.float32)
+    stride = 3 * max(wt, 0) * max(ht, 0)
+    h_flip = None
+    if flips is not None:
+        f = np.ascontiguousarray(np.asarray(flips).reshape(-1) != 0, np.uint8)
+        if f.size != n:
+            raise ValueError("flips: one flag per image")
+        h_flip = (C.c_uint8 * max(n, 1))(*f.tolist())
+    return wt, ht, ctx.empty(n * stride, dtype), stride, h_flip
+
+
+def _tensor_view(out, n, wt, ht, spec):
+    return out.view(n, 3, ht, wt) if spec.layout == _lib.TENSOR_CHW else out.view(n, ht, wt, 3)
+
+
+def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, spec: _lib.TensorSpec, flips=None,
+                   q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+    """decode_resized with the loader's tail in the same call (jpeg_amd_decode_tensor_batch; include/jpeg_amd.h, "tensor
+    output", holds the contract): every view resampled to out_size (Wt, Ht), mirrored along x where flips[i] is set,
+    normalised by `spec` (tensor_spec) and stored in its dtype and layout.  Returns one tensor [n, 3, Ht, Wt] ("chw") or
+    [n, Ht, Wt, 3] ("hwc")."""
+    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    n = vs.shape[0]
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_batch(
+        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
+        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, wt, ht, C.byref(spec), h_flip,
+        out.data_ptr(), stride), "jpeg_amd_decode_tensor_batch", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec)
+
+
+def decode_crops_tensor(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size, spec: _lib.TensorSpec,
+                        flips=None, q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+    """The data-loader call, to the tensor a training loop takes: the views decode_crops_resized chooses for the rectangles
+    (x, y, width, height) of the FULL-SIZE images, through decode_tensors.  Returns (tensor, the views as int32 [n, 5])."""
+    views = _crop_views(size, source_regions, out_size)
+    return decode_tensors(ctx, size, layout, planes, quanta, views, out_size, spec, flips=flips, q=q, color=color, cosite=cosite), views
+
+
+def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None):
+    """The resample and the output stage alone (jpeg_amd_resize_tensor_batch): n device uint8 images [h_i, w_i, 3] of any
+    sizes to one tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3] of spec's dtype, in one launch."""
+    images = list(images)
+    n = len(images)
+    src, src_stride, extents = _pack_images(ctx, images)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_resize_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, C.byref(spec), h_flip,
+                                                       out.data_ptr(), stride), "jpeg_amd_resize_tensor_batch", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec)
 
 
 def _dedupe_q(layout: Layout) -> List[int]:

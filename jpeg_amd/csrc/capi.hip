@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1179,7 +1180,7 @@ constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chu
 // The scale factors of the contract: divided here, in binary32, never on the device.
 ResizeRecord resize_record(uint64_t offset, int32_t w, int32_t h, int32_t out_w, int32_t out_h)
 {
-    return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h};
+    return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h, 0u, 0u};
 }
 
 // The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
@@ -1199,6 +1200,47 @@ int check_resize_target(int n_images, int32_t out_w, int32_t out_h, const uint8_
     if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
     if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
     if (n_images > 1 && dst_stride < (size_t)3 * out_w * out_h) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// The chunks of jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch: consecutive images, m images at a stride of the
+// chunk's largest view, at most kResizeChunkBytes in all; rec[i] is image i's record inside its chunk.  Returns the bytes the
+// largest chunk needs.
+struct ResizeChunk { int i0, m; size_t stride; };
+size_t plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const uint8_t *h_flip,
+                          std::vector<ResizeChunk> &chunks, std::vector<ResizeRecord> &rec)
+{
+    size_t need = 0;
+    for (int i0 = 0; i0 < n_images;) {
+        int m = 0;
+        size_t stride = 0;
+        for (; i0 + m < n_images; ++m) {
+            const jpeg_amd_region &r = h_views[i0 + m].region;
+            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
+            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
+            stride = s;
+        }
+        for (int j = 0; j < m; ++j) {
+            const jpeg_amd_region &r = h_views[i0 + j].region;
+            rec[(size_t)(i0 + j)] = resize_record((uint64_t)j * stride, r.width, r.height, out_w, out_h);
+            rec[(size_t)(i0 + j)].flip = h_flip && h_flip[i0 + j] ? 1u : 0u;
+        }
+        chunks.push_back(ResizeChunk{i0, m, stride});
+        need = std::max(need, stride * (size_t)m);
+        i0 += m;
+    }
+    return need;
+}
+
+// What the tensor calls require of the output, beyond jpeg_amd_tensor_extent.
+int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const void *d_dst,
+                        size_t dst_stride, size_t *elem_bytes)
+{
+    size_t image_elems = 0;
+    JA_TRY(jpeg_amd_tensor_extent(spec, out_w, out_h, elem_bytes, &image_elems));
+    if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
+    if ((uintptr_t)d_dst % *elem_bytes != 0) return JPEG_AMD_EINVAL;
+    if (n_images > 1 && dst_stride < image_elems) return JPEG_AMD_EINVAL;
     return JPEG_AMD_OK;
 }
 
@@ -1249,33 +1291,14 @@ try {
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
 
-    // chunks of consecutive images: m images at a stride of the chunk's largest view, at most kResizeChunkBytes in all
-    struct Chunk { int i0, m; size_t stride; };
-    std::vector<Chunk> chunks;
+    std::vector<ResizeChunk> chunks;
     std::vector<ResizeRecord> rec((size_t)n_images);
-    size_t need = 0;
-    for (int i0 = 0; i0 < n_images;) {
-        int m = 0;
-        size_t stride = 0;
-        for (; i0 + m < n_images; ++m) {
-            const jpeg_amd_region &r = h_views[i0 + m].region;
-            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
-            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
-            stride = s;
-        }
-        for (int j = 0; j < m; ++j) {
-            const jpeg_amd_region &r = h_views[i0 + j].region;
-            rec[(size_t)(i0 + j)] = resize_record((uint64_t)j * stride, r.width, r.height, out_w, out_h);
-        }
-        chunks.push_back(Chunk{i0, m, stride});
-        need = std::max(need, stride * (size_t)m);
-        i0 += m;
-    }
+    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, nullptr, chunks, rec);
     JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
     JA_TRY(upload_records(ctx, rec));
     uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
     const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
-    for (const Chunk &k : chunks) {
+    for (const ResizeChunk &k : chunks) {
         const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
         const DecodeCall part = c.images(k.i0, k.m, coef);
         JA_TRY(jpeg_amd_decode_view_batch(ctx, L, k.m, coef, coef_stride, part.d_quanta, quanta_stride, ntables, cosited, color,
@@ -1298,6 +1321,106 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const i
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
     return jpeg_amd_decode_resized_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, d_pixels,
                                          0);
+}
+
+int jpeg_amd_tensor_extent(const jpeg_amd_tensor_spec *spec, int32_t out_w, int32_t out_h, size_t *elem_bytes, size_t *image_elems)
+{
+    if (!spec) return JPEG_AMD_EINVAL;
+    if (spec->dtype != JPEG_AMD_F32 && spec->dtype != JPEG_AMD_F16 && spec->dtype != JPEG_AMD_BF16) return JPEG_AMD_EINVAL;
+    if (spec->layout != JPEG_AMD_TENSOR_HWC && spec->layout != JPEG_AMD_TENSOR_CHW) return JPEG_AMD_EINVAL;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(spec->mean[c]) || !std::isfinite(spec->scale[c])) return JPEG_AMD_EINVAL;
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
+    if (elem_bytes) *elem_bytes = spec->dtype == JPEG_AMD_F32 ? 4 : 2;
+    if (image_elems) *image_elems = (size_t)3 * out_w * out_h;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_resize_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    // every argument first, the context last, as jpeg_amd_resize_batch
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    size_t elem_bytes = 0;
+    JA_TRY(check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes));
+    std::vector<ResizeRecord> rec((size_t)n_images);
+    if (n_images > 0) {
+        if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
+        for (int i = 0; i < n_images; ++i) {
+            const jpeg_amd_extent &e = h_extents[i];
+            if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
+            if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
+            rec[(size_t)i] = resize_record((uint64_t)i * src_stride, e.width, e.height, out_w, out_h);
+            rec[(size_t)i].flip = h_flip && h_flip[i] ? 1u : 0u;
+        }
+    }
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+    JA_TRY(upload_records(ctx, rec));
+    JA_HIP(ctx, launch_resize_tensor(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), out_w,
+                                     out_h, *spec, d_dst, dst_stride));
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                 int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                 void *d_dst, size_t dst_stride)
+try {
+    // jpeg_amd_decode_resized_batch with another last launch: the same refusals in the same order, the same chunks
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                       static_cast<uint8_t *>(d_dst), 0};
+    DecodeCall views = c;
+    views.pixel_stride = ~(size_t)0;
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
+    size_t elem_bytes = 0;
+    JA_TRY(check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes));
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+
+    std::vector<ResizeChunk> chunks;
+    std::vector<ResizeRecord> rec((size_t)n_images);
+    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, h_flip, chunks, rec);
+    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
+    JA_TRY(upload_records(ctx, rec));
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
+    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
+    for (const ResizeChunk &k : chunks) {
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall part = c.images(k.i0, k.m, coef);
+        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, k.m, coef, coef_stride, part.d_quanta, quanta_stride, ntables, cosited, color,
+                                          h_views + k.i0, d_views, k.stride));
+        JA_HIP(ctx, launch_resize_tensor(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, *spec,
+                                         static_cast<uint8_t *>(d_dst) + (size_t)k.i0 * dst_stride * elem_bytes, dst_stride));
+    }
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_view *view, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
+                           int flip, void *d_dst)
+{
+    // as jpeg_amd_decode_resized: what can be refused is refused before a table is staged
+    JA_TRY(check_one_view(L, ntables, color, view));
+    size_t elem_bytes = 0;
+    JA_TRY(check_tensor_target(1, out_w, out_h, spec, d_dst, 0, &elem_bytes));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const uint8_t h_flip = flip ? 1 : 0;
+    return jpeg_amd_decode_tensor_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, spec,
+                                        &h_flip, d_dst, 0);
 }
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,

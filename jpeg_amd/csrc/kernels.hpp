@@ -144,11 +144,21 @@ struct ResizeRecord {
     uint64_t offset;   // bytes from d_src
     int32_t  w, h;     // > 0
     float    kx, ky;   // (float)w / (float)out_w, (float)h / (float)out_h
+    uint32_t flip;     // k_resize_tensor only: nonzero = the resampled image is stored mirrored along x
+    uint32_t reserved;
 };
 constexpr int kResizeMaxSide = 1 << 30;          // of the output: the kernel's pixel indices are int
 uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the launch's grid.x, which holds 2^31 - 1 at most
 hipError_t launch_resize_bilinear(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
                                   int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
+
+// ---- resample to a normalised tensor (kernels_tensor.hip) ------------------------------------------------
+// The resample above with the output stage of include/jpeg_amd.h ("tensor output") in the same launch (k_resize_tensor): the
+// byte of (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted to spec.dtype and stored in
+// spec.layout.  d_dst and dst_stride in ELEMENTS of spec.dtype; d_dst aligned to the element.  spec is valid
+// (jpeg_amd_tensor_extent), the other arguments as launch_resize_bilinear.
+hipError_t launch_resize_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
+                                int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
 
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op

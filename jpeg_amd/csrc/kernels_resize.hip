@@ -1,7 +1,7 @@
 // kernels_resize.hip -- bilinear resample of pixel images to one target size (jpeg_amd_resize_batch, and behind
 // jpeg_amd_decode_view_batch in jpeg_amd_decode_resized_batch).  include/jpeg_amd.h ("resized decode") holds the contract:
 // half-pixel centres, the horizontal pass first, every operation one binary32 operation, the scale factors divided on the
-// host.  axis_tap and resample below are that text, statement by statement.
+// host.  axis_tap and resample (resample.hpp, shared with k_resize_tensor) are that text, statement by statement.
 //
 // k_resize_bilinear: a static grid of (tiles of the output) x (images); the output size is the same for every image, so
 // there is no prefix and no search.  A tile is 64 x 32 output pixels.  Its workgroup
@@ -21,16 +21,11 @@
 
 #include "fused_common.hpp"
 #include "kernels.hpp"
+#include "resample.hpp"
 
 namespace jpeg_amd {
 
 namespace {
-
-constexpr int kTileW = 64, kTileH = 32;    // output pixels per tile
-constexpr int kRun = 4;                    // output pixels per work-item and row: 12 bytes, three dwords
-constexpr int kLanesX = kTileW / kRun;     // work-items across a tile
-constexpr int kRowStep = kThreads / kLanesX;
-static_assert(kTileW + kTileH <= kThreads && kTileH % kRowStep == 0 && kThreads % kLanesX == 0, "roles");
 
 struct ResizeArgs {
     const uint8_t *src;
@@ -40,25 +35,6 @@ struct ResizeArgs {
     uint8_t *dst;
     size_t dst_stride;   // bytes between output images
 };
-
-// One axis of the contract: output index j of an axis of n source samples, k = (float)n / (float)n_out.
-__device__ __forceinline__ void axis_tap(int j, float k, int n, int &i0, int &i1, float &f)
-{
-    float s = ((float)j + 0.5f) * k - 0.5f;
-    s = fmaxf(s, 0.0f);
-    i0 = min((int)s, n - 1);
-    i1 = min(i0 + 1, n - 1);
-    f = s - (float)i0;
-}
-
-// One channel: the horizontal pass on both rows, the vertical pass, the clamping byte conversion.
-__device__ __forceinline__ uint32_t resample(float a, float b, float c, float d, float fx, float fy)
-{
-    const float top = a + fx * (b - a);
-    const float bot = c + fx * (d - c);
-    const float v = top + fy * (bot - top);
-    return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f);
-}
 
 // nbytes <= 12 bytes, little-endian in (w0, w1, w2), to o: bytes up to the first 4-byte boundary, dwords from there, bytes
 // behind the last whole dword.

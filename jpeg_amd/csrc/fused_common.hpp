@@ -61,18 +61,13 @@ __device__ __forceinline__ void lds_dma16_s(uint64_t sbase, uint32_t voff, uint3
 }
 // The same two without the `nt` hint: for coefficients that neighbouring strips fetch again soon
 // (the chroma blocks around a 4:2:0 strip) and should therefore stay in L2.
-#ifdef JA_X_IN420_NT
-#define JA_KEEP_HINT " nt"
-#else
-#define JA_KEEP_HINT ""
-#endif
 __device__ __forceinline__ void lds_dma16_keep(const void *g, uint32_t lds)
 {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" JA_KEEP_HINT ::"v"(g), "s"(lds) : "memory");
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds) : "memory");
 }
 __device__ __forceinline__ void lds_dma16_s_keep(uint64_t sbase, uint32_t voff, uint32_t lds)
 {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" JA_KEEP_HINT ::"s"(sbase), "v"(voff), "s"(lds) : "memory");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds) : "memory");
 }
 // A RUN of N consecutive 1 KiB pieces (a contiguous source, a contiguous destination): the instruction's offset field moves
 // the global source AND the LDS destination (tools/probe_dma_offset.hip), so the whole run needs one M0 write and one
@@ -86,7 +81,7 @@ __device__ __forceinline__ void lds_dma16_run(uint64_t sbase, uint32_t v0, uint3
             asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0 nt\n\tglobal_load_lds_dwordx4 %2, %0 offset:1024 nt"
                          ::"s"(sbase), "v"(v0), "v"(v1), "s"(lds) : "memory");
         else
-            asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" JA_KEEP_HINT "\n\tglobal_load_lds_dwordx4 %2, %0 offset:1024" JA_KEEP_HINT
+            asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0\n\tglobal_load_lds_dwordx4 %2, %0 offset:1024"
                          ::"s"(sbase), "v"(v0), "v"(v1), "s"(lds) : "memory");
     } else {
         if constexpr (NT)
@@ -94,8 +89,8 @@ __device__ __forceinline__ void lds_dma16_run(uint64_t sbase, uint32_t v0, uint3
                          "global_load_lds_dwordx4 %1, %0 offset:2048 nt\n\tglobal_load_lds_dwordx4 %2, %0 offset:3072 nt"
                          ::"s"(sbase), "v"(v0), "v"(v1), "s"(lds) : "memory");
         else
-            asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" JA_KEEP_HINT "\n\tglobal_load_lds_dwordx4 %2, %0 offset:1024" JA_KEEP_HINT "\n\t"
-                         "global_load_lds_dwordx4 %1, %0 offset:2048" JA_KEEP_HINT "\n\tglobal_load_lds_dwordx4 %2, %0 offset:3072" JA_KEEP_HINT
+            asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0\n\tglobal_load_lds_dwordx4 %2, %0 offset:1024\n\t"
+                         "global_load_lds_dwordx4 %1, %0 offset:2048\n\tglobal_load_lds_dwordx4 %2, %0 offset:3072"
                          ::"s"(sbase), "v"(v0), "v"(v1), "s"(lds) : "memory");
     }
 }
@@ -111,18 +106,18 @@ __device__ __forceinline__ void lds_dma16_brun(i32x4_t srd, uint32_t soff, uint3
 #define JA_BL(v, off, hint) "buffer_load_dwordx4 " v ", %0, %1 offen" off hint " lds"
     if constexpr (N == 1) {
         if constexpr (NT) asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", " nt") ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
-        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", JA_KEEP_HINT) ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
+        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", "") ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
     } else if constexpr (N == 2) {
         if constexpr (NT) asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", " nt") "\n\t" JA_BL("%3", " offset:1024", " nt")
                                        ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
-        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", JA_KEEP_HINT) "\n\t" JA_BL("%3", " offset:1024", JA_KEEP_HINT)
+        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", "") "\n\t" JA_BL("%3", " offset:1024", "")
                           ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
     } else {
         if constexpr (NT) asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", " nt") "\n\t" JA_BL("%3", " offset:1024", " nt") "\n\t"
                                        JA_BL("%2", " offset:2048", " nt") "\n\t" JA_BL("%3", " offset:3072", " nt")
                                        ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
-        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", JA_KEEP_HINT) "\n\t" JA_BL("%3", " offset:1024", JA_KEEP_HINT) "\n\t"
-                          JA_BL("%2", " offset:2048", JA_KEEP_HINT) "\n\t" JA_BL("%3", " offset:3072", JA_KEEP_HINT)
+        else asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\t" JA_BL("%2", "", "") "\n\t" JA_BL("%3", " offset:1024", "") "\n\t"
+                          JA_BL("%2", " offset:2048", "") "\n\t" JA_BL("%3", " offset:3072", "")
                           ::"s"(srd), "s"(soff), "v"(v0), "v"(v1), "s"(lds) : "memory");
     }
 #undef JA_BL
@@ -187,9 +182,6 @@ __device__ __forceinline__ uint32_t lds_peek(uint32_t *counter)
 }
 __device__ __forceinline__ void lds_wait_ge(uint32_t *counter, uint32_t target)
 {
-#ifdef JA_X_NOSYNC   // experiment (wrong pixels): what do the waits of the stack walk cost?
-    return;
-#endif
     asm volatile("" ::: "memory");
     while ((uint32_t)__builtin_amdgcn_readfirstlane((int)lds_peek(counter)) < target) __builtin_amdgcn_s_sleep(1);
     asm volatile("" ::: "memory");
@@ -197,9 +189,6 @@ __device__ __forceinline__ void lds_wait_ge(uint32_t *counter, uint32_t target)
 // the same when the counter was already read a while ago (`seen`, any lane's copy): the common case costs no LDS round trip
 __device__ __forceinline__ void lds_wait_ge_seen(uint32_t *counter, uint32_t target, uint32_t seen)
 {
-#ifdef JA_X_NOSYNC
-    return;
-#endif
     if ((uint32_t)__builtin_amdgcn_readfirstlane((int)seen) < target) lds_wait_ge(counter, target);
     asm volatile("" ::: "memory");
 }
@@ -214,13 +203,8 @@ __device__ __forceinline__ void lds_wait_ge_seen(uint32_t *counter, uint32_t tar
 // Precondition of every trunc_* helper: the wave runs in the default f32 rounding mode (round to nearest even, MODE[1:0] =
 // 0) -- the statement restores THAT, not a saved value (s_getreg + s_setreg_b32 would cost two more scalar slots per
 // pack; no kernel of this library ever leaves another mode set).
-#ifdef JA_X_NOSETREG   // experiment (wrong pixels): the packs without the two mode switches
-#define JA_RTZ_ON ""
-#define JA_RTZ_OFF ""
-#else
 #define JA_RTZ_ON "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\t"
 #define JA_RTZ_OFF "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0"
-#endif
 __device__ __forceinline__ void trunc_pack8(const float *c, uint32_t *d)
 {
     asm volatile(JA_RTZ_ON

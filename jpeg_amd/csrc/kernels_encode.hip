@@ -5,11 +5,11 @@
 // are subsampled 1x or 2x per axis, and for y8 images, without materialising Rectangular /
 // Planar in HBM: one kernel, RGB8 (or YCbCr8) bytes in, quantised zigzag coefficients out.
 //
-// One workgroup = one tile of 32 x 16 luma blocks (256 x 128 px); a work-item converts and
-// transforms two luma blocks (rows t/32 and t/32 + 8 of the tile), pools their chroma into an
+// One workgroup = one tile of 32 x 8 luma blocks (256 x 64 px); a work-item converts and
+// transforms one luma block (row t/32 of the tile), pools its chroma into an
 // LDS tile (box filter of encode.swift:402-423: the window of a 2x subsampled sample lies
 // inside one 8x8 luma block, so no halo is needed), and after one barrier transforms its
-// share of the tile's chroma blocks (one per work-item for 4:2:0).
+// share of the tile's chroma blocks (4:2:0: half of the work-items one each; 4:2:2 / 4:4:0: one per work-item).
 //
 // Arithmetic is the reference's, op for op (-ffp-contract=off): colour matrix
 // jpeg.swift:463-478, FDCT encode.swift:123-196, true IEEE division by the modulated table and
@@ -19,13 +19,14 @@
 //     [0.5, 255.5], so floor() alone is clamp + truncate;
 //   - Float(sum) / Float(n) truncated, n in {1, 2, 4}, is floor(sum * (1/n)) exactly.
 //
-// Development switches (tools/build_exp.sh, never in the product build): JA_X_ENC_NOSTORE,
-// JA_X_ENC_L2LOAD -- the kernel without its stores / with every load hitting L2; JA_X_ENC_NOCOMPUTE -- its memory traffic with next to no
-// arithmetic (round 6, profiles/r06_ablate_encode.txt: memory alone and arithmetic alone need the same 71 us at 8192 x 8192, the kernel 93);
-// JA_X_ENC_NOCHROMA -- without the two-wave
-// chroma tail of a tile (round 4: 23.6 -> 19.3 us at 4096 x 4096, 86.1 -> 68.7 at 8192 x 8192: the tail's share of the
-// tile's instructions, 18 %, is its share of the time -- the kernel is bound by the instructions it issues in all, not by
-// the longest wave); JA_X_ENC_TY, JA_X_ENC_PERHALF_WAVES.
+// Instrumentation (never defined in the product build, results stay right): JA_ENC_TIMELINE (tools/timeline_encode.py).
+// Measured against this kernel: it without its stores and with every load hitting L2, and its memory traffic with next to no
+// arithmetic (round 6, profiles/r06_ablate_encode.txt: memory alone and arithmetic alone need the same 71 us at 8192 x 8192,
+// the kernel 93); it without the two-wave chroma tail of a tile (round 4, profiles/r04_pmc_encode.txt: 23.6 -> 19.3 us at
+// 4096 x 4096, 86.1 -> 68.7 at 8192 x 8192: the tail's share of the tile's instructions, 18 %, is its share of the time -- the
+// kernel is bound by the instructions it issues in all, not by the longest wave); 16-row tiles, two luma blocks per work-item
+// (profiles/r05_ab_encode_8_row_tiles.txt, at the launcher).  Those switches, and the 16-row tile, are in
+// tools/exp_patches/ablation_switches.diff, not in this file.
 #pragma clang fp contract(off)
 
 #include "dct.hpp"
@@ -43,7 +44,6 @@ namespace jpeg_amd {
 namespace {
 
 constexpr int ETX = 32;  // luma blocks per tile row
-constexpr int ETY = 16;  // luma blocks per tile column (8 for the small-image variant, template parameter TY)
 
 struct EncArgs {
     const uint8_t *px;
@@ -132,39 +132,16 @@ __device__ __forceinline__ void fdct_quantise(const float (&g)[64], const float 
 // Store the 64 blocks a wave has just quantised (one per lane, w = 128 bytes each).  A lane
 // storing its own block would write 16 bytes of eight different 128-byte lines per instruction
 // and revisit every line eight times; partial-line writes are what this kernel used to spend a
-// third of its time on.  Instead the blocks go through a wave-private 8 KiB LDS buffer (chunk c
+// third of its time on.  Instead the blocks go through a wave-private LDS buffer (chunk c
 // of lane L at slot c ^ ((L >> 1) & 7), conflict-free for the stride-128-byte writes) and come
-// back lane-linear: instruction i writes the complete lines of blocks 8i .. 8i + 7, each lane one
+// back lane-linear: an instruction writes the complete lines of eight blocks, each lane one
 // 16-byte chunk, with the `nt` hint (streaming output).  `block` = index of the lane's block in
 // `plane` (wave-uniform base; a plane of a 65535 x 65535 image exceeds 4 GiB, so the byte offset
 // is formed in 64 bits by the storing lane), or ~0u for a block outside the plane; the producer's
 // index reaches the storing lane through ds_bpermute.  LDS operations of one wave execute in order, so
 // no barrier is needed; all 64 lanes must call this together.
-__device__ __forceinline__ __attribute__((unused)) void wave_store_blocks(const uint32_t (&w)[32], uint32_t *stage, int lane,
-                                                  int16_t *plane, uint32_t block)
-{
-    uint4 *mine = reinterpret_cast<uint4 *>(stage) + 8 * lane;
-    const int sw = (lane >> 1) & 7;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) mine[c ^ sw] = make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
-    const uint4 *all = reinterpret_cast<const uint4 *>(stage);
-    char *base = reinterpret_cast<char *>(plane);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int producer = 8 * i + (lane >> 3);
-        const uint32_t blk = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * producer, (int)block);
-        const int c = (lane & 7) ^ ((producer >> 1) & 7);
-        const uint4 v = all[64 * i + lane];
-#ifdef JA_X_ENC_NOSTORE
-        if (plane == nullptr)
-#endif
-        if (blk != ~0u) store_nt16(base + ((size_t)blk << 7) + 16 * c, v);
-    }
-}
-
-// The same through a 4 KiB buffer, one half of the wave at a time (lanes 0..31 stage and the whole wave stores their
-// 32 blocks, then lanes 32..63): half the LDS for eight more ds_write instructions.  For the 8-row-tile kernels,
-// which want four workgroups on a CU.
+// The buffer is 4 KiB, one half of the wave at a time (lanes 0..31 stage and the whole wave stores their 32 blocks, then
+// lanes 32..63): half the LDS of a whole-wave buffer for eight more ds_write instructions -- the kernel wants four workgroups on a CU.
 __device__ __forceinline__ void wave_store_blocks_halves(const uint32_t (&w)[32], uint32_t *stage, int lane,
                                                          int16_t *plane, uint32_t block)
 {
@@ -187,9 +164,6 @@ __device__ __forceinline__ void wave_store_blocks_halves(const uint32_t (&w)[32]
             const uint32_t blk = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * producer, (int)block);
             const int c = (lane & 7) ^ ((producer >> 1) & 7);
             const uint4 v = all[64 * i + lane];
-#ifdef JA_X_ENC_NOSTORE
-            if (plane == nullptr)
-#endif
             if (blk != ~0u) store_nt16(base + ((size_t)blk << 7) + 16 * c, v);
         }
         __builtin_amdgcn_wave_barrier();   // the other half's writes stay behind these reads
@@ -199,29 +173,20 @@ __device__ __forceinline__ void wave_store_blocks_halves(const uint32_t (&w)[32]
 // SX, SY: chroma subsampling (1 or 2) per axis; RGB: input is RGB8 (else YCbCr8);
 // CHROMA = false: single-plane image (only Y is produced);
 // FASTIN: W % 8 == 0 and 8-byte aligned rows (vector loads for blocks inside the image).
-// TY: luma block rows per tile.  16: a work-item transforms two luma blocks and (4:2:0) one chroma block.  8: one luma
-// block, and half of the work-items a chroma block -- twice as many workgroups, for images whose 16-row tiles
-// would not fill the chip (a 4096 x 4096 frame is 512 tiles of 16 rows: two waves per SIMD, each of them bound by
-// its own instruction latency).
+// TY: luma block rows per tile, always 8: a work-item transforms one luma block, and (4:2:0) half of the work-items a chroma
+// block.  (16 rows, two luma blocks per work-item, would not fill the chip: a 4096 x 4096 frame is 512 tiles of 16 rows: two
+// waves per SIMD, each of them bound by its own instruction latency.)
 // POOLI: 4:2:0 only -- the 2 x 2 box filter in the integer domain (launches of several rounds; see POOL_INT below).
 #ifdef JA_ENC_TIMELINE
 }  // namespace
 __device__ unsigned long long g_enc_timeline[2 * 32768];
 namespace {
 #endif
-template <int SX, int SY, bool RGB, bool CHROMA, bool FASTIN, int TY = ETY, bool POOLI = false>
-// 4:2:2 / 4:4:0 (chroma pooled per half tile) are built for TWO waves per SIMD: at three (168 VGPRs) the register allocator
-// spills 9-19 registers of the FAST variants, and a spill reload waits with vmcnt(0) for every store in flight -- 4:4:0 at
-// 4096 x 4096 35.3 -> 30.0 us, 4:2:2 33.4 -> 33.0 (profiles/r04_ab_encode_perhalf_two_waves.txt)
-#ifndef JA_X_ENC_PERHALF_WAVES
-#define JA_X_ENC_PERHALF_WAVES 2
-#endif
-__global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1) ? 3 : 4) : (CHROMA && SX == 1 && SY == 1) ? 2 : (CHROMA && SX * SY == 2) ? JA_X_ENC_PERHALF_WAVES : 3)) void k_encode_fused(EncArgs a)
+template <int SX, int SY, bool RGB, bool CHROMA, bool FASTIN, int TY, bool POOLI = false>
+__global__ __launch_bounds__(kThreads, ((CHROMA && SX == 1 && SY == 1) ? 3 : 4)) void k_encode_fused(EncArgs a)
 {
-    // (waves per SIMD declared above: 4 for the 8-row tiles, 2 for 4:4:4 -- its 65 KiB of LDS and 256 VGPRs admit no
-    // more -- 2 for 4:2:2 / 4:4:0, and 3 for the 16-row tiles of the JA_X_ENC_TY experiment)
-    constexpr bool HALFSTAGE = TY == 8;                  // 4 KiB of store staging per wave instead of 8
-    static_assert(TY == 16 || TY == 8, "tiles of 16 or 8 luma block rows");
+    // (waves per SIMD declared above: 4, and 3 for 4:4:4, whose parked chroma samples cost 32 KiB of LDS)
+    static_assert(TY == 8, "tiles of 8 luma block rows");
     constexpr bool INTHREAD = SX == 1 && SY == 1;        // 4:4:4: chroma block == the luma block's pixels
     // 4:2:0: the 2 x 2 box filter in the integer domain (POOLI) removes 1.6 of the 50 instructions per pixel.  It pays where the
     // launch is several rounds of workgroups long (8192 x 8192: 88.6 against 91.5 us) and LOSES where the whole frame is one
@@ -229,22 +194,20 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
     // chain is longer than the float sum it replaces): the launcher picks (profiles/r04_ab_encode_integer_pooling.txt).
     static_assert(!POOLI || (CHROMA && SX == 2 && SY == 2), "integer pooling is the 4:2:0 box filter");
     constexpr bool POOL_INT = POOLI;
-    // 4:2:2 / 4:4:0: the 8 luma block rows of one `half` already hold 256 chroma blocks (one per
-    // work-item), so the chroma tile covers one half at a time and stays at 16 KiB
-    constexpr bool PERHALF = CHROMA && SX * SY == 2 && TY == 16;   // (an 8-row tile of 4:2:2 / 4:4:0 holds one chroma block per work-item: a single pass)
-    constexpr int CW = ETX * 8 / SX, CH = (PERHALF ? TY / 2 : TY) * 8 / SY;  // chroma samples per tile (or half)
+    // (a tile of 4:2:2 / 4:4:0 holds one chroma block per work-item: a single pass over a chroma tile of 16 KiB)
+    constexpr int CW = ETX * 8 / SX, CH = TY * 8 / SY;   // chroma samples per tile
     constexpr int CPITCH = CW / 4;                       // dwords per LDS row
     __shared__ uint32_t sc[(CHROMA && !INTHREAD) ? 2 * CH * CPITCH : 1];
-    __shared__ __attribute__((aligned(16))) uint32_t stage_all[kThreads / 64][HALFSTAGE ? 32 * 32 : 64 * 32];  // 8 (4) KiB per wave
+    __shared__ __attribute__((aligned(16))) uint32_t stage_all[kThreads / 64][32 * 32];  // 4 KiB per wave
     // 4:4:4: the block's Cb / Cr samples wait here (packed 4 per dword, [dword][lane]) while the
     // luma block is transformed -- in registers they cost 32 VGPRs and the kernel spilled
     __shared__ uint32_t stash_all[(CHROMA && INTHREAD) ? kThreads / 64 : 1][(CHROMA && INTHREAD) ? 32 * 64 : 1];
     __shared__ float sq[3][64];   // modulated tables (scale 8) ...
     __shared__ float sr[3][64];   // ... and their correctly rounded reciprocals
 
+    // (a wrapper and not the helper called directly: the direct calls are compiled to other device code)
     auto store_blocks = [](const uint32_t (&w)[32], uint32_t *stage, int lane, int16_t *plane, uint32_t block) {
-        if constexpr (HALFSTAGE) wave_store_blocks_halves(w, stage, lane, plane, block);
-        else wave_store_blocks(w, stage, lane, plane, block);
+        wave_store_blocks_halves(w, stage, lane, plane, block);
     };
 #ifdef JA_ENC_TIMELINE   // development aid (tools/timeline_encode.py): start and end of every workgroup on the constant 100 MHz counter
     const unsigned long long tl_start = __builtin_amdgcn_s_memrealtime();
@@ -254,42 +217,39 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
     // one below.  Measured, not derived (profiles/r02_ab_encode_priority.txt): 4096 x 4096 4:2:0 23.1 against 25.0 us on the
     // same box; any split with the first phase above the default priority 0 gains 5-7 %.  (Layouts without that barrier gain
     // nothing from a raised priority: 4:4:4 loses 2 %.)
-    if constexpr (CHROMA && !INTHREAD && !PERHALF) __builtin_amdgcn_s_setprio(3);
+    if constexpr (CHROMA && !INTHREAD) __builtin_amdgcn_s_setprio(3);
     const int tyi = blockIdx.x / a.tiles_x, txi = blockIdx.x - tyi * a.tiles_x;
     const int lbx = threadIdx.x & (ETX - 1), lby0 = threadIdx.x / ETX;
     const int lane = threadIdx.x & 63;
     uint32_t *stage = stage_all[threadIdx.x >> 6];
     uint32_t *stash = stash_all[(CHROMA && INTHREAD) ? threadIdx.x >> 6 : 0];
 
-    // The tables are first needed by the luma FDCT.  Their quantum is REQUESTED here and turned into table entries only
-    // after the tile's pixel loads have been issued, barrier included.  (Table first, barrier, then the pixel loads put two
-    // memory latencies in a row at the head of every workgroup; a barrier later, in front of the FDCT, re-aligns the four
-    // waves in the middle of their work: 4:2:0 23.5 -> 26.3 us.)
-    // Measured (profiles/r02_ab_encode_tables_first.txt): -1.5 to -2 us for the 16-row tiles (4:2:2 30.3 -> 28.5, 4:4:4 37.0 ->
-    // 35.0 us at 4096 x 4096), but +2.5 us for the 8-row tiles of grey and 4:2:0, whose single round of workgroups then
-    // requests the whole frame in the same instant -- those keep the table in front (TABLES_LATE = false).
-    constexpr bool TABLES_LATE = TY == 16;
+    // The tables are first needed by the luma FDCT and are published up front, in front of the pixel loads.  (Requesting the
+    // quantum here and turning it into table entries only after the tile's pixel loads have been issued, barrier included,
+    // saves the second of two memory latencies in a row at the head of every workgroup -- measured,
+    // profiles/r02_ab_encode_tables_first.txt: -1.5 to -2 us for the 16-row tiles of their day (4:2:2 30.3 -> 28.5, 4:4:4 37.0 ->
+    // 35.0 us at 4096 x 4096), but +2.5 us for the 8-row tiles of grey and 4:2:0, whose single round of workgroups then requests
+    // the whole frame in the same instant.  A barrier later still, in front of the FDCT, re-aligns the four waves in the middle
+    // of their work: 4:2:0 23.5 -> 26.3 us.)
     const bool qthread = threadIdx.x < 192 && (CHROMA || threadIdx.x < 64);
     const int qt = threadIdx.x >> 6, qk = threadIdx.x & 7, qh = (threadIdx.x >> 3) & 7;
     uint16_t qraw = 1;
     if (qthread) qraw = a.quanta[img * a.quanta_stride + 64 * a.qi[qt] + zigzag_of(qk, qh)];
-    auto publish_tables = [&]() {
-        if (qthread) {
-            const float qv = modulate_entry(qk, qh, 8.0f, qraw);
-            sq[qt][8 * qk + qh] = qv;                 // transposed: [k][h]
-            sr[qt][8 * qk + qh] = 1.0f / qv;          // IEEE division: RN(1 / q)
-        }
-    };
-    if constexpr (!TABLES_LATE) { publish_tables(); __syncthreads(); }
+    if (qthread) {
+        const float qv = modulate_entry(qk, qh, 8.0f, qraw);
+        sq[qt][8 * qk + qh] = qv;                 // transposed: [k][h]
+        sr[qt][8 * qk + qh] = 1.0f / qv;          // IEEE division: RN(1 / q)
+    }
+    __syncthreads();
 
-    // chroma blocks of the tile (or of one half of it) from the pooled LDS tile
-    auto chroma_blocks = [&](int half) {
-        constexpr int CBX = ETX / SX, CBY = (PERHALF ? TY / 2 : TY) / SY;  // chroma blocks per plane
+    // chroma blocks of the tile from the pooled LDS tile
+    auto chroma_blocks = [&]() {
+        constexpr int CBX = ETX / SX, CBY = TY / SY;  // chroma blocks per plane
 #pragma unroll 1
         for (int c = threadIdx.x; c < 2 * CBX * CBY; c += kThreads) {
             const int pl = c / (CBX * CBY), r = c - pl * (CBX * CBY);
             const int cby = r / CBX, cbx = r - cby * CBX;
-            const int bx = txi * CBX + cbx, by = tyi * (TY / SY) + half * CBY + cby;
+            const int bx = txi * CBX + cbx, by = tyi * CBY + cby;
             float g[64];
 #pragma unroll
             for (int y = 0; y < 8; ++y) {
@@ -301,12 +261,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
                 g[8 * y + 6] = ubyte<2>(d1); g[8 * y + 7] = ubyte<3>(d1);
             }
             uint32_t w[32];
-#ifdef JA_X_ENC_NOCOMPUTE   // experiment (wrong coefficients): the kernel's memory traffic with next to no arithmetic
-#pragma unroll
-            for (int i = 0; i < 32; ++i) w[i] = __builtin_bit_cast(uint32_t, g[2 * i]) ^ __builtin_bit_cast(uint32_t, g[2 * i + 1]);
-#else
             fdct_quantise(g, sq[1 + pl], sr[1 + pl], w);
-#endif
             // 2 * CBX * CBY and CBX * CBY are multiples of 64: the loop is wave-uniform and a wave
             // never straddles the two planes
             const int plu = __builtin_amdgcn_readfirstlane(pl);
@@ -317,7 +272,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
 
     const uint8_t *base = a.px + img * a.px_stride;
 #pragma unroll 1
-    for (int half = 0; half < TY / 8; ++half) {
+    for (int half = 0; half < TY / 8; ++half) {   // one trip; kept as a loop because a plain block is compiled to another schedule
         const int lby = lby0 + 8 * half;
         const int bx = txi * ETX + lbx, by = tyi * TY + lby;
         float yv[64];
@@ -387,7 +342,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
                             // (one exact FMA instead of a multiply and a floor)
                             packed[i >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(sum, inv, -0.5f * (1.0f - inv)), i & 3, packed[i >> 2]);
                         }
-                        uint32_t *row = sc + (pl * CH + (PERHALF ? lby0 : lby) * (8 / SY) + j) * CPITCH + lbx * (8 / SX) / 4;
+                        uint32_t *row = sc + (pl * CH + lby * (8 / SY) + j) * CPITCH + lbx * (8 / SX) / 4;
 #pragma unroll
                         for (int d = 0; d < (8 / SX + 3) / 4; ++d) row[d] = packed[d];
                     }
@@ -405,11 +360,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
         if (FASTIN && inside) {
             // scalar row base (the tile's first pixel row + y rows: SALU) + one 32-bit per-lane offset for all eight rows:
             // no vector address arithmetic per row (it used to be three 64-bit multiply-adds per row)
-#ifdef JA_X_ENC_L2LOAD   // experiment: every block reads the image's first tile (L2 hits)
-            const uint8_t *tile0 = base;
-#else
             const uint8_t *tile0 = base + ((size_t)(8 * tyi * TY) * a.W + (size_t)8 * txi * ETX) * 3;   // wave-uniform
-#endif
             const uint32_t voff = ((uint32_t)(8 * lby) * (uint32_t)a.W + 8u * lbx) * 3u;   // < 64 rows x 65 535 px x 3 B
 #pragma unroll
             for (int y = 0; y < 8; ++y) {
@@ -452,7 +403,6 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
                 }
             }
         }
-        if (TABLES_LATE && half == 0) { publish_tables(); __syncthreads(); }   // the pixel loads are in flight: the barrier waits under them
 #pragma unroll
         for (int y = 0; y < 8; ++y) {
             __builtin_amdgcn_sched_barrier(0);
@@ -472,16 +422,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) c[ch][x] = x <= xlast ? c[ch][x] : c[ch][x - 1];
             }
-#ifdef JA_X_ENC_NOCOMPUTE
-#pragma unroll
-            for (int x = 0; x < 8; ++x) yv[8 * y + x] = c[0][x] + c[1][x] + c[2][x];
-            if (y == 7 && CHROMA && !INTHREAD) {
-                uint32_t *row = sc + (lby * 4 * CPITCH + lbx) % (2 * CH * CPITCH);
-                row[0] = pix[0][0];
-            }
-#else
             emit_row(y, c[0], c[1], c[2]);
-#endif
 #pragma unroll
             for (int x = 0; x < 8; ++x) asm volatile("" : "+v"(yv[8 * y + x]));
         }
@@ -490,12 +431,7 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
         __builtin_amdgcn_sched_barrier(0);
         {
             uint32_t w[32];
-#ifdef JA_X_ENC_NOCOMPUTE
-#pragma unroll
-            for (int i = 0; i < 32; ++i) w[i] = __builtin_bit_cast(uint32_t, yv[2 * i]) ^ __builtin_bit_cast(uint32_t, yv[2 * i + 1]);
-#else
             fdct_quantise(yv, sq[0], sr[0], w);
-#endif
             const uint32_t off = (bx < a.ux[0] && by < a.uy[0]) ? (uint32_t)(by * a.ux[0] + bx) : ~0u;
             store_blocks(w, stage, lane, a.coef[0] + img * a.coef_stride[0], off);
         }
@@ -515,19 +451,11 @@ __global__ __launch_bounds__(kThreads, (TY == 8 ? ((CHROMA && SX == 1 && SY == 1
                 store_blocks(w, stage, lane, a.coef[1 + pl] + img * a.coef_stride[1 + pl], off);
             }
         }
-        if constexpr (PERHALF) {
-            __syncthreads();          // the half's chroma samples are pooled
-            chroma_blocks(half);
-            if (half == 0) __syncthreads();   // ... and consumed before the next half overwrites them
-        }
     }
-    if constexpr (CHROMA && !INTHREAD && !PERHALF) {
+    if constexpr (CHROMA && !INTHREAD) {
         __syncthreads();
         __builtin_amdgcn_s_setprio(2);   // the tile's tail; the waves that are still converting and transforming luma go first
-#ifdef JA_X_ENC_NOCHROMA   // experiment (no chroma coefficients): what does the two-wave chroma tail of a tile cost?
-        if (a.W < 0)
-#endif
-        chroma_blocks(0);
+        chroma_blocks();
     }
 #ifdef JA_ENC_TIMELINE
     {
@@ -547,16 +475,6 @@ extern "C" int jpeg_amd_debug_encode_timeline(unsigned long long *h_out, size_t 
     return (int)hipMemcpyFromSymbol(h_out, HIP_SYMBOL(jpeg_amd::g_enc_timeline), n * sizeof(unsigned long long));
 }
 #endif
-
-// development switch (-DJA_X_ENC_TY=8 / 16, tools/build_exp.sh): forces the tile height of the grey / 4:2:0 encode kernels
-static int encode_ty_override()
-{
-#ifdef JA_X_ENC_TY
-    return JA_X_ENC_TY;
-#else
-    return 0;
-#endif
-}
 
 bool fused_encode_supported(const jpeg_amd_layout &L)
 {
@@ -601,8 +519,7 @@ hipError_t launch_fused_encode(hipStream_t stream, int n_images, const jpeg_amd_
     // 15.4); 4:2:2 / 4:4:0 / 4:4:4 since round 5 -- an 8-row tile of 4:2:2 / 4:4:0 holds exactly one chroma block per work-item, so the
     // per-half chroma tiles of the 16-row kernels (two waves per SIMD, 151-183 VGPRs) are not needed: 8192 x 8192 4:2:2 112 -> 104 us,
     // 4:4:4 155 -> 128, 4:4:0 118 -> 98; 4096 x 4096 33.3 -> 28.0, 40.2 -> 39.2, 32.5 -> 27.5 (profiles/r05_ab_encode_8_row_tiles.txt).
-    // The 16-row instantiations are built for the JA_X_ENC_TY experiment alone.
-    const int ty = encode_ty_override() == 16 ? 16 : 8;
+    constexpr int ty = 8;
     const int tiles_y = (need_y + ty - 1) / ty;
     if (a.tiles_x * tiles_y == 0 || n_images == 0) return hipSuccess;
     const dim3 grid(a.tiles_x * tiles_y, n_images);
@@ -612,26 +529,20 @@ hipError_t launch_fused_encode(hipStream_t stream, int n_images, const jpeg_amd_
     // (the vector-load path addresses a tile's rows with 32-bit byte offsets: 16 block rows x 8 x W x 3 B must stay below 2^32)
     const bool fast = (L.width & 7) == 0 && (pixel_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(d_pixels) & 7) == 0 &&
                       L.width <= (1 << 23);
-#define JA_E8(SX_, SY_, RGB_, CH_, F_) hipLaunchKernelGGL((k_encode_fused<SX_, SY_, RGB_, CH_, F_, 8>), grid, dim3(kThreads), 0, stream, a)
-#define JA_E8I(SX_, SY_, RGB_, CH_, F_) hipLaunchKernelGGL((k_encode_fused<SX_, SY_, RGB_, CH_, F_, 8, true>), grid, dim3(kThreads), 0, stream, a)
-#ifdef JA_X_ENC_TY
-#define JA_ET(SX_, SY_, RGB_, CH_, F_) do { if (ty == 8) JA_E8(SX_, SY_, RGB_, CH_, F_); else hipLaunchKernelGGL((k_encode_fused<SX_, SY_, RGB_, CH_, F_>), grid, dim3(kThreads), 0, stream, a); } while (0)
-#else
-#define JA_ET(SX_, SY_, RGB_, CH_, F_) JA_E8(SX_, SY_, RGB_, CH_, F_)
-#endif
+#define JA_E8(SX_, SY_, RGB_, CH_, F_) hipLaunchKernelGGL((k_encode_fused<SX_, SY_, RGB_, CH_, F_, ty>), grid, dim3(kThreads), 0, stream, a)
+#define JA_E8I(SX_, SY_, RGB_, CH_, F_) hipLaunchKernelGGL((k_encode_fused<SX_, SY_, RGB_, CH_, F_, ty, true>), grid, dim3(kThreads), 0, stream, a)
 #define JA_E2(RGB_, F_)                                         \
     do {                                                        \
-        if (!chroma) JA_ET(1, 1, RGB_, false, F_);              \
-        else if (sx == 2 && sy == 2 && ty == 8 && several_rounds) JA_E8I(2, 2, RGB_, true, F_); \
-        else if (sx == 2 && sy == 2) JA_ET(2, 2, RGB_, true, F_); \
-        else if (sx == 2 && sy == 1) JA_ET(2, 1, RGB_, true, F_); \
-        else if (sx == 1 && sy == 2) JA_ET(1, 2, RGB_, true, F_); \
-        else JA_ET(1, 1, RGB_, true, F_);                       \
+        if (!chroma) JA_E8(1, 1, RGB_, false, F_);              \
+        else if (sx == 2 && sy == 2 && several_rounds) JA_E8I(2, 2, RGB_, true, F_); \
+        else if (sx == 2 && sy == 2) JA_E8(2, 2, RGB_, true, F_); \
+        else if (sx == 2 && sy == 1) JA_E8(2, 1, RGB_, true, F_); \
+        else if (sx == 1 && sy == 2) JA_E8(1, 2, RGB_, true, F_); \
+        else JA_E8(1, 1, RGB_, true, F_);                       \
     } while (0)
     if (rgb) { if (fast) JA_E2(true, true); else JA_E2(true, false); }
     else     { if (fast) JA_E2(false, true); else JA_E2(false, false); }
 #undef JA_E2
-#undef JA_ET
 #undef JA_E8I
 #undef JA_E8
     return hipGetLastError();

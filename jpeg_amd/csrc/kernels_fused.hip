@@ -22,9 +22,9 @@
 // 4250) because 0.25*c + 0.75*c == c exactly.  Everything that rounds (dequantise, IDCT,
 // colour matrix) is evaluated op-for-op as in dct.hpp / the reference.
 //
-// Development switches (never defined in the product build; tools/build_exp.sh makes A/B builds):
-// JA_X_NOIDCT / JA_X_NOCOLOR / JA_X_NOSTORE (the kernel without its transform / without its upsampling and colour
-// arithmetic / without its stores: tools/ablate.sh), JA_X_NOPRIO.
+// No development switches in this file.  Measured against this kernel: it without its transform, without its stores, without
+// the priorities of its last strips (tools/ablate.sh; profiles/HISTORY.md, profiles/r02_ab_experiments.txt).  Those switches
+// are in tools/exp_patches/ablation_switches.diff, and tools/build_exp.py makes the A/B builds.
 #pragma clang fp contract(off)
 
 #include "dct.hpp"
@@ -283,7 +283,6 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
         //      16 stores behind it. ----
         if (stores_behind_dma == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef JA_X_NOPRIO
         // The waves of a SIMD do not advance at the same pace: the scheduler issues the oldest ready wave first, so with
         // equal shares the first wave of a SIMD is done long before the last (8192 x 8192, four strips each: ends between
         // 30 and 72 us, tools/phase_profile.py) and the SIMD spends the end of the launch with one or two waves -- too
@@ -297,7 +296,6 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             else if (rem == 1) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
-#endif
         uint32_t w[32];
         auto read_block = [&]() {
             const uint4 *cw = reinterpret_cast<const uint4 *>(coef_w) + 8 * lane;
@@ -461,14 +459,9 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
         // ---- luma: dequantise + IDCT, clamp + truncate (decode.swift:4121-4122), kept as
         //      integer-valued floats for the colour matrix ----
         float yv[64];
-#ifdef JA_X_NOIDCT  // experiment: how long is a strip without the IDCT arithmetic?
-#pragma unroll
-        for (int i = 0; i < 64; ++i) yv[i] = (float)(w[i & 31] >> (i & 32 ? 16 : 0) & 0xff);
-#else
         idct_block(w, TransposedTable{sq}, 128.5f, yv);
 #pragma unroll
         for (int i = 0; i < 64; ++i) yv[i] = floorf(__builtin_amdgcn_fmed3f(yv[i], 0.0f, 255.0f));
-#endif
 
         // Pin the IDCT HERE: LLVM otherwise sinks it below the waits / DMA (its results are first
         // used in the colour phase) and the wave would park on the chroma rows before doing any
@@ -590,21 +583,16 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
                 __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (8 * b)), rsrc, (part && b < nbytes) ? base + 4u * nd + b : 0x80000000u, soff, 0);
         };
         auto store_row = [&](int yy) {
-#ifdef JA_X_NOSTORE  // experiment: everything but the global stores
-            if (a.W < 0)
-#endif
-            {
-                const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
-                const uint32_t soff = (uint32_t)yy * pitch;   // scalar
-                asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
-                             "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
-                             "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
-                             ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
-                if constexpr (!FAST) {
-                    if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
-                        store_tail(pv0, base0, rem0, soff);
-                        store_tail(pv1, base1, rem1, soff);
-                    }
+            const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
+            const uint32_t soff = (uint32_t)yy * pitch;   // scalar
+            asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
+                         "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
+                         "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
+                         ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
+            if constexpr (!FAST) {
+                if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
+                    store_tail(pv0, base0, rem0, soff);
+                    store_tail(pv1, base1, rem1, soff);
                 }
             }
         };

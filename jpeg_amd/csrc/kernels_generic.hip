@@ -91,8 +91,9 @@ __device__ __forceinline__ int div_trunc_small(int n, int c, int log2c, uint32_t
     return (int)__umulhi((uint32_t)max(n, 0), magic);
 }
 
-// Development switches (never defined in the product build): JA_GEN_PHASE (tools/phase_generic.py: wall cycles of every 8th wave per
-// phase of its tile), JA_X_GEN_NOLOAD / JA_X_GEN_NOSTORE (the tile without its coefficient loads / its global stores).
+// Instrumentation (never defined in the product build, results stay right): JA_GEN_PHASE (tools/phase_generic.py: wall cycles of
+// every 8th wave per phase of its tile).  The ablation switches -- the tile without its coefficient loads / its global stores, the
+// walk without its priorities -- are in tools/exp_patches/ablation_switches.diff, not in this file.
 #ifdef JA_GEN_PHASE
 __device__ unsigned long long g_gen_phase[4096 * 16];
 #define GP_DECL unsigned long long gp_acc[16] = {}; unsigned long long gp_prev = __builtin_readcyclecounter(); const unsigned long long gp_first = gp_prev, gp_real = __builtin_amdgcn_s_memrealtime();
@@ -138,7 +139,6 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
     if (tile_id >= total_tiles) return;
 #pragma unroll 1
     for (int trip = 0;; ++trip) {
-#ifndef JA_X_GEN_NOPRIO
     if constexpr (WALK)
     // A SIMD issues its OLDEST ready wave first: of the four resident workgroups of a CU the youngest would fall behind trip after trip
     // and finish long after the others (without this: mean life of a workgroup 147 us, the step 291).  As in the strip walks, a wave
@@ -150,7 +150,6 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
         else if (left == 1) __builtin_amdgcn_s_setprio(1);
         else __builtin_amdgcn_s_setprio(0);
     }
-#endif
     KArgs *ap = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (WALK) asm volatile("" : "+s"(ap));
     // (WALK: the arguments through the opaque pointer; else the by-value parameter itself)
@@ -229,11 +228,7 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
             const uint4 *src = reinterpret_cast<const uint4 *>(cbase + (size_t)64 * ((size_t)gby * ux + gbx));
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-#ifdef JA_X_GEN_NOLOAD   // experiment: the tile without its coefficient loads
-                const uint4 v = make_uint4(t + i, gbx, gby, a.W < 0 ? src[i].x : 7u);
-#else
                 const uint4 v = src[i];
-#endif
                 w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
             }
         }
@@ -429,11 +424,7 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
                 if (SROWS * COUNT % 4 != 0 && g >= SROWS * 16 * COUNT) continue;
                 const uint4 v = *reinterpret_cast<const uint4 *>(st + 4 * g);
                 const int yy = y0 + 32 * pass + 8 * wv + SROWS * h + row;
-#ifdef JA_X_GEN_NOSTORE   // experiment: the tile without its global stores
-                if (a.W < 0 || (v.x == 0x12345678u && v.y == 0x9abcdef0u)) {
-#else
                 if (yy < a.H && 8 * cc < nvalid) {
-#endif
                     uint16_t *dst = a.out + img * a.out_stride + ((size_t)yy * a.W + x0) * COUNT + 8 * cc;
                     if (8 * cc + 8 <= nvalid) {
                         *reinterpret_cast<uint4 *>(dst) = v;      // (rows need not be 16-byte aligned: the hardware takes unaligned dwordx4 stores)
@@ -501,7 +492,7 @@ extern "C" int jpeg_amd_debug_gen_phase(unsigned long long *h_out, size_t n)
 }
 namespace {
 #endif
-constexpr int GEW = 128;   // tile width in pixels; its height GEH is 32, or 64 where the blocks under 64 rows still fit 256 work-items
+constexpr int GEW = 128;   // tile width in pixels; its height GEH is 32
 
 struct GenEncPlane {
     int16_t *coef;
@@ -520,8 +511,9 @@ struct GenEncArgs {
 };
 
 template <int COUNT, int GEH, int NT = kGThreads>
-__global__ __launch_bounds__(NT, (GEH == 64 ? 2 : 4)) void k_generic_encode(GenEncArgs a)
+__global__ __launch_bounds__(NT, 4) void k_generic_encode(GenEncArgs a)
 {
+    static_assert(GEH == 32 && NT == kGThreads, "the one tile shape that is launched (64-row tiles were measured slower, below)");
     __shared__ __attribute__((aligned(16))) uint16_t raw[GEW * GEH * COUNT];    // the tile of Rectangular; later the blocks on their way out
     extern __shared__ __attribute__((aligned(16))) uint16_t tile[];                // plane tiles: as many samples as the layout's planes have under a tile
     __shared__ float sq[JPEG_AMD_MAX_PLANES][64];                                // modulated tables (natural order, scale 8) ...
@@ -889,40 +881,19 @@ hipError_t launch_generic_encode(hipStream_t stream, int n_images, const jpeg_am
     }
     if (n_images == 0 || need_x == 0 || need_y == 0) return hipSuccess;
     // tile height: 32 rows.  64 rows would fill the workgroup better (4:2:0: 192 blocks instead of 96 under 32 rows)
-    int blocks64 = 0, blocks32 = 0;
-    for (int p = 0; p < L.nplanes; ++p) {
-        blocks64 += (GEW / (8 * a.pl[p].rx)) * (64 / (8 * a.pl[p].ry));
-        blocks32 += (GEW / (8 * a.pl[p].rx)) * (32 / (8 * a.pl[p].ry));
-    }
-    (void)blocks32;
     // (measured: 64-row tiles are SLOWER -- 8192 x 8192 12-bit 4:2:0 472 against 403 us, 4:2:2 923 against 490 -- although they fill
-    // the workgroup's lanes: fewer, larger workgroups hide less of each other's barriers.  JA_X_GENERIC_ENCODE_64 builds them.)
-#ifdef JA_X_GENERIC_ENCODE_64
-    const int geh = (L.nplanes <= 3 && blocks64 <= kGThreads) ? 64 : 32;
-#else
-    const int geh = 32;
-    (void)blocks64;
-#endif
+    // the workgroup's lanes: fewer, larger workgroups hide less of each other's barriers.)
+    constexpr int geh = 32;
     a.tiles_x = (need_x + GEW - 1) / GEW;
     const dim3 grid(a.tiles_x * ((need_y + geh - 1) / geh), n_images);
     size_t tile_bytes = 0;
     for (int p = 0; p < L.nplanes; ++p) tile_bytes += (size_t)2 * (GEW / a.pl[p].rx) * (geh / a.pl[p].ry);
-#ifdef JA_X_GENERIC_ENCODE_64
-#define JA_GE(C_) do { if (geh == 64) hipLaunchKernelGGL((k_generic_encode<C_, 64>), grid, dim3(kGThreads), tile_bytes, stream, a); \
-                       else hipLaunchKernelGGL((k_generic_encode<C_, 32>), grid, dim3(kGThreads), tile_bytes, stream, a); } while (0)
-#else
-#ifdef JA_X_GENC_NT
-#define JA_GE(C_) do { if (blocks32 <= JA_X_GENC_NT) hipLaunchKernelGGL((k_generic_encode<C_, 32, JA_X_GENC_NT>), grid, dim3(JA_X_GENC_NT), tile_bytes, stream, a); \
-                       else hipLaunchKernelGGL((k_generic_encode<C_, 32>), grid, dim3(kGThreads), tile_bytes, stream, a); } while (0)
-#else
-#define JA_GE(C_) hipLaunchKernelGGL((k_generic_encode<C_, 32>), grid, dim3(kGThreads), tile_bytes, stream, a)
-#endif
-#endif
+#define JA_GE(C_) hipLaunchKernelGGL((k_generic_encode<C_, geh>), grid, dim3(kGThreads), tile_bytes, stream, a)
     switch (L.nplanes) {
     case 1: JA_GE(1); break;
     case 2: JA_GE(2); break;
     case 3: JA_GE(3); break;
-    default: hipLaunchKernelGGL((k_generic_encode<4, 32>), grid, dim3(kGThreads), tile_bytes, stream, a); break;
+    default: JA_GE(4); break;
     }
 #undef JA_GE
     return hipGetLastError();

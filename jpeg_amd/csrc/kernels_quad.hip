@@ -27,12 +27,15 @@
 // input).  Strips, stacks and tile columns that reach past the image or the plane are handled in place (clamped fetches,
 // predicated stores, the reference's index clamps repaired in the tile), so any image size takes this kernel.
 //
-// Development switches (never defined in the product build): JA_PHASE_PROFILE, JA_X_NOSYNC, JA_X_NOCIDCT, JA_X_NOIDCT,
-// JA_X_NOSTORE, JA_X_STAGGER=<cycles>, JA_X_GRID_PER_CU=<1 | 2>, JA_QUAD_WAVES=4 + JA_X_LDSHACK (round 4: what four waves per SIMD would be
-// worth -- pairs of waves share a coefficient buffer, wrong pixels; profiles/r04_ab_four_waves_per_simd.txt).  (Round 3 also measured: the DMA instructions paced over the pixel rows or
-// interleaved with the transform's columns, several priority schemes, progress feedback between the workgroups of a CU,
-// one chroma pass per strip instead of the roles -- profiles/r03_ab_*.txt; those variants are in git history or under
-// tools/exp_patches/, not in this file.)
+// Instrumentation (never defined in the product build, leaves the pixels right): JA_PHASE_PROFILE (tools/phase_profile.py).
+// This file holds only what runs.  Measured against it: the walk without its waits, without the arithmetic of its transforms,
+// without its stores (profiles/r03_ablate1.txt, profiles/HISTORY.md), workgroups that start a third of a strip apart, two
+// resident workgroups per CU (profiles/r03_ab_two_workgroups_per_cu.txt), every wave taking every role once in four trips
+// (profiles/r05_ab_selects_and_role_rotation.txt), and four waves per SIMD with pairs of waves sharing a coefficient buffer
+// (round 4, profiles/r04_ab_four_waves_per_simd.txt); those switches are in tools/exp_patches/ablation_switches.diff.  Round 3
+// also measured: the DMA instructions paced over the pixel rows or interleaved with the transform's columns, several
+// priority schemes, progress feedback between the workgroups of a CU, one chroma pass per strip instead of the roles
+// (profiles/r03_ab_*.txt); those variants are in the other patches under tools/exp_patches/ or in git history.
 #pragma clang fp contract(off)
 
 #include "dct.hpp"
@@ -68,9 +71,6 @@ struct QuadArgs {
     int nstacks;                   // of the whole call
 };
 
-#ifndef JA_QUAD_WAVES
-#define JA_QUAD_WAVES 3   // waves per SIMD the register allocation aims at
-#endif
 template <int BX> struct QuadShape {
     static constexpr int BY = 64 / BX;
     static constexpr int QS = kThreads / 64;              // strips (= waves) per stack: one stack per workgroup
@@ -79,7 +79,7 @@ template <int BX> struct QuadShape {
 // MODE: 0 = YCbCr bytes, 1 = RGB bytes.  FAST: W % 16 == 0 and 16-byte aligned rows, so every 16-byte chunk of a row
 // segment is entirely inside the image or entirely outside (no tail code for the partial last chunk of a row).
 template <int MODE, int BX, bool FAST, bool DYN>
-__global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
+__global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: waves per SIMD the register allocation aims at
 {
     constexpr int BY = QuadShape<BX>::BY, QS = QuadShape<BX>::QS;
     constexpr int NW = kThreads / 64;
@@ -105,11 +105,7 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
     constexpr int NHROW = 4 * CBW, NSIDE = 4 * (QS * CBR + 2);   // blocks of role 2 / role 3: 64 / 24 (32 x 2 strips), 32 / 40
     constexpr int NDMA_C = 8;                             // LDS-DMA instructions of a chroma pass at most (8 blocks each)
 
-#ifdef JA_X_LDSHACK   // experiment (wrong pixels): pairs of waves share a coefficient buffer -- what are four waves per SIMD worth?
-    __shared__ __attribute__((aligned(16))) uint32_t coefbuf[NW / 2][64 * 32];
-#else
     __shared__ __attribute__((aligned(16))) uint32_t coefbuf[NW][64 * 32];   // 8 KiB per wave
-#endif
     __shared__ __attribute__((aligned(16))) uint32_t stage[NW][BY * SEG_DW]; // one pixel row x BY block rows
     __shared__ uint32_t qt[2 * PLANE];                    // the stack's tile; row 0: halo above, rows 1 + CR p ...: strip p, last row: halo below
     __shared__ __attribute__((aligned(16))) float sqw[NW][3][64];   // modulated tables: Y, Cb, Cr -- TRANSPOSED ([8 k + h], dct.hpp TransposedTable)
@@ -120,11 +116,7 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
 
     const int lane0 = threadIdx.x & 63;
     const int qp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the wave's strip of the stack; strip math stays scalar
-#ifdef JA_X_LDSHACK
-    uint32_t *coef_w = coefbuf[qp & 1], *stage_w = stage[qp];
-#else
     uint32_t *coef_w = coefbuf[qp], *stage_w = stage[qp];
-#endif
     const uint32_t coef_lds = lds_address(coef_w);
     uint32_t *sc = qt + CR * qp * PITCH;                  // this wave's window: row 0 = the sample row above its own rows
     uint32_t *ready = &qsync[0], *done = &qsync[1], *pub = &qsync[2];   // pub: dynamic walk, "the next stack is published"
@@ -142,11 +134,7 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
         sxi = (int)col + a.sx0;
     };
     const int strips_y = (a.uy + BY - 1) / BY;
-#ifdef JA_X_ROLEROT   // experiment: every wave takes every role once in four trips (instead of swapping between the wave pairs)
-    auto role_of = [&](int t) -> int { return (qp + t) & 3; };
-#else
     auto role_of = [&](int t) -> int { return (qp + 2 * (t & 1)) & 3; };
-#endif
 
     // LDS-DMA of a pass's blocks: an instruction moves 64 x 16 B; slot u = 64 i + lane of the wave's buffer holds chunk
     // (u & 7) ^ ((b >> 1) & 7) of block b = u >> 3 -- the XOR on the SOURCE address makes the later per-work-item ds_read_b128
@@ -223,9 +211,6 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
         }
     };
 
-#ifdef JA_X_STAGGER   // experiment: the three workgroups of a CU start a third of a strip apart
-    for (int d = (int)(blockIdx.x / 256u) * (JA_X_STAGGER); d > 0; d -= 64 * 100) __builtin_amdgcn_s_sleep(100);
-#endif
     if ((int)blockIdx.x >= a.nstacks) return;   // (the grid is never larger than the call)
     // The walk.  Static (a.tickets == nullptr): workgroup b takes stacks b, b + grid, ...  Dynamic, for calls that are many
     // trips long: the first stack is b, every further one a ticket from a global counter -- wave 0 draws it at the top of a
@@ -318,12 +303,7 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
             uint32_t *tile = qt + pl * PLANE;
             if (role < 2) {
                 float g[64];
-#ifdef JA_X_NOCIDCT   // experiment (wrong pixels): the walk without the arithmetic of its chroma transform
-#pragma unroll
-                for (int i = 0; i < 64; ++i) g[i] = (float)(w[i & 31] >> (i & 32 ? 16 : 0) & 0xff) + sqw[qp][1 + pl][i];
-#else
                 idct_block(w, TransposedTable{sqw[qp][1 + pl]}, 128.5f, g);
-#endif
                 uint32_t pk[16];
                 trunc_pack24(g, pk); trunc_pack24(g + 24, pk + 6); trunc_pack16(g + 48, pk + 12);
 #pragma unroll
@@ -440,12 +420,7 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
         uint32_t ypk[16];
         {
             float yv[64];
-#ifdef JA_X_NOIDCT  // experiment (wrong pixels): how long is a strip without the IDCT arithmetic?
-#pragma unroll
-            for (int i = 0; i < 64; ++i) yv[i] = (float)(w[i & 31] >> (i & 32 ? 16 : 0) & 0xff);
-#else
             idct_block(w, TransposedTable{sqw[qp][0]}, 128.5f, yv);
-#endif
             trunc_pack24(yv, ypk); trunc_pack24(yv + 24, ypk + 6); trunc_pack16(yv + 48, ypk + 12);
         }
         // pin the IDCT here (LLVM otherwise sinks it into the pixel rows)
@@ -560,23 +535,18 @@ __global__ __launch_bounds__(kThreads, JA_QUAD_WAVES) void k_quad420(QuadArgs a)
                 __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (8 * b)), rsrc, (part && b < nbytes) ? base + 4u * nd + b : 0x80000000u, soff, 0);
         };
         auto store_row = [&](int yy) {
-#ifdef JA_X_NOSTORE  // experiment: everything but the global stores
-            if (a.W < 0)
-#endif
-            {
-                // chunk `lane` from every lane, chunk 64 + lane from lanes 0 .. 31 (the others carry an out-of-range voffset):
-                // exactly two store instructions per pixel row, whatever the strip's place in the image
-                const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
-                const uint32_t soff = (uint32_t)yy * pitch;   // scalar
-                asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
-                             "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
-                             "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
-                             ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
-                if constexpr (!FAST) {
-                    if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
-                        store_tail(pv0, base0, rem0, soff);
-                        store_tail(pv1, base1, rem1, soff);
-                    }
+            // chunk `lane` from every lane, chunk 64 + lane from lanes 0 .. 31 (the others carry an out-of-range voffset):
+            // exactly two store instructions per pixel row, whatever the strip's place in the image
+            const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
+            const uint32_t soff = (uint32_t)yy * pitch;   // scalar
+            asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
+                         "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
+                         "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
+                         ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
+            if constexpr (!FAST) {
+                if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
+                    store_tail(pv0, base0, rem0, soff);
+                    store_tail(pv1, base1, rem1, soff);
                 }
             }
         };
@@ -654,9 +624,6 @@ template <int MODE, int BX, bool FAST, bool DYN>
 hipError_t launch_quad_walk(hipStream_t stream, const QuadArgs &a)
 {
     int cap = quad_resident_workgroups<MODE, BX, FAST, DYN>();
-#ifdef JA_X_GRID_PER_CU   // experiment: fewer resident workgroups per CU than fit
-    cap = std::min(cap, (JA_X_GRID_PER_CU) * (cap / 3));
-#endif
 #ifdef JA_PHASE_PROFILE   // development aid: JA_GRID_CAP=256 runs one workgroup per CU (a wave alone on its SIMD)
     if (const char *e = std::getenv("JA_GRID_CAP")) cap = std::min(cap, std::atoi(e));
 #endif
@@ -697,12 +664,10 @@ bool quad_decode_supported(const jpeg_amd_layout &L)
 // columns and ONE column of 16 x 4 strips for a remainder of at most 16 blocks (1920 x 1080: 7 columns x 17 stacks + 1 x 9
 // = 128 stacks per image for 126.6 stacks' worth of blocks, where 15 columns of 16 x 4 strips need 135 and 8 of 32 x 2 136).
 struct QuadCut { int parts; int bx[2], sx0[2], cols[2]; };
+constexpr int kTicketTrips = 16;   // tickets for walks of at least 16 trips (kernel header: shorter ones are better planned than drawn)
 static long quad_stacks(int cols, int uy, int by) { return (long)cols * (((uy + by - 1) / by + 3) / 4); }
 QuadCut quad_cut(int ux, int uy, long n_images, long resident)
 {
-#ifdef JA_X_FORCE_BX
-    return QuadCut{1, {JA_X_FORCE_BX, 0}, {0, 0}, {(ux + JA_X_FORCE_BX - 1) / JA_X_FORCE_BX, 0}};
-#endif
     const long wide = quad_stacks((ux + 31) / 32, uy, 2), narrow = quad_stacks((ux + 15) / 16, uy, 4);
     QuadCut best = narrow < wide ? QuadCut{1, {16, 0}, {0, 0}, {(ux + 15) / 16, 0}} : QuadCut{1, {32, 0}, {0, 0}, {(ux + 31) / 32, 0}};
     const int whole = ux / 32, rest = ux - 32 * whole;
@@ -747,11 +712,7 @@ hipError_t launch_quad_decode(hipStream_t stream, int n_images, const jpeg_amd_l
         const long nstacks = (long)a.stacks_per_image * n_images;
         if (nstacks > 0x3fffffffL) return hipErrorInvalidValue;
         a.nstacks = (int)nstacks;
-        // tickets for walks of at least 16 trips (kernel header: shorter ones are better planned than drawn)
-#ifndef JA_X_TICKET_TRIPS
-#define JA_X_TICKET_TRIPS 16
-#endif
-        a.tickets = nstacks >= (long)(JA_X_TICKET_TRIPS) * resident(bx) ? d_walk_counters : nullptr;
+        a.tickets = nstacks >= (long)kTicketTrips * resident(bx) ? d_walk_counters : nullptr;
         if (a.tickets) {   // (a 2 us node in front of a call of a millisecond or more)
             const hipError_t m = hipMemsetAsync(a.tickets, 0, sizeof(uint32_t), stream);
             if (m != hipSuccess) return m;

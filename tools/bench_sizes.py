@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fused 4:2:0 decode time for one image of several sizes and for batches, RGB and YCbCr targets
-(development aid; A/B against a tools/build_exp.sh build through JPEG_AMD_LIBRARY)."""
+(development aid; A/B against a tools/build_exp.py build through JPEG_AMD_LIBRARY)."""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase wall cycles of k_generic_fused's waves, one 8192 x 8192 4:2:0 12-bit image (needs a -DJA_GEN_PHASE build):
-    tools/build_exp.sh gphase -DJA_GEN_PHASE
+    tools/build_exp.py gphase -DJA_GEN_PHASE
     JPEG_AMD_LIBRARY=tools/exp/libjpeg_amd_gphase.so python tools/phase_generic.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase wall cycles of k_quad420's waves (one 8192 x 8192 4:2:0 image) (needs a -DJA_PHASE_PROFILE build):
-    tools/build_exp.sh prof -DJA_PHASE_PROFILE
+    tools/build_exp.py prof -DJA_PHASE_PROFILE
     JPEG_AMD_LIBRARY=tools/exp/libjpeg_amd_prof.so python tools/phase_profile.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How many workgroups of k_encode_fused are resident at once?  (needs a -DJA_ENC_TIMELINE build)
-    tools/build_exp.sh enctl -DJA_ENC_TIMELINE; JPEG_AMD_LIBRARY=tools/exp/libjpeg_amd_enctl.so python tools/timeline_encode.py [size]"""
+    tools/build_exp.py enctl -DJA_ENC_TIMELINE; JPEG_AMD_LIBRARY=tools/exp/libjpeg_amd_enctl.so python tools/timeline_encode.py [size]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -636,18 +636,17 @@ def region_window(size, layout: Layout, region, cosite: bool = False, units=None
     return [(w[p].x, w[p].y, w[p].width, w[p].height) for p in range(layout.count)]
 
 
-def decode_regions(ctx: Context, size, layout: Layout, planes, quanta, regions, q: Optional[Sequence[int]] = None, color=RGB,
-                   cosite: bool = False):
-    """Decode n images of one layout, each cropped to its own region, in one call (jpeg_amd_decode_region_batch).
-    planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or device); regions: [n, 4] of (x, y, width,
-    height) in pixels.  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+def _batch_args(ctx: Context, size, layout: Layout, planes, quanta, q, n=None):
+    """What the batch decodes of n images of one layout check and pass alike; n=None takes n from the planes.  -> (head, keep):
+    the arguments between the context and `cosited` (layout, n, plane pointers and strides, tables, their stride and count),
+    and the (n, planes, quanta on the device, c layout) that the pointers in `head` point into."""
     torch = _torch()
-    regs = np.ascontiguousarray(np.asarray(regions, np.int32).reshape(-1, 4))
-    n = regs.shape[0]
     q = list(q) if q is not None else _dedupe_q(layout)
     planes = list(planes)
     if len(planes) != layout.count or len(q) != layout.count:
         raise ValueError("plane count does not match layout")
+    if n is None:
+        n = int(planes[0].shape[0]) if planes and planes[0].dim() == 4 else -1
     for p in planes:
         if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
             raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
@@ -657,16 +656,28 @@ def decode_regions(ctx: Context, size, layout: Layout, planes, quanta, regions, 
     if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
         raise ValueError("quanta: [n, ntables, 64]")
     L = layout.c_layout(size, units, q)
+    ntables = int(quanta.shape[1])
+    head = (C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
+            ntables * 64, ntables)
+    return head, (n, planes, quanta, L)
+
+
+def decode_regions(ctx: Context, size, layout: Layout, planes, quanta, regions, q: Optional[Sequence[int]] = None, color=RGB,
+                   cosite: bool = False):
+    """Decode n images of one layout, each cropped to its own region, in one call (jpeg_amd_decode_region_batch).
+    planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or device); regions: [n, 4] of (x, y, width,
+    height) in pixels.  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+    regs = np.ascontiguousarray(np.asarray(regions, np.int32).reshape(-1, 4))
+    n = regs.shape[0]
+    head, keep = _batch_args(ctx, size, layout, planes, quanta, q, n)
     areas = [3 * int(w) * int(h) for w, h in regs[:, 2:4]] if n else [0]
     stride = max(max(areas), 0)
-    out = ctx.empty(n * stride, torch.uint8)
+    out = ctx.empty(n * stride, _torch().uint8)
     h_regions = (_lib.Region * max(n, 1))()
     for i, (x, y, w, h) in enumerate(regs.tolist()):
         h_regions[i].x, h_regions[i].y, h_regions[i].width, h_regions[i].height = x, y, w, h
-    _lib.check(_lib.lib().jpeg_amd_decode_region_batch(
-        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() for p in planes]), quanta.data_ptr(),
-        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_regions, out.data_ptr(), stride),
-        "jpeg_amd_decode_region_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_region_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_regions, out.data_ptr(),
+                                                       stride), "jpeg_amd_decode_region_batch", ctx.handle)
     return [out[i * stride:i * stride + areas[i]].view(int(regs[i, 3]), int(regs[i, 2]), 3) for i in range(n)]
 
 
@@ -682,28 +693,13 @@ def decode_scaled(ctx: Context, size, layout: Layout, planes, quanta, denom: int
                   cosite: bool = False):
     """Decode n images of one layout at 1/denom size in one call (jpeg_amd_decode_scaled_batch).  planes[p]: device int16
     [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or device).  Returns one uint8 tensor [n, H', W', 3]."""
-    torch = _torch()
-    q = list(q) if q is not None else _dedupe_q(layout)
-    planes = list(planes)
-    if len(planes) != layout.count or len(q) != layout.count:
-        raise ValueError("plane count does not match layout")
-    n = int(planes[0].shape[0]) if planes and planes[0].dim() == 4 else -1
-    for p in planes:
-        if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
-            raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
-    units = [(int(p.shape[2]), int(p.shape[1])) for p in planes]
-    if isinstance(quanta, np.ndarray):
-        quanta = ctx.upload(np.asarray(quanta, np.uint16))
-    if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
-        raise ValueError("quanta: [n, ntables, 64]")
+    head, keep = _batch_args(ctx, size, layout, planes, quanta, q)
+    n = keep[0]
     w, h = scaled_size(size, denom)
-    L = layout.c_layout(size, units, q)
     stride = 3 * w * h
-    out = ctx.empty(n * stride, torch.uint8)
-    _lib.check(_lib.lib().jpeg_amd_decode_scaled_batch(
-        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
-        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, int(denom), out.data_ptr(), stride),
-        "jpeg_amd_decode_scaled_batch", ctx.handle)
+    out = ctx.empty(n * stride, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_scaled_batch(ctx.handle, *head, 1 if cosite else 0, color.code, int(denom), out.data_ptr(),
+                                                       stride), "jpeg_amd_decode_scaled_batch", ctx.handle)
     return out.view(n, h, w, 3)
 
 
@@ -734,27 +730,14 @@ def view_denom(source_size, want_size) -> int:
 
 
 def _view_batch_args(ctx: Context, size, layout: Layout, planes, quanta, views, q):
-    """The arguments decode_views and decode_resized share: (vs [n, 5], planes, quanta on the device, c layout, c views)."""
-    torch = _torch()
+    """The arguments decode_views, decode_resized and decode_tensors share: (vs [n, 5], head and keep of _batch_args, c views)."""
     vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
     n = vs.shape[0]
-    q = list(q) if q is not None else _dedupe_q(layout)
-    planes = list(planes)
-    if len(planes) != layout.count or len(q) != layout.count:
-        raise ValueError("plane count does not match layout")
-    for p in planes:
-        if p.dtype != torch.int16 or not p.is_contiguous() or p.dim() != 4 or p.shape[0] != n:
-            raise ValueError("planes: contiguous int16 device tensors [n, uy, ux, 64]")
-    units = [(int(p.shape[2]), int(p.shape[1])) for p in planes]
-    if isinstance(quanta, np.ndarray):
-        quanta = ctx.upload(np.asarray(quanta, np.uint16))
-    if quanta.dim() != 3 or quanta.shape[0] != n or quanta.shape[2] != 64 or not quanta.is_contiguous():
-        raise ValueError("quanta: [n, ntables, 64]")
-    L = layout.c_layout(size, units, q)
+    head, keep = _batch_args(ctx, size, layout, planes, quanta, q, n)
     h_views = (_lib.View * max(n, 1))()
     for i, row in enumerate(vs.tolist()):
         h_views[i] = _view(row[0], row[1:])
-    return vs, planes, quanta, L, h_views
+    return vs, head, keep, h_views
 
 
 def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: Optional[Sequence[int]] = None, color=RGB,
@@ -762,16 +745,13 @@ def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: O
     """Decode n images of one layout, each at its own denominator and cropped to its own rectangle of that scaled image, in
     one call (jpeg_amd_decode_view_batch).  planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or
     device); views: [n, 5] of (denom, x, y, width, height).  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
-    torch = _torch()
-    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
     stride = max(areas)
-    out = ctx.empty(n * stride, torch.uint8)
-    _lib.check(_lib.lib().jpeg_amd_decode_view_batch(
-        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
-        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, out.data_ptr(), stride),
-        "jpeg_amd_decode_view_batch", ctx.handle)
+    out = ctx.empty(n * stride, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_view_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, out.data_ptr(), stride),
+               "jpeg_amd_decode_view_batch", ctx.handle)
     return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
 
 
@@ -780,16 +760,13 @@ def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     """decode_views with every image bilinearly resampled to out_size (Wt, Ht), in one call
     (jpeg_amd_decode_resized_batch; include/jpeg_amd.h holds the filter's contract).  Arguments as decode_views.  Returns one
     uint8 tensor [n, Ht, Wt, 3]."""
-    torch = _torch()
-    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht = int(out_size[0]), int(out_size[1])
     stride = 3 * max(wt, 0) * max(ht, 0)
-    out = ctx.empty(n * stride, torch.uint8)
-    _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(
-        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
-        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, wt, ht, out.data_ptr(), stride),
-        "jpeg_amd_decode_resized_batch", ctx.handle)
+    out = ctx.empty(n * stride, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                        out.data_ptr(), stride), "jpeg_amd_decode_resized_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
@@ -888,13 +865,11 @@ def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     output", holds the contract): every view resampled to out_size (Wt, Ht), mirrored along x where flips[i] is set,
     normalised by `spec` (tensor_spec) and stored in its dtype and layout.  Returns one tensor [n, 3, Ht, Wt] ("chw") or
     [n, Ht, Wt, 3] ("hwc")."""
-    vs, planes, quanta, L, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_batch(
-        ctx.handle, C.byref(L), n, _ptrs(planes), _lib.size_array([p[0].numel() if n else 0 for p in planes]), quanta.data_ptr(),
-        int(quanta.shape[1]) * 64, int(quanta.shape[1]), 1 if cosite else 0, color.code, h_views, wt, ht, C.byref(spec), h_flip,
-        out.data_ptr(), stride), "jpeg_amd_decode_tensor_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht, C.byref(spec),
+                                                       h_flip, out.data_ptr(), stride), "jpeg_amd_decode_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 

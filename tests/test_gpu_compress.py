@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _golden as G
+from _calls import ctx  # noqa: F401  (the fixture)
 from jpeg_amd import _lib
 from jpeg_amd.api import _scan_array, _metadata_array
 
@@ -15,12 +16,6 @@ pytestmark = pytest.mark.gpu
 
 SCANS = [[(0, 0, 0)], [(1, 1, 1), (2, 1, 1)]]      # examples/encode-basic/main.swift:42-46
 JFIF = [("jfif", (2, 2, 1, 1))]                                # .init(version: .v1_2, density: (1, 1, .centimeters))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import jpeg_amd as J
-    return J.Context()
 
 
 def _quanta(level):

@@ -7,15 +7,10 @@ import numpy as np
 import pytest
 
 import _golden as G
+from _calls import ctx  # noqa: F401  (the fixture)
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import jpeg_amd as J
-    return J.Context()
 
 
 def _decompress(ctx, path, color):

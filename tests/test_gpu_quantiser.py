@@ -18,7 +18,7 @@ import _reduce_ref as R
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0x5A5A
+FILL = 0x5A5A
 CROP = (3, 5)                 # a width that is no multiple of 8: the byte-wise fetch, an edge-replicated block column and row
 
 
@@ -65,7 +65,7 @@ def _layout(e, b):
 
 
 def _outputs(e, units, n):
-    return [e["torch"].full((n, 64 * ux * uy), SENTINEL, dtype=e["torch"].int16, device=e["ctx"].torch_device) for ux, uy in units]
+    return [e["torch"].full((n, 64 * ux * uy), FILL, dtype=e["torch"].int16, device=e["ctx"].torch_device) for ux, uy in units]
 
 
 def _device(e, a):
@@ -233,7 +233,7 @@ def test_spectral_reduce_output_ties(env, denom):
     d_in = _device(e, coef.reshape(n, -1))
     d_q = _device(e, np.ones((n, 1, 64), np.uint16))
     d_qo = _device(e, tables)
-    out = torch.full((n, 64 * units[0] * units[1]), SENTINEL, dtype=torch.int16, device=e["ctx"].torch_device)
+    out = torch.full((n, 64 * units[0] * units[1]), FILL, dtype=torch.int16, device=e["ctx"].torch_device)
     st = e["lib"].jpeg_amd_spectral_reduce_batch(e["ctx"].handle, C.byref(L), n, denom, _lib.ptr_array([d_in.data_ptr()]),
                                                  _lib.size_array([64 * ux * uy]), d_q.data_ptr(), 64, 1, d_qo.data_ptr(),
                                                  _lib.ptr_array([out.data_ptr()]), _lib.size_array([64 * units[0] * units[1]]))

@@ -14,45 +14,17 @@ import _reduce_ref as R
 import _scaled_ref as S
 import _transform_ref as T
 import jpeg_amd as J
+from _calls import c_layout, plane_factors, plane_ptrs, plane_units
+from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _golden import GOLDEN
 from jpeg_amd import _lib
 from jpeg_amd.synth import natural_planes_torch
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DENOMS = (2, 4, 8)
-SENTINEL = 0x5A5A
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    return J.Context(0)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
-
-
-def _layout(w, h, factors, scale=None, precision=8, qi=None):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1) if qi is None else qi[p]
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
-
-
-def _units(L):
-    return [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
-
-
-def _factors(L):
-    return [(L.factor_x[p], L.factor_y[p]) for p in range(L.nplanes)]
+FILL = 0x5A5A                                               # what every int16 of an output buffer holds before a call
 
 
 def _reduce_layout(L, denom):
@@ -63,7 +35,7 @@ def _reduce_layout(L, denom):
 
 def _synthetic(ctx, torch, L, n, seed, ntables=None):
     """Natural planes, a tenth of the blocks with DC = +-2000 (the clamp is hit on both sides), and n table sets."""
-    planes = natural_planes_torch(_units(L), n, ctx.torch_device, seed=seed)
+    planes = natural_planes_torch(plane_units(L), n, ctx.torch_device, seed=seed)
     gen = torch.Generator(device=ctx.torch_device).manual_seed(seed + 1)
     for p in planes:
         pick = torch.rand(p.shape[:3], generator=gen, device=ctx.torch_device)
@@ -75,9 +47,9 @@ def _synthetic(ctx, torch, L, n, seed, ntables=None):
 
 
 def _out_planes(ctx, torch, O_, n, gap=0):
-    """Per plane one int16 buffer [n * (samples + gap) + gap] filled with SENTINEL, and the strides."""
-    strides = [64 * ux * uy + gap for ux, uy in _units(O_)]
-    return [torch.full((n * s + gap,), SENTINEL, dtype=torch.int16, device=ctx.torch_device) for s in strides], strides
+    """Per plane one int16 buffer [n * (samples + gap) + gap] filled with FILL, and the strides."""
+    strides = [64 * ux * uy + gap for ux, uy in plane_units(O_)]
+    return [torch.full((n * s + gap,), FILL, dtype=torch.int16, device=ctx.torch_device) for s in strides], strides
 
 
 def _batch(ctx, L, n, denom, in_ptrs, in_strides, dq, q_stride, ntables, dqo, out_ptrs, out_strides):
@@ -93,13 +65,13 @@ def _reduce_batch(ctx, torch, L, n, planes, dq, ntables, denom, dqo=None):
     outs, strides = _out_planes(ctx, torch, O_, n)
     assert _batch(ctx, L, n, denom, [p.data_ptr() for p in planes], [p[0].numel() for p in planes], dq, ntables * 64, ntables,
                   dqo, [o.data_ptr() for o in outs], strides) == 0
-    return [o.cpu().numpy().reshape(n, uy, ux, 64) for o, (ux, uy) in zip(outs, _units(O_))]
+    return [o.cpu().numpy().reshape(n, uy, ux, 64) for o, (ux, uy) in zip(outs, plane_units(O_))]
 
 
 def _reference(L, planes_host, q_host, i, denom, qo_host=None):
     """Image i of a batch through _reduce_ref: planes_host[p] [n, uy, ux, 64], q_host [n, ntables, 64]."""
     qi = [L.qi[p] for p in range(L.nplanes)]
-    size, planes = R.reduce_image([pl[i] for pl in planes_host], [q_host[i, t] for t in qi], _factors(L), (L.scale_x, L.scale_y),
+    size, planes = R.reduce_image([pl[i] for pl in planes_host], [q_host[i, t] for t in qi], plane_factors(L), (L.scale_x, L.scale_y),
                                   (L.width, L.height), denom, None if qo_host is None else [qo_host[i, t] for t in qi], L.precision)
     return planes
 
@@ -136,7 +108,7 @@ def _check_against_reference(ctx, torch, L, seed, with_qout):
 @pytest.mark.parametrize("size", SIZES, ids=["%dx%d" % s for s in SIZES])
 @pytest.mark.parametrize("name", sorted(LAYOUTS))
 def test_synthetic_batches_match_the_reference(ctx, torch, name, size):
-    L = _layout(size[0], size[1], LAYOUTS[name])
+    L = c_layout(size[0], size[1], LAYOUTS[name])
     _check_against_reference(ctx, torch, L, size[0] * 31 + size[1], with_qout=(size[0] + len(name)) % 2 == 0)
 
 
@@ -144,13 +116,13 @@ def test_synthetic_batches_match_the_reference(ctx, torch, name, size):
 def test_tile_seams_at_every_denominator(ctx, torch, name):
     """The kernel's tiles are 16 x 16 output blocks at denominators 2 and 4 and 8 x 8 at 8: 531 x 523 gives more than one
     tile in both axes at each of them (34 x 33, 17 x 17 and 9 x 9 luma blocks), with partial tiles at the far edges."""
-    L = _layout(531, 523, LAYOUTS[name])
+    L = c_layout(531, 523, LAYOUTS[name])
     _check_against_reference(ctx, torch, L, 531, with_qout=False)
 
 
 def test_a_factor_that_does_not_divide_the_scale(ctx, torch):
     """3 in 4 at width 85: the output has a block column with no source sample of its own, replicated whole."""
-    L = _layout(85, 15, [(4, 1), (3, 1), (1, 1)])
+    L = c_layout(85, 15, [(4, 1), (3, 1), (1, 1)])
     sl = _lib.Layout()
     larger = False
     for denom in DENOMS:
@@ -164,7 +136,7 @@ def test_the_12_bit_four_plane_layout(ctx, torch):
     """The layout of examples/custom-color: precision 12, four planes, a table per plane."""
     _, _, factors, _, _, m = G.custom_color()
     assert len(factors) == 4
-    L = _layout(131, 65, factors, precision=12, qi=[0, 1, 2, 3])
+    L = c_layout(131, 65, factors, precision=12, qi=[0, 1, 2, 3])
     _check_against_reference(ctx, torch, L, 12, with_qout=True)
 
 
@@ -176,7 +148,7 @@ def test_one_launch_equals_the_staged_route(ctx, torch, name, size):
     """jpeg_amd_spectral_idct_scaled planes -> jpeg_amd_planar_fdct under jpeg_amd_scaled_layout's layout (the factors divide
     the scale, so its units are the reduced layout's)."""
     lib = _lib.lib()
-    L = _layout(size[0], size[1], LAYOUTS[name])
+    L = c_layout(size[0], size[1], LAYOUTS[name])
     planes, dq, ntables = _synthetic(ctx, torch, L, 1, size[0] + 7 * size[1])
     one = [p[0] for p in planes]
     qh = np.ascontiguousarray(dq[0].cpu().numpy().astype(np.uint16))
@@ -184,16 +156,15 @@ def test_one_launch_equals_the_staged_route(ctx, torch, name, size):
         sl = _lib.Layout()
         assert lib.jpeg_amd_scaled_layout(C.byref(L), denom, C.byref(sl)) == 0
         O_ = _reduce_layout(L, denom)
-        assert _units(sl) == _units(O_) and (sl.width, sl.height) == (O_.width, O_.height)
-        samples = [torch.full((64 * ux * uy,), -1, dtype=torch.int16, device=ctx.torch_device) for ux, uy in _units(sl)]
-        assert lib.jpeg_amd_spectral_idct_scaled(ctx.handle, C.byref(L), _lib.ptr_array([p.data_ptr() for p in one]),
-                                                 qh.ctypes.data, ntables, denom, _lib.ptr_array([p.data_ptr() for p in samples])) == 0
-        staged = [torch.full((64 * ux * uy,), SENTINEL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in _units(sl)]
-        assert lib.jpeg_amd_planar_fdct(ctx.handle, C.byref(sl), _lib.ptr_array([p.data_ptr() for p in samples]), qh.ctypes.data,
-                                        ntables, _lib.ptr_array([p.data_ptr() for p in staged])) == 0
-        fused = [torch.full((64 * ux * uy,), SENTINEL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in _units(O_)]
-        assert lib.jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, _lib.ptr_array([p.data_ptr() for p in one]),
-                                            qh.ctypes.data, ntables, None, _lib.ptr_array([p.data_ptr() for p in fused])) == 0
+        assert plane_units(sl) == plane_units(O_) and (sl.width, sl.height) == (O_.width, O_.height)
+        samples = [torch.full((64 * ux * uy,), -1, dtype=torch.int16, device=ctx.torch_device) for ux, uy in plane_units(sl)]
+        assert lib.jpeg_amd_spectral_idct_scaled(ctx.handle, C.byref(L), plane_ptrs(one), qh.ctypes.data, ntables, denom,
+                                                 plane_ptrs(samples)) == 0
+        staged = [torch.full((64 * ux * uy,), FILL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in plane_units(sl)]
+        assert lib.jpeg_amd_planar_fdct(ctx.handle, C.byref(sl), plane_ptrs(samples), qh.ctypes.data, ntables, plane_ptrs(staged)) == 0
+        fused = [torch.full((64 * ux * uy,), FILL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in plane_units(O_)]
+        assert lib.jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, plane_ptrs(one), qh.ctypes.data, ntables, None,
+                                            plane_ptrs(fused)) == 0
         for p in range(L.nplanes):
             assert torch.equal(staged[p], fused[p]), (name, size, denom, p)
 
@@ -203,7 +174,7 @@ def test_one_launch_equals_the_staged_route(ctx, torch, name, size):
 def test_other_output_tables_and_the_null_default(ctx, torch):
     """Luminance level 0.5 in, 2.0 out; NULL = the input tables."""
     lib = _lib.lib()
-    L = _layout(131, 257, LAYOUTS["420"], qi=[0, 0, 0])
+    L = c_layout(131, 257, LAYOUTS["420"], qi=[0, 0, 0])
     planes, _, _ = _synthetic(ctx, torch, L, 1, 5)
     one = [p[0] for p in planes]
     ph = [p.cpu().numpy() for p in planes]
@@ -214,10 +185,9 @@ def test_other_output_tables_and_the_null_default(ctx, torch):
         O_ = _reduce_layout(L, denom)
         results = []
         for qo in (q_out, None):
-            outs = [torch.full((64 * ux * uy,), SENTINEL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in _units(O_)]
-            assert lib.jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, _lib.ptr_array([p.data_ptr() for p in one]),
-                                                q_in.ctypes.data, 1, qo.ctypes.data if qo is not None else None,
-                                                _lib.ptr_array([p.data_ptr() for p in outs])) == 0
+            outs = [torch.full((64 * ux * uy,), FILL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in plane_units(O_)]
+            assert lib.jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, plane_ptrs(one), q_in.ctypes.data, 1,
+                                                qo.ctypes.data if qo is not None else None, plane_ptrs(outs)) == 0
             want = _reference(L, ph, q_in[None, None, :], 0, denom, None if qo is None else qo[None, None, :])
             for p in range(3):
                 assert (outs[p].cpu().numpy().reshape(want[p].shape) == want[p]).all(), (denom, qo is None, p)
@@ -229,7 +199,7 @@ def test_other_output_tables_and_the_null_default(ctx, torch):
 
 @pytest.mark.parametrize("name", ["420", "411"])
 def test_batch_of_64_with_stride_gaps_and_against_single_calls(ctx, torch, name):
-    L = _layout(33, 17, LAYOUTS[name])
+    L = c_layout(33, 17, LAYOUTS[name])
     n, gap = 64, 48
     planes, dq, ntables = _synthetic(ctx, torch, L, n, 64)
     qh = np.ascontiguousarray(dq.cpu().numpy().astype(np.uint16))
@@ -246,18 +216,17 @@ def test_batch_of_64_with_stride_gaps_and_against_single_calls(ctx, torch, name)
         # the outputs start `gap` elements into their buffers: a gap on both sides of every image
         assert _batch(ctx, L, n, denom, [b.data_ptr() for b in spaced], in_strides, dq, ntables * 64, ntables, None,
                       [o.data_ptr() + 2 * gap for o in outs], strides) == 0
-        for p, (ux, uy) in enumerate(_units(O_)):
+        for p, (ux, uy) in enumerate(plane_units(O_)):
             m = 64 * ux * uy
             host = outs[p].cpu().numpy()
-            assert (host[:gap] == SENTINEL).all()
+            assert (host[:gap] == FILL).all()
             body = host[gap:].reshape(n, strides[p])
-            assert (body[:, m:] == SENTINEL).all()
-            assert (body[:, :m] != SENTINEL).any()
+            assert (body[:, m:] == FILL).all()
+            assert (body[:, :m] != FILL).any()
         for i in range(n):
-            single = [torch.full((64 * ux * uy,), SENTINEL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in _units(O_)]
-            assert _lib.lib().jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, _lib.ptr_array([p[i].data_ptr() for p in planes]),
-                                                       qh[i].ctypes.data, ntables, None,
-                                                       _lib.ptr_array([s.data_ptr() for s in single])) == 0
+            single = [torch.full((64 * ux * uy,), FILL, dtype=torch.int16, device=ctx.torch_device) for ux, uy in plane_units(O_)]
+            assert _lib.lib().jpeg_amd_spectral_reduce(ctx.handle, C.byref(L), denom, plane_ptrs([p[i] for p in planes]),
+                                                       qh[i].ctypes.data, ntables, None, plane_ptrs(single)) == 0
             for p in range(L.nplanes):
                 m = single[p].numel()
                 assert torch.equal(single[p], outs[p][gap + i * strides[p]:gap + i * strides[p] + m]), (name, denom, i, p)
@@ -265,7 +234,7 @@ def test_batch_of_64_with_stride_gaps_and_against_single_calls(ctx, torch, name)
 
 @pytest.mark.parametrize("name", ["y8", "420", "411"])
 def test_unread_coefficients_do_not_matter(ctx, torch, name):
-    L = _layout(131, 65, LAYOUTS[name])
+    L = c_layout(131, 65, LAYOUTS[name])
     planes, dq, ntables = _synthetic(ctx, torch, L, 2, 99)
     for denom in DENOMS:
         N = 8 // denom
@@ -286,19 +255,19 @@ def test_unread_coefficients_do_not_matter(ctx, torch, name):
 
 
 def test_an_empty_batch_is_ok(ctx, torch):
-    L = _layout(33, 17, LAYOUTS["420"])
+    L = c_layout(33, 17, LAYOUTS["420"])
     assert _lib.lib().jpeg_amd_spectral_reduce_batch(ctx.handle, C.byref(L), 0, 2, None, None, None, 0, 2, None, None, None) == 0
     planes, dq, ntables = _synthetic(ctx, torch, L, 1, 4)
     outs, strides = _out_planes(ctx, torch, _reduce_layout(L, 2), 1)
     assert _batch(ctx, L, 0, 2, [p.data_ptr() for p in planes], [p[0].numel() for p in planes], dq, ntables * 64, ntables, None,
                   [o.data_ptr() for o in outs], strides) == 0
     ctx.synchronize()
-    assert all((o == SENTINEL).all() for o in outs)
+    assert all((o == FILL).all() for o in outs)
 
 
 def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
     lib = _lib.lib()
-    L = _layout(33, 17, LAYOUTS["420"])
+    L = c_layout(33, 17, LAYOUTS["420"])
     n = 2
     planes, dq, ntables = _synthetic(ctx, torch, L, n, 3)
     qh = np.ascontiguousarray(dq.cpu().numpy().astype(np.uint16))
@@ -337,7 +306,7 @@ def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
     assert single(denom=1) == _lib.EINVAL
     assert single(ins=[planes[0][1].data_ptr(), None, planes[2][1].data_ptr()]) == _lib.EINVAL
     ctx.synchronize()
-    assert all((o == SENTINEL).all() for o in outs)
+    assert all((o == FILL).all() for o in outs)
     # the context still works
     assert call() == 0
     assert single() == 0
@@ -403,7 +372,7 @@ def test_file_to_file(ctx, name, denom):
 def test_python_api(ctx, torch):
     layout = J.Layout("ycc8", {1: J.Component((2, 2), 0), 2: J.Component((1, 1), 1), 3: J.Component((1, 1), 1)})
     size = (131, 65)
-    L = _layout(size[0], size[1], LAYOUTS["420"])
+    L = c_layout(size[0], size[1], LAYOUTS["420"])
     planes, dq, ntables = _synthetic(ctx, torch, L, 1, 11)
     ph = [p.cpu().numpy() for p in planes]
     qh = dq.cpu().numpy().astype(np.uint16)

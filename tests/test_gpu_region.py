@@ -10,71 +10,36 @@ import pytest
 
 import _transform_ref as R
 import jpeg_amd as J
+from _calls import SENTINEL, Out, c_layout, c_regions, full_batch, plane_ptrs, plane_units
+from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _golden import GOLDEN
 from jpeg_amd import _lib
 from jpeg_amd.synth import natural_planes_torch
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
-SENTINEL = 0xA5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    return J.Context(0)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
-
-
-def _layout(w, h, factors, scale=None):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, 8, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
-
-
-def _regions_arg(regions):
-    arr = (_lib.Region * max(len(regions), 1))()
-    for i, r in enumerate(regions):
-        arr[i].x, arr[i].y, arr[i].width, arr[i].height = (int(v) for v in r)
-    return arr
 
 
 def _region_batch(ctx, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, out, stride):
     return _lib.lib().jpeg_amd_decode_region_batch(
-        ctx.handle, C.byref(L), len(regions), _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(coef_stride),
-        dq.data_ptr(), q_stride, ntables, cosited, color, _regions_arg(regions), out.data_ptr() if out is not None else None,
+        ctx.handle, C.byref(L), len(regions), plane_ptrs(planes), _lib.size_array(coef_stride),
+        dq.data_ptr(), q_stride, ntables, cosited, color, c_regions(regions), out.data_ptr() if out is not None else None,
         stride)
 
 
-def _full_batch(ctx, torch, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, n):
-    out = torch.empty((n, L.height, L.width, 3), dtype=torch.uint8, device=ctx.torch_device)
-    assert _lib.lib().jpeg_amd_decode_batch(
-        ctx.handle, C.byref(L), n, _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(coef_stride),
-        dq.data_ptr(), q_stride, ntables, cosited, color, out.data_ptr(), 3 * L.width * L.height) == 0
+def _decode_regions(ctx, torch, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, gap=0):
+    """-> the output buffer, filled with SENTINEL before the call: nothing behind the last image's stride."""
+    out = Out(ctx, torch, [3 * r[2] * r[3] for r in regions], gap=gap)
+    assert _region_batch(ctx, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, out.buf, out.stride) == 0
     return out
 
 
-def _decode_regions(ctx, torch, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, gap=0):
-    stride = max(3 * r[2] * r[3] for r in regions) + gap
-    out = torch.full((len(regions) * stride,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
-    assert _region_batch(ctx, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, out, stride) == 0
-    return out, stride
-
-
-def _crop(out, stride, i, r):
+def _crop(out, i, r):
+    """Image i, still on the device."""
     x, y, w, h = r
-    return out[i * stride:i * stride + 3 * w * h].view(h, w, 3)
+    return out.device(i).view(h, w, 3)
 
 
 def _fixture_regions(W, H, sx, sy, rng, k=20):
@@ -133,23 +98,21 @@ def test_fixture_regions_match_the_full_decode_and_the_oracle(ctx, torch, path):
         _, rect = O.decode(planes, list(quanta), factors, (W, H), cosited=bool(cosited), scale=(info.scale_x, info.scale_y))
         for color in (_lib.COLOR_RGB8, _lib.COLOR_YCC8):
             want = (O.unpack_rgb8 if color == _lib.COLOR_RGB8 else O.unpack_ycc8)(rect, nc).reshape(H, W, 3)
-            full = _full_batch(ctx, torch, L, dev, [0] * 4, dq, 0, nc, cosited, color, 1)[0].cpu().numpy()
+            full = full_batch(ctx, torch, L, 1, dev, [0] * 4, dq, 0, nc, cosited, color)[0].cpu().numpy()
             assert (full == want).all()
-            out, stride = _decode_regions(ctx, torch, L, dev, [0] * 4, dq, 0, nc, cosited, color, regs)
-            host = out.cpu().numpy()
+            host = _decode_regions(ctx, torch, L, dev, [0] * 4, dq, 0, nc, cosited, color, regs).images()
             for i, (x, y, w, h) in enumerate(regs):
-                got = host[i * stride:i * stride + 3 * w * h].reshape(h, w, 3)
+                got = host[i].reshape(h, w, 3)
                 assert (got == want[y:y + h, x:x + w]).all(), (os.path.basename(path), cosited, color, (x, y, w, h))
             # the single-image entry point, and a call whose only region is the whole image (the batch path)
             r = regs[5]
             one = torch.full((3 * r[2] * r[3],), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
             reg = _lib.Region(*r)
-            assert _lib.lib().jpeg_amd_decode_region(ctx.handle, C.byref(L), _lib.ptr_array([p.data_ptr() for p in dev]),
-                                                     quanta.ctypes.data, nc, cosited, color, C.byref(reg),
-                                                     one.data_ptr()) == 0
+            assert _lib.lib().jpeg_amd_decode_region(ctx.handle, C.byref(L), plane_ptrs(dev), quanta.ctypes.data, nc, cosited, color,
+                                                     C.byref(reg), one.data_ptr()) == 0
             assert (one.cpu().numpy().reshape(r[3], r[2], 3) == want[r[1]:r[1] + r[3], r[0]:r[0] + r[2]]).all()
-            whole, s = _decode_regions(ctx, torch, L, dev, [0] * 4, dq, 0, nc, cosited, color, [(0, 0, W, H)])
-            assert (whole.cpu().numpy().reshape(H, W, 3) == want).all()
+            whole = _decode_regions(ctx, torch, L, dev, [0] * 4, dq, 0, nc, cosited, color, [(0, 0, W, H)])
+            assert (whole.images()[0].reshape(H, W, 3) == want).all()
 
 
 SYNTH_LAYOUTS = {"444": [(1, 1)] * 3, "422": [(2, 1), (1, 1), (1, 1)], "440": [(1, 2), (1, 1), (1, 1)],
@@ -166,15 +129,15 @@ def _random_regions(rng, W, H, n):
 
 
 def _check_against_batch(ctx, torch, L, planes, coef_stride, dq, ntables, cosited, color, regs, chunk=16):
-    out, stride = _decode_regions(ctx, torch, L, planes, coef_stride, dq, ntables * 64, ntables, cosited, color, regs)
+    out = _decode_regions(ctx, torch, L, planes, coef_stride, dq, ntables * 64, ntables, cosited, color, regs)
     n = len(regs)
     for i0 in range(0, n, chunk):
         m = min(chunk, n - i0)
         sub = [p[i0:] if s else p for p, s in zip(planes, coef_stride)]
-        full = _full_batch(ctx, torch, L, sub, coef_stride, dq[i0:], ntables * 64, ntables, cosited, color, m)
+        full = full_batch(ctx, torch, L, m, sub, coef_stride, dq[i0:], ntables * 64, ntables, cosited, color)
         for i in range(i0, i0 + m):
             x, y, w, h = regs[i]
-            assert torch.equal(_crop(out, stride, i, regs[i]), full[i - i0, y:y + h, x:x + w]), (i, regs[i])
+            assert torch.equal(_crop(out, i, regs[i]), full[i - i0, y:y + h, x:x + w]), (i, regs[i])
 
 
 @pytest.mark.parametrize("size", SYNTH_SIZES, ids=["%dx%d" % s for s in SYNTH_SIZES])
@@ -182,8 +145,8 @@ def _check_against_batch(ctx, torch, L, planes, coef_stride, dq, ntables, cosite
 def test_synthetic_batch_of_200_regions(ctx, torch, name, size):
     W, H = size
     factors = SYNTH_LAYOUTS[name]
-    L = _layout(W, H, factors)
-    units = [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
+    L = c_layout(W, H, factors)
+    units = plane_units(L)
     n = 200
     per_image = sum(64 * ux * uy for ux, uy in units)
     distinct = per_image * n * 2 <= (1 << 30)              # else all images share one set of coefficients (stride 0)
@@ -202,8 +165,8 @@ def test_synthetic_batch_of_200_regions(ctx, torch, name, size):
                          ids=["420-cosited", "chroma-third", "chroma-quarter", "chroma-third-both"])
 def test_fallback_layouts(ctx, torch, factors, cosited):
     W, H = 301, 187
-    L = _layout(W, H, factors)
-    units = [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
+    L = c_layout(W, H, factors)
+    units = plane_units(L)
     n = 40
     planes = natural_planes_torch(units, n, ctx.torch_device, seed=11)
     coef_stride = [64 * ux * uy for ux, uy in units] + [0]
@@ -216,18 +179,17 @@ def test_fallback_layouts(ctx, torch, factors, cosited):
     q = dq[0].cpu().numpy().view(np.uint16)
     _, rect = O.decode(host, [q[min(p, 1)] for p in range(3)], factors, (W, H), cosited=bool(cosited))
     want = O.unpack_rgb8(rect, 3).reshape(H, W, 3)
-    out, stride = _decode_regions(ctx, torch, L, [p[0] for p in planes], [0] * 4, dq[0:1], 128, 2, cosited,
-                                  _lib.COLOR_RGB8, regs[:1])
+    out = _decode_regions(ctx, torch, L, [p[0] for p in planes], [0] * 4, dq[0:1], 128, 2, cosited, _lib.COLOR_RGB8, regs[:1])
     x, y, w, h = regs[0]
-    assert (_crop(out, stride, 0, regs[0]).cpu().numpy() == want[y:y + h, x:x + w]).all()
+    assert (_crop(out, 0, regs[0]).cpu().numpy() == want[y:y + h, x:x + w]).all()
 
 
 @pytest.mark.parametrize("factors,cosited", [([(2, 2), (1, 1), (1, 1)], 0), ([(2, 2), (1, 1), (1, 1)], 1), ([(1, 1)], 0)],
                          ids=["420", "420-cosited-fallback", "y8"])
 def test_batch_of_64_leaves_the_stride_gaps_alone(ctx, torch, factors, cosited):
     W, H = 333, 251
-    L = _layout(W, H, factors)
-    units = [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
+    L = c_layout(W, H, factors)
+    units = plane_units(L)
     n = 64
     planes = natural_planes_torch(units, n, ctx.torch_device, seed=17)
     coef_stride = [64 * ux * uy for ux, uy in units] + [0] * (4 - len(units))
@@ -235,17 +197,15 @@ def test_batch_of_64_leaves_the_stride_gaps_alone(ctx, torch, factors, cosited):
     dq = torch.randint(1, 24, (n, ntables, 64), dtype=torch.int16, device=ctx.torch_device,
                        generator=torch.Generator(device=ctx.torch_device).manual_seed(9))
     regs = _random_regions(np.random.default_rng(19), W, H, n)
-    out, stride = _decode_regions(ctx, torch, L, planes, coef_stride, dq, ntables * 64, ntables, cosited,
-                                  _lib.COLOR_RGB8, regs, gap=97)
-    full = _full_batch(ctx, torch, L, planes, coef_stride, dq, ntables * 64, ntables, cosited, _lib.COLOR_RGB8, n)
+    out = _decode_regions(ctx, torch, L, planes, coef_stride, dq, ntables * 64, ntables, cosited, _lib.COLOR_RGB8, regs, gap=97)
+    full = full_batch(ctx, torch, L, n, planes, coef_stride, dq, ntables * 64, ntables, cosited, _lib.COLOR_RGB8)
     for i, (x, y, w, h) in enumerate(regs):
-        assert torch.equal(_crop(out, stride, i, regs[i]), full[i, y:y + h, x:x + w])
-        gap = out[i * stride + 3 * w * h:(i + 1) * stride]
-        assert bool((gap == SENTINEL).all()), i
+        assert torch.equal(_crop(out, i, regs[i]), full[i, y:y + h, x:x + w])
+    out.images()                                            # the sentinel in every byte of the stride gaps
 
 
 def test_zero_images(ctx, torch):
-    L = _layout(64, 64, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(64, 64, [(2, 2), (1, 1), (1, 1)])
     lib = _lib.lib()
     assert lib.jpeg_amd_decode_region_batch(ctx.handle, C.byref(L), 0, None, None, None, 0, 2, 0, _lib.COLOR_RGB8, None,
                                             None, 0) == 0
@@ -253,8 +213,8 @@ def test_zero_images(ctx, torch):
 
 def test_invalid_calls_write_nothing_and_the_context_stays_usable(ctx, torch):
     W, H = 130, 77
-    L = _layout(W, H, [(2, 2), (1, 1), (1, 1)])
-    units = [(L.units_x[p], L.units_y[p]) for p in range(3)]
+    L = c_layout(W, H, [(2, 2), (1, 1), (1, 1)])
+    units = plane_units(L)
     planes = natural_planes_torch(units, 4, ctx.torch_device, seed=23)
     coef_stride = [64 * ux * uy for ux, uy in units] + [0]
     dq = torch.randint(1, 24, (4, 2, 64), dtype=torch.int16, device=ctx.torch_device,
@@ -276,24 +236,24 @@ def test_invalid_calls_write_nothing_and_the_context_stays_usable(ctx, torch):
     ctx.synchronize()
     assert bool((out == SENTINEL).all())
     # the next valid call on the same context
-    got, s = _decode_regions(ctx, torch, L, planes, coef_stride, dq, 128, 2, 0, _lib.COLOR_RGB8, good)
-    full = _full_batch(ctx, torch, L, planes, coef_stride, dq, 128, 2, 0, _lib.COLOR_RGB8, 4)
+    got = _decode_regions(ctx, torch, L, planes, coef_stride, dq, 128, 2, 0, _lib.COLOR_RGB8, good)
+    full = full_batch(ctx, torch, L, 4, planes, coef_stride, dq, 128, 2, 0, _lib.COLOR_RGB8)
     for i, (x, y, w, h) in enumerate(good):
-        assert torch.equal(_crop(got, s, i, good[i]), full[i, y:y + h, x:x + w])
+        assert torch.equal(_crop(got, i, good[i]), full[i, y:y + h, x:x + w])
 
 
 def test_8192_420_region_of_4096_at_1237_901(ctx, torch):
     W = H = 8192
-    L = _layout(W, H, [(2, 2), (1, 1), (1, 1)])
-    units = [(L.units_x[p], L.units_y[p]) for p in range(3)]
+    L = c_layout(W, H, [(2, 2), (1, 1), (1, 1)])
+    units = plane_units(L)
     planes = natural_planes_torch(units, 1, ctx.torch_device, seed=29)
     dq = torch.randint(1, 24, (1, 2, 64), dtype=torch.int16, device=ctx.torch_device,
                        generator=torch.Generator(device=ctx.torch_device).manual_seed(2))
     r = (1237, 901, 4096, 4096)
     for color in (_lib.COLOR_RGB8, _lib.COLOR_YCC8):
-        out, s = _decode_regions(ctx, torch, L, [p[0] for p in planes], [0] * 4, dq, 128, 2, 0, color, [r])
-        full = _full_batch(ctx, torch, L, [p[0] for p in planes], [0] * 4, dq, 128, 2, 0, color, 1)
-        assert torch.equal(_crop(out, s, 0, r), full[0, 901:901 + 4096, 1237:1237 + 4096])
+        out = _decode_regions(ctx, torch, L, [p[0] for p in planes], [0] * 4, dq, 128, 2, 0, color, [r])
+        full = full_batch(ctx, torch, L, 1, [p[0] for p in planes], [0] * 4, dq, 128, 2, 0, color)
+        assert torch.equal(_crop(out, 0, r), full[0, 901:901 + 4096, 1237:1237 + 4096])
 
 
 def test_python_api(ctx, torch):
@@ -322,3 +282,7 @@ def test_python_api(ctx, torch):
     for o, (x, y, w, h) in zip(outs, regs):
         assert tuple(o.shape) == (h, w, 3)
         assert torch.equal(o, full[y:y + h, x:x + w])
+    # an empty batch is no images, from decode_regions as from decode_views
+    none = [p[:0] for p in dev]
+    assert J.decode_regions(ctx, (W, H), layout, none, qn[:0], np.zeros((0, 4)), q=[0, 1, 2]) == []
+    assert J.decode_views(ctx, (W, H), layout, none, qn[:0], np.zeros((0, 5)), q=[0, 1, 2]) == []

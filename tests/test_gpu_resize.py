@@ -9,46 +9,18 @@ import pytest
 
 import _resize_ref as R
 import jpeg_amd as J
+from _calls import (RESIZE_CONTENTS as CONTENTS, RESIZE_EXTENTS as EXTENTS, RESIZE_FACTORS as FACTORS, RESIZE_SIZE as SIZE,
+                    RESIZE_TILE_H as TILE_H, RESIZE_TILE_W as TILE_W, RESIZE_VIEWS as VIEWS, SENTINEL, Out, c_layout, pixel_image,
+                    resize_py_layout, resized_call, synthetic)
+from _calls import ctx, torch  # noqa: F401  (the fixtures)
 from jpeg_amd import _lib
-from jpeg_amd.synth import natural_planes_torch
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-TILE_W, TILE_H = 64, 32                                     # k_resize_bilinear's tile of output pixels
 RUN = 4                                                     # output pixels per work-item: 12 bytes, three dwords
-EXTENTS = [(1, 1), (2, 3), (7, 9), (131, 57), (449, 301)]   # (w, h) of the sources of one call
 # (out_w, out_h, bytes between the output images beyond 3 out_w out_h).  (13, 5): 39-byte rows at an odd stride -- runs that
 # start at every alignment, and a last run of one pixel; (TILE_W + 6, 2 * TILE_H + 3): two tiles across, three down
 TARGETS = [(1, 1, 0), (5, 3, 4), (224, 224, 0), (13, 5, 2), (TILE_W + 6, 2 * TILE_H + 3, 1)]
-CONTENTS = ["random", "checker", "zero", "full"]
-
-FACTORS = {"y8": [(1, 1)], "420": [(2, 2), (1, 1), (1, 1)], "420-cosited": [(2, 2), (1, 1), (1, 1)]}
-SIZE = (131, 257)
-# denominators 1, 2, 4, 8 in one call; the scaled images are 131 x 257, 66 x 129, 33 x 65, 17 x 33
-VIEWS = [(2, 3, 5, 60, 100), (1, 10, 20, 100, 200), (8, 0, 0, 17, 33), (4, 1, 1, 30, 60), (2, 65, 128, 1, 1)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    return J.Context(0)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
-
-
-def _image(content, w, h, seed):
-    if content == "random":
-        return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
-    if content == "checker":                                # 0 / 255 per sample: both ends of the clamp and of the rounding
-        yy, xx, cc = np.mgrid[0:h, 0:w, 0:3]
-        return (((xx + yy + cc) & 1) * 255).astype(np.uint8)
-    return np.full((h, w, 3), 0 if content == "zero" else 255, np.uint8)
-
-
 def _resize_call(ctx, torch, images, out_w, out_h, gap=0, src_gap=0, expect=0):
     """jpeg_amd_resize_batch on host images [h, w, 3] -> the outputs as host arrays; the sentinel in every byte of the output
     buffer that belongs to no image is asserted here."""
@@ -58,23 +30,14 @@ def _resize_call(ctx, torch, images, out_w, out_h, gap=0, src_gap=0, expect=0):
     for i, im in enumerate(images):
         src[i * src_stride:i * src_stride + im.size] = im.reshape(-1)
     d_src = torch.from_numpy(src).to(ctx.torch_device)
-    area = 3 * max(out_w, 0) * max(out_h, 0)
-    stride = max(area + gap, 0)
-    out = torch.full((n * stride + 7,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
+    out = Out(ctx, torch, [3 * max(out_w, 0) * max(out_h, 0)] * n, gap=gap, tail=7)
     ext = (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
-    assert _lib.lib().jpeg_amd_resize_batch(ctx.handle, n, d_src.data_ptr(), src_stride, ext, out_w, out_h, out.data_ptr(),
-                                            stride) == expect
-    host = out.cpu().numpy()
+    assert _lib.lib().jpeg_amd_resize_batch(ctx.handle, n, d_src.data_ptr(), src_stride, ext, out_w, out_h, out.ptr,
+                                            out.stride) == expect
     if expect != 0:
-        assert (host == SENTINEL).all()
+        assert out.untouched()
         return None
-    assert (host[n * stride:] == SENTINEL).all()
-    got = []
-    for i in range(n):
-        row = host[i * stride:(i + 1) * stride]
-        assert (row[area:] == SENTINEL).all(), i
-        got.append(row[:area].reshape(out_h, out_w, 3))
-    return got
+    return [g.reshape(out_h, out_w, 3) for g in out.images()]
 
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------------
@@ -85,7 +48,7 @@ def test_kernel_matches_the_contract(ctx, torch, content, target):
     out_w, out_h, gap = target
     assert (out_w, out_h) != (TILE_W + 6, 2 * TILE_H + 3) or (out_w > TILE_W and out_h > 2 * TILE_H)
     assert (out_w, out_h) != (13, 5) or ((3 * out_w) % 4 != 0 and (3 * out_w * out_h + gap) % 2 == 1 and out_w % RUN == 1)
-    images = [_image(content, w, h, 100 * w + h) for w, h in EXTENTS]
+    images = [pixel_image(content, w, h, 100 * w + h) for w, h in EXTENTS]
     got = _resize_call(ctx, torch, images, out_w, out_h, gap=gap, src_gap=3)
     for (w, h), image, g in zip(EXTENTS, images, got):
         assert (g == R.resize(image, out_w, out_h)).all(), (content, (w, h), target)
@@ -93,13 +56,13 @@ def test_kernel_matches_the_contract(ctx, torch, content, target):
 
 def test_identity_size_returns_the_source_bytes(ctx, torch):
     for w, h in EXTENTS + [(TILE_W + 1, TILE_H + 1)]:
-        image = _image("random", w, h, w + h)
+        image = pixel_image("random", w, h, w + h)
         got = _resize_call(ctx, torch, [image, image[::-1].copy()], w, h, gap=1)
         assert (got[0] == image).all() and (got[1] == image[::-1]).all(), (w, h)
 
 
 def test_upscaling_and_a_source_far_larger_than_the_target(ctx, torch):
-    images = [_image("random", 3, 2, 1), _image("random", 1000, 40, 2)]
+    images = [pixel_image("random", 3, 2, 1), pixel_image("random", 1000, 40, 2)]
     for out_w, out_h in [(97, 33), (4, 3)]:
         got = _resize_call(ctx, torch, images, out_w, out_h)
         for image, g in zip(images, got):
@@ -108,78 +71,34 @@ def test_upscaling_and_a_source_far_larger_than_the_target(ctx, torch):
 
 # ---- 2. decode + resample -------------------------------------------------------------------------------------------------------
 
-def _layout(w, h, factors, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = max(f[0] for f in factors), max(f[1] for f in factors)
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
-
-
-def _py_layout(name):
-    if name == "y8":
-        return J.Layout("y8", {1: J.Component((1, 1), 0)})
-    return J.Layout("ycc8", {1: J.Component((2, 2), 0), 2: J.Component((1, 1), 1), 3: J.Component((1, 1), 1)})
-
-
-def _synthetic(ctx, torch, L, n, seed):
-    units = [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
-    planes = natural_planes_torch(units, n, ctx.torch_device, seed=seed)
-    ntables = 2 if L.nplanes == 3 else 1
-    gen = torch.Generator(device=ctx.torch_device).manual_seed(seed + 1)
-    dq = torch.randint(1, 24, (n, ntables, 64), dtype=torch.int16, device=ctx.torch_device, generator=gen)
-    return planes, dq, ntables
-
-
-def _c_views(views):
-    arr = (_lib.View * max(len(views), 1))()
-    for i, v in enumerate(views):
-        arr[i] = _lib.View(v[0], _lib.Region(*v[1:]))
-    return arr
-
-
-def _resized_call(ctx, L, planes, dq, ntables, cosited, color, views, out_w, out_h, out_ptr, stride, layout=None):
-    strides = [64 * L.units_x[p] * L.units_y[p] for p in range(L.nplanes)] + [0] * (4 - L.nplanes)
-    return _lib.lib().jpeg_amd_decode_resized_batch(
-        ctx.handle, C.byref(layout or L), len(views), _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(strides),
-        dq.data_ptr(), ntables * 64, ntables, cosited, color, _c_views(views), out_w, out_h, out_ptr, stride)
-
-
-def _check_images(host, n, out_w, out_h, stride, want, what):
-    area = 3 * out_w * out_h
-    assert (host[n * stride:] == SENTINEL).all(), what
-    for i in range(n):
-        row = host[i * stride:(i + 1) * stride]
-        assert (row[area:] == SENTINEL).all(), (what, i)
-        assert (row[:area].reshape(out_h, out_w, 3) == want[i]).all(), (what, i)
+def _check_images(out, out_w, out_h, want, what):
+    """The first len(want) images of `out` are `want`; the sentinel in every byte that belongs to no image of `out`."""
+    for got, w, i in zip(out.images(), want, range(len(want))):
+        assert (got.reshape(out_h, out_w, 3) == w).all(), (what, i)
 
 
 @pytest.mark.parametrize("name", sorted(FACTORS))
 def test_decode_resized_is_the_view_decode_resampled(ctx, torch, name):
-    L = _layout(SIZE[0], SIZE[1], FACTORS[name])
+    L = c_layout(SIZE[0], SIZE[1], FACTORS[name])
     cosited = 1 if name.endswith("cosited") else 0
     n = len(VIEWS)
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 17)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 17)
     assert sorted({v[0] for v in VIEWS}) == [1, 2, 4, 8]
     for color in (J.RGB, J.YCbCr):
-        decoded = [v.cpu().numpy() for v in J.decode_views(ctx, SIZE, _py_layout(name), planes, dq, VIEWS, color=color,
+        decoded = [v.cpu().numpy() for v in J.decode_views(ctx, SIZE, resize_py_layout(name), planes, dq, VIEWS, color=color,
                                                           cosite=bool(cosited))]
         for out_w, out_h, gap in [(32, 32, 0), (7, 5, 3)]:
             want = [R.resize(d, out_w, out_h) for d in decoded]
-            stride = 3 * out_w * out_h + gap
-            out = torch.full((n * stride + 5,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
-            assert _resized_call(ctx, L, planes, dq, ntables, cosited, color.code, VIEWS, out_w, out_h, out.data_ptr(), stride) == 0
-            _check_images(out.cpu().numpy(), n, out_w, out_h, stride, want, (name, color.__name__, out_w, out_h))
+            out = Out(ctx, torch, [3 * out_w * out_h] * n, gap=gap, tail=5)
+            assert resized_call(ctx, L, planes, dq, ntables, cosited, color.code, VIEWS, out_w, out_h, out.ptr, out.stride) == 0
+            _check_images(out, out_w, out_h, want, (name, color.__name__, out_w, out_h))
 
 
 def test_decode_crops_resized_picks_the_views_and_decodes_them(ctx, torch):
-    L = _layout(SIZE[0], SIZE[1], FACTORS["420"])
-    layout = _py_layout("420")
+    L = c_layout(SIZE[0], SIZE[1], FACTORS["420"])
+    layout = resize_py_layout("420")
     source = [(0, 0, 131, 257), (10, 7, 100, 200), (90, 30, 41, 35), (3, 100, 70, 150), (64, 128, 9, 6)]
-    planes, dq, _ = _synthetic(ctx, torch, L, len(source), 23)
+    planes, dq, _ = synthetic(ctx, torch, L, len(source), 23)
     out_size = (16, 20)
     got, views = J.decode_crops_resized(ctx, SIZE, layout, planes, dq, source, out_size, color=J.YCbCr)
     want_views = [(J.view_denom(s[2:], out_size),) for s in source]
@@ -202,31 +121,28 @@ def test_two_calls_queued_back_to_back_on_a_fresh_context(torch, name):
     first call's kernels may still be running from them; the view call in between regrows the scratch and restages its
     rectangles.  Both results must be the contract's."""
     ctx = J.Context(0)
-    L = _layout(SIZE[0], SIZE[1], FACTORS[name])
+    L = c_layout(SIZE[0], SIZE[1], FACTORS[name])
     cosited = 1 if name.endswith("cosited") else 0
     small = [(4, 1, 1, 9, 7), (8, 0, 0, 5, 5)]
     large = [(1, 0, 0, 131, 257), (2, 1, 1, 64, 120), (1, 3, 3, 120, 250)] + [(2, 0, 0, 66, 129)] * 253
     n = len(large)
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 5)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 5)
     out_w, out_h = 24, 40
-    stride = 3 * out_w * out_h
-    outs = [torch.full((len(v) * stride + 5,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device) for v in (small, large)]
-    decoded = [[d.cpu().numpy() for d in J.decode_views(ctx, SIZE, _py_layout(name), [p[:len(v)] for p in planes], dq[:len(v)], v,
+    outs = [Out(ctx, torch, [3 * out_w * out_h] * len(v), tail=5) for v in (small, large)]
+    decoded = [[d.cpu().numpy() for d in J.decode_views(ctx, SIZE, resize_py_layout(name), [p[:len(v)] for p in planes], dq[:len(v)], v,
                                                         cosite=bool(cosited))] for v in (small[:2], large[:4])]
     ctx.close()
     ctx = J.Context(0)                                      # nothing allocated yet: both calls grow the buffers
     for views, out in zip((small, large), outs):
-        assert _resized_call(ctx, L, planes, dq, ntables, cosited, _lib.COLOR_RGB8, views, out_w, out_h, out.data_ptr(), stride) == 0
-    hosts = [o.cpu().numpy() for o in outs]
-    _check_images(hosts[0], 2, out_w, out_h, stride, [R.resize(d, out_w, out_h) for d in decoded[0]], (name, "first"))
+        assert resized_call(ctx, L, planes, dq, ntables, cosited, _lib.COLOR_RGB8, views, out_w, out_h, out.ptr, out.stride) == 0
+    _check_images(outs[0], out_w, out_h, [R.resize(d, out_w, out_h) for d in decoded[0]], (name, "first"))
     want = [R.resize(d, out_w, out_h) for d in decoded[1]]
-    _check_images(hosts[1][:4 * stride], 4, out_w, out_h, stride, want, (name, "second"))
+    _check_images(outs[1], out_w, out_h, want, (name, "second"))      # the first 4 of n, and the sentinel behind the last
     # images 3 .. n - 1 of the second call have the same view of different images: checked against the view decode alone
-    rest = J.decode_views(ctx, SIZE, _py_layout(name), [p[250:] for p in planes], dq[250:], large[250:], cosite=bool(cosited))
-    tail = hosts[1][250 * stride:n * stride].reshape(n - 250, out_h, out_w, 3)
+    rest = J.decode_views(ctx, SIZE, resize_py_layout(name), [p[250:] for p in planes], dq[250:], large[250:], cosite=bool(cosited))
+    tail = outs[1].images()[250:]
     for i, d in enumerate(rest):
-        assert (tail[i] == R.resize(d.cpu().numpy(), out_w, out_h)).all(), (name, 250 + i)
-    assert (hosts[1][n * stride:] == SENTINEL).all()
+        assert (tail[i].reshape(out_h, out_w, 3) == R.resize(d.cpu().numpy(), out_w, out_h)).all(), (name, 250 + i)
     ctx.close()
 
 
@@ -235,7 +151,7 @@ def test_two_calls_queued_back_to_back_on_a_fresh_context(torch, name):
 def test_an_empty_batch_is_ok(ctx, torch):
     out = torch.full((64,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
     assert _lib.lib().jpeg_amd_resize_batch(ctx.handle, 0, None, 0, None, 4, 4, out.data_ptr(), 0) == 0
-    L = _layout(33, 17, FACTORS["420"])
+    L = c_layout(33, 17, FACTORS["420"])
     assert _lib.lib().jpeg_amd_decode_resized_batch(ctx.handle, C.byref(L), 0, None, None, None, 0, 2, 0, _lib.COLOR_RGB8, None,
                                                     4, 4, out.data_ptr(), 0) == 0
     ctx.synchronize()
@@ -244,7 +160,7 @@ def test_an_empty_batch_is_ok(ctx, torch):
 
 def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
     lib = _lib.lib()
-    images = [_image("random", 9, 7, 1), _image("random", 5, 11, 2)]
+    images = [pixel_image("random", 9, 7, 1), pixel_image("random", 5, 11, 2)]
     for kw in ({"out_w": 0}, {"out_h": 0}, {"out_w": -1}, {"gap": -1}, {"src_gap": -1}):
         args = {"out_w": 6, "out_h": 4, **kw}
         assert _resize_call(ctx, torch, images, expect=_lib.EINVAL, **args) is None
@@ -258,29 +174,29 @@ def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
     ctx.synchronize()
     assert (d == SENTINEL).all()
 
-    L = _layout(131, 65, FACTORS["420"])
+    L = c_layout(131, 65, FACTORS["420"])
     good = [(2, 3, 5, 20, 9), (4, 1, 1, 20, 9), (8, 0, 0, 17, 9), (1, 100, 40, 20, 9)]
     n = len(good)
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 3)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 3)
     out_w, out_h = 10, 6
-    stride = 3 * out_w * out_h
-    out = torch.full((n * stride,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
+    out = Out(ctx, torch, [3 * out_w * out_h] * n)
+    stride = out.stride
 
-    def call(views=good, layout=None, w=out_w, h=out_h, ptr=out.data_ptr(), s=stride):
-        return _resized_call(ctx, L, planes, dq, ntables, 0, _lib.COLOR_RGB8, views, w, h, ptr, s, layout=layout)
+    def call(views=good, layout=None, w=out_w, h=out_h, ptr=out.ptr, s=stride):
+        return resized_call(ctx, L, planes, dq, ntables, 0, _lib.COLOR_RGB8, views, w, h, ptr, s, layout=layout)
 
     for denom in (0, 3, 16):                                # what the view call refuses, in the LAST image of the batch
         assert call(views=good[:3] + [(denom, 0, 0, 17, 9)]) == _lib.EINVAL
     assert call(views=good[:3] + [(4, 33 - 20 + 1, 1, 20, 9)]) == _lib.EINVAL       # one pixel past W' = 33
-    assert call(layout=_layout(131, 65, FACTORS["420"], precision=12)) == _lib.ENOSUP
+    assert call(layout=c_layout(131, 65, FACTORS["420"], precision=12)) == _lib.ENOSUP
     assert call(w=0) == _lib.EINVAL and call(h=0) == _lib.EINVAL
     assert call(s=stride - 1) == _lib.EINVAL
     assert call(ptr=None) == _lib.EINVAL
     ctx.synchronize()
-    assert (out == SENTINEL).all()
+    assert out.untouched()
     assert call() == 0
-    decoded = J.decode_views(ctx, (131, 65), _py_layout("420"), planes, dq, good)
-    _check_images(out.cpu().numpy(), n, out_w, out_h, stride, [R.resize(v.cpu().numpy(), out_w, out_h) for v in decoded], "valid")
+    decoded = J.decode_views(ctx, (131, 65), resize_py_layout("420"), planes, dq, good)
+    _check_images(out, out_w, out_h, [R.resize(v.cpu().numpy(), out_w, out_h) for v in decoded], "valid")
     got = _resize_call(ctx, torch, images, 6, 4)
     assert all((g == R.resize(im, 6, 4)).all() for g, im in zip(got, images))
 
@@ -288,9 +204,9 @@ def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
 # ---- 4. the Python API ------------------------------------------------------------------------------------------------------------
 
 def test_python_api(ctx, torch):
-    L = _layout(SIZE[0], SIZE[1], FACTORS["420"])
-    layout = _py_layout("420")
-    planes, dq, _ = _synthetic(ctx, torch, L, 2, 11)
+    L = c_layout(SIZE[0], SIZE[1], FACTORS["420"])
+    layout = resize_py_layout("420")
+    planes, dq, _ = synthetic(ctx, torch, L, 2, 11)
     qh = dq.cpu().numpy().astype(np.uint16)
     sp = J.Spectral(ctx, SIZE, layout, [p[1] for p in planes], [qh[1, 0], qh[1, 1]], [0, 1, 1])
     view = (2, 3, 5, 60, 100)
@@ -302,7 +218,7 @@ def test_python_api(ctx, torch):
         assert tuple(one.shape) == (20, 32, 3)
         assert (one.cpu().numpy() == R.resize(plain.cpu().numpy(), 32, 20)).all()
         assert cosite or (one.cpu().numpy() == batch[1]).all()
-    images = [torch.from_numpy(_image("random", w, h, w)).to(ctx.torch_device) for w, h in EXTENTS]
+    images = [torch.from_numpy(pixel_image("random", w, h, w)).to(ctx.torch_device) for w, h in EXTENTS]
     got = J.resize(ctx, images, (31, 9))
     assert tuple(got.shape) == (len(EXTENTS), 9, 31, 3) and got.dtype == torch.uint8
     for g, im in zip(got.cpu().numpy(), images):

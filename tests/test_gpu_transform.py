@@ -12,23 +12,19 @@ import pytest
 
 import _transform_ref as R
 import jpeg_amd as J
+from _calls import ctx  # noqa: F401  (the fixture)
+from _golden import GOLDEN
 from jpeg_amd import _lib
 from jpeg_amd.api import _metadata_array, _scan_array, Scan
 from test_entropy_encode_cpu import _script, _sorted_dht
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SOURCE = R.xpath("karlie-kwk-wwdc-2017.jpg")
 ROTATED = {"ii": 5, "iii": 6, "iv": 3}
 CASES = (sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg"))) +
          [os.path.join(GOLDEN, "encode", f) for f in ("karlie-milan-sp12-2011-4-2-2-1.0.jpg",
                                                       "karlie-milan-sp12-2011-4-4-0-1.0.jpg", "custom-color-output.jpg")])
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    return J.Context(0)
 
 
 def _bytes(path):

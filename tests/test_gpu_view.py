@@ -9,19 +9,16 @@ import pytest
 
 import _scaled_ref as S
 import jpeg_amd as J
+from _calls import COLORS, FUSED, SENTINEL, Out, c_layout, c_regions, c_views, plane_ptrs, strides, synthetic
+from _calls import ctx, torch  # noqa: F401  (the fixtures)
 from jpeg_amd import _lib
-from jpeg_amd.synth import natural_planes_torch
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-COLORS = (_lib.COLOR_RGB8, _lib.COLOR_YCC8)
 DENOMS = (1, 2, 4, 8)
 TILE_W, TILE_H = 128, 32
 
-FUSED = {"y8": [(1, 1)], "444": [(1, 1)] * 3, "420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)],
-         "440": [(1, 2), (1, 1), (1, 1)]}
 # name -> (factors, cosited)
 LAYOUTS = {**{k: (v, 0) for k, v in FUSED.items()}, "411": ([(4, 1), (1, 1), (1, 1)], 0),
            "420-cosited": ([(2, 2), (1, 1), (1, 1)], 1)}
@@ -29,74 +26,19 @@ LAYOUTS = {**{k: (v, 0) for k, v in FUSED.items()}, "411": ([(4, 1), (1, 1), (1,
 SIZES = [(1, 1), (7, 9), (17, 33), (131, 257), (1100, 300)]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    return J.Context(0)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    return torch
-
-
-def _layout(w, h, factors, scale=None, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
-
-
-def _units(L):
-    return [(L.units_x[p], L.units_y[p]) for p in range(L.nplanes)]
-
-
-def _strides(L, distinct=True):
-    return [64 * ux * uy if distinct else 0 for ux, uy in _units(L)] + [0] * (4 - L.nplanes)
-
-
-def _synthetic(ctx, torch, L, n, seed):
-    planes = natural_planes_torch(_units(L), n, ctx.torch_device, seed=seed)
-    ntables = 2 if L.nplanes == 3 else 1
-    gen = torch.Generator(device=ctx.torch_device).manual_seed(seed + 1)
-    dq = torch.randint(1, 24, (n, ntables, 64), dtype=torch.int16, device=ctx.torch_device, generator=gen)
-    return planes, dq, ntables
-
-
-def _c_views(views):
-    arr = (_lib.View * max(len(views), 1))()
-    for i, (denom, region) in enumerate(views):
-        arr[i] = _lib.View(denom, _lib.Region(*region))
-    return arr
-
-
-def _call(ctx, L, n, planes, coef_stride, dq, q_stride, ntables, cosited, color, c_views, out_ptr, stride):
+def _call(ctx, L, n, planes, coef_stride, dq, q_stride, ntables, cosited, color, h_views, out_ptr, stride):
     return _lib.lib().jpeg_amd_decode_view_batch(
-        ctx.handle, C.byref(L), n, _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(coef_stride),
-        dq.data_ptr(), q_stride, ntables, cosited, color, c_views, out_ptr, stride)
+        ctx.handle, C.byref(L), n, plane_ptrs(planes), _lib.size_array(coef_stride),
+        dq.data_ptr(), q_stride, ntables, cosited, color, h_views, out_ptr, stride)
 
 
 def _view_batch(ctx, torch, L, planes, dq, ntables, cosited, color, views, gap=0, distinct=True):
     """One call for `views`, image i from image i of planes / dq (distinct) or every image from image 0.  -> the images as
     host arrays [h_i, w_i, 3]; the sentinel in every byte of the buffer that belongs to no image is asserted here."""
-    n = len(views)
-    areas = [3 * r[2] * r[3] for _, r in views]
-    stride = max(areas) + gap
-    out = torch.full((n * stride + gap,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
-    assert _call(ctx, L, n, planes, _strides(L, distinct), dq, ntables * 64 if distinct else 0, ntables, cosited, color,
-                 _c_views(views), out.data_ptr(), stride) == 0
-    host = out.cpu().numpy()
-    assert (host[n * stride:] == SENTINEL).all()
-    images = []
-    for i, (_, r) in enumerate(views):
-        row = host[i * stride:(i + 1) * stride]
-        assert (row[areas[i]:] == SENTINEL).all(), (i, views[i])
-        images.append(row[:areas[i]].reshape(r[3], r[2], 3))
-    return images
+    out = Out(ctx, torch, [3 * r[2] * r[3] for _, r in views], gap=gap, tail=gap)
+    assert _call(ctx, L, len(views), planes, strides(L, distinct), dq, ntables * 64 if distinct else 0, ntables, cosited, color,
+                 c_views(views), out.ptr, out.stride) == 0
+    return [image.reshape(r[3], r[2], 3) for image, (_, r) in zip(out.images(), views)]
 
 
 def _reference(L, planes_host, quanta_host, i, denom, cosited):
@@ -142,8 +84,8 @@ def _regions(rng, W, H, N):
 @pytest.mark.parametrize("name", sorted(LAYOUTS))
 def test_views_match_the_reference(ctx, torch, name, size):
     factors, cosited = LAYOUTS[name]
-    L = _layout(size[0], size[1], factors)
-    planes, dq, ntables = _synthetic(ctx, torch, L, 1, size[0] * 31 + size[1])
+    L = c_layout(size[0], size[1], factors)
+    planes, dq, ntables = synthetic(ctx, torch, L, 1, size[0] * 31 + size[1])
     ph = [p.cpu().numpy() for p in planes]
     qh = dq.cpu().numpy().astype(np.uint16)
     rng = np.random.default_rng(size[0] + 1000 * size[1])
@@ -166,9 +108,9 @@ def test_views_match_the_reference(ctx, torch, name, size):
 # ---- 2. mixed denominators --------------------------------------------------------------------------------------------------
 
 def test_a_batch_of_64_with_mixed_denominators(ctx, torch):
-    L = _layout(403, 150, FUSED["420"])
+    L = c_layout(403, 150, FUSED["420"])
     n, gap = 64, 5
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 64)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 64)
     ph = [p.cpu().numpy() for p in planes]
     qh = np.ascontiguousarray(dq.cpu().numpy().astype(np.uint16))
     rng = np.random.default_rng(64)
@@ -182,7 +124,7 @@ def test_a_batch_of_64_with_mixed_denominators(ctx, torch):
         assert (image == want).all(), (i, denom, r)
         one = torch.full((image.size + 8,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
         view = _lib.View(denom, _lib.Region(*r))
-        assert _lib.lib().jpeg_amd_decode_view(ctx.handle, C.byref(L), _lib.ptr_array([p[i].data_ptr() for p in planes]),
+        assert _lib.lib().jpeg_amd_decode_view(ctx.handle, C.byref(L), plane_ptrs([p[i] for p in planes]),
                                                qh[i].ctypes.data, ntables, 0, _lib.COLOR_RGB8, C.byref(view), one.data_ptr()) == 0
         one = one.cpu().numpy()
         assert (one[:image.size] == image.reshape(-1)).all() and (one[image.size:] == SENTINEL).all(), (i, denom, r)
@@ -194,10 +136,10 @@ def test_a_batch_of_64_with_mixed_denominators(ctx, torch):
 def test_views_equal_the_existing_calls(ctx, torch, name):
     factors, cosited = LAYOUTS[name]
     size = (131, 65)
-    L = _layout(size[0], size[1], factors)
+    L = c_layout(size[0], size[1], factors)
     n = 5
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 33)
-    ptrs, strides = _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(_strides(L))
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 33)
+    ptrs, coef_strides = plane_ptrs(planes), _lib.size_array(strides(L))
     rng = np.random.default_rng(33)
     lib = _lib.lib()
     for color in COLORS:
@@ -206,7 +148,7 @@ def test_views_equal_the_existing_calls(ctx, torch, name):
             w, h = S.scaled_size(size, denom)
             got = _view_batch(ctx, torch, L, planes, dq, ntables, cosited, color, [(denom, (0, 0, w, h))] * n)
             scaled = torch.empty((n, h, w, 3), dtype=torch.uint8, device=ctx.torch_device)
-            assert lib.jpeg_amd_decode_scaled_batch(ctx.handle, C.byref(L), n, ptrs, strides, dq.data_ptr(), ntables * 64, ntables,
+            assert lib.jpeg_amd_decode_scaled_batch(ctx.handle, C.byref(L), n, ptrs, coef_strides, dq.data_ptr(), ntables * 64, ntables,
                                                     cosited, color, denom, scaled.data_ptr(), 3 * w * h) == 0
             scaled = scaled.cpu().numpy()
             assert all((got[i] == scaled[i]).all() for i in range(n)), (name, color, denom)
@@ -215,9 +157,8 @@ def test_views_equal_the_existing_calls(ctx, torch, name):
         regions = [_random_region(rng, size[0], size[1]) for _ in range(n)]
         stride = max(3 * r[2] * r[3] for r in regions)
         out = torch.empty((n * stride,), dtype=torch.uint8, device=ctx.torch_device)
-        h_regions = (_lib.Region * n)(*[_lib.Region(*r) for r in regions])
-        assert lib.jpeg_amd_decode_region_batch(ctx.handle, C.byref(L), n, ptrs, strides, dq.data_ptr(), ntables * 64, ntables,
-                                                cosited, color, h_regions, out.data_ptr(), stride) == 0
+        assert lib.jpeg_amd_decode_region_batch(ctx.handle, C.byref(L), n, ptrs, coef_strides, dq.data_ptr(), ntables * 64, ntables,
+                                                cosited, color, c_regions(regions), out.data_ptr(), stride) == 0
         out = out.cpu().numpy()
         want = [out[i * stride:i * stride + 3 * r[2] * r[3]].reshape(r[3], r[2], 3) for i, r in enumerate(regions)]
         alone = _view_batch(ctx, torch, L, planes, dq, ntables, cosited, color, [(1, r) for r in regions])
@@ -233,8 +174,8 @@ def test_the_two_full_size_kernels_agree_across_their_tile_seams(ctx, torch, nam
     """k_region_decode (128 x 64 tiles) and k_view_decode<8> (128 x 32) run one tile body.  The rectangle's tile grid is
     anchored at (8, 8): it crosses x = 136 and 264, and y = 40, 72 and 104 of the view kernel, y = 72 of the region kernel."""
     size, r = (300, 150), (13, 11, 270, 120)
-    L = _layout(size[0], size[1], FUSED[name])
-    planes, dq, ntables = _synthetic(ctx, torch, L, 2, 77)
+    L = c_layout(size[0], size[1], FUSED[name])
+    planes, dq, ntables = synthetic(ctx, torch, L, 2, 77)
     ph = [p.cpu().numpy() for p in planes]
     qh = dq.cpu().numpy().astype(np.uint16)
     want = _reference(L, ph, qh, 0, 1, 0)
@@ -242,7 +183,7 @@ def test_the_two_full_size_kernels_agree_across_their_tile_seams(ctx, torch, nam
     for color in COLORS:
         out = torch.full((area + 16,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
         assert _lib.lib().jpeg_amd_decode_region_batch(
-            ctx.handle, C.byref(L), 1, _lib.ptr_array([p.data_ptr() for p in planes]), _lib.size_array(_strides(L)), dq.data_ptr(),
+            ctx.handle, C.byref(L), 1, plane_ptrs(planes), _lib.size_array(strides(L)), dq.data_ptr(),
             ntables * 64, ntables, 0, color, (_lib.Region * 1)(_lib.Region(*r)), out.data_ptr(), area) == 0
         out = out.cpu().numpy()
         assert (out[area:] == SENTINEL).all()
@@ -261,9 +202,9 @@ def test_unread_coefficients_do_not_matter(ctx, torch, name, denom):
     """Every coefficient with k >= N or h >= N (at denominator 4 that holds every k >= 4 or h >= 4), and every block outside
     jpeg_amd_view_window, randomised: the same bytes."""
     N = 8 // denom
-    L = _layout(403, 150, FUSED[name])
+    L = c_layout(403, 150, FUSED[name])
     n = 3
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 99)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 99)
     rng = np.random.default_rng(denom)
     W1, H1 = S.scaled_size((403, 150), denom)
     views = [(denom, r) for r in ((37, 11, 60, 20), (W1 - 31, H1 - 9, 31, 9), _random_region(rng, W1, H1, 150, 60))]
@@ -291,7 +232,7 @@ def test_unread_coefficients_do_not_matter(ctx, torch, name, denom):
 # ---- 5. empty batch; invalid calls --------------------------------------------------------------------------------------------
 
 def test_an_empty_batch_is_ok(ctx, torch):
-    L = _layout(33, 17, FUSED["420"])
+    L = c_layout(33, 17, FUSED["420"])
     out = torch.full((64,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
     assert _lib.lib().jpeg_amd_decode_view_batch(ctx.handle, C.byref(L), 0, None, None, None, 0, 2, 0, _lib.COLOR_RGB8, None,
                                                  out.data_ptr(), 0) == 0
@@ -300,21 +241,21 @@ def test_an_empty_batch_is_ok(ctx, torch):
 
 
 def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
-    L = _layout(131, 65, FUSED["420"])
+    L = c_layout(131, 65, FUSED["420"])
     n = 4
-    planes, dq, ntables = _synthetic(ctx, torch, L, n, 3)
+    planes, dq, ntables = synthetic(ctx, torch, L, n, 3)
     good = [(2, (3, 5, 20, 9)), (4, (1, 1, 20, 9)), (8, (0, 0, 17, 9)), (1, (100, 40, 20, 9))]
     stride = 3 * 20 * 9
     out = torch.full((n * stride,), SENTINEL, dtype=torch.uint8, device=ctx.torch_device)
 
     def call(views=good, layout=L, ptr=out.data_ptr(), s=stride):
-        return _call(ctx, layout, n, planes, _strides(L), dq, ntables * 64, ntables, 0, _lib.COLOR_RGB8, _c_views(views), ptr, s)
+        return _call(ctx, layout, n, planes, strides(L), dq, ntables * 64, ntables, 0, _lib.COLOR_RGB8, c_views(views), ptr, s)
 
     for denom in (0, 3, 16, -1):                           # a bad denominator in the middle of the batch
         assert call(views=good[:2] + [(denom, (0, 0, 17, 9))] + good[3:]) == _lib.EINVAL
     assert call(views=good[:1] + [(4, (33 - 20 + 1, 1, 20, 9))] + good[2:]) == _lib.EINVAL   # one pixel past W' = 33
     assert call(views=good[:2] + [(8, (0, 0, 17, 10))] + good[3:]) == _lib.EINVAL            # one pixel past H' = 9
-    assert call(layout=_layout(131, 65, FUSED["420"], precision=12)) == _lib.ENOSUP
+    assert call(layout=c_layout(131, 65, FUSED["420"], precision=12)) == _lib.ENOSUP
     assert call(s=stride - 1) == _lib.EINVAL
     assert call(ptr=None) == _lib.EINVAL
     ctx.synchronize()
@@ -333,8 +274,8 @@ def test_invalid_calls_write_nothing_and_leave_the_context_usable(ctx, torch):
 def test_python_api(ctx, torch):
     layout = J.Layout("ycc8", {1: J.Component((2, 2), 0), 2: J.Component((1, 1), 1), 3: J.Component((1, 1), 1)})
     size = (131, 65)
-    L = _layout(size[0], size[1], FUSED["420"])
-    planes, dq, ntables = _synthetic(ctx, torch, L, 3, 11)
+    L = c_layout(size[0], size[1], FUSED["420"])
+    planes, dq, ntables = synthetic(ctx, torch, L, 3, 11)
     ph = [p.cpu().numpy() for p in planes]
     qh = dq.cpu().numpy().astype(np.uint16)
     source = [(10, 7, 100, 50), (90, 30, 41, 35), (0, 0, 131, 65)]

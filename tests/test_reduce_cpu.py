@@ -9,23 +9,13 @@ import pytest
 
 import _reduce_ref as R
 import _scaled_ref as S
+from _calls import c_layout, plane_factors, plane_units
+from _golden import GOLDEN
 from jpeg_amd import _lib
 from oracle import oracle as O
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
 DENOMS = (2, 4, 8)
-
-
-def _layout(w, h, factors, scale=None, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
 
 
 def _reduced(L, denom):
@@ -40,7 +30,7 @@ def _scaled(L, denom):
 
 
 def _check(L):
-    factors = [(L.factor_x[p], L.factor_y[p]) for p in range(L.nplanes)]
+    factors = plane_factors(L)
     for denom in DENOMS:
         st, out = _reduced(L, denom)
         assert st == 0
@@ -49,10 +39,10 @@ def _check(L):
         assert (out.precision, out.nplanes, out.scale_x, out.scale_y) == (L.precision, L.nplanes, L.scale_x, L.scale_y)
         for p in range(_lib.MAX_PLANES):
             assert (out.factor_x[p], out.factor_y[p], out.qi[p]) == (L.factor_x[p], L.factor_y[p], L.qi[p])
-        assert [(out.units_x[p], out.units_y[p]) for p in range(L.nplanes)] == units
+        assert plane_units(out) == units
         # what a reader of the output file derives from its header
-        again = _layout(out.width, out.height, factors, (L.scale_x, L.scale_y), L.precision)
-        assert [(again.units_x[p], again.units_y[p]) for p in range(L.nplanes)] == units
+        again = c_layout(out.width, out.height, factors, (L.scale_x, L.scale_y), L.precision)
+        assert plane_units(again) == units
         # against jpeg_amd_scaled_layout: equal where every factor divides the scale, never smaller, at most one larger
         sc = _scaled(L, denom)
         for p in range(L.nplanes):
@@ -82,7 +72,7 @@ def test_reduce_layout_of_every_fixture_layout():
     assert len(layouts) >= 3
     for factors, scale, precision in layouts:
         for w, h in ((1, 1), (7, 9), (8, 16), (17, 33), (131, 257), (1920, 1080)):
-            _check(_layout(w, h, list(factors), scale, precision))
+            _check(c_layout(w, h, list(factors), scale, precision))
 
 
 def test_reduce_layout_of_2000_random_sizes_and_layouts():
@@ -93,13 +83,13 @@ def test_reduce_layout_of_2000_random_sizes_and_layouts():
         factors = [(int(rng.integers(1, sx + 1)), int(rng.integers(1, sy + 1))) for _ in range(n)]
         factors[0] = (sx, sy)
         w, h = int(rng.integers(1, 700)), int(rng.integers(1, 700))
-        _check(_layout(w, h, factors, (sx, sy), int(rng.integers(1, 17))))
+        _check(c_layout(w, h, factors, (sx, sy), int(rng.integers(1, 17))))
 
 
 @pytest.mark.parametrize("width", [21, 41, 85])
 def test_a_factor_that_does_not_divide_the_scale_can_take_one_more_unit(width):
     """3 in 4: the units recomputed from (W', H') exceed jpeg_amd_scaled_layout's ceil(N units / 8) at some denominator."""
-    L = _layout(width, 16, [(4, 1), (3, 1), (1, 1)])
+    L = c_layout(width, 16, [(4, 1), (3, 1), (1, 1)])
     _check(L)
     larger = []
     for denom in DENOMS:
@@ -114,7 +104,7 @@ def test_a_factor_that_does_not_divide_the_scale_can_take_one_more_unit(width):
 
 
 def test_reduce_layout_refuses_other_denominators_and_bad_layouts():
-    L = _layout(33, 17, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(33, 17, [(2, 2), (1, 1), (1, 1)])
     for denom in (1, 3, 16, 0, -2):
         out = _lib.Layout()
         out.width = 12345
@@ -122,7 +112,7 @@ def test_reduce_layout_refuses_other_denominators_and_bad_layouts():
         assert out.width == 12345
     assert _lib.lib().jpeg_amd_reduce_layout(C.byref(L), 2, None) == _lib.EINVAL
     assert _lib.lib().jpeg_amd_reduce_layout(None, 2, C.byref(_lib.Layout())) == _lib.EINVAL
-    bad = _layout(33, 17, [(2, 2), (1, 1), (1, 1)])
+    bad = c_layout(33, 17, [(2, 2), (1, 1), (1, 1)])
     bad.precision = 17
     assert _reduced(bad, 2)[0] == _lib.EINVAL
 

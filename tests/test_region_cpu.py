@@ -9,24 +9,11 @@ import numpy as np
 import pytest
 
 import jpeg_amd as J
+from _calls import c_layout
+from _golden import GOLDEN
 from jpeg_amd import _lib
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
-
-
-def _units(n, s):
-    return n // s + (1 if n % s else 0)
-
-
-def _layout(w, h, factors, scale=None):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, 8, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
 
 
 def _window(L, cosited, region):
@@ -113,7 +100,7 @@ def test_window_of_random_layouts():
             scale = (max(max(f[0] for f in factors), int(rng.integers(1, 5))),
                      max(max(f[1] for f in factors), int(rng.integers(1, 5))))
         W, H = int(rng.integers(1, 301)), int(rng.integers(1, 301))
-        L = _layout(W, H, factors, scale)
+        L = c_layout(W, H, factors, scale)
         _check_all(L, rng, 3)
 
 
@@ -122,7 +109,7 @@ def test_window_at_edges_of_sizes_off_the_mcu_grid():
     for W, H in ((17, 33), (31, 15), (47, 1), (1, 47), (161, 97)):
         for factors in ([(2, 2), (1, 1), (1, 1)], [(2, 1), (1, 1), (1, 1)], [(1, 2), (1, 1), (1, 1)], [(1, 1)] * 3,
                         [(4, 2), (1, 1), (2, 1)], [(1, 1)]):
-            L = _layout(W, H, factors)
+            L = c_layout(W, H, factors)
             for cosited in (0, 1):
                 for x in range(max(0, W - 18), W):
                     for y in (0, H - 1, max(0, H - 9)):
@@ -132,7 +119,7 @@ def test_window_at_edges_of_sizes_off_the_mcu_grid():
 
 
 def test_window_of_a_420_region_holds_the_chroma_halo():
-    L = _layout(1920, 1080, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(1920, 1080, [(2, 2), (1, 1), (1, 1)])
     st, w = _window(L, 0, (1237 % 1920, 901 % 1080, 64, 64))
     assert st == 0
     # luma: the blocks under the pixels; chroma: one sample beyond on each side of 32 x 32 samples
@@ -187,11 +174,11 @@ def test_planes_must_cover_the_image():
         if n == 3 and rng.random() < 0.2:
             scale = (max(max(f[0] for f in factors), int(rng.integers(1, 5))),
                      max(max(f[1] for f in factors), int(rng.integers(1, 5))))
-        layouts.append(_layout(int(rng.integers(1, 301)), int(rng.integers(1, 301)), factors, scale))
+        layouts.append(c_layout(int(rng.integers(1, 301)), int(rng.integers(1, 301)), factors, scale))
     for W, H in ((17, 33), (31, 15), (47, 1), (1, 47), (161, 97), (8, 8), (16, 16), (9, 9)):   # ... and of the edge test
         for factors in ([(2, 2), (1, 1), (1, 1)], [(2, 1), (1, 1), (1, 1)], [(1, 2), (1, 1), (1, 1)], [(1, 1)] * 3,
                         [(4, 2), (1, 1), (2, 1)], [(1, 1)]):
-            layouts.append(_layout(W, H, factors))
+            layouts.append(c_layout(W, H, factors))
     for L in layouts:
         accepted += _check_cover(L)
         total += 9 * L.nplanes
@@ -201,7 +188,7 @@ def test_planes_must_cover_the_image():
 def test_python_wrapper():
     layout = J.Layout("ycc8", {1: ((2, 2), 0), 2: ((1, 1), 1), 3: ((1, 1), 1)})
     got = J.region_window((100, 60), layout, (17, 9, 30, 20))
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     assert got == _brute(L, 0, (17, 9, 30, 20))[:3]
     assert J.region_window((100, 60), layout, (17, 9, 30, 20), cosite=True) == _brute(L, 1, (17, 9, 30, 20))[:3]
     with pytest.raises(J.JpegAmdError):
@@ -212,13 +199,13 @@ def test_python_wrapper():
                                     (97, 0, 4, 4), (0, 57, 4, 4), (0, 0, 101, 60), (0, 0, 100, 61),
                                     (5, 0, 2 ** 31 - 1, 4), (0, 5, 4, 2 ** 31 - 1), (2 ** 31 - 1, 0, 1, 1)])
 def test_window_rejects_regions_outside_the_image(region):
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     for cosited in (0, 1):
         assert _window(L, cosited, region)[0] == _lib.EINVAL
 
 
 def test_window_rejects_null_arguments():
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     r = _lib.Region(0, 0, 1, 1)
     w = (_lib.Region * _lib.MAX_PLANES)()
     lib = _lib.lib()
@@ -229,7 +216,7 @@ def test_window_rejects_null_arguments():
 
 def test_region_entry_points_check_their_arguments_before_the_device():
     """A NULL context is EINVAL before anything else (the device entry points need one; here there is no GPU)."""
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     r = _lib.Region(0, 0, 1, 1)
     lib = _lib.lib()
     assert lib.jpeg_amd_decode_region(None, C.byref(L), None, None, 2, 0, 1, C.byref(r), None) == _lib.EINVAL

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import _resize_ref as R
+from _calls import c_layout
 from jpeg_amd import _lib
 
 # (source w, h) -> (target w, h)
@@ -75,10 +76,7 @@ def test_refused_calls_do_not_touch_a_device():
     assert call() == _lib.EINVAL                                 # a valid call without a context: refused, not run
 
     # the decode form validates like the view call, the context last: a 12-bit layout is ENOSUP although there is no context
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes, L.scale_x, L.scale_y = 16, 16, 12, 1, 1, 1
-    L.factor_x[0] = L.factor_y[0] = 1
-    assert lib.jpeg_amd_layout_units(C.byref(L)) == 0
+    L = c_layout(16, 16, [(1, 1)], precision=12)
     view = _lib.View(1, _lib.Region(0, 0, 8, 8))
     args = (_lib.ptr_array([0x3000]), _lib.size_array([0]), C.c_void_p(0x4000), 0, 1, 0, _lib.COLOR_RGB8, C.byref(view))
     assert lib.jpeg_amd_decode_resized_batch(None, C.byref(L), 1, *args, 8, 8, dst, 0) == _lib.ENOSUP

@@ -10,22 +10,12 @@ import pytest
 
 import _scaled_ref as S
 import jpeg_amd as J
+from _calls import c_layout
+from _golden import GOLDEN
 from jpeg_amd import _lib
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
 DENOMS = (1, 2, 4, 8)
-
-
-def _layout(w, h, factors, scale=None, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
 
 
 def _scaled(L, denom):
@@ -93,7 +83,7 @@ def test_scaled_layout_of_every_fixture_layout_at_sizes_1_to_70():
     for factors, scale in layouts:
         for W in range(1, 71):
             for H in range(1, 71):
-                _check(_layout(W, H, list(factors), scale))
+                _check(c_layout(W, H, list(factors), scale))
 
 
 def test_scaled_layout_of_random_layouts():
@@ -105,18 +95,18 @@ def test_scaled_layout_of_random_layouts():
         if n == 3 and rng.random() < 0.2:   # a component the format does not recognise sets the scale
             scale = (max(max(f[0] for f in factors), int(rng.integers(1, 5))),
                      max(max(f[1] for f in factors), int(rng.integers(1, 5))))
-        _check(_layout(int(rng.integers(1, 5000)), int(rng.integers(1, 5000)), factors, scale))
+        _check(c_layout(int(rng.integers(1, 5000)), int(rng.integers(1, 5000)), factors, scale))
 
 
 def test_denom_1_is_the_same_layout():
-    L = _layout(319, 480, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(319, 480, [(2, 2), (1, 1), (1, 1)])
     st, out = _scaled(L, 1)
     assert st == 0 and bytes(out) == bytes(L)
 
 
 @pytest.mark.parametrize("denom", [0, 3, 16, -1])
 def test_other_denoms_are_einval(denom):
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     lib = _lib.lib()
     assert _scaled(L, denom)[0] == _lib.EINVAL
     with pytest.raises(ValueError):
@@ -128,7 +118,7 @@ def test_other_denoms_are_einval(denom):
 
 
 def test_scaled_layout_rejects_null_and_bad_layouts():
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     out = _lib.Layout()
     lib = _lib.lib()
     assert lib.jpeg_amd_scaled_layout(None, 2, C.byref(out)) == _lib.EINVAL
@@ -140,7 +130,7 @@ def test_scaled_layout_rejects_null_and_bad_layouts():
 def test_python_scaled_size():
     for size in ((1, 1), (7, 9), (319, 480), (1920, 1080)):
         for denom in DENOMS:
-            st, out = _scaled(_layout(size[0], size[1], [(1, 1)]), denom)
+            st, out = _scaled(c_layout(size[0], size[1], [(1, 1)]), denom)
             assert st == 0 and J.scaled_size(size, denom) == (out.width, out.height)
 
 

@@ -9,21 +9,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from _calls import c_layout
 from jpeg_amd import _lib
 
 EINVAL, ENOSUP = -1, -5                                            # JPEG_AMD_EINVAL, JPEG_AMD_ENOSUP, as literals
 CASES = ("valid", "null layout", "12-bit layout", "two planes", "n_images = -1", "bad denominator or empty region")
-
-
-def _layout(factors, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = 16, 16, precision, len(factors)
-    L.scale_x, L.scale_y = max(f[0] for f in factors), max(f[1] for f in factors)
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
 
 
 class Args:
@@ -32,7 +22,7 @@ class Args:
 
     def __init__(self, case):
         f420 = [(2, 2), (1, 1), (1, 1)]
-        self.layout = _layout(f420[:2] if case == "two planes" else f420, 12 if case == "12-bit layout" else 8)
+        self.layout = c_layout(16, 16, f420[:2] if case == "two planes" else f420, precision=12 if case == "12-bit layout" else 8)
         self.L = None if case == "null layout" else C.byref(self.layout)
         self.precision = self.layout.precision
         self.nplanes = self.layout.nplanes

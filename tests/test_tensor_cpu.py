@@ -8,6 +8,7 @@ import pytest
 
 import _tensor_ref as T
 import jpeg_amd as J
+from _calls import c_layout
 from jpeg_amd import _lib
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -152,10 +153,7 @@ def test_refused_calls_do_not_touch_a_device():
     assert call(src=None) == _lib.EINVAL and call(dst=None) == _lib.EINVAL and call(ext=None) == _lib.EINVAL
     assert call() == _lib.EINVAL                                                           # valid, but no context: refused, not run
 
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes, L.scale_x, L.scale_y = 16, 16, 12, 1, 1, 1
-    L.factor_x[0] = L.factor_y[0] = 1
-    assert lib.jpeg_amd_layout_units(C.byref(L)) == 0
+    L = c_layout(16, 16, [(1, 1)], precision=12)
     view = _lib.View(1, _lib.Region(0, 0, 8, 8))
     args = (_lib.ptr_array([0x3000]), _lib.size_array([0]), C.c_void_p(0x4000), 0, 1, 0, _lib.COLOR_RGB8, C.byref(view))
     assert lib.jpeg_amd_decode_tensor_batch(None, C.byref(L), 1, *args, 8, 8, C.byref(good), None, dst, 0) == _lib.ENOSUP

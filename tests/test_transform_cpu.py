@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 import _transform_ref as R
+from _golden import GOLDEN
 from jpeg_amd import _lib
 from test_entropy_encode_cpu import _script
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 JPEGS = sorted(glob.glob(os.path.join(GOLDEN, "**", "*.jpg"), recursive=True))
 
 

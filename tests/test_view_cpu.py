@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 
 import jpeg_amd as J
+from _calls import c_layout
+from _golden import GOLDEN
 from jpeg_amd import _lib
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
 DENOMS = (1, 2, 4, 8)
 
@@ -24,17 +25,6 @@ def _ceil(a, b):
 def _scaled_size(W, H, denom):
     N = 8 // denom
     return _ceil(W * N, 8), _ceil(H * N, 8)
-
-
-def _layout(w, h, factors, scale=None, precision=8):
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = w, h, precision, len(factors)
-    L.scale_x, L.scale_y = scale or (max(f[0] for f in factors), max(f[1] for f in factors))
-    for p, (fx, fy) in enumerate(factors):
-        L.factor_x[p], L.factor_y[p] = fx, fy
-        L.qi[p] = min(p, 1)
-    assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
-    return L
 
 
 def _window(L, cosited, denom, region):
@@ -129,7 +119,7 @@ def test_window_of_random_layouts():
             scale = (max(max(f[0] for f in factors), int(rng.integers(1, 5))),
                      max(max(f[1] for f in factors), int(rng.integers(1, 5))))
         W, H = int(rng.integers(1, 301)), int(rng.integers(1, 301))
-        _check_all(_layout(W, H, factors, scale), rng, 2)
+        _check_all(c_layout(W, H, factors, scale), rng, 2)
 
 
 def test_window_at_edges_of_sizes_off_the_mcu_grid():
@@ -138,7 +128,7 @@ def test_window_at_edges_of_sizes_off_the_mcu_grid():
     for W, H in ((17, 33), (31, 15), (47, 1), (1, 47), (161, 97)):
         for factors in ([(2, 2), (1, 1), (1, 1)], [(2, 1), (1, 1), (1, 1)], [(1, 2), (1, 1), (1, 1)], [(1, 1)] * 3,
                         [(4, 2), (1, 1), (2, 1)], [(1, 1)]):
-            L = _layout(W, H, factors)
+            L = c_layout(W, H, factors)
             for denom in DENOMS:
                 W1, H1 = _scaled_size(W, H, denom)
                 for cosited in (0, 1):
@@ -150,7 +140,7 @@ def test_window_at_edges_of_sizes_off_the_mcu_grid():
 
 
 def test_window_of_a_420_view_holds_the_chroma_halo():
-    L = _layout(1920, 1080, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(1920, 1080, [(2, 2), (1, 1), (1, 1)])
     st, w = _window(L, 0, 4, (237, 101, 64, 64))          # N = 2: blocks of 2 x 2 samples
     assert st == 0
     assert w[0] == (237 // 2, 101 // 2, (237 + 63) // 2 - 237 // 2 + 1, (101 + 63) // 2 - 101 // 2 + 1)
@@ -166,7 +156,7 @@ def test_view_of_source_sizes_1_to_70():
     for denom in DENOMS:
         N = 8 // denom
         for size in range(1, 71):
-            L = _layout(size, 71 - size, [(1, 1)])
+            L = c_layout(size, 71 - size, [(1, 1)])
             W1, H1 = _scaled_size(size, 71 - size, denom)
             ys, hs = (71 - size) // 3, max(1, (71 - size) // 2)
             hs = min(hs, 71 - size - ys)
@@ -185,7 +175,7 @@ def test_view_of_source_sizes_1_to_70():
 @pytest.mark.parametrize("src", [(-1, 0, 4, 4), (0, -1, 4, 4), (0, 0, 0, 4), (0, 0, 4, 0), (97, 0, 4, 4), (0, 57, 4, 4),
                                  (0, 0, 101, 60), (5, 0, 2 ** 31 - 1, 4), (2 ** 31 - 1, 0, 1, 1)])
 def test_view_of_source_rejects_rectangles_outside_the_image(src):
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     out = _lib.Region()
     r = _lib.Region(*src)
     for denom in DENOMS:
@@ -217,7 +207,7 @@ def test_view_denom_over_a_grid_of_sizes():
 
 def test_python_wrapper():
     layout = J.Layout("ycc8", {1: ((2, 2), 0), 2: ((1, 1), 1), 3: ((1, 1), 1)})
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     for denom in DENOMS:
         W1, H1 = _scaled_size(100, 60, denom)
         region = (W1 // 3, H1 // 4, W1 - W1 // 3, H1 // 2)
@@ -237,14 +227,14 @@ OUTSIDE = [(2, (-1, 0, 4, 4)), (2, (0, -1, 4, 4)), (2, (0, 0, 0, 4)), (2, (0, 0,
 
 @pytest.mark.parametrize("denom,region", OUTSIDE)
 def test_window_rejects_regions_outside_the_scaled_image(denom, region):
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     for cosited in (0, 1):
         assert _window(L, cosited, denom, region)[0] == _lib.EINVAL
 
 
 @pytest.mark.parametrize("denom", [0, 3, 16, -1, -8])
 def test_other_denoms_are_einval(denom):
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     lib = _lib.lib()
     r, out = _lib.Region(0, 0, 1, 1), _lib.Region()
     assert _window(L, 0, denom, (0, 0, 1, 1))[0] == _lib.EINVAL
@@ -252,7 +242,7 @@ def test_other_denoms_are_einval(denom):
 
 
 def test_host_calls_reject_null_arguments():
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     r, out = _lib.Region(0, 0, 1, 1), _lib.Region()
     w = (_lib.Region * _lib.MAX_PLANES)()
     lib = _lib.lib()
@@ -277,8 +267,8 @@ def _decode_view_batch(ctx, L, n, views, coef=None, strides=None, quanta=None, p
 def test_view_entry_points_check_their_arguments_before_the_device():
     """There is no GPU here and the context is NULL: a status other than EINVAL shows that the arguments are judged before
     the context is looked at, and a valid call with a NULL context is EINVAL."""
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
-    L12 = _layout(100, 60, [(2, 2), (1, 1), (1, 1)], precision=12)
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L12 = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)], precision=12)
     ok = _lib.View(2, _lib.Region(0, 0, 1, 1))
     assert _decode_view(None, L12, ok) == _lib.ENOSUP
     assert _decode_view_batch(None, L12, 1, C.byref(ok)) == _lib.ENOSUP
@@ -304,7 +294,7 @@ def test_view_entry_points_check_their_arguments_before_the_device():
 
 def test_batch_checks_every_view_and_the_stride_before_the_device():
     """Host pointers stand in for the device's: with a NULL context a call is refused before anything could read them."""
-    L = _layout(100, 60, [(2, 2), (1, 1), (1, 1)])
+    L = c_layout(100, 60, [(2, 2), (1, 1), (1, 1)])
     n = 5
     views = (_lib.View * n)(*[_lib.View(d, _lib.Region(1, 2, 5, 3)) for d in (1, 2, 8, 4, 2)])
     buf = np.zeros(64, np.int16)

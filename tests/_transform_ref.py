@@ -114,6 +114,42 @@ def requantize_ref(plane_t, q_in_t, q_out):
     return np.trunc(r).astype(np.int64), trapped
 
 
+# ---- the shapes of the seam tests (test_gpu_transform_shapes, test_transform_cpu) ---------------
+# A workgroup of k_spectral_transform covers 256 x 1 output blocks (ops that keep the axes) or 32 x 8 (transposing ops).
+LAYOUTS = {"y8": [(1, 1)], "444": [(1, 1)] * 3, "420": [(2, 2), (1, 1), (1, 1)], "422": [(2, 1), (1, 1), (1, 1)],
+           "440": [(1, 2), (1, 1), (1, 1)], "411": [(4, 1), (1, 1), (1, 1)], "4p": [(2, 2), (2, 2), (2, 2), (1, 1)]}
+# (4133, 37): luma 517 x 5 blocks, split 256 / 256 / 5 by the 256-block workgroups, 4:2:0 chroma 259 x 3 behind it;
+# (150, 600): luma 19 x 75, 4:2:0 chroma 10 x 38: transposed, past 32 blocks in x and 8 in y in every plane;
+# (1, 1), (9, 15): planes of one block and of 2 x 2
+SEAM_SIZES = [(4133, 37), (150, 600), (1, 1), (9, 15)]
+# luma 257 x 33: one block past a seam of either workgroup shape, where a rounded-down count of workgroups per row shows
+# (none of the sizes above has a plane of 256 k + 1 or 32 k + 1 blocks other than 1)
+SEAM_PLUS_ONE = {"y8": [(2049, 257)], "420": [(2049, 257)]}
+
+
+def seam_sizes(name):
+    return SEAM_SIZES + SEAM_PLUS_ONE.get(name, [])
+
+
+def layout_tables(name):
+    """-> (qi per plane, number of tables) of a LAYOUTS entry."""
+    n = len(LAYOUTS[name])
+    qi = [0, 1, 1, 2] if n == 4 else [min(p, 1) for p in range(n)]
+    return qi, max(qi) + 1
+
+
+def seam_regions(w, h, factors):
+    """None, an interior region (where there is room for one), a region that grows from the origin past a workgroup seam of
+    either tile shape, and one that grows from the last MCU column, so that almost every output block is new."""
+    sx, sy = max(f[0] for f in factors), max(f[1] for f in factors)
+    regions = [None]
+    if w - 8 * sx - 5 > 0 and h - 8 * sy - 3 > 0:
+        regions.append((8 * sx, 8 * sy, w - 8 * sx - 5, h - 8 * sy - 3))
+    regions.append((0, 0, w + 320 * sx + 3, h + 72 * sy + 1))
+    regions.append(((w - 1) // (8 * sx) * 8 * sx, 0, 320 * sx + 3, h + 72 * sy + 1))
+    return regions
+
+
 # ---- the C entry points ------------------------------------------------------------------------
 def c_layout(width, height, factors, precision=8):
     L = _lib.Layout()

@@ -62,6 +62,68 @@ def test_layout_of_every_op_on_every_fixture_frame(path):
         _check(L, factors, op, (0, 8 * sy, info.width + 37, info.height + 3))
 
 
+@pytest.mark.parametrize("name", sorted(R.LAYOUTS))
+def test_layout_of_every_op_at_the_seam_shapes(name):
+    """The layouts, sizes and regions of test_gpu_transform_shapes: the library's geometry against the restatement's, EINVAL
+    exactly where a mirror trims the image to nothing."""
+    factors = R.LAYOUTS[name]
+    qi, _ = R.layout_tables(name)
+    refused = 0
+    for w, h in R.seam_sizes(name):
+        L = R.c_layout(w, h, factors)
+        for p, t in enumerate(qi):
+            L.qi[p] = t
+        for op in range(8):
+            for region in R.seam_regions(w, h, factors):
+                refused += _check(L, factors, op, region) is None
+    assert refused                                        # (1, 1) under a mirror, at the least
+    # the unit counts the seam tests are built on
+    units = lambda size, op=0: R.layout_ref(*size, factors, op)[3]
+    assert units((4133, 37))[0] == (517, 5) and units((150, 600))[0] == (19, 75)
+    assert units((150, 600), 1)[0] == (75, 19)
+    assert all(units(size)[0] == (257, 33) for size in R.SEAM_PLUS_ONE.get(name, []))
+    if name == "420":
+        assert units((4133, 37))[1] == (259, 3) and units((150, 600))[1] == (10, 38)
+    if name == "411":
+        assert units((4133, 37))[1] == (130, 5)
+
+
+def test_every_op_of_the_restatement_is_the_geometric_transform_in_pixel_space():
+    """The float64 inverse cosine transform of R.transform_plane(plane, op) is that of the plane, transposed and / or mirrored
+    as op's bits say.  In real arithmetic the identity is exact (a mirror of cos((2x+1)k pi/16) in x is its negation for odd
+    k), so the bound is float64 rounding alone: 1e-12 of the largest source sample (the worst of the 8 ops is 1.1e-15 of it).
+    This anchors the restatement's TRANSPOSE, FLIP_H, FLIP_V and TRANSVERSE, which no file of the reference covers."""
+    from jpeg_amd.zigzag import z as zz
+    ux, uy = 5, 7
+    rng = np.random.default_rng(23)
+    plane = rng.integers(-32767, 32768, (uy, ux, 64)).astype(np.int16)
+    k = np.arange(8)
+    basis = np.cos((2 * k[:, None] + 1) * k[None, :] * np.pi / 16)         # [x, k]
+    basis[:, 0] = 1 / np.sqrt(2)
+    unzig = np.array([[zz(kk, hh) for kk in range(8)] for hh in range(8)])  # [h, k]
+
+    def samples(p):
+        f = p.astype(np.float64)[..., unzig]                                # [by, bx, h, k]
+        s = np.einsum("yh,xk,abhk->aybx", basis, basis, f)
+        return s.reshape(8 * p.shape[0], 8 * p.shape[1])
+
+    source = samples(plane)
+    bound = 1e-12 * np.abs(source).max()
+    for op in range(8):
+        want = source
+        if op & 1:
+            want = want.T
+        if op & 2:
+            want = want[:, ::-1]
+        if op & 4:
+            want = want[::-1, :]
+        got = samples(R.transform_plane(plane, op, (ux, uy), (0, 0)))
+        assert got.shape == want.shape
+        err = np.abs(got - want).max()
+        print(f"op {op}: {err / np.abs(source).max():.2e} of the largest sample")
+        assert err <= bound, (op, err, bound)
+
+
 def test_transposing_ops_swap_the_sampling_layout():
     for factors, want in (([(2, 1), (1, 1), (1, 1)], [(1, 2), (1, 1), (1, 1)]),     # 4:2:2 -> 4:4:0
                           ([(2, 2), (1, 1), (1, 1)], [(2, 2), (1, 1), (1, 1)]),     # 4:2:0 stays

@@ -781,6 +781,54 @@ int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, con
                            const jpeg_amd_view *view, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
                            int flip, void *d_dst);
 
+/* ---- mixed calls: views of images of different sizes and layouts in one call -----------------------------
+ * What a data loader has: n files of n sizes, some 4:2:0, some 4:4:4, some grey, to one tensor.  The view, resized and
+ * tensor calls above take one layout per call; these take one per IMAGE. */
+typedef struct jpeg_amd_image {          /* one image of a mixed call */
+    jpeg_amd_layout layout;              /* its own geometry */
+    const int16_t  *d_coef[JPEG_AMD_MAX_PLANES];
+    const uint16_t *d_quanta;            /* device, [ntables][64], zigzag */
+    int32_t         ntables;
+} jpeg_amd_image;
+
+/* THE CONTRACT (the one statement of it): image i of the output is EXACTLY WHAT THE UNIFORM CALL WRITES FOR IMAGE i WHEN
+ * CALLED ON IT ALONE, bit for bit -- jpeg_amd_decode_view_batch, jpeg_amd_decode_resized_batch or
+ * jpeg_amd_decode_tensor_batch with n_images = 1, h_images[i].layout, its planes (any strides), its tables (ntables of
+ * them), h_views[i] and, for the tensor call, h_flip[i].  No arithmetic is defined here.
+ *
+ * h_images and h_views are HOST arrays of n_images elements; the call copies them before it returns (h_flip as in
+ * jpeg_amd_resize_tensor_batch: NULL = no image mirrored).  cosited and color hold for every image.  Output placement and
+ * strides are the uniform calls': for the view call image i is at d_pixels + i * pixel_stride, region.height rows of
+ * region.width * 3 bytes, and pixel_stride >= 3 * width_i * height_i for every i (any value when n_images == 1); for the
+ * resized and the tensor call as in jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch.  Bytes in the stride
+ * gaps are left alone.
+ *
+ * Everything is judged before anything is enqueued, the context last.  Each image's layout, planes, tables and view are
+ * checked against ITS OWN layout, and the status is the one the uniform call gives for the first offending image in index
+ * order: EINVAL for a view outside that image's scaled size, a null plane pointer, a denominator not in {1, 2, 4, 8}, an
+ * ntables at or below a plane's qi, a stride that is too small; ENOSUP for an image that is not 8-bit (one 12-bit image
+ * refuses the whole call).  EINVAL also for n_images < 0 or above 65 535, null h_images or h_views, and a launch whose
+ * summed workgroups do not fit a grid.  After a refused call nothing has been written and the context is usable.
+ * n_images == 0 is OK.
+ *
+ * Cost: the images whose layout the fused decode takes (y8; ycc8 with full-factor luma and chroma at 1x or 2x per axis,
+ * centred) are grouped by (N = 8 / denom, 1 or 3 planes): at most EIGHT launches of the tile kernel, each over the images
+ * of its group whatever their sizes and whatever their mix of 4:4:4, 4:2:2, 4:4:0 and 4:2:0, behind ONE host-to-device
+ * copy of the per-image records.  The mixed calls ALWAYS take the tile kernel for those images: a call of whole images, or
+ * of denominators that are all 1, has no shortcut into the whole-image or the region kernels as the uniform view call has;
+ * for such a batch of one geometry the uniform calls are the faster ones.  Every other image (cosited calls, factors 3 or
+ * 4, chroma not at 1x or 2x) goes through the uniform call ONE IMAGE AT A TIME: correct, and as costly as that sounds.
+ * The resized and the tensor call follow jpeg_amd_decode_resized_batch's route: chunks of consecutive images of at most
+ * 1 GiB of compact views in a buffer of the context, per chunk the mixed view decode and then ONE resample launch. */
+int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                               jpeg_amd_color color, const jpeg_amd_view *h_views, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                  jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                  uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                 jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride);
+
 /* ---- spectral reduce: a Spectral at 1/2, 1/4 or 1/8 size, coefficients in and coefficients out ----------
  * JPEG in, smaller JPEG out, without pixels in between: no interleave, no colour conversion and no second generation of
  * chroma rounding, so every layout, plane count and precision is served alike.  It composes two contracts that are stated

@@ -138,6 +138,9 @@ SIGNATURES = {
     "jpeg_amd_decode_tensor_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p, C.c_int32,
                                                C.c_int32, _p, _p, _p, C.c_size_t]),
     "jpeg_amd_decode_tensor": (C.c_int, [_p, _L, _pp, _p, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, C.c_int, _p]),
+    "jpeg_amd_decode_view_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_resized_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, _p, _p, C.c_size_t]),
     "jpeg_amd_reduce_layout": (C.c_int, [_L, C.c_int, _L]),
     "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
     "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
@@ -153,6 +156,11 @@ class Region(C.Structure):
 class View(C.Structure):
     """struct jpeg_amd_view"""
     _fields_ = [("denom", C.c_int32), ("region", Region)]
+
+
+class Image(C.Structure):
+    """struct jpeg_amd_image"""
+    _fields_ = [("layout", Layout), ("d_coef", C.c_void_p * MAX_PLANES), ("d_quanta", C.c_void_p), ("ntables", C.c_int32)]
 
 
 class Extent(C.Structure):

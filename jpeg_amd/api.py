@@ -881,6 +881,91 @@ def decode_crops_tensor(ctx: Context, size, layout: Layout, planes, quanta, sour
     return decode_tensors(ctx, size, layout, planes, quanta, views, out_size, spec, flips=flips, q=q, color=color, cosite=cosite), views
 
 
+def _mixed_args(ctx: Context, spectrals, views):
+    """The arguments the mixed calls share: (vs [n, 5], c images, c views, keep).  Every image's tables go up in ONE upload;
+    `keep` holds what the pointers in the c images point into."""
+    torch = _torch()
+    spectrals = list(spectrals)
+    vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
+    n = vs.shape[0]
+    if len(spectrals) != n:
+        raise ValueError("views: one (denom, x, y, width, height) per image")
+    tables = [t for s in spectrals for t in s.quanta]
+    quanta = ctx.upload(np.stack(tables).astype(np.uint16)) if tables else None
+    h_images = (_lib.Image * max(n, 1))()
+    first = 0
+    for i, s in enumerate(spectrals):
+        for p in s.planes:
+            if p.dtype != torch.int16 or not p.is_contiguous():
+                raise ValueError("spectrals: planes are contiguous int16 device tensors")
+        h_images[i].layout = s._layout()
+        for p, plane in enumerate(s.planes):
+            h_images[i].d_coef[p] = plane.data_ptr()
+        h_images[i].d_quanta = quanta.data_ptr() + 128 * first
+        h_images[i].ntables = len(s.quanta)
+        first += len(s.quanta)
+    h_views = (_lib.View * max(n, 1))()
+    for i, row in enumerate(vs.tolist()):
+        h_views[i] = _view(row[0], row[1:])
+    return vs, h_images, h_views, (spectrals, quanta)
+
+
+def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool = False):
+    """decode_views for images of DIFFERENT sizes and layouts in one call (jpeg_amd_decode_view_mixed).  spectrals: a sequence
+    of Spectral objects (what Spectral.decompress returns), any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0 and of grey;
+    views: [n, 5] of (denom, x, y, width, height), each against its own image.  Image i is what Spectral.view gives for it.
+    Returns n uint8 views [h_i, w_i, 3] into one allocation."""
+    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
+    n = vs.shape[0]
+    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
+    stride = max(areas)
+    out = ctx.empty(n * stride, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_view_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, out.data_ptr(),
+                                                     stride), "jpeg_amd_decode_view_mixed", ctx.handle)
+    return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
+
+
+def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False):
+    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_mixed); arguments as
+    decode_views_mixed.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
+    n = vs.shape[0]
+    wt, ht = int(out_size[0]), int(out_size[1])
+    stride = 3 * max(wt, 0) * max(ht, 0)
+    out = ctx.empty(n * stride, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_decode_resized_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                        out.data_ptr(), stride), "jpeg_amd_decode_resized_mixed", ctx.handle)
+    return out.view(n, ht, wt, 3)
+
+
+def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
+                         cosite: bool = False):
+    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_mixed); arguments as
+    decode_views_mixed, then as decode_tensors.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
+    n = vs.shape[0]
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                       C.byref(spec), h_flip, out.data_ptr(), stride),
+               "jpeg_amd_decode_tensor_mixed", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec)
+
+
+def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
+                              cosite: bool = False):
+    """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
+    full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
+    size -- through decode_tensors_mixed.  Returns (tensor, the views as int32 [n, 5])."""
+    spectrals = list(spectrals)
+    regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
+    if regs.shape[0] != len(spectrals):
+        raise ValueError("source_regions: one (x, y, width, height) per image")
+    views = np.empty((len(spectrals), 5), np.int32)
+    for i, s in enumerate(spectrals):
+        views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
+    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite), views
+
+
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None):
     """The resample and the output stage alone (jpeg_amd_resize_tensor_batch): n device uint8 images [h_i, w_i, 3] of any
     sizes to one tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3] of spec's dtype, in one launch."""

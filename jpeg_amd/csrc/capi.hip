@@ -44,6 +44,9 @@ struct jpeg_amd_ctx {
     // jpeg_amd_decode_resized_batch / jpeg_amd_resize_batch: the decoded views of a chunk and the resample's per-image records.
     // Buffers of their own: the view call in between regrows `scratch` and overwrites `region`.
     DeviceBuffer resize_src, resize_rec;
+    // the mixed calls (jpeg_amd_decode_view_mixed, ...): the per-image records, index lists and tile prefixes of their launches.
+    // A buffer of its own: the uniform calls of a mixed call's fallback images rewrite `region`, the resample rewrites the others.
+    DeviceBuffer mixed;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -505,7 +508,7 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->workers.reset();
     ctx->copiers.reset();
-    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec})
+    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed})
         if (buf->ptr) (void)hipFree(buf->ptr);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
@@ -1422,6 +1425,178 @@ int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
     return jpeg_amd_decode_tensor_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, spec,
                                         &h_flip, d_dst, 0);
 }
+
+namespace {
+
+constexpr int kMixedGroups = 2 * kViewDenoms;   // group 2 k + (three planes): the images of N = 8 >> k with that many planes
+
+// Images [0, m) of a mixed call, or of a chunk of one, sorted into the launches of k_view_decode_mixed and the images that
+// take the uniform call.
+struct MixedPlan {
+    std::vector<uint32_t> members[kMixedGroups];   // the group's images, in index order
+    uint32_t nwg[kMixedGroups] = {};
+    std::vector<int> fallback;                     // no tile kernel for the layout: the uniform call, image by image
+};
+
+// What the uniform view call with n_images = 1 judges of image `im` with view `v`, in its order (check_views itself), then the
+// stride that the mixed call's placement needs.
+int check_mixed_image(const jpeg_amd_image &im, int n_images, int cosited, jpeg_amd_color color, const jpeg_amd_view &v,
+                      const void *d_out, size_t pixel_stride)
+{
+    const DecodeCall c{&im.layout, 1, im.d_coef, kOneImage, im.d_quanta, 0, im.ntables, cosited, color,
+                       static_cast<uint8_t *>(const_cast<void *>(d_out)), 0};
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(c, &v, S, count, &whole, &cs));
+    if (n_images > 1 && pixel_stride < (size_t)3 * v.region.width * v.region.height) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// The plan of m checked images; EINVAL: a launch of more workgroups than a grid holds.
+int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosited, MixedPlan *plan)
+{
+    uint64_t acc[kMixedGroups] = {};
+    for (int i = 0; i < m; ++i) {
+        if (!fused_decode_supported(im[i].layout, cosited != 0)) {
+            plan->fallback.push_back(i);
+            continue;
+        }
+        const int k = view_slot(v[i].denom), g = 2 * k + (im[i].layout.nplanes == 3 ? 1 : 0);
+        plan->members[g].push_back((uint32_t)i);
+        acc[g] += view_tiles(8 >> k, v[i].region);
+    }
+    for (int g = 0; g < kMixedGroups; ++g) {
+        if (acc[g] > 0x7fffffffu) return JPEG_AMD_EINVAL;
+        plan->nwg[g] = (uint32_t)acc[g];
+    }
+    return JPEG_AMD_OK;
+}
+
+// The planned images into d_pixels, image i at i * pixel_stride: one copy of the records [m], then per group its index list
+// and tile prefix, into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when the call
+// returns -- as stage_quanta); a launch per group; the uniform call for each of the others.
+int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *v, int m, const MixedPlan &plan, int cosited,
+              jpeg_amd_color color, uint8_t *d_pixels, size_t pixel_stride)
+{
+    const size_t rec_bytes = mixed_record_bytes(), lists = rec_bytes * (size_t)m;
+    size_t words = 0;
+    for (int g = 0; g < kMixedGroups; ++g)
+        if (!plan.members[g].empty()) words += 2 * plan.members[g].size() + 1;
+    if (words != 0) {
+        std::vector<uint8_t> buf(lists + 4 * words);   // the records of the uniform call's images stay zero: no list names them
+        uint32_t *w = reinterpret_cast<uint32_t *>(buf.data() + lists);
+        size_t at[kMixedGroups] = {}, fill = 0;
+        for (int g = 0; g < kMixedGroups; ++g) {
+            const std::vector<uint32_t> &mem = plan.members[g];
+            if (mem.empty()) continue;
+            const int n = 8 >> (g / 2);
+            at[g] = fill;
+            uint32_t acc = 0;
+            for (size_t j = 0; j < mem.size(); ++j) {
+                const uint32_t i = mem[j];
+                mixed_record(buf.data() + rec_bytes * i, im[i].layout, n, im[i].d_coef, im[i].d_quanta, v[i].region,
+                             d_pixels + (size_t)i * pixel_stride);
+                w[fill + j] = i;
+                w[fill + mem.size() + j] = acc;
+                acc += view_tiles(n, v[i].region);
+            }
+            w[fill + 2 * mem.size()] = acc;
+            fill += 2 * mem.size() + 1;
+        }
+        JA_TRY(ensure_buffer(ctx, ctx->mixed, buf.size()));
+        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, buf.data(), buf.size(), hipMemcpyHostToDevice, ctx->stream));
+        const uint32_t *d_w = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(ctx->mixed.ptr) + lists);
+        for (int g = 0; g < kMixedGroups; ++g) {
+            const int count = (int)plan.members[g].size();
+            if (count == 0) continue;
+            JA_HIP(ctx, launch_view_decode_mixed(ctx->stream, count, 8 >> (g / 2), g % 2 ? 3 : 1, color == JPEG_AMD_COLOR_RGB8,
+                                                 ctx->mixed.ptr, d_w + at[g], d_w + at[g] + count, plan.nwg[g]));
+        }
+    }
+    for (const int i : plan.fallback)
+        JA_TRY(jpeg_amd_decode_view_batch(ctx, &im[i].layout, 1, im[i].d_coef, kOneImage, im[i].d_quanta, 0, im[i].ntables, cosited,
+                                          color, &v[i], d_pixels + (size_t)i * pixel_stride, 0));
+    return JPEG_AMD_OK;
+}
+
+// The resized and the tensor call (spec != nullptr): jpeg_amd_decode_resized_batch's route with the mixed view decode.
+int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                  const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, bool tensor,
+                  const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+{
+    // every argument first, the context last; the target is judged where the uniform call judges it: behind the first image
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
+    size_t elem_bytes = 1;
+    const auto check_target = [&]() {
+        return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes)
+                      : check_resize_target(n_images, out_w, out_h, static_cast<const uint8_t *>(d_dst), dst_stride);
+    };
+    for (int i = 0; i < n_images; ++i) {
+        JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], d_dst, 0));   // the views' stride is ours
+        if (i == 0) JA_TRY(check_target());
+    }
+    if (n_images == 0) JA_TRY(check_target());
+    std::vector<ResizeChunk> chunks;
+    std::vector<ResizeRecord> rec((size_t)n_images);
+    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, h_flip, chunks, rec);
+    std::vector<MixedPlan> plans(chunks.size());
+    for (size_t c = 0; c < chunks.size(); ++c)
+        JA_TRY(plan_mixed(h_images + chunks[c].i0, h_views + chunks[c].i0, chunks[c].m, cosited, &plans[c]));
+    if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
+    JA_TRY(bind(ctx));
+
+    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
+    JA_TRY(upload_records(ctx, rec));
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
+    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
+    for (size_t c = 0; c < chunks.size(); ++c) {
+        const ResizeChunk &k = chunks[c];
+        JA_TRY(run_mixed(ctx, h_images + k.i0, h_views + k.i0, k.m, plans[c], cosited, color, d_views, k.stride));
+        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)k.i0 * dst_stride * elem_bytes;
+        if (tensor)
+            JA_HIP(ctx, launch_resize_tensor(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, *spec, d_out, dst_stride));
+        else
+            JA_HIP(ctx, launch_resize_bilinear(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, d_out, dst_stride));
+    }
+    return JPEG_AMD_OK;
+}
+
+}  // namespace
+
+int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                               jpeg_amd_color color, const jpeg_amd_view *h_views, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
+    for (int i = 0; i < n_images; ++i) JA_TRY(check_mixed_image(h_images[i], n_images, cosited, color, h_views[i], d_pixels, pixel_stride));
+    MixedPlan plan;
+    JA_TRY(plan_mixed(h_images, h_views, n_images, cosited, &plan));
+    if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
+    JA_TRY(bind(ctx));
+    return run_mixed(ctx, h_images, h_views, n_images, plan, cosited, color, d_pixels, pixel_stride);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                  jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                  uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, nullptr, false, nullptr, d_pixels,
+                         pixel_stride);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                 jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, spec, true, h_flip, d_dst, dst_stride);
+}
+JA_NOTHROW_TAIL
 
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const uint32_t *d_desc,
                                    size_t desc_stride, const uint32_t *d_entries, size_t entries_stride, const uint8_t *d_skip,

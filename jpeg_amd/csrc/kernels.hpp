@@ -136,6 +136,17 @@ hipError_t launch_view_decode(hipStream_t stream, int n_images, const jpeg_amd_l
                               bool rgb, const uint32_t *d_index, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
                               uint8_t *d_pixels, size_t pixel_stride);
 
+// ... and for images of different layouts (k_view_decode_mixed): the images of a call that share n and the number of planes
+// (1 or 3), every one with the layout, planes, tables, rectangle and output of its own, in ONE launch.  d_records: one record
+// of mixed_record_bytes() bytes per image of the call, 16-byte aligned, written by mixed_record on the host -- `layout` is
+// one of fused_decode_supported, `region` a rectangle of its image at n samples per block, d_pixels where that rectangle's
+// first pixel goes (rows of region.width * 3 bytes); d_index and d_tiles as above, over view_tiles(n, region).
+size_t     mixed_record_bytes();
+void       mixed_record(void *dst, const jpeg_amd_layout &layout, int n, const int16_t *const d_coef[], const uint16_t *d_quanta,
+                        const jpeg_amd_region &region, uint8_t *d_pixels);
+hipError_t launch_view_decode_mixed(hipStream_t stream, int n_images, int n, int nplanes, bool rgb, const void *d_records,
+                                    const uint32_t *d_index, const uint32_t *d_tiles, uint32_t nwg);
+
 // ---- bilinear resample (kernels_resize.hip) ------------------------------------------------
 // n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h by the contract of include/jpeg_amd.h
 // ("resized decode") in ONE launch (k_resize_bilinear).  d_records: one ResizeRecord per image -- the image's first byte at

@@ -6,8 +6,14 @@
 // makes a call of mixed denominators one launch per denominator.  The tile is the scaled kernel's: 128 x 32 output pixels.
 // N = 8 gives the bytes of k_region_decode, for the denominator-1 images of a mixed call.
 //
+// k_view_decode_mixed<N, planes, rgb>: the same grid and body for images of DIFFERENT sizes and samplings
+// (jpeg_amd_decode_view_mixed): one launch per (N, planes) of the call, every image with a record of its own in device
+// memory in the place of the kernel argument.
+//
 // Compile with -ffp-contract=off (see dct.hpp).
 #pragma clang fp contract(off)
+
+#include <cstring>
 
 #include "tile_decode.hpp"
 
@@ -43,7 +49,55 @@ void launch_view(dim3 grid, hipStream_t stream, int nplanes, bool rgb, const Vie
     }
 }
 
+// The same workgroup for the images of a mixed call (jpeg_amd_decode_view_mixed) that share N and the number of planes:
+// sizes and samplings differ from image to image, so what decode_tile reads comes from the image's MixedRecord.
+template <int N, int NP, bool RGB>
+__global__ __launch_bounds__(kThreads) void k_view_decode_mixed(MixedArgs g)
+{
+    Tile tile;
+    if (const MixedRecord *rec = mixed_tile<N, kTileH>(g, tile))
+        decode_tile<N, NP, RGB, kTileW, kTileH, chroma_span<N>(kTileW), chroma_span<N>(kTileH)>(rec->t, tile);
+}
+
+template <int N>
+void launch_mixed(dim3 grid, hipStream_t stream, int nplanes, bool rgb, const MixedArgs &g)
+{
+    if (nplanes == 1) {
+        if (rgb) hipLaunchKernelGGL((k_view_decode_mixed<N, 1, true>), grid, dim3(kThreads), 0, stream, g);
+        else hipLaunchKernelGGL((k_view_decode_mixed<N, 1, false>), grid, dim3(kThreads), 0, stream, g);
+    } else {
+        if (rgb) hipLaunchKernelGGL((k_view_decode_mixed<N, 3, true>), grid, dim3(kThreads), 0, stream, g);
+        else hipLaunchKernelGGL((k_view_decode_mixed<N, 3, false>), grid, dim3(kThreads), 0, stream, g);
+    }
+}
+
 }  // namespace
+
+size_t mixed_record_bytes() { return sizeof(MixedRecord); }
+
+void mixed_record(void *dst, const jpeg_amd_layout &L, int n, const int16_t *const d_coef[], const uint16_t *d_quanta,
+                  const jpeg_amd_region &r, uint8_t *d_pixels)
+{
+    PlaneSet coef{};
+    for (int p = 0; p < L.nplanes; ++p) coef.ptr[p] = d_coef[p];
+    const MixedRecord rec{tile_args(L, n, coef, QuantaRef{d_quanta, 0}, d_pixels, 0), int4{r.x, r.y, r.width, r.height}};
+    memcpy(dst, &rec, sizeof rec);
+}
+
+hipError_t launch_view_decode_mixed(hipStream_t stream, int n_images, int n, int nplanes, bool rgb, const void *d_records,
+                                    const uint32_t *d_index, const uint32_t *d_tiles, uint32_t nwg)
+{
+    if (n_images == 0 || nwg == 0) return hipSuccess;
+    if (nplanes != 1 && nplanes != 3) return hipErrorInvalidValue;
+    const MixedArgs g{static_cast<const MixedRecord *>(d_records), d_tiles, d_index, n_images};
+    const dim3 grid(nwg);
+    if (n == 8) launch_mixed<8>(grid, stream, nplanes, rgb, g);
+    else if (n == 4) launch_mixed<4>(grid, stream, nplanes, rgb, g);
+    else if (n == 2) launch_mixed<2>(grid, stream, nplanes, rgb, g);
+    else if (n == 1) launch_mixed<1>(grid, stream, nplanes, rgb, g);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 
 uint32_t view_tiles(int n, const jpeg_amd_region &r) { return rect_tiles(n, kTileH, r); }
 

@@ -1,7 +1,8 @@
-// tile_decode.hpp -- the workgroup body that k_region_decode, k_scaled_decode and k_view_decode share: one tile of output
-// pixels of one image, straight from the coefficients, at N x N samples per block (N = 8 / denom in {8, 4, 2, 1}; N = 8 is
-// the full-size transform).  The three kernels differ in how a workgroup finds its image and its tile, in the tile's height
-// and in the set of N they are built for; what a workgroup then does is decode_tile, written once:
+// tile_decode.hpp -- the workgroup body that k_region_decode, k_scaled_decode, k_view_decode and k_view_decode_mixed share:
+// one tile of output pixels of one image, straight from the coefficients, at N x N samples per block (N = 8 / denom in
+// {8, 4, 2, 1}; N = 8 is the full-size transform).  The kernels differ in how a workgroup finds its image and its tile, in
+// where what it reads of the image comes from (the kernel's arguments, or a record per image in device memory), in the
+// tile's height and in the set of N they are built for; what a workgroup then does is decode_tile, written once:
 //   1. modulate the image's N x N tables into LDS and write the per-column / per-row interleave maps of its chroma planes
 //      (the sample pair and the fraction of decode.swift:4240-4251, tile-local), with last = N units - 1;
 //   2. transform every block of every plane that the tile's pixels read -- axis_span of interleave.hpp, the chroma halo
@@ -222,28 +223,72 @@ inline uint32_t rect_tiles(int n, int tile_h, const jpeg_amd_region &r)
     return (uint32_t)((r.x + r.width - 1 - ax0) / kTileW + 1) * (uint32_t)((r.y + r.height - 1 - ay0) / tile_h + 1);
 }
 
-// Workgroup blockIdx.x's tile; false: it has none.  index: [n], the launch's image i is image index[i] of the call and has
-// that image's rectangle, or nullptr: it is image i.
-template <int N, int TH>
-__device__ __forceinline__ bool rect_tile(const RectArgs &g, const uint32_t *index, const TileArgs &a, Tile &t)
+// The launch's image of workgroup wg: the last i with tiles[i] <= wg.
+__device__ __forceinline__ int rect_image(const uint32_t *tiles, int n_images, uint32_t wg)
 {
-    const uint32_t wg = blockIdx.x;
-    int lo = 0, hi = g.n_images;                          // the launch's image: the last i with tiles[i] <= wg
+    int lo = 0, hi = n_images;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (g.tiles[mid] <= wg) lo = mid; else hi = mid;
+        if (tiles[mid] <= wg) lo = mid; else hi = mid;
     }
-    t.img = index ? (int)index[lo] : lo;
-    const int4 r = g.regions[t.img];
-    const int tile = (int)(wg - g.tiles[lo]);
+    return lo;
+}
+
+// Tile number `tile` of rectangle r, whose first pixel is at `base`: everything of t but img; false: r has no such tile.
+template <int N, int TH>
+__device__ __forceinline__ bool tile_of_rect(const int4 &r, int tile, uint8_t *base, Tile &t)
+{
     const int ax0 = N * udiv<N>(r.x), ay0 = N * udiv<N>(r.y);   // the tile grid's anchor: the luma window's first block
     const int ntx = udiv<kTileW>(r.x + r.z - 1 - ax0) + 1;
     const int ty = tile / ntx, tx = tile - ty * ntx;
     t.px0 = max(r.x, ax0 + kTileW * tx); t.px1 = min(r.x + r.z, ax0 + kTileW * (tx + 1));
     t.py0 = max(r.y, ay0 + TH * ty); t.py1 = min(r.y + r.w, ay0 + TH * (ty + 1));
     t.row_bytes = 3 * (size_t)r.z;
-    t.out = a.pixels + (size_t)t.img * a.pixel_stride + 3 * ((size_t)(t.py0 - r.y) * r.z + (t.px0 - r.x));
+    t.out = base + 3 * ((size_t)(t.py0 - r.y) * r.z + (t.px0 - r.x));
     return t.px1 > t.px0 && t.py1 > t.py0;                // a prefix that is not this rectangle's: a host bug -- write nothing
+}
+
+// Workgroup blockIdx.x's tile; false: it has none.  index: [n], the launch's image i is image index[i] of the call and has
+// that image's rectangle, or nullptr: it is image i.
+template <int N, int TH>
+__device__ __forceinline__ bool rect_tile(const RectArgs &g, const uint32_t *index, const TileArgs &a, Tile &t)
+{
+    const uint32_t wg = blockIdx.x;
+    const int lo = rect_image(g.tiles, g.n_images, wg);
+    t.img = index ? (int)index[lo] : lo;
+    const int4 r = g.regions[t.img];
+    return tile_of_rect<N, TH>(r, (int)(wg - g.tiles[lo]), a.pixels + (size_t)t.img * a.pixel_stride, t);
+}
+
+// ---- the mixed rectangle kernel: every image of a launch with a geometry of its own ---------------------------------------
+// The rectangle grid above, but what decode_tile reads of an image comes from device memory, not from the kernel's
+// arguments: one record per image of the call, staged by the host with the prefix and the index list.  The record's
+// pointers are the image's own (decode_tile runs with Tile::img = 0, the strides are not read), ux, qi, ax, ay with
+// last = N units - 1 are its layout's, `region` is its rectangle of the scaled image.
+struct MixedRecord {
+    TileArgs t;
+    int4 region;                  // x, y, width, height in pixels
+};
+static_assert(sizeof(MixedRecord) % 16 == 0, "records lie in an array that the host stages as bytes");
+
+struct MixedArgs {
+    const MixedRecord *records;   // [images of the call]
+    const uint32_t *tiles;        // [n + 1]
+    const uint32_t *index;        // [n]: the launch's image i is image index[i] of the call
+    int n_images;                 // of the launch
+};
+
+// Workgroup blockIdx.x's image -- its record, which decode_tile then reads in place -- and tile; nullptr: it has none.
+// The record's address is the same for every work-item of the workgroup.
+template <int N, int TH>
+__device__ __forceinline__ const MixedRecord *mixed_tile(const MixedArgs &g, Tile &t)
+{
+    const uint32_t wg = blockIdx.x;
+    const int lo = rect_image(g.tiles, g.n_images, wg);
+    const MixedRecord *rec = g.records + g.index[lo];
+    t.img = 0;
+    const int4 r = rec->region;
+    return tile_of_rect<N, TH>(r, (int)(wg - g.tiles[lo]), rec->t.pixels, t) ? rec : nullptr;
 }
 
 }  // namespace jpeg_amd

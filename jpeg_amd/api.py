@@ -552,6 +552,15 @@ def _view(denom, region) -> "_lib.View":
     return v
 
 
+def _views(views):
+    """views [n, 5] of (denom, x, y, width, height) -> (them as int32 [n, 5], the c views)."""
+    vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
+    h_views = (_lib.View * max(vs.shape[0], 1))()
+    for i, row in enumerate(vs.tolist()):
+        h_views[i] = _view(row[0], row[1:])
+    return vs, h_views
+
+
 def transform_quanta(op, table) -> np.ndarray:
     """q_out[z] = q_in[m(z)] (jpeg_amd_transform_quanta)."""
     t = np.ascontiguousarray(np.asarray(table, np.uint16).reshape(64))
@@ -731,13 +740,18 @@ def view_denom(source_size, want_size) -> int:
 
 def _view_batch_args(ctx: Context, size, layout: Layout, planes, quanta, views, q):
     """The arguments decode_views, decode_resized and decode_tensors share: (vs [n, 5], head and keep of _batch_args, c views)."""
-    vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
-    n = vs.shape[0]
-    head, keep = _batch_args(ctx, size, layout, planes, quanta, q, n)
-    h_views = (_lib.View * max(n, 1))()
-    for i, row in enumerate(vs.tolist()):
-        h_views[i] = _view(row[0], row[1:])
+    vs, h_views = _views(views)
+    head, keep = _batch_args(ctx, size, layout, planes, quanta, q, vs.shape[0])
     return vs, head, keep, h_views
+
+
+def _views_out(ctx: Context, vs):
+    """Room for the n views vs [n, 5] in one allocation -> (it, its stride, the n slices of it as uint8 [h_i, w_i, 3])."""
+    n = vs.shape[0]
+    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
+    stride = max(areas)
+    out = ctx.empty(n * stride, _torch().uint8)
+    return out, stride, [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
 
 
 def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: Optional[Sequence[int]] = None, color=RGB,
@@ -746,13 +760,10 @@ def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: O
     one call (jpeg_amd_decode_view_batch).  planes[p]: device int16 [n, uy, ux, 64]; quanta: [n, ntables, 64] (host or
     device); views: [n, 5] of (denom, x, y, width, height).  Returns n uint8 views [h_i, w_i, 3] into one allocation."""
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
-    n = vs.shape[0]
-    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
-    stride = max(areas)
-    out = ctx.empty(n * stride, _torch().uint8)
+    out, stride, slices = _views_out(ctx, vs)
     _lib.check(_lib.lib().jpeg_amd_decode_view_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, out.data_ptr(), stride),
                "jpeg_amd_decode_view_batch", ctx.handle)
-    return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
+    return slices
 
 
 def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, q: Optional[Sequence[int]] = None,
@@ -762,9 +773,7 @@ def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     uint8 tensor [n, Ht, Wt, 3]."""
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
-    wt, ht = int(out_size[0]), int(out_size[1])
-    stride = 3 * max(wt, 0) * max(ht, 0)
-    out = ctx.empty(n * stride, _torch().uint8)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
                                                         out.data_ptr(), stride), "jpeg_amd_decode_resized_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
@@ -809,13 +818,10 @@ def _pack_images(ctx: Context, images):
 def resize(ctx: Context, images, out_size):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
     (jpeg_amd_resize_batch).  The images are packed into one allocation first (torch copies).  Returns uint8 [n, Ht, Wt, 3]."""
-    torch = _torch()
     images = list(images)
     n = len(images)
     src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht = int(out_size[0]), int(out_size[1])
-    stride = 3 * max(wt, 0) * max(ht, 0)
-    out = ctx.empty(n * stride, torch.uint8)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     _lib.check(_lib.lib().jpeg_amd_resize_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, out.data_ptr(), stride),
                "jpeg_amd_resize_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
@@ -838,6 +844,13 @@ def tensor_spec(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.Te
         spec.mean[c] = 0.0 if mean is None else float(np.float32(255.0 * float(mean[c])))
         spec.scale[c] = 1.0 if std is None else float(np.float32(1.0 / (255.0 * float(std[c]))))
     return spec
+
+
+def _bytes_out(ctx: Context, n: int, out_size):
+    """-> (wt, ht, room for n byte images of out_size [n * 3 wt ht], its stride)."""
+    wt, ht = int(out_size[0]), int(out_size[1])
+    stride = 3 * max(wt, 0) * max(ht, 0)
+    return wt, ht, ctx.empty(n * stride, _torch().uint8), stride
 
 
 def _tensor_out(ctx: Context, n: int, out_size, spec: _lib.TensorSpec, flips):
@@ -886,7 +899,7 @@ def _mixed_args(ctx: Context, spectrals, views):
     `keep` holds what the pointers in the c images point into."""
     torch = _torch()
     spectrals = list(spectrals)
-    vs = np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 5))
+    vs, h_views = _views(views)
     n = vs.shape[0]
     if len(spectrals) != n:
         raise ValueError("views: one (denom, x, y, width, height) per image")
@@ -904,9 +917,6 @@ def _mixed_args(ctx: Context, spectrals, views):
         h_images[i].d_quanta = quanta.data_ptr() + 128 * first
         h_images[i].ntables = len(s.quanta)
         first += len(s.quanta)
-    h_views = (_lib.View * max(n, 1))()
-    for i, row in enumerate(vs.tolist()):
-        h_views[i] = _view(row[0], row[1:])
     return vs, h_images, h_views, (spectrals, quanta)
 
 
@@ -916,13 +926,10 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
     views: [n, 5] of (denom, x, y, width, height), each against its own image.  Image i is what Spectral.view gives for it.
     Returns n uint8 views [h_i, w_i, 3] into one allocation."""
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
-    n = vs.shape[0]
-    areas = [3 * max(int(w), 0) * max(int(h), 0) for w, h in vs[:, 3:5]] if n else [0]
-    stride = max(areas)
-    out = ctx.empty(n * stride, _torch().uint8)
-    _lib.check(_lib.lib().jpeg_amd_decode_view_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, out.data_ptr(),
-                                                     stride), "jpeg_amd_decode_view_mixed", ctx.handle)
-    return [out[i * stride:i * stride + areas[i]].view(int(vs[i, 4]), int(vs[i, 3]), 3) for i in range(n)]
+    out, stride, slices = _views_out(ctx, vs)
+    _lib.check(_lib.lib().jpeg_amd_decode_view_mixed(ctx.handle, vs.shape[0], h_images, 1 if cosite else 0, color.code, h_views,
+                                                     out.data_ptr(), stride), "jpeg_amd_decode_view_mixed", ctx.handle)
+    return slices
 
 
 def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False):
@@ -930,9 +937,7 @@ def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, co
     decode_views_mixed.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
-    wt, ht = int(out_size[0]), int(out_size[1])
-    stride = 3 * max(wt, 0) * max(ht, 0)
-    out = ctx.empty(n * stride, _torch().uint8)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     _lib.check(_lib.lib().jpeg_amd_decode_resized_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
                                                         out.data_ptr(), stride), "jpeg_amd_decode_resized_mixed", ctx.handle)
     return out.view(n, ht, wt, 3)

@@ -739,6 +739,22 @@ int upload_regions(jpeg_amd_ctx *ctx, const std::vector<uint32_t> &buf)
     return JPEG_AMD_OK;
 }
 
+// One launch of a view decode kernel, appended to the words that are staged for it: the index list [m] of its images, then the
+// prefix [m + 1] of their tiles at n samples per block.  *nwg: the launch's workgroups; EINVAL: more of them than a grid holds.
+int stage_group(std::vector<uint32_t> &buf, const std::vector<uint32_t> &members, int n, const jpeg_amd_view *h_views, uint32_t *nwg)
+{
+    buf.insert(buf.end(), members.begin(), members.end());
+    uint64_t acc = 0;
+    for (const uint32_t i : members) {
+        buf.push_back((uint32_t)acc);
+        acc += view_tiles(n, h_views[i].region);
+    }
+    if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;
+    buf.push_back((uint32_t)acc);
+    *nwg = (uint32_t)acc;
+    return JPEG_AMD_OK;
+}
+
 // The regions (int32 [n][4]) and their tile prefix (uint32 [n + 1]) in the context's region buffer, one copy from a host
 // buffer (pageable, so the copy has taken it when the call returns -- as stage_quanta).  Returns the workgroup count.
 int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int32_t **d_regions, const uint32_t **d_tiles,
@@ -1079,8 +1095,8 @@ try {
 
     const size_t n = (size_t)n_images;
     if (fused_decode_supported(*L, cosited != 0)) {
-        // staged in one copy: the rectangles [n][4], then per denominator of the call its index list [m] and tile prefix [m + 1]
-        std::vector<uint32_t> buf(4 * n);
+        // staged in one copy: the rectangles [n][4], then per denominator of the call its group (stage_group)
+        std::vector<uint32_t> buf(4 * n), members;
         for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
         size_t at[kViewDenoms];
         uint32_t nwg[kViewDenoms];
@@ -1088,17 +1104,10 @@ try {
             at[k] = buf.size();
             nwg[k] = 0;
             if (count[k] == 0) continue;
+            members.clear();
             for (size_t i = 0; i < n; ++i)
-                if (view_slot(h_views[i].denom) == k) buf.push_back((uint32_t)i);
-            uint64_t acc = 0;
-            for (size_t i = 0; i < n; ++i) {
-                if (view_slot(h_views[i].denom) != k) continue;
-                buf.push_back((uint32_t)acc);
-                acc += view_tiles(8 >> k, h_views[i].region);
-            }
-            if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
-            buf.push_back((uint32_t)acc);
-            nwg[k] = (uint32_t)acc;
+                if (view_slot(h_views[i].denom) == k) members.push_back((uint32_t)i);
+            JA_TRY(stage_group(buf, members, 8 >> k, h_views, &nwg[k]));
         }
         JA_TRY(upload_regions(ctx, buf));
         const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->region.ptr);
@@ -1178,13 +1187,7 @@ int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t wa
 
 namespace {
 
-constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of jpeg_amd_decode_resized_batch
-
-// The scale factors of the contract: divided here, in binary32, never on the device.
-ResizeRecord resize_record(uint64_t offset, int32_t w, int32_t h, int32_t out_w, int32_t out_h)
-{
-    return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h, 0u, 0u};
-}
+constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of the resized and tensor decodes
 
 // The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
 // returns -- as stage_quanta).
@@ -1197,42 +1200,13 @@ int upload_records(jpeg_amd_ctx *ctx, const std::vector<ResizeRecord> &rec)
 }
 
 // What both resample calls require of the output.
-int check_resize_target(int n_images, int32_t out_w, int32_t out_h, const uint8_t *d_dst, size_t dst_stride)
+int check_resize_target(int n_images, int32_t out_w, int32_t out_h, const void *d_dst, size_t dst_stride)
 {
     if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
     if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
     if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
     if (n_images > 1 && dst_stride < (size_t)3 * out_w * out_h) return JPEG_AMD_EINVAL;
     return JPEG_AMD_OK;
-}
-
-// The chunks of jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch: consecutive images, m images at a stride of the
-// chunk's largest view, at most kResizeChunkBytes in all; rec[i] is image i's record inside its chunk.  Returns the bytes the
-// largest chunk needs.
-struct ResizeChunk { int i0, m; size_t stride; };
-size_t plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const uint8_t *h_flip,
-                          std::vector<ResizeChunk> &chunks, std::vector<ResizeRecord> &rec)
-{
-    size_t need = 0;
-    for (int i0 = 0; i0 < n_images;) {
-        int m = 0;
-        size_t stride = 0;
-        for (; i0 + m < n_images; ++m) {
-            const jpeg_amd_region &r = h_views[i0 + m].region;
-            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
-            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
-            stride = s;
-        }
-        for (int j = 0; j < m; ++j) {
-            const jpeg_amd_region &r = h_views[i0 + j].region;
-            rec[(size_t)(i0 + j)] = resize_record((uint64_t)j * stride, r.width, r.height, out_w, out_h);
-            rec[(size_t)(i0 + j)].flip = h_flip && h_flip[i0 + j] ? 1u : 0u;
-        }
-        chunks.push_back(ResizeChunk{i0, m, stride});
-        need = std::max(need, stride * (size_t)m);
-        i0 += m;
-    }
-    return need;
 }
 
 // What the tensor calls require of the output, beyond jpeg_amd_tensor_extent.
@@ -1247,14 +1221,93 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
     return JPEG_AMD_OK;
 }
 
-}  // namespace
+// Where the resampled images of a call go: bytes (k_resize_bilinear) or, in a tensor call, elements of `spec` (k_resize_tensor).
+// `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.
+struct ResampleTarget {
+    int32_t out_w, out_h;
+    bool tensor;
+    const jpeg_amd_tensor_spec *spec;
+    const uint8_t *h_flip;   // per image, or nullptr: none is mirrored
+    void *d_dst;
+    size_t stride;           // between images, in elements
+    size_t elem_bytes = 1;   // of a tensor call: check() sets it
 
-int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
-                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
-try {
+    int check(int n_images)
+    {
+        return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
+                      : check_resize_target(n_images, out_w, out_h, d_dst, stride);
+    }
+    // Image i of the call, w x h at `offset` bytes from the launch's source.  The scale factors of the contract: divided here,
+    // in binary32, never on the device.
+    ResizeRecord record(int i, uint64_t offset, int32_t w, int32_t h) const
+    {
+        return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h, h_flip && h_flip[i] ? 1u : 0u, 0u};
+    }
+    // Images [i0, i0 + m) of the call, from their records d_rec + i0.
+    hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const ResizeRecord *d_rec, int i0) const
+    {
+        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
+        return tensor ? launch_resize_tensor(stream, m, d_src, d_rec + i0, out_w, out_h, *spec, d_out, stride)
+                      : launch_resize_bilinear(stream, m, d_src, d_rec + i0, out_w, out_h, d_out, stride);
+    }
+};
+
+// The chunks of the resized and tensor decodes: consecutive images, m images at a stride of the chunk's largest view, at most
+// kResizeChunkBytes in all; rec[i] is image i's record inside its chunk; need: the bytes the largest chunk takes.
+struct ResizeChunk { int i0, m; size_t stride; };
+struct ResizePlan {
+    std::vector<ResizeChunk> chunks;
+    std::vector<ResizeRecord> rec;
+    size_t need = 0;
+};
+extern "C++" ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, const ResampleTarget &t)
+{
+    ResizePlan plan;
+    plan.rec.resize((size_t)n_images);
+    for (int i0 = 0; i0 < n_images;) {
+        int m = 0;
+        size_t stride = 0;
+        for (; i0 + m < n_images; ++m) {
+            const jpeg_amd_region &r = h_views[i0 + m].region;
+            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
+            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
+            stride = s;
+        }
+        for (int j = 0; j < m; ++j) {
+            const jpeg_amd_region &r = h_views[i0 + j].region;
+            plan.rec[(size_t)(i0 + j)] = t.record(i0 + j, (uint64_t)j * stride, r.width, r.height);
+        }
+        plan.chunks.push_back(ResizeChunk{i0, m, stride});
+        plan.need = std::max(plan.need, stride * (size_t)m);
+        i0 += m;
+    }
+    return plan;
+}
+
+// The route of every resized and tensor decode, behind its checks and on a bound context: chunk by chunk,
+// decode(c, chunk, d_views) puts the views of chunk c into the context's buffer at the chunk's stride, and the target's launch
+// resamples them from there.  (C++ linkage, here and above: see check_one_view.)
+extern "C++" template <typename Decode>
+int resample_chunks(jpeg_amd_ctx *ctx, const ResizePlan &plan, const ResampleTarget &t, Decode decode)
+{
+    JA_TRY(ensure_buffer(ctx, ctx->resize_src, plan.need));
+    JA_TRY(upload_records(ctx, plan.rec));
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const ResizeChunk &k = plan.chunks[c];
+        JA_TRY(decode(c, k, d_views));
+        JA_HIP(ctx, t.launch(ctx->stream, k.m, d_views, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), k.i0));
+    }
+    return JPEG_AMD_OK;
+}
+
+// jpeg_amd_resize_batch and jpeg_amd_resize_tensor_batch.
+int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride, const jpeg_amd_extent *h_extents,
+                  ResampleTarget t)
+{
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    JA_TRY(check_resize_target(n_images, out_w, out_h, d_dst, dst_stride));
+    JA_TRY(t.check(n_images));
     std::vector<ResizeRecord> rec((size_t)n_images);
     if (n_images > 0) {
         if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
@@ -1262,15 +1315,45 @@ try {
             const jpeg_amd_extent &e = h_extents[i];
             if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
             if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
-            rec[(size_t)i] = resize_record((uint64_t)i * src_stride, e.width, e.height, out_w, out_h);
+            rec[(size_t)i] = t.record(i, (uint64_t)i * src_stride, e.width, e.height);
         }
     }
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
     JA_TRY(upload_records(ctx, rec));
-    JA_HIP(ctx, launch_resize_bilinear(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), out_w,
-                                       out_h, d_dst, dst_stride));
+    JA_HIP(ctx, t.launch(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), 0));
     return JPEG_AMD_OK;
+}
+
+// jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch; c.d_pixels is t.d_dst, and its stride is not looked at.
+int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, ResampleTarget t)
+{
+    // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
+    // ours and always large enough), then what the target refuses
+    DecodeCall views = c;
+    views.pixel_stride = ~(size_t)0;
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
+    JA_TRY(t.check(c.n_images));
+    JA_TRY(bind(ctx));
+    if (c.n_images == 0) return JPEG_AMD_OK;
+    return resample_chunks(ctx, plan_resize_chunks(c.n_images, h_views, t), t, [&](size_t, const ResizeChunk &k, uint8_t *d_views) {
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall part = c.images(k.i0, k.m, coef);
+        return jpeg_amd_decode_view_batch(ctx, c.L, k.m, coef, c.coef_stride, part.d_quanta, c.quanta_stride, c.ntables, c.cosited,
+                                          c.color, h_views + k.i0, d_views, k.stride);
+    });
+}
+
+}  // namespace
+
+int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1280,35 +1363,8 @@ int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, i
                                   int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
                                   int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
-    // ours and always large enough)
-    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
-    DecodeCall views = c;
-    views.pixel_stride = ~(size_t)0;
-    jpeg_amd_layout S[kViewDenoms];
-    int count[kViewDenoms] = {0, 0, 0, 0};
-    bool whole = true;
-    PlaneSet cs{};
-    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
-    JA_TRY(check_resize_target(n_images, out_w, out_h, d_pixels, pixel_stride));
-    JA_TRY(bind(ctx));
-    if (n_images == 0) return JPEG_AMD_OK;
-
-    std::vector<ResizeChunk> chunks;
-    std::vector<ResizeRecord> rec((size_t)n_images);
-    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, nullptr, chunks, rec);
-    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
-    JA_TRY(upload_records(ctx, rec));
-    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
-    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
-    for (const ResizeChunk &k : chunks) {
-        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        const DecodeCall part = c.images(k.i0, k.m, coef);
-        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, k.m, coef, coef_stride, part.d_quanta, quanta_stride, ntables, cosited, color,
-                                          h_views + k.i0, d_views, k.stride));
-        JA_HIP(ctx, launch_resize_bilinear(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, part.d_pixels, pixel_stride));
-    }
-    return JPEG_AMD_OK;
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, 0},
+                            h_views, ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, pixel_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1318,7 +1374,7 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const i
 {
     // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    JA_TRY(check_resize_target(1, out_w, out_h, d_pixels, 0));
+    JA_TRY((ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, 0}.check(1)));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -1344,27 +1400,7 @@ int jpeg_amd_resize_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t 
                                  const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h,
                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
 try {
-    // every argument first, the context last, as jpeg_amd_resize_batch
-    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    size_t elem_bytes = 0;
-    JA_TRY(check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes));
-    std::vector<ResizeRecord> rec((size_t)n_images);
-    if (n_images > 0) {
-        if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
-        for (int i = 0; i < n_images; ++i) {
-            const jpeg_amd_extent &e = h_extents[i];
-            if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
-            if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
-            rec[(size_t)i] = resize_record((uint64_t)i * src_stride, e.width, e.height, out_w, out_h);
-            rec[(size_t)i].flip = h_flip && h_flip[i] ? 1u : 0u;
-        }
-    }
-    JA_TRY(bind(ctx));
-    if (n_images == 0) return JPEG_AMD_OK;
-    JA_TRY(upload_records(ctx, rec));
-    JA_HIP(ctx, launch_resize_tensor(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), out_w,
-                                     out_h, *spec, d_dst, dst_stride));
-    return JPEG_AMD_OK;
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1375,37 +1411,9 @@ int jpeg_amd_decode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
                                  int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
                                  void *d_dst, size_t dst_stride)
 try {
-    // jpeg_amd_decode_resized_batch with another last launch: the same refusals in the same order, the same chunks
-    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
-                       static_cast<uint8_t *>(d_dst), 0};
-    DecodeCall views = c;
-    views.pixel_stride = ~(size_t)0;
-    jpeg_amd_layout S[kViewDenoms];
-    int count[kViewDenoms] = {0, 0, 0, 0};
-    bool whole = true;
-    PlaneSet cs{};
-    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
-    size_t elem_bytes = 0;
-    JA_TRY(check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes));
-    JA_TRY(bind(ctx));
-    if (n_images == 0) return JPEG_AMD_OK;
-
-    std::vector<ResizeChunk> chunks;
-    std::vector<ResizeRecord> rec((size_t)n_images);
-    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, h_flip, chunks, rec);
-    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
-    JA_TRY(upload_records(ctx, rec));
-    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
-    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
-    for (const ResizeChunk &k : chunks) {
-        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
-        const DecodeCall part = c.images(k.i0, k.m, coef);
-        JA_TRY(jpeg_amd_decode_view_batch(ctx, L, k.m, coef, coef_stride, part.d_quanta, quanta_stride, ntables, cosited, color,
-                                          h_views + k.i0, d_views, k.stride));
-        JA_HIP(ctx, launch_resize_tensor(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, *spec,
-                                         static_cast<uint8_t *>(d_dst) + (size_t)k.i0 * dst_stride * elem_bytes, dst_stride));
-    }
-    return JPEG_AMD_OK;
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            static_cast<uint8_t *>(d_dst), 0},
+                            h_views, ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1416,8 +1424,7 @@ int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
 {
     // as jpeg_amd_decode_resized: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    size_t elem_bytes = 0;
-    JA_TRY(check_tensor_target(1, out_w, out_h, spec, d_dst, 0, &elem_bytes));
+    JA_TRY((ResampleTarget{out_w, out_h, true, spec, nullptr, d_dst, 0}.check(1)));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -1434,7 +1441,6 @@ constexpr int kMixedGroups = 2 * kViewDenoms;   // group 2 k + (three planes): t
 // take the uniform call.
 struct MixedPlan {
     std::vector<uint32_t> members[kMixedGroups];   // the group's images, in index order
-    uint32_t nwg[kMixedGroups] = {};
     std::vector<int> fallback;                     // no tile kernel for the layout: the uniform call, image by image
 };
 
@@ -1454,7 +1460,8 @@ int check_mixed_image(const jpeg_amd_image &im, int n_images, int cosited, jpeg_
     return JPEG_AMD_OK;
 }
 
-// The plan of m checked images; EINVAL: a launch of more workgroups than a grid holds.
+// The plan of m checked images; EINVAL: a launch of more workgroups than a grid holds (refused here, before the context is
+// looked at, and so never by run_mixed).
 int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosited, MixedPlan *plan)
 {
     uint64_t acc[kMixedGroups] = {};
@@ -1467,52 +1474,45 @@ int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosi
         plan->members[g].push_back((uint32_t)i);
         acc[g] += view_tiles(8 >> k, v[i].region);
     }
-    for (int g = 0; g < kMixedGroups; ++g) {
+    for (int g = 0; g < kMixedGroups; ++g)
         if (acc[g] > 0x7fffffffu) return JPEG_AMD_EINVAL;
-        plan->nwg[g] = (uint32_t)acc[g];
-    }
     return JPEG_AMD_OK;
 }
 
 // The planned images into d_pixels, image i at i * pixel_stride: one copy of the records [m], then per group its index list
-// and tile prefix, into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when the call
-// returns -- as stage_quanta); a launch per group; the uniform call for each of the others.
+// and tile prefix (stage_group), into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when
+// the call returns -- as stage_quanta); a launch per group; the uniform call for each of the others.
 int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *v, int m, const MixedPlan &plan, int cosited,
               jpeg_amd_color color, uint8_t *d_pixels, size_t pixel_stride)
 {
-    const size_t rec_bytes = mixed_record_bytes(), lists = rec_bytes * (size_t)m;
+    const size_t rec_bytes = mixed_record_bytes(), lists = rec_bytes * (size_t)m / 4;
     size_t words = 0;
     for (int g = 0; g < kMixedGroups; ++g)
         if (!plan.members[g].empty()) words += 2 * plan.members[g].size() + 1;
     if (words != 0) {
-        std::vector<uint8_t> buf(lists + 4 * words);   // the records of the uniform call's images stay zero: no list names them
-        uint32_t *w = reinterpret_cast<uint32_t *>(buf.data() + lists);
-        size_t at[kMixedGroups] = {}, fill = 0;
+        std::vector<uint32_t> buf;
+        buf.reserve(lists + words);
+        buf.resize(lists);   // the records of the uniform call's images stay zero: no list names them
+        size_t at[kMixedGroups] = {};
+        uint32_t nwg[kMixedGroups] = {};
         for (int g = 0; g < kMixedGroups; ++g) {
             const std::vector<uint32_t> &mem = plan.members[g];
             if (mem.empty()) continue;
             const int n = 8 >> (g / 2);
-            at[g] = fill;
-            uint32_t acc = 0;
-            for (size_t j = 0; j < mem.size(); ++j) {
-                const uint32_t i = mem[j];
-                mixed_record(buf.data() + rec_bytes * i, im[i].layout, n, im[i].d_coef, im[i].d_quanta, v[i].region,
-                             d_pixels + (size_t)i * pixel_stride);
-                w[fill + j] = i;
-                w[fill + mem.size() + j] = acc;
-                acc += view_tiles(n, v[i].region);
-            }
-            w[fill + 2 * mem.size()] = acc;
-            fill += 2 * mem.size() + 1;
+            for (const uint32_t i : mem)
+                mixed_record(reinterpret_cast<uint8_t *>(buf.data()) + rec_bytes * i, im[i].layout, n, im[i].d_coef, im[i].d_quanta,
+                             v[i].region, d_pixels + (size_t)i * pixel_stride);
+            at[g] = buf.size();
+            JA_TRY(stage_group(buf, mem, n, v, &nwg[g]));
         }
-        JA_TRY(ensure_buffer(ctx, ctx->mixed, buf.size()));
-        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, buf.data(), buf.size(), hipMemcpyHostToDevice, ctx->stream));
-        const uint32_t *d_w = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(ctx->mixed.ptr) + lists);
+        JA_TRY(ensure_buffer(ctx, ctx->mixed, 4 * buf.size()));
+        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, ctx->stream));
+        const uint32_t *d_w = static_cast<const uint32_t *>(ctx->mixed.ptr);
         for (int g = 0; g < kMixedGroups; ++g) {
             const int count = (int)plan.members[g].size();
             if (count == 0) continue;
             JA_HIP(ctx, launch_view_decode_mixed(ctx->stream, count, 8 >> (g / 2), g % 2 ? 3 : 1, color == JPEG_AMD_COLOR_RGB8,
-                                                 ctx->mixed.ptr, d_w + at[g], d_w + at[g] + count, plan.nwg[g]));
+                                                 ctx->mixed.ptr, d_w + at[g], d_w + at[g] + count, nwg[g]));
         }
     }
     for (const int i : plan.fallback)
@@ -1521,47 +1521,27 @@ int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *
     return JPEG_AMD_OK;
 }
 
-// The resized and the tensor call (spec != nullptr): jpeg_amd_decode_resized_batch's route with the mixed view decode.
+// jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed: decode_resampled's route with the mixed view decode.
 int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                  const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, bool tensor,
-                  const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+                  const jpeg_amd_view *h_views, ResampleTarget t)
 {
     // every argument first, the context last; the target is judged where the uniform call judges it: behind the first image
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
-    size_t elem_bytes = 1;
-    const auto check_target = [&]() {
-        return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, dst_stride, &elem_bytes)
-                      : check_resize_target(n_images, out_w, out_h, static_cast<const uint8_t *>(d_dst), dst_stride);
-    };
     for (int i = 0; i < n_images; ++i) {
-        JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], d_dst, 0));   // the views' stride is ours
-        if (i == 0) JA_TRY(check_target());
+        JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], t.d_dst, 0));   // the views' stride is ours
+        if (i == 0) JA_TRY(t.check(n_images));
     }
-    if (n_images == 0) JA_TRY(check_target());
-    std::vector<ResizeChunk> chunks;
-    std::vector<ResizeRecord> rec((size_t)n_images);
-    const size_t need = plan_resize_chunks(n_images, h_views, out_w, out_h, h_flip, chunks, rec);
-    std::vector<MixedPlan> plans(chunks.size());
-    for (size_t c = 0; c < chunks.size(); ++c)
-        JA_TRY(plan_mixed(h_images + chunks[c].i0, h_views + chunks[c].i0, chunks[c].m, cosited, &plans[c]));
+    if (n_images == 0) JA_TRY(t.check(n_images));
+    const ResizePlan plan = plan_resize_chunks(n_images, h_views, t);
+    std::vector<MixedPlan> plans(plan.chunks.size());
+    for (size_t c = 0; c < plans.size(); ++c)
+        JA_TRY(plan_mixed(h_images + plan.chunks[c].i0, h_views + plan.chunks[c].i0, plan.chunks[c].m, cosited, &plans[c]));
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
     JA_TRY(bind(ctx));
-
-    JA_TRY(ensure_buffer(ctx, ctx->resize_src, need));
-    JA_TRY(upload_records(ctx, rec));
-    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
-    const ResizeRecord *d_rec = static_cast<const ResizeRecord *>(ctx->resize_rec.ptr);
-    for (size_t c = 0; c < chunks.size(); ++c) {
-        const ResizeChunk &k = chunks[c];
-        JA_TRY(run_mixed(ctx, h_images + k.i0, h_views + k.i0, k.m, plans[c], cosited, color, d_views, k.stride));
-        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)k.i0 * dst_stride * elem_bytes;
-        if (tensor)
-            JA_HIP(ctx, launch_resize_tensor(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, *spec, d_out, dst_stride));
-        else
-            JA_HIP(ctx, launch_resize_bilinear(ctx->stream, k.m, d_views, d_rec + k.i0, out_w, out_h, d_out, dst_stride));
-    }
-    return JPEG_AMD_OK;
+    return resample_chunks(ctx, plan, t, [&](size_t c, const ResizeChunk &k, uint8_t *d_views) {
+        return run_mixed(ctx, h_images + k.i0, h_views + k.i0, k.m, plans[c], cosited, color, d_views, k.stride);
+    });
 }
 
 }  // namespace
@@ -1585,8 +1565,8 @@ int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_am
                                   jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                   uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, nullptr, false, nullptr, d_pixels,
-                         pixel_stride);
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, pixel_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1594,7 +1574,8 @@ int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd
                                  jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, spec, true, h_flip, d_dst, dst_stride);
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 

@@ -1,20 +1,15 @@
-// kernels_resize.hip -- bilinear resample of pixel images to one target size (jpeg_amd_resize_batch, and behind
-// jpeg_amd_decode_view_batch in jpeg_amd_decode_resized_batch).  include/jpeg_amd.h ("resized decode") holds the contract:
-// half-pixel centres, the horizontal pass first, every operation one binary32 operation, the scale factors divided on the
-// host.  axis_tap and resample (resample.hpp, shared with k_resize_tensor) are that text, statement by statement.
+// kernels_resize.hip -- bilinear resample of pixel images to one target size, bytes out (jpeg_amd_resize_batch, and behind
+// the view decode in the resized calls).  include/jpeg_amd.h ("resized decode") holds the contract: half-pixel centres, the
+// horizontal pass first, every operation one binary32 operation, the scale factors divided on the host.  The filter, the tile
+// and the head of the arguments are resample.hpp's, shared with k_resize_tensor.
 //
-// k_resize_bilinear: a static grid of (tiles of the output) x (images); the output size is the same for every image, so
-// there is no prefix and no search.  A tile is 64 x 32 output pixels.  Its workgroup
-//   1. writes the tile's per-column (x0, x1, fx) and per-row (y0, y1, fy) into LDS, one work-item per column or row --
-//      they are not computed again per pixel;
-//   2. gives every work-item runs of 4 output pixels of one row (16 work-items across, 16 rows per trip, 2 trips): the four
-//      taps of each channel come straight from the source (byte loads; neighbouring lanes share the lines), the 12 result
-//      bytes are packed into three dwords and leave as dword stores from the first 4-byte boundary of the run on, with
-//      byte stores in front of and behind them (store_run).  Where 3 out_w, dst_stride and d_dst are multiples of 4 --
-//      224 x 224 into a dense tensor -- every full run is three dword stores.
-// Reads stay inside the image (x0, x1 <= w - 1, y0, y1 <= h - 1, both >= 0: the contract clamps them); writes stay inside
-// out_h rows of 3 out_w bytes.  The columns and rows of an edge tile that lie past the output get the taps of index 0 and
-// are never stored.
+// k_resize_bilinear: the walk that resample.hpp describes (resample_walk, never flipped: ResizeRecord::flip is not read),
+// written out here with the packing inside the tap loop.  Through resample_walk, which hands over a finished run, the compiler
+// packs the 12 bytes with four instructions per dword where this text gets three, and the kernel measured 1.3 % slower on the
+// MI355X (profiles/resample_refactor.txt); so this kernel keeps its own text, and a change to the walk is made in both places.
+// The 12 result bytes of a run are packed into three dwords and leave as dword stores from the first 4-byte boundary of the
+// run on, with byte stores in front of and behind them (store_run).  Where 3 out_w, dst_stride and d_dst are multiples of 4 --
+// 224 x 224 into a dense tensor -- every full run is three dword stores.  Writes stay inside out_h rows of 3 out_w bytes.
 //
 // Compile with -ffp-contract=off (see dct.hpp).
 #pragma clang fp contract(off)
@@ -27,11 +22,7 @@ namespace jpeg_amd {
 
 namespace {
 
-struct ResizeArgs {
-    const uint8_t *src;
-    const ResizeRecord *records;
-    int out_w, out_h;
-    FastDiv tiles_x;     // tiles across the output; the reciprocal comes from the host
+struct ResizeArgs : ResampleArgs {
     uint8_t *dst;
     size_t dst_stride;   // bytes between output images
 };
@@ -130,20 +121,12 @@ hipError_t launch_resize_bilinear(hipStream_t stream, int n_images, const uint8_
                                   int out_w, int out_h, uint8_t *d_dst, size_t dst_stride)
 {
     if (n_images == 0) return hipSuccess;
-    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide || n_images < 0 || n_images > 65535)
-        return hipErrorInvalidValue;
-    const uint64_t tiles = resize_tiles(out_w, out_h);
-    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
     ResizeArgs a{};
-    a.src = d_src;
-    a.records = d_records;
-    a.out_w = out_w;
-    a.out_h = out_h;
-    a.tiles_x.d = (uint32_t)((out_w + kTileW - 1) / kTileW);
-    a.tiles_x.m = 0xffffffffu / a.tiles_x.d;
+    dim3 grid;
+    if (const hipError_t e = resample_launch(n_images, d_src, d_records, out_w, out_h, a, grid)) return e;
     a.dst = d_dst;
     a.dst_stride = dst_stride;
-    hipLaunchKernelGGL(k_resize_bilinear, dim3((uint32_t)tiles, (uint32_t)n_images), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(k_resize_bilinear, grid, dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -1,20 +1,17 @@
 // kernels_tensor.hip -- the bilinear resample with the loader's output stage in the same launch (jpeg_amd_resize_tensor_batch,
-// and behind jpeg_amd_decode_view_batch in jpeg_amd_decode_tensor_batch).  include/jpeg_amd.h ("tensor output") holds the
-// contract: the byte u that the resample defines ("resized decode"; axis_tap and resample of resample.hpp are that text, shared
+// and behind the view decode in the tensor calls).  include/jpeg_amd.h ("tensor output") holds the contract: the byte u that
+// the resample defines ("resized decode"; the filter and the walk over the output are resample.hpp's, the filter shared
 // with k_resize_bilinear), then
 //     t = (float)u - mean[c];  v = t * scale[c]          two binary32 operations, nothing contracted, no division
 // and v stored as binary32, or rounded to nearest even to binary16 or bfloat16.
 //
-// k_resize_tensor<T, CHW>: grid, tile (64 x 32 output pixels), LDS tap tables and roles are k_resize_bilinear's.  What differs:
-//   1. the column table is written for the SOURCE column of the stored pixel: the work-item of stored column x computes the
-//      taps of xs = flip ? out_w - 1 - x : x.  A flipped image costs nothing per pixel, and the partial last tile column
-//      needs no case of its own (the columns past out_w get the taps of index 0 and are never stored, as before).
-//   2. the 12 results of a run of 4 pixels stay in registers as elements and leave through store_elems: HWC one run of 12
-//      consecutive elements, CHW three runs of 4.  Element stores up to the first address that is a multiple of 4 elements,
-//      4-element vector stores from there (16 bytes at binary32, 8 bytes at the 16-bit types; two of them merged into one
-//      16-byte store where the address allows), element stores behind the last whole vector.  Any element-aligned base and any
-//      stride are correct; where out_w is a multiple of 4 and d_dst and dst_stride are multiples of 4 elements -- 224 x 224
-//      into a dense tensor -- every run leaves in vector stores only.
+// k_resize_tensor<T, CHW>: resample_walk, flipped where the image's record says so, with the sink that turns the 12 bytes of
+// a run into elements, which stay in registers and leave through store_elems: HWC one run of 12 consecutive elements, CHW
+// three runs of 4.  Element stores up to the first address that is a multiple of 4 elements, 4-element vector stores from
+// there (16 bytes at binary32, 8 bytes at the 16-bit types; two of them merged into one 16-byte store where the address
+// allows), element stores behind the last whole vector.  Any element-aligned base and any stride are correct; where out_w is a
+// multiple of 4 and d_dst and dst_stride are multiples of 4 elements -- 224 x 224 into a dense tensor -- every run leaves in
+// vector stores only.
 // Conversions: binary16 is the compiler's float -> _Float16 conversion of the finished binary32 product (v_cvt_f16_f32, round
 // to nearest even in the default mode; see to_element).  bfloat16 is INTEGER ARITHMETIC ON THE BITS, bits + 0x7fff + ((bits >> 16) & 1), the upper half kept -- not the
 // packed hardware convert: it is the contract's own formula, it needs no inline assembly, and every value here is finite.
@@ -37,11 +34,7 @@ enum class bf16_t : uint16_t {};   // bfloat16 as its bit pattern (a scalar type
 static_assert(sizeof(bf16_t) == 2 && sizeof(_Float16) == 2, "element sizes");
 
 template <typename T>
-struct TensorArgs {
-    const uint8_t *src;
-    const ResizeRecord *records;
-    int out_w, out_h;
-    FastDiv tiles_x;     // tiles across the output; the reciprocal comes from the host
+struct TensorArgs : ResampleArgs {
     float mean[3], scale[3];
     T *dst;
     size_t dst_stride;   // elements between output images
@@ -133,101 +126,41 @@ __device__ __forceinline__ void store_elems(T *p, const T (&v)[N], int n)
 template <typename T, bool CHW>
 __global__ __launch_bounds__(kThreads) void k_resize_tensor(TensorArgs<T> a)
 {
-    __shared__ int cx0[kTileW], cx1[kTileW], ry0[kTileH], ry1[kTileH];
-    __shared__ float cfx[kTileW], rfy[kTileH];
-
-    const int t = threadIdx.x;
-    uint32_t txi;
-    const uint32_t tyi = a.tiles_x.div(blockIdx.x, txi);
-    const int px0 = kTileW * (int)txi, py0 = kTileH * (int)tyi;
-    const ResizeRecord r = a.records[blockIdx.y];
-    if (t < kTileW) {
-        int i0 = 0, i1 = 0;
-        float f = 0.0f;
-        if (px0 + t < a.out_w) axis_tap(r.flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.w, i0, i1, f);
-        cx0[t] = i0; cx1[t] = i1; cfx[t] = f;
-    } else if (t < kTileW + kTileH) {
-        const int u = t - kTileW;
-        int i0 = 0, i1 = 0;
-        float f = 0.0f;
-        if (py0 + u < a.out_h) axis_tap(py0 + u, r.ky, r.h, i0, i1, f);
-        ry0[u] = i0; ry1[u] = i1; rfy[u] = f;
-    }
-    __syncthreads();
-
-    const int ly = t / kLanesX, lx = t - ly * kLanesX;
-    const int x = px0 + kRun * lx;
-    const int npix = min(kRun, a.out_w - x);
-    if (npix <= 0) return;
-    size_t x0[kRun], x1[kRun];
-    float fx[kRun];
-#pragma unroll
-    for (int k = 0; k < kRun; ++k) {
-        x0[k] = (size_t)3 * (uint32_t)cx0[kRun * lx + k];
-        x1[k] = (size_t)3 * (uint32_t)cx1[kRun * lx + k];
-        fx[k] = cfx[kRun * lx + k];
-    }
-    const size_t row_bytes = (size_t)3 * (uint32_t)r.w;
-    const uint8_t *src = a.src + r.offset;
     T *dst = a.dst + (size_t)blockIdx.y * a.dst_stride;
     const size_t plane = (size_t)(uint32_t)a.out_w * (uint32_t)a.out_h;
+    resample_walk(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+        T e[CHW ? 3 : 1][CHW ? kRun : 3 * kRun];   // CHW: three runs of kRun, HWC: one run of 3 kRun
 #pragma unroll
-    for (int u = ly; u < kTileH; u += kRowStep) {
-        const int y = py0 + u;
-        if (y >= a.out_h) break;
-        const uint8_t *r0 = src + (size_t)(uint32_t)ry0[u] * row_bytes, *r1 = src + (size_t)(uint32_t)ry1[u] * row_bytes;
-        const float fy = rfy[u];
+        for (int k = 0; k < kRun; ++k) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float d = (float)o[k][c] - a.mean[c];
+                e[CHW ? c : 0][CHW ? k : 3 * k + c] = to_element<T>(d * a.scale[c]);
+            }
+        }
         const size_t at = (size_t)(uint32_t)y * (uint32_t)a.out_w + (uint32_t)x;
         if constexpr (CHW) {
-            T e[3][kRun];
-#pragma unroll
-            for (int k = 0; k < kRun; ++k) {
-                const uint8_t *pa = r0 + x0[k], *pb = r0 + x1[k], *pc = r1 + x0[k], *pd = r1 + x1[k];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const uint32_t o = resample((float)pa[c], (float)pb[c], (float)pc[c], (float)pd[c], fx[k], fy);
-                    const float d = (float)o - a.mean[c];
-                    e[c][k] = to_element<T>(d * a.scale[c]);
-                }
-            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) store_elems<T, kRun>(dst + c * plane + at, e[c], npix);
         } else {
-            T e[3 * kRun];
-#pragma unroll
-            for (int k = 0; k < kRun; ++k) {
-                const uint8_t *pa = r0 + x0[k], *pb = r0 + x1[k], *pc = r1 + x0[k], *pd = r1 + x1[k];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const uint32_t o = resample((float)pa[c], (float)pb[c], (float)pc[c], (float)pd[c], fx[k], fy);
-                    const float d = (float)o - a.mean[c];
-                    e[3 * k + c] = to_element<T>(d * a.scale[c]);
-                }
-            }
-            store_elems<T, 3 * kRun>(dst + 3 * at, e, 3 * npix);
+            store_elems<T, 3 * kRun>(dst + 3 * at, e[0], 3 * npix);
         }
-    }
+    });
 }
 
 template <typename T, bool CHW>
-hipError_t launch(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records, int out_w, int out_h,
-                  const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride)
+hipError_t launch(hipStream_t stream, const ResampleArgs &head, dim3 grid, const jpeg_amd_tensor_spec &spec, void *d_dst,
+                  size_t dst_stride)
 {
     TensorArgs<T> a{};
-    a.src = d_src;
-    a.records = d_records;
-    a.out_w = out_w;
-    a.out_h = out_h;
-    a.tiles_x.d = (uint32_t)((out_w + kTileW - 1) / kTileW);
-    a.tiles_x.m = 0xffffffffu / a.tiles_x.d;
+    static_cast<ResampleArgs &>(a) = head;
     for (int c = 0; c < 3; ++c) {
         a.mean[c] = spec.mean[c];
         a.scale[c] = spec.scale[c];
     }
     a.dst = static_cast<T *>(d_dst);
     a.dst_stride = dst_stride;
-    hipLaunchKernelGGL((k_resize_tensor<T, CHW>), dim3((uint32_t)resize_tiles(out_w, out_h), (uint32_t)n_images), dim3(kThreads), 0,
-                       stream, a);
+    hipLaunchKernelGGL((k_resize_tensor<T, CHW>), grid, dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -237,21 +170,21 @@ hipError_t launch_resize_tensor(hipStream_t stream, int n_images, const uint8_t 
                                 int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride)
 {
     if (n_images == 0) return hipSuccess;
-    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide || n_images < 0 || n_images > 65535)
-        return hipErrorInvalidValue;
-    if (resize_tiles(out_w, out_h) > 0x7fffffffu) return hipErrorInvalidValue;
+    ResampleArgs head{};
+    dim3 grid;
+    if (const hipError_t e = resample_launch(n_images, d_src, d_records, out_w, out_h, head, grid)) return e;
     const bool chw = spec.layout == JPEG_AMD_TENSOR_CHW;
     if (!chw && spec.layout != JPEG_AMD_TENSOR_HWC) return hipErrorInvalidValue;
     switch (spec.dtype) {
     case JPEG_AMD_F32:
-        return chw ? launch<float, true>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride)
-                   : launch<float, false>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride);
+        return chw ? launch<float, true>(stream, head, grid, spec, d_dst, dst_stride)
+                   : launch<float, false>(stream, head, grid, spec, d_dst, dst_stride);
     case JPEG_AMD_F16:
-        return chw ? launch<_Float16, true>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride)
-                   : launch<_Float16, false>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride);
+        return chw ? launch<_Float16, true>(stream, head, grid, spec, d_dst, dst_stride)
+                   : launch<_Float16, false>(stream, head, grid, spec, d_dst, dst_stride);
     case JPEG_AMD_BF16:
-        return chw ? launch<bf16_t, true>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride)
-                   : launch<bf16_t, false>(stream, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride);
+        return chw ? launch<bf16_t, true>(stream, head, grid, spec, d_dst, dst_stride)
+                   : launch<bf16_t, false>(stream, head, grid, spec, d_dst, dst_stride);
     default:
         return hipErrorInvalidValue;
     }

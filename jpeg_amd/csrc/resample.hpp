@@ -1,12 +1,27 @@
-// resample.hpp -- the bilinear filter of include/jpeg_amd.h ("resized decode"), stated once for the kernels that apply it:
-// k_resize_bilinear (kernels_resize.hip, bytes out) and k_resize_tensor (kernels_tensor.hip, normalised elements out).  Both
-// walk the output in the same tiles with the same roles, so the tile is here too.
+// resample.hpp -- the bilinear filter of include/jpeg_amd.h ("resized decode") and the walk that applies it, for
+// k_resize_bilinear (kernels_resize.hip, bytes out) and k_resize_tensor (kernels_tensor.hip, normalised elements out): the
+// filter, the tile, the head of the kernels' arguments with the host code that fills it, and resample_walk, which computes
+// every run of output bytes of a workgroup's tile and hands it to a sink.  k_resize_tensor is resample_walk with its sink;
+// k_resize_bilinear keeps a text of its own of the same walk (kernels_resize.hip says why), so a change here is made there too.
+//
+// resample_walk: a static grid of (tiles of the output) x (images); the output size is the same for every image, so there is
+// no prefix and no search.  A tile is 64 x 32 output pixels.  Its workgroup
+//   1. writes the tile's per-column (x0, x1, fx) and per-row (y0, y1, fy) into LDS, one work-item per column or row -- they
+//      are not computed again per pixel.  The column table is written for the SOURCE column of the stored pixel: the work-item
+//      of stored column x computes the taps of xs = flip ? out_w - 1 - x : x, so a flipped image costs nothing per pixel and
+//      the partial last tile column needs no case of its own;
+//   2. gives every work-item runs of 4 output pixels of one row (16 work-items across, 16 rows per trip, 2 trips): the four
+//      taps of each channel come straight from the source (byte loads; neighbouring lanes share the lines), and the 12
+//      result bytes go to the sink.
+// Reads stay inside the image (x0, x1 <= w - 1, y0, y1 <= h - 1, both >= 0: the contract clamps them).  The columns and rows
+// of an edge tile that lie past the output get the taps of index 0 and never reach the sink.
 //
 // Compile with -ffp-contract=off (see dct.hpp): every statement below is one binary32 operation.
 #pragma once
 #pragma clang fp contract(off)
 
 #include "fused_common.hpp"
+#include "kernels.hpp"
 
 namespace jpeg_amd {
 
@@ -33,6 +48,91 @@ __device__ __forceinline__ uint32_t resample(float a, float b, float c, float d,
     const float bot = c + fx * (d - c);
     const float v = top + fy * (bot - top);
     return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f);
+}
+
+// What the arguments of both kernels begin with.
+struct ResampleArgs {
+    const uint8_t *src;
+    const ResizeRecord *records;
+    int out_w, out_h;
+    FastDiv tiles_x;     // tiles across the output; the reciprocal comes from the host
+};
+
+// The head and the grid of a launch over n_images > 0 images, or what the launchers refuse.
+inline hipError_t resample_launch(int n_images, const uint8_t *d_src, const ResizeRecord *d_records, int out_w, int out_h,
+                                  ResampleArgs &a, dim3 &grid)
+{
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide || n_images < 0 || n_images > 65535)
+        return hipErrorInvalidValue;
+    const uint64_t tiles = resize_tiles(out_w, out_h);
+    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
+    a.src = d_src;
+    a.records = d_records;
+    a.out_w = out_w;
+    a.out_h = out_h;
+    a.tiles_x.d = (uint32_t)((out_w + kTileW - 1) / kTileW);
+    a.tiles_x.m = 0xffffffffu / a.tiles_x.d;
+    grid = dim3((uint32_t)tiles, (uint32_t)n_images);
+    return hipSuccess;
+}
+
+// The tile blockIdx.x of image blockIdx.y: sink(o, y, x, npix) for every run of the tile, o[k][c] the byte of channel c of the
+// pixel stored at (x + k, y), k < npix <= kRun.  flips: the image's ResizeRecord::flip counts (it is not read otherwise).
+template <typename Sink>
+__device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips, Sink sink)
+{
+    __shared__ int cx0[kTileW], cx1[kTileW], ry0[kTileH], ry1[kTileH];
+    __shared__ float cfx[kTileW], rfy[kTileH];
+
+    const int t = threadIdx.x;
+    uint32_t txi;
+    const uint32_t tyi = a.tiles_x.div(blockIdx.x, txi);
+    const int px0 = kTileW * (int)txi, py0 = kTileH * (int)tyi;
+    const ResizeRecord r = a.records[blockIdx.y];
+    const bool flip = flips && r.flip;
+    if (t < kTileW) {
+        int i0 = 0, i1 = 0;
+        float f = 0.0f;
+        if (px0 + t < a.out_w) axis_tap(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.w, i0, i1, f);
+        cx0[t] = i0; cx1[t] = i1; cfx[t] = f;
+    } else if (t < kTileW + kTileH) {
+        const int u = t - kTileW;
+        int i0 = 0, i1 = 0;
+        float f = 0.0f;
+        if (py0 + u < a.out_h) axis_tap(py0 + u, r.ky, r.h, i0, i1, f);
+        ry0[u] = i0; ry1[u] = i1; rfy[u] = f;
+    }
+    __syncthreads();
+
+    const int ly = t / kLanesX, lx = t - ly * kLanesX;
+    const int x = px0 + kRun * lx;
+    const int npix = min(kRun, a.out_w - x);
+    if (npix <= 0) return;
+    size_t x0[kRun], x1[kRun];
+    float fx[kRun];
+#pragma unroll
+    for (int k = 0; k < kRun; ++k) {
+        x0[k] = (size_t)3 * (uint32_t)cx0[kRun * lx + k];
+        x1[k] = (size_t)3 * (uint32_t)cx1[kRun * lx + k];
+        fx[k] = cfx[kRun * lx + k];
+    }
+    const size_t row_bytes = (size_t)3 * (uint32_t)r.w;
+    const uint8_t *src = a.src + r.offset;
+#pragma unroll
+    for (int u = ly; u < kTileH; u += kRowStep) {
+        const int y = py0 + u;
+        if (y >= a.out_h) break;
+        const uint8_t *r0 = src + (size_t)(uint32_t)ry0[u] * row_bytes, *r1 = src + (size_t)(uint32_t)ry1[u] * row_bytes;
+        const float fy = rfy[u];
+        uint32_t o[kRun][3];
+#pragma unroll
+        for (int k = 0; k < kRun; ++k) {
+            const uint8_t *pa = r0 + x0[k], *pb = r0 + x1[k], *pc = r1 + x0[k], *pd = r1 + x1[k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[k][c] = resample((float)pa[c], (float)pb[c], (float)pc[c], (float)pd[c], fx[k], fy);
+        }
+        sink(o, y, x, npix);
+    }
 }
 
 }  // namespace jpeg_amd

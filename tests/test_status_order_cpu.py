@@ -3,7 +3,9 @@ pointers is called with a NULL context (bind then returns EINVAL before any HIP 
 one of them valid and the others wrong in one more way.  Most entry points look at the context first and so answer EINVAL
 whatever else is wrong; the view, resized and resize calls judge everything else first, and there the layout's verdict
 (ENOSUP for 12 bits) comes through.  The expected statuses are not reasoned out: they are what the library returned before
-the argument handling of capi.hip was gathered into one record, so a change of the order of checks shows here."""
+the argument handling of capi.hip was gathered into one record, so a change of the order of checks shows here.  A second
+table holds calls that are wrong twice, in the view (ENOSUP) and in the target (EINVAL): there the order between the two
+checks shows, and what an empty call answers without a context."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +14,7 @@ import pytest
 from _calls import c_layout
 from jpeg_amd import _lib
 
-EINVAL, ENOSUP = -1, -5                                            # JPEG_AMD_EINVAL, JPEG_AMD_ENOSUP, as literals
+OK, EINVAL, ENOSUP = 0, -1, -5                                     # JPEG_AMD_OK, _EINVAL, _ENOSUP, as literals
 CASES = ("valid", "null layout", "12-bit layout", "two planes", "n_images = -1", "bad denominator or empty region")
 
 
@@ -37,6 +39,21 @@ class Args:
         self.view = _lib.View(self.denom, _lib.Region(0, 0, 4, 4))
         self.extent = _lib.Extent(4, 4)
         self.r, self.v, self.e = C.byref(self.region), C.byref(self.view), C.byref(self.extent)
+        self.spec = _lib.TensorSpec(_lib.F32, _lib.TENSOR_HWC, (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1))
+        self.s = C.byref(self.spec)
+        # the mixed calls: the layout lies inside the image, so "null layout" is a null image array there
+        self.image = image(self.layout, self.p)
+        self.im = None if case == "null layout" else C.byref(self.image)
+
+
+def image(layout, p):
+    """struct jpeg_amd_image of `layout` with the pointer p for every plane and for its two tables."""
+    im = _lib.Image()
+    im.layout = layout
+    for c in range(layout.nplanes):
+        im.d_coef[c] = p
+    im.d_quanta, im.ntables = p, 2
+    return im
 
 
 RGB = _lib.COLOR_RGB8
@@ -53,6 +70,12 @@ CALLS = {
     "jpeg_amd_decode_resized_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.p, 768),
     "jpeg_amd_decode_resized": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 8, 8, a.p),
     "jpeg_amd_resize_batch": lambda a: (a.n, a.p, 48, a.e, 8, 8, a.p, 192),
+    "jpeg_amd_resize_tensor_batch": lambda a: (a.n, a.p, 48, a.e, 8, 8, a.s, None, a.p, 192),
+    "jpeg_amd_decode_tensor_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192),
+    "jpeg_amd_decode_tensor": lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 8, 8, a.s, 0, a.p),
+    "jpeg_amd_decode_view_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, a.p, 768),
+    "jpeg_amd_decode_resized_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, a.p, 768),
+    "jpeg_amd_decode_tensor_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192),
     "jpeg_amd_encode_batch": lambda a: (a.L, a.n, a.p, 768, RGB, a.p, 64, 2, a.pp, a.sz),
     "jpeg_amd_encode": lambda a: (a.L, a.p, RGB, a.p, 2, a.pp),
     "jpeg_amd_spectral_rectangular_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, a.p, 768),
@@ -92,6 +115,12 @@ EXPECTED = {
     "jpeg_amd_decode_resized_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_decode_resized": (EINVAL, EINVAL, ENOSUP, EINVAL, _, EINVAL),
     "jpeg_amd_resize_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_resize_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_tensor_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor": (EINVAL, EINVAL, ENOSUP, EINVAL, _, EINVAL),
+    "jpeg_amd_decode_view_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_resized_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_encode_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
     "jpeg_amd_encode": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
     "jpeg_amd_spectral_rectangular_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
@@ -132,3 +161,68 @@ def statuses(name):
 def test_status_of_a_refused_call(name):
     assert statuses(name) == EXPECTED[name]
 
+
+
+def two_images(first_12_bit):
+    """(keep, image array, view array) of two images, one of them of 12 bits: the first, or the second behind a valid one."""
+    a = [Args("12-bit layout" if (i == 0) == first_12_bit else "valid") for i in range(2)]
+    images = (_lib.Image * 2)(a[0].image, a[1].image)
+    views = (_lib.View * 2)(a[0].view, a[1].view)
+    return a, images, views
+
+
+def mixed_twice(name, first_12_bit):
+    """The mixed resized or tensor call on two_images with out_w = 0."""
+    a, images, views = two_images(first_12_bit)
+    tail = (a[0].s, None, a[0].p, 192) if "tensor" in name else (a[0].p, 768)
+    return getattr(_lib.lib(), name)(None, 2, images, 0, RGB, views, 0, 8, *tail)
+
+
+def call(name, case, args):
+    a = Args(case)
+    return getattr(_lib.lib(), name)(None, *args(a))
+
+
+# Calls that are wrong twice, and empty calls: description -> (the call, the status of the library before the change).
+T12 = "12-bit layout"
+TWICE = {
+    "resized batch, 12 bits and out_w = 0":
+        (lambda: call("jpeg_amd_decode_resized_batch", T12, lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 0, 8, a.p, 768)), ENOSUP),
+    "tensor batch, 12 bits and out_w = 0":
+        (lambda: call("jpeg_amd_decode_tensor_batch", T12,
+                      lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 0, 8, a.s, None, a.p, 192)), ENOSUP),
+    "resized, 12 bits and out_w = 0":
+        (lambda: call("jpeg_amd_decode_resized", T12, lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 0, 8, a.p)), ENOSUP),
+    "tensor, 12 bits and out_w = 0":
+        (lambda: call("jpeg_amd_decode_tensor", T12, lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 0, 8, a.s, 0, a.p)), ENOSUP),
+    "tensor batch, 12 bits and a null spec":
+        (lambda: call("jpeg_amd_decode_tensor_batch", T12,
+                      lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, None, None, a.p, 192)), ENOSUP),
+    "tensor, 12 bits and a null spec":
+        (lambda: call("jpeg_amd_decode_tensor", T12, lambda a: (a.L, a.pp, a.p, 2, 0, RGB, a.v, 8, 8, None, 0, a.p)), ENOSUP),
+    "resized mixed, image 0 of 12 bits and out_w = 0": (lambda: mixed_twice("jpeg_amd_decode_resized_mixed", True), ENOSUP),
+    "resized mixed, image 1 of 12 bits and out_w = 0": (lambda: mixed_twice("jpeg_amd_decode_resized_mixed", False), EINVAL),
+    "tensor mixed, image 0 of 12 bits and out_w = 0": (lambda: mixed_twice("jpeg_amd_decode_tensor_mixed", True), ENOSUP),
+    "tensor mixed, image 1 of 12 bits and out_w = 0": (lambda: mixed_twice("jpeg_amd_decode_tensor_mixed", False), EINVAL),
+    "resize batch, empty":
+        (lambda: call("jpeg_amd_resize_batch", "valid", lambda a: (0, a.p, 48, a.e, 8, 8, a.p, 192)), EINVAL),
+    "resize tensor batch, empty":
+        (lambda: call("jpeg_amd_resize_tensor_batch", "valid", lambda a: (0, a.p, 48, a.e, 8, 8, a.s, None, a.p, 192)), EINVAL),
+    "resized batch, empty":
+        (lambda: call("jpeg_amd_decode_resized_batch", "valid", lambda a: (a.L, 0, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.p, 768)), EINVAL),
+    "tensor batch, empty":
+        (lambda: call("jpeg_amd_decode_tensor_batch", "valid",
+                      lambda a: (a.L, 0, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192)), EINVAL),
+    "view mixed, empty":
+        (lambda: call("jpeg_amd_decode_view_mixed", "valid", lambda a: (0, a.im, 0, RGB, a.v, a.p, 768)), OK),
+    "resized mixed, empty":
+        (lambda: call("jpeg_amd_decode_resized_mixed", "valid", lambda a: (0, a.im, 0, RGB, a.v, 8, 8, a.p, 768)), OK),
+    "tensor mixed, empty":
+        (lambda: call("jpeg_amd_decode_tensor_mixed", "valid", lambda a: (0, a.im, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192)), OK),
+}
+
+
+@pytest.mark.parametrize("what", sorted(TWICE))
+def test_status_of_a_call_that_is_wrong_twice_or_empty(what):
+    run, want = TWICE[what]
+    assert run() == want

@@ -689,8 +689,9 @@ int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t wa
  * (y0, x0), (y0, x1), (y1, x0), (y1, x1) converted to float -- the horizontal pass first, then the vertical pass:
  *   top = a + fx * (b - a);  bot = c + fx * (d - c);  v = top + fy * (bot - top)
  *   out = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
- * There is no antialiasing filter: with a denominator from jpeg_amd_view_denom what is left to reduce is below 2 per axis
- * unless the source is more than 8 times the target.  out_w == w and out_h == h give the source bytes (sx = j, fx = 0).
+ * There is no antialiasing filter in these calls ("antialiased resample" below has them with one): with a denominator
+ * from jpeg_amd_view_denom what is left to reduce is below 2 per axis unless the source is more than 8 times the target.
+ * out_w == w and out_h == h give the source bytes (sx = j, fx = 0).
  * Upscaling is the same formula. */
 typedef struct jpeg_amd_extent {
     int32_t width, height;
@@ -828,6 +829,72 @@ int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_am
 int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
                                  jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride);
+
+/* ---- antialiased resample: a second filter for the resized, tensor and mixed calls ----------------------
+ * The bilinear filter of "resized decode" reads two source samples per axis whatever the reduction, so it aliases as soon as
+ * a source is larger than the target.  This is the triangle filter WIDENED BY THE SCALE FACTOR, the filter that
+ * torch.nn.functional.interpolate(mode="bilinear", antialias=True) and PIL's BILINEAR compute.  THE CONTRACT (the one
+ * statement of it), every statement ONE binary32 operation, nothing contracted:
+ *
+ * Per axis, for n source samples, n_out outputs and output index j:
+ *   k  = (float)n / (float)n_out          on the host, per image, as in "resized decode"
+ *   s  = max(k, 1.0f)                     on the host
+ *   r  = 1.0f / s                         on the host: the kernel is handed k, s and r
+ *   c  = ((float)j + 0.5f) * k
+ *   lo = max((int)((c - s) + 0.5f), 0)
+ *   hi = min((int)((c + s) + 0.5f), n)    taps t = lo .. hi - 1, at least one
+ *   u_t = (((float)t - c) + 0.5f) * r
+ *   w_t = max(1.0f - fabsf(u_t), 0.0f)
+ *   total = w_lo + w_(lo+1) + ...         left to right, ascending t
+ *   W_t = w_t / total                     IEEE-754 correctly rounded binary32 division
+ * The division happens once per output column and once per output row of a tile of the kernel, never per pixel; the library
+ * is built without fast-math and with the compiler's default, correctly rounded, division.
+ * Per channel, with p(y, t) the source byte converted to float -- the horizontal pass first, its result kept as a float:
+ *   h(y) = (...((0.0f + W_lo * p(y, lo)) + W_(lo+1) * p(y, lo+1)) + ...)      x taps ascending; a product, then a sum
+ *   v    = (...((0.0f + Wy_lo * h(lo)) + Wy_(lo+1) * h(lo+1)) + ...)          y taps ascending
+ *   out  = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
+ * out_w == w and out_h == h give the source bytes (the weights are 1 and 0).  Upscaling is the same formula with s = 1.
+ * The tensor output is unchanged: with u(i, y, x, c) this byte, "tensor output" applies as it stands -- the flip of the
+ * RESAMPLED image, minus mean, times scale, one rounding.
+ *
+ * THE LIMIT.  s <= 16 per axis keeps the taps of an output at 33 or fewer (the interval has length 2 s).  An image whose kx
+ * or ky, as computed above in binary32, exceeds 16.0f makes the whole call JPEG_AMD_ENOSUP: after everything the bilinear
+ * form of the same call refuses and before the context is touched, by the first offending image in index order; nothing is
+ * written and the context stays usable.  Behind a denominator of 8 that is a reduction of 128 per axis.
+ *
+ * THE CALLS.  Each takes exactly the arguments of the call it is named after, with `filter` directly after out_h.
+ * JPEG_AMD_FILTER_BILINEAR is, bit for bit and status for status, that call.  Any other value of `filter` than the two below
+ * is EINVAL.  There are no single-image forms: n_images == 1 serves.
+ * Cost: the route of the call it is named after, with the antialiasing kernel in the place of the bilinear one.  That
+ * kernel reads every source pixel of an output tile's footprint once per tile (the bilinear one reads four per output
+ * pixel), so its time grows with kx ky. */
+enum { JPEG_AMD_FILTER_BILINEAR = 0, JPEG_AMD_FILTER_ANTIALIAS = 1 };
+
+int jpeg_amd_resize_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                 uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_resize_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                                        size_t dst_stride);
+int jpeg_amd_decode_resized_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                         const int16_t *const d_coef[], const size_t coef_stride[],
+                                         const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                         int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                         int32_t out_w, int32_t out_h, int filter, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                        const int16_t *const d_coef[], const size_t coef_stride[],
+                                        const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                        int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                        int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                        const uint8_t *h_flip, void *d_dst, size_t dst_stride);
+int jpeg_amd_decode_resized_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                         int filter, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                                        size_t dst_stride);
 
 /* ---- spectral reduce: a Spectral at 1/2, 1/4 or 1/8 size, coefficients in and coefficients out ----------
  * JPEG in, smaller JPEG out, without pixels in between: no interleave, no colour conversion and no second generation of

@@ -142,6 +142,7 @@ struct layout {
 };
 
 enum class color { ycbcr = JPEG_AMD_COLOR_YCC8, rgb = JPEG_AMD_COLOR_RGB8 };
+enum class filter { bilinear = JPEG_AMD_FILTER_BILINEAR, antialias = JPEG_AMD_FILTER_ANTIALIAS };  // of the resample
 using quanta_map = std::map<int, std::vector<uint16_t>>;  // quanta key -> 64 zigzag values
 
 class planar;
@@ -338,6 +339,23 @@ class spectral {
                                       cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, px.data()), "jpeg_amd_decode_resized");
         return px.host();
     }
+    /// ... resampled by `f`: filter::antialias is the triangle filter widened by the scale factor (jpeg_amd.h, "antialiased
+    /// resample"), which refuses a view more than 16 times the target on an axis (JPEG_AMD_ENOSUP); filter::bilinear is the
+    /// call above.  The C ABI has no single-image form with a filter: the tables are uploaded and the batch call runs on one image
+    std::vector<uint8_t> decode_resized(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h, filter f, bool cosite = false) const
+    {
+        if (f == filter::bilinear) return decode_resized(target, view, out_w, out_h, cosite);
+        jpeg_amd_layout l = lay.c_layout(size, units, q);
+        const size_t w = out_w > 0 ? out_w : 0, h = out_h > 0 ? out_h : 0;
+        device_array<uint8_t> px(*ctx, 3 * w * h);
+        device_array<uint16_t> dq(*ctx, tables);
+        auto in = detail::pointers(planes);
+        const size_t one_image[JPEG_AMD_MAX_PLANES] = {};
+        check(jpeg_amd_decode_resized_filter_batch(ctx->handle(), &l, 1, const_cast<const int16_t *const *>(in.data()), one_image, dq.data(),
+                                                   0, ntables(), cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, (int)f,
+                                                   px.data(), 0), "jpeg_amd_decode_resized_filter_batch");
+        return px.host();
+    }
     /// decode_resized(target, view, out_w, out_h, cosite) through the output stage of `spec`, mirrored along x if `flip`:
     /// the raw bytes of the 3 * out_w * out_h elements in spec's dtype and layout (jpeg_amd.h, "tensor output")
     std::vector<uint8_t> decode_tensor(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h,
@@ -351,6 +369,24 @@ class spectral {
         check(jpeg_amd_decode_tensor(ctx->handle(), &l, const_cast<const int16_t *const *>(in.data()), tables.data(), ntables(),
                                      cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, &spec, flip ? 1 : 0, px.data()),
               "jpeg_amd_decode_tensor");
+        return px.host();
+    }
+    /// ... with the resample's filter chosen, as decode_resized's
+    std::vector<uint8_t> decode_tensor(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h,
+                                       const jpeg_amd_tensor_spec &spec, filter f, bool flip = false, bool cosite = false) const
+    {
+        if (f == filter::bilinear) return decode_tensor(target, view, out_w, out_h, spec, flip, cosite);
+        jpeg_amd_layout l = lay.c_layout(size, units, q);
+        size_t elem_bytes = 0, elems = 0;
+        check(jpeg_amd_tensor_extent(&spec, out_w, out_h, &elem_bytes, &elems), "jpeg_amd_tensor_extent");
+        device_array<uint8_t> px(*ctx, elem_bytes * elems);
+        device_array<uint16_t> dq(*ctx, tables);
+        auto in = detail::pointers(planes);
+        const size_t one_image[JPEG_AMD_MAX_PLANES] = {};
+        const uint8_t h_flip = flip ? 1 : 0;
+        check(jpeg_amd_decode_tensor_filter_batch(ctx->handle(), &l, 1, const_cast<const int16_t *const *>(in.data()), one_image, dq.data(),
+                                                  0, ntables(), cosite ? 1 : 0, (jpeg_amd_color)target, &view, out_w, out_h, (int)f, &spec,
+                                                  &h_flip, px.data(), 0), "jpeg_amd_decode_tensor_filter_batch");
         return px.host();
     }
 

@@ -141,6 +141,17 @@ SIGNATURES = {
     "jpeg_amd_decode_view_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, C.c_size_t]),
     "jpeg_amd_decode_resized_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, C.c_size_t]),
     "jpeg_amd_decode_tensor_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_resize_filter_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, C.c_size_t]),
+    "jpeg_amd_resize_filter_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, _p,
+                                                      C.c_size_t]),
+    "jpeg_amd_decode_resized_filter_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p,
+                                                       C.c_int32, C.c_int32, C.c_int, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_filter_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p,
+                                                      C.c_int32, C.c_int32, C.c_int, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_resized_filter_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p,
+                                                       C.c_size_t]),
+    "jpeg_amd_decode_tensor_filter_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                      _p, C.c_size_t]),
     "jpeg_amd_reduce_layout": (C.c_int, [_L, C.c_int, _L]),
     "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
     "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
@@ -175,6 +186,7 @@ class TensorSpec(C.Structure):
 
 F32, F16, BF16 = 0, 1, 2                # JPEG_AMD_F32 ...
 TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
+FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V
 XFORM_TRANSPOSE, XFORM_FLIP_H, XFORM_FLIP_V = 1, 2, 4

@@ -266,18 +266,28 @@ class Spectral:
             1 if cosite else 0, color.code, out.data_ptr()), "jpeg_amd_decode", self.ctx.handle)
         return out.view(-1, 3)
 
-    def view(self, region, scale: int, color=RGB, cosite: bool = False, size=None):
+    def view(self, region, scale: int, color=RGB, cosite: bool = False, size=None, filter: str = "bilinear"):
         """The image at 1/scale size (scale 1 | 2 | 4 | 8, as decode(scale=)) cropped to region (x, y, width, height) in
         pixels of THAT image, any alignment, bit for bit, as uint8 [height, width, 3] (jpeg_amd_decode_view).  view_of_source
         turns a rectangle of the full-size image into such a region, view_denom picks the scale for a target size.
-        size (Wt, Ht): that view bilinearly resampled to Wt x Ht, as uint8 [Ht, Wt, 3] (jpeg_amd_decode_resized)."""
+        size (Wt, Ht): that view bilinearly resampled to Wt x Ht, as uint8 [Ht, Wt, 3] (jpeg_amd_decode_resized);
+        filter="antialias": resampled with the antialiasing filter instead (jpeg_amd_decode_resized_filter_batch on one
+        image, the tables uploaded first)."""
         torch = _torch()
         L = self._layout()
         qarr, qptr = _quanta_array(self.quanta)
         v = _view(scale, region)
+        code = _filter(filter)
         if size is not None:
             wt, ht = int(size[0]), int(size[1])
             out = self.ctx.empty(max(wt, 0) * max(ht, 0) * 3, torch.uint8)
+            if code != _lib.FILTER_BILINEAR:
+                dq = self.ctx.upload(np.stack(self.quanta).astype(np.uint16))
+                _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_batch(
+                    self.ctx.handle, C.byref(L), 1, _ptrs(self.planes), _lib.size_array([0] * _lib.MAX_PLANES), dq.data_ptr(), 0,
+                    len(self.quanta), 1 if cosite else 0, color.code, C.byref(v), wt, ht, code, out.data_ptr(), 0),
+                    "jpeg_amd_decode_resized_filter_batch", self.ctx.handle)
+                return out.view(ht, wt, 3)
             _lib.check(_lib.lib().jpeg_amd_decode_resized(
                 self.ctx.handle, C.byref(L), _ptrs(self.planes), qptr, len(self.quanta),
                 1 if cosite else 0, color.code, C.byref(v), wt, ht, out.data_ptr()), "jpeg_amd_decode_resized", self.ctx.handle)
@@ -738,6 +748,15 @@ def view_denom(source_size, want_size) -> int:
     return int(_lib.lib().jpeg_amd_view_denom(int(source_size[0]), int(source_size[1]), int(want_size[0]), int(want_size[1])))
 
 
+def _filter(filter) -> int:
+    """filter="bilinear" | "antialias" of the resample calls -> 0 for the bilinear filter, whose calls are the entry points
+    without a filter argument, or the JPEG_AMD_FILTER_* code for the *_filter_* entry points."""
+    codes = {"bilinear": _lib.FILTER_BILINEAR, "antialias": _lib.FILTER_ANTIALIAS}
+    if filter not in codes:
+        raise ValueError("filter: 'bilinear' or 'antialias'")
+    return codes[filter]
+
+
 def _view_batch_args(ctx: Context, size, layout: Layout, planes, quanta, views, q):
     """The arguments decode_views, decode_resized and decode_tensors share: (vs [n, 5], head and keep of _batch_args, c views)."""
     vs, h_views = _views(views)
@@ -767,13 +786,20 @@ def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: O
 
 
 def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, q: Optional[Sequence[int]] = None,
-                   color=RGB, cosite: bool = False):
+                   color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """decode_views with every image bilinearly resampled to out_size (Wt, Ht), in one call
-    (jpeg_amd_decode_resized_batch; include/jpeg_amd.h holds the filter's contract).  Arguments as decode_views.  Returns one
-    uint8 tensor [n, Ht, Wt, 3]."""
+    (jpeg_amd_decode_resized_batch; include/jpeg_amd.h holds the filter's contract).  Arguments as decode_views.
+    filter="antialias": the antialiasing filter instead ("antialiased resample" there; jpeg_amd_decode_resized_filter_batch),
+    which refuses a view more than 16 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    code = _filter(filter)
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                                   code, out.data_ptr(), stride),
+                   "jpeg_amd_decode_resized_filter_batch", ctx.handle)
+        return out.view(n, ht, wt, 3)
     _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
                                                         out.data_ptr(), stride), "jpeg_amd_decode_resized_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
@@ -790,13 +816,14 @@ def _crop_views(size, source_regions, out_size) -> np.ndarray:
 
 
 def decode_crops_resized(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size,
-                         q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+                         q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """The data-loader call: per image a rectangle (x, y, width, height) of the FULL-SIZE image, decoded at the cheapest
     denominator that is still no smaller than out_size -- view_denom((width, height), out_size), then view_of_source -- and
-    resampled to out_size (Wt, Ht) by decode_resized.  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
+    resampled to out_size (Wt, Ht) by decode_resized, with its `filter` (the denominator is chosen the same way for both
+    filters).  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
     [n, 5] of (denom, x, y, width, height))."""
     views = _crop_views(size, source_regions, out_size)
-    return decode_resized(ctx, size, layout, planes, quanta, views, out_size, q=q, color=color, cosite=cosite), views
+    return decode_resized(ctx, size, layout, planes, quanta, views, out_size, q=q, color=color, cosite=cosite, filter=filter), views
 
 
 def _pack_images(ctx: Context, images):
@@ -815,13 +842,20 @@ def _pack_images(ctx: Context, images):
     return src, src_stride, extents
 
 
-def resize(ctx: Context, images, out_size):
+def resize(ctx: Context, images, out_size, filter: str = "bilinear"):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
-    (jpeg_amd_resize_batch).  The images are packed into one allocation first (torch copies).  Returns uint8 [n, Ht, Wt, 3]."""
+    (jpeg_amd_resize_batch), or with filter="antialias" through the antialiasing filter (jpeg_amd_resize_filter_batch; no
+    image more than 16 times the target on an axis).  The images are packed into one allocation first (torch copies).
+    Returns uint8 [n, Ht, Wt, 3]."""
+    code = _filter(filter)
     images = list(images)
     n = len(images)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                           out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
+        return out.view(n, ht, wt, 3)
     _lib.check(_lib.lib().jpeg_amd_resize_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, out.data_ptr(), stride),
                "jpeg_amd_resize_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
@@ -873,25 +907,32 @@ def _tensor_view(out, n, wt, ht, spec):
 
 
 def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, spec: _lib.TensorSpec, flips=None,
-                   q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+                   q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """decode_resized with the loader's tail in the same call (jpeg_amd_decode_tensor_batch; include/jpeg_amd.h, "tensor
     output", holds the contract): every view resampled to out_size (Wt, Ht), mirrored along x where flips[i] is set,
-    normalised by `spec` (tensor_spec) and stored in its dtype and layout.  Returns one tensor [n, 3, Ht, Wt] ("chw") or
-    [n, Ht, Wt, 3] ("hwc")."""
+    normalised by `spec` (tensor_spec) and stored in its dtype and layout; `filter` as in decode_resized
+    (jpeg_amd_decode_tensor_filter_batch).  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    code = _filter(filter)
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                                  code, C.byref(spec), h_flip, out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_filter_batch", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec)
     _lib.check(_lib.lib().jpeg_amd_decode_tensor_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht, C.byref(spec),
                                                        h_flip, out.data_ptr(), stride), "jpeg_amd_decode_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 
 def decode_crops_tensor(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size, spec: _lib.TensorSpec,
-                        flips=None, q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False):
+                        flips=None, q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """The data-loader call, to the tensor a training loop takes: the views decode_crops_resized chooses for the rectangles
     (x, y, width, height) of the FULL-SIZE images, through decode_tensors.  Returns (tensor, the views as int32 [n, 5])."""
     views = _crop_views(size, source_regions, out_size)
-    return decode_tensors(ctx, size, layout, planes, quanta, views, out_size, spec, flips=flips, q=q, color=color, cosite=cosite), views
+    return decode_tensors(ctx, size, layout, planes, quanta, views, out_size, spec, flips=flips, q=q, color=color, cosite=cosite,
+                          filter=filter), views
 
 
 def _mixed_args(ctx: Context, spectrals, views):
@@ -932,24 +973,38 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
     return slices
 
 
-def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False):
-    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_mixed); arguments as
-    decode_views_mixed.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear"):
+    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_mixed, or with
+    filter="antialias" jpeg_amd_decode_resized_filter_mixed); arguments as decode_views_mixed.  Returns one uint8 tensor
+    [n, Ht, Wt, 3]."""
+    code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                   ht, code, out.data_ptr(), stride),
+                   "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
+        return out.view(n, ht, wt, 3)
     _lib.check(_lib.lib().jpeg_amd_decode_resized_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
                                                         out.data_ptr(), stride), "jpeg_amd_decode_resized_mixed", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                         cosite: bool = False):
-    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_mixed); arguments as
-    decode_views_mixed, then as decode_tensors.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+                         cosite: bool = False, filter: str = "bilinear"):
+    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_mixed, or with
+    filter="antialias" jpeg_amd_decode_tensor_filter_mixed); arguments as decode_views_mixed, then as decode_tensors.
+    Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                  ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec)
     _lib.check(_lib.lib().jpeg_amd_decode_tensor_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
                                                        C.byref(spec), h_flip, out.data_ptr(), stride),
                "jpeg_amd_decode_tensor_mixed", ctx.handle)
@@ -957,7 +1012,7 @@ def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.Te
 
 
 def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                              cosite: bool = False):
+                              cosite: bool = False, filter: str = "bilinear"):
     """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
     full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
     size -- through decode_tensors_mixed.  Returns (tensor, the views as int32 [n, 5])."""
@@ -968,16 +1023,23 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
     views = np.empty((len(spectrals), 5), np.int32)
     for i, s in enumerate(spectrals):
         views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
-    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite), views
+    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter), views
 
 
-def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None):
-    """The resample and the output stage alone (jpeg_amd_resize_tensor_batch): n device uint8 images [h_i, w_i, 3] of any
-    sizes to one tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3] of spec's dtype, in one launch."""
+def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear"):
+    """The resample and the output stage alone (jpeg_amd_resize_tensor_batch, or with filter="antialias"
+    jpeg_amd_resize_filter_tensor_batch): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
+    [n, Ht, Wt, 3] of spec's dtype, in one launch."""
+    code = _filter(filter)
     images = list(images)
     n = len(images)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if code != _lib.FILTER_BILINEAR:
+        _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                                  C.byref(spec), h_flip, out.data_ptr(), stride),
+                   "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec)
     _lib.check(_lib.lib().jpeg_amd_resize_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, C.byref(spec), h_flip,
                                                        out.data_ptr(), stride), "jpeg_amd_resize_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)

@@ -1,0 +1,167 @@
+// antialias.hpp -- the antialiasing filter of include/jpeg_amd.h ("antialiased resample") and the walk that applies it, for
+// k_antialias_bytes and k_antialias_tensor (kernels_antialias.hip): the triangle filter widened by the scale factor, whose
+// footprint per output pixel is up to 33 x 33 source pixels.  The tile, the grid and the head of the arguments are
+// resample.hpp's: (tiles of 64 x 32 output pixels) x (images), no prefix and no search.
+//
+// antialias_walk: the workgroup of a tile
+//   1. TABLES.  Writes the tile's per-column and per-row (lo, count, W[count]) into LDS, one work-item per column or row: the
+//      weights, their ascending sum and the one division per weight happen here and nowhere else.  The column table is written
+//      for the SOURCE column of the stored pixel (xs = flip ? out_w - 1 - x : x), so a flipped image costs nothing per pixel.
+//      Columns and rows of an edge tile that lie past the output get a count of 0: they read nothing and reach no sink.
+//   2. SOURCE ROWS IN CHUNKS.  lo and lo + count do not decrease with the output index (every operation that makes them is
+//      monotonic in binary32), so the tile's vertical footprint is [lo of its first row, lo + count of its last row).  The
+//      workgroup walks those source rows in ascending order, kChunk at a time:
+//        a. horizontal pass: wave v computes h(row, column, channel) of the chunk's rows v, v + 4, ... for the tile's 64
+//           columns, one column per lane (byte loads; neighbouring lanes share the lines), tap by tap in ascending order, a
+//           product and then a sum, and writes them to LDS [row][channel][column] (consecutive lanes, consecutive banks);
+//        b. after a barrier, vertical pass: every work-item owns one column of 8 consecutive output rows (wave v: rows 8 v ...
+//           8 v + 7) and adds Wy * h into 24 register accumulators, for each of its rows over that row's taps inside the
+//           chunk.  Ascending source rows inside a chunk and ascending chunks are the contract's order; h is computed once per
+//           source row and column, whatever the number of output rows that read it.
+//      At k = 2 a tile's footprint is about 132 x 68 source pixels (3 chunks), at k = 16 1 056 x 544 (17 chunks).
+//   3. STORES.  The accumulators become bytes (clamp, + 0.5, truncate), go through LDS (the chunk buffer, free by then) and
+//      leave as resample_walk's runs: sink(o, y, x, npix) for 4 pixels of one row per work-item, 16 work-items across.
+// Reads stay inside the image: lo >= 0 and lo + count <= n on both axes.  The count is clamped to kAntialiasMaxTaps, the
+// tables' width, whatever the record says; the host refuses k > kAntialiasMaxScale, below which the clamp never binds.
+//
+// LDS: tables (64 + 32) x (33 + 2) x 4 = 13 440 bytes, chunk buffer 32 x 3 x 64 x 4 = 24 576 bytes; 38 016 in all, four
+// workgroups per CU.
+//
+// Compile with -ffp-contract=off (see dct.hpp): every statement below is one binary32 operation.  The division is hipcc's
+// default for HIP, correctly rounded (no fast-math, no -fhip-fp32-correctly-rounded-divide-sqrt=off).
+#pragma once
+#pragma clang fp contract(off)
+
+#include "fused_common.hpp"
+#include "kernels.hpp"
+#include "resample.hpp"
+
+namespace jpeg_amd {
+
+constexpr int kChunk = 32;                        // source rows per chunk
+constexpr int kWaves = kThreads / kTileW;         // one column per lane in the horizontal pass
+constexpr int kChunkRows = kChunk / kWaves;       // source rows per wave and chunk
+constexpr int kOwnRows = kTileH / kWaves;         // output rows per work-item in the vertical pass
+static_assert(kThreads == kWaves * kTileW && kChunk % kWaves == 0 && kTileH % kWaves == 0, "roles");
+static_assert(kChunk * 3 * kTileW * sizeof(float) >= (size_t)3 * kTileW * kTileH, "the byte tile lies in the chunk buffer");
+
+// One axis of the contract: output index j of an axis of n source samples.  W: the row of the table.
+__device__ __forceinline__ void antialias_taps(int j, float k, float s, float r, int n, int &lo, int &count, float *W)
+{
+    const float c = ((float)j + 0.5f) * k;
+    lo = max((int)((c - s) + 0.5f), 0);
+    const int hi = min((int)((c + s) + 0.5f), n);
+    count = min(max(hi - lo, 0), kAntialiasMaxTaps);
+    float total = 0.0f;
+    for (int i = 0; i < count; ++i) {
+        const float u = (((float)(lo + i) - c) + 0.5f) * r;
+        const float w = fmaxf(1.0f - fabsf(u), 0.0f);
+        W[i] = w;
+        total = i == 0 ? w : total + w;
+    }
+    for (int i = 0; i < count; ++i) W[i] = W[i] / total;
+}
+
+__device__ __forceinline__ uint32_t antialias_byte(float v) { return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f); }
+
+// The tile blockIdx.x of image blockIdx.y, with resample_walk's sink.  a.records is not read: the records are `records`.
+template <typename Sink>
+__device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const AntialiasRecord *records, bool flips, Sink sink)
+{
+    __shared__ int tlo[kTileW + kTileH], tcount[kTileW + kTileH];   // columns, then rows
+    __shared__ float tw[kTileW + kTileH][kAntialiasMaxTaps];
+    __shared__ float hbuf[kChunk * 3 * kTileW];
+
+    const int t = threadIdx.x;
+    uint32_t txi;
+    const uint32_t tyi = a.tiles_x.div(blockIdx.x, txi);
+    const int px0 = kTileW * (int)txi, py0 = kTileH * (int)tyi;
+    const AntialiasRecord r = records[blockIdx.y];
+    const bool flip = flips && r.flip;
+    if (t < kTileW) {
+        int lo = 0, count = 0;
+        if (px0 + t < a.out_w) antialias_taps(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
+        tlo[t] = lo; tcount[t] = count;
+    } else if (t < kTileW + kTileH) {
+        int lo = 0, count = 0;
+        if (py0 + (t - kTileW) < a.out_h) antialias_taps(py0 + (t - kTileW), r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
+        tlo[t] = lo; tcount[t] = count;
+    }
+    __syncthreads();
+
+    const int col = t % kTileW, wave = t / kTileW;
+    const int rows = min(kTileH, a.out_h - py0);   // of the tile, >= 1
+    const int ybeg = tlo[kTileW], yend = tlo[kTileW + rows - 1] + tcount[kTileW + rows - 1];
+    const int xcount = tcount[col];
+    const size_t row_bytes = (size_t)3 * (uint32_t)r.w;
+    const uint8_t *src = a.src + r.offset + (size_t)3 * (uint32_t)tlo[col];
+    const float *wx = tw[col];
+    float acc[kOwnRows][3];
+#pragma unroll
+    for (int i = 0; i < kOwnRows; ++i)
+        acc[i][0] = acc[i][1] = acc[i][2] = 0.0f;
+
+    for (int y0 = ybeg; y0 < yend; y0 += kChunk) {   // the same trips for every work-item: the barriers are inside
+        float h[kChunkRows][3];
+#pragma unroll
+        for (int i = 0; i < kChunkRows; ++i)
+            h[i][0] = h[i][1] = h[i][2] = 0.0f;
+        for (int k = 0; k < xcount; ++k) {
+            const float w = wx[k];
+#pragma unroll
+            for (int i = 0; i < kChunkRows; ++i) {
+                const int y = y0 + wave + kWaves * i;
+                if (y < yend) {
+                    const uint8_t *p = src + (size_t)(uint32_t)y * row_bytes + 3 * k;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) h[i][c] = h[i][c] + w * (float)p[c];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kChunkRows; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) hbuf[((wave + kWaves * i) * 3 + c) * kTileW + col] = h[i][c];
+        __syncthreads();
+        const int yc = min(y0 + kChunk, yend);
+#pragma unroll
+        for (int i = 0; i < kOwnRows; ++i) {
+            const int u = kTileW + kOwnRows * wave + i;
+            const int lo = tlo[u];
+            const int e = min(lo + tcount[u], yc);
+            for (int y = max(lo, y0); y < e; ++y) {
+                const float w = tw[u][y - lo];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[i][c] = acc[i][c] + w * hbuf[((y - y0) * 3 + c) * kTileW + col];
+            }
+        }
+        __syncthreads();
+    }
+
+    uint8_t *tile = reinterpret_cast<uint8_t *>(hbuf);   // [kTileH][3 kTileW]: every read of the last chunk is behind a barrier
+#pragma unroll
+    for (int i = 0; i < kOwnRows; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tile[(kOwnRows * wave + i) * (3 * kTileW) + 3 * col + c] = (uint8_t)antialias_byte(acc[i][c]);
+    __syncthreads();
+
+    const int ly = t / kLanesX, lx = t - ly * kLanesX;
+    const int x = px0 + kRun * lx;
+    const int npix = min(kRun, a.out_w - x);
+    if (npix <= 0) return;
+#pragma unroll
+    for (int u = ly; u < kTileH; u += kRowStep) {
+        const int y = py0 + u;
+        if (y >= a.out_h) break;
+        const uint32_t *run = reinterpret_cast<const uint32_t *>(tile + u * (3 * kTileW) + 3 * kRun * lx);
+        const uint32_t w[3] = {run[0], run[1], run[2]};
+        uint32_t o[kRun][3];
+#pragma unroll
+        for (int k = 0; k < kRun; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[k][c] = (w[(3 * k + c) >> 2] >> (8 * ((3 * k + c) & 3))) & 0xffu;
+        sink(o, y, x, npix);
+    }
+}
+
+}  // namespace jpeg_amd

@@ -1191,11 +1191,10 @@ constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chu
 
 // The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
 // returns -- as stage_quanta).
-int upload_records(jpeg_amd_ctx *ctx, const std::vector<ResizeRecord> &rec)
+int upload_records(jpeg_amd_ctx *ctx, const std::vector<uint8_t> &rec)
 {
-    const size_t bytes = rec.size() * sizeof(ResizeRecord);
-    JA_TRY(ensure_buffer(ctx, ctx->resize_rec, bytes));
-    JA_HIP(ctx, hipMemcpyAsync(ctx->resize_rec.ptr, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(ensure_buffer(ctx, ctx->resize_rec, rec.size()));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->resize_rec.ptr, rec.data(), rec.size(), hipMemcpyHostToDevice, ctx->stream));
     return JPEG_AMD_OK;
 }
 
@@ -1221,10 +1220,13 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
     return JPEG_AMD_OK;
 }
 
-// Where the resampled images of a call go: bytes (k_resize_bilinear) or, in a tensor call, elements of `spec` (k_resize_tensor).
-// `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.
+// Where the resampled images of a call go, and through which filter: bytes (k_resize_bilinear, k_antialias_bytes) or, in a
+// tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor).  `tensor` is not `spec != nullptr`: a tensor call
+// without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
+// ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others.
 struct ResampleTarget {
     int32_t out_w, out_h;
+    int filter;              // JPEG_AMD_FILTER_*
     bool tensor;
     const jpeg_amd_tensor_spec *spec;
     const uint8_t *h_flip;   // per image, or nullptr: none is mirrored
@@ -1232,38 +1234,61 @@ struct ResampleTarget {
     size_t stride;           // between images, in elements
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
 
+    bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS; }
     int check(int n_images)
     {
+        if (filter != JPEG_AMD_FILTER_BILINEAR && filter != JPEG_AMD_FILTER_ANTIALIAS) return JPEG_AMD_EINVAL;
         return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride);
     }
     // Image i of the call, w x h at `offset` bytes from the launch's source.  The scale factors of the contract: divided here,
     // in binary32, never on the device.
-    ResizeRecord record(int i, uint64_t offset, int32_t w, int32_t h) const
+    // ENOSUP: the antialiasing filter's tap limit, kx or ky above kAntialiasMaxScale.  The record is written either way, and
+    // the caller keeps the verdict of the first such image until everything else of the call has been judged.
+    size_t record_bytes() const { return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord); }
+    int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
-        return ResizeRecord{offset, w, h, (float)w / (float)out_w, (float)h / (float)out_h, h_flip && h_flip[i] ? 1u : 0u, 0u};
+        const float kx = (float)w / (float)out_w, ky = (float)h / (float)out_h;
+        const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
+        if (!antialias()) {
+            const ResizeRecord r{offset, w, h, kx, ky, flip, 0u};
+            std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+            return JPEG_AMD_OK;
+        }
+        const float sx = std::max(kx, 1.0f), sy = std::max(ky, 1.0f);
+        const AntialiasRecord r{offset, w, h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u};
+        std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+        return kx > kAntialiasMaxScale || ky > kAntialiasMaxScale ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
     }
-    // Images [i0, i0 + m) of the call, from their records d_rec + i0.
-    hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const ResizeRecord *d_rec, int i0) const
+    // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards.
+    hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
-        return tensor ? launch_resize_tensor(stream, m, d_src, d_rec + i0, out_w, out_h, *spec, d_out, stride)
-                      : launch_resize_bilinear(stream, m, d_src, d_rec + i0, out_w, out_h, d_out, stride);
+        if (antialias()) {
+            const AntialiasRecord *rec = static_cast<const AntialiasRecord *>(d_rec) + i0;
+            return tensor ? launch_antialias_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
+                          : launch_antialias_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
+        }
+        const ResizeRecord *rec = static_cast<const ResizeRecord *>(d_rec) + i0;
+        return tensor ? launch_resize_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
+                      : launch_resize_bilinear(stream, m, d_src, rec, out_w, out_h, d_out, stride);
     }
 };
 
 // The chunks of the resized and tensor decodes: consecutive images, m images at a stride of the chunk's largest view, at most
-// kResizeChunkBytes in all; rec[i] is image i's record inside its chunk; need: the bytes the largest chunk takes.
+// kResizeChunkBytes in all; rec holds image i's record inside its chunk (the target's kind of record); need: the bytes the
+// largest chunk takes; status: what the target's record() says of the first image it refuses.
 struct ResizeChunk { int i0, m; size_t stride; };
 struct ResizePlan {
     std::vector<ResizeChunk> chunks;
-    std::vector<ResizeRecord> rec;
+    std::vector<uint8_t> rec;
     size_t need = 0;
+    int status = JPEG_AMD_OK;
 };
 extern "C++" ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, const ResampleTarget &t)
 {
     ResizePlan plan;
-    plan.rec.resize((size_t)n_images);
+    plan.rec.resize((size_t)n_images * t.record_bytes());
     for (int i0 = 0; i0 < n_images;) {
         int m = 0;
         size_t stride = 0;
@@ -1275,7 +1300,8 @@ extern "C++" ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_
         }
         for (int j = 0; j < m; ++j) {
             const jpeg_amd_region &r = h_views[i0 + j].region;
-            plan.rec[(size_t)(i0 + j)] = t.record(i0 + j, (uint64_t)j * stride, r.width, r.height);
+            const int verdict = t.record(plan.rec, i0 + j, i0 + j, (uint64_t)j * stride, r.width, r.height);
+            if (plan.status == JPEG_AMD_OK) plan.status = verdict;
         }
         plan.chunks.push_back(ResizeChunk{i0, m, stride});
         plan.need = std::max(plan.need, stride * (size_t)m);
@@ -1296,36 +1322,39 @@ int resample_chunks(jpeg_amd_ctx *ctx, const ResizePlan &plan, const ResampleTar
     for (size_t c = 0; c < plan.chunks.size(); ++c) {
         const ResizeChunk &k = plan.chunks[c];
         JA_TRY(decode(c, k, d_views));
-        JA_HIP(ctx, t.launch(ctx->stream, k.m, d_views, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), k.i0));
+        JA_HIP(ctx, t.launch(ctx->stream, k.m, d_views, ctx->resize_rec.ptr, k.i0));
     }
     return JPEG_AMD_OK;
 }
 
-// jpeg_amd_resize_batch and jpeg_amd_resize_tensor_batch.
+// jpeg_amd_resize_batch and jpeg_amd_resize_tensor_batch, and their forms with a filter.
 int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride, const jpeg_amd_extent *h_extents,
                   ResampleTarget t)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     JA_TRY(t.check(n_images));
-    std::vector<ResizeRecord> rec((size_t)n_images);
+    std::vector<uint8_t> rec((size_t)n_images * t.record_bytes());
+    int taps = JPEG_AMD_OK;   // the tap limit: judged last, by the first image over it
     if (n_images > 0) {
         if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
         for (int i = 0; i < n_images; ++i) {
             const jpeg_amd_extent &e = h_extents[i];
             if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
             if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
-            rec[(size_t)i] = t.record(i, (uint64_t)i * src_stride, e.width, e.height);
+            const int verdict = t.record(rec, i, i, (uint64_t)i * src_stride, e.width, e.height);
+            if (taps == JPEG_AMD_OK) taps = verdict;
         }
     }
+    JA_TRY(taps);
     JA_TRY(bind(ctx));
     if (n_images == 0) return JPEG_AMD_OK;
     JA_TRY(upload_records(ctx, rec));
-    JA_HIP(ctx, t.launch(ctx->stream, n_images, d_src, static_cast<const ResizeRecord *>(ctx->resize_rec.ptr), 0));
+    JA_HIP(ctx, t.launch(ctx->stream, n_images, d_src, ctx->resize_rec.ptr, 0));
     return JPEG_AMD_OK;
 }
 
-// jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch; c.d_pixels is t.d_dst, and its stride is not looked at.
+// jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch, and their forms with a filter; c.d_pixels is t.d_dst, and its stride is not looked at.
 int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, ResampleTarget t)
 {
     // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
@@ -1338,9 +1367,11 @@ int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view
     PlaneSet cs{};
     JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
     JA_TRY(t.check(c.n_images));
+    const ResizePlan plan = plan_resize_chunks(c.n_images, h_views, t);
+    JA_TRY(plan.status);
     JA_TRY(bind(ctx));
     if (c.n_images == 0) return JPEG_AMD_OK;
-    return resample_chunks(ctx, plan_resize_chunks(c.n_images, h_views, t), t, [&](size_t, const ResizeChunk &k, uint8_t *d_views) {
+    return resample_chunks(ctx, plan, t, [&](size_t, const ResizeChunk &k, uint8_t *d_views) {
         const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
         const DecodeCall part = c.images(k.i0, k.m, coef);
         return jpeg_amd_decode_view_batch(ctx, c.L, k.m, coef, c.coef_stride, part.d_quanta, c.quanta_stride, c.ntables, c.cosited,
@@ -1353,7 +1384,7 @@ int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view
 int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
                           const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_dst, dst_stride});
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1364,7 +1395,7 @@ int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, i
                                   int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride)
 try {
     return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, 0},
-                            h_views, ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, pixel_stride});
+                            h_views, ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_pixels, pixel_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1374,7 +1405,7 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const i
 {
     // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    JA_TRY((ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, 0}.check(1)));
+    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_pixels, 0}.check(1)));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -1400,7 +1431,7 @@ int jpeg_amd_resize_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t 
                                  const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h,
                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents, ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1413,7 +1444,7 @@ int jpeg_amd_decode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
 try {
     return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
                                             static_cast<uint8_t *>(d_dst), 0},
-                            h_views, ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
+                            h_views, ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1424,7 +1455,7 @@ int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
 {
     // as jpeg_amd_decode_resized: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    JA_TRY((ResampleTarget{out_w, out_h, true, spec, nullptr, d_dst, 0}.check(1)));
+    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, nullptr, d_dst, 0}.check(1)));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -1537,6 +1568,7 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
     std::vector<MixedPlan> plans(plan.chunks.size());
     for (size_t c = 0; c < plans.size(); ++c)
         JA_TRY(plan_mixed(h_images + plan.chunks[c].i0, h_views + plan.chunks[c].i0, plan.chunks[c].m, cosited, &plans[c]));
+    JA_TRY(plan.status);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
     JA_TRY(bind(ctx));
     return resample_chunks(ctx, plan, t, [&](size_t c, const ResizeChunk &k, uint8_t *d_views) {
@@ -1566,7 +1598,7 @@ int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_am
                                   uint8_t *d_pixels, size_t pixel_stride)
 try {
     return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, false, nullptr, nullptr, d_pixels, pixel_stride});
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_pixels, pixel_stride});
 }
 JA_NOTHROW_TAIL
 
@@ -1575,7 +1607,69 @@ int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd
                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
 try {
     return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, true, spec, h_flip, d_dst, dst_stride});
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+// The six calls above with the filter chosen by the caller ("antialiased resample"): the same routes, the filter in the target.
+int jpeg_amd_resize_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter, uint8_t *d_dst,
+                                 size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_resize_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                         const int16_t *const d_coef[], const size_t coef_stride[],
+                                         const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                         int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                         int32_t out_w, int32_t out_h, int filter, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, 0},
+                            h_views, ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                        const int16_t *const d_coef[], const size_t coef_stride[],
+                                        const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                        int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                        int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                        const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            static_cast<uint8_t *>(d_dst), 0},
+                            h_views, ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                         int filter, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                                        size_t dst_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
 }
 JA_NOTHROW_TAIL
 

@@ -171,6 +171,27 @@ hipError_t launch_resize_bilinear(hipStream_t stream, int n_images, const uint8_
 hipError_t launch_resize_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
                                 int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
 
+// ---- antialiased resample (kernels_antialias.hip) ------------------------------------------------
+// The two launches above with the filter of include/jpeg_amd.h ("antialiased resample"): the triangle filter widened by the
+// scale factor, bytes out (k_antialias_bytes) or elements out (k_antialias_tensor).  d_records: one AntialiasRecord per image;
+// per axis the scale factor k, s = max(k, 1) and r = 1 / s, all made on the host.  Every kx and ky is at most
+// kAntialiasMaxScale: the kernels' tables hold kAntialiasMaxTaps weights per column and row (they clamp the count to it).
+// Every other argument as launch_resize_bilinear and launch_resize_tensor.
+struct AntialiasRecord {
+    uint64_t offset;       // bytes from d_src
+    int32_t  w, h;         // > 0
+    float    kx, sx, rx;   // (float)w / (float)out_w, max(kx, 1.0f), 1.0f / sx
+    float    ky, sy, ry;   // the same of h and out_h
+    uint32_t flip;         // k_antialias_tensor only: nonzero = the resampled image is stored mirrored along x
+    uint32_t reserved;
+};
+constexpr float kAntialiasMaxScale = 16.0f;
+constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
+hipError_t launch_antialias_bytes(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
+                                  int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
+hipError_t launch_antialias_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
+                                   int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

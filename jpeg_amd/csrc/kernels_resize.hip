@@ -27,30 +27,6 @@ struct ResizeArgs : ResampleArgs {
     size_t dst_stride;   // bytes between output images
 };
 
-// nbytes <= 12 bytes, little-endian in (w0, w1, w2), to o: bytes up to the first 4-byte boundary, dwords from there, bytes
-// behind the last whole dword.
-__device__ __forceinline__ void store_run(uint8_t *o, uint32_t w0, uint32_t w1, uint32_t w2, int nbytes)
-{
-    const int head = min((int)((4u - (uint32_t)(uintptr_t)o) & 3u), nbytes);
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        if (k < head) o[k] = (uint8_t)(w0 >> (8 * k));
-    const int sh = 8 * head;
-    const uint32_t d0 = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
-    const uint32_t d1 = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
-    const uint32_t d2 = w2 >> sh;
-    uint8_t *p = o + head;
-    const int rem = nbytes - head;
-    if (rem >= 4) *reinterpret_cast<uint32_t *>(p) = d0;
-    if (rem >= 8) *reinterpret_cast<uint32_t *>(p + 4) = d1;
-    if (rem >= 12) *reinterpret_cast<uint32_t *>(p + 8) = d2;
-    const int nd = rem & ~3;
-    const uint32_t t = nd == 0 ? d0 : nd == 4 ? d1 : d2;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        if (nd + k < rem) p[nd + k] = (uint8_t)(t >> (8 * k));
-}
-
 __global__ __launch_bounds__(kThreads) void k_resize_bilinear(ResizeArgs a)
 {
     __shared__ int cx0[kTileW], cx1[kTileW], ry0[kTileH], ry1[kTileH];

@@ -6,7 +6,9 @@
 // and v stored as binary32, or rounded to nearest even to binary16 or bfloat16.
 //
 // k_resize_tensor<T, CHW>: resample_walk, flipped where the image's record says so, with the sink that turns the 12 bytes of
-// a run into elements, which stay in registers and leave through store_elems: HWC one run of 12 consecutive elements, CHW
+// a run into elements (the conversions and the stores are tensor_sink.hpp's, shared with k_antialias_tensor; the sink's own
+// dozen lines stand here and, as a function, there: handed the function, the compiler builds other code for these kernels, as
+// it does for k_resize_bilinear through resample_walk, and the bilinear kernels are to stay the code they were), which stay in registers and leave through store_elems: HWC one run of 12 consecutive elements, CHW
 // three runs of 4.  Element stores up to the first address that is a multiple of 4 elements, 4-element vector stores from
 // there (16 bytes at binary32, 8 bytes at the 16-bit types; two of them merged into one 16-byte store where the address
 // allows), element stores behind the last whole vector.  Any element-aligned base and any stride are correct; where out_w is a
@@ -20,108 +22,14 @@
 // Compile with -ffp-contract=off (see dct.hpp).
 #pragma clang fp contract(off)
 
-#include <type_traits>
-
 #include "fused_common.hpp"
 #include "kernels.hpp"
 #include "resample.hpp"
+#include "tensor_sink.hpp"
 
 namespace jpeg_amd {
 
 namespace {
-
-enum class bf16_t : uint16_t {};   // bfloat16 as its bit pattern (a scalar type: arrays of it stay in registers)
-static_assert(sizeof(bf16_t) == 2 && sizeof(_Float16) == 2, "element sizes");
-
-template <typename T>
-struct TensorArgs : ResampleArgs {
-    float mean[3], scale[3];
-    T *dst;
-    size_t dst_stride;   // elements between output images
-};
-
-template <typename T>
-__device__ __forceinline__ T to_element(float v)
-{
-    if constexpr (std::is_same<T, float>::value) {
-        return v;
-    } else if constexpr (std::is_same<T, _Float16>::value) {
-        // v is pinned as a binary32 value first: left alone, the compiler folds the multiply that made it into the conversion
-        // (v_fma_mixlo_f16 a, b, 0), which is not the contract's product rounded to binary32 and turns a product of -0 into +0
-        asm("" : "+v"(v));
-        return (_Float16)v;
-    } else {
-        const uint32_t bits = __float_as_uint(v);
-        return (bf16_t)(uint16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
-    }
-}
-
-__device__ __forceinline__ uint32_t bits16(_Float16 v) { return __builtin_bit_cast(uint16_t, v); }
-__device__ __forceinline__ uint32_t bits16(bf16_t v) { return (uint16_t)v; }
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-
-// 4 elements to an address that is a multiple of 4 elements.
-template <typename T>
-__device__ __forceinline__ void store4(T *p, const T *v)
-{
-    if constexpr (sizeof(T) == 4)
-        *reinterpret_cast<f32x4_t *>(p) = f32x4_t{v[0], v[1], v[2], v[3]};
-    else
-        *reinterpret_cast<u32x2_t *>(p) = u32x2_t{bits16(v[0]) | (bits16(v[1]) << 16), bits16(v[2]) | (bits16(v[3]) << 16)};
-}
-
-// 8 elements of 2 bytes to an address that is a multiple of 16 bytes.
-template <typename T>
-__device__ __forceinline__ void store8(T *p, const T *v)
-{
-    *reinterpret_cast<u32x4_t *>(p) = u32x4_t{bits16(v[0]) | (bits16(v[1]) << 16), bits16(v[2]) | (bits16(v[3]) << 16),
-                                              bits16(v[4]) | (bits16(v[5]) << 16), bits16(v[6]) | (bits16(v[7]) << 16)};
-}
-
-// The first n of v's N elements to p, whose first multiple of 4 elements is H elements ahead (H static, so that every
-// register index is): elements up to it, vectors of 4 from there, elements behind the last whole vector.
-template <typename T, int N, int H>
-__device__ __forceinline__ void store_from(T *p, const T (&v)[N], int n)
-{
-#pragma unroll
-    for (int k = 0; k < H; ++k)
-        if (k < n) p[k] = v[k];
-    if constexpr (H == 0 && N == 12 && sizeof(T) == 2) {
-        if (n == N) {   // 24 bytes: 16 + 8 or 8 + 16
-            if (((uint32_t)(uintptr_t)p & 15u) == 0) {
-                store8(p, &v[0]);
-                store4(p + 8, &v[8]);
-            } else {
-                store4(p, &v[0]);
-                store8(p + 4, &v[4]);
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int b = H; b < N; b += 4) {
-        if (b + 4 <= N && b + 4 <= n) {
-            store4(p + b, &v[b]);
-        } else {
-#pragma unroll
-            for (int k = b; k < b + 4 && k < N; ++k)
-                if (k < n) p[k] = v[k];
-        }
-    }
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void store_elems(T *p, const T (&v)[N], int n)
-{
-    switch (((0u - (uint32_t)(uintptr_t)p) / (uint32_t)sizeof(T)) & 3u) {
-    case 0: store_from<T, N, 0>(p, v, n); break;
-    case 1: store_from<T, N, 1>(p, v, n); break;
-    case 2: store_from<T, N, 2>(p, v, n); break;
-    default: store_from<T, N, 3>(p, v, n); break;
-    }
-}
 
 template <typename T, bool CHW>
 __global__ __launch_bounds__(kThreads) void k_resize_tensor(TensorArgs<T> a)

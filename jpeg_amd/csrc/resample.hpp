@@ -3,6 +3,8 @@
 // filter, the tile, the head of the kernels' arguments with the host code that fills it, and resample_walk, which computes
 // every run of output bytes of a workgroup's tile and hands it to a sink.  k_resize_tensor is resample_walk with its sink;
 // k_resize_bilinear keeps a text of its own of the same walk (kernels_resize.hip says why), so a change here is made there too.
+// store_run, the byte store of a run, is here for k_resize_bilinear and k_antialias_bytes (kernels_antialias.hip); the tile and
+// the head are antialias.hpp's as well.
 //
 // resample_walk: a static grid of (tiles of the output) x (images); the output size is the same for every image, so there is
 // no prefix and no search.  A tile is 64 x 32 output pixels.  Its workgroup
@@ -48,6 +50,30 @@ __device__ __forceinline__ uint32_t resample(float a, float b, float c, float d,
     const float bot = c + fx * (d - c);
     const float v = top + fy * (bot - top);
     return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f);
+}
+
+// nbytes <= 12 bytes, little-endian in (w0, w1, w2), to o: bytes up to the first 4-byte boundary, dwords from there, bytes
+// behind the last whole dword.
+__device__ __forceinline__ void store_run(uint8_t *o, uint32_t w0, uint32_t w1, uint32_t w2, int nbytes)
+{
+    const int head = min((int)((4u - (uint32_t)(uintptr_t)o) & 3u), nbytes);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < head) o[k] = (uint8_t)(w0 >> (8 * k));
+    const int sh = 8 * head;
+    const uint32_t d0 = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+    const uint32_t d1 = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
+    const uint32_t d2 = w2 >> sh;
+    uint8_t *p = o + head;
+    const int rem = nbytes - head;
+    if (rem >= 4) *reinterpret_cast<uint32_t *>(p) = d0;
+    if (rem >= 8) *reinterpret_cast<uint32_t *>(p + 4) = d1;
+    if (rem >= 12) *reinterpret_cast<uint32_t *>(p + 8) = d2;
+    const int nd = rem & ~3;
+    const uint32_t t = nd == 0 ? d0 : nd == 4 ? d1 : d2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (nd + k < rem) p[nd + k] = (uint8_t)(t >> (8 * k));
 }
 
 // What the arguments of both kernels begin with.

@@ -749,8 +749,8 @@ def view_denom(source_size, want_size) -> int:
 
 
 def _filter(filter) -> int:
-    """filter="bilinear" | "antialias" of the resample calls -> 0 for the bilinear filter, whose calls are the entry points
-    without a filter argument, or the JPEG_AMD_FILTER_* code for the *_filter_* entry points."""
+    """filter="bilinear" | "antialias" of the resample calls -> the JPEG_AMD_FILTER_* code for the *_filter_* entry points
+    (with the bilinear code they are the entry points without a filter argument)."""
     codes = {"bilinear": _lib.FILTER_BILINEAR, "antialias": _lib.FILTER_ANTIALIAS}
     if filter not in codes:
         raise ValueError("filter: 'bilinear' or 'antialias'")
@@ -788,20 +788,16 @@ def decode_views(ctx: Context, size, layout: Layout, planes, quanta, views, q: O
 def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, q: Optional[Sequence[int]] = None,
                    color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """decode_views with every image bilinearly resampled to out_size (Wt, Ht), in one call
-    (jpeg_amd_decode_resized_batch; include/jpeg_amd.h holds the filter's contract).  Arguments as decode_views.
-    filter="antialias": the antialiasing filter instead ("antialiased resample" there; jpeg_amd_decode_resized_filter_batch),
-    which refuses a view more than 16 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    (jpeg_amd_decode_resized_filter_batch; include/jpeg_amd.h, "resized decode", holds the filter's contract).  Arguments as
+    decode_views.  filter="antialias": the antialiasing filter instead ("antialiased resample" there), which refuses a view
+    more than 16 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                                   code, out.data_ptr(), stride),
-                   "jpeg_amd_decode_resized_filter_batch", ctx.handle)
-        return out.view(n, ht, wt, 3)
-    _lib.check(_lib.lib().jpeg_amd_decode_resized_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                        out.data_ptr(), stride), "jpeg_amd_decode_resized_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                               code, out.data_ptr(), stride),
+               "jpeg_amd_decode_resized_filter_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
@@ -844,20 +840,15 @@ def _pack_images(ctx: Context, images):
 
 def resize(ctx: Context, images, out_size, filter: str = "bilinear"):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
-    (jpeg_amd_resize_batch), or with filter="antialias" through the antialiasing filter (jpeg_amd_resize_filter_batch; no
-    image more than 16 times the target on an axis).  The images are packed into one allocation first (torch copies).
-    Returns uint8 [n, Ht, Wt, 3]."""
+    (jpeg_amd_resize_filter_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
+    the target on an axis).  The images are packed into one allocation first (torch copies).  Returns uint8 [n, Ht, Wt, 3]."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                           out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
-        return out.view(n, ht, wt, 3)
-    _lib.check(_lib.lib().jpeg_amd_resize_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, out.data_ptr(), stride),
-               "jpeg_amd_resize_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                       out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
@@ -908,21 +899,17 @@ def _tensor_view(out, n, wt, ht, spec):
 
 def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, spec: _lib.TensorSpec, flips=None,
                    q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
-    """decode_resized with the loader's tail in the same call (jpeg_amd_decode_tensor_batch; include/jpeg_amd.h, "tensor
-    output", holds the contract): every view resampled to out_size (Wt, Ht), mirrored along x where flips[i] is set,
-    normalised by `spec` (tensor_spec) and stored in its dtype and layout; `filter` as in decode_resized
-    (jpeg_amd_decode_tensor_filter_batch).  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    """decode_resized with the loader's tail in the same call (jpeg_amd_decode_tensor_filter_batch; include/jpeg_amd.h,
+    "tensor output", holds the contract): every view resampled to out_size (Wt, Ht), mirrored along x where flips[i] is set,
+    normalised by `spec` (tensor_spec) and stored in its dtype and layout; `filter` as in decode_resized.  Returns one tensor
+    [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                                  code, C.byref(spec), h_flip, out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_filter_batch", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht, C.byref(spec),
-                                                       h_flip, out.data_ptr(), stride), "jpeg_amd_decode_tensor_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
+                                                              code, C.byref(spec), h_flip, out.data_ptr(), stride),
+               "jpeg_amd_decode_tensor_filter_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 
@@ -974,40 +961,29 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
 
 
 def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear"):
-    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_mixed, or with
-    filter="antialias" jpeg_amd_decode_resized_filter_mixed); arguments as decode_views_mixed.  Returns one uint8 tensor
-    [n, Ht, Wt, 3]."""
+    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_filter_mixed);
+    arguments as decode_views_mixed, `filter` as in decode_resized.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                   ht, code, out.data_ptr(), stride),
-                   "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
-        return out.view(n, ht, wt, 3)
-    _lib.check(_lib.lib().jpeg_amd_decode_resized_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                        out.data_ptr(), stride), "jpeg_amd_decode_resized_mixed", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                               ht, code, out.data_ptr(), stride),
+               "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                          cosite: bool = False, filter: str = "bilinear"):
-    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_mixed, or with
-    filter="antialias" jpeg_amd_decode_tensor_filter_mixed); arguments as decode_views_mixed, then as decode_tensors.
-    Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
+    as decode_views_mixed, then as decode_tensors.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                  ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                       C.byref(spec), h_flip, out.data_ptr(), stride),
-               "jpeg_amd_decode_tensor_mixed", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                              ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
+               "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 
@@ -1027,21 +1003,16 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
 
 
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear"):
-    """The resample and the output stage alone (jpeg_amd_resize_tensor_batch, or with filter="antialias"
-    jpeg_amd_resize_filter_tensor_batch): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
+    """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
     [n, Ht, Wt, 3] of spec's dtype, in one launch."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if code != _lib.FILTER_BILINEAR:
-        _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                                  C.byref(spec), h_flip, out.data_ptr(), stride),
-                   "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec)
-    _lib.check(_lib.lib().jpeg_amd_resize_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, C.byref(spec), h_flip,
-                                                       out.data_ptr(), stride), "jpeg_amd_resize_tensor_batch", ctx.handle)
+    _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                              C.byref(spec), h_flip, out.data_ptr(), stride),
+               "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 

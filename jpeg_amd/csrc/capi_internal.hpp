@@ -1,0 +1,222 @@
+// capi_internal.hpp -- what the units of the C layer (capi*.hip) share: the context, the status macros, the layout checks,
+// the argument record of the batch decodes and the buffer and staging helpers.  The helpers are defined in capi.hip.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <chrono>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+#include "interleave.hpp"
+#include "kernels.hpp"
+#include "transform.hpp"
+#include "worker_pool.hpp"
+
+// Device memory a context keeps between calls and grows on demand (ensure_buffer).
+struct DeviceBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
+struct jpeg_amd_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    DeviceBuffer scratch;          // the planes of the staged paths, the whole images of the fallbacks
+    uint16_t *d_qstage = nullptr;  // ring of staged host tables
+    uint32_t *d_walk = nullptr;    // the ticket counter of the 4:2:0 walk of long calls (kernels_quad.hip)
+    int32_t *d_flag = nullptr;     // the overflow dword of jpeg_amd_spectral_transform (allocated on first use)
+    DeviceBuffer region;           // staged regions + tile prefix of jpeg_amd_decode_region_batch / _view_batch
+    // jpeg_amd_decode_resized_batch / jpeg_amd_resize_batch: the decoded views of a chunk and the resample's per-image records.
+    // Buffers of their own: the view call in between regrows `scratch` and overwrites `region`.
+    DeviceBuffer resize_src, resize_rec;
+    // the mixed calls (jpeg_amd_decode_view_mixed, ...): the per-image records, index lists and tile prefixes of their launches.
+    // A buffer of its own: the uniform calls of a mixed call's fallback images rewrite `region`, the resample rewrites the others.
+    DeviceBuffer mixed;
+    int qslot = 0;
+    int last_hip = 0;
+    // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
+    // host slots (the host threads work in one while the device works from / into the other) and two device slots
+    void *file_pinned[2] = {nullptr, nullptr};
+    void *file_device = nullptr;                      // both device slots
+    size_t file_pinned_bytes = 0, file_device_bytes = 0;
+    hipEvent_t file_done[2] = {nullptr, nullptr};     // chunk's pixels (decode) / first stage of its download (encode) are back
+    hipEvent_t file_decoded[2] = {nullptr, nullptr};  // chunk's kernels are done (device -> host copy may start)
+    hipEvent_t file_fetched[2] = {nullptr, nullptr};  // encode: the second stage of the chunk's download is back
+    hipStream_t file_d2h = nullptr;                   // downloads overlap the next chunk's uploads (full-duplex PCIe)
+    std::unique_ptr<jpeg_amd::WorkerPool> workers, copiers;   // host threads of the batch file paths: entropy coding; copies out of the pinned slots
+    std::vector<std::vector<uint32_t>> records;       // a sparse record per entropy-decoding thread
+};
+
+#define JA_HIP(ctx, expr)                                         \
+    do {                                                          \
+        const hipError_t e_ = (expr);                             \
+        if (e_ != hipSuccess) {                                   \
+            (ctx)->last_hip = (int)e_;                            \
+            return e_ == hipErrorOutOfMemory ? JPEG_AMD_ENOMEM : JPEG_AMD_EHIP; \
+        }                                                         \
+    } while (0)
+
+// Function-try-block tail of the entry points that allocate host memory or start threads: the header promises plain
+// C, so no C++ exception (std::bad_alloc, std::system_error from a thread that cannot be started) leaves the library.
+#define JA_NOTHROW_TAIL                                               \
+    catch (const std::bad_alloc &) { return JPEG_AMD_ENOMEM; }        \
+    catch (...) { return JPEG_AMD_ENOMEM; }
+
+#define JA_TRY(expr)                          \
+    do {                                      \
+        const int s_ = (expr);                \
+        if (s_ != JPEG_AMD_OK) return s_;     \
+    } while (0)
+
+namespace jpeg_amd {
+namespace capi {
+
+constexpr int kQSlots = 32;                                   // staged table sets in flight
+constexpr size_t kQSlotElems = JPEG_AMD_MAX_PLANES * 64;      // uint16 per slot
+
+// The single-image forms are their batch forms with one image, staged tables and these strides.
+constexpr size_t kOneImage[JPEG_AMD_MAX_PLANES] = {0, 0, 0, 0};
+
+int bind(jpeg_amd_ctx *ctx);
+int check_layout(const jpeg_amd_layout *L, int ntables);
+int check_planes_cover_image(const jpeg_amd_layout *L);
+int check_batch8(const jpeg_amd_layout *L, int n_images, jpeg_amd_color color);
+size_t plane_samples(const jpeg_amd_layout *L, int p);
+int ensure_buffer(jpeg_amd_ctx *ctx, DeviceBuffer &buf, size_t bytes);
+int stage_quanta(jpeg_amd_ctx *ctx, const uint16_t *h_quanta, int ntables, const uint16_t **d_out);
+size_t align256(size_t n);
+size_t scratch_planes_bytes(const jpeg_amd_layout *L, int n_images, size_t sample_bytes);
+int scratch_planes(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, size_t sample_bytes, PlaneSetMut *ps);
+jpeg_amd_layout layout_of_info(const jpeg_amd_frame_info &fi, int nplanes);
+int layout_of_frame(jpeg_amd_frame_info *frame, const int32_t *quanta_key, const int32_t *h_quanta_keys, int ntables,
+                    jpeg_amd_layout *L);
+int reduce_n(int denom);   // (capi_spectral.hip)
+
+// The ABI's per-plane pointer (and stride: nullptr = one image) arrays as a PlaneSet / PlaneSetMut.  Decode inputs
+// (need_all) reject any null plane pointer, encode outputs only where the plane has samples.
+template <typename Set, typename T>
+int plane_set(const jpeg_amd_layout *L, T *const d_planes[], const size_t stride[], bool need_all, Set *ps)
+{
+    *ps = Set{};
+    for (int p = 0; p < L->nplanes; ++p) {
+        if (!d_planes[p] && (need_all || plane_samples(L, p))) return JPEG_AMD_EINVAL;
+        ps->ptr[p] = d_planes[p];
+        ps->stride[p] = stride ? stride[p] : 0;
+    }
+    return JPEG_AMD_OK;
+}
+
+// The arguments the batch decode entry points (whole, region, scaled, view, resized) share, as the caller gave them.
+struct DecodeCall {
+    const jpeg_amd_layout *L;
+    int n_images;
+    const int16_t *const *d_coef;
+    const size_t *coef_stride;
+    const uint16_t *d_quanta;
+    size_t quanta_stride;
+    int ntables, cosited;
+    jpeg_amd_color color;
+    uint8_t *d_pixels;
+    size_t pixel_stride;
+
+    // What is judged before the image count may end the call, in the order that decides the status of a call that is wrong
+    // twice.  The context is no part of it: every entry point binds where it always did.
+    int check() const
+    {
+        JA_TRY(check_layout(L, ntables));
+        JA_TRY(check_planes_cover_image(L));
+        return check_batch8(L, n_images, color);
+    }
+    // ... and of a call with images: no null pointer (per_image: the entry point's regions or views are there, where it
+    // has any) and the coefficient planes as a PlaneSet.
+    int planes(PlaneSet *cs, bool per_image = true) const
+    {
+        if (!d_coef || !coef_stride || !d_quanta || !d_pixels || !per_image) return JPEG_AMD_EINVAL;
+        return plane_set(L, d_coef, coef_stride, true, cs);
+    }
+    // Images [i0, i0 + m) of this call; `coef` is the caller's room for their plane pointers.
+    DecodeCall images(int i0, int m, const int16_t *coef[JPEG_AMD_MAX_PLANES]) const
+    {
+        for (int p = 0; p < L->nplanes; ++p) coef[p] = d_coef[p] + (size_t)i0 * coef_stride[p];
+        return DecodeCall{L, m, coef, coef_stride, d_quanta + (size_t)i0 * quanta_stride, quanta_stride, ntables, cosited, color,
+                          d_pixels + (size_t)i0 * pixel_stride, pixel_stride};
+    }
+    QuantaRef quanta() const { return QuantaRef{d_quanta, quanta_stride}; }
+    bool rgb() const { return color == JPEG_AMD_COLOR_RGB8; }
+};
+
+// Small RAII bag of device buffers for the host wrappers: single buffers, or every plane of a layout (T: the 16-bit sample;
+// a plane without samples gets the 16 bytes of an empty buffer and no copy).
+struct DeviceBag {
+    jpeg_amd_ctx *ctx;
+    std::vector<void *> ptrs;
+    explicit DeviceBag(jpeg_amd_ctx *c) : ctx(c) {}
+    ~DeviceBag()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    int alloc(size_t bytes, void **out)
+    {
+        *out = nullptr;
+        if (bytes == 0) bytes = 16;
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) { ctx->last_hip = (int)e; return JPEG_AMD_ENOMEM; }
+        ptrs.push_back(*out);
+        return JPEG_AMD_OK;
+    }
+    int upload(const void *h, size_t bytes, void **out)
+    {
+        JA_TRY(alloc(bytes, out));
+        if (bytes == 0) return JPEG_AMD_OK;
+        if (!h) return JPEG_AMD_EINVAL;
+        JA_HIP(ctx, hipMemcpyAsync(*out, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return JPEG_AMD_OK;
+    }
+    int download(void *h, const void *d, size_t bytes)
+    {
+        if (bytes == 0) return JPEG_AMD_OK;
+        if (!h) return JPEG_AMD_EINVAL;
+        JA_HIP(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return JPEG_AMD_OK;
+    }
+    template <typename T>
+    int alloc_planes(const jpeg_amd_layout *L, T *d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(alloc(plane_samples(L, p) * sizeof(T), (void **)&d[p]));
+        return JPEG_AMD_OK;
+    }
+    template <typename T>
+    int upload_planes(const jpeg_amd_layout *L, const T *const h[], const T *d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(upload(h[p], plane_samples(L, p) * sizeof(T), (void **)&d[p]));
+        return JPEG_AMD_OK;
+    }
+    template <typename T>
+    int download_planes(const jpeg_amd_layout *L, T *const h[], T *const d[])
+    {
+        for (int p = 0; p < L->nplanes; ++p) JA_TRY(download(h[p], d[p], plane_samples(L, p) * sizeof(T)));
+        return JPEG_AMD_OK;
+    }
+    // the downloads have arrived in the caller's memory
+    int finish()
+    {
+        JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return JPEG_AMD_OK;
+    }
+};
+
+}  // namespace capi
+}  // namespace jpeg_amd

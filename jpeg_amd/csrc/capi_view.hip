@@ -1,0 +1,961 @@
+// capi_view.hip -- the C ABI, view unit: region, scaled and view decode, the resample route and its targets (resized,
+// tensor, filter), and the mixed calls.
+#pragma clang fp contract(off)
+
+#include "capi_internal.hpp"
+
+using namespace jpeg_amd;
+using namespace jpeg_amd::capi;
+
+namespace {
+
+// A pixel region of jpeg_amd_decode_region_batch / jpeg_amd_region_window: inside the image, not empty.
+int check_region(const jpeg_amd_layout *L, const jpeg_amd_region &r)
+{
+    if (r.x < 0 || r.y < 0 || r.width <= 0 || r.height <= 0) return JPEG_AMD_EINVAL;
+    if ((long long)r.x + r.width > L->width || (long long)r.y + r.height > L->height) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+bool whole_image(const jpeg_amd_layout *L, const jpeg_amd_region &r)
+{
+    return r.x == 0 && r.y == 0 && r.width == L->width && r.height == L->height;
+}
+
+// `buf` into the context's region buffer (grown on demand), one copy from a host buffer (pageable, so the copy has taken
+// it when the call returns -- as stage_quanta).
+int upload_regions(jpeg_amd_ctx *ctx, const std::vector<uint32_t> &buf)
+{
+    const size_t bytes = 4 * buf.size();
+    JA_TRY(ensure_buffer(ctx, ctx->region, bytes));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->region.ptr, buf.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    return JPEG_AMD_OK;
+}
+
+// One launch of a view decode kernel, appended to the words that are staged for it: the index list [m] of its images, then the
+// prefix [m + 1] of their tiles at n samples per block.  *nwg: the launch's workgroups; EINVAL: more of them than a grid holds.
+int stage_group(std::vector<uint32_t> &buf, const std::vector<uint32_t> &members, int n, const jpeg_amd_view *h_views, uint32_t *nwg)
+{
+    buf.insert(buf.end(), members.begin(), members.end());
+    uint64_t acc = 0;
+    for (const uint32_t i : members) {
+        buf.push_back((uint32_t)acc);
+        acc += view_tiles(n, h_views[i].region);
+    }
+    if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;
+    buf.push_back((uint32_t)acc);
+    *nwg = (uint32_t)acc;
+    return JPEG_AMD_OK;
+}
+
+// The regions (int32 [n][4]) and their tile prefix (uint32 [n + 1]) in the context's region buffer, one copy from a host
+// buffer (pageable, so the copy has taken it when the call returns -- as stage_quanta).  Returns the workgroup count.
+int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int32_t **d_regions, const uint32_t **d_tiles,
+                  uint32_t *nwg)
+{
+    const size_t bytes = (size_t)16 * n + 4 * ((size_t)n + 1);
+    std::vector<uint32_t> buf(bytes / 4);
+    uint32_t acc = 0;
+    for (int i = 0; i < n; ++i) {
+        std::memcpy(&buf[4 * (size_t)i], &h[i], 16);
+        buf[4 * (size_t)n + i] = acc;
+        acc += region_tiles(h[i]);
+    }
+    buf[4 * (size_t)n + n] = acc;
+    JA_TRY(upload_regions(ctx, buf));
+    *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
+    *d_tiles = reinterpret_cast<const uint32_t *>(*d_regions + 4 * (size_t)n);
+    *nwg = acc;
+    return JPEG_AMD_OK;
+}
+
+constexpr size_t kFallbackChunkBytes = (size_t)1 << 30;   // scratch per chunk of a fallback's whole-image decodes or planes
+
+constexpr int kViewDenoms = 4;   // slot k: denom 1 << k
+int view_slot(int denom) { return denom == 1 ? 0 : denom == 2 ? 1 : denom == 4 ? 2 : denom == 8 ? 3 : -1; }
+
+// The region and the view call's fallback for the layouts without a tile kernel: the whole scaled images of a run of
+// consecutive images of one denominator into scratch behind the staged paths' planes (S's planes are no larger than L's),
+// then one crop launch; a run is at most a chunk.  S[k]: the image at denominator 1 << k, for every k among the views.
+int crop_fallback(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, const jpeg_amd_layout S[kViewDenoms])
+{
+    const jpeg_amd_layout *L = c.L;
+    const int n_images = c.n_images;
+    const size_t n = (size_t)n_images;
+    size_t full_max = 0;
+    std::vector<uint32_t> buf(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const jpeg_amd_layout &Si = S[view_slot(h_views[i].denom)];
+        full_max = std::max(full_max, (size_t)3 * Si.width * Si.height);
+        std::memcpy(&buf[4 * i], &h_views[i].region, 16);
+    }
+    const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kFallbackChunkBytes / per_image));
+    const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
+    JA_TRY(ensure_buffer(ctx, ctx->scratch, planes_bytes + align256(full_max * chunk)));
+    uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch.ptr) + planes_bytes;   // the staged paths' planes stay below it
+    JA_TRY(upload_regions(ctx, buf));
+    const int32_t *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
+    for (int i0 = 0; i0 < n_images;) {
+        const int denom = h_views[i0].denom;
+        const jpeg_amd_layout &Sd = S[view_slot(denom)];
+        int m = 0;
+        size_t max_bytes = 0;
+        for (; i0 + m < n_images && m < chunk && h_views[i0 + m].denom == denom; ++m)
+            max_bytes = std::max(max_bytes, (size_t)3 * h_views[i0 + m].region.width * h_views[i0 + m].region.height);
+        const size_t full = (size_t)3 * Sd.width * Sd.height;
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall run = c.images(i0, m, coef);
+        JA_TRY(jpeg_amd_decode_scaled_batch(ctx, L, m, coef, c.coef_stride, run.d_quanta, c.quanta_stride, c.ntables, c.cosited, c.color,
+                                            denom, d_full, full));
+        JA_HIP(ctx, launch_region_crop(ctx->stream, m, d_full, full, Sd.width, d_regions + 4 * (size_t)i0, max_bytes, run.d_pixels,
+                                       c.pixel_stride));
+        i0 += m;
+    }
+    return JPEG_AMD_OK;
+}
+
+}  // namespace
+
+int jpeg_amd_decode_region_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_region *h_regions,
+                                 uint8_t *d_pixels, size_t pixel_stride)
+try {
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
+    JA_TRY(bind(ctx));
+    JA_TRY(c.check());
+    if (n_images == 0) return JPEG_AMD_OK;
+    PlaneSet cs;
+    JA_TRY(c.planes(&cs, h_regions != nullptr));
+    bool whole = true;
+    for (int i = 0; i < n_images; ++i) {
+        JA_TRY(check_region(L, h_regions[i]));
+        if (n_images > 1 && pixel_stride < (size_t)3 * h_regions[i].width * h_regions[i].height) return JPEG_AMD_EINVAL;
+        whole = whole && whole_image(L, h_regions[i]);
+    }
+    if (whole)
+        return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                     d_pixels, pixel_stride);
+
+    if (fused_decode_supported(*L, cosited != 0)) {
+        const int32_t *d_regions = nullptr;
+        const uint32_t *d_tiles = nullptr;
+        uint32_t nwg = 0;
+        JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
+        JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, c.quanta(), c.rgb(), d_tiles, d_regions, nwg, d_pixels,
+                                         pixel_stride));
+        return JPEG_AMD_OK;
+    }
+
+    // the crop fallback at denominator 1, where the scaled image is the image
+    std::vector<jpeg_amd_view> views((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) views[(size_t)i] = jpeg_amd_view{1, h_regions[i]};
+    const jpeg_amd_layout S[kViewDenoms] = {*L};
+    return crop_fallback(ctx, c, views.data(), S);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_region(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_region *region, uint8_t *d_pixels)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (!region) return JPEG_AMD_EINVAL;
+    JA_TRY(check_region(L, *region));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    return jpeg_amd_decode_region_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, region, d_pixels, 0);
+}
+
+int jpeg_amd_region_window(const jpeg_amd_layout *L, int cosited, const jpeg_amd_region *region,
+                           jpeg_amd_region windows[JPEG_AMD_MAX_PLANES])
+{
+    if (!region || !windows) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_region(L, *region));
+    const jpeg_amd_region &r = *region;
+    for (int p = 0; p < JPEG_AMD_MAX_PLANES; ++p) {
+        windows[p] = jpeg_amd_region{0, 0, 0, 0};
+        if (p >= L->nplanes) continue;
+        int32_t x0, x1, y0, y1;
+        axis_span(interleave_axis(*L, p, cosited != 0, false), r.x, r.x + r.width - 1, x0, x1);
+        axis_span(interleave_axis(*L, p, cosited != 0, true), r.y, r.y + r.height - 1, y0, y1);
+        windows[p] = jpeg_amd_region{x0 >> 3, y0 >> 3, (x1 >> 3) - (x0 >> 3) + 1, (y1 >> 3) - (y0 >> 3) + 1};
+    }
+    return JPEG_AMD_OK;
+}
+
+namespace {
+
+// N = 8 / denom for a denom of the contract, else 0.
+int scaled_n(int denom) { return denom == 1 || denom == 2 || denom == 4 || denom == 8 ? 8 / denom : 0; }
+
+// The planes, N x N samples per block, must cover the scaled image as check_planes_cover_image asks of the full-size one:
+// with units = ceil(size factor / (8 scale)) they always do (include/jpeg_amd.h has the proof); units given by hand may not.
+int check_planes_cover_scaled(const jpeg_amd_layout *L, const jpeg_amd_layout *S, int n)
+{
+    for (int p = 0; p < L->nplanes; ++p) {
+        const long long sx = (long long)n * L->units_x[p], sy = (long long)n * L->units_y[p];
+        if (plane_is_direct(*L, p)) {
+            if (sx < S->width || sy < S->height) return JPEG_AMD_EINVAL;
+        } else {
+            if (sx < 1 || sy < 1) return JPEG_AMD_EINVAL;
+            if (axis_index(interleave_axis(*L, p, true, false), S->width - 1) >= sx) return JPEG_AMD_EINVAL;
+            if (axis_index(interleave_axis(*L, p, true, true), S->height - 1) >= sy) return JPEG_AMD_EINVAL;
+        }
+    }
+    return JPEG_AMD_OK;
+}
+
+}  // namespace
+
+int jpeg_amd_scaled_layout(const jpeg_amd_layout *in, int denom, jpeg_amd_layout *out)
+{
+    if (!out) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(in, -1));
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout s = *in;
+    s.width = (int32_t)(((long long)in->width * n + 7) / 8);
+    s.height = (int32_t)(((long long)in->height * n + 7) / 8);
+    for (int p = 0; p < in->nplanes; ++p) {
+        s.units_x[p] = (int32_t)(((long long)in->units_x[p] * n + 7) / 8);
+        s.units_y[p] = (int32_t)(((long long)in->units_y[p] * n + 7) / 8);
+    }
+    *out = s;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, int denom,
+                                 uint8_t *d_pixels, size_t pixel_stride)
+{
+    if (denom == 1)
+        return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                     d_pixels, pixel_stride);
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
+    JA_TRY(bind(ctx));
+    JA_TRY(c.check());
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(jpeg_amd_scaled_layout(L, denom, &S));
+    JA_TRY(check_planes_cover_scaled(L, &S, n));
+    if (n_images == 0) return JPEG_AMD_OK;
+    PlaneSet cs;
+    JA_TRY(c.planes(&cs));
+    if (n_images > 1 && pixel_stride < (size_t)3 * S.width * S.height) return JPEG_AMD_EINVAL;
+    const QuantaRef q = c.quanta();
+    const bool rgb = c.rgb();
+    if (fused_decode_supported(*L, cosited != 0)) {
+        JA_HIP(ctx, launch_scaled_decode(ctx->stream, n_images, *L, n, S.width, S.height, cs, q, rgb, d_pixels, pixel_stride));
+        return JPEG_AMD_OK;
+    }
+
+    // fallback: every plane N x N per block into byte planes in scratch, padded to S's whole blocks by edge replication, then
+    // the staged interleave + colour kernel under S, chunk by chunk
+    const size_t per_image = std::max<size_t>(1, scratch_planes_bytes(&S, 1, sizeof(uint8_t)));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kFallbackChunkBytes / per_image));
+    PlaneSetMut scratch;
+    JA_TRY(scratch_planes(ctx, &S, chunk, sizeof(uint8_t), &scratch));
+    for (int i0 = 0; i0 < n_images; i0 += chunk) {
+        const int m = std::min(chunk, n_images - i0);
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall part = c.images(i0, m, coef);
+        PlaneSet ps{};
+        for (int p = 0; p < L->nplanes; ++p) {
+            JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, m, coef[p], coef_stride[p], part.quanta(), L->qi[p], L->units_x[p],
+                                                 L->units_y[p], n, L->precision, scratch.ptr[p], scratch.stride[p], true));
+            ps.ptr[p] = scratch.ptr[p];
+            ps.stride[p] = scratch.stride[p];
+        }
+        JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, m, S, ps, true, cosited != 0, rgb ? PixelKind::RGB8 : PixelKind::YCC8,
+                                            part.d_pixels, pixel_stride));
+    }
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_decode_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color, int denom,
+                           uint8_t *d_pixels)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (scaled_n(denom) == 0) return JPEG_AMD_EINVAL;
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    return jpeg_amd_decode_scaled_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, denom, d_pixels, 0);
+}
+
+int jpeg_amd_spectral_idct_scaled(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                                  const uint16_t *h_quanta, int ntables, int denom, uint16_t *const d_planes[])
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, ntables));
+    if (denom == 1) return jpeg_amd_spectral_idct(ctx, L, d_coef, h_quanta, ntables, d_planes);
+    const int n = scaled_n(denom);
+    if (n == 0 || !d_coef || !d_planes) return JPEG_AMD_EINVAL;
+    for (int p = 0; p < L->nplanes; ++p)
+        if (plane_samples(L, p) != 0 && (!d_coef[p] || !d_planes[p])) return JPEG_AMD_EINVAL;
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    for (int p = 0; p < L->nplanes; ++p)
+        JA_HIP(ctx, launch_idct_scaled_plane(ctx->stream, 1, d_coef[p], 0, QuantaRef{d_q, 0}, L->qi[p], L->units_x[p], L->units_y[p], n,
+                                             L->precision, d_planes[p], 0, false));
+    return JPEG_AMD_OK;
+}
+
+namespace {
+
+// The image at `denom` as the scaled contract defines it: *S is jpeg_amd_scaled_layout's, and the planes cover it.
+int scaled_image(const jpeg_amd_layout *L, int denom, jpeg_amd_layout *S)
+{
+    const int n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    JA_TRY(jpeg_amd_scaled_layout(L, denom, S));
+    return denom == 1 ? JPEG_AMD_OK : check_planes_cover_scaled(L, S, n);
+}
+
+// Every argument of jpeg_amd_decode_view_batch but the context, in the order that decides the status of a call that is wrong
+// twice.  S[k] / count[k]: the scaled image and the number of views of denominator 1 << k; *whole: every view a whole image.
+int check_views(const DecodeCall &c, const jpeg_amd_view *h_views, jpeg_amd_layout S[kViewDenoms], int count[kViewDenoms], bool *whole,
+                PlaneSet *cs)
+{
+    const jpeg_amd_layout *L = c.L;
+    const int n_images = c.n_images;
+    JA_TRY(c.check());
+    if (n_images == 0) return JPEG_AMD_OK;
+    JA_TRY(c.planes(cs, h_views != nullptr));
+    for (int i = 0; i < n_images; ++i) {
+        const int k = view_slot(h_views[i].denom);
+        if (k < 0) return JPEG_AMD_EINVAL;
+        if (count[k]++ == 0) JA_TRY(scaled_image(L, h_views[i].denom, &S[k]));
+        const jpeg_amd_region &r = h_views[i].region;
+        JA_TRY(check_region(&S[k], r));
+        if (n_images > 1 && c.pixel_stride < (size_t)3 * r.width * r.height) return JPEG_AMD_EINVAL;
+        *whole = *whole && whole_image(&S[k], r);
+    }
+    return JPEG_AMD_OK;
+}
+
+// What jpeg_amd_decode_view and jpeg_amd_decode_resized refuse before a table is staged: check_views for their one view.
+int check_one_view(const jpeg_amd_layout *L, int ntables, jpeg_amd_color color, const jpeg_amd_view *view)
+{
+    JA_TRY(check_layout(L, ntables));
+    JA_TRY(check_planes_cover_image(L));
+    JA_TRY(check_batch8(L, 1, color));
+    if (!view) return JPEG_AMD_EINVAL;
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, view->denom, &S));
+    return check_region(&S, view->region);
+}
+
+}  // namespace
+
+int jpeg_amd_decode_view_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                               const int16_t *const d_coef[], const size_t coef_stride[],
+                               const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                               int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                               uint8_t *d_pixels, size_t pixel_stride)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    const DecodeCall c{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, pixel_stride};
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(c, h_views, S, count, &whole, &cs));
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+
+    const int denom0 = h_views[0].denom;
+    if (whole && count[view_slot(denom0)] == n_images)
+        return jpeg_amd_decode_scaled_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            denom0, d_pixels, pixel_stride);
+    if (count[0] == n_images) {   // every view a region of the full-size image
+        std::vector<jpeg_amd_region> regions((size_t)n_images);
+        for (int i = 0; i < n_images; ++i) regions[(size_t)i] = h_views[i].region;
+        return jpeg_amd_decode_region_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            regions.data(), d_pixels, pixel_stride);
+    }
+
+    const size_t n = (size_t)n_images;
+    if (fused_decode_supported(*L, cosited != 0)) {
+        // staged in one copy: the rectangles [n][4], then per denominator of the call its group (stage_group)
+        std::vector<uint32_t> buf(4 * n), members;
+        for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
+        size_t at[kViewDenoms];
+        uint32_t nwg[kViewDenoms];
+        for (int k = 0; k < kViewDenoms; ++k) {
+            at[k] = buf.size();
+            nwg[k] = 0;
+            if (count[k] == 0) continue;
+            members.clear();
+            for (size_t i = 0; i < n; ++i)
+                if (view_slot(h_views[i].denom) == k) members.push_back((uint32_t)i);
+            JA_TRY(stage_group(buf, members, 8 >> k, h_views, &nwg[k]));
+        }
+        JA_TRY(upload_regions(ctx, buf));
+        const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->region.ptr);
+        for (int k = 0; k < kViewDenoms; ++k) {
+            if (count[k] == 0) continue;
+            JA_HIP(ctx, launch_view_decode(ctx->stream, count[k], *L, 8 >> k, cs, c.quanta(), c.rgb(), d_buf + at[k],
+                                           d_buf + at[k] + count[k], reinterpret_cast<const int32_t *>(d_buf), nwg[k], d_pixels,
+                                           pixel_stride));
+        }
+        return JPEG_AMD_OK;
+    }
+
+    return crop_fallback(ctx, c, h_views, S);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_view(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                         const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                         const jpeg_amd_view *view, uint8_t *d_pixels)
+{
+    // as the batch call: what can be refused is refused before a table is staged
+    JA_TRY(check_one_view(L, ntables, color, view));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    return jpeg_amd_decode_view_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, d_pixels, 0);
+}
+
+int jpeg_amd_view_window(const jpeg_amd_layout *L, int cosited, int denom, const jpeg_amd_region *region,
+                         jpeg_amd_region windows[JPEG_AMD_MAX_PLANES])
+{
+    if (!region || !windows) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    JA_TRY(check_planes_cover_image(L));
+    jpeg_amd_layout S;
+    JA_TRY(scaled_image(L, denom, &S));
+    JA_TRY(check_region(&S, *region));
+    const jpeg_amd_region &r = *region;
+    const int32_t n = scaled_n(denom);
+    for (int p = 0; p < JPEG_AMD_MAX_PLANES; ++p) {
+        windows[p] = jpeg_amd_region{0, 0, 0, 0};
+        if (p >= L->nplanes) continue;
+        InterleaveAxis mx = interleave_axis(*L, p, cosited != 0, false), my = interleave_axis(*L, p, cosited != 0, true);
+        mx.last = n * L->units_x[p] - 1;   // the scaled plane's padded edge
+        my.last = n * L->units_y[p] - 1;
+        int32_t x0, x1, y0, y1;
+        axis_span(mx, r.x, r.x + r.width - 1, x0, x1);
+        axis_span(my, r.y, r.y + r.height - 1, y0, y1);
+        windows[p] = jpeg_amd_region{x0 / n, y0 / n, x1 / n - x0 / n + 1, y1 / n - y0 / n + 1};
+    }
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_view_of_source(const jpeg_amd_layout *L, int denom, const jpeg_amd_region *source_region, jpeg_amd_region *region)
+{
+    if (!source_region || !region) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(L, -1));
+    const long long n = scaled_n(denom);
+    if (n == 0) return JPEG_AMD_EINVAL;
+    JA_TRY(check_region(L, *source_region));
+    const jpeg_amd_region &s = *source_region;
+    const long long w1 = ((long long)L->width * n + 7) / 8, h1 = ((long long)L->height * n + 7) / 8;
+    const long long x0 = s.x * n / 8, x1 = std::min(w1, (((long long)s.x + s.width) * n + 7) / 8);
+    const long long y0 = s.y * n / 8, y1 = std::min(h1, (((long long)s.y + s.height) * n + 7) / 8);
+    *region = jpeg_amd_region{(int32_t)x0, (int32_t)y0, (int32_t)(x1 - x0), (int32_t)(y1 - y0)};
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t want_h)
+{
+    for (int denom = 8; denom > 1; denom /= 2) {
+        const long long n = 8 / denom;
+        if (src_w * n / 8 >= want_w && src_h * n / 8 >= want_h) return denom;
+    }
+    return 1;
+}
+
+namespace {
+
+constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of the resized and tensor decodes
+
+// The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
+// returns -- as stage_quanta).
+int upload_records(jpeg_amd_ctx *ctx, const std::vector<uint8_t> &rec)
+{
+    JA_TRY(ensure_buffer(ctx, ctx->resize_rec, rec.size()));
+    JA_HIP(ctx, hipMemcpyAsync(ctx->resize_rec.ptr, rec.data(), rec.size(), hipMemcpyHostToDevice, ctx->stream));
+    return JPEG_AMD_OK;
+}
+
+// What both resample calls require of the output.
+int check_resize_target(int n_images, int32_t out_w, int32_t out_h, const void *d_dst, size_t dst_stride)
+{
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
+    if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
+    if (n_images > 1 && dst_stride < (size_t)3 * out_w * out_h) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// What the tensor calls require of the output, beyond jpeg_amd_tensor_extent.
+int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const void *d_dst,
+                        size_t dst_stride, size_t *elem_bytes)
+{
+    size_t image_elems = 0;
+    JA_TRY(jpeg_amd_tensor_extent(spec, out_w, out_h, elem_bytes, &image_elems));
+    if (n_images > 0 && !d_dst) return JPEG_AMD_EINVAL;
+    if ((uintptr_t)d_dst % *elem_bytes != 0) return JPEG_AMD_EINVAL;
+    if (n_images > 1 && dst_stride < image_elems) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// Where the resampled images of a call go, and through which filter: bytes (k_resize_bilinear, k_antialias_bytes) or, in a
+// tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor).  `tensor` is not `spec != nullptr`: a tensor call
+// without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
+// ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others.
+struct ResampleTarget {
+    int32_t out_w, out_h;
+    int filter;              // JPEG_AMD_FILTER_*
+    bool tensor;
+    const jpeg_amd_tensor_spec *spec;
+    const uint8_t *h_flip;   // per image, or nullptr: none is mirrored
+    void *d_dst;
+    size_t stride;           // between images, in elements
+    size_t elem_bytes = 1;   // of a tensor call: check() sets it
+
+    bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS; }
+    int check(int n_images)
+    {
+        if (filter != JPEG_AMD_FILTER_BILINEAR && filter != JPEG_AMD_FILTER_ANTIALIAS) return JPEG_AMD_EINVAL;
+        return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
+                      : check_resize_target(n_images, out_w, out_h, d_dst, stride);
+    }
+    // Image i of the call, w x h at `offset` bytes from the launch's source.  The scale factors of the contract: divided here,
+    // in binary32, never on the device.
+    // ENOSUP: the antialiasing filter's tap limit, kx or ky above kAntialiasMaxScale.  The record is written either way, and
+    // the caller keeps the verdict of the first such image until everything else of the call has been judged.
+    size_t record_bytes() const { return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord); }
+    int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
+    {
+        const float kx = (float)w / (float)out_w, ky = (float)h / (float)out_h;
+        const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
+        if (!antialias()) {
+            const ResizeRecord r{offset, w, h, kx, ky, flip, 0u};
+            std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+            return JPEG_AMD_OK;
+        }
+        const float sx = std::max(kx, 1.0f), sy = std::max(ky, 1.0f);
+        const AntialiasRecord r{offset, w, h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u};
+        std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+        return kx > kAntialiasMaxScale || ky > kAntialiasMaxScale ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
+    }
+    // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards.
+    hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
+    {
+        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
+        if (antialias()) {
+            const AntialiasRecord *rec = static_cast<const AntialiasRecord *>(d_rec) + i0;
+            return tensor ? launch_antialias_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
+                          : launch_antialias_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
+        }
+        const ResizeRecord *rec = static_cast<const ResizeRecord *>(d_rec) + i0;
+        return tensor ? launch_resize_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
+                      : launch_resize_bilinear(stream, m, d_src, rec, out_w, out_h, d_out, stride);
+    }
+};
+
+// The chunks of the resized and tensor decodes: consecutive images, m images at a stride of the chunk's largest view, at most
+// kResizeChunkBytes in all; rec holds image i's record inside its chunk (the target's kind of record); need: the bytes the
+// largest chunk takes; status: what the target's record() says of the first image it refuses.
+struct ResizeChunk { int i0, m; size_t stride; };
+struct ResizePlan {
+    std::vector<ResizeChunk> chunks;
+    std::vector<uint8_t> rec;
+    size_t need = 0;
+    int status = JPEG_AMD_OK;
+};
+ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, const ResampleTarget &t)
+{
+    ResizePlan plan;
+    plan.rec.resize((size_t)n_images * t.record_bytes());
+    for (int i0 = 0; i0 < n_images;) {
+        int m = 0;
+        size_t stride = 0;
+        for (; i0 + m < n_images; ++m) {
+            const jpeg_amd_region &r = h_views[i0 + m].region;
+            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
+            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
+            stride = s;
+        }
+        for (int j = 0; j < m; ++j) {
+            const jpeg_amd_region &r = h_views[i0 + j].region;
+            const int verdict = t.record(plan.rec, i0 + j, i0 + j, (uint64_t)j * stride, r.width, r.height);
+            if (plan.status == JPEG_AMD_OK) plan.status = verdict;
+        }
+        plan.chunks.push_back(ResizeChunk{i0, m, stride});
+        plan.need = std::max(plan.need, stride * (size_t)m);
+        i0 += m;
+    }
+    return plan;
+}
+
+// The route of every resized and tensor decode, behind its checks and on a bound context: chunk by chunk,
+// decode(c, chunk, d_views) puts the views of chunk c into the context's buffer at the chunk's stride, and the target's launch
+// resamples them from there.
+template <typename Decode>
+int resample_chunks(jpeg_amd_ctx *ctx, const ResizePlan &plan, const ResampleTarget &t, Decode decode)
+{
+    JA_TRY(ensure_buffer(ctx, ctx->resize_src, plan.need));
+    JA_TRY(upload_records(ctx, plan.rec));
+    uint8_t *d_views = static_cast<uint8_t *>(ctx->resize_src.ptr);
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const ResizeChunk &k = plan.chunks[c];
+        JA_TRY(decode(c, k, d_views));
+        JA_HIP(ctx, t.launch(ctx->stream, k.m, d_views, ctx->resize_rec.ptr, k.i0));
+    }
+    return JPEG_AMD_OK;
+}
+
+// jpeg_amd_resize_batch and jpeg_amd_resize_tensor_batch, and their forms with a filter.
+int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride, const jpeg_amd_extent *h_extents,
+                  ResampleTarget t)
+{
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    JA_TRY(t.check(n_images));
+    std::vector<uint8_t> rec((size_t)n_images * t.record_bytes());
+    int taps = JPEG_AMD_OK;   // the tap limit: judged last, by the first image over it
+    if (n_images > 0) {
+        if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
+        for (int i = 0; i < n_images; ++i) {
+            const jpeg_amd_extent &e = h_extents[i];
+            if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
+            if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
+            const int verdict = t.record(rec, i, i, (uint64_t)i * src_stride, e.width, e.height);
+            if (taps == JPEG_AMD_OK) taps = verdict;
+        }
+    }
+    JA_TRY(taps);
+    JA_TRY(bind(ctx));
+    if (n_images == 0) return JPEG_AMD_OK;
+    JA_TRY(upload_records(ctx, rec));
+    JA_HIP(ctx, t.launch(ctx->stream, n_images, d_src, ctx->resize_rec.ptr, 0));
+    return JPEG_AMD_OK;
+}
+
+// jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch, and their forms with a filter; c.d_pixels is t.d_dst, and its stride is not looked at.
+int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, ResampleTarget t)
+{
+    // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
+    // ours and always large enough), then what the target refuses
+    DecodeCall views = c;
+    views.pixel_stride = ~(size_t)0;
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(views, h_views, S, count, &whole, &cs));
+    JA_TRY(t.check(c.n_images));
+    const ResizePlan plan = plan_resize_chunks(c.n_images, h_views, t);
+    JA_TRY(plan.status);
+    JA_TRY(bind(ctx));
+    if (c.n_images == 0) return JPEG_AMD_OK;
+    return resample_chunks(ctx, plan, t, [&](size_t, const ResizeChunk &k, uint8_t *d_views) {
+        const int16_t *coef[JPEG_AMD_MAX_PLANES] = {};
+        const DecodeCall part = c.images(k.i0, k.m, coef);
+        return jpeg_amd_decode_view_batch(ctx, c.L, k.m, coef, c.coef_stride, part.d_quanta, c.quanta_stride, c.ntables, c.cosited,
+                                          c.color, h_views + k.i0, d_views, k.stride);
+    });
+}
+
+}  // namespace
+
+int jpeg_amd_resize_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_resize_filter_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, d_dst, dst_stride);
+}
+
+int jpeg_amd_decode_resized_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                  const int16_t *const d_coef[], const size_t coef_stride[],
+                                  const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                  int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                  int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride)
+{
+    return jpeg_amd_decode_resized_filter_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, h_views,
+                                                out_w, out_h, JPEG_AMD_FILTER_BILINEAR, d_pixels, pixel_stride);
+}
+
+int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                            const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                            const jpeg_amd_view *view, int32_t out_w, int32_t out_h, uint8_t *d_pixels)
+{
+    // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
+    JA_TRY(check_one_view(L, ntables, color, view));
+    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_pixels, 0}.check(1)));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    return jpeg_amd_decode_resized_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, d_pixels,
+                                         0);
+}
+
+int jpeg_amd_tensor_extent(const jpeg_amd_tensor_spec *spec, int32_t out_w, int32_t out_h, size_t *elem_bytes, size_t *image_elems)
+{
+    if (!spec) return JPEG_AMD_EINVAL;
+    if (spec->dtype != JPEG_AMD_F32 && spec->dtype != JPEG_AMD_F16 && spec->dtype != JPEG_AMD_BF16) return JPEG_AMD_EINVAL;
+    if (spec->layout != JPEG_AMD_TENSOR_HWC && spec->layout != JPEG_AMD_TENSOR_CHW) return JPEG_AMD_EINVAL;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(spec->mean[c]) || !std::isfinite(spec->scale[c])) return JPEG_AMD_EINVAL;
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    if (resize_tiles(out_w, out_h) > 0x7fffffffu) return JPEG_AMD_EINVAL;   // more workgroups than a grid holds
+    if (elem_bytes) *elem_bytes = spec->dtype == JPEG_AMD_F32 ? 4 : 2;
+    if (image_elems) *image_elems = (size_t)3 * out_w * out_h;
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_resize_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_resize_filter_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, spec, h_flip,
+                                               d_dst, dst_stride);
+}
+
+int jpeg_amd_decode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                 const int16_t *const d_coef[], const size_t coef_stride[],
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                 int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                 void *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_decode_tensor_filter_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, h_views,
+                                               out_w, out_h, JPEG_AMD_FILTER_BILINEAR, spec, h_flip, d_dst, dst_stride);
+}
+
+int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const int16_t *const d_coef[],
+                           const uint16_t *h_quanta, int ntables, int cosited, jpeg_amd_color color,
+                           const jpeg_amd_view *view, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
+                           int flip, void *d_dst)
+{
+    // as jpeg_amd_decode_resized: what can be refused is refused before a table is staged
+    JA_TRY(check_one_view(L, ntables, color, view));
+    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, nullptr, d_dst, 0}.check(1)));
+    JA_TRY(bind(ctx));
+    const uint16_t *d_q = nullptr;
+    JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
+    const uint8_t h_flip = flip ? 1 : 0;
+    return jpeg_amd_decode_tensor_batch(ctx, L, 1, d_coef, kOneImage, d_q, 0, ntables, cosited, color, view, out_w, out_h, spec,
+                                        &h_flip, d_dst, 0);
+}
+
+namespace {
+
+constexpr int kMixedGroups = 2 * kViewDenoms;   // group 2 k + (three planes): the images of N = 8 >> k with that many planes
+
+// Images [0, m) of a mixed call, or of a chunk of one, sorted into the launches of k_view_decode_mixed and the images that
+// take the uniform call.
+struct MixedPlan {
+    std::vector<uint32_t> members[kMixedGroups];   // the group's images, in index order
+    std::vector<int> fallback;                     // no tile kernel for the layout: the uniform call, image by image
+};
+
+// What the uniform view call with n_images = 1 judges of image `im` with view `v`, in its order (check_views itself), then the
+// stride that the mixed call's placement needs.
+int check_mixed_image(const jpeg_amd_image &im, int n_images, int cosited, jpeg_amd_color color, const jpeg_amd_view &v,
+                      const void *d_out, size_t pixel_stride)
+{
+    const DecodeCall c{&im.layout, 1, im.d_coef, kOneImage, im.d_quanta, 0, im.ntables, cosited, color,
+                       static_cast<uint8_t *>(const_cast<void *>(d_out)), 0};
+    jpeg_amd_layout S[kViewDenoms];
+    int count[kViewDenoms] = {0, 0, 0, 0};
+    bool whole = true;
+    PlaneSet cs{};
+    JA_TRY(check_views(c, &v, S, count, &whole, &cs));
+    if (n_images > 1 && pixel_stride < (size_t)3 * v.region.width * v.region.height) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// The plan of m checked images; EINVAL: a launch of more workgroups than a grid holds (refused here, before the context is
+// looked at, and so never by run_mixed).
+int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosited, MixedPlan *plan)
+{
+    uint64_t acc[kMixedGroups] = {};
+    for (int i = 0; i < m; ++i) {
+        if (!fused_decode_supported(im[i].layout, cosited != 0)) {
+            plan->fallback.push_back(i);
+            continue;
+        }
+        const int k = view_slot(v[i].denom), g = 2 * k + (im[i].layout.nplanes == 3 ? 1 : 0);
+        plan->members[g].push_back((uint32_t)i);
+        acc[g] += view_tiles(8 >> k, v[i].region);
+    }
+    for (int g = 0; g < kMixedGroups; ++g)
+        if (acc[g] > 0x7fffffffu) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+
+// The planned images into d_pixels, image i at i * pixel_stride: one copy of the records [m], then per group its index list
+// and tile prefix (stage_group), into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when
+// the call returns -- as stage_quanta); a launch per group; the uniform call for each of the others.
+int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *v, int m, const MixedPlan &plan, int cosited,
+              jpeg_amd_color color, uint8_t *d_pixels, size_t pixel_stride)
+{
+    const size_t rec_bytes = mixed_record_bytes(), lists = rec_bytes * (size_t)m / 4;
+    size_t words = 0;
+    for (int g = 0; g < kMixedGroups; ++g)
+        if (!plan.members[g].empty()) words += 2 * plan.members[g].size() + 1;
+    if (words != 0) {
+        std::vector<uint32_t> buf;
+        buf.reserve(lists + words);
+        buf.resize(lists);   // the records of the uniform call's images stay zero: no list names them
+        size_t at[kMixedGroups] = {};
+        uint32_t nwg[kMixedGroups] = {};
+        for (int g = 0; g < kMixedGroups; ++g) {
+            const std::vector<uint32_t> &mem = plan.members[g];
+            if (mem.empty()) continue;
+            const int n = 8 >> (g / 2);
+            for (const uint32_t i : mem)
+                mixed_record(reinterpret_cast<uint8_t *>(buf.data()) + rec_bytes * i, im[i].layout, n, im[i].d_coef, im[i].d_quanta,
+                             v[i].region, d_pixels + (size_t)i * pixel_stride);
+            at[g] = buf.size();
+            JA_TRY(stage_group(buf, mem, n, v, &nwg[g]));
+        }
+        JA_TRY(ensure_buffer(ctx, ctx->mixed, 4 * buf.size()));
+        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, ctx->stream));
+        const uint32_t *d_w = static_cast<const uint32_t *>(ctx->mixed.ptr);
+        for (int g = 0; g < kMixedGroups; ++g) {
+            const int count = (int)plan.members[g].size();
+            if (count == 0) continue;
+            JA_HIP(ctx, launch_view_decode_mixed(ctx->stream, count, 8 >> (g / 2), g % 2 ? 3 : 1, color == JPEG_AMD_COLOR_RGB8,
+                                                 ctx->mixed.ptr, d_w + at[g], d_w + at[g] + count, nwg[g]));
+        }
+    }
+    for (const int i : plan.fallback)
+        JA_TRY(jpeg_amd_decode_view_batch(ctx, &im[i].layout, 1, im[i].d_coef, kOneImage, im[i].d_quanta, 0, im[i].ntables, cosited,
+                                          color, &v[i], d_pixels + (size_t)i * pixel_stride, 0));
+    return JPEG_AMD_OK;
+}
+
+// jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed: decode_resampled's route with the mixed view decode.
+int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                  const jpeg_amd_view *h_views, ResampleTarget t)
+{
+    // every argument first, the context last; the target is judged where the uniform call judges it: behind the first image
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
+    for (int i = 0; i < n_images; ++i) {
+        JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], t.d_dst, 0));   // the views' stride is ours
+        if (i == 0) JA_TRY(t.check(n_images));
+    }
+    if (n_images == 0) JA_TRY(t.check(n_images));
+    const ResizePlan plan = plan_resize_chunks(n_images, h_views, t);
+    std::vector<MixedPlan> plans(plan.chunks.size());
+    for (size_t c = 0; c < plans.size(); ++c)
+        JA_TRY(plan_mixed(h_images + plan.chunks[c].i0, h_views + plan.chunks[c].i0, plan.chunks[c].m, cosited, &plans[c]));
+    JA_TRY(plan.status);
+    if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
+    JA_TRY(bind(ctx));
+    return resample_chunks(ctx, plan, t, [&](size_t c, const ResizeChunk &k, uint8_t *d_views) {
+        return run_mixed(ctx, h_images + k.i0, h_views + k.i0, k.m, plans[c], cosited, color, d_views, k.stride);
+    });
+}
+
+}  // namespace
+
+int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                               jpeg_amd_color color, const jpeg_amd_view *h_views, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
+    for (int i = 0; i < n_images; ++i) JA_TRY(check_mixed_image(h_images[i], n_images, cosited, color, h_views[i], d_pixels, pixel_stride));
+    MixedPlan plan;
+    JA_TRY(plan_mixed(h_images, h_views, n_images, cosited, &plan));
+    if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
+    JA_TRY(bind(ctx));
+    return run_mixed(ctx, h_images, h_views, n_images, plan, cosited, color, d_pixels, pixel_stride);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                  jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                  uint8_t *d_pixels, size_t pixel_stride)
+{
+    return jpeg_amd_decode_resized_filter_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, JPEG_AMD_FILTER_BILINEAR,
+                                                d_pixels, pixel_stride);
+}
+
+int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                 jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_decode_tensor_filter_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, spec,
+                                               h_flip, d_dst, dst_stride);
+}
+
+// The six resample calls with the filter chosen by the caller ("antialiased resample"); their forms without a filter argument,
+// above, are these with JPEG_AMD_FILTER_BILINEAR.
+int jpeg_amd_resize_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter, uint8_t *d_dst,
+                                 size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_resize_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                         const int16_t *const d_coef[], const size_t coef_stride[],
+                                         const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                         int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                         int32_t out_w, int32_t out_h, int filter, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, 0},
+                            h_views, ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
+                                        const int16_t *const d_coef[], const size_t coef_stride[],
+                                        const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                        int cosited, jpeg_amd_color color, const jpeg_amd_view *h_views,
+                                        int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                        const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+try {
+    return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
+                                            static_cast<uint8_t *>(d_dst), 0},
+                            h_views, ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                         int filter, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                                        size_t dst_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+}
+JA_NOTHROW_TAIL

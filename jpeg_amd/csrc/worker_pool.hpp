@@ -1,11 +1,14 @@
-// worker_pool.hpp -- the host threads of the batch file paths (capi.hip).  Header-only and free of HIP so that
-// tests/cpp/worker_pool_test.cpp can run it under ThreadSanitizer on a machine without a GPU.
+// worker_pool.hpp -- the host threads of the batch file paths (capi_file.hip): the pool, the file queue of the batch decode
+// and the drain of its pixels.  Header-only and free of HIP so that tests/cpp/worker_pool_test.cpp can run it under
+// ThreadSanitizer on a machine without a GPU.
 #pragma once
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -179,6 +182,63 @@ private:
     std::atomic<int> next_{0};
     int open_ = 0;
     bool abort_ = false;
+};
+
+// m images of `bytes` bytes each, cut into pieces of at most `piece` bytes so that one huge image is shared by the threads of
+// a region too: item j of count(m) is bytes [lo, lo + len) of image i.
+struct Pieces {
+    size_t bytes, piece, per_image;
+    Pieces(size_t bytes_, size_t piece_) : bytes(bytes_), piece(piece_), per_image((bytes_ + piece_ - 1) / piece_) {}
+    int count(int m) const { return (int)(per_image * (size_t)m); }
+    struct At { size_t i, lo, len; };
+    At at(size_t j) const
+    {
+        const size_t lo = (j % per_image) * piece;
+        return At{j / per_image, lo, std::min(piece, bytes - lo)};
+    }
+};
+
+// The way back of a chunk's pixels in jpeg_amd_decompress_batch: m images of `bytes` bytes, one behind the other at `src`, are
+// copied to `dst` at a pitch of `dst_stride` by the threads of a pool (pieces of <= 8 MiB; the test takes smaller ones) once
+// their download is complete.
+// `arrived` waits for the download and says whether the pixels are there: the first thread to get to the region runs it,
+// exactly once, and the others wait for that thread; nothing is copied before it has answered true, and nothing at all once it
+// has answered false.  begin() returns at once; end() has the calling thread copy too, joins the region and reports whether
+// the pixels arrived (true as well when nothing was begun).  The destructor joins: no region outlives its drain.
+class PixelDrain {
+public:
+    PixelDrain(WorkerPool *pool, int threads, size_t piece = (size_t)8 << 20) : pool_(pool), threads_(threads), piece_(piece) {}
+    ~PixelDrain() { (void)end(); }
+    PixelDrain(const PixelDrain &) = delete;
+    PixelDrain &operator=(const PixelDrain &) = delete;
+    void begin(int m, const uint8_t *src, size_t bytes, uint8_t *dst, size_t dst_stride, std::function<bool()> arrived)
+    {
+        const Pieces pieces(bytes, piece_);
+        state_.store(0);
+        draining_ = true;
+        pool_->begin(pieces.count(m), [this, pieces, src, dst, dst_stride, arrived](int j) {
+            int zero = 0;
+            if (state_.compare_exchange_strong(zero, 1)) state_.store(arrived() ? 2 : 3);
+            while (state_.load() < 2) std::this_thread::sleep_for(std::chrono::microseconds(50));
+            if (state_.load() != 2) return;
+            const Pieces::At p = pieces.at((size_t)j);
+            std::memcpy(dst + p.i * dst_stride + p.lo, src + pieces.bytes * p.i + p.lo, p.len);
+        }, threads_);
+    }
+    bool end()
+    {
+        if (!draining_) return true;
+        pool_->finish();
+        draining_ = false;
+        return state_.load() == 2;
+    }
+
+private:
+    WorkerPool *pool_;
+    const int threads_;
+    const size_t piece_;
+    std::atomic<int> state_{0};      // 0: nobody has looked yet, 1: a thread is waiting, 2: the pixels are there, 3: failed
+    bool draining_ = false;
 };
 
 }  // namespace jpeg_amd

@@ -1,8 +1,9 @@
-// WorkerPool and FileQueue (jpeg_amd/csrc/worker_pool.hpp) under ThreadSanitizer: every item of every region runs exactly once,
+// WorkerPool, FileQueue and PixelDrain (jpeg_amd/csrc/worker_pool.hpp) under ThreadSanitizer: every item of every region runs exactly once,
 // a region uses no more threads than it was given, begin() returns before the work is done and finish() joins it, regions of
 // every size follow each other on one pool; the file queue of jpeg_amd_decompress_batch decodes every file exactly once and
 // every chunk completely, on the calling thread when the pool has no helper, and a call that fails in chunk 0 while chunk 1 is
-// being decoded stops its threads before it trims their records and never starts a chunk that was not opened.
+// being decoded stops its threads before it trims their records and never starts a chunk that was not opened; the pixel drain
+// of that call: drain_failures() below.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -16,7 +17,58 @@
 #include "worker_pool.hpp"
 
 using jpeg_amd::FileQueue;
+using jpeg_amd::PixelDrain;
 using jpeg_amd::WorkerPool;
+
+// The pixel drain of jpeg_amd_decompress_batch (PixelDrain): m images of 1, 3 and 33 pieces (and of 33 pieces and a rest) to
+// a destination with a pitch, on pools of 1, 2, 5 and 16 threads, several drains back to back on each pool.  A drain whose
+// pixels arrive: the callable runs exactly once, held for a few milliseconds it still finds the destination untouched when it
+// answers, and afterwards every byte of every image is there and the pitch's gaps are not written (two threads copying one
+// piece would be a data race, which ThreadSanitizer reports).  A drain whose callable answers false copies nothing and end()
+// says so.  A drain that is begun and then abandoned is joined by its destructor, with the pixels copied.
+static int drain_failures()
+{
+    int failures = 0;
+    const size_t piece = 64, gap = 24;
+    const int m = 5;
+    for (int pool_threads : {1, 2, 5, 16}) {
+        WorkerPool pool(pool_threads);
+        for (size_t bytes : {piece, 3 * piece, 33 * piece, 33 * piece + 7}) {
+            const size_t pitch = bytes + gap;
+            std::vector<uint8_t> src(bytes * m), dst;
+            for (size_t b = 0; b < src.size(); ++b) src[b] = (uint8_t)(1 + b % 251);   // never the 0 the destination starts from
+            for (int mode = 0; mode < 3; ++mode) {                                     // 0: arrives, 1: fails, 2: arrives, abandoned
+                dst.assign(pitch * m, 0);
+                std::atomic<int> calls{0};
+                bool early = false, ended = true;
+                auto arrived = [&]() -> bool {
+                    calls.fetch_add(1);
+                    std::this_thread::sleep_for(std::chrono::milliseconds(3));
+                    for (uint8_t v : dst) early = early || v != 0;                     // (a copy under way here is a race for TSan too)
+                    return mode != 1;
+                };
+                {
+                    PixelDrain drain(&pool, pool_threads, piece);
+                    if (!drain.end()) { std::printf("drain: end() without begin() failed\n"); ++failures; }
+                    drain.begin(m, src.data(), bytes, dst.data(), pitch, arrived);
+                    if (mode != 2) ended = drain.end();
+                }
+                const char *what = mode == 0 ? "arrives" : mode == 1 ? "fails" : "abandoned";
+                if (calls.load() != 1) { std::printf("drain %s, pool %d, %zu bytes: the callable ran %d times\n", what, pool_threads, bytes, calls.load()); ++failures; }
+                if (early) { std::printf("drain %s, pool %d, %zu bytes: copied before the callable answered\n", what, pool_threads, bytes); ++failures; }
+                if (ended != (mode != 1)) { std::printf("drain %s, pool %d, %zu bytes: end() returned %d\n", what, pool_threads, bytes, (int)ended); ++failures; }
+                size_t wrong = 0;
+                for (size_t b = 0; b < dst.size(); ++b) {
+                    const size_t i = b / pitch, at = b % pitch;
+                    const uint8_t want = mode != 1 && at < bytes ? src[i * bytes + at] : 0;
+                    wrong += dst[b] != want;
+                }
+                if (wrong) { std::printf("drain %s, pool %d, %zu bytes: %zu bytes of the destination are wrong\n", what, pool_threads, bytes, wrong); ++failures; }
+            }
+        }
+    }
+    return failures;
+}
 
 int main()
 {
@@ -110,6 +162,7 @@ int main()
         }
         for (int f = 0; f < files; ++f) if (hits[(size_t)f] != 1) { std::printf("no helper: file %d ran %d times\n", f, hits[(size_t)f]); ++failures; }
     }
+    failures += drain_failures();
     std::printf("%s\n", failures ? "FAILED" : "ok");
     return failures ? 1 : 0;
 }

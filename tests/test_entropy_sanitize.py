@@ -26,7 +26,8 @@ def test_entropy_coder_is_clean_under_asan_and_ubsan(tmp_path):
 def test_worker_pool_is_clean_under_tsan(tmp_path):
     """The host thread pool of the batch file paths (csrc/worker_pool.hpp) under ThreadSanitizer: regions of every size and
     thread limit on pools of 1, 2, 5 and 16 threads -- every item exactly once, never more threads than the region was given,
-    begin() / finish() apart -- and the directing-thread queue pattern of jpeg_amd_decompress_batch to its end."""
+    begin() / finish() apart -- the directing-thread queue pattern of jpeg_amd_decompress_batch to its end, and the drain of
+    its pixels (every byte once, the wait for the download exactly once and before any copy, failure, abandonment)."""
     exe = str(tmp_path / "worker_pool_test")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "jpeg_amd", "csrc"),
                            os.path.join(ROOT, "tests", "cpp", "worker_pool_test.cpp"), "-o", exe, "-lpthread"])

@@ -148,17 +148,19 @@ def test_twelve_bit_four_component_compress_reproduces_the_references_file(ctx):
     assert bytes(out) == data.tobytes()
 
 
-@pytest.mark.parametrize("pinned", [False, True])
-def test_compress_batch_over_several_chunks_pageable_and_pinned_pixels(ctx, pinned):
+@pytest.mark.parametrize("pinned, pitch", [(False, 32), (True, 32), (False, 0), (True, 0)],
+                         ids=["False", "True", "False-contiguous", "True-contiguous"])
+def test_compress_batch_over_several_chunks_pageable_and_pinned_pixels(ctx, pinned, pitch):
     """70 pictures = three chunks of the pipeline; the pixels either in pageable memory (staged through the library's pinned
-    slots by the host threads) or page-locked (uploaded from where they are), with a pitch between the pictures; picture i
+    slots by the host threads) or page-locked (uploaded from where they are), with a pitch of 32 bytes between the pictures
+    (page-locked: a copy per picture) or none, passed as a stride of 0 (page-locked: one copy per chunk); picture i
     is the example picture with its first bytes changed, so that a chunk or slot mix-up cannot go unnoticed."""
     import torch
     import jpeg_amd as J
     case = next(c for c in G.encode_cases() if c["mode"] == "4-2-0" and c["level"] == 0.5)
     rgb, (w, h) = G.encode_source()
     n = 70
-    stride = w * h * 3 + 32
+    stride = w * h * 3 + pitch
     holder = torch.zeros(n * stride, dtype=torch.uint8, pin_memory=pinned)
     px = holder.numpy()
     for i in range(n):
@@ -178,7 +180,7 @@ def test_compress_batch_over_several_chunks_pageable_and_pinned_pixels(ctx, pinn
     for threads in (1, 6):
         out = np.zeros((n, cap), np.uint8)
         sizes = (C.c_size_t * n)()
-        st = lib.jpeg_amd_compress_batch(ctx.handle, C.byref(info), px.ctypes.data, stride, n, J.RGB.code, qkey, tables.ctypes.data,
+        st = lib.jpeg_amd_compress_batch(ctx.handle, C.byref(info), px.ctypes.data, stride if pitch else 0, n, J.RGB.code, qkey, tables.ctypes.data,
                                          tk, 2, sarr, 2, marr, nmeta, threads, out.ctypes.data, cap, sizes)
         assert st == 0, st
         for i in range(n):

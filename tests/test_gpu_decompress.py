@@ -149,11 +149,13 @@ def test_twelve_bit_four_component_file_through_the_staged_path(ctx):
     assert rect.max() > 255          # really more than 8 bits
 
 
-@pytest.mark.parametrize("pinned", [False, True])
-def test_decompress_batch_over_several_chunks_pageable_and_pinned_output(ctx, pinned):
+@pytest.mark.parametrize("pinned, pitch", [(False, 64), (True, 64), (False, 0), (True, 0)],
+                         ids=["False", "True", "False-contiguous", "True-contiguous"])
+def test_decompress_batch_over_several_chunks_pageable_and_pinned_output(ctx, pinned, pitch):
     """70 files = three chunks of the pipeline (both pinned / device slots are reused); the output either in pageable memory
     (downloaded into the library's pinned slot and copied out by the host threads) or page-locked (downloaded straight into
-    the caller's buffer), with a row pitch between the images."""
+    the caller's buffer), with a pitch of 64 bytes between the images (page-locked: a copy per image) or none, passed as a
+    stride of 0 (page-locked: one copy per chunk)."""
     import torch
     import jpeg_amd as J
     lib = _lib.lib()
@@ -163,14 +165,14 @@ def test_decompress_batch_over_several_chunks_pageable_and_pinned_output(ctx, pi
     n = 70
     batch = [files[i % len(files)] for i in range(n)]
     w, h = G.entry(names[0])["width"], G.entry(names[0])["height"]
-    stride = w * h * 3 + 64
+    stride = w * h * 3 + pitch
     holder = torch.zeros(n * stride, dtype=torch.uint8, pin_memory=pinned)
     out = holder.numpy()
     ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in batch])
     sizes = (C.c_size_t * n)(*[f.size for f in batch])
     for threads in (1, 5):
         out[:] = 0
-        st = lib.jpeg_amd_decompress_batch(ctx.handle, ptrs, sizes, n, threads, 0, J.RGB.code, out.ctypes.data, stride, None)
+        st = lib.jpeg_amd_decompress_batch(ctx.handle, ptrs, sizes, n, threads, 0, J.RGB.code, out.ctypes.data, stride if pitch else 0, None)
         assert st == 0, st
         for i in range(n):
             assert G.sha(out[i * stride:i * stride + w * h * 3]) == G.entry(names[i % len(names)])["gold"]["rgb_sha256"], (i, threads)

@@ -3,9 +3,11 @@ pointers is called with a NULL context (bind then returns EINVAL before any HIP 
 one of them valid and the others wrong in one more way.  Most entry points look at the context first and so answer EINVAL
 whatever else is wrong; the view, resized and resize calls judge everything else first, and there the layout's verdict
 (ENOSUP for 12 bits) comes through.  The expected statuses are not reasoned out: they are what the library returned before
-the argument handling of capi.hip was gathered into one record, so a change of the order of checks shows here.  A second
-table holds calls that are wrong twice, in the view (ENOSUP) and in the target (EINVAL): there the order between the two
-checks shows, and what an empty call answers without a context."""
+the argument handling of the C layer (jpeg_amd/csrc/capi*.hip) was gathered into one record, so a change of the order of
+checks shows here.  The six resample calls are there twice, without a filter argument and as their *_filter_* forms with the
+bilinear filter: the first forward to the second.  A second table holds calls that are wrong twice, in the view (ENOSUP) and
+in the target (EINVAL), and calls with an unknown filter: there the order between the checks shows, and what an empty call
+answers without a context."""
 import ctypes as C
 
 import numpy as np
@@ -57,6 +59,8 @@ def image(layout, p):
 
 
 RGB = _lib.COLOR_RGB8
+BILINEAR = _lib.FILTER_BILINEAR
+UNKNOWN_FILTER = 7
 # name -> the arguments behind the context, from an Args
 CALLS = {
     "jpeg_amd_decode_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.p, 768),
@@ -76,6 +80,14 @@ CALLS = {
     "jpeg_amd_decode_view_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, a.p, 768),
     "jpeg_amd_decode_resized_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, a.p, 768),
     "jpeg_amd_decode_tensor_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192),
+    # ... and with the filter named: the argument sets of the six calls without one, the bilinear filter
+    "jpeg_amd_resize_filter_batch": lambda a: (a.n, a.p, 48, a.e, 8, 8, BILINEAR, a.p, 192),
+    "jpeg_amd_resize_filter_tensor_batch": lambda a: (a.n, a.p, 48, a.e, 8, 8, BILINEAR, a.s, None, a.p, 192),
+    "jpeg_amd_decode_resized_filter_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, BILINEAR, a.p, 768),
+    "jpeg_amd_decode_tensor_filter_batch":
+        lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, BILINEAR, a.s, None, a.p, 192),
+    "jpeg_amd_decode_resized_filter_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, BILINEAR, a.p, 768),
+    "jpeg_amd_decode_tensor_filter_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, BILINEAR, a.s, None, a.p, 192),
     "jpeg_amd_encode_batch": lambda a: (a.L, a.n, a.p, 768, RGB, a.p, 64, 2, a.pp, a.sz),
     "jpeg_amd_encode": lambda a: (a.L, a.p, RGB, a.p, 2, a.pp),
     "jpeg_amd_spectral_rectangular_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, a.p, 768),
@@ -121,6 +133,12 @@ EXPECTED = {
     "jpeg_amd_decode_view_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_decode_resized_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_decode_tensor_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_resize_filter_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_resize_filter_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_resized_filter_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor_filter_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_resized_filter_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor_filter_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_encode_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
     "jpeg_amd_encode": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
     "jpeg_amd_spectral_rectangular_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
@@ -213,6 +231,30 @@ TWICE = {
     "tensor batch, empty":
         (lambda: call("jpeg_amd_decode_tensor_batch", "valid",
                       lambda a: (a.L, 0, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, a.s, None, a.p, 192)), EINVAL),
+    # an unknown filter: the target's to refuse, behind the view (a 12-bit layout comes first) and with no image at all
+    "resize filter batch, unknown filter":
+        (lambda: call("jpeg_amd_resize_filter_batch", "valid", lambda a: (1, a.p, 48, a.e, 8, 8, UNKNOWN_FILTER, a.p, 192)), EINVAL),
+    "resize filter batch, unknown filter, empty":
+        (lambda: call("jpeg_amd_resize_filter_batch", "valid", lambda a: (0, a.p, 48, a.e, 8, 8, UNKNOWN_FILTER, a.p, 192)), EINVAL),
+    "resize filter tensor batch, unknown filter":
+        (lambda: call("jpeg_amd_resize_filter_tensor_batch", "valid",
+                      lambda a: (1, a.p, 48, a.e, 8, 8, UNKNOWN_FILTER, a.s, None, a.p, 192)), EINVAL),
+    "resized filter batch, unknown filter":
+        (lambda: call("jpeg_amd_decode_resized_filter_batch", "valid",
+                      lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.p, 768)), EINVAL),
+    "resized filter batch, 12 bits and an unknown filter":
+        (lambda: call("jpeg_amd_decode_resized_filter_batch", T12,
+                      lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.p, 768)), ENOSUP),
+    "tensor filter batch, unknown filter":
+        (lambda: call("jpeg_amd_decode_tensor_filter_batch", "valid",
+                      lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.s, None, a.p, 192)), EINVAL),
+    "resized filter mixed, unknown filter":
+        (lambda: call("jpeg_amd_decode_resized_filter_mixed", "valid", lambda a: (1, a.im, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.p, 768)), EINVAL),
+    "resized filter mixed, unknown filter, empty":
+        (lambda: call("jpeg_amd_decode_resized_filter_mixed", "valid", lambda a: (0, a.im, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.p, 768)), EINVAL),
+    "tensor filter mixed, unknown filter":
+        (lambda: call("jpeg_amd_decode_tensor_filter_mixed", "valid",
+                      lambda a: (1, a.im, 0, RGB, a.v, 8, 8, UNKNOWN_FILTER, a.s, None, a.p, 192)), EINVAL),
     "view mixed, empty":
         (lambda: call("jpeg_amd_decode_view_mixed", "valid", lambda a: (0, a.im, 0, RGB, a.v, a.p, 768)), OK),
     "resized mixed, empty":

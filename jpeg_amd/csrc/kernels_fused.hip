@@ -22,6 +22,12 @@
 // 4250) because 0.25*c + 0.75*c == c exactly.  Everything that rounds (dequantise, IDCT,
 // colour matrix) is evaluated op-for-op as in dct.hpp / the reference.
 //
+// What this walk has in common with k_quad420 is stated once, in fused_common.hpp ("the strip walks' shared stages"): the block
+// fetch from the swizzled LDS image, the table modulation, the counted wait for the DMA, the 2x chroma row, the vertical window,
+// the floor-free rounding, the colour matrix and the whole pixel store path (StripStore).  Here: the walk itself, the chroma
+// passes of the three layouts, the 4:4:4 stash, the pair walk, the priorities -- and the source swizzle, sgpr() and the
+// resource over a strip's block rows, which change this kernel's instructions when hoisted (profiles/strip_walk_shared_isa.txt).
+//
 // No development switches in this file.  Measured against this kernel: it without its transform, without its stores, without
 // the priorities of its last strips (tools/ablate.sh; profiles/HISTORY.md, profiles/r02_ab_experiments.txt).  Those switches
 // are in tools/exp_patches/ablation_switches.diff, and tools/build_exp.py makes the A/B builds.
@@ -115,7 +121,6 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
     constexpr bool INTHREAD = CHROMA && SX == 1 && SY == 1;
     constexpr int PLANE = (CHROMA && !INTHREAD) ? ROWS * PITCH : 1;   // dwords per plane of the tile
     constexpr int SEG_DW = BX * 6;                       // one pixel row of one block row: 24 B per block
-    constexpr int CPS = SEG_DW / 4;                      // 16-byte chunks per such segment
     // 4:2:2 (wide strips): the 16 x 2 chroma blocks per plane under a strip are exactly one block per
     // work-item for both planes together; a second, nearly empty pass transforms the 8 neighbour
     // blocks that supply the one-sample halo left and right.  No chroma intermediate in HBM (round 2; it was
@@ -265,13 +270,10 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
 
         // ---- modulated table (only when the image changes) ----
         if (img != img_of_table) {
-            const int qk = lane & 7, qh = lane >> 3;
-            sq[8 * qk + qh] = modulate_entry(qk, qh, 0.125f, a.quanta[img * a.quanta_stride + 64 * a.qi + zigzag_of(qk, qh)]);
+            modulate_table(sq, a.quanta, img, a.quanta_stride, a.qi, lane);
             if constexpr (INSTRIP) {
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    sqw[wave][1 + pl][8 * qk + qh] = modulate_entry(qk, qh, 0.125f,
-                        a.quanta[img * a.quanta_stride + 64 * a.cqi[pl] + zigzag_of(qk, qh)]);
+                for (int pl = 0; pl < 2; ++pl) modulate_table(sqw[wave][1 + pl], a.quanta, img, a.quanta_stride, a.cqi[pl], lane);
             }
             img_of_table = img;
         }
@@ -281,8 +283,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
         //      strip's pixel stores: when that strip took the branch-free store path (exactly
         //      2 store instructions per pixel row) only the DMA has to be waited for, not the
         //      16 stores behind it. ----
-        if (stores_behind_dma == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_dma(stores_behind_dma);
         // The waves of a SIMD do not advance at the same pace: the scheduler issues the oldest ready wave first, so with
         // equal shares the first wave of a SIMD is done long before the last (8192 x 8192, four strips each: ends between
         // 30 and 72 us, tools/phase_profile.py) and the SIMD spends the end of the launch with one or two waves -- too
@@ -297,16 +298,9 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             else __builtin_amdgcn_s_setprio(0);
         }
         uint32_t w[32];
-        auto read_block = [&]() {
-            const uint4 *cw = reinterpret_cast<const uint4 *>(coef_w) + 8 * lane;
-            const int sw = (lane >> 1) & 7;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const uint4 v = cw[i ^ sw];
-                w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-            }
-        };
-        read_block();
+        // (a wrapper, like put_row below: read_block of fused_common.hpp called directly is compiled to other device code)
+        auto fetch_block = [&]() { read_block(coef_w, lane, w); };
+        fetch_block();
         // 4:4:4: the work-item's own Cb / Cr samples, four to a dword, wait in 32 registers while the luma block is
         // transformed (as 8 KiB of LDS per wave they held the kernel at two waves per SIMD)
         uint32_t stash[2][INTHREAD ? 16 : 1];
@@ -330,7 +324,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
                 for (int i = 0; i < (INTHREAD ? 16 : 1); ++i) asm volatile("" : "+v"(stash[pl][i]));
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                read_block();
+                fetch_block();
             }
         }
 
@@ -395,7 +389,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             }
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            read_block();
+            fetch_block();
         }
 
         if constexpr (IN440) {
@@ -419,7 +413,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                read_block();
+                fetch_block();
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             dma_at(img, syi0, sxi, lane, 0);
@@ -452,7 +446,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             }
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            read_block();
+            fetch_block();
           }
         }
 
@@ -493,12 +487,10 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             }
         };
         // 4:2:2 / 4:4:0: the samples enter as 2^15 + p + 1/32 (ubyte_magic, upsample.hpp) so that the ONE 3a + b step is exact
-        // (2^17 + v + 1/8) and its rounding needs no floor (finish)
+        // (2^17 + v + 1/8) and its rounding needs no floor (chroma_finish, fused_common.hpp)
         auto hconv = [&](const uint32_t (&r)[3], float (&o)[8]) {
             if constexpr (SX == 2) {
-                const float p[6] = {ubyte_magic<3>(r[0]), ubyte_magic<0>(r[1]), ubyte_magic<1>(r[1]),
-                                    ubyte_magic<2>(r[1]), ubyte_magic<3>(r[1]), ubyte_magic<0>(r[2])};
-                lerp_row_2x(p, o);
+                hconv_2x(r, o);
             } else if constexpr (SY == 2) {
                 o[0] = ubyte_magic<0>(r[0]); o[1] = ubyte_magic<1>(r[0]); o[2] = ubyte_magic<2>(r[0]); o[3] = ubyte_magic<3>(r[0]);
                 o[4] = ubyte_magic<0>(r[1]); o[5] = ubyte_magic<1>(r[1]); o[6] = ubyte_magic<2>(r[1]); o[7] = ubyte_magic<3>(r[1]);
@@ -513,13 +505,10 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             hconv(r, o);
         };
         // final chroma value of one pixel.  4:4:4: the sample itself [- 128].  One subsampled axis: floor(v / 4 + 1/2) [- 128] of
-        // v = 3a + b, without a floor -- V = 2^17 + v + 1/8 arrives exact, and fma(V, 1/4, 1.5 * 2^23 - 2^15 [- 128]) is ONE rounding of
-        // 1.5 * 2^23 [- 128] + v / 4 + 1/32 to a float whose ulp is 1; v / 4 + 1/32 is never half-way, and at v / 4 = n + 1/2 the 1/32
-        // tips it up like the reference's round-half-away (tests/test_colour_rounding.py enumerates every byte pair).  An FMA and a
-        // subtraction instead of an FMA and a v_floor_f32 (half rate): -128 slow instructions per strip.
+        // v = 3a + b (chroma_finish, fused_common.hpp)
         auto finish = [&](float v) -> float {
             if constexpr (SX == 1 && SY == 1) return MODE == 1 ? v - 128.0f : v;
-            else return __builtin_fmaf(v, 0.25f, kMagic - 32768.0f - (MODE == 1 ? 128.0f : 0.0f)) - kMagic;
+            else return chroma_finish<MODE, 4>(v);
         };
 
         float hw[2][3][8];  // SY == 2: patch rows j-1, j, j+1 of both planes (sliding window)
@@ -532,36 +521,9 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             for (int pl = 0; pl < 2; ++pl) hraw(pl, 0, rawn[pl]);
         }
 
-        // ---- store geometry: per pixel row the strip's BY segments are 96 chunks of 16 B; a lane
-        //      stores chunk `lane` (and lanes 0..31 also chunk 64 + lane).  Byte offsets relative to
-        //      the strip's first pixel are computed once; the row advance is scalar.  Both store
-        //      instructions of a row cover whole 128-byte lines (segments are 768 or 384 B). ----
-        const int tile_px = min(BX * 8, a.W - BX * 8 * sxi);    // pixels of this strip inside the image
-        const int nb = 3 * tile_px;                              // bytes per row segment to write
-        const uint32_t pitch = 3u * a.W;
-        uint8_t *strip_out = a.out + img * a.out_stride + ((size_t)(8 * BY * syi) * a.W + BX * 8 * sxi) * 3;
-        int sg0, sg1;   // segments of chunk `lane` and of chunk 64 + lane (the latter for lanes 0..31)
-        if constexpr (BX == 32) { sg0 = 1 + ((lane - 48) >> 31); sg1 = 1; asm volatile("" : "+v"(sg0)); }   // (lane >= 48 ? 1 : 0, without a select)
-        else { sg0 = (int)((unsigned)lane / CPS); sg1 = (int)((64u + (unsigned)lane) / CPS); }
-        const int j0 = lane - CPS * sg0, j1 = 64 + lane - CPS * sg1;
-        // inside the image: 16 j < nb (and lane < 32 for the second chunk) as the SIGN of a difference (kernels_quad.hip: no v_cndmask_b32)
-        const int in0 = 16 * j0 - nb, in1 = max(16 * j1 - nb, lane - 32);            // negative: inside
-        const bool col0 = in0 < 0, col1 = in1 < 0;
-        // The strip's rows through a BUFFER RESOURCE (round 5, as in k_quad420): base = the strip's first pixel, num_records = the
-        // bytes to the end of its last row INSIDE the image -- a row below the image is out of range and the hardware drops its
-        // store; a chunk right of the image gets an out-of-range voffset.  Two store instructions per pixel row, no predicate, no
-        // branch, the row is the scalar soffset.  FAST = false (any width): whole chunks the same way, the partial last chunk of
-        // a row (right-edge column only) dword- and byte-wise (store_tail).
-        const int rows_here = min(8 * BY, a.H - 8 * BY * syi);
-        const uint32_t strip_bytes = (uint32_t)rows_here * pitch;
-        const i32x4_t out_srd = make_srd(strip_out, strip_bytes);
-        const int rem0 = col0 ? nb - 16 * j0 : 0, rem1 = col1 ? nb - 16 * j1 : 0;   // bytes of the lane's chunks inside the image
-        const uint32_t base0 = sg0 * 8u * pitch + 16u * j0, base1 = sg1 * 8u * pitch + 16u * j1;
-        auto place = [](uint32_t base, int d) -> uint32_t {      // base where d < 0, an out-of-range voffset elsewhere: one v_bfi_b32
-            const uint32_t m = (uint32_t)(d >> 31);
-            return (base & m) | (0x80000000u & ~m);
-        };
-        const uint32_t voff0 = place(base0, FAST ? in0 : in0 + 15), voff1 = place(base1, FAST ? in1 : max(16 * j1 - nb + 15, lane - 32));
+        // ---- store geometry and the store path of the strip: StripStore, fused_common.hpp (this kernel launders the segment
+        //      of chunk `lane`, k_quad420 does not) ----
+        const StripStore<BX, FAST, true> out(a, img, syi, sxi, lane);
         stores_behind_dma = FAST ? 16 : 0;
 
         // One pixel row of the strip's BY block rows at a time.  The row's LDS and memory traffic is software-
@@ -569,72 +531,25 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
         // (ds_read) right after its arithmetic, but the chunks are stored only after the arithmetic of row y + 1;
         // the chroma dwords of the next patch row are requested a row (SY == 1) or two (SY == 2) ahead.
         uint4 pv0 = make_uint4(0, 0, 0, 0), pv1 = make_uint4(0, 0, 0, 0);   // chunks of the previous pixel row
-        auto store_tail = [&](const uint4 &v, uint32_t base, int rem, uint32_t soff) {   // the first `rem` (1 .. 15) bytes of a chunk
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(strip_out, 0, (int)strip_bytes, 0x00020000);
-            const bool part = rem > 0 && rem < 16;
-            const int nd = rem >> 2, nbytes = rem & 3;
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                __builtin_amdgcn_raw_buffer_store_b32(d[k], rsrc, (part && k < nd) ? base + 4u * k : 0x80000000u, soff, 0);
-            const uint32_t w = nd == 0 ? v.x : nd == 1 ? v.y : nd == 2 ? v.z : v.w;
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (8 * b)), rsrc, (part && b < nbytes) ? base + 4u * nd + b : 0x80000000u, soff, 0);
-        };
-        auto store_row = [&](int yy) {
-            const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
-            const uint32_t soff = (uint32_t)yy * pitch;   // scalar
-            asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
-                         "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
-                         "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
-                         ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
-            if constexpr (!FAST) {
-                if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
-                    store_tail(pv0, base0, rem0, soff);
-                    store_tail(pv1, base1, rem1, soff);
-                }
-            }
-        };
+        // (a wrapper and not the member called directly: the direct calls are compiled to another order of the walk's scalar copies)
+        auto put_row = [&](int yy) { out.store_row(yy, pv0, pv1); };
         // colour of pixel row y of the work-item's block from its luma samples and the row's chroma values; packed as 24 bytes
         auto colour_row = [&](int y, const float (&cv)[2][8], uint32_t (&d)[6]) {
             float c[24];
 #pragma unroll
             for (int x = 0; x < 8; ++x) {
                 const float yy = yv[8 * y + x];
-                float c0, c1, c2;
-                if constexpr (MODE == 1) {
-                    if constexpr (CHROMA) {
-                        const float pb = cv[0][x], pr = cv[1][x];
-                        // jpeg.swift:441-453: x = (y + m_cb cb) + m_cr cr (the 0.0 * c terms are exact no-ops), clamped and
-                        // TRUNCATED -- the pack below.  One FMA for R and B, two for G in this association (the other one is
-                        // NOT exact): after the truncation every one of the 2^16 / 2^24 input combinations gives the
-                        // reference's byte (tests/test_colour_rounding.py enumerates them).
-                        c0 = __builtin_fmaf(1.40200f, pr, yy);
-                        c1 = __builtin_fmaf(-0.71414f, pr, __builtin_fmaf(-0.34414f, pb, yy));
-                        c2 = __builtin_fmaf(1.77200f, pb, yy);
-                    } else {
-                        c0 = c1 = c2 = yy;  // cb = cr = 128: every matrix term is +-0
-                    }
-                } else {
-                    c0 = yy;
-                    c1 = CHROMA ? cv[0][x] : 128.0f;
-                    c2 = CHROMA ? cv[1][x] : 128.0f;
-                }
-                c[3 * x + 0] = c0; c[3 * x + 1] = c1; c[3 * x + 2] = c2;
+                if constexpr (CHROMA) colour_pixel<MODE>(yy, cv[0][x], cv[1][x], c + 3 * x);   // the colour matrix: fused_common.hpp
+                else if constexpr (MODE == 1) c[3 * x + 0] = c[3 * x + 1] = c[3 * x + 2] = yy;   // cb = cr = 128: every matrix term is +-0
+                else { c[3 * x + 0] = yy; c[3 * x + 1] = 128.0f; c[3 * x + 2] = 128.0f; }
             }
             trunc_pack24(c, d);   // clamp [0, 255] + truncate (fused_common.hpp)
         };
         // the row's traffic: store the PREVIOUS row's chunks (their LDS read was issued a row ago; prev < 0: there is none),
         // stage this row (LDS ops of one wave execute in order) and read it back as chunks
         auto emit_row = [&](int prev, const uint32_t (&d)[6]) {
-            if (prev >= 0) store_row(prev);
-            uint2 *sw = reinterpret_cast<uint2 *>(stage_w + seg * SEG_DW + lbx * 6);
-            sw[0] = make_uint2(d[0], d[1]);
-            sw[1] = make_uint2(d[2], d[3]);
-            sw[2] = make_uint2(d[4], d[5]);
-            pv0 = *reinterpret_cast<const uint4 *>(stage_w + 4 * lane);
-            pv1 = *reinterpret_cast<const uint4 *>(stage_w + 4 * (64 + (lane & 31)));
+            if (prev >= 0) put_row(prev);
+            out.stage_row(d, stage_w, seg, lbx, lane, pv0, pv1);
         };
 #pragma unroll
         for (int y = 0; y < 8; ++y) {  // pixel row y of every block row of the strip
@@ -644,16 +559,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) {
                     if constexpr (SY == 2) {
-                        // window holds patch rows (y>>1), (y>>1)+1, (y>>1)+2; the nearer row
-                        // (middle) weighs 3, the farther one (above for even y, below for odd) 1
-                        if ((y & 1) == 1) hconv(rawn[pl], hw[pl][2]);
-#pragma unroll
-                        for (int x = 0; x < 8; ++x)
-                            cv[pl][x] = finish(w31(hw[pl][1][x], hw[pl][(y & 1) ? 2 : 0][x]));
-                        if ((y & 1) == 1) {
-#pragma unroll
-                            for (int x = 0; x < 8; ++x) { hw[pl][0][x] = hw[pl][1][x]; hw[pl][1][x] = hw[pl][2][x]; }
-                        }
+                        window_row<MODE, 4>(y, hconv, rawn[pl], hw[pl], cv[pl]);   // the sliding window: fused_common.hpp
                     } else {
                         float h[8];
                         hconv(rawn[pl], h);
@@ -681,7 +587,7 @@ __global__ __launch_bounds__(kThreads, (luma_waves_per_simd<SX, SY, CHROMA>())) 
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        store_row(7);
+        put_row(7);
       }   // strips of the unit
     }
 }

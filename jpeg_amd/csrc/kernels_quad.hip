@@ -23,8 +23,10 @@
 // during the chroma transform, the NEXT stack's chroma blocks during the luma transform and the pixel rows.
 //
 // Exactness: dct.hpp op for op (-ffp-contract=off); upsample.hpp for the exact shortcuts of the filter (small-integer
-// arithmetic, floor-free rounding); the colour matrix as in k_luma_fused (tests/test_colour_rounding.py enumerates every
-// input).  Strips, stacks and tile columns that reach past the image or the plane are handled in place (clamped fetches,
+// arithmetic, floor-free rounding); the colour matrix is k_luma_fused's (tests/test_colour_rounding.py enumerates every
+// input).  What the two strip walks have in common is stated once, in fused_common.hpp ("the strip walks' shared stages"): block
+// fetch, table modulation, counted wait, 2x chroma row, vertical window, rounding, colour matrix, pixel store path (StripStore).
+// Strips, stacks and tile columns that reach past the image or the plane are handled in place (clamped fetches,
 // predicated stores, the reference's index clamps repaired in the tile), so any image size takes this kernel.
 //
 // Instrumentation (never defined in the product build, leaves the pixels right): JA_PHASE_PROFILE (tools/phase_profile.py).
@@ -90,7 +92,6 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
     constexpr int QROWS = QS * CR + 2;                    // sample rows of the stack's tile: halo, QS x CR rows, halo (34 / 66)
     constexpr int PLANE = QROWS * PITCH;                  // dwords per plane of the tile
     constexpr int SEG_DW = BX * 6;                        // one pixel row of one block row: 24 B per block
-    constexpr int CPS = SEG_DW / 4;                       // 16-byte chunks per such segment
     // The stack's chroma blocks are dealt to its four waves BY KIND (the wave's ROLE of the trip), not by strip:
     //   role 0, 1   the 64 blocks under strips 0, 1 / 2, 3 of the stack (work-item b: strip b >> 5, plane (b >> 4) & 1, then
     //               row-major over CBR rows of CBW columns): a full transform, all work-items busy;
@@ -243,18 +244,13 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
         // ---- modulated tables (only when they change: per image, or never when the batch shares one set) ----
         const int table_id = a.quanta_stride == 0 ? 0 : img;
         if (table_id != img_of_table) {
-            const int qk = lane & 7, qh = lane >> 3;
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-                sqw[qp][p][8 * qk + qh] = modulate_entry(qk, qh, 0.125f, a.quanta[img * a.quanta_stride + 64 * a.qi[p] + zigzag_of(qk, qh)]);
+            for (int p = 0; p < 3; ++p) modulate_table(sqw[qp][p], a.quanta, img, a.quanta_stride, a.qi[p], lane);
             img_of_table = table_id;
         }
 
-        // ---- the chroma pass's coefficients: wait for the DMA, read 8 x 16 B (swizzled).  VM operations retire in issue
-        //      order and the DMA was issued BEFORE the previous strip's pixel stores: when that strip took the branch-free
-        //      store path (exactly 2 store instructions per pixel row) only the DMA has to be waited for ----
-        if (stores_behind_dma == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // ---- the chroma pass's coefficients: wait for the DMA (not for the stores behind it), read 8 x 16 B (swizzled) ----
+        wait_dma(stores_behind_dma);
         JA_PHASE(0)
         // The scheduler of a SIMD issues its oldest ready wave first.  From the start of a strip to the arrival at the
         // "ready" counter a wave runs at the top priority (whoever arrives late is waited for by the others);
@@ -263,16 +259,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
         uint32_t ticket = 0;
         if (dyn && qp == 0 && lane0 == 0) ticket = __hip_atomic_fetch_add(a.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ONE lane
         uint32_t w[32];
-        auto read_block = [&]() {
-            const uint4 *cw = reinterpret_cast<const uint4 *>(coef_w) + 8 * lane;
-            const int sw = (lane >> 1) & 7;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const uint4 v = cw[i ^ sw];
-                w[4 * i + 0] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-            }
-        };
-        read_block();
+        read_block(coef_w, lane, w);
         const uint32_t done_seen = lds_peek(done);   // checked after the transform; read here so that the check costs no round trip
         // w holds the chroma pass's block; the luma blocks of the strip follow it into the buffer
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -402,7 +389,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
             if (lane0 == 0) *(volatile uint32_t *)&next_slot[trip & 1] = gridDim.x + ticket;
             lds_arrive(pub);
         }
-        read_block();
+        read_block(coef_w, lane, w);
         // ---- the coefficient buffer is consumed: prefetch the next stack's chroma pass into it.  From here to the end of
         //      the strip only stores are issued, so nothing waits on the DMA.  (One DMA instruction in front of each column of
         //      the transform instead of eight in a row, pinned with scheduling barriers, costs the transform more than the
@@ -452,22 +439,14 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
         }
 
         // ---- chroma rows, produced just in time from the tile.  Patch row j of a block: window row seg (8 / 2) + j;
-        //      the LDS reads (hraw) and the conversion + horizontal interpolation (hconv) are separate so that the reads
-        //      can be issued well ahead of their use ----
+        //      the LDS reads (hraw) and the conversion + horizontal interpolation (hconv_2x, fused_common.hpp) are separate so
+        //      that the reads can be issued well ahead of their use ----
         auto hraw = [&](int pl, int j, uint32_t (&r)[3]) {
             const uint32_t *row = sc + pl * PLANE + (seg * 4 + j) * PITCH;
             r[0] = row[lbx]; r[1] = row[1 + lbx]; r[2] = row[2 + lbx];
         };
-        auto hconv = [&](const uint32_t (&r)[3], float (&o)[8]) {   // samples enter as 2^15 + p + 1/32 (upsample.hpp)
-            const float p[6] = {ubyte_magic<3>(r[0]), ubyte_magic<0>(r[1]), ubyte_magic<1>(r[1]),
-                                ubyte_magic<2>(r[1]), ubyte_magic<3>(r[1]), ubyte_magic<0>(r[2])};
-            lerp_row_2x(p, o);
-        };
-        // final chroma value of one pixel from the vertically combined sum: floor(v / 16 + 1/2) [- 128], without a floor
-        auto finish = [&](float v) -> float {
-            return __builtin_fmaf(v, 0.0625f, kMagic - 32768.0f - (MODE == 1 ? 128.0f : 0.0f)) - kMagic;
-        };
-        // sliding window over the patch rows: slots hold rows (y >> 1), (y >> 1) + 1, (y >> 1) + 2
+        auto hconv = [](const uint32_t (&r)[3], float (&o)[8]) { hconv_2x(r, o); };
+        // sliding window over the patch rows (window_row, fused_common.hpp)
         float hw[2][3][8];
         uint32_t rawn[2][3];
 #pragma unroll
@@ -477,95 +456,24 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
             hconv(r0, hw[pl][0]); hconv(r1, hw[pl][1]);
         }
 
-        // ---- store geometry: per pixel row the strip's BY segments are 96 chunks of 16 B; a lane stores chunk `lane` (and
-        //      lanes 0..31 also chunk 64 + lane).  Both store instructions of a row cover whole 128-byte lines. ----
-        const int tile_px = min(BX * 8, a.W - BX * 8 * sxi);    // pixels of this strip inside the image
-        const int nb = 3 * tile_px;                              // bytes per row segment to write
-        const uint32_t pitch = 3u * a.W;
-        uint8_t *strip_out = a.out + img * a.out_stride + ((size_t)(8 * BY * syi) * a.W + BX * 8 * sxi) * 3;
-        int sg0, sg1;   // segments of chunk `lane` and of chunk 64 + lane (the latter for lanes 0..31)
-        if constexpr (BX == 32) { sg0 = 1 + ((lane - 48) >> 31); sg1 = 1; }   // (lane >= 48 ? 1 : 0, without a select)
-        else { sg0 = (int)((unsigned)lane / CPS); sg1 = (int)((64u + (unsigned)lane) / CPS); }
-        const int j0 = lane - CPS * sg0, j1 = 64 + lane - CPS * sg1;
-        // inside the image: 16 j < nb (and, for the second chunk, lane < 32) -- as the SIGN of a difference, so that what depends on it
-        // is formed with shifts and v_bfi instead of v_cndmask_b32 (ten times slower than either on gfx950)
-        const int in0 = 16 * j0 - nb, in1 = max(16 * j1 - nb, lane - 32);            // negative: inside
-        const bool col0 = in0 < 0, col1 = in1 < 0;
-        // FAST: the strip's rows through a BUFFER RESOURCE (round 5).  base = the strip's first pixel, num_records = the bytes from
-        // there to the end of the strip's last row INSIDE the image: a row below the image is out of range and the hardware drops
-        // its store (range check: voffset >= num_records - soffset, tools/probe_buffer.hip); a chunk right of the image gets a
-        // voffset that is out of range for every row.  No predicate, no branch and no 64-bit address per row: the row is the
-        // scalar soffset.  (num_records <= 32 rows x 3 x 65 535 B: the resource describes a strip, not the image, which may
-        // exceed 4 GiB.)
-        const int rows_here = min(8 * BY, a.H - 8 * BY * syi);
-        const uint32_t strip_bytes = (uint32_t)rows_here * pitch;
-        const i32x4_t out_srd = make_srd(strip_out, strip_bytes);
-        // FAST: every chunk is whole or outside.  Otherwise (any width: rows start at any byte address, which buffer stores
-        // take) a chunk is whole, outside, or -- in the strip column that holds the image's right edge -- the PARTIAL last chunk
-        // of its row segment (1 .. 15 bytes), which goes dword- and byte-wise (store_tail below).
-        const int rem0 = col0 ? nb - 16 * j0 : 0, rem1 = col1 ? nb - 16 * j1 : 0;   // bytes of the lane's chunks inside the image
-        const uint32_t base0 = sg0 * 8u * pitch + 16u * j0, base1 = sg1 * 8u * pitch + 16u * j1;
-        // voffset = the chunk's place, or an out-of-range value: base where d < 0, 0x80000000 elsewhere (d: FAST in0 / in1; else "fewer than
-        // 16 bytes of the chunk are inside")
-        auto place = [](uint32_t base, int d) -> uint32_t {
-            const uint32_t m = (uint32_t)(d >> 31);               // all ones where d < 0
-            return (base & m) | (0x80000000u & ~m);               // one v_bfi_b32
-        };
-        const uint32_t voff0 = place(base0, FAST ? in0 : in0 + 15), voff1 = place(base1, FAST ? in1 : max(16 * j1 - nb + 15, lane - 32));
+        // ---- store geometry and the store path of the strip: StripStore, fused_common.hpp ----
+        const StripStore<BX, FAST, false> out(a, img, syi, sxi, lane);
         stores_behind_dma = FAST ? 16 : 0;
         JA_PHASE(7)
 
         // One pixel row of the strip's BY block rows at a time, software-pipelined: row y is staged (ds_write) and read
         // back as 16-byte chunks (ds_read) right after its arithmetic, but the chunks are stored only after the arithmetic
         // of the next row; the chroma dwords of the next patch row are requested two rows ahead.
+        // (a wrapper and not the member called directly: the direct calls are compiled to another order of the walk's scalar copies)
         uint4 pv0 = make_uint4(0, 0, 0, 0), pv1 = make_uint4(0, 0, 0, 0);   // chunks of the previous pixel row
-        // FAST = false, right-edge column: the first `rem` (1 .. 15) bytes of a chunk -- up to three dwords, then up to three
-        // bytes; a lane without a partial chunk carries out-of-range offsets throughout (rem outside 1 .. 15)
-        auto store_tail = [&](const uint4 &v, uint32_t base, int rem, uint32_t soff) {
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(strip_out, 0, (int)strip_bytes, 0x00020000);
-            const bool part = rem > 0 && rem < 16;
-            const int nd = rem >> 2, nbytes = rem & 3;
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                __builtin_amdgcn_raw_buffer_store_b32(d[k], rsrc, (part && k < nd) ? base + 4u * k : 0x80000000u, soff, 0);
-            const uint32_t w = nd == 0 ? v.x : nd == 1 ? v.y : nd == 2 ? v.z : v.w;
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (8 * b)), rsrc, (part && b < nbytes) ? base + 4u * nd + b : 0x80000000u, soff, 0);
-        };
-        auto store_row = [&](int yy) {
-            // chunk `lane` from every lane, chunk 64 + lane from lanes 0 .. 31 (the others carry an out-of-range voffset):
-            // exactly two store instructions per pixel row, whatever the strip's place in the image
-            const u32x4_t q0 = {pv0.x, pv0.y, pv0.z, pv0.w}, q1 = {pv1.x, pv1.y, pv1.z, pv1.w};
-            const uint32_t soff = (uint32_t)yy * pitch;   // scalar
-            asm volatile("buffer_store_dwordx4 %0, %1, %4, %5 offen nt\n\t"
-                         "buffer_store_dwordx4 %2, %3, %4, %5 offen nt\n\t"
-                         "s_nop 0"   // a store of more than 64 bits with an SGPR offset: one wait state before its data registers may be rewritten
-                         ::"v"(q0), "v"(voff0), "v"(q1), "v"(voff1), "s"(out_srd), "s"(soff) : "memory");
-            if constexpr (!FAST) {
-                if (nb & 15) {   // wave-uniform: this strip column holds the image's right edge
-                    store_tail(pv0, base0, rem0, soff);
-                    store_tail(pv1, base1, rem1, soff);
-                }
-            }
-        };
+        auto put_row = [&](int yy) { out.store_row(yy, pv0, pv1); };
 #pragma unroll
         for (int y = 0; y < 8; ++y) {  // pixel row y of every block row of the strip
             __builtin_amdgcn_sched_barrier(0);
-            // vertical interpolation: the nearer patch row (the middle of the window) weighs 3, the farther one (above
-            // for even y, below for odd) 1; then colour and pack
+            // vertical interpolation (the final value is floor(v / 16 + 1/2) [- 128] of the combined sum); then colour and pack
             float cv[2][8];
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                if ((y & 1) == 1) hconv(rawn[pl], hw[pl][2]);
-#pragma unroll
-                for (int x = 0; x < 8; ++x) cv[pl][x] = finish(w31(hw[pl][1][x], hw[pl][(y & 1) ? 2 : 0][x]));
-                if ((y & 1) == 1) {
-#pragma unroll
-                    for (int x = 0; x < 8; ++x) { hw[pl][0][x] = hw[pl][1][x]; hw[pl][1][x] = hw[pl][2][x]; }
-                }
-            }
+            for (int pl = 0; pl < 2; ++pl) window_row<MODE, 16>(y, hconv, rawn[pl], hw[pl], cv[pl]);
             uint32_t d[6];
             {
                 float c[24];
@@ -573,29 +481,14 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
                 for (int x = 0; x < 8; ++x) {
                     const float yy = x == 0 ? ubyte<0>(ypk[2 * y]) : x == 1 ? ubyte<1>(ypk[2 * y]) : x == 2 ? ubyte<2>(ypk[2 * y]) : x == 3 ? ubyte<3>(ypk[2 * y])
                                    : x == 4 ? ubyte<0>(ypk[2 * y + 1]) : x == 5 ? ubyte<1>(ypk[2 * y + 1]) : x == 6 ? ubyte<2>(ypk[2 * y + 1]) : ubyte<3>(ypk[2 * y + 1]);
-                    if constexpr (MODE == 1) {
-                        const float pb = cv[0][x], pr = cv[1][x];
-                        // jpeg.swift:441-453: x = (y + m_cb cb) + m_cr cr, clamped and TRUNCATED -- the pack below.  One FMA
-                        // for R and B, two for G: after the truncation every one of the 2^16 / 2^24 input combinations gives
-                        // the reference's byte (tests/test_colour_rounding.py enumerates them).
-                        c[3 * x + 0] = __builtin_fmaf(1.40200f, pr, yy);
-                        c[3 * x + 1] = __builtin_fmaf(-0.71414f, pr, __builtin_fmaf(-0.34414f, pb, yy));
-                        c[3 * x + 2] = __builtin_fmaf(1.77200f, pb, yy);
-                    } else {
-                        c[3 * x + 0] = yy; c[3 * x + 1] = cv[0][x]; c[3 * x + 2] = cv[1][x];
-                    }
+                    colour_pixel<MODE>(yy, cv[0][x], cv[1][x], c + 3 * x);
                 }
                 trunc_pack24(c, d);   // clamp [0, 255] + truncate
             }
             __builtin_amdgcn_sched_barrier(0);
             // the row's traffic: the previous row's stores, this row's staging, the request for the next patch row
-            if (y > 0) store_row(y - 1);
-            uint2 *sw = reinterpret_cast<uint2 *>(stage_w + seg * SEG_DW + lbx * 6);
-            sw[0] = make_uint2(d[0], d[1]);
-            sw[1] = make_uint2(d[2], d[3]);
-            sw[2] = make_uint2(d[4], d[5]);
-            pv0 = *reinterpret_cast<const uint4 *>(stage_w + 4 * lane);
-            pv1 = *reinterpret_cast<const uint4 *>(stage_w + 4 * (64 + (lane & 31)));
+            if (y > 0) put_row(y - 1);
+            out.stage_row(d, stage_w, seg, lbx, lane, pv0, pv1);
             if ((y & 1) == 1 && y < 7) {
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) hraw(pl, (y >> 1) + 3, rawn[pl]);
@@ -605,7 +498,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_quad420(QuadArgs a)   // 3: wav
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        store_row(7);
+        put_row(7);
         JA_PHASE(10)
         if (!more) break;
     }

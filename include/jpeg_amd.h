@@ -896,6 +896,70 @@ int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
                                         size_t dst_stride);
 
+/* ---- tensor sources: float and uint8 tensors (CHW / HWC) into the encoders --------------------------------
+ * The mirror of "tensor output": what a framework holds -- a model's float CHW output in 0 ... 1 or in normalised units,
+ * torchvision's uint8 [3, H, W] -- turned into the encoders' tight uint8 [H][W][3] rows by ONE launch, in the place of the
+ * mul, add, clamp, round, cast, permute, contiguous a caller runs otherwise.  THE CONTRACT (the one statement of it): the
+ * byte u(i, y, x, c) of image i is made from the element e of (i, c, y, x); every line is ONE binary32 operation, nothing
+ * contracted:
+ *   f = e as binary32                 JPEG_AMD_F16 and JPEG_AMD_BF16 convert exactly; subnormal elements are numbers (no
+ *                                     flushing)
+ *   p = f * scale[c]
+ *   s = p + offset[c]
+ *   b = fminf(fmaxf(s, 0), 255)       fmaxf / fminf return the other operand when one is NaN: NaN -> 0, +Inf -> 255,
+ *                                     -Inf -> 0
+ *   u = (uint8_t)(int)(b + 0.5f)      the sum rounded to binary32, then truncated: the conversion of "resized decode"
+ *   JPEG_AMD_U8:  u = e;  scale and offset are not read
+ * scale and offset are in BYTE units (255 * std and 255 * mean invert "tensor output"; 255 and 0 take 0 ... 1), both rounded
+ * to binary32 by the caller: the kernel holds no division.  There are always three channels, and `color` passes through to
+ * the encoder unchanged.  Element indices of `layout` are those of "tensor output" with (w, h) for (out_w, out_h); image i
+ * is at d_src + i * src_stride ELEMENTS.
+ * The encode and compress calls below define no encoder arithmetic: their coefficients and files are, bit for bit, those of
+ * jpeg_amd_encode_batch / jpeg_amd_compress_batch_device on the bytes u. */
+enum { JPEG_AMD_U8 = 3 };   /* sources only; jpeg_amd_tensor_extent keeps refusing it */
+typedef struct jpeg_amd_tensor_source {
+    int32_t dtype;    /* JPEG_AMD_F32 | JPEG_AMD_F16 | JPEG_AMD_BF16 | JPEG_AMD_U8 */
+    int32_t layout;   /* JPEG_AMD_TENSOR_HWC | JPEG_AMD_TENSOR_CHW, element indices as in "tensor output" */
+    float scale[3], offset[3];
+} jpeg_amd_tensor_source;
+
+/* Host only, pure.  *elem_bytes = the element size (4, 2, 2, 1) and *image_elems = 3 * w * h (either pointer may be NULL).
+ * EINVAL for a NULL source, an unknown dtype or layout, a scale or offset that is not finite under a float dtype, or a w or
+ * h outside 1 ... 65 535. */
+int jpeg_amd_tensor_source_extent(const jpeg_amd_tensor_source *src, int32_t w, int32_t h, size_t *elem_bytes,
+                                  size_t *image_elems);
+/* The front alone, one launch: n_images sources of w x h to bytes, image i at d_pixels + i * pixel_stride (h rows of 3 w
+ * bytes; pixel_stride in bytes, 0 = 3 w h).  d_src is aligned to the element size; src_stride (elements) and pixel_stride
+ * >= 3 w h (any value when n_images == 1); bytes in the stride gaps are left alone; the source and the output must not
+ * overlap.  src is copied before the call returns.  At most 65 535 images, n_images == 0 is OK.  Everything is validated
+ * before anything is enqueued: on EINVAL -- what jpeg_amd_tensor_source_extent refuses, a misaligned d_src, a stride that
+ * is too small, a null pointer -- nothing is written and the context stays usable. */
+int jpeg_amd_tensor_pixels_batch(jpeg_amd_ctx *ctx, int n_images, const void *d_src, size_t src_stride, int32_t w, int32_t h,
+                                 const jpeg_amd_tensor_source *src, uint8_t *d_pixels, size_t pixel_stride);
+/* jpeg_amd_encode_batch with (d_src, src_stride, src) in the place of (d_pixels, pixel_stride); the extent is the layout's.
+ * Whatever jpeg_amd_encode_batch refuses is refused first, with its status, then what jpeg_amd_tensor_pixels_batch refuses;
+ * nothing is enqueued on a refusal.
+ * Cost: chunks of consecutive images of at most 1 GiB of bytes in a buffer of the context, per chunk ONE front launch and
+ * then jpeg_amd_encode_batch as it stands -- every layout it takes works, its staged layouts included.  A JPEG_AMD_U8,
+ * JPEG_AMD_TENSOR_HWC source IS jpeg_amd_encode_batch on d_src: no launch, no buffer. */
+int jpeg_amd_encode_tensor_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images, const void *d_src,
+                                 size_t src_stride, const jpeg_amd_tensor_source *src, jpeg_amd_color color,
+                                 const uint16_t *d_quanta, size_t quanta_stride, int ntables,
+                                 int16_t *const d_coef[], const size_t coef_stride[]);
+/* single image, host tables */
+int jpeg_amd_encode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, const void *d_src,
+                           const jpeg_amd_tensor_source *src, jpeg_amd_color color, const uint16_t *h_quanta, int ntables,
+                           int16_t *const d_coef[]);
+/* jpeg_amd_compress_batch_device with (d_src, src_stride, src) in the place of (d_pixels, pixel_stride); src_stride in
+ * elements, 0 = 3 W H.  Whatever that call refuses is refused first, then the source.  The front launch writes each
+ * chunk's bytes into the pipeline's device slot; everything behind it is that call's. */
+int jpeg_amd_compress_tensor_batch_device(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const void *d_src,
+                            size_t src_stride, const jpeg_amd_tensor_source *src, int n_images, jpeg_amd_color color,
+                            const int32_t *quanta_key, const uint16_t *h_quanta,
+                            const int32_t *h_quanta_keys, int ntables, const jpeg_amd_scan *scans,
+                            int nscans, const jpeg_amd_metadata *metadata, int nmetadata, int nthreads,
+                            uint8_t *h_out, size_t out_stride, size_t nbytes[]);
+
 /* ---- spectral reduce: a Spectral at 1/2, 1/4 or 1/8 size, coefficients in and coefficients out ----------
  * JPEG in, smaller JPEG out, without pixels in between: no interleave, no colour conversion and no second generation of
  * chroma rounding, so every layout, plane count and precision is served alike.  It composes two contracts that are stated

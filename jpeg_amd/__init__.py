@@ -8,15 +8,15 @@ include/jpeg_amd.h.  All arithmetic runs in hand-written HIP kernels
 from ._lib import JpegAmdError, LIB_PATH  # noqa: F401
 from .api import (  # noqa: F401
     RGB, YCbCr, Component, Context, Layout, Planar, Rectangular, Scan, Spectral,
-    compression_quanta, decode_crops_resized, decode_crops_tensor, decode_crops_tensor_mixed, decode_regions, decode_resized,
+    compress_tensors, compression_quanta, decode_crops_resized, decode_crops_tensor, decode_crops_tensor_mixed, decode_regions, decode_resized,
     decode_resized_mixed, decode_scaled, decode_tensors, decode_tensors_mixed, decode_views, decode_views_mixed, default_context,
-    inspect, reduce, reduce_layout, region_window, resize, resize_tensor, scaled_size, tensor_spec,
+    encode_tensors, inspect, reduce, reduce_layout, region_window, resize, resize_tensor, scaled_size, tensor_pixels, tensor_source, tensor_spec,
     transform, transform_quanta, view_denom, view_of_source, view_window,
 )
 
 __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangular",
-           "Scan", "Spectral", "JpegAmdError", "compression_quanta", "decode_crops_resized", "decode_crops_tensor", "decode_crops_tensor_mixed",
+           "Scan", "Spectral", "JpegAmdError", "compress_tensors", "compression_quanta", "decode_crops_resized", "decode_crops_tensor", "decode_crops_tensor_mixed",
            "decode_regions", "decode_resized", "decode_resized_mixed", "decode_scaled", "decode_tensors", "decode_tensors_mixed",
-           "decode_views", "decode_views_mixed", "default_context", "inspect", "reduce", "reduce_layout",
-           "region_window", "resize", "resize_tensor", "scaled_size", "tensor_spec", "transform", "transform_quanta", "view_denom",
+           "decode_views", "decode_views_mixed", "default_context", "encode_tensors", "inspect", "reduce", "reduce_layout",
+           "region_window", "resize", "resize_tensor", "scaled_size", "tensor_pixels", "tensor_source", "tensor_spec", "transform", "transform_quanta", "view_denom",
            "view_of_source", "view_window"]

@@ -152,6 +152,12 @@ SIGNATURES = {
                                                        C.c_size_t]),
     "jpeg_amd_decode_tensor_filter_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
                                                       _p, C.c_size_t]),
+    "jpeg_amd_tensor_source_extent": (C.c_int, [_p, C.c_int32, C.c_int32, _szp, _szp]),
+    "jpeg_amd_tensor_pixels_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, C.c_int32, C.c_int32, _p, _p, C.c_size_t]),
+    "jpeg_amd_encode_tensor_batch": (C.c_int, [_p, _L, C.c_int, _p, C.c_size_t, _p, C.c_int, _p, C.c_size_t, C.c_int, _pp, _szp]),
+    "jpeg_amd_encode_tensor": (C.c_int, [_p, _L, _p, _p, C.c_int, _p, C.c_int, _pp]),
+    "jpeg_amd_compress_tensor_batch_device": (C.c_int, [_p, _p, _p, C.c_size_t, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int, _p,
+                                                        C.c_int, _p, C.c_int, C.c_int, _p, C.c_size_t, _p]),
     "jpeg_amd_reduce_layout": (C.c_int, [_L, C.c_int, _L]),
     "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
     "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
@@ -184,7 +190,13 @@ class TensorSpec(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("layout", C.c_int32), ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class TensorSource(C.Structure):
+    """struct jpeg_amd_tensor_source"""
+    _fields_ = [("dtype", C.c_int32), ("layout", C.c_int32), ("scale", C.c_float * 3), ("offset", C.c_float * 3)]
+
+
 F32, F16, BF16 = 0, 1, 2                # JPEG_AMD_F32 ...
+U8 = 3                                  # JPEG_AMD_U8: tensor sources only
 TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
 FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
 

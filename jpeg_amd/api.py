@@ -1016,6 +1016,133 @@ def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=N
     return _tensor_view(out, n, wt, ht, spec)
 
 
+def tensor_source(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.TensorSource:
+    """The input stage of the tensor encode calls (struct jpeg_amd_tensor_source), the inverse of tensor_spec: mean and std per
+    channel in 0 ... 1 units give scale = float32(255 std) and offset = float32(255 mean), each computed in float64 and rounded
+    once; byte = clamp(element * scale + offset) rounded.  std=None: scale = 1; mean=None: offset = 0 (both None: elements
+    in byte units; std (1, 1, 1) and mean (0, 0, 0): elements in 0 ... 1).  dtype: torch.float32, torch.float16 (the default),
+    torch.bfloat16 or torch.uint8 (the bytes themselves; mean and std are not used); layout: "chw" or "hwc"."""
+    torch = _torch()
+    dtype = torch.float16 if dtype is None else dtype
+    codes = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16, torch.uint8: _lib.U8}
+    layouts = {"hwc": _lib.TENSOR_HWC, "chw": _lib.TENSOR_CHW}
+    if dtype not in codes or str(layout).lower() not in layouts:
+        raise ValueError("tensor_source: dtype float32 / float16 / bfloat16 / uint8, layout 'chw' / 'hwc'")
+    src = _lib.TensorSource()
+    src.dtype, src.layout = codes[dtype], layouts[str(layout).lower()]
+    for c in range(3):
+        src.scale[c] = 1.0 if std is None else float(np.float32(255.0 * float(std[c])))
+        src.offset[c] = 0.0 if mean is None else float(np.float32(255.0 * float(mean[c])))
+    return src
+
+
+def _source_args(ctx: Context, tensors, source: _lib.TensorSource):
+    """What the tensor encode calls take of `tensors`, [n, 3, H, W] ("chw") or [n, H, W, 3] ("hwc") of source's dtype on the
+    context's device, each image contiguous: -> (n, W, H, elements between the images)."""
+    torch = _torch()
+    dtypes = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16, _lib.U8: torch.uint8}
+    if not isinstance(tensors, torch.Tensor) or tensors.dim() != 4:
+        raise ValueError("tensors: one tensor [n, 3, H, W] or [n, H, W, 3]")
+    if tensors.dtype != dtypes.get(source.dtype):
+        raise ValueError("tensors: dtype %s does not match the source's" % tensors.dtype)
+    n = int(tensors.shape[0])
+    c, h, w = tensors.shape[1:] if source.layout == _lib.TENSOR_CHW else (tensors.shape[3], tensors.shape[1], tensors.shape[2])
+    if c != 3 or h < 1 or w < 1:
+        raise ValueError("tensors: three channels in the source's layout, H and W at least 1")
+    if tensors.device != ctx.torch_device:
+        raise ValueError("tensors: on the context's device")
+    if n > 0 and not tensors[0].is_contiguous():
+        raise ValueError("tensors: each image contiguous")
+    stride = int(tensors.stride(0)) if n > 1 else 3 * int(w) * int(h)
+    if stride < 3 * w * h:
+        raise ValueError("tensors: images overlap")
+    return n, int(w), int(h), stride
+
+
+def _encode_tables(layout: Layout, quanta):
+    """-> (one table per distinct quanta key of the layout in plane order, the table index of every plane)."""
+    q = _dedupe_q(layout)
+    keys: List[int] = []
+    for c in layout.planes:
+        if c.qi not in quanta:
+            raise _lib.JpegAmdError(_lib.EINVAL, f"missing quantization table for quanta key {c.qi}")
+        if c.qi not in keys:
+            keys.append(c.qi)
+    return [np.asarray(quanta[k], np.uint16).reshape(64) for k in keys], q
+
+
+def tensor_pixels(ctx: Context, tensors, source: _lib.TensorSource):
+    """Tensors to the encoders' bytes in one launch (jpeg_amd_tensor_pixels_batch; include/jpeg_amd.h, "tensor sources", holds
+    the contract).  tensors: [n, 3, H, W] or [n, H, W, 3] as `source` (tensor_source) says, on the context's device, each image
+    contiguous, the batch stride taken from stride(0).  Returns uint8 [n, H, W, 3]."""
+    n, w, h, stride = _source_args(ctx, tensors, source)
+    out = ctx.empty(n * 3 * w * h, _torch().uint8)
+    _lib.check(_lib.lib().jpeg_amd_tensor_pixels_batch(ctx.handle, n, tensors.data_ptr(), stride, w, h, C.byref(source),
+                                                       out.data_ptr(), 3 * w * h), "jpeg_amd_tensor_pixels_batch", ctx.handle)
+    return out.view(n, h, w, 3)
+
+
+def encode_tensors(ctx: Context, tensors, layout: Layout, quanta: Dict[int, Sequence[int]], source: _lib.TensorSource,
+                   color=RGB) -> List[Spectral]:
+    """Rectangular.encode for a batch of tensors in one call (jpeg_amd_encode_tensor_batch): tensors as in tensor_pixels,
+    layout and quanta as in Rectangular.encode.  Returns one Spectral per image; their planes are views into one allocation
+    per plane."""
+    torch = _torch()
+    n, w, h, stride = _source_args(ctx, tensors, source)
+    tables, q = _encode_tables(layout, quanta)
+    size = (w, h)
+    units = layout.units(size)
+    L = layout.c_layout(size, units, q)
+    planes = [ctx.empty(n * 64 * ux * uy, torch.int16).view(n, uy, ux, 64) for ux, uy in units]
+    dq = ctx.upload(np.stack(tables).astype(np.uint16))
+    _lib.check(_lib.lib().jpeg_amd_encode_tensor_batch(
+        ctx.handle, C.byref(L), n, tensors.data_ptr(), stride, C.byref(source), color.code, dq.data_ptr(), 0, len(tables),
+        _ptrs(planes), _lib.size_array([64 * ux * uy for ux, uy in units])), "jpeg_amd_encode_tensor_batch", ctx.handle)
+    return [Spectral(ctx, size, layout, [p[i] for p in planes], tables, q) for i in range(n)]
+
+
+def compress_tensors(ctx: Context, tensors, layout: Layout, quanta: Dict[int, Sequence[int]], source: _lib.TensorSource, scans,
+                     process: str = "baseline", metadata=None, threads: int = 0, color=RGB) -> List[bytes]:
+    """Tensors to JPEG files in one call (jpeg_amd_compress_tensor_batch_device): the front launch and the fused encoder on the
+    device, chunk by chunk, the entropy coding on `threads` host threads (0: all cores).  tensors as in tensor_pixels; layout,
+    quanta, scans, process and metadata as in Rectangular.compress.  Returns the n files' bytes."""
+    n, w, h, stride = _source_args(ctx, tensors, source)
+    info = _lib.FrameInfo()
+    info.width, info.height = w, h
+    info.precision, info.ncomponents = layout.precision, layout.count
+    info.process = {"baseline": 0, "extended": 1, "progressive": 2}[process]
+    keys = []
+    for p, (key, comp) in enumerate(zip(layout.recognized, layout.planes)):
+        info.id[p] = int(key)
+        info.factor_x[p], info.factor_y[p] = comp.factor
+        keys.append(comp.qi)
+    tkeys = sorted(set(keys))
+    for k in tkeys:
+        if k not in quanta:
+            raise _lib.JpegAmdError(_lib.EINVAL, f"missing quantization table for quanta key {k}")
+    tables = np.stack([np.asarray(quanta[k], np.uint16).reshape(64) for k in tkeys])
+    qkey = (C.c_int32 * len(keys))(*keys)
+    tk = (C.c_int32 * len(tkeys))(*tkeys)
+    sarr = _scan_array(scans)
+    marr, nmeta, _keep = _metadata_array(metadata)
+    if n == 0:
+        return []
+    sizes = (C.c_size_t * n)()
+    # sized generously (raw samples + headers), and the call repeated only if that was too small for some file
+    cap = 3 * w * h * 2 + (1 << 16)
+    for _ in range(2):
+        out = np.empty((n, cap), np.uint8)
+        st = _lib.lib().jpeg_amd_compress_tensor_batch_device(
+            ctx.handle, C.byref(info), tensors.data_ptr(), stride, C.byref(source), n, color.code, qkey, tables.ctypes.data, tk,
+            len(tkeys), sarr, len(scans), marr, nmeta, int(threads), out.ctypes.data, cap, sizes)
+        if st == _lib.EINVAL and max(sizes) > cap:
+            cap = max(sizes)
+            continue
+        _lib.check(st, "jpeg_amd_compress_tensor_batch_device", ctx.handle)
+        break
+    return [out[i, :sizes[i]].tobytes() for i in range(n)]
+
+
 def _dedupe_q(layout: Layout) -> List[int]:
     """Spectral.set(quanta:) (decode.swift:2510-2543): one table per distinct quanta key,
     in plane order."""

@@ -1,7 +1,7 @@
 // capi.hip -- the C ABI declared in include/jpeg_amd.h, first unit: the helpers every unit shares (capi_internal.hpp),
 // the context with its memory and timing calls, and the whole-image decode and encode stages.  The view and resample calls
-// are in capi_view.hip, the host-buffer conveniences in capi_host.hip, the file calls in capi_file.hip and the
-// coefficient-domain calls in capi_spectral.hip.
+// are in capi_view.hip, the host-buffer conveniences in capi_host.hip, the file calls in capi_file.hip, the
+// coefficient-domain calls in capi_spectral.hip and the tensor sources of the encoders in capi_tensor.hip.
 // No arithmetic on samples happens here; all of it is in kernels_*.hip.
 #pragma clang fp contract(off)
 
@@ -272,7 +272,7 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->workers.reset();
     ctx->copiers.reset();
-    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed})
+    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed, &ctx->tensor_px})
         if (buf->ptr) (void)hipFree(buf->ptr);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);

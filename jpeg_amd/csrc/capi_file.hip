@@ -557,6 +557,11 @@ struct BatchEncode {
     SlotLayout at;
     Pieces staging{1, 1};                      // pixels are staged in pieces of <= 4 MiB
     WorkerPool *pool;
+    // jpeg_amd_compress_tensor_batch_device: the pictures are tensors on the device (include/jpeg_amd.h, "tensor sources"),
+    // image i at d_tensor + i * tensor_stride elements of elem_bytes; source == nullptr: they are pixels
+    const void *d_tensor = nullptr;
+    size_t tensor_stride = 0, elem_bytes = 1;
+    const jpeg_amd_tensor_source *source = nullptr;
 
     int images(int k) const { return std::min(chunk, n_images - k * chunk); }
     int submit(int k);
@@ -577,7 +582,11 @@ int BatchEncode::submit(int k)
     for (int c = 0; c < nc; ++c) d_coef[c] = reinterpret_cast<int16_t *>(dev + at.coef_off[c]);
     const uint8_t *d_px = reinterpret_cast<const uint8_t *>(dev);
     size_t d_px_stride = npx;
-    if (on_device) { d_px = d_pixels_in + (size_t)k * chunk * pixel_stride; d_px_stride = pixel_stride; }   // encoded where they are
+    // tensors: the front launch writes the chunk's bytes into the slot's pixel area, where uploaded pixels would lie
+    if (source)
+        JA_HIP(ctx, launch_tensor_pixels(ctx->stream, m, static_cast<const char *>(d_tensor) + (size_t)k * chunk * tensor_stride * elem_bytes,
+                                         tensor_stride, L.width, L.height, *source, reinterpret_cast<uint8_t *>(dev), npx));
+    else if (on_device) { d_px = d_pixels_in + (size_t)k * chunk * pixel_stride; d_px_stride = pixel_stride; }   // encoded where they are
     // from the pinned slot, or from the caller's page-locked buffer where they are
     else if (!direct_in) JA_HIP(ctx, copy_images(ctx->stream, hipMemcpyHostToDevice, dev, npx, host, npx, npx, m));
     else JA_HIP(ctx, copy_images(ctx->stream, hipMemcpyHostToDevice, dev, npx, h_pixels + (size_t)k * chunk * pixel_stride, pixel_stride, npx, m));
@@ -685,16 +694,18 @@ int BatchEncode::run()
     return after_both_streams(ctx, result);
 }
 
-// Pixels -> files; the pixels in host memory (h_pixels) or already on the device (d_pixels_in): jpeg_amd_compress_batch[_device].
+// Pixels -> files; the pixels in host memory (h_pixels) or already on the device (d_pixels_in): jpeg_amd_compress_batch[_device];
+// or tensors on the device (d_tensor, tensor_stride in elements, source): jpeg_amd_compress_tensor_batch_device.
 int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uint8_t *h_pixels, const uint8_t *d_pixels_in,
-                        size_t pixel_stride, int n_images, jpeg_amd_color color,
+                        size_t pixel_stride, const void *d_tensor, size_t tensor_stride, const jpeg_amd_tensor_source *source,
+                        int n_images, jpeg_amd_color color,
                         const int32_t *quanta_key, const uint16_t *h_quanta, const int32_t *h_quanta_keys,
                         int ntables, const jpeg_amd_scan *scans, int nscans,
                         const jpeg_amd_metadata *metadata, int nmetadata, int nthreads,
                         uint8_t *h_out, size_t out_stride, size_t nbytes[])
 {
     JA_TRY(bind(ctx));
-    const bool on_device = d_pixels_in != nullptr;
+    const bool on_device = d_pixels_in != nullptr || d_tensor != nullptr;
     if (!frame || (!h_pixels && !on_device) || !quanta_key || !h_quanta || !h_quanta_keys || !scans || !h_out || !nbytes || n_images < 0)
         return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
@@ -707,6 +718,11 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
                   metadata, nmetadata, nthreads, h_out, out_stride, nbytes, nc, npx};
     JA_TRY(layout_of_frame(frame, quanta_key, h_quanta_keys, ntables, &e.L));
     for (int c = 0; c < nc; ++c) e.plane[c] = plane_samples(&e.L, c);
+    if (d_tensor) {   // behind everything the pixel call refuses
+        if (tensor_stride == 0) tensor_stride = npx;
+        JA_TRY(check_tensor_source(n_images, d_tensor, tensor_stride, frame->width, frame->height, source, &e.elem_bytes));
+        e.d_tensor = d_tensor; e.tensor_stride = tensor_stride; e.source = source;
+    }
     e.chunk = std::min(n_images, 32);
     if (e.nthreads <= 0) e.nthreads = default_host_threads();
     e.nthreads = std::max(1, e.nthreads);
@@ -744,7 +760,7 @@ int jpeg_amd_compress_batch(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const
                             uint8_t *h_out, size_t out_stride, size_t nbytes[])
 try {
     if (!h_pixels) return JPEG_AMD_EINVAL;
-    return compress_batch_impl(ctx, frame, h_pixels, nullptr, pixel_stride, n_images, color, quanta_key, h_quanta, h_quanta_keys, ntables,
+    return compress_batch_impl(ctx, frame, h_pixels, nullptr, pixel_stride, nullptr, 0, nullptr, n_images, color, quanta_key, h_quanta, h_quanta_keys, ntables,
                                scans, nscans, metadata, nmetadata, nthreads, h_out, out_stride, nbytes);
 }
 JA_NOTHROW_TAIL
@@ -757,8 +773,26 @@ int jpeg_amd_compress_batch_device(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame
                                    uint8_t *h_out, size_t out_stride, size_t nbytes[])
 try {
     if (!d_pixels) return JPEG_AMD_EINVAL;
-    return compress_batch_impl(ctx, frame, nullptr, d_pixels, pixel_stride, n_images, color, quanta_key, h_quanta, h_quanta_keys, ntables,
+    return compress_batch_impl(ctx, frame, nullptr, d_pixels, pixel_stride, nullptr, 0, nullptr, n_images, color, quanta_key, h_quanta, h_quanta_keys, ntables,
                                scans, nscans, metadata, nmetadata, nthreads, h_out, out_stride, nbytes);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_compress_tensor_batch_device(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const void *d_src, size_t src_stride,
+                                          const jpeg_amd_tensor_source *src, int n_images, jpeg_amd_color color,
+                                          const int32_t *quanta_key, const uint16_t *h_quanta, const int32_t *h_quanta_keys,
+                                          int ntables, const jpeg_amd_scan *scans, int nscans,
+                                          const jpeg_amd_metadata *metadata, int nmetadata, int nthreads,
+                                          uint8_t *h_out, size_t out_stride, size_t nbytes[])
+try {
+    if (!d_src) return JPEG_AMD_EINVAL;
+    // bytes in the encoder's own order are the pixel call: no launch
+    if (src && src->dtype == JPEG_AMD_U8 && src->layout == JPEG_AMD_TENSOR_HWC)
+        return compress_batch_impl(ctx, frame, nullptr, static_cast<const uint8_t *>(d_src), src_stride, nullptr, 0, nullptr, n_images, color,
+                                   quanta_key, h_quanta, h_quanta_keys, ntables, scans, nscans, metadata, nmetadata, nthreads, h_out,
+                                   out_stride, nbytes);
+    return compress_batch_impl(ctx, frame, nullptr, nullptr, 0, d_src, src_stride, src, n_images, color, quanta_key, h_quanta, h_quanta_keys,
+                               ntables, scans, nscans, metadata, nmetadata, nthreads, h_out, out_stride, nbytes);
 }
 JA_NOTHROW_TAIL
 

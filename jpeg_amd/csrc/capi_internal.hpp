@@ -44,6 +44,9 @@ struct jpeg_amd_ctx {
     // the mixed calls (jpeg_amd_decode_view_mixed, ...): the per-image records, index lists and tile prefixes of their launches.
     // A buffer of its own: the uniform calls of a mixed call's fallback images rewrite `region`, the resample rewrites the others.
     DeviceBuffer mixed;
+    // jpeg_amd_encode_tensor_batch: the bytes of a chunk, between the front launch and the encoder.  A buffer of its own: the
+    // staged encode behind it regrows `scratch`.
+    DeviceBuffer tensor_px;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -103,6 +106,9 @@ jpeg_amd_layout layout_of_info(const jpeg_amd_frame_info &fi, int nplanes);
 int layout_of_frame(jpeg_amd_frame_info *frame, const int32_t *quanta_key, const int32_t *h_quanta_keys, int ntables,
                     jpeg_amd_layout *L);
 int reduce_n(int denom);   // (capi_spectral.hip)
+// What the calls that take a tensor source require of it, beyond jpeg_amd_tensor_source_extent (capi_tensor.hip).
+int check_tensor_source(int n_images, const void *d_src, size_t src_stride, int32_t w, int32_t h,
+                        const jpeg_amd_tensor_source *src, size_t *elem_bytes);
 
 // The ABI's per-plane pointer (and stride: nullptr = one image) arrays as a PlaneSet / PlaneSetMut.  Decode inputs
 // (need_all) reject any null plane pointer, encode outputs only where the plane has samples.

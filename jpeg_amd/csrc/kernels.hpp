@@ -192,6 +192,14 @@ hipError_t launch_antialias_bytes(hipStream_t stream, int n_images, const uint8_
 hipError_t launch_antialias_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
                                    int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
 
+// ---- tensors to pixel bytes (kernels_pixels.hip) ------------------------------------------------
+// n_images tensors of w x h x 3 elements of source.dtype in source.layout to bytes by the contract of include/jpeg_amd.h
+// ("tensor sources") in ONE launch (k_tensor_pixels).  Image i at d_src + i * src_stride ELEMENTS, d_src aligned to the
+// element; its h rows of 3 w bytes at d_dst + i * dst_stride.  source is valid (jpeg_amd_tensor_source_extent).
+constexpr int kTensorSourceMaxSide = 65535;      // of a source: the sides of a JPEG frame
+hipError_t launch_tensor_pixels(hipStream_t stream, int n_images, const void *d_src, size_t src_stride, int w, int h,
+                                const jpeg_amd_tensor_source &source, uint8_t *d_dst, size_t dst_stride);
+
 // ---- lossless spectral transforms (kernels_transform.hip) -----------------------------
 // Every plane of n_images images in one launch: output block (x, y) of plane p (out's units) reads the source block the op
 // maps it to, offset by (ox[p], oy[p]) blocks (the region's origin), or zeros past in's units.  d_quanta_out: nullptr = copy,

@@ -1020,6 +1020,88 @@ int jpeg_amd_spectral_reduce(jpeg_amd_ctx *ctx, const jpeg_amd_layout *in_layout
 int jpeg_amd_reduce(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int denom, const uint16_t *h_requant,
                     int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out, jpeg_amd_frame_info *out_info);
 
+/* ---- files to tensors: JPEG files of mixed sizes and layouts to one training tensor in one call ------------------------
+ * The file front end of the mixed calls: what a data loader has is a list of FILES -- a size per file, 4:2:0 beside 4:4:4,
+ * some grey, some progressive -- and what it wants is one normalised [n, 3, Ht, Wt] tensor.
+ *
+ * 1. THE WINDOWED EXPAND.  jpeg_amd_spectral_expand_batch for images of different geometries in ONE launch, each plane cut
+ * to a window of blocks and each block to its head.  Item i describes one image: its layout (units_x is the pitch of its
+ * planes, in blocks), its planes d_coef[p] (device, whole planes of units_x * units_y blocks of 64 int16), per plane a window
+ * (x, y, width, height in BLOCKS of that plane; width or height 0: nothing of the plane), `head`, the number of leading
+ * 16-byte octets (eight coefficients in zigzag order) of each block to write, and where its sparse record lies in d_records:
+ * its descriptors (one per block of the frame, as jpeg_amd_jpeg_decode_sparse orders them) at element desc_at and its
+ * entries at element entries_at; a descriptor counts from entries_at.  The heads the view decode reads:
+ *   denominator 8 reads zigzag index 0, denominator 4 indices 0 .. 4: both inside octet 0           head 1
+ *   denominator 2 reads indices 0 .. 24: octets 0 .. 3                                              head 4
+ *   denominator 1 reads the block                                                                   head 8
+ * THE CONTRACT (the one statement of it): the bytes the call writes -- the first 16 * head bytes of every block of every
+ * window -- are exactly the bytes jpeg_amd_spectral_expand_batch writes at the same addresses for the same record; every other
+ * byte of the planes is left as it was, and is not read.  A descriptor of 0xFFFFFFFF gives zeros.  The entries of a block must
+ * be in ascending zigzag order, as jpeg_amd_jpeg_decode_sparse and the encoders' sparse download write them: the walk of a
+ * block stops at the first entry at or behind 8 * head.
+ * h_items is a HOST array of n_images items; the call copies it before it returns.  Everything is judged before anything is
+ * enqueued, the context last: EINVAL for n_images < 0 or above 65 535, null h_items or d_records, a layout
+ * jpeg_amd_spectral_expand_batch refuses or whose blocks 32-bit descriptors cannot number, a head not in {1, 4, 8}, a plane
+ * pointer that is null or not 16-byte aligned, a window outside its plane (or of negative width or height), and work
+ * that does not fit a grid (2^31 - 1 workgroups of 256 octets); after a refused call nothing has been written.
+ * n_images == 0 is OK.  Asynchronous on the context's stream.
+ * Cost: one host-to-device copy of the item records, one launch; a work-item per octet written. */
+typedef struct jpeg_amd_expand_item {
+    jpeg_amd_layout layout;
+    int16_t        *d_coef[JPEG_AMD_MAX_PLANES];
+    jpeg_amd_region window[JPEG_AMD_MAX_PLANES];   /* blocks */
+    int32_t         head;                          /* 1 | 4 | 8 octets */
+    uint64_t        desc_at, entries_at;           /* elements into d_records */
+} jpeg_amd_expand_item;
+int jpeg_amd_spectral_expand_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_expand_item *h_items,
+                                   const uint32_t *d_records);
+
+/* 2. FILES TO A TENSOR, AND FILES TO RESIZED BYTES.  THE CONTRACT, by reference only -- no arithmetic is defined here: image i
+ * of the output is, bit for bit, what jpeg_amd_decode_tensor_filter_mixed (jpeg_amd_decode_resized_filter_mixed for the byte
+ * call) writes for file i when
+ *   - the file is decoded by jpeg_amd_jpeg_decode_spectral into WHOLE planes, with the layout of its frame (component c's
+ *     table is table c, ntables = its number of components), and
+ *   - the view is the one the data-loader call chooses: denom = jpeg_amd_view_denom(source width, source height, out_w,
+ *     out_h), region = jpeg_amd_view_of_source(that file's own size, denom, source rectangle),
+ * with the same cosited, color, out_w, out_h, filter, spec and h_flip[i].  h_source_regions: a HOST array of n_images
+ * rectangles in pixels of each file's full-size image, or NULL: the whole images.  h_info and h_views (optional, n_images
+ * each) receive every file's frame and the view chosen for it; they are written as far as the files were judged, also by a
+ * call that is then refused.  Output placement, strides, spec and h_flip as in the mixed calls.
+ *
+ * Everything that can be judged from the files' HEADERS is judged before anything is enqueued, the context last, file by file
+ * in index order: a null file pointer (EINVAL), what jpeg_amd_jpeg_inspect says of the file, a frame that is not 8-bit with 1
+ * or 3 components (ENOSUP: one such file refuses the whole call), a source rectangle outside the image (EINVAL); then, of
+ * the files in front of the first offending one, whatever the mixed call refuses, the target included; last the antialias
+ * filter's 16x limit (ENOSUP).  After a refused call nothing has been written and the context is usable.  n_images == 0 is OK.
+ * A file whose entropy-coded data proves damaged AFTER the call has started ends the call with that file's status: every
+ * copy and kernel in flight is waited for and the context stays usable, but output images of chunks already submitted MAY
+ * HAVE BEEN WRITTEN.  There are no per-file statuses, and a bad file is not skipped.
+ *
+ * Route and cost.  The files go in CHUNKS of consecutive files, at most 32 and at most 1 GiB of coefficient planes (a larger
+ * single file is a chunk of its own).  `nthreads` host threads (<= 0: all cores) beside the calling one entropy-decode the
+ * files of ONE queue for the whole call, each into the SPARSE form (jpeg_amd_jpeg_decode_sparse), packed into a pinned slot
+ * of the context; a file the sparse decoder does not take (progressive, a missing restart marker, too dense) is decoded into
+ * planes there.  Per chunk ONE copy carries the tables, the item records and the packed records; planes of the dense files
+ * go up whole; ONE launch of the windowed expand writes, for every sparse file, only the heads of the blocks of its view's
+ * windows (jpeg_amd_view_window) into the context's plane buffer; then the mixed call runs on the chunk, as it stands.  Two
+ * pinned slots: the threads decode chunk k + 1 while the device works on chunk k.  An image the tile kernels do not take
+ * (cosited calls, factors 3 or 4, chroma not at 1x or 2x) is expanded whole, as its one-image fallback reads it whole.
+ * A 224 x 224 crop of a 2000 x 1500 file at denominator 4 has 16 of 128 bytes written for the blocks under the crop and
+ * nothing for the others; at denominator 1 the expand writes as much as jpeg_amd_spectral_expand_batch inside the window.
+ * What is NOT saved: the entropy decoding of the whole file, and the planes keep their full pitch in device memory (the
+ * plane buffer of the largest chunk stays in the context, as do two pinned slots of up to 1.8 times that).
+ * Returns when the last chunk's kernels have finished. */
+int jpeg_amd_decompress_tensor_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                     int nthreads, int cosited, jpeg_amd_color color,
+                                     const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter,
+                                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
+                                     jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views);
+int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                      int nthreads, int cosited, jpeg_amd_color color,
+                                      const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter,
+                                      uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
+                                      jpeg_amd_view *h_views);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,11 @@ SIGNATURES = {
     "jpeg_amd_spectral_reduce_batch": (C.c_int, [_p, _L, C.c_int, C.c_int, _pp, _szp, _p, C.c_size_t, C.c_int, _p, _pp, _szp]),
     "jpeg_amd_spectral_reduce": (C.c_int, [_p, _L, C.c_int, _pp, _p, C.c_int, _p, _pp]),
     "jpeg_amd_reduce": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.c_int, _p, C.c_size_t, _p, _p]),
+    "jpeg_amd_spectral_expand_mixed": (C.c_int, [_p, C.c_int, _p, _p]),
+    "jpeg_amd_decompress_tensor_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int,
+                                                   _p, _p, _p, C.c_size_t, _p, _p]),
+    "jpeg_amd_decompress_resized_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int,
+                                                    _p, C.c_size_t, _p, _p]),
 }
 
 
@@ -178,6 +183,12 @@ class View(C.Structure):
 class Image(C.Structure):
     """struct jpeg_amd_image"""
     _fields_ = [("layout", Layout), ("d_coef", C.c_void_p * MAX_PLANES), ("d_quanta", C.c_void_p), ("ntables", C.c_int32)]
+
+
+class ExpandItem(C.Structure):
+    """struct jpeg_amd_expand_item"""
+    _fields_ = [("layout", Layout), ("d_coef", C.c_void_p * MAX_PLANES), ("window", Region * MAX_PLANES), ("head", C.c_int32),
+                ("desc_at", C.c_uint64), ("entries_at", C.c_uint64)]
 
 
 class Extent(C.Structure):

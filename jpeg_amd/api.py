@@ -1002,6 +1002,61 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
     return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter), views
 
 
+def _file_args(sources, source_regions):
+    """The arguments the file calls share: (n, c file pointers, c sizes, c source rectangles or None, room for the frame
+    infos, room for the views, keep).  sources: paths or the files' bytes."""
+    files = [_file_bytes(s) for s in sources]
+    n = len(files)
+    ptrs = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in files])
+    sizes = (C.c_size_t * max(n, 1))(*[f.size for f in files])
+    regions = None
+    if source_regions is not None:
+        regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
+        if regs.shape[0] != n:
+            raise ValueError("source_regions: one (x, y, width, height) per file")
+        regions = (_lib.Region * max(n, 1))()
+        for i, r in enumerate(regs.tolist()):
+            regions[i].x, regions[i].y, regions[i].width, regions[i].height = r
+    return n, ptrs, sizes, regions, (_lib.FrameInfo * max(n, 1))(), (_lib.View * max(n, 1))(), files
+
+
+def _views_array(h_views, n) -> np.ndarray:
+    return np.array([(v.denom, v.region.x, v.region.y, v.region.width, v.region.height) for v in h_views[:n]], np.int32).reshape(n, 5)
+
+
+def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
+                       cosite: bool = False, filter: str = "bilinear", threads: int = 0):
+    """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
+    and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
+    tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
+    (x, y, width, height) of its full-size image (source_regions; None: the whole images), decoded at the cheapest denominator
+    that is still no smaller than out_size (Wt, Ht), resampled by `filter`, mirrored where flips[i] is set, normalised by
+    `spec` (tensor_spec).  The files are entropy-decoded on `threads` host threads (0: all cores) into the sparse form, and
+    only the parts of the coefficient planes that the views read are rebuilt on the device.
+    Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5] of (denom, x, y, width, height), the files'
+    frame infos)."""
+    code = _filter(filter)
+    n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
+                                                           regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
+                                                           infos, h_views), "jpeg_amd_decompress_tensor_mixed", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n])
+
+
+def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
+                       filter: str = "bilinear", threads: int = 0):
+    """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
+    (Wt, Ht) as bytes.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    code = _filter(filter)
+    n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    _lib.check(_lib.lib().jpeg_amd_decompress_resized_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
+                                                            regions, wt, ht, code, out.data_ptr(), stride, infos, h_views),
+               "jpeg_amd_decompress_resized_mixed", ctx.handle)
+    return out.view(n, ht, wt, 3)
+
+
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear"):
     """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
     [n, Ht, Wt, 3] of spec's dtype, in one launch."""

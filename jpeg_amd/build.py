@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
-SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resize.hip", "kernels_tensor.hip", "kernels_antialias.hip", "kernels_reduce.hip", "kernels_pixels.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
+SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resize.hip", "kernels_tensor.hip", "kernels_antialias.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
 HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
@@ -40,9 +40,10 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
 # encode variants): it is reported, and an error only under JPEG_AMD_STRICT_SPILL=1 (a register-allocation change in a ROCm update
 # must not leave a user without a library).  k_resize_bilinear counts nothing, but it is small (54 VGPRs) and every lane streams
 # bytes: a spill there is a mistake in the source, so it is held to the strict rule; k_resize_tensor, the same walk with
-# another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise.
+# another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise; k_expand_mixed, an entry walk and one store,
+# likewise.
 NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused", "kernels_resize.hip": "k_resize_bilinear",
-              "kernels_tensor.hip": "k_resize_tensor", "kernels_pixels.hip": "k_tensor_pixels"}
+              "kernels_tensor.hip": "k_resize_tensor", "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform", "kernels_region.hip": "k_region_decode",
                 "kernels_scaled.hip": "k_scaled_decode", "kernels_view.hip": "k_view_decode",

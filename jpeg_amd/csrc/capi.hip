@@ -1,7 +1,8 @@
 // capi.hip -- the C ABI declared in include/jpeg_amd.h, first unit: the helpers every unit shares (capi_internal.hpp),
 // the context with its memory and timing calls, and the whole-image decode and encode stages.  The view and resample calls
-// are in capi_view.hip, the host-buffer conveniences in capi_host.hip, the file calls in capi_file.hip, the
-// coefficient-domain calls in capi_spectral.hip and the tensor sources of the encoders in capi_tensor.hip.
+// are in capi_view.hip, the host-buffer conveniences in capi_host.hip, the file calls in capi_file.hip (files of mixed
+// sizes to one tensor: capi_files.hip), the coefficient-domain calls in capi_spectral.hip and the tensor sources of the
+// encoders in capi_tensor.hip.
 // No arithmetic on samples happens here; all of it is in kernels_*.hip.
 #pragma clang fp contract(off)
 
@@ -272,7 +273,8 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->workers.reset();
     ctx->copiers.reset();
-    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed, &ctx->tensor_px})
+    for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed, &ctx->tensor_px, &ctx->expand,
+                              &ctx->file_planes})
         if (buf->ptr) (void)hipFree(buf->ptr);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
@@ -492,6 +494,61 @@ int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, 
     JA_HIP(ctx, launch_expand_sparse(ctx->stream, n_images, *L, d_desc, desc_stride, d_entries, entries_stride, d_skip, cs));
     return JPEG_AMD_OK;
 }
+
+namespace jpeg_amd {
+namespace capi {
+
+// What jpeg_amd_spectral_expand_mixed requires of one item; *groups: the workgroups it takes.
+int check_expand_item(const jpeg_amd_expand_item &it, uint64_t *groups)
+{
+    JA_TRY(check_layout(&it.layout, -1));
+    if (it.head != 1 && it.head != 4 && it.head != 8) return JPEG_AMD_EINVAL;
+    uint64_t blocks = 0;
+    for (int p = 0; p < it.layout.nplanes; ++p) {
+        if (!it.d_coef[p] || reinterpret_cast<uintptr_t>(it.d_coef[p]) % 16 != 0) return JPEG_AMD_EINVAL;
+        const jpeg_amd_region &w = it.window[p];
+        if (w.x < 0 || w.y < 0 || w.width < 0 || w.height < 0) return JPEG_AMD_EINVAL;
+        if ((long long)w.x + w.width > it.layout.units_x[p] || (long long)w.y + w.height > it.layout.units_y[p]) return JPEG_AMD_EINVAL;
+        blocks += (uint64_t)it.layout.units_x[p] * (uint64_t)it.layout.units_y[p];
+    }
+    if (blocks >= 0xffffffffull) return JPEG_AMD_EINVAL;   // descriptors are 32-bit indices, 0xFFFFFFFF is taken
+    *groups = expand_mixed_groups(it);
+    return JPEG_AMD_OK;
+}
+
+}  // namespace capi
+}  // namespace jpeg_amd
+
+int jpeg_amd_spectral_expand_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_expand_item *h_items, const uint32_t *d_records)
+try {
+    // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
+    if (!h_items || !d_records) return JPEG_AMD_EINVAL;
+    // staged in one copy: the item records [n], then the prefix of their workgroups [n + 1]
+    const size_t n = (size_t)n_images, rec_bytes = expand_mixed_record_bytes();
+    std::vector<uint8_t> buf(rec_bytes * n + 4 * (n + 1));
+    uint64_t acc = 0;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t groups = 0;
+        JA_TRY(check_expand_item(h_items[i], &groups));
+        expand_mixed_record(buf.data() + rec_bytes * i, h_items[i]);
+        const uint32_t before = (uint32_t)acc;
+        std::memcpy(buf.data() + rec_bytes * n + 4 * i, &before, 4);
+        acc += groups;
+        if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;     // more workgroups than a grid holds
+    }
+    const uint32_t nwg = (uint32_t)acc;
+    std::memcpy(buf.data() + rec_bytes * n + 4 * n, &nwg, 4);
+    JA_TRY(bind(ctx));
+    JA_TRY(ensure_buffer(ctx, ctx->expand, buf.size()));
+    // (from a pageable host buffer, so the copy has taken it when the call returns -- as stage_quanta)
+    JA_HIP(ctx, hipMemcpyAsync(ctx->expand.ptr, buf.data(), buf.size(), hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t *d = static_cast<const uint8_t *>(ctx->expand.ptr);
+    JA_HIP(ctx, launch_expand_mixed(ctx->stream, n_images, d, reinterpret_cast<const uint32_t *>(d + rec_bytes * n), nwg, d_records));
+    return JPEG_AMD_OK;
+}
+JA_NOTHROW_TAIL
 
 int jpeg_amd_spectral_rectangular_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images,
                                         const int16_t *const d_coef[], const size_t coef_stride[],

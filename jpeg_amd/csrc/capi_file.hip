@@ -1,5 +1,6 @@
 // capi_file.hip -- the C ABI, file unit: JPEG bytes to pixels and back (one file, and the two batch pipelines), and the
-// file-to-file calls of the coefficient domain.  The host threads and the pixel drain are in worker_pool.hpp.
+// file-to-file calls of the coefficient domain.  The host threads and the pixel drain are in worker_pool.hpp; the files of
+// mixed sizes to one tensor are in capi_files.hip, which shares the staging helpers at the head of this file.
 #pragma clang fp contract(off)
 
 #include "capi_internal.hpp"
@@ -7,16 +8,13 @@
 using namespace jpeg_amd;
 using namespace jpeg_amd::capi;
 
-namespace {
+namespace jpeg_amd {
+namespace capi {
 
 // The sparse form of a frame's coefficients in the batch paths (jpeg_amd_jpeg_decode_sparse, k_sparsify): per image a
 // descriptor per block and an arena of 24 entries per block (3/4 of the planes' bytes at most; only what is used travels).
 // Descriptors are 32-bit indices into the arena: a frame whose record would not be addressable that way (25 * blocks >= 2^32:
 // beyond 60 000 x 60 000 4:4:4) travels as planes (ok = false).
-struct SparseBudget {
-    size_t blocks, arena, elems;   // elems: uint32 per image, [descriptors][entries]
-    bool ok;
-};
 SparseBudget sparse_budget(const jpeg_amd_layout &L)
 {
     size_t blocks = 0;
@@ -28,7 +26,7 @@ SparseBudget sparse_budget(const jpeg_amd_layout &L)
 // The staging the two batch entry points for files share, kept in the context between calls: two pinned host slots (the host
 // threads work in one while the device works from / into the other), two device slots, two events per slot and a second
 // stream so that uploads and downloads overlap (full-duplex PCIe).
-int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes)
+int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes, size_t device_slot_bytes)
 {
     if (ctx->file_pinned_bytes < slot_bytes) {
         JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -43,12 +41,12 @@ int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes)
         ctx->file_pinned_bytes = slot_bytes;
     }
     if (!ctx->file_d2h) JA_HIP(ctx, hipStreamCreateWithFlags(&ctx->file_d2h, hipStreamNonBlocking));
-    if (ctx->file_device_bytes < 2 * slot_bytes) {           // two device slots as well
+    if (ctx->file_device_bytes < 2 * device_slot_bytes) {           // two device slots as well
         JA_HIP(ctx, hipStreamSynchronize(ctx->stream));
         JA_HIP(ctx, hipStreamSynchronize(ctx->file_d2h));
         if (ctx->file_device) { (void)hipFree(ctx->file_device); ctx->file_device = nullptr; ctx->file_device_bytes = 0; }
-        JA_HIP(ctx, hipMalloc(&ctx->file_device, 2 * slot_bytes));
-        ctx->file_device_bytes = 2 * slot_bytes;
+        JA_HIP(ctx, hipMalloc(&ctx->file_device, 2 * device_slot_bytes));
+        ctx->file_device_bytes = 2 * device_slot_bytes;
     }
     return JPEG_AMD_OK;
 }
@@ -95,6 +93,25 @@ hipError_t wait_event(hipEvent_t ev)
     }
 }
 
+// the context's pool, with at least `threads` threads (the calling one included)
+WorkerPool &pool_with(std::unique_ptr<WorkerPool> &pool, int threads)
+{
+    if (!pool || pool->size() < threads) pool.reset(new WorkerPool(threads));
+    return *pool;
+}
+
+// The way out of both pipelines: a failure leaves copies and kernels in flight, so both streams are waited for.
+int after_both_streams(jpeg_amd_ctx *ctx, int result)
+{
+    if (result != JPEG_AMD_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->file_d2h); }
+    return result;
+}
+
+}  // namespace capi
+}  // namespace jpeg_amd
+
+namespace {
+
 // Is [p, p + bytes) page-locked host memory (hipHostMalloc / hipHostRegister) that a copy engine reaches directly?  Then the
 // batch entry points move the caller's buffer itself instead of staging it through their own pinned slots.
 bool is_pinned_host(const void *p, size_t bytes)
@@ -107,13 +124,6 @@ bool is_pinned_host(const void *p, size_t bytes)
         if (at.type != hipMemoryTypeHost || at.isManaged) return false;
     }
     return true;
-}
-
-// the context's pool, with at least `threads` threads (the calling one included)
-WorkerPool &pool_with(std::unique_ptr<WorkerPool> &pool, int threads)
-{
-    if (!pool || pool->size() < threads) pool.reset(new WorkerPool(threads));
-    return *pool;
 }
 
 // Where the parts of a staging slot of the batch pipelines begin (pinned and device slots alike): take(n) gives the next n
@@ -140,13 +150,6 @@ hipError_t copy_images(hipStream_t stream, hipMemcpyKind kind, void *dst, size_t
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-// The way out of both pipelines: a failure leaves copies and kernels in flight, so both streams are waited for.
-int after_both_streams(jpeg_amd_ctx *ctx, int result)
-{
-    if (result != JPEG_AMD_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->file_d2h); }
-    return result;
 }
 
 // Host memory for the coefficient planes of a layout, and the array of pointers into them that the entry points take.
@@ -450,7 +453,7 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
     d.at.where_off = d.at.take((size_t)d.chunk * 8);
     d.at.sparse_off = d.at.take(d.sb.elems * 4 * d.chunk);
     d.at.px_off = d.at.take(d.to_host ? d.npx * d.chunk : 0);
-    JA_TRY(ensure_file_staging(ctx, d.at.slot_bytes));
+    JA_TRY(ensure_file_staging(ctx, d.at.slot_bytes, d.at.slot_bytes));
     d.auto_threads = nthreads <= 0;
     if (d.auto_threads) nthreads = default_host_threads();
     d.nthreads = std::max(1, nthreads);
@@ -739,7 +742,7 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
     for (int c = 0; c < nc; ++c) e.at.coef_off[c] = e.at.take(e.plane[c] * 2 * e.chunk);
     e.at.sparse_off = e.at.take(e.sparse_down ? e.sb.elems * 4 * e.chunk : 0);
     e.at.count_off = e.at.take((size_t)e.chunk * 4);
-    JA_TRY(ensure_file_staging(ctx, e.at.slot_bytes));
+    JA_TRY(ensure_file_staging(ctx, e.at.slot_bytes, e.at.slot_bytes));
 
     e.nchunks = (n_images + e.chunk - 1) / e.chunk;
     // a caller whose pixels are page-locked gets them uploaded from where they are: nothing to stage

@@ -47,6 +47,12 @@ struct jpeg_amd_ctx {
     // jpeg_amd_encode_tensor_batch: the bytes of a chunk, between the front launch and the encoder.  A buffer of its own: the
     // staged encode behind it regrows `scratch`.
     DeviceBuffer tensor_px;
+    // jpeg_amd_spectral_expand_mixed: the item records and workgroup prefix of its launch.  A buffer of its own: the mixed
+    // call that follows an expand rewrites `mixed`.
+    DeviceBuffer expand;
+    // the file calls to tensors (capi_files.hip): the coefficient planes of a chunk's files.  Only the heads of the blocks of
+    // the views' windows are ever written: nothing else of it may be read.
+    DeviceBuffer file_planes;
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
@@ -109,6 +115,29 @@ int reduce_n(int denom);   // (capi_spectral.hip)
 // What the calls that take a tensor source require of it, beyond jpeg_amd_tensor_source_extent (capi_tensor.hip).
 int check_tensor_source(int n_images, const void *d_src, size_t src_stride, int32_t w, int32_t h,
                         const jpeg_amd_tensor_source *src, size_t *elem_bytes);
+
+// What jpeg_amd_spectral_expand_mixed requires of one item; *groups: the workgroups it takes (capi.hip).
+int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
+// What jpeg_amd_decode_resized_filter_mixed (tensor: jpeg_amd_decode_tensor_filter_mixed) refuses before it looks at the
+// context, for the file calls, which judge a call before its planes exist (the images' pointers only have to be non-null):
+// of the first `judged` images of a call of n_images, in the mixed call's order; *taps: with judged == n_images the verdict on
+// the antialiasing filter's tap limit, which that call gives last (capi_view.hip).
+int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                          bool tensor, void *d_dst, size_t dst_stride, int *taps);
+
+// The staging of the batch file paths and what their chunk loops share (capi_file.hip).
+struct SparseBudget {
+    size_t blocks, arena, elems;   // elems: uint32 per image, [descriptors][entries]
+    bool ok;
+};
+SparseBudget sparse_budget(const jpeg_amd_layout &L);   // of a frame's sparse record
+// Two pinned host slots of slot_bytes and two device slots of device_slot_bytes, two events per slot and the second stream.
+int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes, size_t device_slot_bytes);
+int default_host_threads();                   // how many host threads "all cores" means
+hipError_t wait_event(hipEvent_t ev);         // by polling
+WorkerPool &pool_with(std::unique_ptr<WorkerPool> &pool, int threads);   // the context's pool, with at least `threads` threads
+int after_both_streams(jpeg_amd_ctx *ctx, int result);   // the way out of the pipelines: a failure waits for both streams
 
 // The ABI's per-plane pointer (and stride: nullptr = one image) arrays as a PlaneSet / PlaneSetMut.  Decode inputs
 // (need_all) reject any null plane pointer, encode outputs only where the plane has samples.

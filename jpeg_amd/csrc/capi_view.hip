@@ -840,22 +840,36 @@ int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *
     return JPEG_AMD_OK;
 }
 
-// jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed: decode_resampled's route with the mixed view decode.
-int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                  const jpeg_amd_view *h_views, ResampleTarget t)
+// What jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed judge of a call of n_images images before they look at
+// the context, the tap limit (plan->status) aside; the target is judged where the uniform call judges it: behind the first
+// image.  judged < n_images (the file calls, whose image `judged` is already refused): only the images in front of it, and
+// nothing that comes behind the images -- no plan.
+int judge_resized_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                        const jpeg_amd_view *h_views, ResampleTarget &t, ResizePlan *plan, std::vector<MixedPlan> *plans)
 {
-    // every argument first, the context last; the target is judged where the uniform call judges it: behind the first image
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
-    for (int i = 0; i < n_images; ++i) {
+    for (int i = 0; i < judged; ++i) {
         JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], t.d_dst, 0));   // the views' stride is ours
         if (i == 0) JA_TRY(t.check(n_images));
     }
     if (n_images == 0) JA_TRY(t.check(n_images));
-    const ResizePlan plan = plan_resize_chunks(n_images, h_views, t);
-    std::vector<MixedPlan> plans(plan.chunks.size());
-    for (size_t c = 0; c < plans.size(); ++c)
-        JA_TRY(plan_mixed(h_images + plan.chunks[c].i0, h_views + plan.chunks[c].i0, plan.chunks[c].m, cosited, &plans[c]));
+    if (judged < n_images) return JPEG_AMD_OK;
+    *plan = plan_resize_chunks(n_images, h_views, t);
+    plans->resize(plan->chunks.size());
+    for (size_t c = 0; c < plans->size(); ++c)
+        JA_TRY(plan_mixed(h_images + plan->chunks[c].i0, h_views + plan->chunks[c].i0, plan->chunks[c].m, cosited, &(*plans)[c]));
+    return JPEG_AMD_OK;
+}
+
+// jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed: decode_resampled's route with the mixed view decode.
+int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                  const jpeg_amd_view *h_views, ResampleTarget t)
+{
+    // every argument first, the context last
+    ResizePlan plan;
+    std::vector<MixedPlan> plans;
+    JA_TRY(judge_resized_mixed(n_images, n_images, h_images, cosited, color, h_views, t, &plan, &plans));
     JA_TRY(plan.status);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
     JA_TRY(bind(ctx));
@@ -865,6 +879,18 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
 }
 
 }  // namespace
+
+int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
+                                          const jpeg_amd_tensor_spec *spec, bool tensor, void *d_dst, size_t dst_stride, int *taps)
+{
+    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride};
+    ResizePlan plan;
+    std::vector<MixedPlan> plans;
+    JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
+    *taps = plan.status;
+    return JPEG_AMD_OK;
+}
 
 int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
                                jpeg_amd_color color, const jpeg_amd_view *h_views, uint8_t *d_pixels, size_t pixel_stride)

@@ -59,6 +59,19 @@ hipError_t launch_expand_sparse(hipStream_t stream, int n_images, const jpeg_amd
 hipError_t launch_sparsify(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef, uint32_t *d_desc,
                            size_t desc_stride, uint32_t *d_entries, size_t entries_stride, uint32_t capacity, uint32_t *d_cursor);
 
+// ---- windowed, mixed-geometry expand (kernels_expand.hip) ------------------------------------------------
+// launch_expand_sparse for images of different geometries in ONE launch of nwg workgroups (k_expand_mixed), each plane cut
+// to a window of blocks and each block to its first `head` octets: what include/jpeg_amd.h ("files to tensors") says of
+// jpeg_amd_spectral_expand_mixed.  d_items: one record of expand_mixed_record_bytes() bytes per image, 16-byte aligned,
+// written by expand_mixed_record on the host from an item that is VALID (windows inside their planes, head 1 | 4 | 8);
+// d_groups: uint32 [n_images + 1], the prefix of expand_mixed_groups over the images (d_groups[n_images] == nwg, at most
+// 2^31 - 1); d_records: what the items' desc_at and entries_at count from.
+size_t     expand_mixed_record_bytes();
+uint64_t   expand_mixed_groups(const jpeg_amd_expand_item &item);   // workgroups of one image
+void       expand_mixed_record(void *dst, const jpeg_amd_expand_item &item);
+hipError_t launch_expand_mixed(hipStream_t stream, int n_images, const void *d_items, const uint32_t *d_groups, uint32_t nwg,
+                               const uint32_t *d_records);
+
 // a9 (+ a11/a12): upsample + interleave, written as Rectangular uint16, or colour-converted
 // straight to YCbCr / RGB bytes.  Planes are uint16 (or uint8 when planes_u8).
 hipError_t launch_planar_to_pixels(hipStream_t stream, int n_images,

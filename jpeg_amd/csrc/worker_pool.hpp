@@ -100,7 +100,8 @@ private:
     bool stop_ = false;
 };
 
-// The host-thread side of a batch decode (jpeg_amd_decompress_batch): `files` files in chunks of `chunk`, drawn from ONE
+// The host-thread side of a batch decode (jpeg_amd_decompress_batch, jpeg_amd_decompress_tensor_mixed): `files` files in chunks
+// of `chunk` -- or in chunks of sizes of the caller's, given by their first files -- drawn from ONE
 // counter for the whole call by `threads` threads of the pool, each with its own record (records[index], kept by the caller
 // between calls).  No barrier between chunks: a thread that is done with its file of chunk k goes on with chunk k + 1 while a
 // slower one still works on chunk k -- but a file is not started before its chunk is opened.  The calling thread directs:
@@ -111,10 +112,16 @@ public:
     using Decode = std::function<int(int, std::vector<uint32_t> &)>;
     FileQueue(WorkerPool &pool, std::vector<std::vector<uint32_t>> &records, int files, int chunk, int threads, Decode decode,
               size_t trim_above)
-        : pool_(pool), records_(records), decode_(std::move(decode)), files_(files), chunk_(chunk), trim_above_(trim_above),
-          inline_(pool.size() < 2), status_((size_t)files, 0), left_((size_t)((files + chunk - 1) / chunk))
+        : FileQueue(pool, records, uniform_chunks(files, chunk), threads, std::move(decode), trim_above)
     {
-        for (size_t k = 0; k < left_.size(); ++k) left_[k] = std::min(chunk, files - (int)k * chunk);
+    }
+    // Chunks of different sizes: chunk k is files [first[k], first[k + 1]), first.back() the number of files.
+    FileQueue(WorkerPool &pool, std::vector<std::vector<uint32_t>> &records, std::vector<int> first, int threads, Decode decode,
+              size_t trim_above)
+        : pool_(pool), records_(records), decode_(std::move(decode)), first_(std::move(first)), files_(first_.back()),
+          trim_above_(trim_above), inline_(pool.size() < 2), status_((size_t)files_, 0), left_(first_.size() - 1)
+    {
+        for (size_t k = 0; k < left_.size(); ++k) left_[k] = first_[k + 1] - first_[k];
         if (records_.size() < (size_t)std::max(1, threads)) records_.resize((size_t)std::max(1, threads));
         if (!inline_) pool_.begin(threads, [this](int index) { work(records_[(size_t)index]); }, threads + 1);
     }
@@ -138,23 +145,31 @@ public:
     // chunk k must have been opened; returns the status of its last failing file (0: every file decoded)
     int wait(int k)
     {
-        const int end = std::min(files_, (k + 1) * chunk_);
+        const int end = first_[(size_t)k + 1];
         if (inline_)
             while (next_.load() < end) run(next_.fetch_add(1), records_[0]);
         std::unique_lock<std::mutex> g(m_);
         cv_.wait(g, [&] { return left_[(size_t)k] == 0; });
         int st = 0;
-        for (int file = k * chunk_; file < end; ++file)
+        for (int file = first_[(size_t)k]; file < end; ++file)
             if (status_[(size_t)file] != 0) st = status_[(size_t)file];
         return st;
     }
 
 private:
+    static std::vector<int> uniform_chunks(int files, int chunk)
+    {
+        std::vector<int> first;
+        for (int f = 0; f < files; f += chunk) first.push_back(f);
+        first.push_back(files);
+        return first;
+    }
+    int chunk_of(int file) const { return (int)(std::upper_bound(first_.begin(), first_.end(), file) - first_.begin()) - 1; }
     void run(int file, std::vector<uint32_t> &record)
     {
         status_[(size_t)file] = decode_(file, record);
         std::lock_guard<std::mutex> g(m_);
-        if (--left_[(size_t)(file / chunk_)] == 0) cv_.notify_all();
+        if (--left_[(size_t)chunk_of(file)] == 0) cv_.notify_all();
     }
     void work(std::vector<uint32_t> &record)
     {
@@ -163,7 +178,7 @@ private:
             if (file >= files_) return;
             {
                 std::unique_lock<std::mutex> g(m_);
-                cv_.wait(g, [&] { return abort_ || open_ > file / chunk_; });
+                cv_.wait(g, [&] { return abort_ || open_ > chunk_of(file); });
                 if (abort_) return;
             }
             run(file, record);
@@ -172,7 +187,8 @@ private:
     WorkerPool &pool_;
     std::vector<std::vector<uint32_t>> &records_;
     const Decode decode_;
-    const int files_, chunk_;
+    const std::vector<int> first_;   // chunk k: files [first_[k], first_[k + 1])
+    const int files_;
     const size_t trim_above_;
     const bool inline_;
     std::vector<int> status_;        // per file, read by wait() once the file's chunk is complete

@@ -511,7 +511,7 @@ int check_expand_item(const jpeg_amd_expand_item &it, uint64_t *groups)
         if ((long long)w.x + w.width > it.layout.units_x[p] || (long long)w.y + w.height > it.layout.units_y[p]) return JPEG_AMD_EINVAL;
         blocks += (uint64_t)it.layout.units_x[p] * (uint64_t)it.layout.units_y[p];
     }
-    if (blocks >= 0xffffffffull) return JPEG_AMD_EINVAL;   // descriptors are 32-bit indices, 0xFFFFFFFF is taken
+    if (blocks >= sparse::kAbsent) return JPEG_AMD_EINVAL;   // descriptors are 32-bit indices, and one value means no block
     *groups = expand_mixed_groups(it);
     return JPEG_AMD_OK;
 }

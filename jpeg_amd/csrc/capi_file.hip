@@ -11,18 +11,6 @@ using namespace jpeg_amd::capi;
 namespace jpeg_amd {
 namespace capi {
 
-// The sparse form of a frame's coefficients in the batch paths (jpeg_amd_jpeg_decode_sparse, k_sparsify): per image a
-// descriptor per block and an arena of 24 entries per block (3/4 of the planes' bytes at most; only what is used travels).
-// Descriptors are 32-bit indices into the arena: a frame whose record would not be addressable that way (25 * blocks >= 2^32:
-// beyond 60 000 x 60 000 4:4:4) travels as planes (ok = false).
-SparseBudget sparse_budget(const jpeg_amd_layout &L)
-{
-    size_t blocks = 0;
-    for (int c = 0; c < L.nplanes; ++c) blocks += (size_t)L.units_x[c] * L.units_y[c];
-    const size_t arena = 24 * blocks;
-    return {blocks, arena, blocks + arena, blocks + arena < 0xffffffffull};
-}
-
 // The staging the two batch entry points for files share, kept in the context between calls: two pinned host slots (the host
 // threads work in one while the device works from / into the other), two device slots, two events per slot and a second
 // stream so that uploads and downloads overlap (full-duplex PCIe).
@@ -107,6 +95,82 @@ int after_both_streams(jpeg_amd_ctx *ctx, int result)
     return result;
 }
 
+// The `nthreads` argument of the batch file calls: <= 0 leaves the number to the library.
+int host_threads(int nthreads, bool *auto_threads)
+{
+    if (auto_threads) *auto_threads = nthreads <= 0;
+    return std::max(1, nthreads <= 0 ? default_host_threads() : nthreads);
+}
+
+// (the infos are the parser's: the units follow from the size and the factors, so this is "one geometry" and no more)
+static bool same_frame(const jpeg_amd_frame_info &a, const jpeg_amd_frame_info &b)
+{
+    bool same = a.width == b.width && a.height == b.height && a.precision == b.precision && a.ncomponents == b.ncomponents;
+    for (int c = 0; same && c < a.ncomponents; ++c)
+        same = a.factor_x[c] == b.factor_x[c] && a.factor_y[c] == b.factor_y[c] && a.units_x[c] == b.units_x[c] && a.units_y[c] == b.units_y[c];
+    return same;
+}
+
+int FileBatch::decode_to_slot(int file, const Into &to, const jpeg_amd_frame_info &frame, const SparseBudget &sb, bool inspect_dense,
+                              std::vector<uint32_t> &record, uint64_t *where, bool *dense)
+try {
+    const uint8_t *data = h_jpeg[file];
+    *dense = true;
+    if (!data) return JPEG_AMD_EINVAL;
+    jpeg_amd_frame_info seen{};
+    // Sparse first, without a look at the headers beforehand: the decoder itself refuses a frame with more blocks than the
+    // descriptor array holds and never writes past the arena, so a file of another geometry is caught afterwards.
+    if (sb.ok) {
+        if (record.size() < sb.elems) record.resize(sb.elems);          // (this thread's; kept in the context between calls, trimmed on the way out when huge)
+        size_t n = 0;
+        const int ss = jpeg_amd_jpeg_decode_sparse(data, nbytes[file], record.data(), sb.blocks, record.data() + sb.blocks, sb.arena, &n, to.quanta, &seen);
+        if (ss == JPEG_AMD_OK) {
+            if (!same_frame(seen, frame)) return JPEG_AMD_EINVAL;       // (mixed calls: the bytes changed under the call)
+            // the record goes behind the ones already in the slot (the records of a chunk, of at most sb.elems each, always fit)
+            *where = loop.packed_end[to.slot].fetch_add(sb.blocks + n);
+            std::memcpy(to.packed + *where, record.data(), (sb.blocks + n) * 4);
+            *dense = false;
+            return JPEG_AMD_OK;
+        }
+        if (ss != JPEG_AMD_ENOSUP) return ss;                           // (EINVAL may be "more blocks than the frame": the same verdict either way)
+    }
+    // progressive, a missing restart marker, too dense, or not tried: planes (fewer files than threads: the spare threads go to
+    // the file's restart intervals)
+    if (inspect_dense) {
+        JA_TRY(jpeg_amd_jpeg_inspect(data, nbytes[file], &seen));
+        if (!same_frame(seen, frame)) return JPEG_AMD_EINVAL;
+    }
+    const int inner = std::max(1, nthreads / to.m);
+    return jpeg_amd_jpeg_decode_spectral_mt(data, nbytes[file], to.planes, to.quanta, nullptr, inner > 1 && auto_threads ? 0 : inner);
+}
+catch (...) { return JPEG_AMD_ENOMEM; }   // (the record's growth: nothing may be thrown on a thread of the queue)
+
+// The loop's device side on the context's stream and events: file_decoded[slot] is recorded behind the uploads and kernels of
+// a chunk, file_done[slot] where its pixels are where the call leaves them (submit records both); a failure is JPEG_AMD_EHIP
+// with the context's last_hip set.
+ChunkDevice FileBatch::device(std::function<int(int)> submit)
+{
+    jpeg_amd_ctx *c = ctx;
+    auto reached = [c](hipEvent_t ev) {
+        const hipError_t w = wait_event(ev);
+        if (w != hipSuccess) c->last_hip = (int)w;
+        return w == hipSuccess;
+    };
+    ChunkDevice dev;
+    dev.slot_free = [c, reached](int slot) { return reached(c->file_decoded[slot]); };
+    dev.finished = [c, reached](int slot) { return reached(c->file_done[slot]); };
+    dev.submit = std::move(submit);
+    dev.failure = JPEG_AMD_EHIP;
+    return dev;
+}
+
+// (the threads' sparse records stay in the context between calls -- a batch of 1080p files: 5 MB per thread -- unless huge)
+int FileBatch::run_chunks(const std::vector<int> &first, const FileQueue::Decode &decode, const ChunkDevice &dev)
+{
+    const int t_n = std::min(nthreads, n_images);
+    return after_both_streams(ctx, loop.run(pool_with(ctx->workers, t_n + 1), ctx->records, first, t_n, decode, (size_t)16 << 20, dev));
+}
+
 }  // namespace capi
 }  // namespace jpeg_amd
 
@@ -125,19 +189,6 @@ bool is_pinned_host(const void *p, size_t bytes)
     }
     return true;
 }
-
-// Where the parts of a staging slot of the batch pipelines begin (pinned and device slots alike): take(n) gives the next n
-// bytes, aligned to 256, and a part of no bytes takes none.  Each pipeline uses the parts it has.
-struct SlotLayout {
-    size_t coef_off[JPEG_AMD_MAX_PLANES] = {};
-    size_t quanta_off = 0, skip_off = 0, where_off = 0, sparse_off = 0, count_off = 0, px_off = 0, slot_bytes = 0;
-    size_t take(size_t n)
-    {
-        const size_t at = slot_bytes;
-        slot_bytes += align256(n);
-        return at;
-    }
-};
 
 // m images of npx bytes between host and device, image i at i * stride on either side: one copy when both sides are
 // contiguous (a staging slot always is; a caller's buffer with a stride of npx), else a copy per image.
@@ -177,8 +228,7 @@ try {
     jpeg_amd_frame_info fi;
     JA_TRY(jpeg_amd_jpeg_inspect(h_jpeg, nbytes, &fi));
     if (info_out) *info_out = fi;
-    // JPEG.Common recognises 8-bit images of arity 1 or 3 (jpeg.swift:357-424)
-    if (fi.precision != 8 || (fi.ncomponents != 1 && fi.ncomponents != 3)) return JPEG_AMD_ENOSUP;
+    if (!jpeg_common(fi.precision, fi.ncomponents)) return JPEG_AMD_ENOSUP;
     const size_t need = (size_t)fi.width * fi.height * 3;
     if (!h_pixels || pixel_capacity < need) return JPEG_AMD_EINVAL;
     // a batch of one: pinned staging kept in the context, restart intervals and the copy-out on
@@ -222,13 +272,7 @@ namespace {
 
 // One call of jpeg_amd_decompress_batch[_device] behind its checks: what is constant for the call (set by
 // decompress_batch_impl), and the parts of the pipeline.
-struct BatchDecode {
-    jpeg_amd_ctx *ctx;
-    const uint8_t *const *h_jpeg;
-    const size_t *nbytes;
-    int n_images, nthreads, cosited;
-    bool auto_threads;
-    jpeg_amd_color color;
+struct BatchDecode : FileBatch {
     uint8_t *h_pixels, *d_pixels_out;          // in host memory, or left on the device
     size_t pixel_stride, npx, plane[JPEG_AMD_MAX_PLANES] = {};
     jpeg_amd_frame_info fi;                    // image 0's: one geometry per batch
@@ -237,35 +281,8 @@ struct BatchDecode {
     SparseBudget sb;
     SlotLayout at;
     bool to_host, direct_out, copies_out;
-    std::atomic<size_t> packed_end[2];         // per slot: elements of the records packed so far
 
     int images(int k) const { return std::min(chunk, n_images - k * chunk); }
-    // one geometry per batch: the buffers are sized for image 0
-    bool same_geometry(const jpeg_amd_frame_info &f) const
-    {
-        bool same = f.width == fi.width && f.height == fi.height && f.precision == 8 && f.ncomponents == nc;
-        for (int c = 0; same && c < nc; ++c)
-            same = f.factor_x[c] == fi.factor_x[c] && f.factor_y[c] == fi.factor_y[c];
-        return same;
-    }
-    // Chunk k on its way back: its pixels are copied out of the pinned slot by the context's copy threads once the download is
-    // complete (PixelDrain: the first thread to get there waits for it, the others for that thread).
-    void begin_drain(PixelDrain &drain, int k)
-    {
-        const int slot = k & 1, device = ctx->device;
-        hipEvent_t done = ctx->file_done[slot];
-        drain.begin(images(k), static_cast<const uint8_t *>(ctx->file_pinned[slot]) + at.px_off, npx, h_pixels + (size_t)k * chunk * pixel_stride,
-                    pixel_stride, [device, done] {
-                        (void)hipSetDevice(device);
-                        return wait_event(done) == hipSuccess;
-                    });
-    }
-    int end_drain(PixelDrain &drain)
-    {
-        if (drain.end()) return JPEG_AMD_OK;
-        ctx->last_hip = (int)hipErrorUnknown;
-        return JPEG_AMD_EHIP;
-    }
     int decode_file(int file, std::vector<uint32_t> &record);
     int submit(int k);
     int run();
@@ -274,53 +291,25 @@ struct BatchDecode {
 // The entropy decoding of one file, on a thread of the file queue, into pinned slot k & 1 of its chunk k.
 int BatchDecode::decode_file(int file, std::vector<uint32_t> &record)
 {
-    const int k = file / chunk, i = file - k * chunk, slot = k & 1, m = images(k);
-    char *host = static_cast<char *>(ctx->file_pinned[slot]);
-    uint8_t *skip = reinterpret_cast<uint8_t *>(host + at.skip_off);
-    // fewer files than threads: the spare threads go to the restart intervals of each file (planes: the sparse form
-    // is written by one thread per file)
-    const int inner = std::max(1, nthreads / m);
-    int16_t *planes[JPEG_AMD_MAX_PLANES] = {};
-    for (int c = 0; c < nc; ++c) planes[c] = reinterpret_cast<int16_t *>(host + at.coef_off[c]) + plane[c] * i;
-    uint16_t(*quanta)[64] = reinterpret_cast<uint16_t(*)[64]>(host + at.quanta_off + (size_t)i * kQSlotElems * 2);
-    jpeg_amd_frame_info f{};
-    skip[i] = 1;
-    if (!h_jpeg[file]) return JPEG_AMD_EINVAL;
-    int st = JPEG_AMD_OK;
-    // Sparse first, without a look at the headers beforehand: the decoder itself refuses a frame with more blocks than the
-    // descriptor array holds and never writes past the arena, so a file of another geometry is caught afterwards.
-    // (spare threads only help a file that has restart intervals; such a file is decoded into planes on `inner` threads)
-    bool sparse_done = false;
-    if ((inner == 1 || fi.restart_interval == 0) && sb.ok) {
-        if (record.size() < sb.elems) record.resize(sb.elems);      // (this thread's; kept in the context between calls, trimmed on the way out when huge)
-        size_t n = 0;
-        const int ss = jpeg_amd_jpeg_decode_sparse(h_jpeg[file], nbytes[file], record.data(), sb.blocks, record.data() + sb.blocks, sb.arena, &n, quanta, &f);
-        if (ss == JPEG_AMD_OK) {
-            if (!same_geometry(f)) return JPEG_AMD_EINVAL;
-            // the record goes behind the ones already in the slot (m records of at most sb.elems always fit)
-            const size_t where = packed_end[slot].fetch_add(sb.blocks + n);
-            std::memcpy(reinterpret_cast<uint32_t *>(host + at.sparse_off) + where, record.data(), (sb.blocks + n) * 4);
-            reinterpret_cast<uint64_t *>(host + at.where_off)[i] = where;
-            skip[i] = 0;
-            sparse_done = true;
-        } else if (ss != JPEG_AMD_ENOSUP) {
-            // (EINVAL may be "more blocks than image 0": the same verdict either way)
-            return ss;
-        }
-    }
-    if (!sparse_done) {
-        st = jpeg_amd_jpeg_inspect(h_jpeg[file], nbytes[file], &f);
-        if (st == JPEG_AMD_OK && !same_geometry(f)) st = JPEG_AMD_EINVAL;
-    }
-    if (st == JPEG_AMD_OK && skip[i])
-        st = jpeg_amd_jpeg_decode_spectral_mt(h_jpeg[file], nbytes[file], planes, quanta, nullptr, inner > 1 && auto_threads ? 0 : inner);
+    const int k = file / chunk, i = file - k * chunk, m = images(k);
+    char *host = static_cast<char *>(ctx->file_pinned[k & 1]);
+    Into to{k & 1, m, reinterpret_cast<uint32_t *>(host + at.sparse_off), reinterpret_cast<uint16_t(*)[64]>(host + at.quanta_off + (size_t)i * kQSlotElems * 2), {}};
+    for (int c = 0; c < nc; ++c) to.planes[c] = reinterpret_cast<int16_t *>(host + at.coef_off[c]) + plane[c] * i;
+    // spare threads only help a file that has restart intervals, and the sparse form is written by one thread per file: with
+    // fewer files than threads a batch of such files travels as planes
+    SparseBudget mine = sb;
+    mine.ok = sb.ok && (nthreads / m <= 1 || fi.restart_interval == 0);
+    bool dense = true;
+    // (one geometry per batch, image 0's: the buffers are sized for it, and no other file has been looked at)
+    const int st = decode_to_slot(file, to, fi, mine, true, record, reinterpret_cast<uint64_t *>(host + at.where_off) + i, &dense);
+    reinterpret_cast<uint8_t *>(host + at.skip_off)[i] = dense;
     return st;
 }
 
 // the device side of chunk k (asynchronous); the host moves on to chunk k + 1 meanwhile.
 // Device slot `slot` was last read by the download of chunk k - 2, finished before drain(k - 2)
 // returned.  Upload + kernels on the context's stream, download on the second one.
-// (a failure in here leaves copies and kernels in flight: no early return in run(), its common tail waits for both streams)
+// (a failure in here leaves copies and kernels in flight: run_chunks() waits for both streams on the way out)
 int BatchDecode::submit(int k)
 {
     const int slot = k & 1, base = k * chunk, m = images(k);
@@ -338,7 +327,7 @@ int BatchDecode::submit(int k)
                                            hipMemcpyHostToDevice, ctx->stream));
     }
     // tables, flags, record offsets and the packed records: one copy
-    JA_HIP(ctx, hipMemcpyAsync(dev + at.quanta_off, host + at.quanta_off, at.sparse_off - at.quanta_off + packed_end[slot].load() * 4, hipMemcpyHostToDevice, ctx->stream));
+    JA_HIP(ctx, hipMemcpyAsync(dev + at.quanta_off, host + at.quanta_off, at.sparse_off - at.quanta_off + loop.packed_end[slot].load() * 4, hipMemcpyHostToDevice, ctx->stream));
     if (any_sparse) {
         PlaneSetMut cs{};
         for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = plane[c]; }
@@ -361,56 +350,36 @@ int BatchDecode::submit(int k)
     return JPEG_AMD_OK;
 }
 
-// The chunk loop.  The entropy decoding: ONE queue of files for the whole call (FileQueue), decoded on t_n host threads beside
-// this one, which directs; this thread submits a chunk to the device as soon as its last file is in.  Chunk j is decoded into
-// pinned slot j & 1, which is free once the kernels of chunk j - 2 are done (its uploads read the slot's coefficient, sparse and
-// table regions; file_decoded[slot] is recorded behind them).  The helper thread that copies chunk j - 2's pixels out of the same
-// slot may still be running; it only reads the pixel region, which the decoders do not touch.
+// The chunk loop is worker_pool.hpp's (ChunkLoop); this is its device side.  The helper threads that copy chunk k - 2's pixels
+// out of a pinned slot may still be running while chunk k is decoded into it: they only read the pixel region, which the
+// decoders do not touch.
 int BatchDecode::run()
 {
-    int result = JPEG_AMD_OK;
     WorkerPool *copiers = copies_out ? &pool_with(ctx->copiers, std::min(nthreads, 16) + 1) : nullptr;
-    PixelDrain drain(copiers, std::min(nthreads, 16) + 1);   // (declared before the queue: joined on every way out, after it)
-    packed_end[0].store(0); packed_end[1].store(0);
-    const int t_n = std::min(nthreads, n_images);
-    // (the threads' sparse records stay in the context between calls -- a batch of 1080p files: 5 MB per thread -- unless huge)
-    FileQueue queue(pool_with(ctx->workers, t_n + 1), ctx->records, n_images, chunk, t_n, [this](int file, std::vector<uint32_t> &record) {
-        try { return decode_file(file, record); } catch (...) { return (int)JPEG_AMD_ENOMEM; }
-    }, (size_t)16 << 20);
-    for (int k = 0; k < nchunks && result == JPEG_AMD_OK; ++k) {
-        const int slot = k & 1;
-        // (like every failure inside this loop it leaves through the common tail below, which waits for both streams)
-        // With threads, chunk k + 1 is opened while they are in chunk k: a thread that is through with chunk k goes straight on,
-        // and this thread waits for chunk k - 1's kernels here, where it has nothing else to do.  Without, this thread decodes
-        // chunk k itself (in wait(k)), in front of the chunk's submission.
-        const int j = queue.threaded() ? k + 1 : k;
-        if (j >= 2 && j < nchunks) {
-            const hipError_t w = wait_event(ctx->file_decoded[j & 1]);
-            if (w != hipSuccess) { ctx->last_hip = (int)w; result = JPEG_AMD_EHIP; break; }
-            packed_end[j & 1].store(0);                       // (chunks 0 and 1 start from the initial zeros)
-        }
-        queue.open(std::min(j + 1, nchunks));
-        result = queue.wait(k);
-        { const int ds = end_drain(drain); if (ds != JPEG_AMD_OK) result = ds; }   // chunk k - 1 is out of its pinned slot: chunk k + 1's download may land there
-        // (downloads that go straight into the caller's buffer are not waited for by a copy out: the device slot's pixels of
-        // chunk k - 2 must have left before chunk k's kernels write there)
-        if (result == JPEG_AMD_OK && direct_out && k >= 2) {
-            const hipError_t w = wait_event(ctx->file_done[slot]);
-            if (w != hipSuccess) { ctx->last_hip = (int)w; result = JPEG_AMD_EHIP; }
-        }
-        if (result != JPEG_AMD_OK) break;
-        result = submit(k);
-        if (result != JPEG_AMD_OK) break;
-        // chunk k - 1 is copied out by the copy threads WHILE the others decode chunk k + 1; it has
-        // to be finished before chunk k + 1 is submitted (its download lands in the same pinned slot)
-        if (k >= 1 && copies_out) begin_drain(drain, k - 1);
+    PixelDrain drain(copiers, std::min(nthreads, 16) + 1);
+    ChunkDevice dev = device([this](int k) { return submit(k); });
+    // (downloads that go straight into the caller's buffer are not waited for by a copy out: the device slot's pixels of chunk
+    // k - 2 must have left before chunk k's kernels write there)
+    if (direct_out) dev.pixels_gone = dev.finished;
+    // Chunk k on its way back: its pixels are copied out of the pinned slot by the context's copy threads once the download is
+    // complete (PixelDrain: the first thread to get there waits for it, the others for that thread).
+    if (copies_out) {
+        dev.begin_drain = [this, &drain](int k) {
+            const int device = ctx->device;
+            hipEvent_t done = ctx->file_done[k & 1];
+            drain.begin(images(k), static_cast<const uint8_t *>(ctx->file_pinned[k & 1]) + at.px_off, npx, h_pixels + (size_t)k * chunk * pixel_stride,
+                        pixel_stride, [device, done] {
+                            (void)hipSetDevice(device);
+                            return wait_event(done) == hipSuccess;
+                        });
+        };
+        dev.end_drain = [this, &drain] {
+            const bool arrived = drain.end();
+            if (!arrived) ctx->last_hip = (int)hipErrorUnknown;
+            return arrived;
+        };
     }
-    { const int ds = end_drain(drain); if (result == JPEG_AMD_OK) result = ds; }
-    if (result != JPEG_AMD_OK) return after_both_streams(ctx, result);
-    // the last chunk: wait for it (and for everything before it on the download stream), copy it out
-    JA_HIP(ctx, wait_event(ctx->file_done[(nchunks - 1) & 1]));
-    if (copies_out) { begin_drain(drain, nchunks - 1); JA_TRY(end_drain(drain)); }
-    return JPEG_AMD_OK;
+    return run_chunks(FileQueue::uniform_chunks(n_images, chunk), [this](int file, std::vector<uint32_t> &record) { return decode_file(file, record); }, dev);
 }
 
 // Files -> pixels, in host memory (h_pixels) or left on the device (d_pixels_out): see jpeg_amd_decompress_batch[_device].
@@ -428,7 +397,7 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
     d.to_host = h_pixels != nullptr;
     JA_TRY(jpeg_amd_jpeg_inspect(h_jpeg[0], nbytes[0], &d.fi));
     if (info_out) *info_out = d.fi;
-    if (d.fi.precision != 8 || (d.fi.ncomponents != 1 && d.fi.ncomponents != 3)) return JPEG_AMD_ENOSUP;
+    if (!jpeg_common(d.fi.precision, d.fi.ncomponents)) return JPEG_AMD_ENOSUP;
     d.nc = d.fi.ncomponents;
     d.npx = (size_t)d.fi.width * d.fi.height * 3;
     if (pixel_stride == 0) pixel_stride = d.npx;
@@ -454,9 +423,7 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
     d.at.sparse_off = d.at.take(d.sb.elems * 4 * d.chunk);
     d.at.px_off = d.at.take(d.to_host ? d.npx * d.chunk : 0);
     JA_TRY(ensure_file_staging(ctx, d.at.slot_bytes, d.at.slot_bytes));
-    d.auto_threads = nthreads <= 0;
-    if (d.auto_threads) nthreads = default_host_threads();
-    d.nthreads = std::max(1, nthreads);
+    d.nthreads = host_threads(nthreads, &d.auto_threads);
 
     d.nchunks = (n_images + d.chunk - 1) / d.chunk;
     // a caller whose pixel buffer is page-locked gets the download straight into it: no copy out of the pinned slot
@@ -495,8 +462,7 @@ try {
     JA_TRY(bind(ctx));
     if (!frame || !h_pixels || !quanta_key || !h_quanta || !h_quanta_keys || !scans || !nbytes) return JPEG_AMD_EINVAL;
     const int nc = frame->ncomponents;
-    // JPEG.Common: 8-bit, arity 1 or 3 (jpeg.swift:357-424)
-    if (frame->precision != 8 || (nc != 1 && nc != 3)) return JPEG_AMD_ENOSUP;
+    if (!jpeg_common(frame->precision, nc)) return JPEG_AMD_ENOSUP;
     jpeg_amd_layout L;
     JA_TRY(layout_of_frame(frame, quanta_key, h_quanta_keys, ntables, &L));
     HostPlanes out(L);
@@ -713,7 +679,7 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
         return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
     const int nc = frame->ncomponents;
-    if (frame->precision != 8 || (nc != 1 && nc != 3)) return JPEG_AMD_ENOSUP;
+    if (!jpeg_common(frame->precision, nc)) return JPEG_AMD_ENOSUP;
     const size_t npx = (size_t)frame->width * frame->height * 3;
     if (pixel_stride == 0) pixel_stride = npx;
     if (pixel_stride < npx) return JPEG_AMD_EINVAL;
@@ -727,8 +693,7 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
         e.d_tensor = d_tensor; e.tensor_stride = tensor_stride; e.source = source;
     }
     e.chunk = std::min(n_images, 32);
-    if (e.nthreads <= 0) e.nthreads = default_host_threads();
-    e.nthreads = std::max(1, e.nthreads);
+    e.nthreads = host_threads(e.nthreads, nullptr);
 
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &e.d_q));
     // Sequential scans: the coefficients come down as SPARSE entries (k_sparsify: a descriptor per block + an entry per

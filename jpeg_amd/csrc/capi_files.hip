@@ -1,7 +1,8 @@
 // capi_files.hip -- the C ABI, files of mixed sizes and layouts to one tensor (jpeg_amd_decompress_tensor_mixed) or to
 // resized bytes (jpeg_amd_decompress_resized_mixed): the file front end of the mixed calls of capi_view.hip.  The contract,
-// the route and the cost are stated in include/jpeg_amd.h ("files to tensors"); the host threads are worker_pool.hpp's, the
-// staging is capi_file.hip's.
+// the route and the cost are stated in include/jpeg_amd.h ("files to tensors").  The pipeline is the one of the uniform batch
+// decode -- worker_pool.hpp's chunk loop over capi_file.hip's staging, the threads' work and the loop's device side (see
+// capi_internal.hpp) -- with chunks of the call's own cutting, no pixels to bring back, and this file's submit(k).
 #pragma clang fp contract(off)
 
 #include "capi_internal.hpp"
@@ -36,13 +37,7 @@ struct FileChunk {
 };
 
 // One call behind its checks.
-struct FilesDecode {
-    jpeg_amd_ctx *ctx;
-    const uint8_t *const *h_jpeg;
-    const size_t *nbytes;
-    int n_images, nthreads, cosited;
-    bool auto_threads;
-    jpeg_amd_color color;
+struct FilesDecode : FileBatch {
     int32_t out_w, out_h;
     int filter;
     bool tensor;
@@ -50,65 +45,36 @@ struct FilesDecode {
     const uint8_t *h_flip;
     void *d_dst;
     size_t dst_stride, elem_bytes;
-    std::vector<FileSpec> files;               // (declared before run()'s queue: the threads write into it until they are stopped)
+    std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
     std::vector<FileChunk> chunks;
     std::vector<int> chunk_of;                 // per file
-    std::atomic<size_t> packed_end[2];         // per slot: elements of the records packed so far
 
     int decode_file(int file, std::vector<uint32_t> &record);
     int submit(int k);
     int run();
 };
 
-bool same_frame(const jpeg_amd_frame_info &a, const jpeg_amd_frame_info &b)
-{
-    bool same = a.width == b.width && a.height == b.height && a.precision == b.precision && a.ncomponents == b.ncomponents;
-    for (int c = 0; same && c < a.ncomponents; ++c)
-        same = a.factor_x[c] == b.factor_x[c] && a.factor_y[c] == b.factor_y[c] && a.units_x[c] == b.units_x[c] && a.units_y[c] == b.units_y[c];
-    return same;
-}
-
-// The entropy decoding of one file, on a thread of the file queue, into pinned slot k & 1 of its chunk k: sparse first, packed
-// behind the records already in the slot as BatchDecode::decode_file packs them; planes where the sparse decoder says ENOSUP.
+// The entropy decoding of one file, on a thread of the file queue, into pinned slot k & 1 of its chunk k.
 int FilesDecode::decode_file(int file, std::vector<uint32_t> &record)
 {
-    const int k = chunk_of[(size_t)file], slot = k & 1;
+    const int k = chunk_of[(size_t)file];
     const FileChunk &ch = chunks[(size_t)k];
     FileSpec &f = files[(size_t)file];
-    char *host = static_cast<char *>(ctx->file_pinned[slot]);
-    uint16_t(*quanta)[64] = reinterpret_cast<uint16_t(*)[64]>(host + ch.quanta_off + (size_t)(file - ch.i0) * kQSlotElems * 2);
-    f.dense = true;
-    if (f.sb.ok) {
-        if (record.size() < f.sb.elems) record.resize(f.sb.elems);      // (this thread's; kept in the context between calls)
-        size_t n = 0;
-        jpeg_amd_frame_info seen{};
-        const int ss = jpeg_amd_jpeg_decode_sparse(h_jpeg[file], nbytes[file], record.data(), f.sb.blocks, record.data() + f.sb.blocks,
-                                                   f.sb.arena, &n, quanta, &seen);
-        if (ss == JPEG_AMD_OK) {
-            if (!same_frame(seen, f.info)) return JPEG_AMD_EINVAL;      // (the bytes changed under the call)
-            f.where = packed_end[slot].fetch_add(f.sb.blocks + n);
-            std::memcpy(reinterpret_cast<uint32_t *>(host + ch.sparse_off) + f.where, record.data(), (f.sb.blocks + n) * 4);
-            f.dense = false;
-            return JPEG_AMD_OK;
-        }
-        if (ss != JPEG_AMD_ENOSUP) return ss;
-    }
-    // progressive, a missing restart marker, too dense: planes (fewer files than threads: the spare threads go to its restart
-    // intervals)
-    const int inner = std::max(1, nthreads / ch.m);
-    int16_t *planes[JPEG_AMD_MAX_PLANES] = {};
+    char *host = static_cast<char *>(ctx->file_pinned[k & 1]);
+    Into to{k & 1, ch.m, reinterpret_cast<uint32_t *>(host + ch.sparse_off),
+            reinterpret_cast<uint16_t(*)[64]>(host + ch.quanta_off + (size_t)(file - ch.i0) * kQSlotElems * 2), {}};
     size_t at = f.dense_off;
     for (int c = 0; c < f.layout.nplanes; ++c) {
-        planes[c] = reinterpret_cast<int16_t *>(host + ch.dense_off + at);
+        to.planes[c] = reinterpret_cast<int16_t *>(host + ch.dense_off + at);
         at += align256(plane_samples(&f.layout, c) * 2);
     }
-    return jpeg_amd_jpeg_decode_spectral_mt(h_jpeg[file], nbytes[file], planes, quanta, nullptr, inner > 1 && auto_threads ? 0 : inner);
+    return decode_to_slot(file, to, f.info, f.sb, false, record, &f.where, &f.dense);   // (what pass 0 saw, headers included)
 }
 
 // The device side of chunk k, asynchronous on the context's stream: the planes of its dense files, ONE copy of the tables, the
 // item records and the packed records, ONE windowed expand, then the mixed call on the chunk's images, as it stands.  The
 // plane buffer is one for all chunks: chunk k's copies and expand come behind chunk k - 1's kernels on the stream.
-// (a failure in here leaves copies and kernels in flight: run()'s tail waits for both streams)
+// (a failure in here leaves copies and kernels in flight: run_chunks() waits for both streams on the way out)
 int FilesDecode::submit(int k)
 {
     const int slot = k & 1;
@@ -150,7 +116,7 @@ int FilesDecode::submit(int k)
         acc += expand_mixed_groups(item);            // (the chunk's sum fits a grid: judged in pass 0)
     }
     groups[n_items] = (uint32_t)acc;
-    JA_HIP(ctx, hipMemcpyAsync(dev + ch.quanta_off, host + ch.quanta_off, ch.sparse_off - ch.quanta_off + packed_end[slot].load() * 4,
+    JA_HIP(ctx, hipMemcpyAsync(dev + ch.quanta_off, host + ch.quanta_off, ch.sparse_off - ch.quanta_off + loop.packed_end[slot].load() * 4,
                                hipMemcpyHostToDevice, ctx->stream));
     JA_HIP(ctx, launch_expand_mixed(ctx->stream, n_items, dev + ch.items_off, reinterpret_cast<const uint32_t *>(dev + ch.groups_off),
                                     (uint32_t)acc, reinterpret_cast<const uint32_t *>(dev + ch.sparse_off)));
@@ -164,42 +130,18 @@ int FilesDecode::submit(int k)
         JA_TRY(jpeg_amd_decode_resized_filter_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
                                                     static_cast<uint8_t *>(d_out), dst_stride));
     JA_HIP(ctx, hipEventRecord(ctx->file_decoded[slot], ctx->stream));
+    JA_HIP(ctx, hipEventRecord(ctx->file_done[slot], ctx->stream));     // the tensor stays where it is: done when the kernels are
     return JPEG_AMD_OK;
 }
 
-// The chunk loop, as BatchDecode::run has it: ONE queue of files for the whole call, decoded on t_n host threads beside this
-// one, which directs; this thread submits a chunk as soon as its last file is in.  Chunk j is decoded into pinned slot j & 1,
-// which is free once chunk j - 2's copies have read it (file_decoded[slot] is recorded behind them).
+// The chunk loop (ChunkLoop, worker_pool.hpp) without a drain.  (`files`, which the threads write into, is declared before it.)
 int FilesDecode::run()
 {
-    int result = JPEG_AMD_OK;
-    packed_end[0].store(0); packed_end[1].store(0);
-    const int nchunks = (int)chunks.size(), t_n = std::min(nthreads, n_images);
     std::vector<int> first;
     for (const FileChunk &ch : chunks) first.push_back(ch.i0);
     first.push_back(n_images);
-    {
-        // (the queue stops and joins the threads on every way out, a failed chunk included, BEFORE `files`, which they write
-        // into, goes away with this call -- and before it trims their records)
-        FileQueue queue(pool_with(ctx->workers, t_n + 1), ctx->records, first, t_n, [this](int file, std::vector<uint32_t> &record) {
-            try { return decode_file(file, record); } catch (...) { return (int)JPEG_AMD_ENOMEM; }
-        }, (size_t)16 << 20);
-        for (int k = 0; k < nchunks && result == JPEG_AMD_OK; ++k) {
-            // With threads, chunk k + 1 is opened while they are in chunk k; without, this thread decodes chunk k itself (in wait(k)).
-            const int j = queue.threaded() ? k + 1 : k;
-            if (j >= 2 && j < nchunks) {
-                const hipError_t w = wait_event(ctx->file_decoded[j & 1]);
-                if (w != hipSuccess) { ctx->last_hip = (int)w; result = JPEG_AMD_EHIP; break; }
-                packed_end[j & 1].store(0);                       // (chunks 0 and 1 start from the initial zeros)
-            }
-            queue.open(std::min(j + 1, nchunks));
-            result = queue.wait(k);
-            if (result == JPEG_AMD_OK) result = submit(k);
-        }
-    }
-    if (result != JPEG_AMD_OK) return after_both_streams(ctx, result);
-    JA_HIP(ctx, wait_event(ctx->file_decoded[(nchunks - 1) & 1]));
-    return JPEG_AMD_OK;
+    return run_chunks(first, [this](int file, std::vector<uint32_t> &record) { return decode_file(file, record); },
+                      device([this](int k) { return submit(k); }));
 }
 
 int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads, int cosited,
@@ -222,8 +164,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     for (int i = 0; i < n_images && bad == n_images; ++i) {
         FileSpec &f = d.files[(size_t)i];
         int st = h_jpeg[i] ? jpeg_amd_jpeg_inspect(h_jpeg[i], nbytes[i], &f.info) : JPEG_AMD_EINVAL;
-        // JPEG.Common recognises 8-bit images of arity 1 or 3 (jpeg.swift:357-424)
-        if (st == JPEG_AMD_OK && (f.info.precision != 8 || (f.info.ncomponents != 1 && f.info.ncomponents != 3))) st = JPEG_AMD_ENOSUP;
+        if (st == JPEG_AMD_OK && !jpeg_common(f.info.precision, f.info.ncomponents)) st = JPEG_AMD_ENOSUP;
         if (st == JPEG_AMD_OK) {
             if (h_info) h_info[i] = f.info;
             f.layout = layout_of_info(f.info, f.info.ncomponents);
@@ -276,10 +217,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
             } else {
                 for (int c = 0; c < f.layout.nplanes; ++c) f.window[c] = jpeg_amd_region{0, 0, f.layout.units_x[c], f.layout.units_y[c]};
             }
-            // (the decoder wants room for a whole block -- 72 entries -- in front of every block: without it a file of a
-            // few blocks would never travel sparse)
-            f.sb = sparse_budget(f.layout);
-            f.sb.arena += 72; f.sb.elems += 72;
+            f.sb = sparse_budget(f.layout, kSparseDecoderHeadroom);    // (or a file of a few blocks would never travel sparse)
             f.dense_off = dense;
             for (int c = 0; c < f.layout.nplanes; ++c) {
                 f.plane_off[c] = planes;
@@ -295,15 +233,14 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
         }
         if (groups > 0x7fffffffu) return JPEG_AMD_EINVAL;          // more workgroups than a grid holds
         // slot layout: [quanta x m][item records x m][workgroup prefix m + 1][packed records ...] | [planes of the dense files]
-        size_t at = 0;
-        auto take = [&at](size_t n) { const size_t was = at; at += align256(n); return was; };
-        ch.quanta_off = take((size_t)ch.m * kQSlotElems * 2);
-        ch.items_off = take((size_t)ch.m * rec_bytes);
-        ch.groups_off = take(((size_t)ch.m + 1) * 4);
-        ch.sparse_off = take(sparse);
-        ch.device_bytes = at;                                      // the dense files' planes go straight into the plane buffer
-        ch.dense_off = take(dense);
-        ch.slot_bytes = at;
+        SlotLayout at;
+        ch.quanta_off = at.take((size_t)ch.m * kQSlotElems * 2);
+        ch.items_off = at.take((size_t)ch.m * rec_bytes);
+        ch.groups_off = at.take(((size_t)ch.m + 1) * 4);
+        ch.sparse_off = at.take(sparse);
+        ch.device_bytes = at.slot_bytes;                           // the dense files' planes go straight into the plane buffer
+        ch.dense_off = at.take(dense);
+        ch.slot_bytes = at.slot_bytes;
         slot_bytes = std::max(slot_bytes, ch.slot_bytes);
         device_bytes = std::max(device_bytes, ch.device_bytes);
         plane_bytes = std::max(plane_bytes, planes);
@@ -315,9 +252,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     JA_TRY(bind(ctx));
     JA_TRY(ensure_file_staging(ctx, slot_bytes, device_bytes));
     JA_TRY(ensure_buffer(ctx, ctx->file_planes, std::max<size_t>(plane_bytes, 256)));
-    d.auto_threads = nthreads <= 0;
-    if (d.auto_threads) nthreads = default_host_threads();
-    d.nthreads = std::max(1, nthreads);
+    d.nthreads = host_threads(nthreads, &d.auto_threads);
     return d.run();
 }
 

@@ -11,6 +11,7 @@
 #include <new>
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <chrono>
 #include <system_error>
@@ -19,6 +20,7 @@
 
 #include "interleave.hpp"
 #include "kernels.hpp"
+#include "sparse_format.hpp"
 #include "transform.hpp"
 #include "worker_pool.hpp"
 
@@ -55,12 +57,13 @@ struct jpeg_amd_ctx {
     DeviceBuffer file_planes;
     int qslot = 0;
     int last_hip = 0;
-    // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_compress_batch), kept between calls: two pinned
-    // host slots (the host threads work in one while the device works from / into the other) and two device slots
+    // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_decompress_tensor_mixed, jpeg_amd_compress_batch), kept
+    // between calls: two pinned host slots (the host threads work in one while the device works from / into the other) and two
+    // device slots.  The decodes run worker_pool.hpp's ChunkLoop over it (below, "the batch file paths"); the encode has its own loop.
     void *file_pinned[2] = {nullptr, nullptr};
     void *file_device = nullptr;                      // both device slots
     size_t file_pinned_bytes = 0, file_device_bytes = 0;
-    hipEvent_t file_done[2] = {nullptr, nullptr};     // chunk's pixels (decode) / first stage of its download (encode) are back
+    hipEvent_t file_done[2] = {nullptr, nullptr};     // chunk's pixels are where the call leaves them (decode) / first stage of its download is back (encode)
     hipEvent_t file_decoded[2] = {nullptr, nullptr};  // chunk's kernels are done (device -> host copy may start)
     hipEvent_t file_fetched[2] = {nullptr, nullptr};  // encode: the second stage of the chunk's download is back
     hipStream_t file_d2h = nullptr;                   // downloads overlap the next chunk's uploads (full-duplex PCIe)
@@ -126,12 +129,56 @@ int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_imag
                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
                           bool tensor, void *d_dst, size_t dst_stride, int *taps);
 
-// The staging of the batch file paths and what their chunk loops share (capi_file.hip).
-struct SparseBudget {
-    size_t blocks, arena, elems;   // elems: uint32 per image, [descriptors][entries]
-    bool ok;
+// ---- the batch file paths: the staging, and what the two decode pipelines share (capi_file.hip) ---------------------------------
+// Both decode pipelines (files of one geometry to pixels, capi_file.hip; files of mixed sizes to one tensor, capi_files.hip) are
+// the chunk loop of worker_pool.hpp (ChunkLoop) over the staging below, with FileBatch::device() as its device side and
+// FileBatch::decode_to_slot() as the work of its threads; what differs is where a chunk's parts lie in its slot and what submit(k)
+// enqueues.  The encode pipeline has another shape (a two-stage download, one parallel region per step) and its own loop.
+
+// Where the parts of a staging slot of the batch pipelines begin (pinned and device slots alike): take(n) gives the next n
+// bytes, aligned to 256, and a part of no bytes takes none.  Each pipeline uses the parts it has.
+struct SlotLayout {
+    size_t coef_off[JPEG_AMD_MAX_PLANES] = {};
+    size_t quanta_off = 0, skip_off = 0, where_off = 0, sparse_off = 0, count_off = 0, px_off = 0, slot_bytes = 0;
+    size_t take(size_t n)
+    {
+        const size_t at = slot_bytes;
+        slot_bytes += align256(n);
+        return at;
+    }
 };
-SparseBudget sparse_budget(const jpeg_amd_layout &L);   // of a frame's sparse record
+// One call of a batch decode of files behind its checks: what the two pipelines share of it.
+struct FileBatch {
+    jpeg_amd_ctx *ctx;
+    const uint8_t *const *h_jpeg;
+    const size_t *nbytes;
+    int n_images, nthreads, cosited;
+    bool auto_threads;
+    jpeg_amd_color color;
+    ChunkLoop loop;
+
+    // Where a file, one of the m of its chunk, goes in the chunk's pinned slot: the slot's packed records, the file's tables
+    // and, should it travel dense, its planes.
+    struct Into {
+        int slot, m;
+        uint32_t *packed;
+        uint16_t (*quanta)[64];
+        int16_t *planes[JPEG_AMD_MAX_PLANES];
+    };
+    // One file, on a thread of the file queue: sparse into the thread's own record, then packed behind the records already in
+    // the slot (one fetch_add on loop.packed_end[slot]; *where: its offset in `packed`, elements); where the sparse decoder says
+    // ENOSUP, or sb.ok is false, into the planes on nthreads / m threads (*dense).  `frame`: what the file must be;
+    // inspect_dense: look at the headers of a file that goes into planes, because nobody has yet.
+    int decode_to_slot(int file, const Into &to, const jpeg_amd_frame_info &frame, const SparseBudget &sb, bool inspect_dense,
+                       std::vector<uint32_t> &record, uint64_t *where, bool *dense);
+    // The loop's device side on the context's stream and events, around the pipeline's submit(k).
+    ChunkDevice device(std::function<int(int)> submit);
+    // The chunk loop over chunks `first` on the context's threads; every way out is through after_both_streams.
+    int run_chunks(const std::vector<int> &first, const FileQueue::Decode &decode, const ChunkDevice &dev);
+};
+int host_threads(int nthreads, bool *auto_threads);   // the `nthreads` argument: <= 0 = default_host_threads(); at least 1
+// JPEG.Common recognises 8-bit images of arity 1 or 3 (jpeg.swift:357-424): what the pixel calls take
+inline bool jpeg_common(int precision, int ncomponents) { return precision == 8 && (ncomponents == 1 || ncomponents == 3); }
 // Two pinned host slots of slot_bytes and two device slots of device_slot_bytes, two events per slot and the second stream.
 int ensure_file_staging(jpeg_amd_ctx *ctx, size_t slot_bytes, size_t device_slot_bytes);
 int default_host_threads();                   // how many host threads "all cores" means

@@ -28,6 +28,9 @@
 #endif
 
 #include "../../include/jpeg_amd.h"
+#include "sparse_format.hpp"
+
+namespace sparse_fmt = jpeg_amd::sparse;   // (Decoder::sparse is the output of a sparse decode)
 
 namespace {
 
@@ -332,18 +335,14 @@ struct Component {
     size_t first_block = 0;   // sparse output: index of the plane's block (0, 0) in the descriptor array
 };
 
-// Sparse output of a sequential file (jpeg_amd_jpeg_decode_sparse): instead of int16 planes -- 128 bytes per block, of which a
-// typical file fills three or four coefficients -- one 32-bit ENTRY per nonzero coefficient (the DC always has one), the
-// entries of a block in a row, and per block the index of its first entry.  An eighth of the bytes to write on the host and
-// to move across PCIe; k_expand_sparse (kernels_stage.hip) turns it into the planes on the device.
-//   entry: bits 0-15 the coefficient, bits 16-21 its zigzag index, bit 31 the block's last entry
-//   descriptor: index of the block's first entry; kSparseAbsent = no scan reached the block (all zero)
+// Sparse output of a sequential file (jpeg_amd_jpeg_decode_sparse): the record of sparse_format.hpp instead of int16 planes.
+// An eighth of the bytes to write on the host and to move across PCIe; k_expand_sparse (kernels_stage.hip) turns it into the
+// planes on the device.
 struct SparseOut {
     uint32_t *desc = nullptr;
     uint32_t *entries = nullptr;
     size_t ndesc = 0, capacity = 0, n = 0;
 };
-constexpr uint32_t kSparseAbsent = 0xffffffffu, kSparseLast = 0x80000000u;
 int16_t g_sparse_sentinel[1];   // what Component::coef points at in a sparse decode (never dereferenced)
 
 struct Decoder {
@@ -728,7 +727,7 @@ struct Decoder {
             constexpr bool SPARSE = decltype(sparse_kind)::value;
             uint32_t *const ent0 = w.ent;
             if constexpr (SPARSE) {
-                if (w.ent + 72 > w.ent_end) return JPEG_AMD_ENOSUP;      // the arena is full: the caller decodes this file densely
+                if (w.ent + jpeg_amd::kSparseDecoderHeadroom > w.ent_end) return JPEG_AMD_ENOSUP;      // the arena is full: the caller decodes this file densely
             }
             const Slot &sl = slots[w.si];
             Component *c = sl.c;
@@ -749,7 +748,7 @@ struct Decoder {
                 if (t > 16) return JPEG_AMD_EINVAL;
                 if (t) w.pred[ci] += w.br.magnitude(t);
             }
-            if constexpr (SPARSE) *w.ent++ = (uint32_t)(uint16_t)(int16_t)w.pred[ci];
+            if constexpr (SPARSE) *w.ent++ = sparse_fmt::make((uint16_t)(int16_t)w.pred[ci], 0);
             else w.tmp[0] = (int16_t)w.pred[ci];
             // ---- AC (T.81 F.2.2.2) ----
             int k = 1;
@@ -778,7 +777,7 @@ struct Decoder {
                             continue;
                         }
                         k += r;
-                        if constexpr (SPARSE) *w.ent++ = (uint32_t)k << 16 | (uint16_t)(int16_t)w.br.magnitude(sz);
+                        if constexpr (SPARSE) *w.ent++ = sparse_fmt::make((uint16_t)(int16_t)w.br.magnitude(sz), (uint32_t)k);
                         else w.tmp[k] = (int16_t)w.br.magnitude(sz);  // k <= 63 + 15
                         ++k;
                         continue;
@@ -790,8 +789,8 @@ struct Decoder {
                         // coefficient is never zero; an entry without one has value 0, one with a single one repeats it)
                         const uint32_t a1 = (uint32_t)(en >> 4) & 127, a2 = (uint32_t)(en >> 11) & 127;
                         const uint32_t v1 = (uint32_t)(en >> 32) & 0xffffu, v2 = (uint32_t)(en >> 48);
-                        w.ent[0] = ((uint32_t)k + a1) << 16 | v1;
-                        w.ent[1] = ((uint32_t)k + a2) << 16 | v2;
+                        w.ent[0] = sparse_fmt::make(v1, (uint32_t)k + a1);
+                        w.ent[1] = sparse_fmt::make(v2, (uint32_t)k + a2);
                         w.ent += (v1 != 0) + (a1 != a2);
                     } else {
                         w.tmp[k + ((en >> 4) & 127)] = (int16_t)(en >> 32);
@@ -806,10 +805,10 @@ struct Decoder {
                     if (__builtin_expect(k > 64, 0)) {                   // a damaged stream ran past the block: drop what lies beyond
                         uint32_t *keep = ent0;
                         for (const uint32_t *q = ent0; q < w.ent; ++q)
-                            if ((*q >> 16) < 64) *keep++ = *q;
+                            if ((*q >> sparse_fmt::kZigzagShift) < 64) *keep++ = *q;   // (the whole index: no flag is set yet)
                         w.ent = keep;                                    // (the DC entry is always kept)
                     }
-                    w.ent[-1] |= kSparseLast;
+                    w.ent[-1] |= sparse_fmt::kLast;
                     sparse->desc[c->first_block + (size_t)c->ux * y + x] = (uint32_t)(ent0 - sparse->entries);
                 } else {
                     w.ent = ent0;                                        // decoded and dropped (decode.swift:1459-1475)
@@ -984,7 +983,7 @@ struct Decoder {
                             if (info.process == 2) return JPEG_AMD_ENOSUP;      // progressive scans add to a block: planes only
                             size_t frame_blocks = 0;
                             for (const Component &c : comps) frame_blocks += (size_t)c.ux * c.uy;
-                            if (frame_blocks > sparse->ndesc || frame_blocks >= kSparseAbsent) return JPEG_AMD_EINVAL;   // the caller's array is too small
+                            if (frame_blocks > sparse->ndesc || frame_blocks >= sparse_fmt::kAbsent) return JPEG_AMD_EINVAL;   // the caller's array is too small
                             std::memset(sparse->desc, 0xff, frame_blocks * sizeof(uint32_t));
                             for (int c = 0; c < info.ncomponents; ++c) comps[c].coef = g_sparse_sentinel;
                         } else if (coef)

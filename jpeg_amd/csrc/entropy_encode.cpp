@@ -45,6 +45,9 @@ asm(".pushsection .text\n.p2align 6\n.popsection");
 #endif
 
 #include "../../include/jpeg_amd.h"
+#include "sparse_format.hpp"
+
+namespace sparse = jpeg_amd::sparse;
 
 namespace {
 
@@ -387,7 +390,7 @@ struct Plane {
     }
 };
 
-// tokenize_block for a block given as entries (value, zigzag index, last-of-block flag; ascending index, the DC first):
+// tokenize_block for a block given as entries (sparse_format.hpp: ascending index, the DC first):
 // the runs come from the indices, no coefficient is looked at that is zero.  A block outside the plane or without a
 // descriptor is all zero.  Entries that run past the arena, or whose indices do not ascend, end the block (a damaged arena
 // must not be read out of bounds; the file is then simply not the image).
@@ -395,13 +398,13 @@ inline void tokenize_sparse(const Plane &p, int x, int y, int16_t &pred, TokenLi
 {
     uint32_t *t = list.room(70);
     const uint32_t *const t0 = t;
-    size_t at = (x < p.ux && y < p.uy) ? p.desc[(size_t)p.ux * y + x] : 0xffffffffu;
-    if (at >= p.nentries) at = p.nentries;                       // absent (0xFFFFFFFF) or out of range: no entries
+    size_t at = (x < p.ux && y < p.uy) ? p.desc[(size_t)p.ux * y + x] : sparse::kAbsent;
+    if (at >= p.nentries) at = p.nentries;                       // absent or out of range: no entries
     int16_t dc = 0;
     bool more = at < p.nentries;
-    if (more && ((p.entries[at] >> 16) & 63) == 0) {
-        dc = (int16_t)(p.entries[at] & 0xffffu);
-        more = !(p.entries[at] >> 31);
+    if (more && sparse::zigzag(p.entries[at]) == 0) {
+        dc = (int16_t)sparse::value(p.entries[at]);
+        more = !sparse::is_last(p.entries[at]);
         ++at;
     }
     int binade;
@@ -414,9 +417,9 @@ inline void tokenize_sparse(const Plane &p, int x, int y, int16_t &pred, TokenLi
     int prev = 0;
     while (more && at < p.nentries) {
         const uint32_t e = p.entries[at++];
-        more = !(e >> 31);
-        const int z = (int)(e >> 16) & 63;
-        const int16_t v = (int16_t)(e & 0xffffu);
+        more = !sparse::is_last(e);
+        const int z = (int)sparse::zigzag(e);
+        const int16_t v = (int16_t)(e & sparse::kValueMask);     // (sparse::value(e), spelled out: through the helper clang lays this loop out another way)
         if (z <= prev) break;
         if (v == 0) continue;                                    // (a zero is no entry; tolerated)
         int run = z - prev - 1;

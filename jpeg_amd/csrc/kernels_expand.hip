@@ -10,13 +10,10 @@
 // row by row, so the work-items of a wave write neighbouring blocks of one block row: at h = 8 a wave writes 1 KiB in a row, at
 // h = 4 the first half and at h = 1 the first eighth of each 128-byte block -- the planes keep their pitch, so a short head
 // can fill no more of a line than that; what it saves is the other bytes of the line and the entries behind the head.
-//
-// THE ORDER OF A BLOCK'S ENTRIES.  Both writers of the sparse form -- jpeg_amd_jpeg_decode_sparse (entropy.cpp: the DC, then
-// every AC coefficient as the scan's run lengths reach it, k only ever growing) and k_sparsify (kernels_stage.hip: i = 0 .. 31,
-// low half before high half) -- write a block's entries in ASCENDING zigzag order.  The walk relies on it: it stops at the first
-// entry at or behind 8 * head, or at the last-entry flag, whichever comes first.  Entries behind the head are not read beyond
-// that one.
+// The walk relies on the order of a block's entries (sparse_format.hpp): it stops at the first entry at or behind 8 * head, or
+// at the last-entry flag, whichever comes first.  Entries behind the head are not read beyond that one.
 #include "kernels.hpp"
+#include "sparse_format.hpp"
 
 #include <cstring>
 
@@ -70,20 +67,20 @@ __global__ __launch_bounds__(kThreads) void k_expand_mixed(ExpandMixedArgs g)
     const uint32_t block = ((uint32_t)r.y[p] + by) * (uint32_t)r.units_x[p] + (uint32_t)r.x[p] + bx;
     uint32_t w[4] = {0, 0, 0, 0};
     uint32_t at = g.packed[r.desc_at + r.desc_first[p] + block];
-    if (at != 0xffffffffu) {
+    if (at != sparse::kAbsent) {
         const uint32_t *e = g.packed + r.entries_at;
         const uint32_t end = 8u << shift;                 // the first zigzag index behind the head
         for (;; ++at) {
             const uint32_t v = e[at];
-            const uint32_t pos = (v >> 16) & 63;
+            const uint32_t pos = sparse::zigzag(v);
             if (pos >= end) break;                        // ascending: nothing of the head follows
             if ((pos >> 3) == octet) {
                 const uint32_t half = (pos & 1) * 16, word = (pos >> 1) & 3;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (word == (uint32_t)i) w[i] = (w[i] & ~(0xffffu << half)) | ((v & 0xffffu) << half);
+                    if (word == (uint32_t)i) w[i] = (w[i] & ~(sparse::kValueMask << half)) | (sparse::value(v) << half);
             }
-            if (v >> 31) break;
+            if (sparse::is_last(v)) break;
         }
     }
     *reinterpret_cast<uint4 *>(r.coef[p] + (size_t)block * 64 + 8 * octet) = make_uint4(w[0], w[1], w[2], w[3]);

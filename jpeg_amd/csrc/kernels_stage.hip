@@ -17,6 +17,7 @@
 #include "dct.hpp"
 #include "interleave.hpp"
 #include "kernels.hpp"
+#include "sparse_format.hpp"
 
 namespace jpeg_amd {
 
@@ -343,18 +344,19 @@ __global__ __launch_bounds__(kThreads) void k_sparsify(SparsifyArgs a)
     a.desc[img * a.desc_stride + b] = at;
     uint32_t *e = a.entries + img * a.entries_stride;
     uint32_t left = count;
+    // (an entry is sparse::make(value, index) | kLast on the last, spelled out: through the helper one v_or3_b32 takes its operands in another order)
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
         const uint32_t lo = w[i] & 0xffffu, hi = w[i] >> 16;
-        if (lo != 0 || i == 0) { --left; e[at++] = lo | (uint32_t)(2 * i) << 16 | (left == 0 ? 0x80000000u : 0u); }
-        if (hi != 0) { --left; e[at++] = hi | (uint32_t)(2 * i + 1) << 16 | (left == 0 ? 0x80000000u : 0u); }
+        if (lo != 0 || i == 0) { --left; e[at++] = lo | (uint32_t)(2 * i) << sparse::kZigzagShift | (left == 0 ? sparse::kLast : 0u); }
+        if (hi != 0) { --left; e[at++] = hi | (uint32_t)(2 * i + 1) << sparse::kZigzagShift | (left == 0 ? sparse::kLast : 0u); }
     }
 }
 
 // ---- sparse coefficients -> planes (the device side of jpeg_amd_jpeg_decode_sparse, entropy.cpp) -------------------------
 // Eight work-items per block, one 16-byte octet of the block each: they walk the block's entries together (the same address
 // for all eight: one fetch) and keep what falls into their octet; a workgroup writes 32 whole blocks = 4 KiB in a row.
-// Blocks no scan reached (descriptor 0xFFFFFFFF) and images flagged in `skip` (their planes were uploaded as they are) aside,
+// Blocks no scan reached (sparse::kAbsent) and images flagged in `skip` (their planes were uploaded as they are) aside,
 // every byte of the planes is written: no memset in front.
 struct ExpandArgs {
     const uint32_t *desc;      size_t desc_stride;       // per image: one descriptor per block, planes in frame order
@@ -377,21 +379,21 @@ __global__ __launch_bounds__(kThreads) void k_expand_sparse(ExpandArgs a)
     int p = 0;
 #pragma unroll
     for (int q = 1; q < JPEG_AMD_MAX_PLANES; ++q) p += (q < a.nplanes && b >= a.first[q]);
-    uint32_t w[4] = {0, 0, 0, 0};
     const uint32_t *desc = a.packed ? a.desc + a.packed[img] : a.desc + img * a.desc_stride;
+    uint32_t w[4] = {0, 0, 0, 0};
     uint32_t at = desc[b];
-    if (at != 0xffffffffu) {
+    if (at != sparse::kAbsent) {
         const uint32_t *e = a.packed ? desc + a.first[a.nplanes] : a.entries + img * a.entries_stride;
         for (;; ++at) {
             const uint32_t v = e[at];
-            const uint32_t pos = (v >> 16) & 63;
+            const uint32_t pos = sparse::zigzag(v);
             if ((pos >> 3) == octet) {
                 const uint32_t half = (pos & 1) * 16, word = (pos >> 1) & 3;
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (word == (uint32_t)k) w[k] = (w[k] & ~(0xffffu << half)) | ((v & 0xffffu) << half);
+                    if (word == (uint32_t)k) w[k] = (w[k] & ~(sparse::kValueMask << half)) | (sparse::value(v) << half);
             }
-            if (v >> 31) break;
+            if (sparse::is_last(v)) break;
         }
     }
     int16_t *dst = a.coef[0];

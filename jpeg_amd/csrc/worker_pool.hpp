@@ -1,6 +1,6 @@
-// worker_pool.hpp -- the host threads of the batch file paths (capi_file.hip): the pool, the file queue of the batch decode
-// and the drain of its pixels.  Header-only and free of HIP so that tests/cpp/worker_pool_test.cpp can run it under
-// ThreadSanitizer on a machine without a GPU.
+// worker_pool.hpp -- the host threads of the batch file paths (capi_file.hip, capi_files.hip): the pool, the file queue of the
+// batch decodes, the drain of their pixels and the chunk loop that directs them.  Header-only and free of HIP so that
+// tests/cpp/worker_pool_test.cpp and chunk_loop_test.cpp can run it under ThreadSanitizer on a machine without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -156,7 +156,6 @@ public:
         return st;
     }
 
-private:
     static std::vector<int> uniform_chunks(int files, int chunk)
     {
         std::vector<int> first;
@@ -164,6 +163,8 @@ private:
         first.push_back(files);
         return first;
     }
+
+private:
     int chunk_of(int file) const { return (int)(std::upper_bound(first_.begin(), first_.end(), file) - first_.begin()) - 1; }
     void run(int file, std::vector<uint32_t> &record)
     {
@@ -255,6 +256,72 @@ private:
     const size_t piece_;
     std::atomic<int> state_{0};      // 0: nobody has looked yet, 1: a thread is waiting, 2: the pixels are there, 3: failed
     bool draining_ = false;
+};
+
+// The device side of a batch decode, as the chunk loop sees it.  Chunk k is decoded into pinned slot k & 1 and submitted from
+// there; a callable that answers false has failed (and has noted why), and the loop ends with `failure`.
+struct ChunkDevice {
+    std::function<bool(int)> slot_free;      // (slot) wait until the chunk last submitted from the slot has been read out of it
+    std::function<int(int)> submit;          // (k) enqueue chunk k, whose files are all decoded; a status
+    std::function<bool(int)> finished;       // (slot) wait until the chunk last submitted from the slot is where the call leaves it
+    // a call whose pixels go straight from the device slot to the caller: (slot) wait until the pixels of the chunk last
+    // submitted from the slot have left, in front of the next submission from it (empty: nothing of the kind)
+    std::function<bool(int)> pixels_gone;
+    // a call whose pixels are copied out of the pinned slot by host threads (PixelDrain): begin(k) starts the copy of chunk k
+    // once it has arrived, end() joins it and says whether it arrived (empty: no copy)
+    std::function<void(int)> begin_drain;
+    std::function<bool()> end_drain;
+    int failure;
+};
+
+// The chunk loop of the batch decodes (jpeg_amd_decompress_batch[_device], jpeg_amd_decompress_tensor_mixed, _resized_mixed):
+// ONE queue of files for the whole call (FileQueue), decoded on `threads` host threads beside the calling one, which directs and
+// submits a chunk to the device as soon as its last file is in.
+//  - With threads, chunk k + 1 is opened while they are in chunk k: a thread that is through with chunk k goes straight on, and
+//    the director waits for chunk k - 1's kernels where it has nothing else to do.  Without, it decodes chunk k itself, in
+//    wait(k), in front of the chunk's submission.
+//  - Chunk j is decoded into pinned slot j & 1, which is opened again only after slot_free(j & 1): the uploads of chunk j - 2
+//    have read it.  packed_end[j & 1] -- the elements of the sparse records that the files of a chunk have packed one behind
+//    the other into the slot, drawn by each with one fetch_add -- is reset then, and read by submit(j).
+//  - The drain of chunk k - 1 runs beside the decoding of chunk k + 1 and is joined before chunk k + 1 is submitted: its download
+//    lands in the same pinned slot.  The copy only reads the slot's pixels, which the decoders do not touch.
+//  - The last chunk is waited for (and drained) on the way out.
+// Returns the first failing status: of a file (the last failing one of its chunk), of submit, or `failure`.  On a failure copies
+// and kernels may be in flight: the caller waits for its streams.  The queue dies in here, so the threads are stopped and
+// joined before run() returns: what decode() writes into must have been declared before the call, nothing more.
+struct ChunkLoop {
+    std::atomic<size_t> packed_end[2];
+
+    int run(WorkerPool &pool, std::vector<std::vector<uint32_t>> &records, const std::vector<int> &first, int threads,
+            FileQueue::Decode decode, size_t trim_above, const ChunkDevice &dev)
+    {
+        const int nchunks = (int)first.size() - 1, ok = 0;
+        int result = ok;
+        packed_end[0].store(0); packed_end[1].store(0);
+        auto end_drain = [&] { return !dev.end_drain || dev.end_drain() ? ok : dev.failure; };
+        {
+            FileQueue queue(pool, records, first, threads, std::move(decode), trim_above);
+            for (int k = 0; k < nchunks && result == ok; ++k) {
+                const int j = queue.threaded() ? k + 1 : k;
+                if (j >= 2 && j < nchunks) {
+                    if (!dev.slot_free(j & 1)) { result = dev.failure; break; }
+                    packed_end[j & 1].store(0);                       // (chunks 0 and 1 start from the initial zeros)
+                }
+                queue.open(std::min(j + 1, nchunks));
+                result = queue.wait(k);
+                if (end_drain() != ok) result = dev.failure;          // chunk k - 1 is out of its pinned slot: chunk k + 1's download may land there
+                if (result == ok && dev.pixels_gone && k >= 2 && !dev.pixels_gone(k & 1)) result = dev.failure;
+                if (result == ok) result = dev.submit(k);
+                if (result == ok && k >= 1 && dev.begin_drain) dev.begin_drain(k - 1);
+            }
+            const int drained = end_drain();
+            if (result == ok) result = drained;
+        }
+        if (result != ok) return result;
+        if (!dev.finished((nchunks - 1) & 1)) return dev.failure;
+        if (dev.begin_drain) dev.begin_drain(nchunks - 1);
+        return end_drain();
+    }
 };
 
 }  // namespace jpeg_amd

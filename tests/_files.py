@@ -99,6 +99,23 @@ def synthetic_file(name, size, seed, kind="sequential", restart=0, precision=8, 
     return write_file(L, planes, tables(L.nplanes, seed), "sequential" if kind == "dense" else kind, restart), L
 
 
+def undefined_tables(data):
+    """A copy whose first scan header names Huffman tables the file does not define: it passes jpeg_amd_jpeg_inspect and fails
+    in the entropy decoder, sparse or not."""
+    bad = data.copy()
+    sos = bytes(bad).index(b"\xff\xda")
+    assert bad[sos + 6] in (0, 0x11)
+    bad[sos + 6] = 0x33
+    return bad
+
+
+def lossless_marker(data):
+    """A copy whose frame header is marked lossless (SOF3): ENOSUP from every reader, jpeg_amd_jpeg_inspect included."""
+    bad = data.copy()
+    bad[bytes(bad).index(b"\xff\xc0") + 1] = 0xC3
+    return bad
+
+
 def golden_file(name):
     return np.fromfile(G.path("decode/" + name), np.uint8)
 

@@ -36,3 +36,14 @@ def test_worker_pool_is_clean_under_tsan(tmp_path):
     # mapping".  The child runs without address-space randomisation (setarch -R: a personality flag of that process only).
     r = subprocess.run(["setarch", platform.machine(), "-R", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])
+
+
+def test_chunk_loop_is_clean_under_tsan(tmp_path):
+    """The chunk loop of the batch decodes (csrc/worker_pool.hpp, ChunkLoop) under ThreadSanitizer with a fake device: which
+    slot is opened when, the record cursor of a slot, the order of submissions and drains, the three ways a call fails
+    (tests/cpp/chunk_loop_test.cpp lists the assertions); built and run as its neighbour above."""
+    exe = str(tmp_path / "chunk_loop_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "jpeg_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "chunk_loop_test.cpp"), "-o", exe, "-lpthread"])
+    r = subprocess.run(["setarch", platform.machine(), "-R", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])

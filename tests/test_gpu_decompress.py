@@ -322,6 +322,102 @@ def test_a_file_of_another_geometry_in_chunk_0_fails_the_call_and_the_context_de
         assert G.sha(out[i * w * h * 3:(i + 1) * w * h * 3]) == G.entry(names[i % len(names)])["gold"]["rgb_sha256"], i
 
 
+# ---- the status of the batch call, fault by fault (files of 16 x 16 to 48 x 32) --------------------------------------------------
+# File 0 sets the geometry: 4:2:2, 32 x 32, 32 blocks.  What a later file may be, and what the call then returns:
+BATCH_FAULTS = {
+    "smaller": _lib.EINVAL,              # fewer blocks: the sparse decoder takes it, the geometry check refuses it
+    "more-blocks": _lib.EINVAL,          # more blocks than file 0's descriptors: the sparse decoder refuses it
+    "other-subsampling": _lib.EINVAL,    # 4:4:0, 32 x 32: file 0's size AND block count; only the factors differ
+    "444": _lib.EINVAL,                  # file 0's size, more blocks
+    "null": _lib.EINVAL,
+    "undefined-tables": _lib.EINVAL,     # fails in the entropy decoder
+    "lossless": _lib.ENOSUP,             # a frame header no reader here takes: the one status of this list that is not EINVAL
+    "progressive": 0,                    # decoded into planes, among files that travel sparse
+}
+
+
+@pytest.fixture(scope="module")
+def batch_files():
+    import _files as F
+    good = [F.synthetic_file("422", (32, 32), 40 + i)[0] for i in range(3)]
+    faults = {
+        "smaller": F.synthetic_file("422", (16, 16), 50)[0],
+        "more-blocks": F.synthetic_file("422", (48, 32), 51)[0],
+        "other-subsampling": F.synthetic_file("440", (32, 32), 52)[0],
+        "444": F.synthetic_file("444", (32, 32), 53)[0],
+        "null": None,
+        "undefined-tables": F.undefined_tables(good[1]),
+        "lossless": F.lossless_marker(good[2]),
+        "progressive": F.synthetic_file("422", (32, 32), 54, kind="progressive")[0],
+    }
+    assert F.decode_sparse(faults["other-subsampling"])[2].size >= 32 and F.inspect(faults["other-subsampling"]).units_x[1] == 4
+    return good, faults
+
+
+def _batch_call(ctx, files, threads, npx=32 * 32 * 3):
+    """jpeg_amd_decompress_batch into pageable memory -> (status, pixels [n, npx])."""
+    import jpeg_amd as J
+    n = len(files)
+    out = np.zeros((n, npx), np.uint8)
+    ptrs = (C.c_void_p * n)(*[None if f is None else f.ctypes.data for f in files])
+    sizes = (C.c_size_t * n)(*[0 if f is None else f.size for f in files])
+    st = _lib.lib().jpeg_amd_decompress_batch(ctx.handle, ptrs, sizes, n, threads, 0, J.RGB.code, out.ctypes.data, 0, None)
+    return st, out
+
+
+def _one_by_one(ctx, files, npx=32 * 32 * 3):
+    """The per-file jpeg_amd_decompress of every file -> pixels [n, npx]."""
+    import jpeg_amd as J
+    out = np.zeros((len(files), npx), np.uint8)
+    for f, o in zip(files, out):
+        assert _lib.lib().jpeg_amd_decompress(ctx.handle, f.ctypes.data, f.size, 0, J.RGB.code, o.ctypes.data, o.size, None) == 0
+    return out
+
+
+@pytest.mark.parametrize("fault", sorted(BATCH_FAULTS))
+def test_batch_status_of_one_fault_behind_file_0(ctx, batch_files, fault):
+    good, faults = batch_files
+    files = [good[0], good[1], faults[fault], good[2]]
+    for threads in (1, 3, 0):
+        st, out = _batch_call(ctx, files, threads)
+        assert st == BATCH_FAULTS[fault], (fault, threads, st)
+        if st == 0:
+            assert (out == _one_by_one(ctx, files)).all()
+    st, out = _batch_call(ctx, good, 3)                                # the context after a refused call
+    assert st == 0 and (out == _one_by_one(ctx, good)).all()
+
+
+@pytest.mark.parametrize("first, second", [("smaller", "lossless"), ("lossless", "smaller"), ("null", "undefined-tables"),
+                                           ("undefined-tables", "null"), ("lossless", "more-blocks"), ("progressive", "lossless")])
+def test_batch_status_of_two_faults_is_the_later_file_s(ctx, batch_files, first, second):
+    """Two faults in one chunk: the call returns the status of the LAST failing file of the chunk, whichever thread met it
+    first."""
+    good, faults = batch_files
+    files = [good[0], faults[first], good[1], faults[second], good[2]]
+    for threads in (1, 3, 0):
+        assert _batch_call(ctx, files, threads)[0] == BATCH_FAULTS[second], (first, second, threads)
+
+
+@pytest.mark.parametrize("fault", ["smaller", "undefined-tables", "lossless", "null"])
+def test_batch_status_of_a_fault_in_chunk_2_behind_a_progressive_file_in_chunk_1(ctx, batch_files, fault):
+    """70 files = three chunks: pinned slot 0 is used again and its record cursor reset; a progressive file (planes) in chunk 1,
+    the fault in chunk 2; with 1, 2 and all threads.  (The clean three-chunk batch into pageable, page-locked and device memory,
+    progressive files in every chunk: test_decompress_batch_over_several_chunks_pageable_and_pinned_output and
+    test_decompress_batch_device_leaves_the_pixels_on_the_device, against the golds that the per-file call is held to.)"""
+    good, faults = batch_files
+    files = [good[i % 3] for i in range(70)]
+    files[40] = faults["progressive"]
+    clean = list(files)
+    files[66] = faults[fault]
+    for threads in (1, 2, 0):
+        assert _batch_call(ctx, files, threads)[0] == BATCH_FAULTS[fault], (fault, threads)
+    st, out = _batch_call(ctx, clean, 2)
+    assert st == 0
+    want = _one_by_one(ctx, [good[0], good[1], good[2], faults["progressive"]])
+    for i in range(70):
+        assert (out[i] == want[3 if i == 40 else i % 3]).all(), i
+
+
 def test_decompress_batch_without_a_single_helper_thread():
     """a process that cannot start one more thread (RLIMIT_NPROC reached) used to get ENOMEM for batches of more than
     two chunks; now the calling thread decodes every chunk itself in front of its submission.  In a fresh interpreter: context

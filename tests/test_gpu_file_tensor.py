@@ -77,8 +77,8 @@ def file_call(ctx, datas, regions, out_size, filter, out_ptr, stride, spec=None,
               whole=False):
     """The tensor call (spec) or the byte call -> (status, views [n, 5], infos)."""
     n = len(datas)
-    ptrs = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in datas])
-    sizes = (C.c_size_t * max(n, 1))(*[d.size for d in datas])
+    ptrs = (C.c_void_p * max(n, 1))(*[None if d is None else d.ctypes.data for d in datas])     # (None: a null pointer)
+    sizes = (C.c_size_t * max(n, 1))(*[0 if d is None else d.size for d in datas])
     regs = None if whole else (_lib.Region * max(n, 1))(*[_lib.Region(*r) for r in regions])
     infos, views = (_lib.FrameInfo * max(n, 1))(), (_lib.View * max(n, 1))()
     head = (ctx.handle, ptrs, sizes, n, threads, cosited, color, regs, out_size[0], out_size[1], filter)
@@ -263,6 +263,79 @@ def test_a_damaged_file_ends_the_call_and_the_context_stays_usable(ctx, torch, f
                          threads=threads)[0] == want
     cut = datas[0][:datas[0].size * 2 // 3].copy()
     compare(ctx, torch, [cut] + datas[1:], regions, OUT, _lib.FILTER_BILINEAR, "f16-chw")      # the next call, same context
+
+
+# ---- 5b. the status of the call, fault by fault (files of 16 x 16 to 48 x 32) ---------------------------------------------------------
+# Files of other sizes, block counts and subsamplings than file 0 are what the call is for (section 1).  What else a file may
+# be, and what the call then returns: the first file that pass 0 (the headers) refuses decides, in front of every fault that
+# only shows in the entropy decoder.
+MIXED_FAULTS = {
+    "null": _lib.EINVAL,                 # pass 0
+    "twelve-bit": _lib.ENOSUP,           # pass 0
+    "lossless": _lib.ENOSUP,             # pass 0: a frame header that jpeg_amd_jpeg_inspect refuses
+    "undefined-tables": _lib.EINVAL,     # the entropy decoder, on a thread of the queue
+    "progressive": 0,                    # decoded into planes, among files that travel sparse
+}
+SMALL = (16, 16)
+
+
+@pytest.fixture(scope="module")
+def small_files():
+    shapes = [("420", (32, 32)), ("y8", (48, 32)), ("444", (16, 16)), ("422", (40, 28))]
+    good = [F.synthetic_file(name, size, 600 + i, restart=i % 3)[0] for i, (name, size) in enumerate(shapes)]
+    faults = {
+        "null": None,
+        "twelve-bit": F.synthetic_file("y8", (16, 16), 4, precision=12)[0],
+        "lossless": F.lossless_marker(good[2]),
+        "undefined-tables": F.undefined_tables(good[1]),
+        "progressive": F.synthetic_file("420", (48, 32), 610, kind="progressive")[0],
+    }
+    return good, faults
+
+
+def _status(ctx, torch, datas, threads):
+    out = Out(ctx, torch, [3 * SMALL[0] * SMALL[1]] * len(datas), elem=2)
+    return file_call(ctx, datas, None, SMALL, _lib.FILTER_BILINEAR, out.ptr, out.stride, spec_of("f16-chw"), threads=threads, whole=True)[0]
+
+
+def _whole(datas):
+    return [(0, 0, F.inspect(d).width, F.inspect(d).height) for d in datas]
+
+
+@pytest.mark.parametrize("fault", sorted(MIXED_FAULTS))
+def test_status_of_one_fault_behind_file_0(ctx, torch, small_files, fault):
+    good, faults = small_files
+    datas = [good[0], good[1], faults[fault], good[2], good[3]]
+    for threads in (1, 3, 0):
+        assert _status(ctx, torch, datas, threads) == MIXED_FAULTS[fault], (fault, threads)
+        if MIXED_FAULTS[fault] == 0:
+            compare(ctx, torch, datas, _whole(datas), SMALL, _lib.FILTER_BILINEAR, "f16-chw", whole=True, threads=threads)
+    compare(ctx, torch, good, _whole(good), SMALL, _lib.FILTER_BILINEAR, "f16-chw", whole=True)      # the context after a refused call
+
+
+@pytest.mark.parametrize("first, second, want", [
+    ("null", "twelve-bit", _lib.EINVAL), ("twelve-bit", "null", _lib.ENOSUP),                  # pass 0: the first file decides
+    ("undefined-tables", "lossless", _lib.ENOSUP), ("lossless", "undefined-tables", _lib.ENOSUP),   # pass 0 in front of the decoder
+    ("undefined-tables", "null", _lib.EINVAL), ("undefined-tables", "undefined-tables", _lib.EINVAL),
+    ("progressive", "twelve-bit", _lib.ENOSUP)])
+def test_status_of_two_faults(ctx, torch, small_files, first, second, want):
+    good, faults = small_files
+    datas = [good[0], faults[first], good[1], faults[second], good[2]]
+    for threads in (1, 3, 0):
+        assert _status(ctx, torch, datas, threads) == want, (first, second, threads)
+
+
+def test_a_fault_in_chunk_2_behind_a_progressive_file_in_chunk_1(ctx, torch, small_files):
+    """70 files = three chunks: pinned slot 0 is used again and its record cursor reset; a progressive file (planes) in chunk 1,
+    a file that fails in the entropy decoder in chunk 2; with 1, 2 and all threads.  Then the clean batch, image by image."""
+    good, faults = small_files
+    datas = [good[i % 4] for i in range(70)]
+    datas[40] = faults["progressive"]
+    bad = list(datas)
+    bad[66] = faults["undefined-tables"]
+    for threads in (1, 2, 0):
+        assert _status(ctx, torch, bad, threads) == _lib.EINVAL, threads
+    compare(ctx, torch, datas, _whole(datas), SMALL, _lib.FILTER_BILINEAR, "f16-chw", whole=True, threads=2)
 
 
 # ---- 6. the empty call; the Python functions ------------------------------------------------------------------------------------------

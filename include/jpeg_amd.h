@@ -525,7 +525,8 @@ int jpeg_amd_jpeg_script(const uint8_t *h_jpeg, size_t nbytes, jpeg_amd_scan *sc
  * the GPU, and the host writer keeping the input's process, component ids, scan script, table keys, restart interval and
  * metadata segments verbatim and in order.  Every component of the frame is transformed.  h_requant: NULL or
  * [ncomponents][64] in output orientation (components that share a key must get equal tables).  h_out == NULL only sizes
- * the output (*nbytes_out); out_info (optional) receives the output frame. */
+ * the output (*nbytes_out); out_info (optional) receives the output frame.  (Verbatim includes an Exif segment's Orientation
+ * tag, which jpeg_amd_jpeg_orientation reads: a file rotated here still NAMES its old orientation; the tag is not reset.) */
 int jpeg_amd_transform(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int op, const jpeg_amd_region *region,
                        const uint16_t *h_requant, int nthreads, uint8_t *h_out, size_t capacity, size_t *nbytes_out,
                        jpeg_amd_frame_info *out_info);
@@ -1101,6 +1102,109 @@ int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_
                                       const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter,
                                       uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
                                       jpeg_amd_view *h_views);
+
+/* ---- oriented resample: the eight EXIF orientations in the resample stage of the tensor and file calls ------------------
+ * A portrait photograph from a phone is STORED landscape, with Orientation = 6 in its EXIF segment; PIL's
+ * ImageOps.exif_transpose, torchvision's decode_jpeg(apply_exif_orientation=True) and nvJPEG/DALI hand the loader the
+ * upright image.  These calls do, in the resample stage: the oriented image is the stored one read with signed pixel and row
+ * steps, so an orientation costs no pass of its own.  They also give callers flips, 90-degree rotations and transposes as a
+ * per-image augmentation, with no EXIF involved.
+ *
+ * THE ORIENTATION.  A value o in 1 .. 8 is three bits (T, fx, fy):
+ *     o          1      2      3      4      5      6      7      8
+ *     T fx fy    0 0 0  0 1 0  0 1 1  0 0 1  1 0 0  1 0 1  1 1 1  1 1 0
+ * For a stored image S of w x h the oriented image D is w' x h' = (T ? h : w) x (T ? w : h), and D[y'][x'] = S[ys][xs] with
+ *     without T:  xs = fx ? w - 1 - x' : x',  ys = fy ? h - 1 - y' : y'
+ *     with T:     xs = fx ? w - 1 - y' : y',  ys = fy ? h - 1 - x' : x'
+ * (numpy: S[::-1] if fy, then [:, ::-1] if fx, then .transpose(1, 0, 2) if T; what PIL.ImageOps.exif_transpose gives.)
+ * A rectangle (x', y', w_r', h_r') of D holds the pixels of the stored rectangle that jpeg_amd_orient_region gives: the
+ * pairs swapped if T, then x = fx ? w - x_a - w_a : x_a, then y = fy ? h - y_a - h_a : y_a.
+ *
+ * THE CONTRACT, by reference only -- no arithmetic is defined here: an oriented resample of image i is the contract of its
+ * filter ("resized decode" for JPEG_AMD_FILTER_BILINEAR, "antialiased resample" for JPEG_AMD_FILTER_ANTIALIAS) applied to
+ * the ORIENTED image, with w', h' in the place of w, h everywhere -- in kx = (float)w' / (float)out_w, in the clamps, and in
+ * the tap limit, which is judged on the oriented factors; the horizontal pass runs along oriented x.  The output is, bit for
+ * bit, what the call without orientations writes for a contiguous copy of the oriented pixels.  "tensor output" applies
+ * behind it unchanged: h_flip mirrors the output along x, AFTER the orientation.
+ *
+ * THE CALLS.  Each takes the arguments of the *_filter_* call (or file call) it is named after, and h_orient, a HOST array of
+ * n_images bytes, in front of the output pointer.  h_orient == NULL is, bit for bit and status for status, that call, and so
+ * is an array of ones (it launches the same kernels from the same records); otherwise ONE launch of the oriented kernels
+ * takes all the call's images, orientation 1 included.
+ *   jpeg_amd_resize_oriented_batch, jpeg_amd_resize_oriented_tensor_batch: pixel sources, oriented whole.
+ *   jpeg_amd_decode_resized_oriented_mixed, jpeg_amd_decode_tensor_oriented_mixed: the views stay in STORED scaled
+ *     coordinates, as in the mixed calls; the orientation applies to each view's pixels.
+ *   In these four a value outside 1 .. 8 is EINVAL, judged with image i's other arguments and behind them: in the resize
+ *   calls behind the target and image i's extent, in the mixed calls behind image i's view and, for image 0, in front of
+ *   the target.  The tap limit stays last.
+ *   jpeg_amd_decompress_resized_oriented_mixed, jpeg_amd_decompress_tensor_oriented_mixed: the file calls.  Here
+ *     h_orient[i] == JPEG_AMD_ORIENT_EXIF (0) means what jpeg_amd_jpeg_orientation says of file i, 1 .. 8 force a value, and
+ *     a value above 8 is EINVAL, judged behind what the file call judges of file i's headers and in front of its rectangle.
+ *     h_source_regions[i] is a rectangle of the ORIENTED full-size image -- the image the user sees -- or the whole of it
+ *     (NULL); one outside the oriented image is EINVAL, where the file call judges its rectangle.  The denominator is
+ *     jpeg_amd_view_denom(oriented rectangle's width, height, out_w, out_h), the view jpeg_amd_view_of_source of the STORED
+ *     rectangle (jpeg_amd_orient_region), and h_views reports that stored view.  h_orient_out (optional, n_images values)
+ *     receives the orientation applied to each file, written as far as the files were judged.  Contract by reference, as in
+ *     "files to tensors": image i is what jpeg_amd_decode_tensor_oriented_mixed (jpeg_amd_decode_resized_oriented_mixed)
+ *     writes for the file decoded whole, with that view and that orientation.
+ * There are no oriented forms of the uniform *_batch decodes (the mixed calls serve them), of the region, scaled and view
+ * byte calls, of the full decode or of the encoders.  Nothing is oriented in the coefficient domain: the lossless transforms
+ * cannot orient an image whose size is no multiple of its MCU.
+ * Cost: the route of the call it is named after.  With a transposing orientation (5 .. 8) neighbouring work-items read
+ * bytes one stored row apart instead of 3 bytes apart: more cache lines per load, the same lines per tile. */
+enum {
+    JPEG_AMD_ORIENT_EXIF = 0,    /* the file calls only: the file's own tag */
+    JPEG_AMD_ORIENT_1 = 1,       /* as stored */
+    JPEG_AMD_ORIENT_2 = 2,       /* mirrored along x */
+    JPEG_AMD_ORIENT_3 = 3,       /* rotated by 180 degrees */
+    JPEG_AMD_ORIENT_4 = 4,       /* mirrored along y */
+    JPEG_AMD_ORIENT_5 = 5,       /* transposed */
+    JPEG_AMD_ORIENT_6 = 6,       /* rotated by 90 degrees clockwise */
+    JPEG_AMD_ORIENT_7 = 7,       /* transposed along the other diagonal */
+    JPEG_AMD_ORIENT_8 = 8        /* rotated by 90 degrees counter-clockwise */
+};
+
+/* JPEG.EXIF.parse and its subscript(tag:) (metadata.swift:440-560), for the Orientation field (tag 0x0112) alone: a marker
+ * walk from SOI to the first SOS; of the first APP1 whose payload begins "Exif\0\0" the TIFF header ("II*\0" or "MM\0*") and
+ * the offset of IFD0; of IFD0's 12-byte entries the first with tag 0x0112, type SHORT (3) or LONG (4) and count 1, whose
+ * value is read in the file's byte order from the start of the value field.  EINVAL for null pointers; OK in every other
+ * case, with *orientation = 1 unless a value in 1 .. 8 was found: no EXIF or no tag, a value outside 1 .. 8, another type or
+ * count, an offset or an entry count that leaves the segment, a segment length that leaves the file, and input that is no
+ * JPEG at all give 1.  Whether the file is decodable is jpeg_amd_jpeg_inspect's verdict: a broken EXIF block never fails a
+ * decode.  No byte at or beyond nbytes is read; only IFD0 is looked at.  Host only.
+ * (jpeg_amd_transform keeps APPn segments verbatim, this tag included: it does not reset it.) */
+int jpeg_amd_jpeg_orientation(const uint8_t *h_jpeg, size_t nbytes, int32_t *orientation);
+/* THE ORIENTATION's rectangle mapping for a stored frame of width x height: `oriented`, a rectangle of the oriented image
+ * (NULL: the whole of it), as the stored rectangle that holds its pixels.  EINVAL for an orientation outside 1 .. 8, a
+ * width or height below 1, a null `stored`, and a rectangle that is empty or not inside the oriented image.  Host only, pure. */
+int jpeg_amd_orient_region(int orientation, int32_t width, int32_t height, const jpeg_amd_region *oriented,
+                           jpeg_amd_region *stored);
+
+int jpeg_amd_resize_oriented_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                   const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                   const uint8_t *h_orient, uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_resize_oriented_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                          const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                          void *d_dst, size_t dst_stride);
+int jpeg_amd_decode_resized_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                           int filter, const uint8_t *h_orient, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                          jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                          int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                          const uint8_t *h_orient, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_tensor_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                              int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                              const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h,
+                                              int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                              const uint8_t *h_orient, void *d_dst, size_t dst_stride,
+                                              jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
+int jpeg_amd_decompress_resized_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                               int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                               const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h,
+                                               int filter, const uint8_t *h_orient, uint8_t *d_pixels, size_t pixel_stride,
+                                               jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
 
 #ifdef __cplusplus
 }

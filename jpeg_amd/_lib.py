@@ -167,6 +167,19 @@ SIGNATURES = {
                                                    _p, _p, _p, C.c_size_t, _p, _p]),
     "jpeg_amd_decompress_resized_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int,
                                                     _p, C.c_size_t, _p, _p]),
+    "jpeg_amd_jpeg_orientation": (C.c_int, [_p, C.c_size_t, _p]),
+    "jpeg_amd_orient_region": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _p, _p]),
+    "jpeg_amd_resize_oriented_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, C.c_size_t]),
+    "jpeg_amd_resize_oriented_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, _p, _p,
+                                                        C.c_size_t]),
+    "jpeg_amd_decode_resized_oriented_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                         C.c_size_t]),
+    "jpeg_amd_decode_tensor_oriented_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                        _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_tensor_oriented_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
+                                                            C.c_int, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_decompress_resized_oriented_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
+                                                             C.c_int, _p, _p, C.c_size_t, _p, _p, _p]),
 }
 
 
@@ -210,6 +223,7 @@ F32, F16, BF16 = 0, 1, 2                # JPEG_AMD_F32 ...
 U8 = 3                                  # JPEG_AMD_U8: tensor sources only
 TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
 FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
+ORIENT_EXIF = 0                         # JPEG_AMD_ORIENT_EXIF (the file calls); JPEG_AMD_ORIENT_1 .. _8 are 1 .. 8
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V
 XFORM_TRANSPOSE, XFORM_FLIP_H, XFORM_FLIP_V = 1, 2, 4

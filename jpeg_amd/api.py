@@ -523,6 +523,37 @@ def inspect(source) -> _lib.FrameInfo:
     return info
 
 
+def exif_orientation(source) -> int:
+    """The EXIF orientation of a JPEG file (a path or its bytes), 1 .. 8 (jpeg_amd_jpeg_orientation): IFD0's tag 0x0112 of the
+    first Exif APP1 segment in front of the first scan; 1 where there is none, or none that is well-formed."""
+    data = _file_bytes(source)
+    o = C.c_int32()
+    _lib.check(_lib.lib().jpeg_amd_jpeg_orientation(data.ctypes.data, data.size, C.byref(o)), "jpeg_amd_jpeg_orientation")
+    return int(o.value)
+
+
+def orient_region(orientation: int, size, region=None) -> Tuple[int, int, int, int]:
+    """A rectangle (x, y, width, height) of the ORIENTED image of a stored image of size (w, h) -- None: the whole of it -- as
+    the stored rectangle that holds its pixels (jpeg_amd_orient_region; include/jpeg_amd.h, "oriented resample")."""
+    r = _lib.Region()
+    _lib.check(_lib.lib().jpeg_amd_orient_region(int(orientation), int(size[0]), int(size[1]), _region(region), C.byref(r)),
+               "jpeg_amd_orient_region")
+    return r.x, r.y, r.width, r.height
+
+
+def _orientations(orientations, n: int, exif: bool = False):
+    """orientations=... of the resample calls -> the c bytes for h_orient, or None (today's entry point).  exif: the file
+    calls, where "exif" (the whole call, or an entry of a sequence) is JPEG_AMD_ORIENT_EXIF."""
+    if orientations is None:
+        return None
+    if isinstance(orientations, str):
+        orientations = [orientations] * n
+    vals = [_lib.ORIENT_EXIF if exif and isinstance(o, str) and o.lower() == "exif" else o for o in orientations]
+    if len(vals) != n or any(isinstance(o, str) or not 0 <= int(o) <= 255 for o in vals):
+        raise ValueError("orientations: one value in 1 .. 8 per image" + (', or "exif"' if exif else ""))
+    return (C.c_uint8 * max(n, 1))(*[int(o) for o in vals])
+
+
 def _decode_spectral(data: np.ndarray, scans: int = 0):
     info = inspect(data)
     planes = [np.empty((info.units_y[c], info.units_x[c], 64), np.int16) for c in range(info.ncomponents)]
@@ -838,17 +869,24 @@ def _pack_images(ctx: Context, images):
     return src, src_stride, extents
 
 
-def resize(ctx: Context, images, out_size, filter: str = "bilinear"):
+def resize(ctx: Context, images, out_size, filter: str = "bilinear", orientations=None):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
     (jpeg_amd_resize_filter_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
-    the target on an axis).  The images are packed into one allocation first (torch copies).  Returns uint8 [n, Ht, Wt, 3]."""
+    the target on an axis).  The images are packed into one allocation first (torch copies).  orientations: per image an EXIF
+    orientation 1 .. 8 in which the image is read (jpeg_amd_resize_oriented_batch; include/jpeg_amd.h, "oriented resample").
+    Returns uint8 [n, Ht, Wt, 3]."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
+    h_orient = _orientations(orientations, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                       out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                           out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
+    else:
+        _lib.check(_lib.lib().jpeg_amd_resize_oriented_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code, h_orient,
+                                                             out.data_ptr(), stride), "jpeg_amd_resize_oriented_batch", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
@@ -960,46 +998,74 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
     return slices
 
 
-def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear"):
+def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear",
+                         orientations=None):
     """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_filter_mixed);
-    arguments as decode_views_mixed, `filter` as in decode_resized.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    arguments as decode_views_mixed, `filter` as in decode_resized.  orientations: per image an EXIF orientation 1 .. 8 in which
+    its view's pixels are read (jpeg_amd_decode_resized_oriented_mixed); the views stay rectangles of the STORED scaled
+    images.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
+    h_orient = _orientations(orientations, n)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                               ht, code, out.data_ptr(), stride),
-               "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                   ht, code, out.data_ptr(), stride),
+                   "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
+    else:
+        _lib.check(_lib.lib().jpeg_amd_decode_resized_oriented_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views,
+                                                                     wt, ht, code, h_orient, out.data_ptr(), stride),
+                   "jpeg_amd_decode_resized_oriented_mixed", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                         cosite: bool = False, filter: str = "bilinear"):
+                         cosite: bool = False, filter: str = "bilinear", orientations=None):
     """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
-    as decode_views_mixed, then as decode_tensors.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    as decode_views_mixed, then as decode_tensors.  orientations: as in decode_resized_mixed
+    (jpeg_amd_decode_tensor_oriented_mixed); a flip mirrors the output after the orientation.
+    Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
+    h_orient = _orientations(orientations, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                              ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
-               "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                  ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
+    else:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_oriented_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views,
+                                                                    wt, ht, code, C.byref(spec), h_flip, h_orient, out.data_ptr(),
+                                                                    stride),
+                   "jpeg_amd_decode_tensor_oriented_mixed", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 
 def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                              cosite: bool = False, filter: str = "bilinear"):
+                              cosite: bool = False, filter: str = "bilinear", orientations=None):
     """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
     full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
-    size -- through decode_tensors_mixed.  Returns (tensor, the views as int32 [n, 5])."""
+    size -- through decode_tensors_mixed.  orientations: per image an EXIF orientation 1 .. 8; the rectangles are then
+    rectangles of the ORIENTED images: the denominator is chosen for the oriented rectangle and the view is that of the stored
+    rectangle orient_region maps it to.  Returns (tensor, the views as int32 [n, 5]: stored scaled coordinates)."""
     spectrals = list(spectrals)
     regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
     if regs.shape[0] != len(spectrals):
         raise ValueError("source_regions: one (x, y, width, height) per image")
+    orientations = None if orientations is None else list(orientations)
+    if orientations is not None and len(orientations) != len(spectrals):
+        raise ValueError("orientations: one value in 1 .. 8 per image")
     views = np.empty((len(spectrals), 5), np.int32)
     for i, s in enumerate(spectrals):
-        views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
-    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter), views
+        if orientations is None:
+            views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
+        else:
+            denom = view_denom(regs[i, 2:], out_size)
+            views[i] = (denom,) + view_of_source(s.size, denom, orient_region(orientations[i], s.size, regs[i].tolist()))
+    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
+                                orientations=orientations), views
 
 
 def _file_args(sources, source_regions):
@@ -1025,7 +1091,7 @@ def _views_array(h_views, n) -> np.ndarray:
 
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
-                       cosite: bool = False, filter: str = "bilinear", threads: int = 0):
+                       cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
@@ -1033,41 +1099,68 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     that is still no smaller than out_size (Wt, Ht), resampled by `filter`, mirrored where flips[i] is set, normalised by
     `spec` (tensor_spec).  The files are entropy-decoded on `threads` host threads (0: all cores) into the sparse form, and
     only the parts of the coefficient planes that the views read are rebuilt on the device.
+    orientation: None (the images as they are stored), "exif" (every file in the orientation its EXIF segment names:
+    exif_orientation) or a sequence of 1 .. 8 or "exif" per file (jpeg_amd_decompress_tensor_oriented_mixed; include/jpeg_amd.h,
+    "oriented resample").  With it, source_regions are rectangles of the ORIENTED images -- the images a viewer shows -- while the
+    views that come back stay in stored scaled coordinates.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5] of (denom, x, y, width, height), the files'
-    frame infos)."""
+    frame infos), and with `orientation` given a fourth item, the orientations applied as int32 [n]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
+    h_orient = _orientations(orientation, n, exif=True)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
-                                                           regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
-                                                           infos, h_views), "jpeg_amd_decompress_tensor_mixed", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n])
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
+                                                               regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
+                                                               infos, h_views), "jpeg_amd_decompress_tensor_mixed", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n])
+    applied = (C.c_int32 * max(n, 1))()
+    _lib.check(_lib.lib().jpeg_amd_decompress_tensor_oriented_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                    color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
+                                                                    out.data_ptr(), stride, infos, h_views, applied),
+               "jpeg_amd_decompress_tensor_oriented_mixed", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]), np.array(applied[:n], np.int32)
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
-                       filter: str = "bilinear", threads: int = 0):
+                       filter: str = "bilinear", threads: int = 0, orientation=None):
     """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
-    (Wt, Ht) as bytes.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    (Wt, Ht) as bytes; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
+    Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
+    h_orient = _orientations(orientation, n, exif=True)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_decompress_resized_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
-                                                            regions, wt, ht, code, out.data_ptr(), stride, infos, h_views),
-               "jpeg_amd_decompress_resized_mixed", ctx.handle)
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_decompress_resized_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
+                                                                regions, wt, ht, code, out.data_ptr(), stride, infos, h_views),
+                   "jpeg_amd_decompress_resized_mixed", ctx.handle)
+    else:
+        _lib.check(_lib.lib().jpeg_amd_decompress_resized_oriented_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                         color.code, regions, wt, ht, code, h_orient, out.data_ptr(),
+                                                                         stride, infos, h_views, None),
+                   "jpeg_amd_decompress_resized_oriented_mixed", ctx.handle)
     return out.view(n, ht, wt, 3)
 
 
-def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear"):
+def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None):
     """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
-    [n, Ht, Wt, 3] of spec's dtype, in one launch."""
+    [n, Ht, Wt, 3] of spec's dtype, in one launch.  orientations: as in resize (jpeg_amd_resize_oriented_tensor_batch); a flip
+    mirrors the output after the orientation."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
+    h_orient = _orientations(orientations, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                              C.byref(spec), h_flip, out.data_ptr(), stride),
-               "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
+    if h_orient is None:
+        _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                                  C.byref(spec), h_flip, out.data_ptr(), stride),
+                   "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
+    else:
+        _lib.check(_lib.lib().jpeg_amd_resize_oriented_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                                    C.byref(spec), h_flip, h_orient, out.data_ptr(), stride),
+                   "jpeg_amd_resize_oriented_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 

@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
-SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resize.hip", "kernels_tensor.hip", "kernels_antialias.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
-HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp"]
+SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resize.hip", "kernels_tensor.hip", "kernels_antialias.hip", "kernels_oriented.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
+HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
 # Per-source flags.  The transform kernels are compiled WITHOUT the SLP vectoriser: it turns the float arithmetic of the 8-point
@@ -30,7 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "kernels_stage.hip": _NO_SLP,
                "kernels_region.hip": _NO_SLP, "kernels_scaled.hip": _NO_SLP, "kernels_view.hip": _NO_SLP, "kernels_resize.hip": _NO_SLP,
-               "kernels_tensor.hip": _NO_SLP, "kernels_antialias.hip": _NO_SLP, "kernels_reduce.hip": _NO_SLP,
+               "kernels_tensor.hip": _NO_SLP, "kernels_antialias.hip": _NO_SLP, "kernels_oriented.hip": _NO_SLP, "kernels_reduce.hip": _NO_SLP,
                "kernels_pixels.hip": _NO_SLP}
 
 
@@ -47,7 +47,8 @@ NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fuse
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform", "kernels_region.hip": "k_region_decode",
                 "kernels_scaled.hip": "k_scaled_decode", "kernels_view.hip": "k_view_decode",
-                "kernels_reduce.hip": "k_spectral_reduce", "kernels_antialias.hip": "k_antialias_"}   # _bytes and _tensor
+                "kernels_reduce.hip": "k_spectral_reduce", "kernels_antialias.hip": "k_antialias_",   # _bytes and _tensor
+                "kernels_oriented.hip": "_oriented_"}       # k_resize_oriented_* and k_antialias_oriented_*
 
 
 def check_no_scratch(src: str, remarks: str, fragment: str, strict: bool = True) -> None:

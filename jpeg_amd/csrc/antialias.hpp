@@ -32,6 +32,8 @@
 #pragma once
 #pragma clang fp contract(off)
 
+#include <type_traits>
+
 #include "fused_common.hpp"
 #include "kernels.hpp"
 #include "resample.hpp"
@@ -65,9 +67,14 @@ __device__ __forceinline__ void antialias_taps(int j, float k, float s, float r,
 __device__ __forceinline__ uint32_t antialias_byte(float v) { return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f); }
 
 // The tile blockIdx.x of image blockIdx.y, with resample_walk's sink.  a.records is not read: the records are `records`.
-template <typename Sink>
-__device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const AntialiasRecord *records, bool flips, Sink sink)
+// Oriented (Record = OrientedAntialiasRecord, "oriented resample"): w and h are the ORIENTED image's, offset its first byte,
+// and the byte of channel c of its pixel (x', y') lies at offset + x' step_x + y' step_y + c, the steps signed: the
+// horizontal pass runs along oriented x, and the vertical pass never sees the difference.
+template <typename Record, typename Sink>
+__device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Record *records, bool flips, Sink sink)
 {
+    constexpr bool Oriented = std::is_same<Record, OrientedAntialiasRecord>::value;
+    using Step = typename std::conditional<Oriented, int64_t, size_t>::type;   // (the additions wrap to the same address)
     __shared__ int tlo[kTileW + kTileH], tcount[kTileW + kTileH];   // columns, then rows
     __shared__ float tw[kTileW + kTileH][kAntialiasMaxTaps];
     __shared__ float hbuf[kChunk * 3 * kTileW];
@@ -76,7 +83,7 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Anti
     uint32_t txi;
     const uint32_t tyi = a.tiles_x.div(blockIdx.x, txi);
     const int px0 = kTileW * (int)txi, py0 = kTileH * (int)tyi;
-    const AntialiasRecord r = records[blockIdx.y];
+    const Record r = records[blockIdx.y];
     const bool flip = flips && r.flip;
     if (t < kTileW) {
         int lo = 0, count = 0;
@@ -93,8 +100,12 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Anti
     const int rows = min(kTileH, a.out_h - py0);   // of the tile, >= 1
     const int ybeg = tlo[kTileW], yend = tlo[kTileW + rows - 1] + tcount[kTileW + rows - 1];
     const int xcount = tcount[col];
-    const size_t row_bytes = (size_t)3 * (uint32_t)r.w;
-    const uint8_t *src = a.src + r.offset + (size_t)3 * (uint32_t)tlo[col];
+    Step pixel_bytes = 3, row_bytes = (Step)3 * (uint32_t)r.w;
+    if constexpr (Oriented) {
+        pixel_bytes = r.step_x;
+        row_bytes = r.step_y;
+    }
+    const uint8_t *src = a.src + r.offset + pixel_bytes * (uint32_t)tlo[col];
     const float *wx = tw[col];
     float acc[kOwnRows][3];
 #pragma unroll
@@ -112,7 +123,7 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Anti
             for (int i = 0; i < kChunkRows; ++i) {
                 const int y = y0 + wave + kWaves * i;
                 if (y < yend) {
-                    const uint8_t *p = src + (size_t)(uint32_t)y * row_bytes + 3 * k;
+                    const uint8_t *p = src + (Step)(uint32_t)y * row_bytes + (Oriented ? pixel_bytes * k : (Step)(3 * k));
 #pragma unroll
                     for (int c = 0; c < 3; ++c) h[i][c] = h[i][c] + w * (float)p[c];
                 }

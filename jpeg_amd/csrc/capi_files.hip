@@ -6,6 +6,7 @@
 #pragma clang fp contract(off)
 
 #include "capi_internal.hpp"
+#include "orient.hpp"
 
 using namespace jpeg_amd;
 using namespace jpeg_amd::capi;
@@ -43,6 +44,7 @@ struct FilesDecode : FileBatch {
     bool tensor;
     const jpeg_amd_tensor_spec *spec;
     const uint8_t *h_flip;
+    std::vector<uint8_t> orient;               // per file, what the call applies; empty: the call names no orientations
     void *d_dst;
     size_t dst_stride, elem_bytes;
     std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
@@ -123,12 +125,13 @@ int FilesDecode::submit(int k)
     std::vector<jpeg_amd_view> views((size_t)ch.m);
     for (int i = 0; i < ch.m; ++i) views[(size_t)i] = files[(size_t)(ch.i0 + i)].view;
     void *d_out = static_cast<char *>(d_dst) + (size_t)ch.i0 * dst_stride * elem_bytes;
+    const uint8_t *h_orient = orient.empty() ? nullptr : orient.data() + ch.i0;   // (nullptr: the calls without orientations)
     if (tensor)
-        JA_TRY(jpeg_amd_decode_tensor_filter_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
-                                                   h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride));
+        JA_TRY(jpeg_amd_decode_tensor_oriented_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
+                                                     h_flip ? h_flip + ch.i0 : nullptr, h_orient, d_out, dst_stride));
     else
-        JA_TRY(jpeg_amd_decode_resized_filter_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
-                                                    static_cast<uint8_t *>(d_out), dst_stride));
+        JA_TRY(jpeg_amd_decode_resized_oriented_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
+                                                      h_orient, static_cast<uint8_t *>(d_out), dst_stride));
     JA_HIP(ctx, hipEventRecord(ctx->file_decoded[slot], ctx->stream));
     JA_HIP(ctx, hipEventRecord(ctx->file_done[slot], ctx->stream));     // the tensor stays where it is: done when the kernels are
     return JPEG_AMD_OK;
@@ -146,8 +149,8 @@ int FilesDecode::run()
 
 int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads, int cosited,
                      jpeg_amd_color color, const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter, bool tensor,
-                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
-                     jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views)
+                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, void *d_dst, size_t dst_stride,
+                     jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
@@ -157,6 +160,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     d.out_w = out_w; d.out_h = out_h; d.filter = filter; d.tensor = tensor; d.spec = spec; d.h_flip = h_flip; d.d_dst = d_dst;
     d.dst_stride = dst_stride;
     d.files.resize((size_t)n_images);
+    if (h_orient) d.orient.assign((size_t)n_images, 1);   // (1 behind a refused file: the mixed call's judgement stops in front of it)
     // ---- pass 0: the headers, file by file; the first file that is refused ends it
     int bad = n_images, bad_status = JPEG_AMD_OK;
     std::vector<jpeg_amd_image> images((size_t)n_images);
@@ -168,10 +172,27 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
         if (st == JPEG_AMD_OK) {
             if (h_info) h_info[i] = f.info;
             f.layout = layout_of_info(f.info, f.info.ncomponents);
-            const jpeg_amd_region source = h_source_regions ? h_source_regions[i] : jpeg_amd_region{0, 0, f.info.width, f.info.height};
-            // the data-loader call's view (decode_crops_tensor_mixed): the cheapest denominator, then the rectangle at it
-            f.view.denom = jpeg_amd_view_denom(source.width, source.height, out_w, out_h);
-            st = jpeg_amd_view_of_source(&f.layout, f.view.denom, &source, &f.view.region);
+            // the orientation the call applies: the file's tag, or the caller's value; the source rectangle is one of the
+            // ORIENTED image then, and `source` the stored rectangle that holds its pixels
+            int32_t o = 1;
+            if (h_orient && h_orient[i] == JPEG_AMD_ORIENT_EXIF) st = jpeg_amd_jpeg_orientation(h_jpeg[i], nbytes[i], &o);
+            else if (h_orient) o = h_orient[i];
+            // `seen`: the rectangle of the oriented image the caller named, or the whole of it, w' x h' -- which is what the
+            // denominator is chosen for; `source`: the stored rectangle that holds its pixels
+            jpeg_amd_region source{0, 0, f.info.width, f.info.height}, seen = source;
+            if (st == JPEG_AMD_OK && !orientation_valid(o)) st = JPEG_AMD_EINVAL;
+            if (st == JPEG_AMD_OK) {
+                const OrientedSource whole = oriented_source(o, 0, f.info.width, f.info.height);
+                seen = h_source_regions ? h_source_regions[i] : jpeg_amd_region{0, 0, whole.w, whole.h};
+                st = jpeg_amd_orient_region(o, f.info.width, f.info.height, &seen, &source);
+            }
+            if (st == JPEG_AMD_OK) {
+                if (h_orient) d.orient[(size_t)i] = (uint8_t)o;
+                if (h_orient_out) h_orient_out[i] = o;
+                // the data-loader call's view (decode_crops_tensor_mixed): the cheapest denominator, then the rectangle at it
+                f.view.denom = jpeg_amd_view_denom(seen.width, seen.height, out_w, out_h);
+                st = jpeg_amd_view_of_source(&f.layout, f.view.denom, &source, &f.view.region);
+            }
         }
         if (st != JPEG_AMD_OK) { bad = i; bad_status = st; break; }
         if (h_views) h_views[i] = f.view;
@@ -186,8 +207,8 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     }
     // ... then what the mixed call refuses of the files in front of that one, the target included; the tap limit last
     int taps = JPEG_AMD_OK;
-    JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor, d_dst,
-                                 dst_stride, &taps));
+    JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
+                                 d.orient.empty() ? nullptr : d.orient.data(), d_dst, dst_stride, &taps));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
@@ -264,7 +285,7 @@ int jpeg_amd_decompress_tensor_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_j
                                      size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, d_dst, dst_stride, h_info, h_views);
+                            h_flip, nullptr, d_dst, dst_stride, h_info, h_views, nullptr);
 }
 JA_NOTHROW_TAIL
 
@@ -274,6 +295,29 @@ int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_
                                       jpeg_amd_view *h_views)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views);
+                            nullptr, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, nullptr);
+}
+JA_NOTHROW_TAIL
+
+// The two file calls with an orientation per file ("oriented resample"): 0 = the file's EXIF tag, 1 .. 8 = that value.
+int jpeg_amd_decompress_tensor_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                              int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
+                                              int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                              const uint8_t *h_flip, const uint8_t *h_orient, void *d_dst, size_t dst_stride,
+                                              jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
+                            h_flip, h_orient, d_dst, dst_stride, h_info, h_views, h_orient_out);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decompress_resized_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                               int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
+                                               int32_t out_w, int32_t out_h, int filter, const uint8_t *h_orient, uint8_t *d_pixels,
+                                               size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                               int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
+                            nullptr, nullptr, h_orient, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
 }
 JA_NOTHROW_TAIL

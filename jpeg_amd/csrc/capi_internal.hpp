@@ -124,10 +124,11 @@ int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
 // What jpeg_amd_decode_resized_filter_mixed (tensor: jpeg_amd_decode_tensor_filter_mixed) refuses before it looks at the
 // context, for the file calls, which judge a call before its planes exist (the images' pointers only have to be non-null):
 // of the first `judged` images of a call of n_images, in the mixed call's order; *taps: with judged == n_images the verdict on
-// the antialiasing filter's tap limit, which that call gives last (capi_view.hip).
+// the antialiasing filter's tap limit, which that call gives last (capi_view.hip).  h_orient: as in the *_oriented_mixed calls
+// (n_images values, or nullptr).
 int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
-                          bool tensor, void *d_dst, size_t dst_stride, int *taps);
+                          bool tensor, const uint8_t *h_orient, void *d_dst, size_t dst_stride, int *taps);
 
 // ---- the batch file paths: the staging, and what the two decode pipelines share (capi_file.hip) ---------------------------------
 // Both decode pipelines (files of one geometry to pixels, capi_file.hip; files of mixed sizes to one tensor, capi_files.hip) are

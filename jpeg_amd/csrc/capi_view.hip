@@ -3,6 +3,7 @@
 #pragma clang fp contract(off)
 
 #include "capi_internal.hpp"
+#include "orient.hpp"
 
 using namespace jpeg_amd;
 using namespace jpeg_amd::capi;
@@ -516,6 +517,9 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
 // tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor).  `tensor` is not `spec != nullptr`: a tensor call
 // without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
 // ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others.
+// h_orient ("oriented resample"): per image an orientation in 1 .. 8, or nullptr.  A call in which it is nullptr or every
+// value is 1 is today's call -- today's records, today's kernels; in any other, check() sets `oriented`, every record is the
+// oriented one (orientation 1 included: base = offset, steps 3 and 3 w) and ONE launch of the oriented kernels takes them all.
 struct ResampleTarget {
     int32_t out_w, out_h;
     int filter;              // JPEG_AMD_FILTER_*
@@ -524,38 +528,56 @@ struct ResampleTarget {
     const uint8_t *h_flip;   // per image, or nullptr: none is mirrored
     void *d_dst;
     size_t stride;           // between images, in elements
+    const uint8_t *h_orient = nullptr;   // per image, or nullptr: every image as it is stored
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
+    bool oriented = false;   // check() sets it
 
     bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS; }
     int check(int n_images)
     {
+        oriented = false;   // (not a verdict: which records the call writes)
+        for (int i = 0; h_orient && i < n_images; ++i) oriented = oriented || h_orient[i] != 1;
         if (filter != JPEG_AMD_FILTER_BILINEAR && filter != JPEG_AMD_FILTER_ANTIALIAS) return JPEG_AMD_EINVAL;
         return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride);
     }
-    // Image i of the call, w x h at `offset` bytes from the launch's source.  The scale factors of the contract: divided here,
-    // in binary32, never on the device.
+    // Image i's orientation: judged with the image's other arguments, behind them, by the callers.  record(i) comes after it.
+    int check_orientation(int i) const { return !h_orient || orientation_valid(h_orient[i]) ? JPEG_AMD_OK : JPEG_AMD_EINVAL; }
+    // Image i of the call, w x h as it is STORED at `offset` bytes from the launch's source.  The scale factors of the
+    // contract: divided here, in binary32, never on the device; of an oriented call they are the ORIENTED extent's.
     // ENOSUP: the antialiasing filter's tap limit, kx or ky above kAntialiasMaxScale.  The record is written either way, and
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
-    size_t record_bytes() const { return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord); }
+    size_t record_bytes() const
+    {
+        if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
+        return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
+    }
     int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
-        const float kx = (float)w / (float)out_w, ky = (float)h / (float)out_h;
+        const OrientedSource s = oriented_source(oriented ? h_orient[i] : 1, offset, w, h);   // (1: the stored image)
+        const float kx = (float)s.w / (float)out_w, ky = (float)s.h / (float)out_h;
         const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
         if (!antialias()) {
-            const ResizeRecord r{offset, w, h, kx, ky, flip, 0u};
-            std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+            const OrientedResizeRecord r{{s.base, s.w, s.h, kx, ky, flip, 0u}, s.step_x, s.step_y};
+            std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());   // (the plain record is its head)
             return JPEG_AMD_OK;
         }
         const float sx = std::max(kx, 1.0f), sy = std::max(ky, 1.0f);
-        const AntialiasRecord r{offset, w, h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u};
-        std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+        const OrientedAntialiasRecord r{{s.base, s.w, s.h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u}, s.step_x, s.step_y};
+        std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());
         return kx > kAntialiasMaxScale || ky > kAntialiasMaxScale ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
     }
     // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards.
     hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
+        if (oriented) {
+            const jpeg_amd_tensor_spec *s = tensor ? spec : nullptr;
+            return antialias() ? launch_antialias_oriented(stream, m, d_src, static_cast<const OrientedAntialiasRecord *>(d_rec) + i0,
+                                                           out_w, out_h, s, d_out, stride)
+                               : launch_resize_oriented(stream, m, d_src, static_cast<const OrientedResizeRecord *>(d_rec) + i0, out_w,
+                                                        out_h, s, d_out, stride);
+        }
         if (antialias()) {
             const AntialiasRecord *rec = static_cast<const AntialiasRecord *>(d_rec) + i0;
             return tensor ? launch_antialias_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
@@ -634,6 +656,7 @@ int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t 
             const jpeg_amd_extent &e = h_extents[i];
             if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
             if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
+            JA_TRY(t.check_orientation(i));
             const int verdict = t.record(rec, i, i, (uint64_t)i * src_stride, e.width, e.height);
             if (taps == JPEG_AMD_OK) taps = verdict;
         }
@@ -851,6 +874,7 @@ int judge_resized_mixed(int n_images, int judged, const jpeg_amd_image *h_images
     if (n_images > 0 && (!h_images || !h_views)) return JPEG_AMD_EINVAL;
     for (int i = 0; i < judged; ++i) {
         JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], t.d_dst, 0));   // the views' stride is ours
+        JA_TRY(t.check_orientation(i));
         if (i == 0) JA_TRY(t.check(n_images));
     }
     if (n_images == 0) JA_TRY(t.check(n_images));
@@ -882,9 +906,10 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
 
 int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
-                                          const jpeg_amd_tensor_spec *spec, bool tensor, void *d_dst, size_t dst_stride, int *taps)
+                                          const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient, void *d_dst,
+                                          size_t dst_stride, int *taps)
 {
-    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride};
+    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient};
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
@@ -929,8 +954,7 @@ int jpeg_amd_resize_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t 
                                  const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter, uint8_t *d_dst,
                                  size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride});
+    return jpeg_amd_resize_oriented_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, nullptr, d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -938,8 +962,8 @@ int jpeg_amd_resize_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const u
                                         const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
                                         const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+    return jpeg_amd_resize_oriented_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, spec, h_flip, nullptr,
+                                                 d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -971,8 +995,8 @@ int jpeg_amd_decode_resized_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const 
                                          jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                          int filter, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+    return jpeg_amd_decode_resized_oriented_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, nullptr, d_pixels,
+                                                  pixel_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -981,7 +1005,58 @@ int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
                                         size_t dst_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+    return jpeg_amd_decode_tensor_oriented_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, spec, h_flip,
+                                                 nullptr, d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL
+
+// The four resample calls above the file level with an orientation per image ("oriented resample"); their forms without one,
+// above, are these with h_orient == nullptr.
+int jpeg_amd_resize_oriented_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                   const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                   const uint8_t *h_orient, uint8_t *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride, h_orient});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_resize_oriented_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                          const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                          const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                          void *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                           int filter, const uint8_t *h_orient, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride, h_orient});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                          jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                          int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                          const uint8_t *h_orient, void *d_dst, size_t dst_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_orient_region(int orientation, int32_t width, int32_t height, const jpeg_amd_region *oriented, jpeg_amd_region *stored)
+{
+    if (!stored || !orientation_valid(orientation) || width < 1 || height < 1) return JPEG_AMD_EINVAL;
+    const OrientedSource s = oriented_source(orientation, 0, width, height);
+    const jpeg_amd_region r = oriented ? *oriented : jpeg_amd_region{0, 0, s.w, s.h};
+    if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.x > s.w - r.width || r.y > s.h - r.height) return JPEG_AMD_EINVAL;
+    const OrientRect m = oriented_rect_to_stored(orientation, width, height, OrientRect{r.x, r.y, r.width, r.height});
+    *stored = jpeg_amd_region{m.x, m.y, m.width, m.height};
+    return JPEG_AMD_OK;
+}

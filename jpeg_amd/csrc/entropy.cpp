@@ -1082,6 +1082,58 @@ int jpeg_amd_jpeg_inspect(const uint8_t *data, size_t nbytes, jpeg_amd_frame_inf
     JA_NOTHROW_END
 }
 
+// The EXIF orientation of a file: JPEG.EXIF.parse and its subscript(tag:) (metadata.swift:440-560) for the one field that
+// changes pixels -- the TIFF header's byte order and IFD0's offset, then IFD0's 12-byte entries, of which the first with tag
+// 0x0112, type SHORT or LONG and count 1 gives the value, read in the file's byte order from the start of the value field.
+// A marker walk from SOI to the first SOS; the first APP1 whose payload begins "Exif\0\0" is the one looked at, IFD0 the only
+// directory.  Everything that is not a well-formed value in 1 .. 8 -- no segment, no tag, another type or count, an offset, an
+// entry count or a segment length that leaves its container, a buffer that is no JPEG -- is orientation 1 and OK: whether the
+// file can be decoded is jpeg_amd_jpeg_inspect's verdict, and a broken EXIF block never fails a decode.  No byte at or behind
+// nbytes is read.
+int jpeg_amd_jpeg_orientation(const uint8_t *data, size_t nbytes, int32_t *orientation)
+{
+    if (!data || !orientation) return JPEG_AMD_EINVAL;
+    *orientation = 1;
+    if (nbytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_AMD_OK;
+    size_t at = 2;
+    while (nbytes - at >= 4) {   // a marker and a length
+        if (data[at] != 0xFF) return JPEG_AMD_OK;
+        const uint8_t marker = data[at + 1];
+        if (marker == 0xFF) { ++at; continue; }                                    // fill bytes in front of a marker
+        if (marker == 0xD8 || marker == 0x01 || (marker >= 0xD0 && marker <= 0xD7)) { at += 2; continue; }   // no length
+        if (marker == 0xDA || marker == 0xD9) return JPEG_AMD_OK;                  // the first scan, or the end
+        const size_t length = ((size_t)data[at + 2] << 8) | data[at + 3];          // counts its own two bytes
+        if (length < 2 || length > nbytes - at - 2) return JPEG_AMD_OK;            // the segment leaves the file
+        const uint8_t *seg = data + at + 4;
+        const size_t n = length - 2;
+        at += 2 + length;
+        if (marker != 0xE1 || n < 6 || std::memcmp(seg, "Exif\0\0", 6) != 0) continue;
+        const uint8_t *tiff = seg + 6;
+        const size_t m = n - 6;
+        if (m < 8) return JPEG_AMD_OK;
+        bool big;
+        if (tiff[0] == 'I' && tiff[1] == 'I' && tiff[2] == 42 && tiff[3] == 0) big = false;
+        else if (tiff[0] == 'M' && tiff[1] == 'M' && tiff[2] == 0 && tiff[3] == 42) big = true;
+        else return JPEG_AMD_OK;
+        const auto u16 = [&](size_t i) -> uint32_t { return big ? ((uint32_t)tiff[i] << 8) | tiff[i + 1] : ((uint32_t)tiff[i + 1] << 8) | tiff[i]; };
+        const auto u32 = [&](size_t i) -> uint32_t { return big ? (u16(i) << 16) | u16(i + 2) : (u16(i + 2) << 16) | u16(i); };
+        const size_t ifd = u32(4);
+        if (ifd > m - 2) return JPEG_AMD_OK;                                        // the offset leaves the segment
+        const size_t count = u16(ifd);
+        if (count > (m - 2 - ifd) / 12) return JPEG_AMD_OK;                         // the entries leave the segment
+        for (size_t e = 0; e < count; ++e) {
+            const size_t entry = ifd + 2 + 12 * e;
+            const uint32_t type = u16(entry + 2);
+            if (u16(entry) != 0x0112 || (type != 3 && type != 4) || u32(entry + 4) != 1) continue;
+            const uint32_t value = type == 3 ? u16(entry + 8) : u32(entry + 8);
+            if (value >= 1 && value <= 8) *orientation = (int32_t)value;
+            return JPEG_AMD_OK;                                                     // the first such entry decides
+        }
+        return JPEG_AMD_OK;
+    }
+    return JPEG_AMD_OK;
+}
+
 // The writer's script of a file (what jpeg_amd_jpeg_encode_spectral takes to write it again): a marker walk that decodes no
 // entropy-coded data.  Table keys: every DQT table DEFINITION is a key, numbered in file order; a component's key is the
 // definition its frame selector points at when its first scan starts (the inverse of JPEG.Layout's slot allocation,

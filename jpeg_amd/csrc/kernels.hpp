@@ -205,6 +205,27 @@ hipError_t launch_antialias_bytes(hipStream_t stream, int n_images, const uint8_
 hipError_t launch_antialias_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
                                    int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
 
+// ---- oriented resample (kernels_oriented.hip) ------------------------------------------------
+// The four launches above for images read in one of the eight EXIF orientations (include/jpeg_amd.h, "oriented resample";
+// orient.hpp states the orientations): the filters' contracts applied to the ORIENTED image, whose pixel (x', y') the walks
+// read through a base and two signed steps.  A record is the filter's record -- offset the byte of the oriented image's first
+// pixel (OrientedSource::base), w and h the ORIENTED extent, the scale factors those of the oriented extent -- and the two
+// steps; oriented_source() makes them on the host.  Every byte read lies inside the stored image.  spec == nullptr: bytes out
+// (k_resize_oriented_bytes, k_antialias_oriented_bytes), d_dst and dst_stride in bytes; else elements out
+// (k_resize_oriented_tensor, k_antialias_oriented_tensor), as launch_resize_tensor.
+struct OrientedResizeRecord : ResizeRecord {
+    int64_t step_x, step_y;   // bytes from a pixel of the oriented image to its right-hand and its lower neighbour
+};
+struct OrientedAntialiasRecord : AntialiasRecord {
+    int64_t step_x, step_y;
+};
+static_assert(sizeof(OrientedResizeRecord) == 48 && sizeof(OrientedAntialiasRecord) == 64, "record layout");
+hipError_t launch_resize_oriented(hipStream_t stream, int n_images, const uint8_t *d_src, const OrientedResizeRecord *d_records,
+                                  int out_w, int out_h, const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
+hipError_t launch_antialias_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
+                                     const OrientedAntialiasRecord *d_records, int out_w, int out_h,
+                                     const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
+
 // ---- tensors to pixel bytes (kernels_pixels.hip) ------------------------------------------------
 // n_images tensors of w x h x 3 elements of source.dtype in source.layout to bytes by the contract of include/jpeg_amd.h
 // ("tensor sources") in ONE launch (k_tensor_pixels).  Image i at d_src + i * src_stride ELEMENTS, d_src aligned to the

@@ -22,6 +22,8 @@
 #pragma once
 #pragma clang fp contract(off)
 
+#include <type_traits>
+
 #include "fused_common.hpp"
 #include "kernels.hpp"
 
@@ -104,9 +106,13 @@ inline hipError_t resample_launch(int n_images, const uint8_t *d_src, const Resi
 
 // The tile blockIdx.x of image blockIdx.y: sink(o, y, x, npix) for every run of the tile, o[k][c] the byte of channel c of the
 // pixel stored at (x + k, y), k < npix <= kRun.  flips: the image's ResizeRecord::flip counts (it is not read otherwise).
-template <typename Sink>
+// Oriented: the records are OrientedResizeRecords ("oriented resample": a.records points at them) -- w and h are the ORIENTED
+// image's, offset its first byte, and the byte of channel c of its pixel (x', y') lies at offset + x' step_x + y' step_y + c,
+// the steps signed; everything else of the walk, the filter included, is the text below, which compiles as it did without.
+template <bool Oriented = false, typename Sink>
 __device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips, Sink sink)
 {
+    using Record = typename std::conditional<Oriented, OrientedResizeRecord, ResizeRecord>::type;
     __shared__ int cx0[kTileW], cx1[kTileW], ry0[kTileH], ry1[kTileH];
     __shared__ float cfx[kTileW], rfy[kTileH];
 
@@ -114,7 +120,7 @@ __device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips,
     uint32_t txi;
     const uint32_t tyi = a.tiles_x.div(blockIdx.x, txi);
     const int px0 = kTileW * (int)txi, py0 = kTileH * (int)tyi;
-    const ResizeRecord r = a.records[blockIdx.y];
+    const Record r = reinterpret_cast<const Record *>(a.records)[blockIdx.y];
     const bool flip = flips && r.flip;
     if (t < kTileW) {
         int i0 = 0, i1 = 0;
@@ -134,21 +140,25 @@ __device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips,
     const int x = px0 + kRun * lx;
     const int npix = min(kRun, a.out_w - x);
     if (npix <= 0) return;
-    size_t x0[kRun], x1[kRun];
+    using Step = typename std::conditional<Oriented, int64_t, size_t>::type;   // (the additions wrap to the same address)
+    Step x0[kRun], x1[kRun], pixel_bytes = 3, row_bytes = (Step)3 * (uint32_t)r.w;
+    if constexpr (Oriented) {
+        pixel_bytes = r.step_x;
+        row_bytes = r.step_y;
+    }
     float fx[kRun];
 #pragma unroll
     for (int k = 0; k < kRun; ++k) {
-        x0[k] = (size_t)3 * (uint32_t)cx0[kRun * lx + k];
-        x1[k] = (size_t)3 * (uint32_t)cx1[kRun * lx + k];
+        x0[k] = pixel_bytes * (uint32_t)cx0[kRun * lx + k];
+        x1[k] = pixel_bytes * (uint32_t)cx1[kRun * lx + k];
         fx[k] = cfx[kRun * lx + k];
     }
-    const size_t row_bytes = (size_t)3 * (uint32_t)r.w;
     const uint8_t *src = a.src + r.offset;
 #pragma unroll
     for (int u = ly; u < kTileH; u += kRowStep) {
         const int y = py0 + u;
         if (y >= a.out_h) break;
-        const uint8_t *r0 = src + (size_t)(uint32_t)ry0[u] * row_bytes, *r1 = src + (size_t)(uint32_t)ry1[u] * row_bytes;
+        const uint8_t *r0 = src + (Step)(uint32_t)ry0[u] * row_bytes, *r1 = src + (Step)(uint32_t)ry1[u] * row_bytes;
         const float fy = rfy[u];
         uint32_t o[kRun][3];
 #pragma unroll

@@ -865,7 +865,7 @@ int jpeg_amd_decode_tensor_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd
  *
  * THE CALLS.  Each takes exactly the arguments of the call it is named after, with `filter` directly after out_h.
  * JPEG_AMD_FILTER_BILINEAR is, bit for bit and status for status, that call.  Any other value of `filter` than the two below
- * is EINVAL.  There are no single-image forms: n_images == 1 serves.
+ * and JPEG_AMD_FILTER_BICUBIC ("bicubic resample") is EINVAL.  There are no single-image forms: n_images == 1 serves.
  * Cost: the route of the call it is named after, with the antialiasing kernel in the place of the bilinear one.  That
  * kernel reads every source pixel of an output tile's footprint once per tile (the bilinear one reads four per output
  * pixel), so its time grows with kx ky. */
@@ -896,6 +896,48 @@ int jpeg_amd_decode_tensor_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                         int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
                                         size_t dst_stride);
+
+/* ---- bicubic resample: a third filter for the same calls ---------------------------------------------------
+ * The filter most published ImageNet recipes resize with.  This is the Keys cubic with a = -0.5, WIDENED BY THE SCALE
+ * FACTOR, clipped at the image edge and renormalised: the filter of torch.nn.functional.interpolate(mode="bicubic",
+ * antialias=True) and of torchvision's Resize(BICUBIC, antialias=True) on tensors.  (torch's bicubic WITHOUT antialias uses
+ * a = -0.75 and four fixed taps: a different filter, which this library does not offer.  PIL's BICUBIC is this kernel too,
+ * but PIL rounds to bytes between its passes, so its bytes differ -- by up to 22 levels on random content.)  THE CONTRACT
+ * (the one statement of it), every statement ONE binary32 operation, nothing contracted:
+ *
+ * Per axis, for n source samples, n_out outputs and output index j:
+ *   k  = (float)n / (float)n_out          on the host, per image
+ *   s  = max(k, 1.0f)                     on the host
+ *   r  = 1.0f / s                         on the host: the kernel is handed k, s and r, as in "antialiased resample"
+ *   p  = 2.0f * s                         (exact) the half-width of the support
+ *   c  = ((float)j + 0.5f) * k
+ *   lo = max((int)((c - p) + 0.5f), 0)
+ *   hi = min((int)((c + p) + 0.5f), n)    taps t = lo .. hi - 1, at least one
+ *   u_t = (((float)t - c) + 0.5f) * r
+ *   x   = fabsf(u_t)
+ *   x < 1:  w_t = ((1.5f * x - 2.5f) * x) * x + 1.0f                     five operations, in this order
+ *   x < 2:  w_t = ((((x - 5.0f) * x + 8.0f) * x) - 4.0f) * -0.5f          six operations, in this order
+ *   else:   w_t = 0.0f
+ *   total = w_lo + w_(lo+1) + ...         left to right, ascending t; positive (0.5 is the least a clipped edge leaves)
+ *   W_t = w_t / total                     IEEE-754 correctly rounded binary32 division
+ * The two passes and the conversion to a byte are those of "antialiased resample", word for word: the horizontal pass first,
+ * its result kept as a float; then the vertical pass; a product and then a sum per tap, ascending; then
+ *   out = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
+ * The weights are negative in the lobes (1 < x < 2), so v leaves 0 ... 255 at hard edges and the clamp is live here.
+ * out_w == w and out_h == h give the source bytes (u is an integer: the weights are exactly 1 and 0).  The tensor output, the
+ * flip and the orientation are unchanged: they act on this byte.
+ *
+ * THE LIMIT.  The support is 4 s wide, so an output reads at most 4 s + 1 taps; s <= 8 per axis keeps them at 33 or fewer.
+ * An image whose kx or ky, as computed above in binary32, exceeds 8.0f makes the whole call JPEG_AMD_ENOSUP, placed and
+ * ordered exactly as the limit of "antialiased resample" is: after everything the bilinear form of the same call refuses and
+ * before the context is touched, by the first offending image in index order; nothing is written and the context stays
+ * usable.  k == 8.0f exactly is accepted (32 taps).  Behind a denominator of 8 that is a reduction of 64 per axis.
+ *
+ * THE CALLS.  Every call that takes `filter` -- the six *_filter_* calls above, the *_oriented_* calls and the file calls
+ * below -- takes this value; there is no new entry point.  The value 2 stays EINVAL.
+ * Cost: the antialiasing kernel's route and walk with tables twice as wide: about twice its taps per output at k >= 1
+ * (four per axis instead of two at k <= 1). */
+enum { JPEG_AMD_FILTER_BICUBIC = 3 };
 
 /* ---- tensor sources: float and uint8 tensors (CHW / HWC) into the encoders --------------------------------
  * The mirror of "tensor output": what a framework holds -- a model's float CHW output in 0 ... 1 or in normalised units,
@@ -1073,7 +1115,7 @@ int jpeg_amd_spectral_expand_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_a
  * in index order: a null file pointer (EINVAL), what jpeg_amd_jpeg_inspect says of the file, a frame that is not 8-bit with 1
  * or 3 components (ENOSUP: one such file refuses the whole call), a source rectangle outside the image (EINVAL); then, of
  * the files in front of the first offending one, whatever the mixed call refuses, the target included; last the antialias
- * filter's 16x limit (ENOSUP).  After a refused call nothing has been written and the context is usable.  n_images == 0 is OK.
+ * filter's 16x limit or the bicubic filter's 8x limit (ENOSUP).  After a refused call nothing has been written and the context is usable.  n_images == 0 is OK.
  * A file whose entropy-coded data proves damaged AFTER the call has started ends the call with that file's status: every
  * copy and kernel in flight is waited for and the context stays usable, but output images of chunks already submitted MAY
  * HAVE BEEN WRITTEN.  There are no per-file statuses, and a bad file is not skipped.
@@ -1121,7 +1163,8 @@ int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_
  * pairs swapped if T, then x = fx ? w - x_a - w_a : x_a, then y = fy ? h - y_a - h_a : y_a.
  *
  * THE CONTRACT, by reference only -- no arithmetic is defined here: an oriented resample of image i is the contract of its
- * filter ("resized decode" for JPEG_AMD_FILTER_BILINEAR, "antialiased resample" for JPEG_AMD_FILTER_ANTIALIAS) applied to
+ * filter ("resized decode" for JPEG_AMD_FILTER_BILINEAR, "antialiased resample" for JPEG_AMD_FILTER_ANTIALIAS, "bicubic
+ * resample" for JPEG_AMD_FILTER_BICUBIC) applied to
  * the ORIENTED image, with w', h' in the place of w, h everywhere -- in kx = (float)w' / (float)out_w, in the clamps, and in
  * the tap limit, which is judged on the oriented factors; the horizontal pass runs along oriented x.  The output is, bit for
  * bit, what the call without orientations writes for a contiguous copy of the oriented pixels.  "tensor output" applies

@@ -142,7 +142,7 @@ struct layout {
 };
 
 enum class color { ycbcr = JPEG_AMD_COLOR_YCC8, rgb = JPEG_AMD_COLOR_RGB8 };
-enum class filter { bilinear = JPEG_AMD_FILTER_BILINEAR, antialias = JPEG_AMD_FILTER_ANTIALIAS };  // of the resample
+enum class filter { bilinear = JPEG_AMD_FILTER_BILINEAR, antialias = JPEG_AMD_FILTER_ANTIALIAS, bicubic = JPEG_AMD_FILTER_BICUBIC };  // of the resample
 using quanta_map = std::map<int, std::vector<uint16_t>>;  // quanta key -> 64 zigzag values
 
 class planar;
@@ -340,7 +340,8 @@ class spectral {
         return px.host();
     }
     /// ... resampled by `f`: filter::antialias is the triangle filter widened by the scale factor (jpeg_amd.h, "antialiased
-    /// resample"), which refuses a view more than 16 times the target on an axis (JPEG_AMD_ENOSUP); filter::bilinear is the
+    /// resample"), which refuses a view more than 16 times the target on an axis (JPEG_AMD_ENOSUP); filter::bicubic is the
+    /// Keys cubic, a = -0.5, widened likewise ("bicubic resample"), which refuses more than 8 times; filter::bilinear is the
     /// call above.  The C ABI has no single-image form with a filter: the tables are uploaded and the batch call runs on one image
     std::vector<uint8_t> decode_resized(color target, const jpeg_amd_view &view, int32_t out_w, int32_t out_h, filter f, bool cosite = false) const
     {

@@ -223,6 +223,7 @@ F32, F16, BF16 = 0, 1, 2                # JPEG_AMD_F32 ...
 U8 = 3                                  # JPEG_AMD_U8: tensor sources only
 TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
 FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
+FILTER_BICUBIC = 3                        # JPEG_AMD_FILTER_BICUBIC (2 is no filter)
 ORIENT_EXIF = 0                         # JPEG_AMD_ORIENT_EXIF (the file calls); JPEG_AMD_ORIENT_1 .. _8 are 1 .. 8
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V

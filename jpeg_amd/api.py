@@ -272,7 +272,7 @@ class Spectral:
         turns a rectangle of the full-size image into such a region, view_denom picks the scale for a target size.
         size (Wt, Ht): that view bilinearly resampled to Wt x Ht, as uint8 [Ht, Wt, 3] (jpeg_amd_decode_resized);
         filter="antialias": resampled with the antialiasing filter instead (jpeg_amd_decode_resized_filter_batch on one
-        image, the tables uploaded first)."""
+        image, the tables uploaded first); filter="bicubic": with the bicubic filter of decode_resized."""
         torch = _torch()
         L = self._layout()
         qarr, qptr = _quanta_array(self.quanta)
@@ -780,11 +780,11 @@ def view_denom(source_size, want_size) -> int:
 
 
 def _filter(filter) -> int:
-    """filter="bilinear" | "antialias" of the resample calls -> the JPEG_AMD_FILTER_* code for the *_filter_* entry points
-    (with the bilinear code they are the entry points without a filter argument)."""
-    codes = {"bilinear": _lib.FILTER_BILINEAR, "antialias": _lib.FILTER_ANTIALIAS}
+    """filter="bilinear" | "antialias" | "bicubic" of the resample calls -> the JPEG_AMD_FILTER_* code for the *_filter_*
+    entry points (with the bilinear code they are the entry points without a filter argument)."""
+    codes = {"bilinear": _lib.FILTER_BILINEAR, "antialias": _lib.FILTER_ANTIALIAS, "bicubic": _lib.FILTER_BICUBIC}
     if filter not in codes:
-        raise ValueError("filter: 'bilinear' or 'antialias'")
+        raise ValueError("filter: 'bilinear', 'antialias' or 'bicubic'")
     return codes[filter]
 
 
@@ -821,7 +821,9 @@ def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     """decode_views with every image bilinearly resampled to out_size (Wt, Ht), in one call
     (jpeg_amd_decode_resized_filter_batch; include/jpeg_amd.h, "resized decode", holds the filter's contract).  Arguments as
     decode_views.  filter="antialias": the antialiasing filter instead ("antialiased resample" there), which refuses a view
-    more than 16 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    more than 16 times the target on an axis.  filter="bicubic": the Keys cubic (a = -0.5) widened by the scale factor
+    ("bicubic resample" there; what torch's interpolate(mode="bicubic", antialias=True) computes, within one level), which
+    refuses a view more than 8 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
     n = vs.shape[0]
@@ -846,8 +848,8 @@ def decode_crops_resized(ctx: Context, size, layout: Layout, planes, quanta, sou
                          q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """The data-loader call: per image a rectangle (x, y, width, height) of the FULL-SIZE image, decoded at the cheapest
     denominator that is still no smaller than out_size -- view_denom((width, height), out_size), then view_of_source -- and
-    resampled to out_size (Wt, Ht) by decode_resized, with its `filter` (the denominator is chosen the same way for both
-    filters).  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
+    resampled to out_size (Wt, Ht) by decode_resized, with its `filter` (the denominator is chosen the same way for every
+    filter).  Returns (uint8 tensor [n, Ht, Wt, 3], the views it chose as int32
     [n, 5] of (denom, x, y, width, height))."""
     views = _crop_views(size, source_regions, out_size)
     return decode_resized(ctx, size, layout, planes, quanta, views, out_size, q=q, color=color, cosite=cosite, filter=filter), views
@@ -872,7 +874,8 @@ def _pack_images(ctx: Context, images):
 def resize(ctx: Context, images, out_size, filter: str = "bilinear", orientations=None):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
     (jpeg_amd_resize_filter_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
-    the target on an axis).  The images are packed into one allocation first (torch copies).  orientations: per image an EXIF
+    the target on an axis), or with filter="bicubic" through the bicubic one (no image more than 8 times; decode_resized says
+    which filter that is).  The images are packed into one allocation first (torch copies).  orientations: per image an EXIF
     orientation 1 .. 8 in which the image is read (jpeg_amd_resize_oriented_batch; include/jpeg_amd.h, "oriented resample").
     Returns uint8 [n, Ht, Wt, 3]."""
     code = _filter(filter)
@@ -954,7 +957,7 @@ def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, ou
 def decode_crops_tensor(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size, spec: _lib.TensorSpec,
                         flips=None, q: Optional[Sequence[int]] = None, color=RGB, cosite: bool = False, filter: str = "bilinear"):
     """The data-loader call, to the tensor a training loop takes: the views decode_crops_resized chooses for the rectangles
-    (x, y, width, height) of the FULL-SIZE images, through decode_tensors.  Returns (tensor, the views as int32 [n, 5])."""
+    (x, y, width, height) of the FULL-SIZE images, through decode_tensors with its `filter`.  Returns (tensor, the views as int32 [n, 5])."""
     views = _crop_views(size, source_regions, out_size)
     return decode_tensors(ctx, size, layout, planes, quanta, views, out_size, spec, flips=flips, q=q, color=color, cosite=cosite,
                           filter=filter), views
@@ -1023,7 +1026,7 @@ def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, co
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                          cosite: bool = False, filter: str = "bilinear", orientations=None):
     """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
-    as decode_views_mixed, then as decode_tensors.  orientations: as in decode_resized_mixed
+    as decode_views_mixed, then as decode_tensors, `filter` ("bilinear" | "antialias" | "bicubic") included.  orientations: as in decode_resized_mixed
     (jpeg_amd_decode_tensor_oriented_mixed); a flip mirrors the output after the orientation.
     Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
@@ -1047,7 +1050,7 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
                               cosite: bool = False, filter: str = "bilinear", orientations=None):
     """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
     full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
-    size -- through decode_tensors_mixed.  orientations: per image an EXIF orientation 1 .. 8; the rectangles are then
+    size -- through decode_tensors_mixed, with its `filter`.  orientations: per image an EXIF orientation 1 .. 8; the rectangles are then
     rectangles of the ORIENTED images: the denominator is chosen for the oriented rectangle and the view is that of the stored
     rectangle orient_region maps it to.  Returns (tensor, the views as int32 [n, 5]: stored scaled coordinates)."""
     spectrals = list(spectrals)
@@ -1096,7 +1099,8 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
     (x, y, width, height) of its full-size image (source_regions; None: the whole images), decoded at the cheapest denominator
-    that is still no smaller than out_size (Wt, Ht), resampled by `filter`, mirrored where flips[i] is set, normalised by
+    that is still no smaller than out_size (Wt, Ht), resampled by `filter` ("bilinear" | "antialias" | "bicubic", as in
+    decode_resized), mirrored where flips[i] is set, normalised by
     `spec` (tensor_spec).  The files are entropy-decoded on `threads` host threads (0: all cores) into the sparse form, and
     only the parts of the coefficient planes that the views read are rebuilt on the device.
     orientation: None (the images as they are stored), "exif" (every file in the orientation its EXIF segment names:
@@ -1125,7 +1129,7 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
                        filter: str = "bilinear", threads: int = 0, orientation=None):
     """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
-    (Wt, Ht) as bytes; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
+    (Wt, Ht) as bytes by `filter`; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
     Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)

@@ -34,7 +34,7 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
                "kernels_pixels.hip": _NO_SLP}
 
 
-# kernels that must not touch scratch memory: source -> mangled-name fragment.  The strip walks count their own VM operations
+# kernels that must not touch scratch memory: source -> mangled-name fragment, or a tuple of fragments.  The strip walks count their own VM operations
 # (a compiler-placed spill would break the count): for them a spill is a build ERROR.  For the encode and generic kernels a spill is
 # a performance bug -- a reload waits with vmcnt(0) for every store in flight -- that has crept in before (round 4: the byte-tail
 # encode variants): it is reported, and an error only under JPEG_AMD_STRICT_SPILL=1 (a register-allocation change in a ROCm update
@@ -47,8 +47,9 @@ NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fuse
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform", "kernels_region.hip": "k_region_decode",
                 "kernels_scaled.hip": "k_scaled_decode", "kernels_view.hip": "k_view_decode",
-                "kernels_reduce.hip": "k_spectral_reduce", "kernels_antialias.hip": "k_antialias_",   # _bytes and _tensor
-                "kernels_oriented.hip": "_oriented_"}       # k_resize_oriented_* and k_antialias_oriented_*
+                "kernels_reduce.hip": "k_spectral_reduce",
+                "kernels_antialias.hip": ("k_antialias_", "k_bicubic_"),   # _bytes and _tensor of either filter
+                "kernels_oriented.hip": "_oriented_"}       # k_resize_oriented_*, k_antialias_oriented_* and k_bicubic_oriented_*
 
 
 def check_no_scratch(src: str, remarks: str, fragment: str, strict: bool = True) -> None:
@@ -130,10 +131,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 sys.stderr.write("\n".join(remarks) + "\n")
             if proc.returncode != 0:
                 raise subprocess.CalledProcessError(proc.returncode, cmd)
-            if src in NO_SCRATCH:
-                check_no_scratch(src, proc.stderr, NO_SCRATCH[src])
-            else:
-                check_no_scratch(src, proc.stderr, WARN_SCRATCH[src], strict=os.environ.get("JPEG_AMD_STRICT_SPILL") == "1")
+            fragments = NO_SCRATCH[src] if src in NO_SCRATCH else WARN_SCRATCH[src]
+            strict = src in NO_SCRATCH or os.environ.get("JPEG_AMD_STRICT_SPILL") == "1"
+            for fragment in (fragments,) if isinstance(fragments, str) else fragments:
+                check_no_scratch(src, proc.stderr, fragment, strict=strict)
         else:
             subprocess.check_call(cmd)
         objs.append(obj)

@@ -3,6 +3,11 @@
 // footprint per output pixel is up to 33 x 33 source pixels.  The tile, the grid and the head of the arguments are
 // resample.hpp's: (tiles of 64 x 32 output pixels) x (images), no prefix and no search.
 //
+// The same walk applies the filter of "bicubic resample" (k_bicubic_*): the Keys cubic widened by the scale factor, whose
+// support is twice as wide, so the host's limit for it is half as large (kBicubicMaxScale) and the tables, the footprint
+// and the LDS are what they are for the triangle at twice the scale factor.  The filter is a type (TriangleFilter,
+// BicubicFilter): the tap loop of the contracts, antialias_taps, exists once.
+//
 // antialias_walk: the workgroup of a tile
 //   1. TABLES.  Writes the tile's per-column and per-row (lo, count, W[count]) into LDS, one work-item per column or row: the
 //      weights, their ascending sum and the one division per weight happen here and nowhere else.  The column table is written
@@ -22,7 +27,8 @@
 //   3. STORES.  The accumulators become bytes (clamp, + 0.5, truncate), go through LDS (the chunk buffer, free by then) and
 //      leave as resample_walk's runs: sink(o, y, x, npix) for 4 pixels of one row per work-item, 16 work-items across.
 // Reads stay inside the image: lo >= 0 and lo + count <= n on both axes.  The count is clamped to kAntialiasMaxTaps, the
-// tables' width, whatever the record says; the host refuses k > kAntialiasMaxScale, below which the clamp never binds.
+// tables' width, whatever the record says; the host refuses k > kAntialiasMaxScale (the cubic: kBicubicMaxScale), below which
+// the clamp never binds.
 //
 // LDS: tables (64 + 32) x (33 + 2) x 4 = 13 440 bytes, chunk buffer 32 x 3 x 64 x 4 = 24 576 bytes; 38 016 in all, four
 // workgroups per CU.
@@ -47,17 +53,36 @@ constexpr int kOwnRows = kTileH / kWaves;         // output rows per work-item i
 static_assert(kThreads == kWaves * kTileW && kChunk % kWaves == 0 && kTileH % kWaves == 0, "roles");
 static_assert(kChunk * 3 * kTileW * sizeof(float) >= (size_t)3 * kTileW * kTileH, "the byte tile lies in the chunk buffer");
 
+// The weight functions that fill the tables: the half-width of the support for s = max(k, 1), and the weight at u, the
+// distance from the centre in units of s.  The walk below is written once and takes either.
+struct TriangleFilter {   // "antialiased resample"
+    static __device__ __forceinline__ float support(float s) { return s; }
+    static __device__ __forceinline__ float weight(float u) { return fmaxf(1.0f - fabsf(u), 0.0f); }
+};
+struct BicubicFilter {    // "bicubic resample": the Keys cubic with a = -0.5; five operations inside 1, six inside 2
+    static __device__ __forceinline__ float support(float s) { return 2.0f * s; }
+    static __device__ __forceinline__ float weight(float u)
+    {
+        const float x = fabsf(u);
+        if (x < 1.0f) return ((1.5f * x - 2.5f) * x) * x + 1.0f;
+        if (x < 2.0f) return ((((x - 5.0f) * x + 8.0f) * x) - 4.0f) * -0.5f;
+        return 0.0f;
+    }
+};
+
 // One axis of the contract: output index j of an axis of n source samples.  W: the row of the table.
+template <typename Filter>
 __device__ __forceinline__ void antialias_taps(int j, float k, float s, float r, int n, int &lo, int &count, float *W)
 {
     const float c = ((float)j + 0.5f) * k;
-    lo = max((int)((c - s) + 0.5f), 0);
-    const int hi = min((int)((c + s) + 0.5f), n);
+    const float p = Filter::support(s);
+    lo = max((int)((c - p) + 0.5f), 0);
+    const int hi = min((int)((c + p) + 0.5f), n);
     count = min(max(hi - lo, 0), kAntialiasMaxTaps);
     float total = 0.0f;
     for (int i = 0; i < count; ++i) {
         const float u = (((float)(lo + i) - c) + 0.5f) * r;
-        const float w = fmaxf(1.0f - fabsf(u), 0.0f);
+        const float w = Filter::weight(u);
         W[i] = w;
         total = i == 0 ? w : total + w;
     }
@@ -70,7 +95,7 @@ __device__ __forceinline__ uint32_t antialias_byte(float v) { return (uint32_t)(
 // Oriented (Record = OrientedAntialiasRecord, "oriented resample"): w and h are the ORIENTED image's, offset its first byte,
 // and the byte of channel c of its pixel (x', y') lies at offset + x' step_x + y' step_y + c, the steps signed: the
 // horizontal pass runs along oriented x, and the vertical pass never sees the difference.
-template <typename Record, typename Sink>
+template <typename Filter, typename Record, typename Sink>
 __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Record *records, bool flips, Sink sink)
 {
     constexpr bool Oriented = std::is_same<Record, OrientedAntialiasRecord>::value;
@@ -87,11 +112,11 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Reco
     const bool flip = flips && r.flip;
     if (t < kTileW) {
         int lo = 0, count = 0;
-        if (px0 + t < a.out_w) antialias_taps(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
+        if (px0 + t < a.out_w) antialias_taps<Filter>(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
         tlo[t] = lo; tcount[t] = count;
     } else if (t < kTileW + kTileH) {
         int lo = 0, count = 0;
-        if (py0 + (t - kTileW) < a.out_h) antialias_taps(py0 + (t - kTileW), r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
+        if (py0 + (t - kTileW) < a.out_h) antialias_taps<Filter>(py0 + (t - kTileW), r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
         tlo[t] = lo; tcount[t] = count;
     }
     __syncthreads();

@@ -513,10 +513,10 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
     return JPEG_AMD_OK;
 }
 
-// Where the resampled images of a call go, and through which filter: bytes (k_resize_bilinear, k_antialias_bytes) or, in a
-// tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor).  `tensor` is not `spec != nullptr`: a tensor call
-// without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
-// ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others.
+// Where the resampled images of a call go, and through which filter: bytes (k_resize_bilinear, k_antialias_bytes,
+// k_bicubic_bytes) or, in a tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor, k_bicubic_tensor).
+// `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
+// ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others (the bicubic filter fills the same one).
 // h_orient ("oriented resample"): per image an orientation in 1 .. 8, or nullptr.  A call in which it is nullptr or every
 // value is 1 is today's call -- today's records, today's kernels; in any other, check() sets `oriented`, every record is the
 // oriented one (orientation 1 included: base = offset, steps 3 and 3 w) and ONE launch of the oriented kernels takes them all.
@@ -532,12 +532,14 @@ struct ResampleTarget {
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
     bool oriented = false;   // check() sets it
 
-    bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS; }
+    bool bicubic() const { return filter == JPEG_AMD_FILTER_BICUBIC; }
+    bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS || bicubic(); }   // the kernels with tables: their records
+    float max_scale() const { return bicubic() ? kBicubicMaxScale : kAntialiasMaxScale; }
     int check(int n_images)
     {
         oriented = false;   // (not a verdict: which records the call writes)
         for (int i = 0; h_orient && i < n_images; ++i) oriented = oriented || h_orient[i] != 1;
-        if (filter != JPEG_AMD_FILTER_BILINEAR && filter != JPEG_AMD_FILTER_ANTIALIAS) return JPEG_AMD_EINVAL;
+        if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
         return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride);
     }
@@ -545,7 +547,8 @@ struct ResampleTarget {
     int check_orientation(int i) const { return !h_orient || orientation_valid(h_orient[i]) ? JPEG_AMD_OK : JPEG_AMD_EINVAL; }
     // Image i of the call, w x h as it is STORED at `offset` bytes from the launch's source.  The scale factors of the
     // contract: divided here, in binary32, never on the device; of an oriented call they are the ORIENTED extent's.
-    // ENOSUP: the antialiasing filter's tap limit, kx or ky above kAntialiasMaxScale.  The record is written either way, and
+    // ENOSUP: the tap limit of the filter the target carries, kx or ky above kAntialiasMaxScale (the bicubic filter, whose
+    // record is the antialiasing one's: kBicubicMaxScale).  The record is written either way, and
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
     size_t record_bytes() const
     {
@@ -565,7 +568,7 @@ struct ResampleTarget {
         const float sx = std::max(kx, 1.0f), sy = std::max(ky, 1.0f);
         const OrientedAntialiasRecord r{{s.base, s.w, s.h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u}, s.step_x, s.step_y};
         std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());
-        return kx > kAntialiasMaxScale || ky > kAntialiasMaxScale ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
+        return kx > max_scale() || ky > max_scale() ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
     }
     // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards.
     hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
@@ -573,13 +576,18 @@ struct ResampleTarget {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
         if (oriented) {
             const jpeg_amd_tensor_spec *s = tensor ? spec : nullptr;
-            return antialias() ? launch_antialias_oriented(stream, m, d_src, static_cast<const OrientedAntialiasRecord *>(d_rec) + i0,
-                                                           out_w, out_h, s, d_out, stride)
-                               : launch_resize_oriented(stream, m, d_src, static_cast<const OrientedResizeRecord *>(d_rec) + i0, out_w,
-                                                        out_h, s, d_out, stride);
+            if (!antialias())
+                return launch_resize_oriented(stream, m, d_src, static_cast<const OrientedResizeRecord *>(d_rec) + i0, out_w, out_h, s,
+                                              d_out, stride);
+            const OrientedAntialiasRecord *rec = static_cast<const OrientedAntialiasRecord *>(d_rec) + i0;
+            return bicubic() ? launch_bicubic_oriented(stream, m, d_src, rec, out_w, out_h, s, d_out, stride)
+                             : launch_antialias_oriented(stream, m, d_src, rec, out_w, out_h, s, d_out, stride);
         }
         if (antialias()) {
             const AntialiasRecord *rec = static_cast<const AntialiasRecord *>(d_rec) + i0;
+            if (bicubic())
+                return tensor ? launch_bicubic_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
+                              : launch_bicubic_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
             return tensor ? launch_antialias_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
                           : launch_antialias_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
         }

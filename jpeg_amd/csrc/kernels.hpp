@@ -200,10 +200,17 @@ struct AntialiasRecord {
 };
 constexpr float kAntialiasMaxScale = 16.0f;
 constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
+constexpr float kBicubicMaxScale = 8.0f;         // "bicubic resample": [c - 2 s, c + 2 s], 4 s + 1 taps in the same tables
 hipError_t launch_antialias_bytes(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
                                   int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
 hipError_t launch_antialias_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
                                    int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
+// ... and with the filter of "bicubic resample" (k_bicubic_bytes, k_bicubic_tensor): the Keys cubic, a = -0.5, widened by the
+// scale factor.  The same records and arguments; every kx and ky is at most kBicubicMaxScale.
+hipError_t launch_bicubic_bytes(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
+                                int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
+hipError_t launch_bicubic_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
+                                 int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
 
 // ---- oriented resample (kernels_oriented.hip) ------------------------------------------------
 // The four launches above for images read in one of the eight EXIF orientations (include/jpeg_amd.h, "oriented resample";
@@ -225,6 +232,9 @@ hipError_t launch_resize_oriented(hipStream_t stream, int n_images, const uint8_
 hipError_t launch_antialias_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
                                      const OrientedAntialiasRecord *d_records, int out_w, int out_h,
                                      const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
+hipError_t launch_bicubic_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,   // k_bicubic_oriented_*
+                                   const OrientedAntialiasRecord *d_records, int out_w, int out_h,
+                                   const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
 
 // ---- tensors to pixel bytes (kernels_pixels.hip) ------------------------------------------------
 // n_images tensors of w x h x 3 elements of source.dtype in source.layout to bytes by the contract of include/jpeg_amd.h

@@ -1,5 +1,5 @@
-// kernels_oriented.hip -- the bilinear and the antialiased resample of pixel images read in one of the eight EXIF orientations
-// (the *_oriented_* calls of include/jpeg_amd.h; "oriented resample" there holds the contract, orient.hpp the orientations):
+// kernels_oriented.hip -- the bilinear, the antialiased and the bicubic resample of pixel images read in one of the eight EXIF
+// orientations (the *_oriented_* calls of include/jpeg_amd.h; "oriented resample" there holds the contract, orient.hpp the orientations):
 // the contract of the filter applied to the oriented image, which is the stored one read through a base and two signed steps
 // (OrientedResizeRecord, OrientedAntialiasRecord: made on the host).  No arithmetic of its own: the walks are resample.hpp's
 // and antialias.hpp's with Oriented set, the sinks those of the four kernels beside which these stand.
@@ -8,6 +8,7 @@
 // k_resize_oriented_tensor<T, CHW>: resample_walk<true>, flipped where the record says so (after the orientation: the flip
 //   mirrors the OUTPUT columns), with tensor_sink.
 // k_antialias_oriented_bytes, k_antialias_oriented_tensor<T, CHW>: antialias_walk over OrientedAntialiasRecords, likewise.
+// k_bicubic_oriented_bytes, k_bicubic_oriented_tensor<T, CHW>: the same two with the bicubic weights (BicubicFilter).
 //
 // Reads: an oriented pixel (x', y') with 0 <= x' < w', 0 <= y' < h' is a stored pixel, so the walks' own clamps keep every
 // read inside the stored image.  With a transposing orientation (5 .. 8) neighbouring lanes read bytes a stored row apart
@@ -57,8 +58,15 @@ __global__ __launch_bounds__(kThreads) void k_resize_oriented_bytes(OrientedByte
 __global__ __launch_bounds__(kThreads) void k_antialias_oriented_bytes(OrientedBytesArgs a)
 {
     uint8_t *dst = a.dst + (size_t)blockIdx.y * a.dst_stride;
-    antialias_walk(a, a.aa_records, false,
-                   [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+    antialias_walk<TriangleFilter>(a, a.aa_records, false,
+                                   [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+}
+
+__global__ __launch_bounds__(kThreads) void k_bicubic_oriented_bytes(OrientedBytesArgs a)
+{
+    uint8_t *dst = a.dst + (size_t)blockIdx.y * a.dst_stride;
+    antialias_walk<BicubicFilter>(a, a.aa_records, false,
+                                  [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
 }
 
 template <typename T, bool CHW>
@@ -76,13 +84,23 @@ __global__ __launch_bounds__(kThreads) void k_antialias_oriented_tensor(Oriented
 {
     T *dst = a.dst + (size_t)blockIdx.y * a.dst_stride;
     const size_t plane = (size_t)(uint32_t)a.out_w * (uint32_t)a.out_h;
-    antialias_walk(a, a.aa_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+    antialias_walk<TriangleFilter>(a, a.aa_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
         tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
     });
 }
 
 template <typename T, bool CHW>
-hipError_t launch(hipStream_t stream, const ResampleArgs &head, dim3 grid, const OrientedAntialiasRecord *aa_records,
+__global__ __launch_bounds__(kThreads) void k_bicubic_oriented_tensor(OrientedTensorArgs<T> a)
+{
+    T *dst = a.dst + (size_t)blockIdx.y * a.dst_stride;
+    const size_t plane = (size_t)(uint32_t)a.out_w * (uint32_t)a.out_h;
+    antialias_walk<BicubicFilter>(a, a.aa_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+    });
+}
+
+template <typename T, bool CHW>
+hipError_t launch(hipStream_t stream, const ResampleArgs &head, dim3 grid, const OrientedAntialiasRecord *aa_records, bool bicubic,
                   const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride)
 {
     OrientedTensorArgs<T> a{};
@@ -94,16 +112,18 @@ hipError_t launch(hipStream_t stream, const ResampleArgs &head, dim3 grid, const
     a.dst = static_cast<T *>(d_dst);
     a.dst_stride = dst_stride;
     a.aa_records = aa_records;
-    if (aa_records)
+    if (aa_records && bicubic)
+        hipLaunchKernelGGL((k_bicubic_oriented_tensor<T, CHW>), grid, dim3(kThreads), 0, stream, a);
+    else if (aa_records)
         hipLaunchKernelGGL((k_antialias_oriented_tensor<T, CHW>), grid, dim3(kThreads), 0, stream, a);
     else
         hipLaunchKernelGGL((k_resize_oriented_tensor<T, CHW>), grid, dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 
-// Either filter: aa_records of the antialiasing one, or nullptr and the bilinear records in `head`.
+// Any filter: aa_records of the antialiasing one or (bicubic) the bicubic one, or nullptr and the bilinear records in `head`.
 hipError_t launch_oriented(hipStream_t stream, const ResampleArgs &head, dim3 grid, const OrientedAntialiasRecord *aa_records,
-                           const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride)
+                           bool bicubic, const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride)
 {
     if (!spec) {
         OrientedBytesArgs a{};
@@ -111,7 +131,9 @@ hipError_t launch_oriented(hipStream_t stream, const ResampleArgs &head, dim3 gr
         a.aa_records = aa_records;
         a.dst = static_cast<uint8_t *>(d_dst);
         a.dst_stride = dst_stride;
-        if (aa_records)
+        if (aa_records && bicubic)
+            hipLaunchKernelGGL(k_bicubic_oriented_bytes, grid, dim3(kThreads), 0, stream, a);
+        else if (aa_records)
             hipLaunchKernelGGL(k_antialias_oriented_bytes, grid, dim3(kThreads), 0, stream, a);
         else
             hipLaunchKernelGGL(k_resize_oriented_bytes, grid, dim3(kThreads), 0, stream, a);
@@ -121,14 +143,14 @@ hipError_t launch_oriented(hipStream_t stream, const ResampleArgs &head, dim3 gr
     if (!chw && spec->layout != JPEG_AMD_TENSOR_HWC) return hipErrorInvalidValue;
     switch (spec->dtype) {
     case JPEG_AMD_F32:
-        return chw ? launch<float, true>(stream, head, grid, aa_records, *spec, d_dst, dst_stride)
-                   : launch<float, false>(stream, head, grid, aa_records, *spec, d_dst, dst_stride);
+        return chw ? launch<float, true>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride)
+                   : launch<float, false>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride);
     case JPEG_AMD_F16:
-        return chw ? launch<_Float16, true>(stream, head, grid, aa_records, *spec, d_dst, dst_stride)
-                   : launch<_Float16, false>(stream, head, grid, aa_records, *spec, d_dst, dst_stride);
+        return chw ? launch<_Float16, true>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride)
+                   : launch<_Float16, false>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride);
     case JPEG_AMD_BF16:
-        return chw ? launch<bf16_t, true>(stream, head, grid, aa_records, *spec, d_dst, dst_stride)
-                   : launch<bf16_t, false>(stream, head, grid, aa_records, *spec, d_dst, dst_stride);
+        return chw ? launch<bf16_t, true>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride)
+                   : launch<bf16_t, false>(stream, head, grid, aa_records, bicubic, *spec, d_dst, dst_stride);
     default:
         return hipErrorInvalidValue;
     }
@@ -144,19 +166,37 @@ hipError_t launch_resize_oriented(hipStream_t stream, int n_images, const uint8_
     ResampleArgs head{};
     dim3 grid;
     if (const hipError_t e = resample_launch(n_images, d_src, d_records, out_w, out_h, head, grid)) return e;
-    return launch_oriented(stream, head, grid, nullptr, spec, d_dst, dst_stride);
+    return launch_oriented(stream, head, grid, nullptr, false, spec, d_dst, dst_stride);
 }
 
-hipError_t launch_antialias_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
-                                     const OrientedAntialiasRecord *d_records, int out_w, int out_h,
-                                     const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride)
+namespace {
+
+hipError_t launch_tables_oriented(hipStream_t stream, bool bicubic, int n_images, const uint8_t *d_src,
+                                  const OrientedAntialiasRecord *d_records, int out_w, int out_h, const jpeg_amd_tensor_spec *spec,
+                                  void *d_dst, size_t dst_stride)
 {
     if (n_images == 0) return hipSuccess;
     if (!d_records) return hipErrorInvalidValue;
     ResampleArgs head{};
     dim3 grid;
     if (const hipError_t e = resample_launch(n_images, d_src, nullptr, out_w, out_h, head, grid)) return e;
-    return launch_oriented(stream, head, grid, d_records, spec, d_dst, dst_stride);
+    return launch_oriented(stream, head, grid, d_records, bicubic, spec, d_dst, dst_stride);
+}
+
+}  // namespace
+
+hipError_t launch_antialias_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
+                                     const OrientedAntialiasRecord *d_records, int out_w, int out_h,
+                                     const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride)
+{
+    return launch_tables_oriented(stream, false, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride);
+}
+
+hipError_t launch_bicubic_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
+                                   const OrientedAntialiasRecord *d_records, int out_w, int out_h,
+                                   const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride)
+{
+    return launch_tables_oriented(stream, true, n_images, d_src, d_records, out_w, out_h, spec, d_dst, dst_stride);
 }
 
 }  // namespace jpeg_amd

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
-SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resize.hip", "kernels_tensor.hip", "kernels_antialias.hip", "kernels_oriented.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
+SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
 HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
@@ -29,9 +29,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # (k_quad420 / k_luma_fused pin their arithmetic with empty asm statements and hold no packed operations either way.)
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "kernels_stage.hip": _NO_SLP,
-               "kernels_region.hip": _NO_SLP, "kernels_scaled.hip": _NO_SLP, "kernels_view.hip": _NO_SLP, "kernels_resize.hip": _NO_SLP,
-               "kernels_tensor.hip": _NO_SLP, "kernels_antialias.hip": _NO_SLP, "kernels_oriented.hip": _NO_SLP, "kernels_reduce.hip": _NO_SLP,
-               "kernels_pixels.hip": _NO_SLP}
+               "kernels_region.hip": _NO_SLP, "kernels_scaled.hip": _NO_SLP, "kernels_view.hip": _NO_SLP, "kernels_resample.hip": _NO_SLP,
+               "kernels_reduce.hip": _NO_SLP, "kernels_pixels.hip": _NO_SLP}
 
 
 # kernels that must not touch scratch memory: source -> mangled-name fragment, or a tuple of fragments.  The strip walks count their own VM operations
@@ -39,17 +38,18 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
 # a performance bug -- a reload waits with vmcnt(0) for every store in flight -- that has crept in before (round 4: the byte-tail
 # encode variants): it is reported, and an error only under JPEG_AMD_STRICT_SPILL=1 (a register-allocation change in a ROCm update
 # must not leave a user without a library).  k_resize_bilinear counts nothing, but it is small (54 VGPRs) and every lane streams
-# bytes: a spill there is a mistake in the source, so it is held to the strict rule; k_resize_tensor, the same walk with
-# another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise; k_expand_mixed, an entry walk and one store,
-# likewise.
-NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused", "kernels_resize.hip": "k_resize_bilinear",
-              "kernels_tensor.hip": "k_resize_tensor", "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
+# bytes: a spill there is a mistake in the source, so it is held to the strict rule; k_resize_tensor<false, ...> (the stored
+# images'), the same walk with another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise; k_expand_mixed, an
+# entry walk and one store, likewise.  A source may stand in both tables, with other fragments.
+NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused",
+              "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E"),
+              "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform", "kernels_region.hip": "k_region_decode",
                 "kernels_scaled.hip": "k_scaled_decode", "kernels_view.hip": "k_view_decode",
                 "kernels_reduce.hip": "k_spectral_reduce",
-                "kernels_antialias.hip": ("k_antialias_", "k_bicubic_"),   # _bytes and _tensor of either filter
-                "kernels_oriented.hip": "_oriented_"}       # k_resize_oriented_*, k_antialias_oriented_* and k_bicubic_oriented_*
+                # the oriented bilinear kernels, and _bytes and _tensor of the filters with tables
+                "kernels_resample.hip": ("k_resize_oriented_bytes", "k_resize_tensorILb1E", "k_tables_")}
 
 
 def check_no_scratch(src: str, remarks: str, fragment: str, strict: bool = True) -> None:
@@ -131,10 +131,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 sys.stderr.write("\n".join(remarks) + "\n")
             if proc.returncode != 0:
                 raise subprocess.CalledProcessError(proc.returncode, cmd)
-            fragments = NO_SCRATCH[src] if src in NO_SCRATCH else WARN_SCRATCH[src]
-            strict = src in NO_SCRATCH or os.environ.get("JPEG_AMD_STRICT_SPILL") == "1"
-            for fragment in (fragments,) if isinstance(fragments, str) else fragments:
-                check_no_scratch(src, proc.stderr, fragment, strict=strict)
+            for table, strict in ((NO_SCRATCH, True), (WARN_SCRATCH, os.environ.get("JPEG_AMD_STRICT_SPILL") == "1")):
+                fragments = table.get(src, ())
+                for fragment in (fragments,) if isinstance(fragments, str) else fragments:
+                    check_no_scratch(src, proc.stderr, fragment, strict=strict)
         else:
             subprocess.check_call(cmd)
         objs.append(obj)

@@ -1,9 +1,9 @@
 // antialias.hpp -- the antialiasing filter of include/jpeg_amd.h ("antialiased resample") and the walk that applies it, for
-// k_antialias_bytes and k_antialias_tensor (kernels_antialias.hip): the triangle filter widened by the scale factor, whose
+// k_tables_bytes and k_tables_tensor (kernels_resample.hip): the triangle filter widened by the scale factor, whose
 // footprint per output pixel is up to 33 x 33 source pixels.  The tile, the grid and the head of the arguments are
 // resample.hpp's: (tiles of 64 x 32 output pixels) x (images), no prefix and no search.
 //
-// The same walk applies the filter of "bicubic resample" (k_bicubic_*): the Keys cubic widened by the scale factor, whose
+// The same walk applies the filter of "bicubic resample" (the same kernels): the Keys cubic widened by the scale factor, whose
 // support is twice as wide, so the host's limit for it is half as large (kBicubicMaxScale) and the tables, the footprint
 // and the LDS are what they are for the triangle at twice the scale factor.  The filter is a type (TriangleFilter,
 // BicubicFilter): the tap loop of the contracts, antialias_taps, exists once.

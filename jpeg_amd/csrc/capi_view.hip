@@ -513,9 +513,8 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
     return JPEG_AMD_OK;
 }
 
-// Where the resampled images of a call go, and through which filter: bytes (k_resize_bilinear, k_antialias_bytes,
-// k_bicubic_bytes) or, in a tensor call, elements of `spec` (k_resize_tensor, k_antialias_tensor, k_bicubic_tensor).
-// `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
+// Where the resampled images of a call go, and through which filter: bytes or, in a tensor call, elements of `spec`
+// (launch_resample).  `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
 // ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others (the bicubic filter fills the same one).
 // h_orient ("oriented resample"): per image an orientation in 1 .. 8, or nullptr.  A call in which it is nullptr or every
 // value is 1 is today's call -- today's records, today's kernels; in any other, check() sets `oriented`, every record is the
@@ -574,26 +573,8 @@ struct ResampleTarget {
     hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
-        if (oriented) {
-            const jpeg_amd_tensor_spec *s = tensor ? spec : nullptr;
-            if (!antialias())
-                return launch_resize_oriented(stream, m, d_src, static_cast<const OrientedResizeRecord *>(d_rec) + i0, out_w, out_h, s,
-                                              d_out, stride);
-            const OrientedAntialiasRecord *rec = static_cast<const OrientedAntialiasRecord *>(d_rec) + i0;
-            return bicubic() ? launch_bicubic_oriented(stream, m, d_src, rec, out_w, out_h, s, d_out, stride)
-                             : launch_antialias_oriented(stream, m, d_src, rec, out_w, out_h, s, d_out, stride);
-        }
-        if (antialias()) {
-            const AntialiasRecord *rec = static_cast<const AntialiasRecord *>(d_rec) + i0;
-            if (bicubic())
-                return tensor ? launch_bicubic_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
-                              : launch_bicubic_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
-            return tensor ? launch_antialias_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
-                          : launch_antialias_bytes(stream, m, d_src, rec, out_w, out_h, d_out, stride);
-        }
-        const ResizeRecord *rec = static_cast<const ResizeRecord *>(d_rec) + i0;
-        return tensor ? launch_resize_tensor(stream, m, d_src, rec, out_w, out_h, *spec, d_out, stride)
-                      : launch_resize_bilinear(stream, m, d_src, rec, out_w, out_h, d_out, stride);
+        const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
+        return launch_resample(stream, ResampleLaunch{filter, oriented, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride});
     }
 };
 

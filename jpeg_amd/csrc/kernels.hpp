@@ -160,66 +160,33 @@ void       mixed_record(void *dst, const jpeg_amd_layout &layout, int n, const i
 hipError_t launch_view_decode_mixed(hipStream_t stream, int n_images, int n, int nplanes, bool rgb, const void *d_records,
                                     const uint32_t *d_index, const uint32_t *d_tiles, uint32_t nwg);
 
-// ---- bilinear resample (kernels_resize.hip) ------------------------------------------------
-// n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h by the contract of include/jpeg_amd.h
-// ("resized decode") in ONE launch (k_resize_bilinear).  d_records: one ResizeRecord per image -- the image's first byte at
-// d_src + offset, its extent, and the scale factors, divided on the host.  Output image i at d_dst + i * dst_stride.
-struct ResizeRecord {
+// ---- resample (kernels_resample.hip) ------------------------------------------------
+// n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h in ONE launch, by the contracts of
+// include/jpeg_amd.h: through one of three filters ("resized decode", "antialiased resample", "bicubic resample"), read as
+// stored or oriented ("oriented resample"), to bytes or to tensor elements ("tensor output").  One record per image, made on
+// the host; which of the four kinds follows from the filter and from whether the call is oriented.
+struct ResizeRecord {      // bilinear
     uint64_t offset;   // bytes from d_src
     int32_t  w, h;     // > 0
     float    kx, ky;   // (float)w / (float)out_w, (float)h / (float)out_h
-    uint32_t flip;     // k_resize_tensor only: nonzero = the resampled image is stored mirrored along x
+    uint32_t flip;     // elements out only: nonzero = the resampled image is stored mirrored along x
     uint32_t reserved;
 };
-constexpr int kResizeMaxSide = 1 << 30;          // of the output: the kernel's pixel indices are int
-uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the launch's grid.x, which holds 2^31 - 1 at most
-hipError_t launch_resize_bilinear(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
-                                  int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
-
-// ---- resample to a normalised tensor (kernels_tensor.hip) ------------------------------------------------
-// The resample above with the output stage of include/jpeg_amd.h ("tensor output") in the same launch (k_resize_tensor): the
-// byte of (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted to spec.dtype and stored in
-// spec.layout.  d_dst and dst_stride in ELEMENTS of spec.dtype; d_dst aligned to the element.  spec is valid
-// (jpeg_amd_tensor_extent), the other arguments as launch_resize_bilinear.
-hipError_t launch_resize_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const ResizeRecord *d_records,
-                                int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
-
-// ---- antialiased resample (kernels_antialias.hip) ------------------------------------------------
-// The two launches above with the filter of include/jpeg_amd.h ("antialiased resample"): the triangle filter widened by the
-// scale factor, bytes out (k_antialias_bytes) or elements out (k_antialias_tensor).  d_records: one AntialiasRecord per image;
-// per axis the scale factor k, s = max(k, 1) and r = 1 / s, all made on the host.  Every kx and ky is at most
-// kAntialiasMaxScale: the kernels' tables hold kAntialiasMaxTaps weights per column and row (they clamp the count to it).
-// Every other argument as launch_resize_bilinear and launch_resize_tensor.
+// The filters with tables: antialias, the triangle widened by the scale factor, and bicubic, the Keys cubic (a = -0.5) likewise.
+// Per axis the scale factor k, s = max(k, 1) and r = 1 / s.  Every kx and ky is at most kAntialiasMaxScale (bicubic:
+// kBicubicMaxScale): the kernels' tables hold kAntialiasMaxTaps weights per column and row (they clamp the count to it).
 struct AntialiasRecord {
     uint64_t offset;       // bytes from d_src
     int32_t  w, h;         // > 0
     float    kx, sx, rx;   // (float)w / (float)out_w, max(kx, 1.0f), 1.0f / sx
     float    ky, sy, ry;   // the same of h and out_h
-    uint32_t flip;         // k_antialias_tensor only: nonzero = the resampled image is stored mirrored along x
+    uint32_t flip;         // as ResizeRecord's
     uint32_t reserved;
 };
-constexpr float kAntialiasMaxScale = 16.0f;
-constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
-constexpr float kBicubicMaxScale = 8.0f;         // "bicubic resample": [c - 2 s, c + 2 s], 4 s + 1 taps in the same tables
-hipError_t launch_antialias_bytes(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
-                                  int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
-hipError_t launch_antialias_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
-                                   int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
-// ... and with the filter of "bicubic resample" (k_bicubic_bytes, k_bicubic_tensor): the Keys cubic, a = -0.5, widened by the
-// scale factor.  The same records and arguments; every kx and ky is at most kBicubicMaxScale.
-hipError_t launch_bicubic_bytes(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
-                                int out_w, int out_h, uint8_t *d_dst, size_t dst_stride);
-hipError_t launch_bicubic_tensor(hipStream_t stream, int n_images, const uint8_t *d_src, const AntialiasRecord *d_records,
-                                 int out_w, int out_h, const jpeg_amd_tensor_spec &spec, void *d_dst, size_t dst_stride);
-
-// ---- oriented resample (kernels_oriented.hip) ------------------------------------------------
-// The four launches above for images read in one of the eight EXIF orientations (include/jpeg_amd.h, "oriented resample";
-// orient.hpp states the orientations): the filters' contracts applied to the ORIENTED image, whose pixel (x', y') the walks
-// read through a base and two signed steps.  A record is the filter's record -- offset the byte of the oriented image's first
-// pixel (OrientedSource::base), w and h the ORIENTED extent, the scale factors those of the oriented extent -- and the two
-// steps; oriented_source() makes them on the host.  Every byte read lies inside the stored image.  spec == nullptr: bytes out
-// (k_resize_oriented_bytes, k_antialias_oriented_bytes), d_dst and dst_stride in bytes; else elements out
-// (k_resize_oriented_tensor, k_antialias_oriented_tensor), as launch_resize_tensor.
+// Oriented (orient.hpp states the eight orientations): the filter's record of the ORIENTED image -- offset the byte of its
+// first pixel (OrientedSource::base), w, h and the scale factors those of the oriented extent -- and the two signed steps
+// through which the walks read its pixel (x', y'); oriented_source() makes them on the host.  Every byte read lies inside the
+// stored image.
 struct OrientedResizeRecord : ResizeRecord {
     int64_t step_x, step_y;   // bytes from a pixel of the oriented image to its right-hand and its lower neighbour
 };
@@ -227,14 +194,28 @@ struct OrientedAntialiasRecord : AntialiasRecord {
     int64_t step_x, step_y;
 };
 static_assert(sizeof(OrientedResizeRecord) == 48 && sizeof(OrientedAntialiasRecord) == 64, "record layout");
-hipError_t launch_resize_oriented(hipStream_t stream, int n_images, const uint8_t *d_src, const OrientedResizeRecord *d_records,
-                                  int out_w, int out_h, const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
-hipError_t launch_antialias_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,
-                                     const OrientedAntialiasRecord *d_records, int out_w, int out_h,
-                                     const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
-hipError_t launch_bicubic_oriented(hipStream_t stream, int n_images, const uint8_t *d_src,   // k_bicubic_oriented_*
-                                   const OrientedAntialiasRecord *d_records, int out_w, int out_h,
-                                   const jpeg_amd_tensor_spec *spec, void *d_dst, size_t dst_stride);
+constexpr int   kResizeMaxSide = 1 << 30;        // of the output: the kernels' pixel indices are int
+constexpr float kAntialiasMaxScale = 16.0f;
+constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
+constexpr float kBicubicMaxScale = 8.0f;         // "bicubic resample": [c - 2 s, c + 2 s], 4 s + 1 taps in the same tables
+uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the launch's grid.x, which holds 2^31 - 1 at most
+
+// Output image i at d_dst + i * dst_stride: bytes, or ELEMENTS of spec->dtype (d_dst aligned to the element), the byte of
+// (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted and stored in spec->layout.  A spec is
+// valid (jpeg_amd_tensor_extent).  hipErrorInvalidValue: an extent or a tile count past the limits above, null records, or a
+// filter, dtype or layout that no kernel exists for.
+struct ResampleLaunch {
+    int filter;                        // JPEG_AMD_FILTER_*
+    bool oriented;                     // the records are the Oriented* ones
+    const jpeg_amd_tensor_spec *spec;  // nullptr: bytes out
+    int n_images;
+    const uint8_t *d_src;
+    const void *d_records;             // record 0 of the launch; the type follows filter and oriented
+    int out_w, out_h;
+    void *d_dst;
+    size_t dst_stride;
+};
+hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l);
 
 // ---- tensors to pixel bytes (kernels_pixels.hip) ------------------------------------------------
 // n_images tensors of w x h x 3 elements of source.dtype in source.layout to bytes by the contract of include/jpeg_amd.h

@@ -1,10 +1,9 @@
-// resample.hpp -- the bilinear filter of include/jpeg_amd.h ("resized decode") and the walk that applies it, for
-// k_resize_bilinear (kernels_resize.hip, bytes out) and k_resize_tensor (kernels_tensor.hip, normalised elements out): the
-// filter, the tile, the head of the kernels' arguments with the host code that fills it, and resample_walk, which computes
-// every run of output bytes of a workgroup's tile and hands it to a sink.  k_resize_tensor is resample_walk with its sink;
-// k_resize_bilinear keeps a text of its own of the same walk (kernels_resize.hip says why), so a change here is made there too.
-// store_run, the byte store of a run, is here for k_resize_bilinear and k_antialias_bytes (kernels_antialias.hip); the tile and
-// the head are antialias.hpp's as well.
+// resample.hpp -- the bilinear filter of include/jpeg_amd.h ("resized decode") and the walk that applies it, for the bilinear
+// kernels of kernels_resample.hip: the filter, the tile, the head of the kernels' arguments with the host code that fills it,
+// and resample_walk, which computes every run of output bytes of a workgroup's tile and hands it to a sink.
+// k_resize_oriented_bytes and k_resize_tensor are resample_walk with a sink; k_resize_bilinear keeps a text of its own of the
+// same walk (kernels_resample.hip says why), so a change here is made there too.  store_run, the byte store of a run, is here
+// for every byte kernel; the tile and the head are antialias.hpp's as well.
 //
 // resample_walk: a static grid of (tiles of the output) x (images); the output size is the same for every image, so there is
 // no prefix and no search.  A tile is 64 x 32 output pixels.  Its workgroup

@@ -1,11 +1,18 @@
 // tensor_sink.hpp -- the output stage of include/jpeg_amd.h ("tensor output") for the kernels that end in it: k_resize_tensor
-// (kernels_tensor.hip, behind resample_walk) and k_antialias_tensor (kernels_antialias.hip, behind antialias_walk).  Both
-// walks hand over a run of kRun pixels of one output row as bytes; tensor_sink turns them into elements,
+// (behind resample_walk) and k_tables_tensor (behind antialias_walk), both in kernels_resample.hip.  Both walks hand over a run
+// of kRun pixels of one output row as bytes; tensor_sink turns them into elements,
 //     t = (float)u - mean[c];  v = t * scale[c]          two binary32 operations, nothing contracted, no division
 // which stay in registers and leave through store_elems: HWC one run of 12 consecutive elements, CHW three runs of 4.
-// kernels_tensor.hip describes the stores and the conversions; the text below was moved from there unchanged.  tensor_sink
-// itself is the text of k_resize_tensor's sink, which that kernel keeps in its body (kernels_tensor.hip says why): a change
-// to one is made to the other.
+// Element stores up to the first address that is a multiple of 4 elements, 4-element vector stores from there (16 bytes at
+// binary32, 8 bytes at the 16-bit types; two of them merged into one 16-byte store where the address allows), element stores
+// behind the last whole vector.  Any element-aligned base and any stride are correct; where out_w is a multiple of 4 and d_dst
+// and dst_stride are multiples of 4 elements -- 224 x 224 into a dense tensor -- every run leaves in vector stores only.
+// Conversions: binary16 is the compiler's float -> _Float16 conversion of the finished binary32 product (round to nearest even
+// in the default mode; see to_element).  bfloat16 is INTEGER ARITHMETIC ON THE BITS, bits + 0x7fff + ((bits >> 16) & 1), the
+// upper half kept -- not the packed hardware convert: it is the contract's own formula, it needs no inline assembly, and every
+// value here is finite.
+// tensor_sink itself is also the text of the sink that k_resize_tensor keeps in its body for the stored records
+// (kernels_resample.hip says why): a change to one is made to the other.
 //
 // Compile with -ffp-contract=off (see dct.hpp).
 #pragma once

@@ -1,4 +1,4 @@
-"""The antialiased resample on the MI355X (the six *_filter_* calls; k_antialias_bytes, k_antialias_tensor): every output is
+"""The antialiased resample on the MI355X (the six *_filter_* calls; k_tables_bytes, k_tables_tensor): every output is
 compared byte for byte, or element for element as a bit pattern, with _antialias_ref -- the contract of include/jpeg_amd.h
 ("antialiased resample") restated in numpy -- applied to the source bytes or to what the existing view decode returns for the
 same views; tensors go through _tensor_ref's output stage.  With JPEG_AMD_FILTER_BILINEAR the six calls must be the calls they
@@ -17,6 +17,7 @@ from _calls import (FUSED, RESIZE_EXTENTS, RESIZE_SIZE, RESIZE_TILE_H as TILE_H,
                     Out, c_layout, c_views, pixel_image, plane_ptrs, resize_py_layout, strides, synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
 from _mixed import c_images
+from _resample import c_bytes as _c_flips, c_spec as _c_spec, host_bits, pack as _pack, same as _same
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -52,16 +53,6 @@ def _resampled(content, out_w, out_h):
     return out
 
 
-def _pack(ctx, torch, images, src_gap):
-    n = len(images)
-    src_stride = max(im.size for im in images) + src_gap
-    src = np.full(n * src_stride, 0x5A, np.uint8)
-    for i, im in enumerate(images):
-        src[i * src_stride:i * src_stride + im.size] = im.reshape(-1)
-    ext = (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
-    return torch.from_numpy(src).to(ctx.torch_device), src_stride, ext
-
-
 def _filter_call(ctx, torch, images, out_w, out_h, filter=AA, gap=0, src_gap=3, expect=0):
     """jpeg_amd_resize_filter_batch on host images [h, w, 3] -> the outputs as host arrays; the sentinel in every byte of the
     output buffer that belongs to no image is asserted here."""
@@ -76,28 +67,10 @@ def _filter_call(ctx, torch, images, out_w, out_h, filter=AA, gap=0, src_gap=3, 
     return [g.reshape(out_h, out_w, 3) for g in out.images()]
 
 
-def _c_spec(spec):
-    s = _lib.TensorSpec()
-    s.dtype, s.layout = spec.dtype, spec.layout
-    for c in range(3):
-        s.mean[c], s.scale[c] = float(spec.mean[c]), float(spec.scale[c])
-    return s
-
-
-def _c_flips(flips):
-    return None if flips is None else (C.c_uint8 * max(len(flips), 1))(*flips)
-
-
 def _bits(out, spec, out_w, out_h):
     """The images of a tensor call's Out as bit patterns in the spec's layout (the sentinel is asserted by Out.images)."""
     shape = (3, out_h, out_w) if spec.layout == T.CHW else (out_h, out_w, 3)
-    return [b.copy().view(T.BITS[spec.dtype]).reshape(shape) for b in out.images()]
-
-
-def _same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), bad[:4].tolist(), [int(got[tuple(b)]) for b in bad[:4]], [int(want[tuple(b)]) for b in bad[:4]])
+    return [host_bits(b, spec).reshape(shape) for b in out.images()]
 
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------------

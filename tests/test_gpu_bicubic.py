@@ -1,5 +1,5 @@
-"""The bicubic resample on the MI355X (JPEG_AMD_FILTER_BICUBIC through every call that takes `filter`; k_bicubic_bytes,
-k_bicubic_tensor, k_bicubic_oriented_*): every output is compared byte for byte, or element for element as a bit pattern,
+"""The bicubic resample on the MI355X (JPEG_AMD_FILTER_BICUBIC through every call that takes `filter`; k_tables_bytes and
+k_tables_tensor with the BicubicFilter): every output is compared byte for byte, or element for element as a bit pattern,
 with _bicubic_ref -- the contract of include/jpeg_amd.h ("bicubic resample") restated in numpy -- applied to the source
 bytes or to what the existing view decode returns for the same views; tensors go through _tensor_ref's output stage,
 orientations through _orient.  The bilinear and the antialiasing filter must give what they gave.  Every raw call writes
@@ -19,6 +19,7 @@ import jpeg_amd as J
 from _calls import (FUSED, RESIZE_SIZE, RESIZE_TILE_H as TILE_H, RESIZE_TILE_W as TILE_W, Out, c_layout, c_views, pixel_image,
                     plane_ptrs, resize_py_layout, strides, synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _resample import c_spec as _c_spec, pack as _pack, same as _same, tensor_bits as _bits, torch_orient
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -62,16 +63,6 @@ def _resampled(out_w, out_h):
     return out
 
 
-def _pack(ctx, torch, images, src_gap=3):
-    n = len(images)
-    src_stride = max(im.size for im in images) + src_gap
-    src = np.full(n * src_stride, 0x5A, np.uint8)
-    for i, im in enumerate(images):
-        src[i * src_stride:i * src_stride + im.size] = im.reshape(-1)
-    ext = (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
-    return torch.from_numpy(src).to(ctx.torch_device), src_stride, ext
-
-
 def _filter_call(ctx, torch, images, out_w, out_h, filter=BICUBIC, gap=0, expect=0):
     """jpeg_amd_resize_filter_batch on host images [h, w, 3] -> the outputs as host arrays; the sentinel in every byte of the
     output buffer that belongs to no image is asserted here."""
@@ -84,26 +75,6 @@ def _filter_call(ctx, torch, images, out_w, out_h, filter=BICUBIC, gap=0, expect
         assert out.untouched()
         return None
     return [g.reshape(out_h, out_w, 3) for g in out.images()]
-
-
-def _c_spec(spec):
-    s = _lib.TensorSpec()
-    s.dtype, s.layout = spec.dtype, spec.layout
-    for c in range(3):
-        s.mean[c], s.scale[c] = float(spec.mean[c]), float(spec.scale[c])
-    return s
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), bad[:4].tolist(), [int(got[tuple(b)]) for b in bad[:4]], [int(want[tuple(b)]) for b in bad[:4]])
-
-
-def _bits(t, torch):
-    """A tensor of a tensor call as bit patterns on the host."""
-    return t.contiguous().view({4: torch.int32, 2: torch.int16}[t.element_size()]).cpu().numpy().view({4: np.uint32, 2: np.uint16}[t.element_size()])
 
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------------
@@ -153,18 +124,6 @@ def test_tensor_form_matches_the_contract(ctx, torch, combo):
 
 # ---- 3. orientations --------------------------------------------------------------------------------------------------------------
 
-def _torch_orient(t, o):
-    """A contiguous oriented copy of a device image [h, w, 3], made with torch."""
-    transpose, fx, fy = E.BITS[o]
-    if fy:
-        t = t.flip(0)
-    if fx:
-        t = t.flip(1)
-    if transpose:
-        t = t.transpose(0, 1)
-    return t.contiguous()
-
-
 def test_all_eight_orientations(ctx, torch):
     out_w, out_h = 24, 40
     cases = [(size, o) for size in ((130, 70), (70, 130)) for o in range(1, 9)] + [((40, 192), 6), ((192, 40), 1)]   # k = 8 along x
@@ -172,7 +131,7 @@ def test_all_eight_orientations(ctx, torch):
     orient = [o for _, o in cases]
     dev = [torch.from_numpy(im).to(ctx.torch_device) for im in images]
     got = J.resize(ctx, dev, (out_w, out_h), filter="bicubic", orientations=orient).cpu().numpy()
-    witness = J.resize(ctx, [_torch_orient(t, o) for t, o in zip(dev, orient)], (out_w, out_h), filter="bicubic").cpu().numpy()
+    witness = J.resize(ctx, [torch_orient(torch, t, o) for t, o in zip(dev, orient)], (out_w, out_h), filter="bicubic").cpu().numpy()
     for i, (im, (size, o)) in enumerate(zip(images, cases)):
         _same(got[i], B.resize(E.orient(im, o), out_w, out_h), (size, o))
         _same(got[i], witness[i], (size, o, "the unoriented call on an oriented copy"))

@@ -1,4 +1,4 @@
-"""The oriented resample on the MI355X (the six *_oriented_* calls; k_resize_oriented_*, k_antialias_oriented_*): the contract
+"""The oriented resample on the MI355X (the six *_oriented_* calls; the kernels over the Oriented* records): the contract
 of include/jpeg_amd.h ("oriented resample") is by reference -- the filter's contract applied to the oriented image -- so every
 output is compared byte for byte, or element for element as a bit pattern, with the existing numpy mirrors (_resize_ref,
 _antialias_ref, _tensor_ref) applied to orient(source, o), and, as a second witness, with what the existing GPU call writes for
@@ -17,6 +17,7 @@ import _tensor_ref as T
 import jpeg_amd as J
 from _calls import Out, pixel_image
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _resample import c_bytes, c_spec, host_bits as bits, pack, same, torch_orient
 from jpeg_amd import _lib
 from jpeg_amd.api import _mixed_args
 
@@ -26,39 +27,6 @@ AA, BILINEAR = _lib.FILTER_ANTIALIAS, _lib.FILTER_BILINEAR
 MIRROR = {BILINEAR: R.resize, AA: A.resize}
 NAME = {BILINEAR: "bilinear", AA: "antialias"}
 SIZES = [(37, 23), (23, 37), (64, 33), (130, 70), (70, 130), (1, 9), (9, 1), (1, 1)]      # (w, h) as stored
-
-
-def torch_orient(torch, t, o):
-    """A contiguous oriented copy of a device image [h, w, 3], made with torch."""
-    T_, fx, fy = E.BITS[o]
-    if fy:
-        t = t.flip(0)
-    if fx:
-        t = t.flip(1)
-    if T_:
-        t = t.transpose(0, 1)
-    return t.contiguous()
-
-
-def c_spec(spec):
-    s = _lib.TensorSpec()
-    s.dtype, s.layout = spec.dtype, spec.layout
-    for c in range(3):
-        s.mean[c], s.scale[c] = float(spec.mean[c]), float(spec.scale[c])
-    return s
-
-
-def c_bytes(values):
-    return None if values is None else (C.c_uint8 * max(len(values), 1))(*[int(v) for v in values])
-
-
-def pack(ctx, torch, images, gap=3):
-    n = len(images)
-    stride = max(im.size for im in images) + gap
-    src = np.full(n * stride, 0x5A, np.uint8)
-    for i, im in enumerate(images):
-        src[i * stride:i * stride + im.size] = im.reshape(-1)
-    return torch.from_numpy(src).to(ctx.torch_device), stride, (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
 
 
 def resize_call(ctx, torch, images, orient, out_w, out_h, filter, spec=None, flips=None, expect=0, old=False):
@@ -82,17 +50,6 @@ def resize_call(ctx, torch, images, orient, out_w, out_h, filter, spec=None, fli
         assert out.untouched()
         return st, None
     return st, out.images()
-
-
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, int(bad.size), bad[:4].tolist(), got[bad[:4]].tolist(), want[bad[:4]].tolist())
-
-
-def bits(b, spec):
-    return np.asarray(b).copy().view(T.BITS[spec.dtype])
 
 
 # ---- 1. bilinear bytes: eight orientations in one launch --------------------------------------------------------------------------

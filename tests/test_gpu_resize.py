@@ -13,6 +13,7 @@ from _calls import (RESIZE_CONTENTS as CONTENTS, RESIZE_EXTENTS as EXTENTS, RESI
                     RESIZE_TILE_H as TILE_H, RESIZE_TILE_W as TILE_W, RESIZE_VIEWS as VIEWS, SENTINEL, Out, c_layout, pixel_image,
                     resize_py_layout, resized_call, synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _resample import pack
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +26,8 @@ def _resize_call(ctx, torch, images, out_w, out_h, gap=0, src_gap=0, expect=0):
     """jpeg_amd_resize_batch on host images [h, w, 3] -> the outputs as host arrays; the sentinel in every byte of the output
     buffer that belongs to no image is asserted here."""
     n = len(images)
-    src_stride = max(im.size for im in images) + src_gap
-    src = np.full(n * src_stride, 0x5A, np.uint8)
-    for i, im in enumerate(images):
-        src[i * src_stride:i * src_stride + im.size] = im.reshape(-1)
-    d_src = torch.from_numpy(src).to(ctx.torch_device)
+    d_src, src_stride, ext = pack(ctx, torch, images, src_gap)
     out = Out(ctx, torch, [3 * max(out_w, 0) * max(out_h, 0)] * n, gap=gap, tail=7)
-    ext = (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
     assert _lib.lib().jpeg_amd_resize_batch(ctx.handle, n, d_src.data_ptr(), src_stride, ext, out_w, out_h, out.ptr,
                                             out.stride) == expect
     if expect != 0:

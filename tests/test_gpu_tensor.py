@@ -15,6 +15,7 @@ from _calls import (RESIZE_CONTENTS as CONTENTS, RESIZE_EXTENTS as EXTENTS, RESI
                     RESIZE_TILE_H as TILE_H, RESIZE_TILE_W as TILE_W, RESIZE_VIEWS as VIEWS, SENTINEL, Out, c_layout, c_views,
                     pixel_image, plane_ptrs, resize_py_layout, resized_call, strides, synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _resample import c_bytes as _c_flips, c_spec as _c_spec, pack, same as _same
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -29,18 +30,6 @@ LAYOUT_NAMES = {T.HWC: "hwc", T.CHW: "chw"}
 ELEM = {T.F32: 4, T.F16: 2, T.BF16: 2}
 COMBOS = [(d, l) for d in T.DTYPES for l in T.LAYOUTS]
 COMBO_IDS = ["%s-%s" % (DTYPE_NAMES[d], LAYOUT_NAMES[l]) for d, l in COMBOS]
-
-
-def _c_spec(spec):
-    s = _lib.TensorSpec()
-    s.dtype, s.layout = spec.dtype, spec.layout
-    for c in range(3):
-        s.mean[c], s.scale[c] = float(spec.mean[c]), float(spec.scale[c])
-    return s
-
-
-def _c_flips(flips):
-    return None if flips is None else (C.c_uint8 * max(len(flips), 1))(*flips)
 
 
 @functools.lru_cache(maxsize=None)
@@ -74,23 +63,11 @@ class TensorOut(Out):
 
 def _resize_tensor_call(ctx, torch, images, out_w, out_h, spec, flips, gap=0, lead=0, src_gap=3):
     n = len(images)
-    src_stride = max(im.size for im in images) + src_gap
-    src = np.full(n * src_stride, 0x5A, np.uint8)
-    for i, im in enumerate(images):
-        src[i * src_stride:i * src_stride + im.size] = im.reshape(-1)
-    d_src = torch.from_numpy(src).to(ctx.torch_device)
+    d_src, src_stride, ext = pack(ctx, torch, images, src_gap)
     out = TensorOut(ctx, torch, n, out_w, out_h, spec, gap=gap, lead=lead)
-    ext = (_lib.Extent * n)(*[_lib.Extent(im.shape[1], im.shape[0]) for im in images])
     assert _lib.lib().jpeg_amd_resize_tensor_batch(ctx.handle, n, d_src.data_ptr(), src_stride, ext, out_w, out_h,
                                                    C.byref(_c_spec(spec)), _c_flips(flips), out.ptr, out.stride) == 0
     return out.images()
-
-
-def _same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), bad[:4].tolist(), [hex(int(got[tuple(b)])) for b in bad[:4]],
-                           [hex(int(want[tuple(b)])) for b in bad[:4]])
 
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import jpeg_amd as J
 from _calls import (FUSED, RESIZE_SIZE as SIZE, RESIZE_TILE_H as TILE_H, RESIZE_TILE_W as TILE_W, RESIZE_VIEWS as VIEWS, c_layout,
                     resize_py_layout, synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _resample import same as _same
 from jpeg_amd import _lib
 from jpeg_amd.api import _metadata_array, _scan_array
 
@@ -70,12 +71,6 @@ def _front(ctx, torch, images, w, h, src, gap=0, lead=0, dst_gap=3):
                                                  out.ptr, out.stride)
     assert st == OK, st
     return out.images()
-
-
-def _same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), bad[:4].tolist(), [int(got[tuple(b)]) for b in bad[:4]], [int(want[tuple(b)]) for b in bad[:4]])
 
 
 # ---- 1. the front alone -------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_antialias.py -- the antialiased resample (k_antialias_tensor) against the bilinear one (k_resize_tensor) and
+"""tools/bench_antialias.py -- the antialiased resample (k_tables_tensor<TriangleFilter, ...>) against the bilinear one (k_resize_tensor) and
 against the route a caller has today to an antialiased tensor, alternating in one process.
 
     python tools/bench_antialias.py [--steps 20] [--warmup 3] [--rounds 5] [--ring 4] [--only-bilinear] [--out profiles/antialias.txt]

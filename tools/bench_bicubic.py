@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""tools/bench_bicubic.py -- the bicubic resample (k_bicubic_tensor) against the antialiased one (k_antialias_tensor) on the
+"""tools/bench_bicubic.py -- the bicubic resample (k_tables_tensor<BicubicFilter, ...>) against the antialiased one (<TriangleFilter, ...>) on the
 same inputs, against the route a caller has today to a bicubic tensor, and against a device copy, alternating in one process.
 
-    python tools/bench_bicubic.py [--steps 20] [--warmup 3] [--rounds 5] [--ring 4] [--only-bilinear | --only-antialias]
+    python tools/bench_bicubic.py [--steps 20] [--warmup 3] [--rounds 5] [--ring 4] [--only-bilinear | --only-antialias | --only-bytes]
                                   [--out profiles/bicubic.txt]
 
 The method and the workload are tools/bench_antialias.py's: each round times `steps` calls of each route between two HIP
@@ -20,7 +20,9 @@ of the sides are cut: the sources are 2.3 GB instead of bench_antialias.py's 2.5
              plus the tensor once
 --only-bilinear and --only-antialias time jpeg_amd_resize_tensor_batch or the antialiased call alone and print one JSON line
 per factor; they touch nothing the parent commit lacks, so a copy of this file in a checkout of the parent, run in
-alternation with this one, shows what this filter's arrival costs the calls that were there.
+alternation with this one, shows what this filter's arrival costs the calls that were there.  --only-bytes times
+jpeg_amd_resize_filter_batch (bytes out: k_tables_bytes) with the antialiasing and the bicubic filter on the same inputs and
+prints one JSON line per factor, for an A/B of two builds of the library (JPEG_AMD_LIBRARY).
 """
 import argparse
 import ctypes as C
@@ -74,6 +76,7 @@ def main():
     ap.add_argument("--ring", type=int, default=4)
     ap.add_argument("--only-bilinear", action="store_true")
     ap.add_argument("--only-antialias", action="store_true")
+    ap.add_argument("--only-bytes", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bicubic.txt"))
     args = ap.parse_args()
     import torch
@@ -107,6 +110,19 @@ def main():
                            "filter %d" % code, ctx.handle)
             return call
 
+        if args.only_bytes:
+            d_bytes = torch.empty(N * out_stride, dtype=torch.uint8, device=dev)
+            res = {"factor": factor}
+            for name, code in (("antialias", _lib.FILTER_ANTIALIAS), ("bicubic", _lib.FILTER_BICUBIC)):
+                def to_bytes(k):
+                    _lib.check(lib.jpeg_amd_resize_filter_batch(ctx.handle, N, sets[k % args.ring].data_ptr(), stride, c_ext, wt, ht, code,
+                                                                d_bytes.data_ptr(), out_stride), "bytes %d" % code, ctx.handle)
+                times = [_timed(torch, to_bytes, args.steps, args.warmup) for _ in range(args.rounds)]
+                res.update({"t_%s_bytes_us" % name: round(statistics.median(times), 1), "rounds_%s" % name: [round(t, 1) for t in times]})
+            print(json.dumps(res), flush=True)
+            del sets, d_bytes
+            torch.cuda.empty_cache()
+            continue
         if args.only_bilinear or args.only_antialias:
             name, fn = ("bilinear", bilinear) if args.only_bilinear else ("antialias", filtered(_lib.FILTER_ANTIALIAS))
             times = [_timed(torch, fn, args.steps, args.warmup) for _ in range(args.rounds)]
@@ -161,7 +177,7 @@ def main():
         print("\n".join(lines[-2:]), flush=True)
         del sets, copy_src, copy_dst
         torch.cuda.empty_cache()
-    if args.out and not (args.only_bilinear or args.only_antialias):
+    if args.out and not (args.only_bilinear or args.only_antialias or args.only_bytes):
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_oriented.py -- the oriented resample (k_resize_oriented_tensor, k_antialias_oriented_tensor) against the
+"""tools/bench_oriented.py -- the oriented resample (k_resize_tensor<true, ...>, k_tables_tensor over OrientedAntialiasRecords) against the
 kernels without orientations and against the route a caller has today to upright tensors, alternating in one process.
 
     python tools/bench_oriented.py [--steps 20] [--warmup 3] [--rounds 5] [--ring 2] [--out profiles/oriented.txt]

@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
-SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_region.hip", "kernels_scaled.hip", "kernels_view.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
-HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp"]
+SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_tile.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
+HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
 # Per-source flags.  The transform kernels are compiled WITHOUT the SLP vectoriser: it turns the float arithmetic of the 8-point
@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # (k_quad420 / k_luma_fused pin their arithmetic with empty asm statements and hold no packed operations either way.)
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "kernels_stage.hip": _NO_SLP,
-               "kernels_region.hip": _NO_SLP, "kernels_scaled.hip": _NO_SLP, "kernels_view.hip": _NO_SLP, "kernels_resample.hip": _NO_SLP,
+               "kernels_tile.hip": _NO_SLP, "kernels_resample.hip": _NO_SLP,
                "kernels_reduce.hip": _NO_SLP, "kernels_pixels.hip": _NO_SLP}
 
 
@@ -45,8 +45,8 @@ NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fuse
               "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E"),
               "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
-                "kernels_transform.hip": "k_spectral_transform", "kernels_region.hip": "k_region_decode",
-                "kernels_scaled.hip": "k_scaled_decode", "kernels_view.hip": "k_view_decode",
+                "kernels_transform.hip": "k_spectral_transform",
+                "kernels_tile.hip": ("k_region_decode", "k_scaled_decode", "k_view_decode"),
                 "kernels_reduce.hip": "k_spectral_reduce",
                 # the oriented bilinear kernels, and _bytes and _tensor of the filters with tables
                 "kernels_resample.hip": ("k_resize_oriented_bytes", "k_resize_tensorILb1E", "k_tables_")}

@@ -4,6 +4,7 @@
 
 #include "capi_internal.hpp"
 #include "orient.hpp"
+#include "tile_staging.hpp"
 
 using namespace jpeg_amd;
 using namespace jpeg_amd::capi;
@@ -33,41 +34,39 @@ int upload_regions(jpeg_amd_ctx *ctx, const std::vector<uint32_t> &buf)
     return JPEG_AMD_OK;
 }
 
-// One launch of a view decode kernel, appended to the words that are staged for it: the index list [m] of its images, then the
-// prefix [m + 1] of their tiles at n samples per block.  *nwg: the launch's workgroups; EINVAL: more of them than a grid holds.
-int stage_group(std::vector<uint32_t> &buf, const std::vector<uint32_t> &members, int n, const jpeg_amd_view *h_views, uint32_t *nwg)
+// The rectangles of the call's views as the payload of what is staged for it (tile_staging.hpp); room for `groups` groups.
+TileStaging stage_rects(const jpeg_amd_view *h_views, size_t n, size_t groups)
 {
-    buf.insert(buf.end(), members.begin(), members.end());
-    uint64_t acc = 0;
-    for (const uint32_t i : members) {
-        buf.push_back((uint32_t)acc);
-        acc += view_tiles(n, h_views[i].region);
-    }
-    if (acc > 0x7fffffffu) return JPEG_AMD_EINVAL;
-    buf.push_back((uint32_t)acc);
-    *nwg = (uint32_t)acc;
-    return JPEG_AMD_OK;
+    TileStaging st(n, sizeof(jpeg_amd_region), groups);
+    for (size_t i = 0; i < n; ++i) st.rect(i, h_views[i].region);
+    return st;
 }
 
-// The regions (int32 [n][4]) and their tile prefix (uint32 [n + 1]) in the context's region buffer, one copy from a host
-// buffer (pageable, so the copy has taken it when the call returns -- as stage_quanta).  Returns the workgroup count.
-int stage_regions(jpeg_amd_ctx *ctx, const jpeg_amd_region *h, int n, const int32_t **d_regions, const uint32_t **d_tiles,
-                  uint32_t *nwg)
+// A launch of `kernel` for images of the call c at n samples per block: everything but what is staged.
+TileLaunch tile_launch(TileKernel kernel, const DecodeCall &c, const PlaneSet &cs, int n)
 {
-    const size_t bytes = (size_t)16 * n + 4 * ((size_t)n + 1);
-    std::vector<uint32_t> buf(bytes / 4);
-    uint32_t acc = 0;
-    for (int i = 0; i < n; ++i) {
-        std::memcpy(&buf[4 * (size_t)i], &h[i], 16);
-        buf[4 * (size_t)n + i] = acc;
-        acc += region_tiles(h[i]);
-    }
-    buf[4 * (size_t)n + n] = acc;
-    JA_TRY(upload_regions(ctx, buf));
-    *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
-    *d_tiles = reinterpret_cast<const uint32_t *>(*d_regions + 4 * (size_t)n);
-    *nwg = acc;
-    return JPEG_AMD_OK;
+    TileLaunch l{};
+    l.kernel = kernel;
+    l.n = n;
+    l.nplanes = c.L->nplanes;
+    l.rgb = c.rgb();
+    l.layout = c.L;
+    l.coef = cs;
+    l.q = c.quanta();
+    l.d_pixels = c.d_pixels;
+    l.pixel_stride = c.pixel_stride;
+    return l;
+}
+
+// ... and what is staged for it: group g of the words that were uploaded to d_words.
+void staged(TileLaunch &l, const void *d_words, const TileGroup &g)
+{
+    const uint32_t *w = static_cast<const uint32_t *>(d_words);
+    l.n_images = g.n_images;
+    l.d_payload = d_words;
+    l.d_index = w + g.index;
+    l.d_tiles = w + g.tiles;
+    l.nwg = g.nwg;
 }
 
 constexpr size_t kFallbackChunkBytes = (size_t)1 << 30;   // scratch per chunk of a fallback's whole-image decodes or planes
@@ -84,18 +83,16 @@ int crop_fallback(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h
     const int n_images = c.n_images;
     const size_t n = (size_t)n_images;
     size_t full_max = 0;
-    std::vector<uint32_t> buf(4 * n);
     for (size_t i = 0; i < n; ++i) {
         const jpeg_amd_layout &Si = S[view_slot(h_views[i].denom)];
         full_max = std::max(full_max, (size_t)3 * Si.width * Si.height);
-        std::memcpy(&buf[4 * i], &h_views[i].region, 16);
     }
     const size_t per_image = full_max + scratch_planes_bytes(L, 1, sizeof(uint8_t));
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, kFallbackChunkBytes / per_image));
     const size_t planes_bytes = scratch_planes_bytes(L, chunk, sizeof(uint8_t));
     JA_TRY(ensure_buffer(ctx, ctx->scratch, planes_bytes + align256(full_max * chunk)));
     uint8_t *d_full = static_cast<uint8_t *>(ctx->scratch.ptr) + planes_bytes;   // the staged paths' planes stay below it
-    JA_TRY(upload_regions(ctx, buf));
+    JA_TRY(upload_regions(ctx, stage_rects(h_views, n, 0).words));
     const int32_t *d_regions = static_cast<const int32_t *>(ctx->region.ptr);
     for (int i0 = 0; i0 < n_images;) {
         const int denom = h_views[i0].denom;
@@ -140,19 +137,25 @@ try {
         return jpeg_amd_decode_batch(ctx, L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
                                      d_pixels, pixel_stride);
 
+    // views at denominator 1, where the scaled image is the image
+    const size_t n = (size_t)n_images;
+    std::vector<jpeg_amd_view> views(n);
+    for (size_t i = 0; i < n; ++i) views[i] = jpeg_amd_view{1, h_regions[i]};
     if (fused_decode_supported(*L, cosited != 0)) {
-        const int32_t *d_regions = nullptr;
-        const uint32_t *d_tiles = nullptr;
-        uint32_t nwg = 0;
-        JA_TRY(stage_regions(ctx, h_regions, n_images, &d_regions, &d_tiles, &nwg));
-        JA_HIP(ctx, launch_region_decode(ctx->stream, n_images, *L, cs, c.quanta(), c.rgb(), d_tiles, d_regions, nwg, d_pixels,
-                                         pixel_stride));
+        // staged in one copy: the rectangles [n][4], then the one group of all images in order (its index list is not read)
+        TileStaging st = stage_rects(views.data(), n, 1);
+        std::vector<uint32_t> all(n);
+        for (size_t i = 0; i < n; ++i) all[i] = (uint32_t)i;
+        TileGroup g;
+        JA_TRY(st.group(all, [&](uint32_t i) { return rect_tiles(8, kRegionTileH, h_regions[i]); }, &g));
+        JA_TRY(upload_regions(ctx, st.words));
+        TileLaunch l = tile_launch(TileKernel::Region, c, cs, 8);
+        staged(l, ctx->region.ptr, g);
+        JA_HIP(ctx, launch_tile_decode(ctx->stream, l));
         return JPEG_AMD_OK;
     }
 
-    // the crop fallback at denominator 1, where the scaled image is the image
-    std::vector<jpeg_amd_view> views((size_t)n_images);
-    for (int i = 0; i < n_images; ++i) views[(size_t)i] = jpeg_amd_view{1, h_regions[i]};
+    // the crop fallback
     const jpeg_amd_layout S[kViewDenoms] = {*L};
     return crop_fallback(ctx, c, views.data(), S);
 }
@@ -252,10 +255,12 @@ int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
     PlaneSet cs;
     JA_TRY(c.planes(&cs));
     if (n_images > 1 && pixel_stride < (size_t)3 * S.width * S.height) return JPEG_AMD_EINVAL;
-    const QuantaRef q = c.quanta();
-    const bool rgb = c.rgb();
     if (fused_decode_supported(*L, cosited != 0)) {
-        JA_HIP(ctx, launch_scaled_decode(ctx->stream, n_images, *L, n, S.width, S.height, cs, q, rgb, d_pixels, pixel_stride));
+        TileLaunch l = tile_launch(TileKernel::Scaled, c, cs, n);
+        l.width = S.width;
+        l.height = S.height;
+        l.n_images = n_images;
+        JA_HIP(ctx, launch_tile_decode(ctx->stream, l));
         return JPEG_AMD_OK;
     }
 
@@ -276,7 +281,7 @@ int jpeg_amd_decode_scaled_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, in
             ps.ptr[p] = scratch.ptr[p];
             ps.stride[p] = scratch.stride[p];
         }
-        JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, m, S, ps, true, cosited != 0, rgb ? PixelKind::RGB8 : PixelKind::YCC8,
+        JA_HIP(ctx, launch_planar_to_pixels(ctx->stream, m, S, ps, true, cosited != 0, c.rgb() ? PixelKind::RGB8 : PixelKind::YCC8,
                                             part.d_pixels, pixel_stride));
     }
     return JPEG_AMD_OK;
@@ -388,27 +393,23 @@ try {
 
     const size_t n = (size_t)n_images;
     if (fused_decode_supported(*L, cosited != 0)) {
-        // staged in one copy: the rectangles [n][4], then per denominator of the call its group (stage_group)
-        std::vector<uint32_t> buf(4 * n), members;
-        for (size_t i = 0; i < n; ++i) std::memcpy(&buf[4 * i], &h_views[i].region, 16);
-        size_t at[kViewDenoms];
-        uint32_t nwg[kViewDenoms];
+        // staged in one copy: the rectangles [n][4], then per denominator of the call its group
+        TileStaging st = stage_rects(h_views, n, kViewDenoms);
+        std::vector<uint32_t> members;
+        TileGroup group[kViewDenoms];
         for (int k = 0; k < kViewDenoms; ++k) {
-            at[k] = buf.size();
-            nwg[k] = 0;
             if (count[k] == 0) continue;
             members.clear();
             for (size_t i = 0; i < n; ++i)
                 if (view_slot(h_views[i].denom) == k) members.push_back((uint32_t)i);
-            JA_TRY(stage_group(buf, members, 8 >> k, h_views, &nwg[k]));
+            JA_TRY(st.group(members, [&](uint32_t i) { return rect_tiles(8 >> k, kViewTileH, h_views[i].region); }, &group[k]));
         }
-        JA_TRY(upload_regions(ctx, buf));
-        const uint32_t *d_buf = static_cast<const uint32_t *>(ctx->region.ptr);
+        JA_TRY(upload_regions(ctx, st.words));
         for (int k = 0; k < kViewDenoms; ++k) {
             if (count[k] == 0) continue;
-            JA_HIP(ctx, launch_view_decode(ctx->stream, count[k], *L, 8 >> k, cs, c.quanta(), c.rgb(), d_buf + at[k],
-                                           d_buf + at[k] + count[k], reinterpret_cast<const int32_t *>(d_buf), nwg[k], d_pixels,
-                                           pixel_stride));
+            TileLaunch l = tile_launch(TileKernel::View, c, cs, 8 >> k);
+            staged(l, ctx->region.ptr, group[k]);
+            JA_HIP(ctx, launch_tile_decode(ctx->stream, l));
         }
         return JPEG_AMD_OK;
     }
@@ -803,7 +804,7 @@ int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosi
         }
         const int k = view_slot(v[i].denom), g = 2 * k + (im[i].layout.nplanes == 3 ? 1 : 0);
         plan->members[g].push_back((uint32_t)i);
-        acc[g] += view_tiles(8 >> k, v[i].region);
+        acc[g] += rect_tiles(8 >> k, kViewTileH, v[i].region);
     }
     for (int g = 0; g < kMixedGroups; ++g)
         if (acc[g] > 0x7fffffffu) return JPEG_AMD_EINVAL;
@@ -811,39 +812,33 @@ int plan_mixed(const jpeg_amd_image *im, const jpeg_amd_view *v, int m, int cosi
 }
 
 // The planned images into d_pixels, image i at i * pixel_stride: one copy of the records [m], then per group its index list
-// and tile prefix (stage_group), into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when
+// and tile prefix (tile_staging.hpp), into the context's `mixed` buffer (from a pageable host buffer, so the copy has taken it when
 // the call returns -- as stage_quanta); a launch per group; the uniform call for each of the others.
 int run_mixed(jpeg_amd_ctx *ctx, const jpeg_amd_image *im, const jpeg_amd_view *v, int m, const MixedPlan &plan, int cosited,
               jpeg_amd_color color, uint8_t *d_pixels, size_t pixel_stride)
 {
-    const size_t rec_bytes = mixed_record_bytes(), lists = rec_bytes * (size_t)m / 4;
-    size_t words = 0;
-    for (int g = 0; g < kMixedGroups; ++g)
-        if (!plan.members[g].empty()) words += 2 * plan.members[g].size() + 1;
-    if (words != 0) {
-        std::vector<uint32_t> buf;
-        buf.reserve(lists + words);
-        buf.resize(lists);   // the records of the uniform call's images stay zero: no list names them
-        size_t at[kMixedGroups] = {};
-        uint32_t nwg[kMixedGroups] = {};
+    if ((size_t)m != plan.fallback.size()) {
+        TileStaging st((size_t)m, mixed_record_bytes(), kMixedGroups);   // the records of the uniform call's images stay zero: no list names them
+        TileGroup group[kMixedGroups];
         for (int g = 0; g < kMixedGroups; ++g) {
             const std::vector<uint32_t> &mem = plan.members[g];
             if (mem.empty()) continue;
             const int n = 8 >> (g / 2);
             for (const uint32_t i : mem)
-                mixed_record(reinterpret_cast<uint8_t *>(buf.data()) + rec_bytes * i, im[i].layout, n, im[i].d_coef, im[i].d_quanta,
-                             v[i].region, d_pixels + (size_t)i * pixel_stride);
-            at[g] = buf.size();
-            JA_TRY(stage_group(buf, mem, n, v, &nwg[g]));
+                mixed_record(st.payload(i), im[i].layout, n, im[i].d_coef, im[i].d_quanta, v[i].region, d_pixels + (size_t)i * pixel_stride);
+            JA_TRY(st.group(mem, [&](uint32_t i) { return rect_tiles(n, kViewTileH, v[i].region); }, &group[g]));
         }
-        JA_TRY(ensure_buffer(ctx, ctx->mixed, 4 * buf.size()));
-        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, ctx->stream));
-        const uint32_t *d_w = static_cast<const uint32_t *>(ctx->mixed.ptr);
+        JA_TRY(ensure_buffer(ctx, ctx->mixed, 4 * st.words.size()));
+        JA_HIP(ctx, hipMemcpyAsync(ctx->mixed.ptr, st.words.data(), 4 * st.words.size(), hipMemcpyHostToDevice, ctx->stream));
         for (int g = 0; g < kMixedGroups; ++g) {
-            const int count = (int)plan.members[g].size();
-            if (count == 0) continue;
-            JA_HIP(ctx, launch_view_decode_mixed(ctx->stream, count, 8 >> (g / 2), g % 2 ? 3 : 1, color == JPEG_AMD_COLOR_RGB8,
-                                                 ctx->mixed.ptr, d_w + at[g], d_w + at[g] + count, nwg[g]));
+            if (plan.members[g].empty()) continue;
+            TileLaunch l{};
+            l.kernel = TileKernel::Mixed;
+            l.n = 8 >> (g / 2);
+            l.nplanes = g % 2 ? 3 : 1;
+            l.rgb = color == JPEG_AMD_COLOR_RGB8;
+            staged(l, ctx->mixed.ptr, group[g]);
+            JA_HIP(ctx, launch_tile_decode(ctx->stream, l));
         }
     }
     for (const int i : plan.fallback)

@@ -114,51 +114,57 @@ bool       generic_fused_supported(const jpeg_amd_layout &layout);
 hipError_t launch_generic_fused(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef,
                                 QuantaRef q, bool cosited, uint32_t *d_walk_counter, uint16_t *d_rect, size_t rect_stride);
 
-// ---- region decode (kernels_region.hip) -----------------------------------------------
-// The layouts of fused_decode_supported: n_images images, image i cut to its rectangle in ONE launch of nwg workgroups.
-// d_regions: int32 [n][4] (x, y, width, height); d_tiles: uint32 [n + 1], the prefix of region_tiles over the images
-// (d_tiles[n] == nwg).  Image i's rows of width * 3 bytes, unpadded, at d_pixels + i * pixel_stride.
-uint32_t   region_tiles(const jpeg_amd_region &region);
-hipError_t launch_region_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, const PlaneSet &coef, QuantaRef q,
-                                bool rgb, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
-                                uint8_t *d_pixels, size_t pixel_stride);
-// Any layout: whole decoded images (width x height x 3 bytes, full_stride apart) cut to their rectangles.  max_bytes: the
-// largest rectangle's byte count.
-hipError_t launch_region_crop(hipStream_t stream, int n_images, const uint8_t *d_full, size_t full_stride, int width,
-                              const int32_t *d_regions, size_t max_bytes, uint8_t *d_pixels, size_t pixel_stride);
+// ---- tile decode (kernels_tile.hip) ------------------------------------------------------
+// The layouts of fused_decode_supported, n x n samples per block (n = 8 / denom): ONE launch of one of the four kernels whose
+// workgroup decodes a tile of output pixels straight from the coefficients.  What the host stages for the rectangle grids --
+// per image of the call a rectangle or a record, per launch an index list and a tile prefix -- is tile_staging.hpp's, which
+// also holds the tile count (rect_tiles) and the tile heights.
+enum class TileKernel : int {
+    Region,   // k_region_decode: n = 8; image i of the launch is image i of the call, cut to its rectangle; tiles of kRegionTileH rows
+    Scaled,   // k_scaled_decode: n in {4, 2, 1}; whole scaled images of width x height on a static grid, nothing staged
+    View,     // k_view_decode: n in {8, 4, 2, 1}; the images of a call that share n, each cut to its rectangle of the scaled image
+    Mixed,    // k_view_decode_mixed: View for images of different layouts that share n and the number of planes (1 or 3)
+};
+struct TileLaunch {
+    TileKernel kernel;
+    int  n, nplanes;
+    bool rgb;
+    // The images -- Region, Scaled, View: `layout` is the FULL-SIZE image's (nplanes its number of planes); image i's
+    // coefficients, tables and pixels (rows of its width * 3 bytes, unpadded, at d_pixels + i * pixel_stride) are image i of
+    // the CALL's.  Mixed: all of that is in the image's record.
+    const jpeg_amd_layout *layout;
+    PlaneSet  coef;
+    QuantaRef q;
+    uint8_t  *d_pixels;
+    size_t    pixel_stride;
+    int       width, height;   // Scaled: W', H'
+    int       n_images;        // of the launch
+    // What is staged -- Region, View, Mixed: the words of a TileStaging on the device.  d_payload: word 0, 16-byte aligned
+    // (Region, View: the rectangles of rect(); Mixed: records of mixed_record_bytes() bytes, written by mixed_record);
+    // d_index, d_tiles, nwg: the launch's TileGroup in them, over rect_tiles(n, kRegionTileH or kViewTileH, rectangle).
+    // Region does not read d_index.
+    const void     *d_payload;
+    const uint32_t *d_index, *d_tiles;
+    uint32_t        nwg;
+};
+// Nothing is launched for no images or no workgroups.  hipErrorInvalidValue: an n that `kernel` is not built for, planes other
+// than 1 or 3, or (Region, Scaled, View) no layout or one of another number of planes.
+hipError_t launch_tile_decode(hipStream_t stream, const TileLaunch &launch);
 
-// ---- scaled decode (kernels_scaled.hip) ------------------------------------------------
-// n = 8 / denom in {4, 2, 1}; `layout` is the FULL-SIZE image's, width x height the scaled image's (W', H').
-// The layouts of fused_decode_supported: n_images images in ONE launch (k_scaled_decode).  Image i's rows of width * 3
-// bytes, unpadded, at d_pixels + i * pixel_stride.
-hipError_t launch_scaled_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, int n, int width, int height,
-                                const PlaneSet &coef, QuantaRef q, bool rgb, uint8_t *d_pixels, size_t pixel_stride);
-// Any layout: one plane (ux x uy blocks) into n x n samples per block, uint16 or uint8, in a plane of ceil(n ux / 8) x
-// ceil(n uy / 8) whole blocks whose padding repeats the edge samples (k_idct_scaled).
-hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int16_t *d_coef, size_t coef_stride, QuantaRef q,
-                                    int qi, int ux, int uy, int n, int precision, void *d_plane, size_t plane_stride, bool out_u8);
-
-// ---- view decode (kernels_view.hip) ------------------------------------------------------
-// The layouts of fused_decode_supported, n = 8 / denom in {8, 4, 2, 1}: the n_images images of a call that share n, each cut
-// to its rectangle of the scaled image, in ONE launch of nwg workgroups (k_view_decode).  d_index: uint32 [n_images], the
-// launch's image i is image d_index[i] of the call -- which is where its coefficients, tables, rectangle (d_regions: int32
-// [images of the call][4]) and pixels are; d_tiles: uint32 [n_images + 1], the prefix of view_tiles over the launch's images
-// (d_tiles[n_images] == nwg).
-uint32_t   view_tiles(int n, const jpeg_amd_region &region);
-hipError_t launch_view_decode(hipStream_t stream, int n_images, const jpeg_amd_layout &layout, int n, const PlaneSet &coef, QuantaRef q,
-                              bool rgb, const uint32_t *d_index, const uint32_t *d_tiles, const int32_t *d_regions, uint32_t nwg,
-                              uint8_t *d_pixels, size_t pixel_stride);
-
-// ... and for images of different layouts (k_view_decode_mixed): the images of a call that share n and the number of planes
-// (1 or 3), every one with the layout, planes, tables, rectangle and output of its own, in ONE launch.  d_records: one record
-// of mixed_record_bytes() bytes per image of the call, 16-byte aligned, written by mixed_record on the host -- `layout` is
-// one of fused_decode_supported, `region` a rectangle of its image at n samples per block, d_pixels where that rectangle's
-// first pixel goes (rows of region.width * 3 bytes); d_index and d_tiles as above, over view_tiles(n, region).
+// A record of the Mixed kernel: `layout` is one of fused_decode_supported, `region` a rectangle of its image at n samples per
+// block, d_pixels where that rectangle's first pixel goes (rows of region.width * 3 bytes).
 size_t     mixed_record_bytes();
 void       mixed_record(void *dst, const jpeg_amd_layout &layout, int n, const int16_t *const d_coef[], const uint16_t *d_quanta,
                         const jpeg_amd_region &region, uint8_t *d_pixels);
-hipError_t launch_view_decode_mixed(hipStream_t stream, int n_images, int n, int nplanes, bool rgb, const void *d_records,
-                                    const uint32_t *d_index, const uint32_t *d_tiles, uint32_t nwg);
+
+// The fallbacks of the layouts without a tile kernel.  Any layout: whole decoded images (width x height x 3 bytes, full_stride
+// apart) cut to their rectangles (d_regions: int32 [n][4]: x, y, width, height).  max_bytes: the largest rectangle's byte count.
+hipError_t launch_region_crop(hipStream_t stream, int n_images, const uint8_t *d_full, size_t full_stride, int width,
+                              const int32_t *d_regions, size_t max_bytes, uint8_t *d_pixels, size_t pixel_stride);
+// Any layout, n in {4, 2, 1}: one plane (ux x uy blocks) into n x n samples per block, uint16 or uint8, in a plane of
+// ceil(n ux / 8) x ceil(n uy / 8) whole blocks whose padding repeats the edge samples (k_idct_scaled).
+hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int16_t *d_coef, size_t coef_stride, QuantaRef q,
+                                    int qi, int ux, int uy, int n, int precision, void *d_plane, size_t plane_stride, bool out_u8);
 
 // ---- resample (kernels_resample.hip) ------------------------------------------------
 // n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h in ONE launch, by the contracts of

@@ -21,10 +21,9 @@
 #include "fused_common.hpp"
 #include "interleave.hpp"
 #include "kernels.hpp"
+#include "tile_staging.hpp"
 
 namespace jpeg_amd {
-
-constexpr int kTileW = 128;   // output pixels per tile row, every kernel's: a workgroup's rows are runs of up to 384 bytes
 
 // What decode_tile reads of a launch; each kernel's own argument struct holds one next to what finds its tiles.
 struct TileArgs {
@@ -37,27 +36,6 @@ struct TileArgs {
     uint8_t *pixels;
     size_t pixel_stride;          // bytes between images
 };
-
-// interleave_axis with the padded edge of a plane of n x n samples per block (n = 8: interleave_axis's own value).
-inline TileArgs tile_args(const jpeg_amd_layout &L, int n, const PlaneSet &coef, QuantaRef q, uint8_t *d_pixels, size_t pixel_stride)
-{
-    TileArgs a{};
-    for (int p = 0; p < L.nplanes; ++p) {
-        a.coef[p] = static_cast<const int16_t *>(coef.ptr[p]);
-        a.coef_stride[p] = coef.stride[p];
-        a.ux[p] = L.units_x[p];
-        a.qi[p] = L.qi[p];
-        a.ax[p] = interleave_axis(L, p, false, false);
-        a.ay[p] = interleave_axis(L, p, false, true);
-        a.ax[p].last = n * L.units_x[p] - 1;
-        a.ay[p].last = n * L.units_y[p] - 1;
-    }
-    a.quanta = q.d_quanta;
-    a.quanta_stride = q.image_stride;
-    a.pixels = d_pixels;
-    a.pixel_stride = pixel_stride;
-    return a;
-}
 
 // One block of the window into N x N byte samples at dst (pitch bytes between rows; dst aligned to N): the contract's
 // passes at level 2^7 + 1/2 (decode.swift:4110-4111), from the head of the block that holds the coefficients they read.
@@ -215,13 +193,6 @@ struct RectArgs {
     const int4 *regions;          // [images of the call]: x, y, width, height in pixels
     int n_images;                 // of the launch
 };
-
-// Tiles of a rectangle at n samples per block and tile_h rows per tile: the host's count, which rect_tile takes apart.
-inline uint32_t rect_tiles(int n, int tile_h, const jpeg_amd_region &r)
-{
-    const int ax0 = n * (r.x / n), ay0 = n * (r.y / n);
-    return (uint32_t)((r.x + r.width - 1 - ax0) / kTileW + 1) * (uint32_t)((r.y + r.height - 1 - ay0) / tile_h + 1);
-}
 
 // The launch's image of workgroup wg: the last i with tiles[i] <= wg.
 __device__ __forceinline__ int rect_image(const uint32_t *tiles, int n_images, uint32_t wg)

@@ -47,3 +47,16 @@ def test_chunk_loop_is_clean_under_tsan(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "chunk_loop_test.cpp"), "-o", exe, "-lpthread"])
     r = subprocess.run(["setarch", platform.machine(), "-R", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])
+
+
+def test_tile_staging_is_clean_under_asan_and_ubsan(tmp_path):
+    """What the host stages for the tile decode kernels (csrc/tile_staging.hpp) under AddressSanitizer and
+    UndefinedBehaviorSanitizer: the region, view and mixed calls' groups against a restatement, and the limit of a grid
+    (tests/cpp/tile_staging_test.cpp lists the assertions)."""
+    exe = str(tmp_path / "tile_staging_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "jpeg_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "tile_staging_test.cpp"),
+                           "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])

@@ -14,12 +14,11 @@ import jpeg_amd as J
 from _calls import COLORS, FUSED, SENTINEL, Out, c_layout, c_views, plane_ptrs, strides, synthetic
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
 from _mixed import resized_mixed, tensor_mixed, view_mixed
+from _tile import TILE_H, TILE_W, crop, random_region, reference
 from jpeg_amd import _lib
-from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-TILE_W, TILE_H = 128, 32
 RGB, YCC = _lib.COLOR_RGB8, _lib.COLOR_YCC8
 F411 = [(4, 1), (1, 1), (1, 1)]
 
@@ -146,19 +145,10 @@ def test_three_images_match_the_oracle(ctx, torch, case):
     got = {color: _mixed_views(ctx, torch, case.images, 0, color) for color in COLORS}
     for i in ORACLE:
         im = case.images[i]
-        L, (denom, r) = im.L, im.view
-        factors = [(L.factor_x[p], L.factor_y[p]) for p in range(L.nplanes)]
-        planes = [p[0].cpu().numpy() for p in im.planes]
-        qh = im.dq.cpu().numpy().astype(np.uint16)
-        quanta = [qh[0, L.qi[p]] for p in range(L.nplanes)]
-        if denom == 1:
-            _, rect = O.decode(planes, quanta, factors, im.size, cosited=False, scale=(L.scale_x, L.scale_y))
-        else:
-            _, rect = S.interleaved_scaled(planes, quanta, factors, im.size, denom, False, (L.scale_x, L.scale_y))
-        w, h = S.scaled_size(im.size, denom)
-        for color, unpack in ((RGB, O.unpack_rgb8), (YCC, O.unpack_ycc8)):
-            want = unpack(rect, L.nplanes).reshape(h, w, 3)[r[1]:r[1] + r[3], r[0]:r[0] + r[2]]
-            assert (got[color][i].reshape(r[3], r[2], 3) == want).all(), (i, color)
+        denom, r = im.view
+        want = reference(im.L, [p.cpu().numpy() for p in im.planes], im.dq.cpu().numpy().astype(np.uint16), 0, denom, 0)
+        for color in COLORS:
+            assert (got[color][i].reshape(r[3], r[2], 3) == crop(want[color], r)).all(), (i, color)
 
 
 # ---- 3. the index list and the prefix --------------------------------------------------------------------------------------------
@@ -183,9 +173,7 @@ def test_eight_images_of_one_geometry_equal_the_uniform_batch_call(ctx, torch):
     views = []
     for i in range(n):
         denom = (1, 2, 4, 8)[i % 4]
-        W1, H1 = S.scaled_size((403, 150), denom)
-        x, y = int(rng.integers(0, W1)), int(rng.integers(0, H1))
-        views.append((denom, (x, y, int(rng.integers(1, W1 - x + 1)), int(rng.integers(1, H1 - y + 1)))))
+        views.append((denom, random_region(rng, *S.scaled_size((403, 150), denom))))
     views[5] = (2,) + ((0, 0) + S.scaled_size((403, 150), 2),)
     areas = [3 * r[2] * r[3] for _, r in views]
     images = [(L, [p[i].data_ptr() for p in planes], dq[i].data_ptr(), ntables) for i in range(n)]

@@ -2,25 +2,21 @@
 the same image, cropped -- against jpeg_amd_decode[_batch] on the device and, for the fixtures, against the oracle's full
 decode on the host as well."""
 import ctypes as C
-import glob
 import os
 
 import numpy as np
 import pytest
 
-import _transform_ref as R
 import jpeg_amd as J
 from _calls import SENTINEL, Out, c_layout, c_regions, full_batch, plane_ptrs, plane_units
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
 from _golden import GOLDEN
+from _tile import FIXTURES, fixture, random_region
 from jpeg_amd import _lib
 from jpeg_amd.synth import natural_planes_torch
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-
-DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
-
 
 def _region_batch(ctx, L, planes, coef_stride, dq, q_stride, ntables, cosited, color, regions, out, stride):
     return _lib.lib().jpeg_amd_decode_region_batch(
@@ -57,38 +53,12 @@ def _fixture_regions(W, H, sx, sy, rng, k=20):
                 regs.append((0, c, W, 1))
     lx, ly = (W - 1) // mw * mw, (H - 1) // mh * mh      # the last (partial) MCU column / row
     regs += [(lx, 0, W - lx, H), (0, ly, W, H - ly), (lx, ly, W - lx, H - ly)]
-    for _ in range(k):
-        x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
-        regs.append((x, y, int(rng.integers(1, W - x + 1)), int(rng.integers(1, H - y + 1))))
-    return regs
-
-
-def _fixture(path):
-    data = np.fromfile(path, np.uint8)
-    info, planes, quanta = R.decode_file(data)
-    nc = info.ncomponents
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = info.width, info.height, info.precision, nc
-    L.scale_x, L.scale_y = info.scale_x, info.scale_y
-    for c in range(nc):
-        L.factor_x[c], L.factor_y[c] = info.factor_x[c], info.factor_y[c]
-        L.units_x[c], L.units_y[c] = info.units_x[c], info.units_y[c]
-        L.qi[c] = c
-    return info, L, planes, np.ascontiguousarray(quanta, np.uint16)
-
-
-FIXTURES = []
-for _p in DECODE:
-    _d = np.fromfile(_p, np.uint8)
-    _i = _lib.FrameInfo()
-    if _lib.lib().jpeg_amd_jpeg_inspect(_d.ctypes.data, _d.size, C.byref(_i)) == 0 and _i.precision == 8 and \
-            _i.ncomponents in (1, 3):
-        FIXTURES.append(_p)
+    return regs + [random_region(rng, W, H) for _ in range(k)]
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=[os.path.basename(p) for p in FIXTURES])
 def test_fixture_regions_match_the_full_decode_and_the_oracle(ctx, torch, path):
-    info, L, planes, quanta = _fixture(path)
+    info, L, planes, quanta = fixture(path)
     W, H, nc = info.width, info.height, info.ncomponents
     dev = [ctx.upload(p) for p in planes]
     dq = ctx.upload(quanta)
@@ -121,11 +91,7 @@ SYNTH_SIZES = [(1, 1), (7, 9), (17, 33), (1919, 1079), (4095, 17), (4096, 4096)]
 
 
 def _random_regions(rng, W, H, n):
-    out = []
-    for _ in range(n):
-        x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
-        out.append((x, y, int(rng.integers(1, W - x + 1)), int(rng.integers(1, H - y + 1))))
-    return out
+    return [random_region(rng, W, H) for _ in range(n)]
 
 
 def _check_against_batch(ctx, torch, L, planes, coef_stride, dq, ntables, cosited, color, regs, chunk=16):
@@ -257,7 +223,7 @@ def test_8192_420_region_of_4096_at_1237_901(ctx, torch):
 
 
 def test_python_api(ctx, torch):
-    info, L, planes, quanta = _fixture(os.path.join(GOLDEN, "decode", "color-sequential-1.jpg"))
+    info, L, planes, quanta = fixture(os.path.join(GOLDEN, "decode", "color-sequential-1.jpg"))
     W, H = info.width, info.height
     layout = J.Layout("ycc8", {1: J.Component((2, 2), 0), 2: J.Component((1, 1), 1), 3: J.Component((1, 1), 2)})
     spectral = J.Spectral.from_host(ctx, (W, H), layout, planes, list(quanta), q=[0, 1, 2])

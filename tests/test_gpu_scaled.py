@@ -3,25 +3,20 @@ the contract of include/jpeg_amd.h as restated in _scaled_ref -- fixtures and sy
 the block, MCU and tile edges -- the fused launch against the staged route, unread coefficients, an anchor to the existing
 decode that needs no test-side reference, batches with stride gaps, and the argument checks."""
 import ctypes as C
-import glob
 import os
 
 import numpy as np
 import pytest
 
 import _scaled_ref as S
-import _transform_ref as R
 import jpeg_amd as J
 from _calls import (COLORS, FUSED, SENTINEL, Out, c_layout, full_batch, plane_factors, plane_ptrs, plane_units, strides,
                     synthetic)
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
-from _golden import GOLDEN
+from _tile import FIXTURES, fixture
 from jpeg_amd import _lib
 
 pytestmark = pytest.mark.gpu
-
-DECODE = sorted(glob.glob(os.path.join(GOLDEN, "decode", "*.jpg")))
-
 
 def _call(ctx, L, n, planes, coef_stride, dq, q_stride, ntables, cosited, color, denom, out_ptr, stride):
     return _lib.lib().jpeg_amd_decode_scaled_batch(
@@ -52,27 +47,10 @@ def _reference(L, planes_host, quanta_host, i, denom, cosited, color):
 
 # ---- the fixtures --------------------------------------------------------------------------------------------------------
 
-FIXTURES = []
-for _p in DECODE:
-    _d = np.fromfile(_p, np.uint8)
-    _i = _lib.FrameInfo()
-    if _lib.lib().jpeg_amd_jpeg_inspect(_d.ctypes.data, _d.size, C.byref(_i)) == 0 and _i.precision == 8 and \
-            _i.ncomponents in (1, 3):
-        FIXTURES.append(_p)
-
-
 @pytest.mark.parametrize("path", FIXTURES, ids=[os.path.basename(p) for p in FIXTURES])
 def test_fixtures_match_the_reference(ctx, torch, path):
-    info, planes, quanta = R.decode_file(np.fromfile(path, np.uint8))
+    info, L, planes, quanta = fixture(path)
     nc = info.ncomponents
-    L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes = info.width, info.height, info.precision, nc
-    L.scale_x, L.scale_y = info.scale_x, info.scale_y
-    for c in range(nc):
-        L.factor_x[c], L.factor_y[c] = info.factor_x[c], info.factor_y[c]
-        L.units_x[c], L.units_y[c] = info.units_x[c], info.units_y[c]
-        L.qi[c] = c
-    quanta = np.ascontiguousarray(quanta, np.uint16)
     dev = [ctx.upload(p) for p in planes]
     factors = [(info.factor_x[c], info.factor_y[c]) for c in range(nc)]
     for denom in (2, 4, 8):

@@ -11,13 +11,12 @@ import _scaled_ref as S
 import jpeg_amd as J
 from _calls import COLORS, FUSED, SENTINEL, Out, c_layout, c_regions, c_views, plane_ptrs, strides, synthetic
 from _calls import ctx, torch  # noqa: F401  (the fixtures)
+from _tile import TILE_H, TILE_W, crop as _crop, random_region, reference as _reference
 from jpeg_amd import _lib
-from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 DENOMS = (1, 2, 4, 8)
-TILE_W, TILE_H = 128, 32
 
 # name -> (factors, cosited)
 LAYOUTS = {**{k: (v, 0) for k, v in FUSED.items()}, "411": ([(4, 1), (1, 1), (1, 1)], 0),
@@ -41,28 +40,8 @@ def _view_batch(ctx, torch, L, planes, dq, ntables, cosited, color, views, gap=0
     return [image.reshape(r[3], r[2], 3) for image, (_, r) in zip(out.images(), views)]
 
 
-def _reference(L, planes_host, quanta_host, i, denom, cosited):
-    """Image i of a batch at `denom`, whole, through the checker -> {color: uint8 [H', W', 3]}."""
-    factors = [(L.factor_x[p], L.factor_y[p]) for p in range(L.nplanes)]
-    planes = [pl[i] for pl in planes_host]
-    quanta = [quanta_host[i, L.qi[p]] for p in range(L.nplanes)]
-    size, scale = (L.width, L.height), (L.scale_x, L.scale_y)
-    if denom == 1:
-        _, rect = O.decode(planes, quanta, factors, size, cosited=bool(cosited), scale=scale)
-    else:
-        _, rect = S.interleaved_scaled(planes, quanta, factors, size, denom, bool(cosited), scale)
-    w, h = S.scaled_size(size, denom)
-    return {_lib.COLOR_RGB8: O.unpack_rgb8(rect, L.nplanes).reshape(h, w, 3),
-            _lib.COLOR_YCC8: O.unpack_ycc8(rect, L.nplanes).reshape(h, w, 3)}
-
-
-def _crop(image, r):
-    return image[r[1]:r[1] + r[3], r[0]:r[0] + r[2]]
-
-
 def _random_region(rng, W, H, max_w=200, max_h=100):
-    x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
-    return x, y, int(rng.integers(1, min(W - x, max_w) + 1)), int(rng.integers(1, min(H - y, max_h) + 1))
+    return random_region(rng, W, H, max_w, max_h)
 
 
 def _regions(rng, W, H, N):

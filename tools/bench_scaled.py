@@ -3,6 +3,7 @@
 against the full decode of the same inputs (jpeg_amd_decode_batch), alternating in one process.
 
     python tools/bench_scaled.py [--steps 200] [--warmup 20] [--rounds 5] [--ring 4] [--json PATH] [--cases A,B,C]
+                                 [--layout 420|y8] [--color rgb|ycc]
 
 Each round times `steps` calls of each path between two HIP events on the context's stream -- the three denominators, then
 the full decode -- over a ring of `ring` input sets (distinct coefficient buffers, together larger than the 256 MiB Infinity
@@ -10,6 +11,8 @@ Cache, as bench.py does); the report is the median per-call time over the rounds
   A  8192 x 8192 4:2:0 RGB, denom 2, 4, 8
   B  256 x 1920 x 1080 4:2:0 RGB, denom 2, 4, 8
   C  4096 x 4096 4:2:0 cosited (the fallback: k_idct_scaled planes + the staged interleave kernel), denom 2, 4, 8
+--layout y8 and --color ycc run the same cases with grey images and to YCbCr bytes: with the defaults, the four kinds of
+k_scaled_decode<N, planes, rgb> at each N.
 Kernel times: run it again under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_scaled.py --steps 20 --rounds 1`.
 """
 import argparse
@@ -28,10 +31,10 @@ from jpeg_amd import _lib  # noqa: E402
 DENOMS = (2, 4, 8)
 
 
-def _layout(w, h):
+def _layout(w, h, grey=False):
     L = _lib.Layout()
-    L.width, L.height, L.precision, L.nplanes, L.scale_x, L.scale_y = w, h, 8, 3, 2, 2
-    for p, f in enumerate((2, 1, 1)):
+    L.width, L.height, L.precision, L.nplanes, L.scale_x, L.scale_y = (w, h, 8, 1, 1, 1) if grey else (w, h, 8, 3, 2, 2)
+    for p, f in enumerate((1,) if grey else (2, 1, 1)):
         L.factor_x[p] = L.factor_y[p] = f
         L.qi[p] = min(p, 1)
     assert _lib.lib().jpeg_amd_layout_units(C.byref(L)) == 0
@@ -40,10 +43,11 @@ def _layout(w, h):
 
 def _case(torch, ctx, name, W, H, n, cosited, args):
     lib = _lib.lib()
-    L = _layout(W, H)
+    L = _layout(W, H, args.layout == "y8")
+    color = _lib.COLOR_YCC8 if args.color == "ycc" else _lib.COLOR_RGB8
     dev = ctx.torch_device
     gen = torch.Generator(device=dev).manual_seed(7)
-    sizes = [64 * L.units_x[p] * L.units_y[p] for p in range(3)]
+    sizes = [64 * L.units_x[p] * L.units_y[p] for p in range(L.nplanes)]
     ring = [[torch.randint(-256, 256, (n * s,), dtype=torch.int16, device=dev, generator=gen) for s in sizes]
             for _ in range(args.ring)]
     q = torch.randint(1, 8, (2 * 64,), dtype=torch.int16, device=dev, generator=gen)
@@ -58,13 +62,13 @@ def _case(torch, ctx, name, W, H, n, cosited, args):
 
         def fn(k):
             st = lib.jpeg_amd_decode_scaled_batch(ctx.handle, C.byref(L), n, ptrs[k % args.ring], strides, q.data_ptr(), 0, 2,
-                                                  cosited, _lib.COLOR_RGB8, denom, out.data_ptr(), 3 * w * h)
+                                                  cosited, color, denom, out.data_ptr(), 3 * w * h)
             assert st == 0, st
         return fn
 
     def whole(k):
         st = lib.jpeg_amd_decode_batch(ctx.handle, C.byref(L), n, ptrs[k % args.ring], strides, q.data_ptr(), 0, 2, cosited,
-                                       _lib.COLOR_RGB8, full.data_ptr(), full_stride)
+                                       color, full.data_ptr(), full_stride)
         assert st == 0, st
 
     def timed(fn):
@@ -84,7 +88,7 @@ def _case(torch, ctx, name, W, H, n, cosited, args):
             times[d].append(timed(scaled(d)))
         times[1].append(timed(whole))
     tf = statistics.median(times[1])
-    res = {"case": name, "size": [W, H], "n": n, "cosited": cosited, "t_full_us": round(tf, 2),
+    res = {"case": name, "layout": args.layout, "color": args.color, "size": [W, H], "n": n, "cosited": cosited, "t_full_us": round(tf, 2),
            "t_full_rounds": [round(t, 2) for t in times[1]], "denoms": {}}
     px = n * W * H
     for d in DENOMS:
@@ -110,6 +114,8 @@ def main():
     ap.add_argument("--ring", type=int, default=4)
     ap.add_argument("--cases", default="A,B,C")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--layout", choices=["420", "y8"], default="420")
+    ap.add_argument("--color", choices=["rgb", "ycc"], default="rgb")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():

@@ -1249,6 +1249,104 @@ int jpeg_amd_decompress_resized_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                int filter, const uint8_t *h_orient, uint8_t *d_pixels, size_t pixel_stride,
                                                jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
 
+/* ---- placed resample: the image in a window of the output canvas, a constant fill around it (letterbox) ------------------
+ *
+ * Every resample call stretches its source over the whole out_w x out_h target.  These calls keep the target as a CANVAS and
+ * resample image i into a WINDOW (x0, y0, ww, wh) of it -- jpeg_amd_region's x, y, width, height -- and write the call's
+ * FILL, three bytes, everywhere else: the letterbox of a detector, "pad to square", fill_values.  One launch still writes every
+ * image of the call, whatever their windows.
+ *
+ * THE CONTRACT, by reference only -- no arithmetic is defined here.  Canvas pixel (X, Y) is the pixel STORED at column
+ * flip ? out_w - 1 - X : X of row Y: the flip of "tensor output" mirrors the whole canvas, window position included, behind
+ * everything else.
+ *   Inside the window, x0 <= X < x0 + ww and y0 <= Y < y0 + wh, canvas pixel (X, Y) is, bit for bit, output pixel
+ *     (X - x0, Y - y0) of the filter's contract ("resized decode", "antialiased resample", "bicubic resample") for a target of
+ *     ww x wh, applied to the oriented image where the call names an orientation ("oriented resample").  ww, wh stand in the
+ *     place of out_w, out_h everywhere in that contract: in kx = (float)w' / (float)ww, in sx and rx, and in the tap limit --
+ *     16 (bicubic: 8) is judged on the window's factors, never the canvas's.
+ *   Outside the window the byte of channel c is fill[c].
+ *   "tensor output" applies behind this unchanged: a padded element is what that contract gives for the byte fill[c],
+ *     ((float)fill[c] - mean[c]) * scale[c] converted; a fill equal to the rounded mean gives about 0.
+ *   In the view and file calls the denominator is jpeg_amd_view_denom(source rectangle's (oriented) width, height, ww, wh):
+ *     chosen against the window, never the canvas.
+ *
+ * THE WINDOWS.  mode JPEG_AMD_PLACE_WINDOWS: the caller's, h_windows[i] for image i.  JPEG_AMD_PLACE_FIT: the largest window
+ * of the source's aspect ratio that the canvas holds; JPEG_AMD_PLACE_FIT_DOWN: the source's own size where the canvas holds it
+ * (nothing is enlarged), FIT otherwise; both at `anchor`.  jpeg_amd_place_window states the integers; the source size it
+ * takes is the ORIENTED image's (the resize calls), the oriented view rectangle's (the mixed calls) or the oriented source
+ * rectangle's of the full-size image (the file calls).
+ *
+ * THE CALLS.  Each takes the arguments of the *_oriented_* call it is named after (h_orient NULL allowed, as there) and, in
+ * front of the output pointer, `place` and h_windows_out: n_images entries that receive the window applied to each image, or
+ * NULL; the file calls write it as far as the files were judged, like h_views.  place == NULL is, bit for bit and status for
+ * status, the oriented call: the same records, the same kernels.  A placed call writes placed records for all its images and
+ * ONE launch of the placed kernels takes them (orientation 1: steps 3 and 3 w).  EINVAL, judged with the target (mode,
+ * anchor, missing windows) and per image behind its orientation (the window), the tap limit staying last: an unknown mode or
+ * anchor; mode WINDOWS with h_windows NULL and n_images > 0; a window with ww < 1 or wh < 1; a window not inside the canvas.
+ * Nothing is enqueued, and the device is not touched, for a call that is refused.
+ *
+ * There are no placed forms of the uniform *_batch decodes (the mixed calls serve them), of the region, scaled and view byte
+ * calls or of the encoders; no per-image output size, no border mode but the constant, no fill per image. */
+enum {
+    JPEG_AMD_PLACE_WINDOWS = 0,   /* h_windows given */
+    JPEG_AMD_PLACE_FIT = 1,       /* aspect-preserving, one side of the window equals the canvas's */
+    JPEG_AMD_PLACE_FIT_DOWN = 2   /* FIT, but never enlarging */
+};
+enum {
+    JPEG_AMD_ANCHOR_CENTRE = 0,
+    JPEG_AMD_ANCHOR_TOP_LEFT = 1
+};
+typedef struct {
+    int32_t mode;                       /* JPEG_AMD_PLACE_* */
+    int32_t anchor;                     /* JPEG_AMD_ANCHOR_*; positions the window in the FIT modes */
+    const jpeg_amd_region *h_windows;   /* n_images, mode WINDOWS only */
+    uint8_t fill[3];
+    uint8_t reserved;
+} jpeg_amd_placement;
+
+/* The window of the FIT modes for a source of src_w x src_h on a canvas of out_w x out_h, in integers.
+ *   FIT: if (int64)out_w * src_h <= (int64)out_h * src_w the width binds: ww = out_w and
+ *     wh = min(out_h, max(1, (2 * src_h * out_w + src_w) / (2 * src_w))) (the quotient rounded to nearest, in int64);
+ *     otherwise the same with the roles of the two axes swapped.
+ *   FIT_DOWN: ww = src_w, wh = src_h if src_w <= out_w and src_h <= out_h; FIT otherwise.
+ *   CENTRE: x0 = (out_w - ww) / 2, y0 = (out_h - wh) / 2.  TOP_LEFT: x0 = y0 = 0.
+ * EINVAL: a mode other than FIT and FIT_DOWN, an unknown anchor, a size below 1, a canvas side above 2^30, a null `window`.
+ * Host only, pure. */
+int jpeg_amd_place_window(int mode, int anchor, int32_t src_w, int32_t src_h, int32_t out_w, int32_t out_h,
+                          jpeg_amd_region *window);
+
+int jpeg_amd_resize_placed_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                 const uint8_t *h_orient, const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out,
+                                 uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_resize_placed_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                        const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out, void *d_dst,
+                                        size_t dst_stride);
+int jpeg_amd_decode_resized_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                         int filter, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                         jpeg_amd_region *h_windows_out, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                        const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                        jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_tensor_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                            int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                            const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h,
+                                            int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                            const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                            jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride,
+                                            jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
+int jpeg_amd_decompress_resized_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                             int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                             const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h,
+                                             int filter, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                             jpeg_amd_region *h_windows_out, uint8_t *d_pixels, size_t pixel_stride,
+                                             jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
+
 #ifdef __cplusplus
 }
 #endif

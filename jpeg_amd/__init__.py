@@ -11,13 +11,13 @@ from .api import (  # noqa: F401
     compress_tensors, compression_quanta, decode_crops_resized, decode_crops_tensor, decode_crops_tensor_mixed, decode_regions, decode_resized,
     decode_resized_mixed, decode_scaled, decode_tensors, decode_tensors_mixed, decode_views, decode_views_mixed, decompress_resized, decompress_tensors,
     default_context,
-    encode_tensors, exif_orientation, inspect, orient_region, reduce, reduce_layout, region_window, resize, resize_tensor, scaled_size, tensor_pixels, tensor_source, tensor_spec,
+    encode_tensors, exif_orientation, inspect, orient_region, place_window, reduce, reduce_layout, region_window, resize, resize_tensor, scaled_size, tensor_pixels, tensor_source, tensor_spec,
     transform, transform_quanta, view_denom, view_of_source, view_window,
 )
 
 __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangular",
            "Scan", "Spectral", "JpegAmdError", "compress_tensors", "compression_quanta", "decode_crops_resized", "decode_crops_tensor", "decode_crops_tensor_mixed",
            "decode_regions", "decode_resized", "decode_resized_mixed", "decode_scaled", "decode_tensors", "decode_tensors_mixed",
-           "decode_views", "decode_views_mixed", "decompress_resized", "decompress_tensors", "default_context", "encode_tensors", "exif_orientation", "inspect", "orient_region", "reduce", "reduce_layout",
+           "decode_views", "decode_views_mixed", "decompress_resized", "decompress_tensors", "default_context", "encode_tensors", "exif_orientation", "inspect", "orient_region", "place_window", "reduce", "reduce_layout",
            "region_window", "resize", "resize_tensor", "scaled_size", "tensor_pixels", "tensor_source", "tensor_spec", "transform", "transform_quanta", "view_denom",
            "view_of_source", "view_window"]

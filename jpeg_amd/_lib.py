@@ -180,12 +180,31 @@ SIGNATURES = {
                                                             C.c_int, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
     "jpeg_amd_decompress_resized_oriented_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
                                                              C.c_int, _p, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_place_window": (C.c_int, [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]),
+    "jpeg_amd_resize_placed_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, _p, _p,
+                                               C.c_size_t]),
+    "jpeg_amd_resize_placed_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, _p, _p,
+                                                      _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_resized_placed_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                       _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_placed_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                      _p, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_tensor_placed_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
+                                                          C.c_int, _p, _p, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_decompress_resized_placed_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
+                                                           C.c_int, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
 }
 
 
 class Region(C.Structure):
     """struct jpeg_amd_region"""
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class Placement(C.Structure):
+    """struct jpeg_amd_placement"""
+    _fields_ = [("mode", C.c_int32), ("anchor", C.c_int32), ("h_windows", C.c_void_p), ("fill", C.c_uint8 * 3),
+                ("reserved", C.c_uint8)]
 
 
 class View(C.Structure):
@@ -224,6 +243,8 @@ U8 = 3                                  # JPEG_AMD_U8: tensor sources only
 TENSOR_HWC, TENSOR_CHW = 0, 1           # JPEG_AMD_TENSOR_HWC ...
 FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
 FILTER_BICUBIC = 3                        # JPEG_AMD_FILTER_BICUBIC (2 is no filter)
+PLACE_WINDOWS, PLACE_FIT, PLACE_FIT_DOWN = 0, 1, 2   # JPEG_AMD_PLACE_*
+ANCHOR_CENTRE, ANCHOR_TOP_LEFT = 0, 1               # JPEG_AMD_ANCHOR_*
 ORIENT_EXIF = 0                         # JPEG_AMD_ORIENT_EXIF (the file calls); JPEG_AMD_ORIENT_1 .. _8 are 1 .. 8
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V

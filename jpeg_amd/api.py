@@ -554,6 +554,60 @@ def _orientations(orientations, n: int, exif: bool = False):
     return (C.c_uint8 * max(n, 1))(*[int(o) for o in vals])
 
 
+_PLACE_MODES = {"fit": _lib.PLACE_FIT, "fit-down": _lib.PLACE_FIT_DOWN, "fit_down": _lib.PLACE_FIT_DOWN}
+_ANCHORS = {"centre": _lib.ANCHOR_CENTRE, "center": _lib.ANCHOR_CENTRE, "top-left": _lib.ANCHOR_TOP_LEFT,
+            "top_left": _lib.ANCHOR_TOP_LEFT}
+
+
+def _anchor(anchor) -> int:
+    if isinstance(anchor, str) and anchor.lower() in _ANCHORS:
+        return _ANCHORS[anchor.lower()]
+    raise ValueError('anchor: "centre" or "top-left"')
+
+
+def place_window(mode, src_size, out_size, anchor="centre") -> Tuple[int, int, int, int]:
+    """The window (x, y, width, height) that place="fit" / "fit-down" gives a source of src_size (w, h) on a canvas of out_size
+    (Wt, Ht) (jpeg_amd_place_window; include/jpeg_amd.h, "placed resample"): aspect-preserving, "fit-down" never enlarging."""
+    if not (isinstance(mode, str) and mode.lower() in _PLACE_MODES):
+        raise ValueError('place_window: mode "fit" or "fit-down"')
+    r = _lib.Region()
+    _lib.check(_lib.lib().jpeg_amd_place_window(_PLACE_MODES[mode.lower()], _anchor(anchor), int(src_size[0]), int(src_size[1]),
+                                                int(out_size[0]), int(out_size[1]), C.byref(r)), "jpeg_amd_place_window")
+    return r.x, r.y, r.width, r.height
+
+
+def _placement(place, anchor, fill, n: int):
+    """place=, anchor=, fill= of the resample calls -> (struct jpeg_amd_placement, room for the applied windows, keep), or
+    (None, None, None) for place=None (today's entry point).  place: "fit", "fit-down" or one (x, y, width, height) per image."""
+    if place is None:
+        return None, None, None
+    p = _lib.Placement()
+    p.anchor = _anchor(anchor)
+    keep = None
+    if isinstance(place, str):
+        if place.lower() not in _PLACE_MODES:
+            raise ValueError('place: None, "fit", "fit-down" or one (x, y, width, height) per image')
+        p.mode = _PLACE_MODES[place.lower()]
+    else:
+        w = np.asarray(place, np.int64).reshape(-1, 4)
+        if w.shape[0] != n:
+            raise ValueError("place: one (x, y, width, height) per image")
+        keep = (_lib.Region * max(n, 1))()
+        for i, r in enumerate(w.tolist()):
+            keep[i].x, keep[i].y, keep[i].width, keep[i].height = r
+        p.mode = _lib.PLACE_WINDOWS
+        p.h_windows = C.cast(keep, C.c_void_p)
+    f = [int(v) for v in fill]
+    if len(f) != 3 or min(f) < 0 or max(f) > 255:
+        raise ValueError("fill: three bytes")
+    p.fill[0], p.fill[1], p.fill[2] = f
+    return p, (_lib.Region * max(n, 1))(), keep
+
+
+def _windows_array(h_windows, n) -> np.ndarray:
+    return np.array([(r.x, r.y, r.width, r.height) for r in h_windows[:n]], np.int32).reshape(n, 4)
+
+
 def _decode_spectral(data: np.ndarray, scans: int = 0):
     info = inspect(data)
     planes = [np.empty((info.units_y[c], info.units_x[c], 64), np.int16) for c in range(info.ncomponents)]
@@ -871,19 +925,29 @@ def _pack_images(ctx: Context, images):
     return src, src_stride, extents
 
 
-def resize(ctx: Context, images, out_size, filter: str = "bilinear", orientations=None):
+def resize(ctx: Context, images, out_size, filter: str = "bilinear", orientations=None, place=None, anchor="centre", fill=(0, 0, 0)):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
     (jpeg_amd_resize_filter_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
     the target on an axis), or with filter="bicubic" through the bicubic one (no image more than 8 times; decode_resized says
     which filter that is).  The images are packed into one allocation first (torch copies).  orientations: per image an EXIF
     orientation 1 .. 8 in which the image is read (jpeg_amd_resize_oriented_batch; include/jpeg_amd.h, "oriented resample").
+    place / anchor / fill: the image in a window of the out_size canvas and the
+    fill's three bytes around it (include/jpeg_amd.h, "placed resample"): place "fit" or "fit-down" (aspect-preserving, at
+    `anchor` "centre" or "top-left") or one window (x, y, width, height) per image; with it the windows applied come back as an
+    extra int32 [n, 4] item.
     Returns uint8 [n, Ht, Wt, 3]."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
     h_orient = _orientations(orientations, n)
+    placement, h_windows, keep = _placement(place, anchor, fill, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if placement is not None:
+        _lib.check(_lib.lib().jpeg_amd_resize_placed_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code, h_orient,
+                                                           C.byref(placement), h_windows, out.data_ptr(), stride),
+                   "jpeg_amd_resize_placed_batch", ctx.handle)
+        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
                                                            out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
@@ -1002,16 +1066,23 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
 
 
 def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear",
-                         orientations=None):
+                         orientations=None, place=None, anchor="centre", fill=(0, 0, 0)):
     """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_filter_mixed);
     arguments as decode_views_mixed, `filter` as in decode_resized.  orientations: per image an EXIF orientation 1 .. 8 in which
     its view's pixels are read (jpeg_amd_decode_resized_oriented_mixed); the views stay rectangles of the STORED scaled
-    images.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    images.  place / anchor / fill: as in resize (jpeg_amd_decode_resized_placed_mixed); "fit" fits the oriented view.
+    Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     h_orient = _orientations(orientations, n)
+    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if placement is not None:
+        _lib.check(_lib.lib().jpeg_amd_decode_resized_placed_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                   ht, code, h_orient, C.byref(placement), h_windows, out.data_ptr(),
+                                                                   stride), "jpeg_amd_decode_resized_placed_mixed", ctx.handle)
+        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
                                                                    ht, code, out.data_ptr(), stride),
@@ -1024,16 +1095,25 @@ def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, co
 
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                         cosite: bool = False, filter: str = "bilinear", orientations=None):
+                         cosite: bool = False, filter: str = "bilinear", orientations=None, place=None, anchor="centre",
+                         fill=(0, 0, 0)):
     """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
     as decode_views_mixed, then as decode_tensors, `filter` ("bilinear" | "antialias" | "bicubic") included.  orientations: as in decode_resized_mixed
     (jpeg_amd_decode_tensor_oriented_mixed); a flip mirrors the output after the orientation.
+    place / anchor / fill: as in resize (jpeg_amd_decode_tensor_placed_mixed); a flip mirrors the whole canvas.
     Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     h_orient = _orientations(orientations, n)
+    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if placement is not None:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_placed_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                  ht, code, C.byref(spec), h_flip, h_orient, C.byref(placement),
+                                                                  h_windows, out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_placed_mixed", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec), _windows_array(h_windows, n)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
                                                                   ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
@@ -1047,12 +1127,15 @@ def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.Te
 
 
 def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                              cosite: bool = False, filter: str = "bilinear", orientations=None):
+                              cosite: bool = False, filter: str = "bilinear", orientations=None, place=None, anchor="centre",
+                              fill=(0, 0, 0)):
     """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
     full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
     size -- through decode_tensors_mixed, with its `filter`.  orientations: per image an EXIF orientation 1 .. 8; the rectangles are then
     rectangles of the ORIENTED images: the denominator is chosen for the oriented rectangle and the view is that of the stored
-    rectangle orient_region maps it to.  Returns (tensor, the views as int32 [n, 5]: stored scaled coordinates)."""
+    rectangle orient_region maps it to.  place / anchor / fill: as in resize; "fit" fits the (oriented) rectangle, and the
+    denominator is chosen against the window, not the canvas.
+    Returns (tensor, the views as int32 [n, 5]: stored scaled coordinates), and with `place` the windows as int32 [n, 4]."""
     spectrals = list(spectrals)
     regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
     if regs.shape[0] != len(spectrals):
@@ -1061,6 +1144,19 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
     if orientations is not None and len(orientations) != len(spectrals):
         raise ValueError("orientations: one value in 1 .. 8 per image")
     views = np.empty((len(spectrals), 5), np.int32)
+    if place is not None:
+        if isinstance(place, str):
+            place = [place_window(place, regs[i, 2:], out_size, anchor) for i in range(len(spectrals))]
+        windows = np.asarray(place, np.int64).reshape(-1, 4)
+        if windows.shape[0] != len(spectrals):
+            raise ValueError("place: one (x, y, width, height) per image")
+        for i, s in enumerate(spectrals):
+            denom = view_denom(regs[i, 2:], windows[i, 2:])
+            stored = regs[i].tolist() if orientations is None else orient_region(orientations[i], s.size, regs[i].tolist())
+            views[i] = (denom,) + view_of_source(s.size, denom, stored)
+        out, applied = decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
+                                            orientations=orientations, place=windows, anchor=anchor, fill=fill)
+        return out, views, applied
     for i, s in enumerate(spectrals):
         if orientations is None:
             views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
@@ -1094,7 +1190,8 @@ def _views_array(h_views, n) -> np.ndarray:
 
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
-                       cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None):
+                       cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None, place=None,
+                       anchor="centre", fill=(0, 0, 0)):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
@@ -1108,11 +1205,25 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     "oriented resample").  With it, source_regions are rectangles of the ORIENTED images -- the images a viewer shows -- while the
     views that come back stay in stored scaled coordinates.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5] of (denom, x, y, width, height), the files'
-    frame infos), and with `orientation` given a fourth item, the orientations applied as int32 [n]."""
+    frame infos), and with `orientation` given a fourth item, the orientations applied as int32 [n].
+    place / anchor / fill: as in resize (jpeg_amd_decompress_tensor_placed_mixed); "fit" fits the (oriented) source rectangle,
+    and the denominator is chosen against the window; with `place` the windows applied come back as the last item."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
     h_orient = _orientations(orientation, n, exif=True)
+    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if placement is not None:
+        applied = (C.c_int32 * max(n, 1))()
+        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_placed_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                      color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
+                                                                      C.byref(placement), h_windows, out.data_ptr(), stride, infos,
+                                                                      h_views, applied),
+                   "jpeg_amd_decompress_tensor_placed_mixed", ctx.handle)
+        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
+        if h_orient is not None:
+            res += (np.array(applied[:n], np.int32),)
+        return res + (_windows_array(h_windows, n),)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
                                                                regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
@@ -1127,14 +1238,22 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
-                       filter: str = "bilinear", threads: int = 0, orientation=None):
+                       filter: str = "bilinear", threads: int = 0, orientation=None, place=None, anchor="centre", fill=(0, 0, 0)):
     """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
     (Wt, Ht) as bytes by `filter`; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
+    place / anchor / fill: as there (jpeg_amd_decompress_resized_placed_mixed), the windows as a second item.
     Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
     h_orient = _orientations(orientation, n, exif=True)
+    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    if placement is not None:
+        _lib.check(_lib.lib().jpeg_amd_decompress_resized_placed_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                       color.code, regions, wt, ht, code, h_orient, C.byref(placement),
+                                                                       h_windows, out.data_ptr(), stride, infos, h_views, None),
+                   "jpeg_amd_decompress_resized_placed_mixed", ctx.handle)
+        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_decompress_resized_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
                                                                 regions, wt, ht, code, out.data_ptr(), stride, infos, h_views),
@@ -1147,16 +1266,25 @@ def decompress_resized(ctx: Context, sources, out_size, source_regions=None, col
     return out.view(n, ht, wt, 3)
 
 
-def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None):
+def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None,
+                  place=None, anchor="centre", fill=(0, 0, 0)):
     """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
     [n, Ht, Wt, 3] of spec's dtype, in one launch.  orientations: as in resize (jpeg_amd_resize_oriented_tensor_batch); a flip
-    mirrors the output after the orientation."""
+    mirrors the output after the orientation.  place / anchor / fill: as in resize (jpeg_amd_resize_placed_tensor_batch); a
+    padded element is the fill byte through `spec`, and a flip mirrors the whole canvas, window position included."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
     h_orient = _orientations(orientations, n)
+    placement, h_windows, keep = _placement(place, anchor, fill, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if placement is not None:
+        _lib.check(_lib.lib().jpeg_amd_resize_placed_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                                  C.byref(spec), h_flip, h_orient, C.byref(placement), h_windows,
+                                                                  out.data_ptr(), stride),
+                   "jpeg_amd_resize_placed_tensor_batch", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec), _windows_array(h_windows, n)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
                                                                   C.byref(spec), h_flip, out.data_ptr(), stride),

@@ -48,8 +48,8 @@ WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "
                 "kernels_transform.hip": "k_spectral_transform",
                 "kernels_tile.hip": ("k_region_decode", "k_scaled_decode", "k_view_decode"),
                 "kernels_reduce.hip": "k_spectral_reduce",
-                # the oriented bilinear kernels, and _bytes and _tensor of the filters with tables
-                "kernels_resample.hip": ("k_resize_oriented_bytes", "k_resize_tensorILb1E", "k_tables_")}
+                # the oriented and the placed bilinear kernels, and _bytes and _tensor of the filters with tables (placed included)
+                "kernels_resample.hip": ("k_resize_oriented_bytes", "k_resize_tensorILb1E", "k_resize_placed_", "k_tables_")}
 
 
 def check_no_scratch(src: str, remarks: str, fragment: str, strict: bool = True) -> None:

@@ -95,10 +95,17 @@ __device__ __forceinline__ uint32_t antialias_byte(float v) { return (uint32_t)(
 // Oriented (Record = OrientedAntialiasRecord, "oriented resample"): w and h are the ORIENTED image's, offset its first byte,
 // and the byte of channel c of its pixel (x', y') lies at offset + x' step_x + y' step_y + c, the steps signed: the
 // horizontal pass runs along oriented x, and the vertical pass never sees the difference.
+// Placed (Record = PlacedAntialiasRecord, "placed resample", oriented as well): canvas column xs = flip ? out_w - 1 - x : x takes
+// the taps of xs - x0 where that lies in [0, ww) and is padded otherwise (lo = -1, count 0: it reads nothing and adds nothing);
+// rows likewise.  The vertical footprint runs from the lo of the tile's first WINDOW row to lo + count of its last one -- a
+// padded row has no lo -- and is empty for a tile without a window pixel, which then reads no source byte; the footprint
+// follows from the record and the tile alone, so every work-item of the workgroup makes the same trips and meets the same
+// barriers.  A padded pixel's bytes in the byte tile are `fill`'s (channel c in bits 8 c ...), in front of the sink.
 template <typename Filter, typename Record, typename Sink>
-__device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Record *records, bool flips, Sink sink)
+__device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Record *records, bool flips, Sink sink, uint32_t fill = 0u)
 {
-    constexpr bool Oriented = std::is_same<Record, OrientedAntialiasRecord>::value;
+    constexpr bool Placed = std::is_same<Record, PlacedAntialiasRecord>::value;
+    constexpr bool Oriented = Placed || std::is_same<Record, OrientedAntialiasRecord>::value;
     using Step = typename std::conditional<Oriented, int64_t, size_t>::type;   // (the additions wrap to the same address)
     __shared__ int tlo[kTileW + kTileH], tcount[kTileW + kTileH];   // columns, then rows
     __shared__ float tw[kTileW + kTileH][kAntialiasMaxTaps];
@@ -112,19 +119,43 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Reco
     const bool flip = flips && r.flip;
     if (t < kTileW) {
         int lo = 0, count = 0;
-        if (px0 + t < a.out_w) antialias_taps<Filter>(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
+        if constexpr (Placed) {
+            const int xs = (flip ? a.out_w - 1 - (px0 + t) : px0 + t) - r.x0;   // (past the output: padded, and reaches no sink)
+            if (xs >= 0 && xs < r.ww) antialias_taps<Filter>(xs, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
+            else lo = -1;
+        } else {
+            if (px0 + t < a.out_w) antialias_taps<Filter>(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.sx, r.rx, r.w, lo, count, tw[t]);
+        }
         tlo[t] = lo; tcount[t] = count;
     } else if (t < kTileW + kTileH) {
         int lo = 0, count = 0;
-        if (py0 + (t - kTileW) < a.out_h) antialias_taps<Filter>(py0 + (t - kTileW), r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
+        if constexpr (Placed) {
+            const int ys = py0 + (t - kTileW) - r.y0;
+            if (ys >= 0 && ys < r.wh) antialias_taps<Filter>(ys, r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
+            else lo = -1;
+        } else {
+            if (py0 + (t - kTileW) < a.out_h) antialias_taps<Filter>(py0 + (t - kTileW), r.ky, r.sy, r.ry, r.h, lo, count, tw[t]);
+        }
         tlo[t] = lo; tcount[t] = count;
     }
     __syncthreads();
 
     const int col = t % kTileW, wave = t / kTileW;
     const int rows = min(kTileH, a.out_h - py0);   // of the tile, >= 1
-    const int ybeg = tlo[kTileW], yend = tlo[kTileW + rows - 1] + tcount[kTileW + rows - 1];
+    int first = 0, last = rows - 1;                // the tile's rows that bound the footprint
+    int wrow0 = 0, wrow1 = kTileH;                 // Placed: the tile's window rows, [wrow0, wrow1)
+    bool any = true;
+    if constexpr (Placed) {
+        wrow0 = max(py0, r.y0) - py0;
+        wrow1 = min(py0 + rows, r.y0 + r.wh) - py0;
+        const int c0 = flip ? a.out_w - kTileW - px0 : px0;   // the canvas columns of the tile: [c0, c0 + kTileW)
+        any = wrow0 < wrow1 && max(c0, r.x0) < min(c0 + kTileW, r.x0 + r.ww);
+        first = any ? wrow0 : 0;
+        last = any ? wrow1 - 1 : 0;
+    }
+    const int ybeg = any ? tlo[kTileW + first] : 0, yend = any ? tlo[kTileW + last] + tcount[kTileW + last] : 0;
     const int xcount = tcount[col];
+    const bool cpad = Placed && tlo[col] < 0;
     Step pixel_bytes = 3, row_bytes = (Step)3 * (uint32_t)r.w;
     if constexpr (Oriented) {
         pixel_bytes = r.step_x;
@@ -178,7 +209,14 @@ __device__ __forceinline__ void antialias_walk(const ResampleArgs &a, const Reco
 #pragma unroll
     for (int i = 0; i < kOwnRows; ++i)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) tile[(kOwnRows * wave + i) * (3 * kTileW) + 3 * col + c] = (uint8_t)antialias_byte(acc[i][c]);
+        for (int c = 0; c < 3; ++c) {
+            uint32_t b = antialias_byte(acc[i][c]);
+            if constexpr (Placed) {   // a select, not a branch: the row's verdict is the wave's, the column's the work-item's
+                const bool pad = cpad || kOwnRows * wave + i < wrow0 || kOwnRows * wave + i >= wrow1;
+                b = pad ? (fill >> (8 * c)) & 0xffu : b;
+            }
+            tile[(kOwnRows * wave + i) * (3 * kTileW) + 3 * col + c] = (uint8_t)b;
+        }
     __syncthreads();
 
     const int ly = t / kLanesX, lx = t - ly * kLanesX;

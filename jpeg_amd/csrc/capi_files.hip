@@ -45,6 +45,9 @@ struct FilesDecode : FileBatch {
     const jpeg_amd_tensor_spec *spec;
     const uint8_t *h_flip;
     std::vector<uint8_t> orient;               // per file, what the call applies; empty: the call names no orientations
+    bool placed = false;                       // "placed resample": `windows` per file, pass 0's, go to the mixed call as they are
+    std::vector<jpeg_amd_region> windows;
+    uint8_t fill[3] = {0, 0, 0};
     void *d_dst;
     size_t dst_stride, elem_bytes;
     std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
@@ -126,12 +129,15 @@ int FilesDecode::submit(int k)
     for (int i = 0; i < ch.m; ++i) views[(size_t)i] = files[(size_t)(ch.i0 + i)].view;
     void *d_out = static_cast<char *>(d_dst) + (size_t)ch.i0 * dst_stride * elem_bytes;
     const uint8_t *h_orient = orient.empty() ? nullptr : orient.data() + ch.i0;   // (nullptr: the calls without orientations)
+    const jpeg_amd_placement here{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, placed ? windows.data() + ch.i0 : nullptr,
+                                  {fill[0], fill[1], fill[2]}, 0};
+    const jpeg_amd_placement *place = placed ? &here : nullptr;
     if (tensor)
-        JA_TRY(jpeg_amd_decode_tensor_oriented_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
-                                                     h_flip ? h_flip + ch.i0 : nullptr, h_orient, d_out, dst_stride));
+        JA_TRY(jpeg_amd_decode_tensor_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
+                                                   h_flip ? h_flip + ch.i0 : nullptr, h_orient, place, nullptr, d_out, dst_stride));
     else
-        JA_TRY(jpeg_amd_decode_resized_oriented_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
-                                                      h_orient, static_cast<uint8_t *>(d_out), dst_stride));
+        JA_TRY(jpeg_amd_decode_resized_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
+                                                    h_orient, place, nullptr, static_cast<uint8_t *>(d_out), dst_stride));
     JA_HIP(ctx, hipEventRecord(ctx->file_decoded[slot], ctx->stream));
     JA_HIP(ctx, hipEventRecord(ctx->file_done[slot], ctx->stream));     // the tensor stays where it is: done when the kernels are
     return JPEG_AMD_OK;
@@ -149,8 +155,9 @@ int FilesDecode::run()
 
 int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads, int cosited,
                      jpeg_amd_color color, const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter, bool tensor,
-                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, void *d_dst, size_t dst_stride,
-                     jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
+                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                     jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                     int32_t *h_orient_out)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
@@ -161,6 +168,11 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     d.dst_stride = dst_stride;
     d.files.resize((size_t)n_images);
     if (h_orient) d.orient.assign((size_t)n_images, 1);   // (1 behind a refused file: the mixed call's judgement stops in front of it)
+    if (place) {
+        d.placed = true;
+        d.windows.assign((size_t)n_images, jpeg_amd_region{0, 0, 0, 0});
+        for (int c = 0; c < 3; ++c) d.fill[c] = place->fill[c];
+    }
     // ---- pass 0: the headers, file by file; the first file that is refused ends it
     int bad = n_images, bad_status = JPEG_AMD_OK;
     std::vector<jpeg_amd_image> images((size_t)n_images);
@@ -190,12 +202,22 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                 if (h_orient) d.orient[(size_t)i] = (uint8_t)o;
                 if (h_orient_out) h_orient_out[i] = o;
                 // the data-loader call's view (decode_crops_tensor_mixed): the cheapest denominator, then the rectangle at it
-                f.view.denom = jpeg_amd_view_denom(seen.width, seen.height, out_w, out_h);
-                st = jpeg_amd_view_of_source(&f.layout, f.view.denom, &source, &f.view.region);
+                // placed: the file's window, of the oriented rectangle's size; the denominator is chosen against it
+                jpeg_amd_region want{0, 0, out_w, out_h};
+                if (place) {
+                    st = check_placement(*place, n_images);
+                    if (st == JPEG_AMD_OK) st = placed_window(*place, i, seen.width, seen.height, out_w, out_h, &want);
+                }
+                if (st == JPEG_AMD_OK) {
+                    if (place) d.windows[(size_t)i] = want;
+                    f.view.denom = jpeg_amd_view_denom(seen.width, seen.height, want.width, want.height);
+                    st = jpeg_amd_view_of_source(&f.layout, f.view.denom, &source, &f.view.region);
+                }
             }
         }
         if (st != JPEG_AMD_OK) { bad = i; bad_status = st; break; }
         if (h_views) h_views[i] = f.view;
+        if (place && h_windows_out) h_windows_out[i] = d.windows[(size_t)i];
         views[(size_t)i] = f.view;
         // (the planes do not exist yet: what the mixed call judges of a pointer is that it is there)
         jpeg_amd_image &im = images[(size_t)i];
@@ -207,8 +229,9 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     }
     // ... then what the mixed call refuses of the files in front of that one, the target included; the tap limit last
     int taps = JPEG_AMD_OK;
+    const jpeg_amd_placement judged{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {d.fill[0], d.fill[1], d.fill[2]}, 0};
     JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
-                                 d.orient.empty() ? nullptr : d.orient.data(), d_dst, dst_stride, &taps));
+                                 d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
@@ -285,7 +308,7 @@ int jpeg_amd_decompress_tensor_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_j
                                      size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, nullptr, d_dst, dst_stride, h_info, h_views, nullptr);
+                            h_flip, nullptr, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, nullptr);
 }
 JA_NOTHROW_TAIL
 
@@ -295,7 +318,7 @@ int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_
                                       jpeg_amd_view *h_views)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, nullptr);
+                            nullptr, nullptr, nullptr, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, nullptr);
 }
 JA_NOTHROW_TAIL
 
@@ -307,7 +330,7 @@ int jpeg_amd_decompress_tensor_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *
                                               jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, h_orient, d_dst, dst_stride, h_info, h_views, h_orient_out);
+                            h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out);
 }
 JA_NOTHROW_TAIL
 
@@ -318,6 +341,31 @@ int jpeg_amd_decompress_resized_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                int32_t *h_orient_out)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, h_orient, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
+                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
+}
+JA_NOTHROW_TAIL
+
+// The two file calls with a placement ("placed resample"): the oriented calls above are these with place == nullptr.
+int jpeg_amd_decompress_tensor_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                            int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
+                                            int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                            const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                            jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info,
+                                            jpeg_amd_view *h_views, int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
+                            h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views, h_orient_out);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decompress_resized_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                             int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
+                                             int32_t out_w, int32_t out_h, int filter, const uint8_t *h_orient,
+                                             const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out, uint8_t *d_pixels,
+                                             size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                             int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
+                            nullptr, nullptr, h_orient, place, h_windows_out, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
 }
 JA_NOTHROW_TAIL

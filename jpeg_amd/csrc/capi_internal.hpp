@@ -125,10 +125,33 @@ int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
 // context, for the file calls, which judge a call before its planes exist (the images' pointers only have to be non-null):
 // of the first `judged` images of a call of n_images, in the mixed call's order; *taps: with judged == n_images the verdict on
 // the antialiasing filter's tap limit, which that call gives last (capi_view.hip).  h_orient: as in the *_oriented_mixed calls
-// (n_images values, or nullptr).
+// (n_images values, or nullptr); place: as in the *_placed_mixed calls (or nullptr).
 int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
-                          bool tensor, const uint8_t *h_orient, void *d_dst, size_t dst_stride, int *taps);
+                          bool tensor, const uint8_t *h_orient, const jpeg_amd_placement *place, void *d_dst, size_t dst_stride,
+                          int *taps);
+// "placed resample": what a placed call refuses of its placement as a whole, and of one image's window on its canvas.
+inline int check_placement(const jpeg_amd_placement &p, int n_images)
+{
+    if (p.mode != JPEG_AMD_PLACE_WINDOWS && p.mode != JPEG_AMD_PLACE_FIT && p.mode != JPEG_AMD_PLACE_FIT_DOWN) return JPEG_AMD_EINVAL;
+    if (p.anchor != JPEG_AMD_ANCHOR_CENTRE && p.anchor != JPEG_AMD_ANCHOR_TOP_LEFT) return JPEG_AMD_EINVAL;
+    if (p.mode == JPEG_AMD_PLACE_WINDOWS && !p.h_windows && n_images > 0) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+inline int check_window(const jpeg_amd_region &w, int32_t out_w, int32_t out_h)
+{
+    if (w.width < 1 || w.height < 1 || w.x < 0 || w.y < 0) return JPEG_AMD_EINVAL;
+    if (w.x > out_w - w.width || w.y > out_h - w.height) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+// Image i's window under a checked placement, for a source of src_w x src_h as the user sees it (oriented), checked.
+inline int placed_window(const jpeg_amd_placement &p, int i, int32_t src_w, int32_t src_h, int32_t out_w, int32_t out_h,
+                         jpeg_amd_region *w)
+{
+    if (p.mode == JPEG_AMD_PLACE_WINDOWS) *w = p.h_windows[i];
+    else if (const int st = jpeg_amd_place_window(p.mode, p.anchor, src_w, src_h, out_w, out_h, w)) return st;
+    return check_window(*w, out_w, out_h);
+}
 
 // ---- the batch file paths: the staging, and what the two decode pipelines share (capi_file.hip) ---------------------------------
 // Both decode pipelines (files of one geometry to pixels, capi_file.hip; files of mixed sizes to one tensor, capi_files.hip) are

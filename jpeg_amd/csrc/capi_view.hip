@@ -520,6 +520,9 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
 // h_orient ("oriented resample"): per image an orientation in 1 .. 8, or nullptr.  A call in which it is nullptr or every
 // value is 1 is today's call -- today's records, today's kernels; in any other, check() sets `oriented`, every record is the
 // oriented one (orientation 1 included: base = offset, steps 3 and 3 w) and ONE launch of the oriented kernels takes them all.
+// place ("placed resample"): the call's placement, or nullptr, which is the oriented call -- its records, its kernels.  With
+// one, check() judges it with the target, window(i) judges and keeps image i's window (behind its orientation), every record
+// is the placed one of its filter, its scale factors the window's, and ONE launch of the placed kernels takes them all.
 struct ResampleTarget {
     int32_t out_w, out_h;
     int filter;              // JPEG_AMD_FILTER_*
@@ -529,8 +532,11 @@ struct ResampleTarget {
     void *d_dst;
     size_t stride;           // between images, in elements
     const uint8_t *h_orient = nullptr;   // per image, or nullptr: every image as it is stored
+    const jpeg_amd_placement *place = nullptr;
+    jpeg_amd_region *h_windows_out = nullptr;   // per image, or nullptr: window(i) writes it
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
     bool oriented = false;   // check() sets it
+    std::vector<jpeg_amd_region> windows;   // of a placed call, per image: check() sizes it, window(i) fills it
 
     bool bicubic() const { return filter == JPEG_AMD_FILTER_BICUBIC; }
     bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS || bicubic(); }   // the kernels with tables: their records
@@ -540,8 +546,22 @@ struct ResampleTarget {
         oriented = false;   // (not a verdict: which records the call writes)
         for (int i = 0; h_orient && i < n_images; ++i) oriented = oriented || h_orient[i] != 1;
         if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
-        return tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
-                      : check_resize_target(n_images, out_w, out_h, d_dst, stride);
+        JA_TRY(tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
+                      : check_resize_target(n_images, out_w, out_h, d_dst, stride));
+        if (!place) return JPEG_AMD_OK;
+        JA_TRY(check_placement(*place, n_images));
+        windows.assign((size_t)std::max(n_images, 0), jpeg_amd_region{0, 0, 0, 0});
+        return JPEG_AMD_OK;
+    }
+    int orientation(int i) const { return place ? (h_orient ? h_orient[i] : 1) : oriented ? h_orient[i] : 1; }
+    // Image i's window, w x h as it is STORED: judged behind its orientation (and behind check()), in front of record(i).
+    int window(int i, int32_t w, int32_t h)
+    {
+        if (!place) return JPEG_AMD_OK;
+        const OrientedSource s = oriented_source(orientation(i), 0, w, h);
+        JA_TRY(placed_window(*place, i, s.w, s.h, out_w, out_h, &windows[(size_t)i]));
+        if (h_windows_out) h_windows_out[i] = windows[(size_t)i];
+        return JPEG_AMD_OK;
     }
     // Image i's orientation: judged with the image's other arguments, behind them, by the callers.  record(i) comes after it.
     int check_orientation(int i) const { return !h_orient || orientation_valid(h_orient[i]) ? JPEG_AMD_OK : JPEG_AMD_EINVAL; }
@@ -552,21 +572,27 @@ struct ResampleTarget {
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
     size_t record_bytes() const
     {
+        if (place) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
         if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
         return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
     }
     int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
-        const OrientedSource s = oriented_source(oriented ? h_orient[i] : 1, offset, w, h);   // (1: the stored image)
-        const float kx = (float)s.w / (float)out_w, ky = (float)s.h / (float)out_h;
+        const OrientedSource s = oriented_source(orientation(i), offset, w, h);   // (1: the stored image)
+        const jpeg_amd_region win = place ? windows[(size_t)i] : jpeg_amd_region{0, 0, out_w, out_h};   // (placed: the window's factors)
+        const float kx = (float)s.w / (float)win.width, ky = (float)s.h / (float)win.height;
         const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
         if (!antialias()) {
-            const OrientedResizeRecord r{{s.base, s.w, s.h, kx, ky, flip, 0u}, s.step_x, s.step_y};
-            std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());   // (the plain record is its head)
+            PlacedResizeRecord r{};
+            static_cast<OrientedResizeRecord &>(r) = OrientedResizeRecord{{s.base, s.w, s.h, kx, ky, flip, 0u}, s.step_x, s.step_y};
+            r.x0 = win.x; r.y0 = win.y; r.ww = win.width; r.wh = win.height;
+            std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());   // (the plain and the oriented record are its head)
             return JPEG_AMD_OK;
         }
         const float sx = std::max(kx, 1.0f), sy = std::max(ky, 1.0f);
-        const OrientedAntialiasRecord r{{s.base, s.w, s.h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u}, s.step_x, s.step_y};
+        PlacedAntialiasRecord r{};
+        static_cast<OrientedAntialiasRecord &>(r) = OrientedAntialiasRecord{{s.base, s.w, s.h, kx, sx, 1.0f / sx, ky, sy, 1.0f / sy, flip, 0u}, s.step_x, s.step_y};
+        r.x0 = win.x; r.y0 = win.y; r.ww = win.width; r.wh = win.height;
         std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());
         return kx > max_scale() || ky > max_scale() ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
     }
@@ -575,7 +601,10 @@ struct ResampleTarget {
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
         const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
-        return launch_resample(stream, ResampleLaunch{filter, oriented, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride});
+        const ResampleRecords kind = place ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
+        ResampleLaunch l{filter, kind, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride, {0, 0, 0}};
+        for (int c = 0; place && c < 3; ++c) l.fill[c] = place->fill[c];
+        return launch_resample(stream, l);
     }
 };
 
@@ -647,6 +676,7 @@ int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t 
             if (e.width < 1 || e.height < 1) return JPEG_AMD_EINVAL;
             if (n_images > 1 && src_stride < (size_t)3 * e.width * e.height) return JPEG_AMD_EINVAL;
             JA_TRY(t.check_orientation(i));
+            JA_TRY(t.window(i, e.width, e.height));
             const int verdict = t.record(rec, i, i, (uint64_t)i * src_stride, e.width, e.height);
             if (taps == JPEG_AMD_OK) taps = verdict;
         }
@@ -860,6 +890,7 @@ int judge_resized_mixed(int n_images, int judged, const jpeg_amd_image *h_images
         JA_TRY(check_mixed_image(h_images[i], 1, cosited, color, h_views[i], t.d_dst, 0));   // the views' stride is ours
         JA_TRY(t.check_orientation(i));
         if (i == 0) JA_TRY(t.check(n_images));
+        JA_TRY(t.window(i, h_views[i].region.width, h_views[i].region.height));
     }
     if (n_images == 0) JA_TRY(t.check(n_images));
     if (judged < n_images) return JPEG_AMD_OK;
@@ -890,10 +921,10 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
 
 int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
-                                          const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient, void *d_dst,
-                                          size_t dst_stride, int *taps)
+                                          const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient,
+                                          const jpeg_amd_placement *place, void *d_dst, size_t dst_stride, int *taps)
 {
-    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient};
+    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place};
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
@@ -1000,8 +1031,8 @@ int jpeg_amd_resize_oriented_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_
                                    const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
                                    const uint8_t *h_orient, uint8_t *d_dst, size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride, h_orient});
+    return jpeg_amd_resize_placed_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, h_orient, nullptr, nullptr, d_dst,
+                                        dst_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -1010,8 +1041,8 @@ int jpeg_amd_resize_oriented_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const
                                           const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
                                           void *d_dst, size_t dst_stride)
 try {
-    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient});
+    return jpeg_amd_resize_placed_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, spec, h_flip, h_orient,
+                                               nullptr, nullptr, d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -1019,8 +1050,8 @@ int jpeg_amd_decode_resized_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, cons
                                            jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
                                            int filter, const uint8_t *h_orient, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride, h_orient});
+    return jpeg_amd_decode_resized_placed_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, h_orient, nullptr,
+                                                nullptr, d_pixels, pixel_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -1029,8 +1060,8 @@ int jpeg_amd_decode_tensor_oriented_mixed(jpeg_amd_ctx *ctx, int n_images, const
                                           int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
                                           const uint8_t *h_orient, void *d_dst, size_t dst_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient});
+    return jpeg_amd_decode_tensor_placed_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, spec, h_flip, h_orient,
+                                               nullptr, nullptr, d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL
 
@@ -1044,3 +1075,69 @@ int jpeg_amd_orient_region(int orientation, int32_t width, int32_t height, const
     *stored = jpeg_amd_region{m.x, m.y, m.width, m.height};
     return JPEG_AMD_OK;
 }
+
+// The four resample calls above the file level with a placement ("placed resample"); their forms without one, above, are
+// these with place == nullptr.
+int jpeg_amd_place_window(int mode, int anchor, int32_t src_w, int32_t src_h, int32_t out_w, int32_t out_h, jpeg_amd_region *window)
+{
+    if (!window || (mode != JPEG_AMD_PLACE_FIT && mode != JPEG_AMD_PLACE_FIT_DOWN)) return JPEG_AMD_EINVAL;
+    if (anchor != JPEG_AMD_ANCHOR_CENTRE && anchor != JPEG_AMD_ANCHOR_TOP_LEFT) return JPEG_AMD_EINVAL;
+    if (src_w < 1 || src_h < 1 || out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    const int64_t sw = src_w, sh = src_h, ow = out_w, oh = out_h;
+    int64_t ww, wh;
+    if (mode == JPEG_AMD_PLACE_FIT_DOWN && sw <= ow && sh <= oh) {
+        ww = sw;
+        wh = sh;
+    } else if (ow * sh <= oh * sw) {   // the width binds
+        ww = ow;
+        wh = std::min(oh, std::max<int64_t>(1, (2 * sh * ow + sw) / (2 * sw)));
+    } else {
+        wh = oh;
+        ww = std::min(ow, std::max<int64_t>(1, (2 * sw * oh + sh) / (2 * sh)));
+    }
+    const bool centre = anchor == JPEG_AMD_ANCHOR_CENTRE;
+    *window = jpeg_amd_region{centre ? (int32_t)((ow - ww) / 2) : 0, centre ? (int32_t)((oh - wh) / 2) : 0, (int32_t)ww, (int32_t)wh};
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_resize_placed_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                 const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                 const uint8_t *h_orient, const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out,
+                                 uint8_t *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride, h_orient, place, h_windows_out});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_resize_placed_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                        const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out, void *d_dst,
+                                        size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_resized_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                         jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                         int filter, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                         jpeg_amd_region *h_windows_out, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride, h_orient, place, h_windows_out});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                        const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                        jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride)
+try {
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out});
+}
+JA_NOTHROW_TAIL

@@ -170,7 +170,7 @@ hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int1
 // n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h in ONE launch, by the contracts of
 // include/jpeg_amd.h: through one of three filters ("resized decode", "antialiased resample", "bicubic resample"), read as
 // stored or oriented ("oriented resample"), to bytes or to tensor elements ("tensor output").  One record per image, made on
-// the host; which of the four kinds follows from the filter and from whether the call is oriented.
+// the host; which of the six kinds follows from the filter and from whether the call is oriented or placed.
 struct ResizeRecord {      // bilinear
     uint64_t offset;   // bytes from d_src
     int32_t  w, h;     // > 0
@@ -200,6 +200,16 @@ struct OrientedAntialiasRecord : AntialiasRecord {
     int64_t step_x, step_y;
 };
 static_assert(sizeof(OrientedResizeRecord) == 48 && sizeof(OrientedAntialiasRecord) == 64, "record layout");
+// Placed ("placed resample"): the oriented record of the filter -- its scale factors those of the oriented extent over the
+// WINDOW's ww x wh -- and the window of the out_w x out_h canvas that the image is resampled into; the rest of the canvas is
+// the launch's fill.  The window lies inside the canvas and is at least 1 x 1.
+struct PlacedResizeRecord : OrientedResizeRecord {
+    int32_t x0, y0, ww, wh;
+};
+struct PlacedAntialiasRecord : OrientedAntialiasRecord {
+    int32_t x0, y0, ww, wh;
+};
+static_assert(sizeof(PlacedResizeRecord) == 64 && sizeof(PlacedAntialiasRecord) == 80, "record layout");
 constexpr int   kResizeMaxSide = 1 << 30;        // of the output: the kernels' pixel indices are int
 constexpr float kAntialiasMaxScale = 16.0f;
 constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
@@ -210,16 +220,18 @@ uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the la
 // (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted and stored in spec->layout.  A spec is
 // valid (jpeg_amd_tensor_extent).  hipErrorInvalidValue: an extent or a tile count past the limits above, null records, or a
 // filter, dtype or layout that no kernel exists for.
+enum class ResampleRecords : int { Stored, Oriented, Placed };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms
 struct ResampleLaunch {
     int filter;                        // JPEG_AMD_FILTER_*
-    bool oriented;                     // the records are the Oriented* ones
+    ResampleRecords records;           // the kind of every record of the launch
     const jpeg_amd_tensor_spec *spec;  // nullptr: bytes out
     int n_images;
     const uint8_t *d_src;
-    const void *d_records;             // record 0 of the launch; the type follows filter and oriented
+    const void *d_records;             // record 0 of the launch; the type follows filter and records
     int out_w, out_h;
     void *d_dst;
     size_t dst_stride;
+    uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window
 };
 hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l);
 

@@ -9,6 +9,9 @@
 // k_resize_tensor<Oriented, T, CHW>: bilinear, elements of T in either layout -- resample_walk<Oriented> with tensor_sink.
 // k_tables_bytes<Filter, Record>, k_tables_tensor<Filter, Record, T, CHW>: the filters with weight tables (TriangleFilter:
 //   antialias, BicubicFilter) over AntialiasRecords or OrientedAntialiasRecords -- antialias_walk with the same two sinks.
+// k_resize_placed_bytes, k_resize_placed_tensor<T, CHW>, k_tables_placed_bytes<Filter>, k_tables_placed_tensor<Filter, T, CHW>:
+//   the same walks over PlacedResizeRecords / PlacedAntialiasRecords ("placed resample") with the same sinks; their arguments
+//   end with the launch's fill.
 // The byte kernels never flip (the records' flip is not read); the tensor kernels flip where the record says so, after the
 // orientation: the flip mirrors the OUTPUT columns.
 //
@@ -50,6 +53,16 @@ struct BytesArgs : ResampleArgs {
 template <typename T, typename Record>
 struct RecordTensorArgs : TensorArgs<T> {
     const Record *tab_records;
+};
+
+// The placed kernels': the oriented kernels' of the sink, then the fill, channel c in bits 8 c ...
+template <typename Record>
+struct PlacedBytesArgs : BytesArgs<Record> {
+    uint32_t fill;
+};
+template <typename T, typename Record>
+struct PlacedTensorArgs : RecordTensorArgs<T, Record> {
+    uint32_t fill;
 };
 
 // Where the image of the workgroup goes, and the elements of one of its channels in CHW.
@@ -191,6 +204,39 @@ __global__ __launch_bounds__(kThreads) void k_tables_tensor(RecordTensorArgs<T, 
     });
 }
 
+__global__ __launch_bounds__(kThreads) void k_resize_placed_bytes(PlacedBytesArgs<PlacedResizeRecord> a)
+{
+    uint8_t *dst = image_dst(a);
+    resample_walk<true, true>(a, false, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); }, a.fill);
+}
+
+template <typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_resize_placed_tensor(PlacedTensorArgs<T, PlacedResizeRecord> a)
+{
+    T *dst = image_dst(a);
+    const size_t plane = image_plane(a);
+    resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+    }, a.fill);
+}
+
+template <typename Filter>
+__global__ __launch_bounds__(kThreads) void k_tables_placed_bytes(PlacedBytesArgs<PlacedAntialiasRecord> a)
+{
+    uint8_t *dst = image_dst(a);
+    antialias_walk<Filter>(a, a.tab_records, false, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); }, a.fill);
+}
+
+template <typename Filter, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_tables_placed_tensor(PlacedTensorArgs<T, PlacedAntialiasRecord> a)
+{
+    T *dst = image_dst(a);
+    const size_t plane = image_plane(a);
+    antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+    }, a.fill);
+}
+
 // ---- the launcher ----
 
 // f(T{}, std::bool_constant<CHW>{}) for the element type and the layout of spec, or what no kernel exists for.
@@ -215,6 +261,7 @@ template <typename Filter, typename Record>
 hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const ResampleArgs &head, dim3 grid)
 {
     constexpr bool bilinear = std::is_same<Filter, Bilinear>::value, oriented = std::is_same<Record, OrientedResizeRecord>::value;
+    constexpr bool placed = std::is_same<Record, PlacedResizeRecord>::value || std::is_same<Record, PlacedAntialiasRecord>::value;
     const auto run = [&](auto kernel, auto a) {   // a: the kernel's args, zeroed
         static_cast<ResampleArgs &>(a) = head;
         if constexpr (bilinear)
@@ -223,6 +270,7 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
             a.tab_records = static_cast<const Record *>(l.d_records);
         a.dst = static_cast<decltype(a.dst)>(l.d_dst);
         a.dst_stride = l.dst_stride;
+        if constexpr (placed) a.fill = (uint32_t)l.fill[0] | (uint32_t)l.fill[1] << 8 | (uint32_t)l.fill[2] << 16;
         if constexpr (!std::is_same<decltype(a.dst), uint8_t *>::value) {
             for (int c = 0; c < 3; ++c) {
                 a.mean[c] = l.spec->mean[c];
@@ -235,13 +283,21 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
     if (l.spec) {
         return with_element(*l.spec, [&](auto t, auto chw) {
             using T = decltype(t);
-            if constexpr (bilinear)
+            if constexpr (placed && bilinear)
+                return run(k_resize_placed_tensor<T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+            else if constexpr (placed)
+                return run(k_tables_placed_tensor<Filter, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+            else if constexpr (bilinear)
                 return run(k_resize_tensor<oriented, T, decltype(chw)::value>, ResizeTensorArgs<oriented, T>{});
             else
                 return run(k_tables_tensor<Filter, Record, T, decltype(chw)::value>, RecordTensorArgs<T, Record>{});
         });
     }
-    if constexpr (!bilinear)
+    if constexpr (placed && bilinear)
+        return run(k_resize_placed_bytes, PlacedBytesArgs<Record>{});
+    else if constexpr (placed)
+        return run(k_tables_placed_bytes<Filter>, PlacedBytesArgs<Record>{});
+    else if constexpr (!bilinear)
         return run(k_tables_bytes<Filter, Record>, BytesArgs<Record>{});
     else if constexpr (oriented)
         return run(k_resize_oriented_bytes, BytesArgs<Record>{});
@@ -249,10 +305,15 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
         return run(k_resize_bilinear, ResizeArgs{});
 }
 
-template <typename Filter, typename Stored, typename Oriented>
+template <typename Filter, typename Stored, typename Oriented, typename Placed>
 hipError_t launch_filter(hipStream_t stream, const ResampleLaunch &l, const ResampleArgs &head, dim3 grid)
 {
-    return l.oriented ? launch_kernel<Filter, Oriented>(stream, l, head, grid) : launch_kernel<Filter, Stored>(stream, l, head, grid);
+    switch (l.records) {
+    case ResampleRecords::Stored: return launch_kernel<Filter, Stored>(stream, l, head, grid);
+    case ResampleRecords::Oriented: return launch_kernel<Filter, Oriented>(stream, l, head, grid);
+    case ResampleRecords::Placed: return launch_kernel<Filter, Placed>(stream, l, head, grid);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
@@ -270,9 +331,9 @@ hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l)
     dim3 grid;
     if (const hipError_t e = resample_launch(l.n_images, l.d_src, nullptr, l.out_w, l.out_h, head, grid)) return e;
     switch (l.filter) {
-    case JPEG_AMD_FILTER_BILINEAR: return launch_filter<Bilinear, ResizeRecord, OrientedResizeRecord>(stream, l, head, grid);
-    case JPEG_AMD_FILTER_ANTIALIAS: return launch_filter<TriangleFilter, AntialiasRecord, OrientedAntialiasRecord>(stream, l, head, grid);
-    case JPEG_AMD_FILTER_BICUBIC: return launch_filter<BicubicFilter, AntialiasRecord, OrientedAntialiasRecord>(stream, l, head, grid);
+    case JPEG_AMD_FILTER_BILINEAR: return launch_filter<Bilinear, ResizeRecord, OrientedResizeRecord, PlacedResizeRecord>(stream, l, head, grid);
+    case JPEG_AMD_FILTER_ANTIALIAS: return launch_filter<TriangleFilter, AntialiasRecord, OrientedAntialiasRecord, PlacedAntialiasRecord>(stream, l, head, grid);
+    case JPEG_AMD_FILTER_BICUBIC: return launch_filter<BicubicFilter, AntialiasRecord, OrientedAntialiasRecord, PlacedAntialiasRecord>(stream, l, head, grid);
     default: return hipErrorInvalidValue;
     }
 }

@@ -103,15 +103,64 @@ inline hipError_t resample_launch(int n_images, const uint8_t *d_src, const Resi
     return hipSuccess;
 }
 
+// The rows of resample_walk for a placed record: its loop with a select per pixel in front of the loads.  A run that
+// straddles a window edge has pixels of both kinds; a padded row is all fill.
+template <typename Sink>
+__device__ __forceinline__ void placed_rows(const ResampleArgs &a, const PlacedResizeRecord &r, const int *cx0, const int *cx1,
+                                            const float *cfx, const int *ry0, const int *ry1, const float *rfy, int px0, int py0,
+                                            int ly, int lx, int x, int npix, uint32_t fill, Sink sink)
+{
+    int64_t x0[kRun], x1[kRun];
+    float fx[kRun];
+    bool xpad[kRun];
+#pragma unroll
+    for (int k = 0; k < kRun; ++k) {
+        const int i0 = cx0[kRun * lx + k];
+        xpad[k] = i0 < 0;
+        x0[k] = r.step_x * (uint32_t)max(i0, 0);
+        x1[k] = r.step_x * (uint32_t)cx1[kRun * lx + k];
+        fx[k] = cfx[kRun * lx + k];
+    }
+    const uint8_t *src = a.src + r.offset;
+#pragma unroll
+    for (int u = ly; u < kTileH; u += kRowStep) {
+        const int y = py0 + u;
+        if (y >= a.out_h) break;
+        const int j0 = ry0[u];
+        const bool ypad = j0 < 0;
+        const uint8_t *r0 = src + (int64_t)(uint32_t)max(j0, 0) * r.step_y, *r1 = src + (int64_t)(uint32_t)ry1[u] * r.step_y;
+        const float fy = rfy[u];
+        uint32_t o[kRun][3];
+#pragma unroll
+        for (int k = 0; k < kRun; ++k) {
+            if (ypad || xpad[k]) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[k][c] = (fill >> (8 * c)) & 0xffu;
+            } else {
+                const uint8_t *pa = r0 + x0[k], *pb = r0 + x1[k], *pc = r1 + x0[k], *pd = r1 + x1[k];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[k][c] = resample((float)pa[c], (float)pb[c], (float)pc[c], (float)pd[c], fx[k], fy);
+            }
+        }
+        sink(o, y, x, npix);
+    }
+}
+
 // The tile blockIdx.x of image blockIdx.y: sink(o, y, x, npix) for every run of the tile, o[k][c] the byte of channel c of the
 // pixel stored at (x + k, y), k < npix <= kRun.  flips: the image's ResizeRecord::flip counts (it is not read otherwise).
 // Oriented: the records are OrientedResizeRecords ("oriented resample": a.records points at them) -- w and h are the ORIENTED
 // image's, offset its first byte, and the byte of channel c of its pixel (x', y') lies at offset + x' step_x + y' step_y + c,
 // the steps signed; everything else of the walk, the filter included, is the text below, which compiles as it did without.
-template <bool Oriented = false, typename Sink>
-__device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips, Sink sink)
+// Placed: the records are PlacedResizeRecords ("placed resample", oriented as well): canvas column xs = flip ? out_w - 1 - x : x
+// takes the taps of xs - x0 where that lies in [0, ww), and is padded (cx0 = -1) otherwise; rows likewise (ry0 = -1).  A padded
+// pixel reads nothing -- so a tile without a window pixel reads no source byte -- and its three values are `fill`'s bytes
+// (channel c in bits 8 c ...).  Without Placed the text compiles as it did.
+template <bool Oriented = false, bool Placed = false, typename Sink>
+__device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips, Sink sink, uint32_t fill = 0u)
 {
-    using Record = typename std::conditional<Oriented, OrientedResizeRecord, ResizeRecord>::type;
+    static_assert(Oriented || !Placed, "a placed record is an oriented one");
+    using Record = typename std::conditional<Placed, PlacedResizeRecord,
+                                             typename std::conditional<Oriented, OrientedResizeRecord, ResizeRecord>::type>::type;
     __shared__ int cx0[kTileW], cx1[kTileW], ry0[kTileH], ry1[kTileH];
     __shared__ float cfx[kTileW], rfy[kTileH];
 
@@ -124,13 +173,25 @@ __device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips,
     if (t < kTileW) {
         int i0 = 0, i1 = 0;
         float f = 0.0f;
-        if (px0 + t < a.out_w) axis_tap(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.w, i0, i1, f);
+        if constexpr (Placed) {
+            const int xs = (flip ? a.out_w - 1 - (px0 + t) : px0 + t) - r.x0;   // (past the output: its taps reach no sink)
+            if (xs >= 0 && xs < r.ww) axis_tap(xs, r.kx, r.w, i0, i1, f);
+            else i0 = -1;
+        } else {
+            if (px0 + t < a.out_w) axis_tap(flip ? a.out_w - 1 - (px0 + t) : px0 + t, r.kx, r.w, i0, i1, f);
+        }
         cx0[t] = i0; cx1[t] = i1; cfx[t] = f;
     } else if (t < kTileW + kTileH) {
         const int u = t - kTileW;
         int i0 = 0, i1 = 0;
         float f = 0.0f;
-        if (py0 + u < a.out_h) axis_tap(py0 + u, r.ky, r.h, i0, i1, f);
+        if constexpr (Placed) {
+            const int ys = py0 + u - r.y0;
+            if (ys >= 0 && ys < r.wh) axis_tap(ys, r.ky, r.h, i0, i1, f);
+            else i0 = -1;
+        } else {
+            if (py0 + u < a.out_h) axis_tap(py0 + u, r.ky, r.h, i0, i1, f);
+        }
         ry0[u] = i0; ry1[u] = i1; rfy[u] = f;
     }
     __syncthreads();
@@ -139,6 +200,10 @@ __device__ __forceinline__ void resample_walk(const ResampleArgs &a, bool flips,
     const int x = px0 + kRun * lx;
     const int npix = min(kRun, a.out_w - x);
     if (npix <= 0) return;
+    if constexpr (Placed) {
+        placed_rows(a, r, cx0, cx1, cfx, ry0, ry1, rfy, px0, py0, ly, lx, x, npix, fill, sink);
+        return;
+    }
     using Step = typename std::conditional<Oriented, int64_t, size_t>::type;   // (the additions wrap to the same address)
     Step x0[kRun], x1[kRun], pixel_bytes = 3, row_bytes = (Step)3 * (uint32_t)r.w;
     if constexpr (Oriented) {

@@ -1347,6 +1347,118 @@ int jpeg_amd_decompress_resized_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *c
                                              jpeg_amd_region *h_windows_out, uint8_t *d_pixels, size_t pixel_stride,
                                              jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out);
 
+/* ---- warped resample: rotate, shear and scale through an affine map, in the resample launch -----------------------------
+ *
+ * Every call above resamples along the axes.  These calls take, per image, a matrix m[6] = (m00, m01, m02, m10, m11, m12) of
+ * binary32 that maps the centre of an OUTPUT pixel to a point of the SOURCE, both in continuous pixel coordinates: pixel i
+ * covers [i, i + 1) and its centre is i + 0.5.  It is the INVERSE map, the one grid_sample and torchvision's affine use:
+ * RandomRotation, RandomAffine, the rotation, shear and scale of a detector's augmentation, deskewing a scan.  One launch
+ * writes every image of the call.
+ *
+ * THE CONTRACT.  A source of w x h pixels of 3 bytes, a target of out_w x out_h.  Every statement is ONE binary32 operation
+ * and nothing is contracted.  For stored output column x and row y:
+ *     xs = flip ? out_w - 1 - x : x             (tensor calls: the WARPED image mirrored, as "tensor output" says; else x)
+ *     xc = (float)xs + 0.5f;   yc = (float)y + 0.5f
+ *     sx = ((m00 * xc) + (m01 * yc)) + m02;   sx = sx - 0.5f;   sx = min(max(sx, -1.0f), (float)w)
+ *     sy = ((m10 * xc) + (m11 * yc)) + m12;   sy = sy - 0.5f;   sy = min(max(sy, -1.0f), (float)h)
+ *     fx0 = floorf(sx);  x0 = (int)fx0;  x1 = x0 + 1;  fx = sx - fx0          (x0 in -1 .. w)
+ *     fy0 = floorf(sy);  y0 = (int)fy0;  y1 = y0 + 1;  fy = sy - fy0          (y0 in -1 .. h)
+ *     a, b, c, d = the taps (y0, x0), (y0, x1), (y1, x0), (y1, x1) of the channel, as float
+ *     top = a + fx * (b - a);  bot = c + fx * (d - c);  v = top + fy * (bot - top)
+ *     out = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
+ * The last two lines are those of "resized decode".  A tap whose column is outside 0 .. w - 1 or whose row is outside
+ * 0 .. h - 1 has, by the call's edge mode,
+ *   JPEG_AMD_EDGE_FILL (0): the value (float)fill[c] -- grid_sample's "zeros" padding with torchvision's fill.  The image's
+ *     border blends into the fill over one pixel, and a pixel well outside the source is the fill exactly (a = b = c = d
+ *     gives v = a);
+ *   JPEG_AMD_EDGE_REPLICATE (1): its indices clamped into the image -- grid_sample's "border".
+ * The filter is the two-tap one at any reduction: there is no tap limit and no ENOSUP.  The tensor output is "tensor output"
+ * applied to this byte, fill pixels included.
+ *
+ * CONSEQUENCES.  The identity (1, 0, 0, 0, 1, 0) at out = (w, h) gives the source bytes.  A translation by integers gives the
+ * bytes shifted, and the fill (or the replicated edge) where they came from outside.  (w / out_w, 0, 0, 0, h / out_h, 0),
+ * divided in binary32, with REPLICATE is jpeg_amd_resize_batch's output bit for bit.  (0, 1, 0, -1, 0, h) to out = (h, w) is
+ * the image rotated by 90 degrees clockwise, as a permutation of bytes.  Against grid_sample(bilinear, align_corners=False)
+ * with "zeros" and "border" the bytes agree within one level (the order of the operations differs).
+ *
+ * EINVAL: a matrix entry that is not finite or exceeds 2^30 in magnitude (with an output side of at most 2^30 no coordinate
+ * overflows and no NaN arises); a source side above 2^24 ((float)w must be exact); an edge mode other than 0 and 1; a null
+ * h_matrices with n_images > 0, a null `warp`; and whatever jpeg_amd_resize_batch or jpeg_amd_tensor_extent refuse.
+ * Everything is judged before anything is enqueued, the context last; n_images == 0 is OK. */
+enum {
+    JPEG_AMD_EDGE_FILL = 0,
+    JPEG_AMD_EDGE_REPLICATE = 1
+};
+typedef struct {
+    int32_t edge;       /* JPEG_AMD_EDGE_* */
+    uint8_t fill[3];    /* EDGE_FILL: the bytes of a tap outside the image */
+} jpeg_amd_warp;
+
+/* Pixels to pixels, one launch: jpeg_amd_resize_batch's and jpeg_amd_resize_tensor_batch's arguments, and h_matrices
+ * ([n_images][6], host, copied before the call returns) and `warp` behind the extents. */
+int jpeg_amd_warp_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                        const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                        int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_warp_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                               const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                               int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                               void *d_dst, size_t dst_stride);
+
+/* The view of an image that a warp reads, and the matrix against that view.  Host only, pure, computed in double.
+ * `m` is in the coordinates of the UPRIGHT image: the stored W x H image of `layout` seen through `orientation` 1 .. 8
+ * ("oriented resample").
+ *   1. The orientation is composed into the matrix.  With the orientation's bits (T, fx, fy) and (Xu, Yu) = m applied to an
+ *      output centre: (a, b) = T ? (Yu, Xu) : (Xu, Yu), Xs = fx ? W - a : a, Ys = fy ? H - b : b.  The result M_s maps output
+ *      centres to STORED coordinates; its linear part is m's entries permuted and negated, which is exact.
+ *   2. The denominator: the largest d in {8, 4, 2, 1} with d * d <= min(m00 m00 + m10 m10, m01 m01 + m11 m11).  Both output
+ *      axes then step at least d source pixels, so the image at 1/d still needs no enlarging: jpeg_amd_view_denom's rule for
+ *      a map without a rectangle.
+ *   3. M_s times 1/d (exact): the matrix against the scaled image of W' x H' (jpeg_amd_scaled_layout).
+ *   4. The footprint: the canvas corners (0, 0), (out_w, 0), (0, out_h), (out_w, out_h) through it, X = (s00 cx + s01 cy)
+ *      + s02; with xmin, xmax the extremes the view's columns are clamp(floor(xmin - 0.5) - 1, 0, W' - 1) ..=
+ *      clamp(floor(xmax - 0.5) + 2, 0, W' - 1), its rows likewise.  The margin of one pixel beyond the taps covers the
+ *      binary32 rounding of the kernel's coordinates.  The view is never empty; where its edge lies inside the image no tap
+ *      reaches it, and where its edge is the image's, fill and replication mean there what they mean for the whole image.
+ *   5. m_view: that matrix with the view's x and y subtracted from its m02 and m12, rounded to binary32 ONCE.
+ * EINVAL: an orientation outside 1 .. 8, a matrix the contract refuses, out_w or out_h outside 1 .. 2^30, a layout
+ * jpeg_amd_scaled_layout refuses, a null pointer. */
+int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const float m[6], int32_t out_w, int32_t out_h,
+                       jpeg_amd_view *view, float m_view[6]);
+
+/* The decode and file routes, by reference only: they define no arithmetic.
+ * jpeg_amd_decode_warped_mixed / jpeg_amd_decode_tensor_warped_mixed: jpeg_amd_decode_resized_mixed's and
+ * jpeg_amd_decode_tensor_mixed's arguments without h_views; h_orient (n_images values in 1 .. 8, NULL = all 1), h_matrices
+ * (upright coordinates of the FULL-SIZE images) and `warp`; h_views_out and h_matrices_out ([n_images] and [n_images][6], or
+ * NULL) receive what jpeg_amd_warp_view gave.  Image i is, bit for bit, jpeg_amd_warp_batch (or the tensor form) applied to
+ * the pixels jpeg_amd_decode_view_batch defines for the view jpeg_amd_warp_view returns, with the m_view it returns.  The
+ * route is the resized calls': the mixed view decode per chunk, then ONE warp launch per chunk.
+ * jpeg_amd_decompress_resized_warped_mixed / jpeg_amd_decompress_tensor_warped_mixed: their file front end, as "files to
+ * tensors" is of the mixed calls: h_orient as in the *_oriented_mixed file calls (JPEG_AMD_ORIENT_EXIF = the file's own tag),
+ * each file's view from jpeg_amd_warp_view; h_info, h_views, h_matrices_out and h_orient_out are written as far as the files
+ * were judged.  There are no source rectangles (the matrix says what is read), no placement and no filter but the bilinear. */
+int jpeg_amd_decode_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                 jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                 const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
+                                 float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                        const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                                        float *h_matrices_out, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_resized_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                             int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                             const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp,
+                                             int32_t out_w, int32_t out_h, uint8_t *d_pixels, size_t pixel_stride,
+                                             jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
+                                             int32_t *h_orient_out);
+int jpeg_amd_decompress_tensor_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                            int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                            const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp,
+                                            int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
+                                            const uint8_t *h_flip, void *d_dst, size_t dst_stride,
+                                            jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
+                                            int32_t *h_orient_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,17 @@ SIGNATURES = {
                                                           C.c_int, _p, _p, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
     "jpeg_amd_decompress_resized_placed_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
                                                            C.c_int, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_warp_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, _p, _p, C.c_int32, C.c_int32, _p, C.c_size_t]),
+    "jpeg_amd_warp_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_warp_view": (C.c_int, [_L, C.c_int, _p, C.c_int32, C.c_int32, _p, _p]),
+    "jpeg_amd_decode_warped_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p,
+                                               C.c_size_t]),
+    "jpeg_amd_decode_tensor_warped_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p,
+                                                      _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_resized_warped_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int32,
+                                                           C.c_int32, _p, C.c_size_t, _p, _p, _p, _p]),
+    "jpeg_amd_decompress_tensor_warped_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int32,
+                                                          C.c_int32, _p, _p, _p, C.c_size_t, _p, _p, _p, _p]),
 }
 
 
@@ -205,6 +216,11 @@ class Placement(C.Structure):
     """struct jpeg_amd_placement"""
     _fields_ = [("mode", C.c_int32), ("anchor", C.c_int32), ("h_windows", C.c_void_p), ("fill", C.c_uint8 * 3),
                 ("reserved", C.c_uint8)]
+
+
+class Warp(C.Structure):
+    """struct jpeg_amd_warp"""
+    _fields_ = [("edge", C.c_int32), ("fill", C.c_uint8 * 3)]
 
 
 class View(C.Structure):
@@ -245,7 +261,8 @@ FILTER_BILINEAR, FILTER_ANTIALIAS = 0, 1  # JPEG_AMD_FILTER_BILINEAR ...
 FILTER_BICUBIC = 3                        # JPEG_AMD_FILTER_BICUBIC (2 is no filter)
 PLACE_WINDOWS, PLACE_FIT, PLACE_FIT_DOWN = 0, 1, 2   # JPEG_AMD_PLACE_*
 ANCHOR_CENTRE, ANCHOR_TOP_LEFT = 0, 1               # JPEG_AMD_ANCHOR_*
-ORIENT_EXIF = 0                         # JPEG_AMD_ORIENT_EXIF (the file calls); JPEG_AMD_ORIENT_1 .. _8 are 1 .. 8
+EDGE_FILL, EDGE_REPLICATE = 0, 1                    # JPEG_AMD_EDGE_*
+ORIENT_EXIF = 0                       # JPEG_AMD_ORIENT_EXIF (the file calls); JPEG_AMD_ORIENT_1 .. _8 are 1 .. 8
 
 # JPEG_AMD_XFORM_*: TRANSPOSE, then FLIP_H, then FLIP_V
 XFORM_TRANSPOSE, XFORM_FLIP_H, XFORM_FLIP_V = 1, 2, 4

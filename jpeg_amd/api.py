@@ -14,6 +14,7 @@ stream; every computation is a call into libjpeg_amd.so.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -608,6 +609,82 @@ def _windows_array(h_windows, n) -> np.ndarray:
     return np.array([(r.x, r.y, r.width, r.height) for r in h_windows[:n]], np.int32).reshape(n, 4)
 
 
+_EDGES = {"fill": _lib.EDGE_FILL, "replicate": _lib.EDGE_REPLICATE}
+
+
+def _warp(edge, fill) -> "_lib.Warp":
+    """edge=, fill= of the warp calls -> struct jpeg_amd_warp."""
+    w = _lib.Warp()
+    if isinstance(edge, str):
+        if edge.lower() not in _EDGES:
+            raise ValueError('edge: "fill" or "replicate"')
+        w.edge = _EDGES[edge.lower()]
+    else:
+        w.edge = int(edge)          # (the library judges it)
+    f = [int(v) for v in fill]
+    if len(f) != 3 or min(f) < 0 or max(f) > 255:
+        raise ValueError("fill: three bytes")
+    w.fill[0], w.fill[1], w.fill[2] = f
+    return w
+
+
+def _matrices(matrices, n: int) -> np.ndarray:
+    """matrices= of the warp calls -> float32 [n, 6], contiguous."""
+    m = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, 6))
+    if m.shape[0] != n:
+        raise ValueError("matrices: one (m00, m01, m02, m10, m11, m12) per image")
+    return m
+
+
+def _cos_sin_degrees(angle: float) -> Tuple[float, float]:
+    """(cos, sin) of an angle in degrees, exact at the multiples of 90."""
+    a = math.fmod(float(angle), 360.0)
+    if a % 90.0 == 0.0:
+        return [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)][int(a // 90.0) % 4]
+    return math.cos(math.radians(a)), math.sin(math.radians(a))
+
+
+def affine_matrix(src_size, out_size, angle: float = 0.0, scale: float = 1.0, shear=(0.0, 0.0), translate=(0.0, 0.0),
+                  source_region=None) -> np.ndarray:
+    """The matrix of the warp calls (include/jpeg_amd.h, "warped resample") for the usual augmentation parameters: the INVERSE
+    map that takes the centre of the out_size (Wt, Ht) canvas to the centre of source_region (x, y, width, height) of an image
+    of src_size (w, h) -- None: the whole image.  The canvas is rotated by `angle` degrees counter-clockwise about its centre,
+    sheared by `shear` degrees (torchvision's convention and formulas: the inverse of RSS), scaled by `scale` and moved by
+    `translate` canvas pixels, and then stretched onto the rectangle, so that angle = 0, shear = 0, scale = 1, translate = 0 is
+    exactly the crop-resize (width / Wt, 0, x, 0, height / Ht, y).  Computed in double, returned as float32 [6]."""
+    x0, y0, w, h = (0, 0, int(src_size[0]), int(src_size[1])) if source_region is None else (int(v) for v in source_region)
+    wt, ht = int(out_size[0]), int(out_size[1])
+    if w < 1 or h < 1 or wt < 1 or ht < 1 or not scale > 0.0:
+        raise ValueError("affine_matrix: sizes of at least 1 and a positive scale")
+    sx, sy = math.radians(float(shear[0])), math.radians(float(shear[1]))
+    # torchvision's _get_inverse_affine_matrix; its angle is clockwise, so rot = -angle
+    c, s = _cos_sin_degrees(-float(angle) - float(shear[1]))
+    c0, s0 = _cos_sin_degrees(-float(angle))
+    a = c / math.cos(sy)
+    b = -c * math.tan(sx) / math.cos(sy) - s0
+    cc = s / math.cos(sy)
+    d = -s * math.tan(sx) / math.cos(sy) + c0
+    l00, l01, l10, l11 = d / scale, -b / scale, -cc / scale, a / scale
+    px, py = wt / 2.0 + float(translate[0]), ht / 2.0 + float(translate[1])
+    p = l00 * px + l01 * py
+    q = l10 * px + l11 * py
+    m = [w * l00 / wt, w * l01 / wt, (x0 + w / 2.0) - w * p / wt, h * l10 / ht, h * l11 / ht, (y0 + h / 2.0) - h * q / ht]
+    return np.array([v + 0.0 for v in m], np.float64).astype(np.float32)
+
+
+def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
+    """The view that a warp of an image of `size` (w, h) and `layout` reads, and the matrix against it (jpeg_amd_warp_view):
+    `matrix` (6 values) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT image, the stored image seen through
+    `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [6])."""
+    m = _matrices(matrix, 1)
+    v = _lib.View()
+    mv = np.zeros(6, np.float32)
+    L = layout.c_layout(size)
+    _lib.check(_lib.lib().jpeg_amd_warp_view(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]),
+                                             C.byref(v), mv.ctypes.data), "jpeg_amd_warp_view")
+    return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
+
+
 def _decode_spectral(data: np.ndarray, scans: int = 0):
     info = inspect(data)
     planes = [np.empty((info.units_y[c], info.units_x[c], 64), np.int16) for c in range(info.ncomponents)]
@@ -1167,6 +1244,44 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
                                 orientations=orientations), views
 
 
+def _warped_mixed_args(ctx: Context, spectrals, matrices, orientations):
+    """The arguments the warped mixed calls share, behind _mixed_args' (with placeholder views)."""
+    spectrals = list(spectrals)
+    n = len(spectrals)
+    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, np.zeros((n, 5), np.int32))
+    return n, h_images, h_views, _matrices(matrices, n), _orientations(orientations, n), np.zeros((n, 6), np.float32), keep
+
+
+def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
+                        edge="fill", fill=(0, 0, 0)):
+    """The warp from Spectral images of different sizes and layouts in one call (jpeg_amd_decode_warped_mixed; include/jpeg_amd.h,
+    "warped resample"): per image a matrix [6] in the coordinates of its UPRIGHT full-size image (the stored image seen through
+    orientations[i], 1 .. 8; None: as stored).  warp_view chooses each image's denominator and view -- only the part the canvas
+    maps into is decoded -- and image i is warp() of decode_views_mixed's pixels for that view with the matrix against it.
+    Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 6])."""
+    n, h_images, h_views, m, h_orient, m_out, keep = _warped_mixed_args(ctx, spectrals, matrices, orientations)
+    w = _warp(edge, fill)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    _lib.check(_lib.lib().jpeg_amd_decode_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient, m.ctypes.data,
+                                                       C.byref(w), wt, ht, h_views, m_out.ctypes.data, out.data_ptr(), stride),
+               "jpeg_amd_decode_warped_mixed", ctx.handle)
+    return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
+
+
+def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
+                                cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0)):
+    """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_mixed); flips, spec as in
+    warp_tensor.  Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
+    n, h_images, h_views, m, h_orient, m_out, keep = _warped_mixed_args(ctx, spectrals, matrices, orientations)
+    w = _warp(edge, fill)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
+                                                              m.ctypes.data, C.byref(w), wt, ht, C.byref(spec), h_flip, h_views,
+                                                              m_out.ctypes.data, out.data_ptr(), stride),
+               "jpeg_amd_decode_tensor_warped_mixed", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
+
+
 def _file_args(sources, source_regions):
     """The arguments the file calls share: (n, c file pointers, c sizes, c source rectangles or None, room for the frame
     infos, room for the views, keep).  sources: paths or the files' bytes."""
@@ -1185,13 +1300,20 @@ def _file_args(sources, source_regions):
     return n, ptrs, sizes, regions, (_lib.FrameInfo * max(n, 1))(), (_lib.View * max(n, 1))(), files
 
 
+def _warp_file_args(warp, n: int, source_regions, place, filter_code: int, edge, fill):
+    """warp=, edge=, fill= of the file calls -> (the matrices [n, 6], room for the applied ones, struct jpeg_amd_warp)."""
+    if source_regions is not None or place is not None or filter_code != _lib.FILTER_BILINEAR:
+        raise ValueError('warp: not together with source_regions, place or a filter other than "bilinear"')
+    return _matrices(warp, n), np.zeros((n, 6), np.float32), _warp(edge, fill)
+
+
 def _views_array(h_views, n) -> np.ndarray:
     return np.array([(v.denom, v.region.x, v.region.y, v.region.width, v.region.height) for v in h_views[:n]], np.int32).reshape(n, 5)
 
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
                        cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None, place=None,
-                       anchor="centre", fill=(0, 0, 0)):
+                       anchor="centre", fill=(0, 0, 0), warp=None, edge="fill"):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
@@ -1207,10 +1329,27 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5] of (denom, x, y, width, height), the files'
     frame infos), and with `orientation` given a fourth item, the orientations applied as int32 [n].
     place / anchor / fill: as in resize (jpeg_amd_decompress_tensor_placed_mixed); "fit" fits the (oriented) source rectangle,
-    and the denominator is chosen against the window; with `place` the windows applied come back as the last item."""
+    and the denominator is chosen against the window; with `place` the windows applied come back as the last item.
+    warp / edge / fill: per file a matrix [6] in the coordinates of its UPRIGHT full-size image, as in decode_warped_mixed
+    (jpeg_amd_decompress_tensor_warped_mixed; include/jpeg_amd.h, "warped resample"); not together with source_regions, place
+    or a filter other than "bilinear" (ValueError).  The views that come back are warp_view's, and the matrices applied to them
+    come back as the last item, float32 [n, 6]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
     h_orient = _orientations(orientation, n, exif=True)
+    if warp is not None:
+        m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
+        wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+        applied = (C.c_int32 * max(n, 1))()
+        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                      color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
+                                                                      C.byref(spec), h_flip, out.data_ptr(), stride, infos, h_views,
+                                                                      m_out.ctypes.data, applied),
+                   "jpeg_amd_decompress_tensor_warped_mixed", ctx.handle)
+        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
+        if h_orient is not None:
+            res += (np.array(applied[:n], np.int32),)
+        return res + (m_out,)
     placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
     if placement is not None:
@@ -1238,14 +1377,25 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
-                       filter: str = "bilinear", threads: int = 0, orientation=None, place=None, anchor="centre", fill=(0, 0, 0)):
+                       filter: str = "bilinear", threads: int = 0, orientation=None, place=None, anchor="centre", fill=(0, 0, 0),
+                       warp=None, edge="fill"):
     """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
     (Wt, Ht) as bytes by `filter`; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
     place / anchor / fill: as there (jpeg_amd_decompress_resized_placed_mixed), the windows as a second item.
+    warp / edge / fill: as there (jpeg_amd_decompress_resized_warped_mixed); with it the views (int32 [n, 5]) and the matrices
+    applied to them (float32 [n, 6]) come back as the last two items.
     Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
     h_orient = _orientations(orientation, n, exif=True)
+    if warp is not None:
+        m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
+        wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+        _lib.check(_lib.lib().jpeg_amd_decompress_resized_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                       color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
+                                                                       out.data_ptr(), stride, infos, h_views, m_out.ctypes.data, None),
+                   "jpeg_amd_decompress_resized_warped_mixed", ctx.handle)
+        return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
     placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     if placement is not None:
@@ -1293,6 +1443,37 @@ def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=N
         _lib.check(_lib.lib().jpeg_amd_resize_oriented_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
                                                                     C.byref(spec), h_flip, h_orient, out.data_ptr(), stride),
                    "jpeg_amd_resize_oriented_tensor_batch", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec)
+
+
+def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
+    """n device uint8 images [h_i, w_i, 3] of any sizes through an affine map each, to out_size (Wt, Ht), in one launch
+    (jpeg_amd_warp_batch; include/jpeg_amd.h, "warped resample", holds the contract).  matrices: [n, 6] of (m00, m01, m02, m10,
+    m11, m12), the INVERSE map from the centres of output pixels to source coordinates (affine_matrix makes one from an angle,
+    a scale and a shear).  edge: "fill" (a tap outside the image has the `fill` bytes: grid_sample's "zeros") or "replicate"
+    (its index is clamped: "border").  Returns uint8 [n, Ht, Wt, 3]."""
+    images = list(images)
+    n = len(images)
+    m, w = _matrices(matrices, n), _warp(edge, fill)
+    src, src_stride, extents = _pack_images(ctx, images)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    _lib.check(_lib.lib().jpeg_amd_warp_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt, ht,
+                                              out.data_ptr(), stride), "jpeg_amd_warp_batch", ctx.handle)
+    return out.view(n, ht, wt, 3)
+
+
+def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0)):
+    """warp with the output stage of the tensor calls (jpeg_amd_warp_tensor_batch): the warped image mirrored along x where
+    flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  Returns one tensor
+    [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    images = list(images)
+    n = len(images)
+    m, w = _matrices(matrices, n), _warp(edge, fill)
+    src, src_stride, extents = _pack_images(ctx, images)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_warp_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt,
+                                                     ht, C.byref(spec), h_flip, out.data_ptr(), stride),
+               "jpeg_amd_warp_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 

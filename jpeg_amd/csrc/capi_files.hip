@@ -48,6 +48,9 @@ struct FilesDecode : FileBatch {
     bool placed = false;                       // "placed resample": `windows` per file, pass 0's, go to the mixed call as they are
     std::vector<jpeg_amd_region> windows;
     uint8_t fill[3] = {0, 0, 0};
+    bool warped = false;                       // "warped resample": pass 0's m_view per file go to the mixed call with the call's warp
+    std::vector<float> matrices;
+    const jpeg_amd_warp *warp = nullptr;
     void *d_dst;
     size_t dst_stride, elem_bytes;
     std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
@@ -132,7 +135,10 @@ int FilesDecode::submit(int k)
     const jpeg_amd_placement here{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, placed ? windows.data() + ch.i0 : nullptr,
                                   {fill[0], fill[1], fill[2]}, 0};
     const jpeg_amd_placement *place = placed ? &here : nullptr;
-    if (tensor)
+    if (warped)
+        JA_TRY(decode_warped_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 6 * (size_t)ch.i0, warp,
+                                         out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride));
+    else if (tensor)
         JA_TRY(jpeg_amd_decode_tensor_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
                                                    h_flip ? h_flip + ch.i0 : nullptr, h_orient, place, nullptr, d_out, dst_stride));
     else
@@ -157,17 +163,25 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                      jpeg_amd_color color, const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter, bool tensor,
                      const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
                      jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
-                     int32_t *h_orient_out)
+                     int32_t *h_orient_out, bool warped = false, const float *h_matrices = nullptr, const jpeg_amd_warp *warp = nullptr,
+                     float *h_matrices_out = nullptr)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_jpeg || !nbytes)) return JPEG_AMD_EINVAL;
+    if (warped && n_images > 0 && !h_matrices) return JPEG_AMD_EINVAL;
     FilesDecode d;
     d.ctx = ctx; d.h_jpeg = h_jpeg; d.nbytes = nbytes; d.n_images = n_images; d.cosited = cosited; d.color = color;
     d.out_w = out_w; d.out_h = out_h; d.filter = filter; d.tensor = tensor; d.spec = spec; d.h_flip = h_flip; d.d_dst = d_dst;
     d.dst_stride = dst_stride;
     d.files.resize((size_t)n_images);
-    if (h_orient) d.orient.assign((size_t)n_images, 1);   // (1 behind a refused file: the mixed call's judgement stops in front of it)
+    // (1 behind a refused file: the mixed call's judgement stops in front of it; warped: the orientation goes into the matrix)
+    if (h_orient && !warped) d.orient.assign((size_t)n_images, 1);
+    if (warped) {
+        d.warped = true;
+        d.warp = warp;
+        d.matrices.assign(6 * (size_t)n_images, 0.0f);
+    }
     if (place) {
         d.placed = true;
         d.windows.assign((size_t)n_images, jpeg_amd_region{0, 0, 0, 0});
@@ -198,7 +212,12 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                 seen = h_source_regions ? h_source_regions[i] : jpeg_amd_region{0, 0, whole.w, whole.h};
                 st = jpeg_amd_orient_region(o, f.info.width, f.info.height, &seen, &source);
             }
-            if (st == JPEG_AMD_OK) {
+            if (st == JPEG_AMD_OK && warped) {
+                // "warped resample": the matrix says what is read -- the view and the matrix against it are jpeg_amd_warp_view's
+                if (h_orient_out) h_orient_out[i] = o;
+                st = jpeg_amd_warp_view(&f.layout, o, h_matrices + 6 * (size_t)i, out_w, out_h, &f.view, &d.matrices[6 * (size_t)i]);
+                if (st == JPEG_AMD_OK && h_matrices_out) std::memcpy(h_matrices_out + 6 * (size_t)i, &d.matrices[6 * (size_t)i], 6 * sizeof(float));
+            } else if (st == JPEG_AMD_OK) {
                 if (h_orient) d.orient[(size_t)i] = (uint8_t)o;
                 if (h_orient_out) h_orient_out[i] = o;
                 // the data-loader call's view (decode_crops_tensor_mixed): the cheapest denominator, then the rectangle at it
@@ -231,7 +250,8 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     int taps = JPEG_AMD_OK;
     const jpeg_amd_placement judged{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {d.fill[0], d.fill[1], d.fill[2]}, 0};
     JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
-                                 d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps));
+                                 d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps,
+                                 d.matrices.data(), warp, warped));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
@@ -367,5 +387,31 @@ int jpeg_amd_decompress_resized_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *c
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
                             nullptr, nullptr, h_orient, place, h_windows_out, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
+}
+JA_NOTHROW_TAIL
+
+// The two file calls through an affine map ("warped resample"): each file's view and matrix from jpeg_amd_warp_view in pass 0.
+int jpeg_amd_decompress_resized_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                             int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                             const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                             uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                             float *h_matrices_out, int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false,
+                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out, true,
+                            h_matrices, warp, h_matrices_out);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decompress_tensor_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                            int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                            const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                            const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
+                                            jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
+                                            int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
+                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
+                            warp, h_matrices_out);
 }
 JA_NOTHROW_TAIL

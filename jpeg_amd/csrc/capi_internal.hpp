@@ -129,7 +129,21 @@ int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
 int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
                           bool tensor, const uint8_t *h_orient, const jpeg_amd_placement *place, void *d_dst, size_t dst_stride,
-                          int *taps);
+                          int *taps, const float *h_view_matrices = nullptr, const jpeg_amd_warp *warp = nullptr, bool warped = false);
+// "warped resample": what the contract requires of one matrix.
+inline int check_warp_matrix(const float *m)
+{
+    if (!m) return JPEG_AMD_EINVAL;
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(m[k]) || std::fabs(m[k]) > kWarpMaxEntry) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
+// jpeg_amd_decode_warped_mixed (tensor: jpeg_amd_decode_tensor_warped_mixed) behind jpeg_amd_warp_view, for the file calls,
+// whose pass 0 has taken every file's view and m_view already: the views and the matrices against them (capi_view.hip).
+int decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                              const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
+                              int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                              size_t dst_stride);
 // "placed resample": what a placed call refuses of its placement as a whole, and of one image's window on its canvas.
 inline int check_placement(const jpeg_amd_placement &p, int n_images)
 {

@@ -534,6 +534,11 @@ struct ResampleTarget {
     const uint8_t *h_orient = nullptr;   // per image, or nullptr: every image as it is stored
     const jpeg_amd_placement *place = nullptr;
     jpeg_amd_region *h_windows_out = nullptr;   // per image, or nullptr: window(i) writes it
+    // "warped resample": `warped` makes the call one (bilinear, no orientations, no placement); per image the matrix m[6]
+    // against the image AS IT IS STORED at the launch's source (of a view: jpeg_amd_warp_view's m_view), and the call's warp
+    const float *h_matrices = nullptr;
+    const jpeg_amd_warp *warp = nullptr;
+    bool warped = false;
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
     bool oriented = false;   // check() sets it
     std::vector<jpeg_amd_region> windows;   // of a placed call, per image: check() sizes it, window(i) fills it
@@ -548,6 +553,11 @@ struct ResampleTarget {
         if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
         JA_TRY(tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride));
+        if (warped) {
+            if (filter != JPEG_AMD_FILTER_BILINEAR || h_orient || place || !warp) return JPEG_AMD_EINVAL;
+            if (warp->edge != JPEG_AMD_EDGE_FILL && warp->edge != JPEG_AMD_EDGE_REPLICATE) return JPEG_AMD_EINVAL;
+            return n_images > 0 && !h_matrices ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
+        }
         if (!place) return JPEG_AMD_OK;
         JA_TRY(check_placement(*place, n_images));
         windows.assign((size_t)std::max(n_images, 0), jpeg_amd_region{0, 0, 0, 0});
@@ -557,6 +567,7 @@ struct ResampleTarget {
     // Image i's window, w x h as it is STORED: judged behind its orientation (and behind check()), in front of record(i).
     int window(int i, int32_t w, int32_t h)
     {
+        if (warped) return w > kWarpMaxSourceSide || h > kWarpMaxSourceSide ? JPEG_AMD_EINVAL : check_warp_matrix(h_matrices + 6 * (size_t)i);
         if (!place) return JPEG_AMD_OK;
         const OrientedSource s = oriented_source(orientation(i), 0, w, h);
         JA_TRY(placed_window(*place, i, s.w, s.h, out_w, out_h, &windows[(size_t)i]));
@@ -572,12 +583,19 @@ struct ResampleTarget {
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
     size_t record_bytes() const
     {
+        if (warped) return sizeof(WarpRecord);
         if (place) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
         if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
         return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
     }
     int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
+        if (warped) {
+            WarpRecord r{offset, w, h, {}, h_flip && h_flip[i] ? 1u : 0u, warp->edge};
+            std::memcpy(r.m, h_matrices + 6 * (size_t)i, sizeof r.m);
+            std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+            return JPEG_AMD_OK;
+        }
         const OrientedSource s = oriented_source(orientation(i), offset, w, h);   // (1: the stored image)
         const jpeg_amd_region win = place ? windows[(size_t)i] : jpeg_amd_region{0, 0, out_w, out_h};   // (placed: the window's factors)
         const float kx = (float)s.w / (float)win.width, ky = (float)s.h / (float)win.height;
@@ -601,9 +619,11 @@ struct ResampleTarget {
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
         const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
-        const ResampleRecords kind = place ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
+        const ResampleRecords kind = warped  ? ResampleRecords::Warped
+                                     : place ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
         ResampleLaunch l{filter, kind, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride, {0, 0, 0}};
         for (int c = 0; place && c < 3; ++c) l.fill[c] = place->fill[c];
+        for (int c = 0; warped && c < 3; ++c) l.fill[c] = warp->fill[c];
         return launch_resample(stream, l);
     }
 };
@@ -922,9 +942,10 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
 int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
                                           const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient,
-                                          const jpeg_amd_placement *place, void *d_dst, size_t dst_stride, int *taps)
+                                          const jpeg_amd_placement *place, void *d_dst, size_t dst_stride, int *taps,
+                                          const float *h_view_matrices, const jpeg_amd_warp *warp, bool warped)
 {
-    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place};
+    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place, nullptr, h_view_matrices, warp, warped};
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
@@ -1139,5 +1160,133 @@ int jpeg_amd_decode_tensor_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const j
 try {
     return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
                          ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out});
+}
+JA_NOTHROW_TAIL
+
+// ---- "warped resample" ----
+int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const float m[6], int32_t out_w, int32_t out_h,
+                       jpeg_amd_view *view, float m_view[6])
+{
+    if (!view || !m_view || !orientation_valid(orientation)) return JPEG_AMD_EINVAL;
+    JA_TRY(check_warp_matrix(m));
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    JA_TRY(check_layout(layout, -1));
+    // 1. the orientation composed into the matrix: output centres to STORED coordinates
+    const Orientation b = orientation_bits(orientation);
+    const double W = layout->width, H = layout->height;
+    double s[6];
+    for (int k = 0; k < 3; ++k) {
+        s[k] = b.T ? m[3 + k] : m[k];
+        s[3 + k] = b.T ? m[k] : m[3 + k];
+    }
+    if (b.fx) { s[0] = -s[0]; s[1] = -s[1]; s[2] = W - s[2]; }
+    if (b.fy) { s[3] = -s[3]; s[4] = -s[4]; s[5] = H - s[5]; }
+    // 2. the denominator
+    const double m00 = m[0], m01 = m[1], m10 = m[3], m11 = m[4];
+    const double step2 = std::min(m00 * m00 + m10 * m10, m01 * m01 + m11 * m11);
+    int denom = 1;
+    for (int d = 8; d > 1; d /= 2)
+        if ((double)(d * d) <= step2) { denom = d; break; }
+    // 3. against the scaled image
+    jpeg_amd_layout S;
+    JA_TRY(jpeg_amd_scaled_layout(layout, denom, &S));
+    const double f = (double)(8 / denom) / 8.0;
+    for (int k = 0; k < 6; ++k) s[k] = s[k] * f;
+    // 4. the footprint of the canvas
+    const double cx[4] = {0.0, (double)out_w, 0.0, (double)out_w}, cy[4] = {0.0, 0.0, (double)out_h, (double)out_h};
+    double lo[2], hi[2];
+    for (int a = 0; a < 2; ++a) {
+        for (int c = 0; c < 4; ++c) {
+            const double v = (s[3 * a] * cx[c] + s[3 * a + 1] * cy[c]) + s[3 * a + 2];
+            lo[a] = c == 0 ? v : std::min(lo[a], v);
+            hi[a] = c == 0 ? v : std::max(hi[a], v);
+        }
+    }
+    const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
+    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
+    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
+    *view = jpeg_amd_view{denom, jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1}};
+    // 5. against the view
+    s[2] = s[2] - (double)x0;
+    s[5] = s[5] - (double)y0;
+    for (int k = 0; k < 6; ++k) m_view[k] = (float)s[k];
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_warp_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                        const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                        int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_matrices, warp, true});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_warp_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                               const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                               int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                               void *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_matrices, warp, true});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd::capi::decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                              jpeg_amd_color color, const jpeg_amd_view *h_views, const float *h_view_matrices,
+                                              const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
+                                              const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+{
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_view_matrices, warp, true});
+}
+
+namespace {
+
+// jpeg_amd_decode_warped_mixed and its tensor form: every image's view and m_view from jpeg_amd_warp_view, then the route of
+// the resized mixed calls with warp records.
+int warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                 const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
+                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out, float *h_matrices_out, void *d_dst,
+                 size_t dst_stride)
+{
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_matrices)) return JPEG_AMD_EINVAL;
+    const size_t n = (size_t)n_images;
+    std::vector<jpeg_amd_view> views(n);
+    std::vector<float> view_matrices(6 * n);
+    for (size_t i = 0; i < n; ++i) {
+        JA_TRY(jpeg_amd_warp_view(&h_images[i].layout, h_orient ? h_orient[i] : 1, h_matrices + 6 * i, out_w, out_h, &views[i],
+                                  &view_matrices[6 * i]));
+        if (h_views_out) h_views_out[i] = views[i];
+        if (h_matrices_out) std::memcpy(h_matrices_out + 6 * i, &view_matrices[6 * i], 6 * sizeof(float));
+    }
+    return decode_warped_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), view_matrices.data(), warp, out_w, out_h, tensor,
+                                     spec, h_flip, d_dst, dst_stride);
+}
+
+}  // namespace
+
+int jpeg_amd_decode_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                 jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                 const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
+                                 float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, false, nullptr, nullptr,
+                        h_views_out, h_matrices_out, d_pixels, pixel_stride);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                        const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                                        float *h_matrices_out, void *d_dst, size_t dst_stride)
+try {
+    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
+                        h_views_out, h_matrices_out, d_dst, dst_stride);
 }
 JA_NOTHROW_TAIL

@@ -170,7 +170,8 @@ hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int1
 // n_images pixel images (rows of 3 w bytes, unpadded) resampled to out_w x out_h in ONE launch, by the contracts of
 // include/jpeg_amd.h: through one of three filters ("resized decode", "antialiased resample", "bicubic resample"), read as
 // stored or oriented ("oriented resample"), to bytes or to tensor elements ("tensor output").  One record per image, made on
-// the host; which of the six kinds follows from the filter and from whether the call is oriented or placed.
+// the host; which of the six kinds follows from the filter and from whether the call is oriented or placed.  A seventh kind,
+// the WarpRecord ("warped resample"), takes the image through an affine map instead of a scale factor per axis.
 struct ResizeRecord {      // bilinear
     uint64_t offset;   // bytes from d_src
     int32_t  w, h;     // > 0
@@ -210,6 +211,18 @@ struct PlacedAntialiasRecord : OrientedAntialiasRecord {
     int32_t x0, y0, ww, wh;
 };
 static_assert(sizeof(PlacedResizeRecord) == 64 && sizeof(PlacedAntialiasRecord) == 80, "record layout");
+// Warped ("warped resample"): the stored image and the matrix that takes the centre of an output pixel to a point of it; there
+// are no scale factors and no tables.  edge is the launch's JPEG_AMD_EDGE_* in every record of it.
+struct WarpRecord {
+    uint64_t offset;   // bytes from d_src
+    int32_t  w, h;     // > 0, at most kWarpMaxSourceSide
+    float    m[6];     // m00, m01, m02, m10, m11, m12: finite, at most kWarpMaxEntry in magnitude
+    uint32_t flip;     // as ResizeRecord's
+    int32_t  edge;
+};
+static_assert(sizeof(WarpRecord) == 48, "record layout");
+constexpr int   kWarpMaxSourceSide = 1 << 24;    // (float)w and (float)h are exact
+constexpr float kWarpMaxEntry = 1073741824.0f;   // 2^30: with an output side of at most 2^30 no coordinate overflows
 constexpr int   kResizeMaxSide = 1 << 30;        // of the output: the kernels' pixel indices are int
 constexpr float kAntialiasMaxScale = 16.0f;
 constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
@@ -220,7 +233,7 @@ uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the la
 // (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted and stored in spec->layout.  A spec is
 // valid (jpeg_amd_tensor_extent).  hipErrorInvalidValue: an extent or a tile count past the limits above, null records, or a
 // filter, dtype or layout that no kernel exists for.
-enum class ResampleRecords : int { Stored, Oriented, Placed };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms
+enum class ResampleRecords : int { Stored, Oriented, Placed, Warped };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms; WarpRecord (bilinear only)
 struct ResampleLaunch {
     int filter;                        // JPEG_AMD_FILTER_*
     ResampleRecords records;           // the kind of every record of the launch
@@ -231,7 +244,7 @@ struct ResampleLaunch {
     int out_w, out_h;
     void *d_dst;
     size_t dst_stride;
-    uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window
+    uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window; Warped: of a tap outside the image
 };
 hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l);
 

@@ -12,6 +12,8 @@
 // k_resize_placed_bytes, k_resize_placed_tensor<T, CHW>, k_tables_placed_bytes<Filter>, k_tables_placed_tensor<Filter, T, CHW>:
 //   the same walks over PlacedResizeRecords / PlacedAntialiasRecords ("placed resample") with the same sinks; their arguments
 //   end with the launch's fill.
+// k_warp_bytes, k_warp_tensor<T, CHW>: "warped resample" -- warp_walk (warp.hpp) over WarpRecords with the same two sinks and
+//   the placed kernels' arguments; no tables, no LDS.
 // The byte kernels never flip (the records' flip is not read); the tensor kernels flip where the record says so, after the
 // orientation: the flip mirrors the OUTPUT columns.
 //
@@ -30,6 +32,7 @@
 #include "kernels.hpp"
 #include "resample.hpp"
 #include "tensor_sink.hpp"
+#include "warp.hpp"
 
 namespace jpeg_amd {
 
@@ -237,6 +240,22 @@ __global__ __launch_bounds__(kThreads) void k_tables_placed_tensor(PlacedTensorA
     }, a.fill);
 }
 
+__global__ __launch_bounds__(kThreads) void k_warp_bytes(PlacedBytesArgs<WarpRecord> a)
+{
+    uint8_t *dst = image_dst(a);
+    warp_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+}
+
+template <typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_warp_tensor(PlacedTensorArgs<T, WarpRecord> a)
+{
+    T *dst = image_dst(a);
+    const size_t plane = image_plane(a);
+    warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+    });
+}
+
 // ---- the launcher ----
 
 // f(T{}, std::bool_constant<CHW>{}) for the element type and the layout of spec, or what no kernel exists for.
@@ -260,17 +279,18 @@ struct Bilinear;   // in place of a filter of antialias.hpp: resample_walk, whos
 template <typename Filter, typename Record>
 hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const ResampleArgs &head, dim3 grid)
 {
+    constexpr bool warped = std::is_same<Record, WarpRecord>::value;   // (the placed kernels' args: records in tab_records, a fill)
     constexpr bool bilinear = std::is_same<Filter, Bilinear>::value, oriented = std::is_same<Record, OrientedResizeRecord>::value;
     constexpr bool placed = std::is_same<Record, PlacedResizeRecord>::value || std::is_same<Record, PlacedAntialiasRecord>::value;
     const auto run = [&](auto kernel, auto a) {   // a: the kernel's args, zeroed
         static_cast<ResampleArgs &>(a) = head;
-        if constexpr (bilinear)
+        if constexpr (bilinear && !warped)
             a.records = static_cast<const Record *>(l.d_records);
         else
             a.tab_records = static_cast<const Record *>(l.d_records);
         a.dst = static_cast<decltype(a.dst)>(l.d_dst);
         a.dst_stride = l.dst_stride;
-        if constexpr (placed) a.fill = (uint32_t)l.fill[0] | (uint32_t)l.fill[1] << 8 | (uint32_t)l.fill[2] << 16;
+        if constexpr (placed || warped) a.fill = (uint32_t)l.fill[0] | (uint32_t)l.fill[1] << 8 | (uint32_t)l.fill[2] << 16;
         if constexpr (!std::is_same<decltype(a.dst), uint8_t *>::value) {
             for (int c = 0; c < 3; ++c) {
                 a.mean[c] = l.spec->mean[c];
@@ -283,7 +303,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
     if (l.spec) {
         return with_element(*l.spec, [&](auto t, auto chw) {
             using T = decltype(t);
-            if constexpr (placed && bilinear)
+            if constexpr (warped)
+                return run(k_warp_tensor<T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+            else if constexpr (placed && bilinear)
                 return run(k_resize_placed_tensor<T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (placed)
                 return run(k_tables_placed_tensor<Filter, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
@@ -293,7 +315,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
                 return run(k_tables_tensor<Filter, Record, T, decltype(chw)::value>, RecordTensorArgs<T, Record>{});
         });
     }
-    if constexpr (placed && bilinear)
+    if constexpr (warped)
+        return run(k_warp_bytes, PlacedBytesArgs<Record>{});
+    else if constexpr (placed && bilinear)
         return run(k_resize_placed_bytes, PlacedBytesArgs<Record>{});
     else if constexpr (placed)
         return run(k_tables_placed_bytes<Filter>, PlacedBytesArgs<Record>{});
@@ -330,6 +354,8 @@ hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l)
     ResampleArgs head{};
     dim3 grid;
     if (const hipError_t e = resample_launch(l.n_images, l.d_src, nullptr, l.out_w, l.out_h, head, grid)) return e;
+    if (l.records == ResampleRecords::Warped)   // "warped resample": the two-tap filter only
+        return l.filter == JPEG_AMD_FILTER_BILINEAR ? launch_kernel<Bilinear, WarpRecord>(stream, l, head, grid) : hipErrorInvalidValue;
     switch (l.filter) {
     case JPEG_AMD_FILTER_BILINEAR: return launch_filter<Bilinear, ResizeRecord, OrientedResizeRecord, PlacedResizeRecord>(stream, l, head, grid);
     case JPEG_AMD_FILTER_ANTIALIAS: return launch_filter<TriangleFilter, AntialiasRecord, OrientedAntialiasRecord, PlacedAntialiasRecord>(stream, l, head, grid);

@@ -1459,6 +1459,82 @@ int jpeg_amd_decompress_tensor_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *co
                                             jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
                                             int32_t *h_orient_out);
 
+/* ---- colour stage: an affine map of (R, G, B) per image between the resample and the tensor output -------------------------
+ *
+ * Brightness, contrast, saturation and hue jitter, a drop to grey, BGR order, a single luma value: each is one affine map of
+ * a pixel's (R, G, B) -- a 3 x 3 matrix and an offset -- followed by a clamp, and so is any composition of them.  The calls
+ * below apply one such map per image inside the resample launch of the tensor calls, between the byte the resample defines
+ * and the (u - mean) * scale of "tensor output".
+ *
+ * THE CONTRACT.  The colour stage defines no resample arithmetic.  Let u(i, y, xs, c) be the byte the underlying call -- the
+ * placed resample with any of the three filters, or the warped resample -- defines for image i at stored column x, after the
+ * flip (xs = flip ? out_w - 1 - x : x); fill pixels of a placement or a warp count as pixels.  With
+ * r, g, b = (float)u(.., 0), (float)u(.., 1), (float)u(.., 2) and image i's twelve binary32 numbers k[c][0 .. 3], for every
+ * channel c, every statement ONE binary32 operation and nothing contracted:
+ *     p = ((k[c][0] * r) + (k[c][1] * g)) + (k[c][2] * b)
+ *     q = p + k[c][3]
+ *     q = q < lo ? lo : q;   q = q > hi ? hi : q        (lo, hi per call, in byte units)
+ *     t = q - mean[c];  v = t * scale[c];  element = v converted                  ("tensor output", unchanged)
+ * The clamp is two comparisons and selects, so that it is defined for zeros of either sign: -0 is not below +0 and stays.
+ * lo = -infinity and hi = +infinity clamp nothing: q is finite.
+ *
+ * CONSEQUENCES.  The identity matrix with offset 0 and no clamp is the underlying tensor call bit for bit (1 * r, + 0 * g,
+ * + 0 * b and + 0 are exact for r, g, b >= 0, and give +0 for 0).  A permutation matrix is that call with the channels
+ * permuted, bit for bit (BGR).  Three equal rows give three equal q (greyscale).  The fill is transformed like any pixel.
+ *
+ * EINVAL, judged with the target, before anything is enqueued and with the context judged last: an entry that is not finite
+ * or exceeds 2^30 in magnitude (so that no NaN or infinity can arise); lo or hi that is a NaN; lo > hi; a null h_matrices
+ * with n_images > 0.  (The colour stage exists for the tensor calls only: the byte calls have no colour forms.) */
+typedef struct {
+    const float *h_matrices;   /* [n_images][12], host: image i's row c is k[c][0 .. 3]; copied before the call returns */
+    float lo, hi;              /* the clamp, in byte units; -INFINITY and INFINITY: none */
+} jpeg_amd_colour;
+
+/* Each call takes the arguments of the call it is named after and `colour` in front of the output pointer: _resize_colour_
+ * tensor_batch of jpeg_amd_resize_placed_tensor_batch, _decode_tensor_colour_mixed of jpeg_amd_decode_tensor_placed_mixed,
+ * _decompress_tensor_colour_mixed of jpeg_amd_decompress_tensor_placed_mixed, _warp_colour_tensor_batch of
+ * jpeg_amd_warp_tensor_batch, and the two *_warped_colour_mixed calls of the *_warped_mixed tensor calls.  With colour == NULL
+ * each IS that call, status for status and bit for bit.  With a colour the route is that call's -- one resample launch per
+ * call or chunk, the colour records in the same upload as the resample records -- and a call without a placement writes
+ * placed records whose window is the whole canvas, which "placed resample" makes the oriented and the stored call. */
+int jpeg_amd_resize_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                        const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out,
+                                        const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+int jpeg_amd_decode_tensor_colour_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                        const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                        jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst,
+                                        size_t dst_stride);
+int jpeg_amd_decompress_tensor_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                            int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                            const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h,
+                                            int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                            const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                            jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst,
+                                            size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                            int32_t *h_orient_out);
+int jpeg_amd_warp_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                      const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                                      int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                      const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+int jpeg_amd_decode_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                               jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                               const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                               const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                               jpeg_amd_view *h_views_out, float *h_matrices_out,
+                                               const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                                   int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                                   const uint8_t *h_orient, const float *h_matrices,
+                                                   const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                                   const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                                   const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
+                                                   jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                                   float *h_matrices_out, int32_t *h_orient_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,19 @@ SIGNATURES = {
                                                            C.c_int32, _p, C.c_size_t, _p, _p, _p, _p]),
     "jpeg_amd_decompress_tensor_warped_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int32,
                                                           C.c_int32, _p, _p, _p, C.c_size_t, _p, _p, _p, _p]),
+    # "colour stage": the arguments of the call each is named after, and the colour in front of the output pointer
+    "jpeg_amd_resize_colour_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, C.c_int32, C.c_int32, C.c_int, _p, _p, _p, _p,
+                                                      _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_colour_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_int32, C.c_int32, C.c_int, _p, _p,
+                                                      _p, _p, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_tensor_colour_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int32, C.c_int32,
+                                                          C.c_int, _p, _p, _p, _p, _p, _p, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_warp_colour_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
+                                                    C.c_size_t]),
+    "jpeg_amd_decode_tensor_warped_colour_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int32, C.c_int32, _p,
+                                                             _p, _p, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_tensor_warped_colour_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int32,
+                                                                 C.c_int32, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, _p]),
 }
 
 
@@ -221,6 +234,11 @@ class Placement(C.Structure):
 class Warp(C.Structure):
     """struct jpeg_amd_warp"""
     _fields_ = [("edge", C.c_int32), ("fill", C.c_uint8 * 3)]
+
+
+class Colour(C.Structure):
+    """struct jpeg_amd_colour"""
+    _fields_ = [("h_matrices", C.c_void_p), ("lo", C.c_float), ("hi", C.c_float)]
 
 
 class View(C.Structure):

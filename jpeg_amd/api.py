@@ -685,6 +685,66 @@ def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
     return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
 
 
+_GREY = (0.2989, 0.587, 0.114)                     # torchvision's rgb_to_grayscale
+_RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.5959, -0.2746, -0.3213), (0.2115, -0.5227, 0.3112))
+
+
+def colour_matrix(brightness: float = 1.0, contrast: float = 1.0, saturation: float = 1.0, hue: float = 0.0, pivot: float = 128.0,
+                  grey: bool = False, order: str = "rgb") -> np.ndarray:
+    """One image's matrix for colour= of the tensor calls (include/jpeg_amd.h, "colour stage"): float32 [3, 4], row c the
+    three factors of (R, G, B) and the offset of output channel c, in byte units.  The four jitter operations compose into
+    B . C . S . H, the hue rotation applied to the pixel first:
+      hue: a rotation of the I/Q plane of YIQ by `hue` TURNS (I' = cos I - sin Q, Q' = sin I + cos Q), written as
+        identity + inverse(T) (R - identity) T so that hue = 0 is the identity exactly;
+      saturation: s x + (1 - s) L x, every row of L torchvision's grey weights (0.2989, 0.587, 0.114): the linear form of
+        adjust_saturation (which clamps to the value range afterwards; here colour_clamp does that, once, at the end);
+      contrast: c x + (1 - c) pivot.  torchvision's adjust_contrast pivots on the grey mean of the image itself, which this
+        stage cannot know: the caller supplies `pivot` (the default is mid-grey; pass the image's mean to match torchvision);
+      brightness: b x.
+    grey: every output channel is L of the result (RandomGrayscale); order "bgr": the output channels reversed.  Both are
+    multiplied on from the left, last.  Composed in double and rounded to float32 once; the defaults give the identity exactly."""
+    if order not in ("rgb", "bgr"):
+        raise ValueError('order: "rgb" or "bgr"')
+
+    def affine(lin, offset=(0.0, 0.0, 0.0)):
+        m = np.eye(4)
+        m[:3, :3] = lin
+        m[:3, 3] = offset
+        return m
+
+    t = np.array(_RGB_TO_YIQ, np.float64)
+    a = 2.0 * math.pi * float(hue)
+    rot = np.array([[0.0, 0.0, 0.0], [0.0, math.cos(a) - 1.0, -math.sin(a)], [0.0, math.sin(a), math.cos(a) - 1.0]])
+    luma = np.array([_GREY] * 3, np.float64)
+    s, c, b = float(saturation), float(contrast), float(brightness)
+    h_m = affine(np.eye(3) + np.linalg.inv(t) @ rot @ t)
+    s_m = affine(s * np.eye(3) + (1.0 - s) * luma)
+    c_m = affine(c * np.eye(3), [(1.0 - c) * float(pivot)] * 3)
+    b_m = affine(b * np.eye(3))
+    m = b_m @ c_m @ s_m @ h_m
+    if grey:
+        m = affine(luma) @ m
+    if order == "bgr":
+        m = affine(np.eye(3)[::-1]) @ m
+    return np.ascontiguousarray((m[:3] + 0.0).astype(np.float32))
+
+
+def _colour(colour, colour_clamp, n: int):
+    """colour=, colour_clamp= of the tensor calls -> (struct jpeg_amd_colour, keep), or (None, None) for colour=None (today's
+    entry point).  colour: [n, 3, 4] or [n, 12]; colour_clamp: (lo, hi) in byte units, None: no clamp."""
+    if colour is None:
+        if colour_clamp is not None:
+            raise ValueError("colour_clamp: only together with colour")
+        return None, None
+    k = np.ascontiguousarray(np.asarray(colour, np.float32).reshape(-1, 12))
+    if k.shape[0] != n:
+        raise ValueError("colour: one matrix [3, 4] per image")
+    lo, hi = (-math.inf, math.inf) if colour_clamp is None else (float(colour_clamp[0]), float(colour_clamp[1]))
+    c = _lib.Colour()
+    c.h_matrices, c.lo, c.hi = k.ctypes.data, lo, hi
+    return c, k
+
+
 def _decode_spectral(data: np.ndarray, scans: int = 0):
     info = inspect(data)
     planes = [np.empty((info.units_y[c], info.units_x[c], 64), np.int16) for c in range(info.ncomponents)]
@@ -1173,18 +1233,28 @@ def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, co
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                          cosite: bool = False, filter: str = "bilinear", orientations=None, place=None, anchor="centre",
-                         fill=(0, 0, 0)):
+                         fill=(0, 0, 0), colour=None, colour_clamp=None):
     """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
     as decode_views_mixed, then as decode_tensors, `filter` ("bilinear" | "antialias" | "bicubic") included.  orientations: as in decode_resized_mixed
     (jpeg_amd_decode_tensor_oriented_mixed); a flip mirrors the output after the orientation.
     place / anchor / fill: as in resize (jpeg_amd_decode_tensor_placed_mixed); a flip mirrors the whole canvas.
+    colour / colour_clamp: as in resize_tensor (jpeg_amd_decode_tensor_colour_mixed).
     Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
     n = vs.shape[0]
     h_orient = _orientations(orientations, n)
     placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if tint is not None:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_colour_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
+                                                                  ht, code, C.byref(spec), h_flip, h_orient,
+                                                                  None if placement is None else C.byref(placement), h_windows,
+                                                                  C.byref(tint), out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_colour_mixed", ctx.handle)
+        res = _tensor_view(out, n, wt, ht, spec)
+        return res if placement is None else (res, _windows_array(h_windows, n))
     if placement is not None:
         _lib.check(_lib.lib().jpeg_amd_decode_tensor_placed_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
                                                                   ht, code, C.byref(spec), h_flip, h_orient, C.byref(placement),
@@ -1205,13 +1275,13 @@ def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.Te
 
 def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                               cosite: bool = False, filter: str = "bilinear", orientations=None, place=None, anchor="centre",
-                              fill=(0, 0, 0)):
+                              fill=(0, 0, 0), colour=None, colour_clamp=None):
     """The data-loader call over files of different sizes and layouts: per image a rectangle (x, y, width, height) of ITS
     full-size image, the view chosen as decode_crops_tensor chooses it -- view_denom, then view_of_source on that image's own
     size -- through decode_tensors_mixed, with its `filter`.  orientations: per image an EXIF orientation 1 .. 8; the rectangles are then
     rectangles of the ORIENTED images: the denominator is chosen for the oriented rectangle and the view is that of the stored
     rectangle orient_region maps it to.  place / anchor / fill: as in resize; "fit" fits the (oriented) rectangle, and the
-    denominator is chosen against the window, not the canvas.
+    denominator is chosen against the window, not the canvas.  colour / colour_clamp: as in decode_tensors_mixed.
     Returns (tensor, the views as int32 [n, 5]: stored scaled coordinates), and with `place` the windows as int32 [n, 4]."""
     spectrals = list(spectrals)
     regs = np.asarray(source_regions, np.int64).reshape(-1, 4)
@@ -1232,7 +1302,8 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
             stored = regs[i].tolist() if orientations is None else orient_region(orientations[i], s.size, regs[i].tolist())
             views[i] = (denom,) + view_of_source(s.size, denom, stored)
         out, applied = decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
-                                            orientations=orientations, place=windows, anchor=anchor, fill=fill)
+                                            orientations=orientations, place=windows, anchor=anchor, fill=fill, colour=colour,
+                                            colour_clamp=colour_clamp)
         return out, views, applied
     for i, s in enumerate(spectrals):
         if orientations is None:
@@ -1241,7 +1312,7 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
             denom = view_denom(regs[i, 2:], out_size)
             views[i] = (denom,) + view_of_source(s.size, denom, orient_region(orientations[i], s.size, regs[i].tolist()))
     return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
-                                orientations=orientations), views
+                                orientations=orientations, colour=colour, colour_clamp=colour_clamp), views
 
 
 def _warped_mixed_args(ctx: Context, spectrals, matrices, orientations):
@@ -1269,12 +1340,21 @@ def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, 
 
 
 def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                                cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0)):
-    """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_mixed); flips, spec as in
-    warp_tensor.  Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
+                                cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None, colour_clamp=None):
+    """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_mixed); flips, spec,
+    colour and colour_clamp (jpeg_amd_decode_tensor_warped_colour_mixed) as in warp_tensor.
+    Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
     n, h_images, h_views, m, h_orient, m_out, keep = _warped_mixed_args(ctx, spectrals, matrices, orientations)
     w = _warp(edge, fill)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if tint is not None:
+        _lib.check(_lib.lib().jpeg_amd_decode_tensor_warped_colour_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code,
+                                                                         h_orient, m.ctypes.data, C.byref(w), wt, ht, C.byref(spec),
+                                                                         h_flip, h_views, m_out.ctypes.data, C.byref(tint),
+                                                                         out.data_ptr(), stride),
+                   "jpeg_amd_decode_tensor_warped_colour_mixed", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
     _lib.check(_lib.lib().jpeg_amd_decode_tensor_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
                                                               m.ctypes.data, C.byref(w), wt, ht, C.byref(spec), h_flip, h_views,
                                                               m_out.ctypes.data, out.data_ptr(), stride),
@@ -1313,7 +1393,7 @@ def _views_array(h_views, n) -> np.ndarray:
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
                        cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None, place=None,
-                       anchor="centre", fill=(0, 0, 0), warp=None, edge="fill"):
+                       anchor="centre", fill=(0, 0, 0), warp=None, edge="fill", colour=None, colour_clamp=None):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
@@ -1333,25 +1413,47 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     warp / edge / fill: per file a matrix [6] in the coordinates of its UPRIGHT full-size image, as in decode_warped_mixed
     (jpeg_amd_decompress_tensor_warped_mixed; include/jpeg_amd.h, "warped resample"); not together with source_regions, place
     or a filter other than "bilinear" (ValueError).  The views that come back are warp_view's, and the matrices applied to them
-    come back as the last item, float32 [n, 6]."""
+    come back as the last item, float32 [n, 6].
+    colour / colour_clamp: as in resize_tensor, per file (jpeg_amd_decompress_tensor_colour_mixed, with `warp`
+    jpeg_amd_decompress_tensor_warped_colour_mixed); what comes back is what the call without them returns."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
     h_orient = _orientations(orientation, n, exif=True)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
     if warp is not None:
         m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
         wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
         applied = (C.c_int32 * max(n, 1))()
-        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                      color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
-                                                                      C.byref(spec), h_flip, out.data_ptr(), stride, infos, h_views,
-                                                                      m_out.ctypes.data, applied),
-                   "jpeg_amd_decompress_tensor_warped_mixed", ctx.handle)
+        if tint is not None:
+            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_colour_mixed(ctx.handle, ptrs, sizes, n, int(threads),
+                                                                                 1 if cosite else 0, color.code, h_orient, m.ctypes.data,
+                                                                                 C.byref(w), wt, ht, C.byref(spec), h_flip, C.byref(tint),
+                                                                                 out.data_ptr(), stride, infos, h_views,
+                                                                                 m_out.ctypes.data, applied),
+                       "jpeg_amd_decompress_tensor_warped_colour_mixed", ctx.handle)
+        else:
+            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                          color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
+                                                                          C.byref(spec), h_flip, out.data_ptr(), stride, infos, h_views,
+                                                                          m_out.ctypes.data, applied),
+                       "jpeg_amd_decompress_tensor_warped_mixed", ctx.handle)
         res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
         if h_orient is not None:
             res += (np.array(applied[:n], np.int32),)
         return res + (m_out,)
     placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if tint is not None:
+        applied = (C.c_int32 * max(n, 1))()
+        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_colour_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
+                                                                      color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
+                                                                      None if placement is None else C.byref(placement), h_windows,
+                                                                      C.byref(tint), out.data_ptr(), stride, infos, h_views, applied),
+                   "jpeg_amd_decompress_tensor_colour_mixed", ctx.handle)
+        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
+        if h_orient is not None:
+            res += (np.array(applied[:n], np.int32),)
+        return res if placement is None else res + (_windows_array(h_windows, n),)
     if placement is not None:
         applied = (C.c_int32 * max(n, 1))()
         _lib.check(_lib.lib().jpeg_amd_decompress_tensor_placed_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
@@ -1417,18 +1519,30 @@ def decompress_resized(ctx: Context, sources, out_size, source_regions=None, col
 
 
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None,
-                  place=None, anchor="centre", fill=(0, 0, 0)):
+                  place=None, anchor="centre", fill=(0, 0, 0), colour=None, colour_clamp=None):
     """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
     [n, Ht, Wt, 3] of spec's dtype, in one launch.  orientations: as in resize (jpeg_amd_resize_oriented_tensor_batch); a flip
     mirrors the output after the orientation.  place / anchor / fill: as in resize (jpeg_amd_resize_placed_tensor_batch); a
-    padded element is the fill byte through `spec`, and a flip mirrors the whole canvas, window position included."""
+    padded element is the fill byte through `spec`, and a flip mirrors the whole canvas, window position included.
+    colour / colour_clamp: per image a matrix [3, 4] (colour_matrix makes one; [n, 3, 4] or [n, 12]) applied to every pixel's
+    (R, G, B), fill pixels included, in front of spec's mean, then clamped to colour_clamp = (lo, hi) in byte units (None: no
+    clamp), in the same launch (jpeg_amd_resize_colour_tensor_batch; include/jpeg_amd.h, "colour stage")."""
     code = _filter(filter)
     images = list(images)
     n = len(images)
     h_orient = _orientations(orientations, n)
     placement, h_windows, keep = _placement(place, anchor, fill, n)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if tint is not None:
+        _lib.check(_lib.lib().jpeg_amd_resize_colour_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
+                                                                  C.byref(spec), h_flip, h_orient,
+                                                                  None if placement is None else C.byref(placement), h_windows,
+                                                                  C.byref(tint), out.data_ptr(), stride),
+                   "jpeg_amd_resize_colour_tensor_batch", ctx.handle)
+        res = _tensor_view(out, n, wt, ht, spec)
+        return res if placement is None else (res, _windows_array(h_windows, n))
     if placement is not None:
         _lib.check(_lib.lib().jpeg_amd_resize_placed_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
                                                                   C.byref(spec), h_flip, h_orient, C.byref(placement), h_windows,
@@ -1462,15 +1576,23 @@ def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
     return out.view(n, ht, wt, 3)
 
 
-def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0)):
+def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
+                colour=None, colour_clamp=None):
     """warp with the output stage of the tensor calls (jpeg_amd_warp_tensor_batch): the warped image mirrored along x where
-    flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  Returns one tensor
-    [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  colour / colour_clamp: as
+    in resize_tensor (jpeg_amd_warp_colour_tensor_batch).  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     images = list(images)
     n = len(images)
     m, w = _matrices(matrices, n), _warp(edge, fill)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
     src, src_stride, extents = _pack_images(ctx, images)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    if tint is not None:
+        _lib.check(_lib.lib().jpeg_amd_warp_colour_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data,
+                                                                C.byref(w), wt, ht, C.byref(spec), h_flip, C.byref(tint),
+                                                                out.data_ptr(), stride),
+                   "jpeg_amd_warp_colour_tensor_batch", ctx.handle)
+        return _tensor_view(out, n, wt, ht, spec)
     _lib.check(_lib.lib().jpeg_amd_warp_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt,
                                                      ht, C.byref(spec), h_flip, out.data_ptr(), stride),
                "jpeg_amd_warp_tensor_batch", ctx.handle)

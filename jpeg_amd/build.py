@@ -41,9 +41,12 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
 # bytes: a spill there is a mistake in the source, so it is held to the strict rule; k_resize_tensor<false, ...> (the stored
 # images'), the same walk with another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise; k_expand_mixed, an
 # entry walk and one store, likewise; k_warp_bytes and k_warp_tensor (52 to 57 VGPRs, no LDS), whose every lane computes its own
-# tap addresses, likewise.  A source may stand in both tables, with other fragments.
+# tap addresses, likewise; the kernels with the colour stage (a leading template flag: ILb1E; those of k_warp_tensor stand
+# under k_warp_), which keep twelve more numbers in SGPRs and nine more operations per pixel in flight, likewise.  A source
+# may stand in both tables, with other fragments.
 NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused",
-              "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E", "k_warp_"),
+              "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E", "k_warp_", "k_resize_placed_tensorILb1E",
+                                       "k_tables_placed_tensorILb1E"),
               "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform",

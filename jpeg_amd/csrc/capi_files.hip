@@ -51,6 +51,7 @@ struct FilesDecode : FileBatch {
     bool warped = false;                       // "warped resample": pass 0's m_view per file go to the mixed call with the call's warp
     std::vector<float> matrices;
     const jpeg_amd_warp *warp = nullptr;
+    const jpeg_amd_colour *colour = nullptr;   // "colour stage": the call's, of which a chunk takes its files' matrices
     void *d_dst;
     size_t dst_stride, elem_bytes;
     std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
@@ -135,12 +136,15 @@ int FilesDecode::submit(int k)
     const jpeg_amd_placement here{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, placed ? windows.data() + ch.i0 : nullptr,
                                   {fill[0], fill[1], fill[2]}, 0};
     const jpeg_amd_placement *place = placed ? &here : nullptr;
+    const jpeg_amd_colour tint{colour ? colour->h_matrices + 12 * (size_t)ch.i0 : nullptr, colour ? colour->lo : 0.0f, colour ? colour->hi : 0.0f};
+    const jpeg_amd_colour *chunk_colour = colour ? &tint : nullptr;   // (nullptr: the calls without a colour stage, as they stand)
     if (warped)
         JA_TRY(decode_warped_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 6 * (size_t)ch.i0, warp,
-                                         out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride));
+                                         out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride, chunk_colour));
     else if (tensor)
-        JA_TRY(jpeg_amd_decode_tensor_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
-                                                   h_flip ? h_flip + ch.i0 : nullptr, h_orient, place, nullptr, d_out, dst_stride));
+        JA_TRY(jpeg_amd_decode_tensor_colour_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
+                                                   h_flip ? h_flip + ch.i0 : nullptr, h_orient, place, nullptr, chunk_colour, d_out,
+                                                   dst_stride));
     else
         JA_TRY(jpeg_amd_decode_resized_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
                                                     h_orient, place, nullptr, static_cast<uint8_t *>(d_out), dst_stride));
@@ -164,7 +168,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                      const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
                      jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                      int32_t *h_orient_out, bool warped = false, const float *h_matrices = nullptr, const jpeg_amd_warp *warp = nullptr,
-                     float *h_matrices_out = nullptr)
+                     float *h_matrices_out = nullptr, const jpeg_amd_colour *colour = nullptr)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
@@ -174,6 +178,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     d.ctx = ctx; d.h_jpeg = h_jpeg; d.nbytes = nbytes; d.n_images = n_images; d.cosited = cosited; d.color = color;
     d.out_w = out_w; d.out_h = out_h; d.filter = filter; d.tensor = tensor; d.spec = spec; d.h_flip = h_flip; d.d_dst = d_dst;
     d.dst_stride = dst_stride;
+    d.colour = colour;
     d.files.resize((size_t)n_images);
     // (1 behind a refused file: the mixed call's judgement stops in front of it; warped: the orientation goes into the matrix)
     if (h_orient && !warped) d.orient.assign((size_t)n_images, 1);
@@ -251,7 +256,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     const jpeg_amd_placement judged{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {d.fill[0], d.fill[1], d.fill[2]}, 0};
     JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
                                  d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps,
-                                 d.matrices.data(), warp, warped));
+                                 d.matrices.data(), warp, warped, colour));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
@@ -413,5 +418,40 @@ try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
                             spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
                             warp, h_matrices_out);
+}
+JA_NOTHROW_TAIL
+
+// The two file calls to a tensor with the "colour stage": with colour == nullptr each is the call it is named after.
+int jpeg_amd_decompress_tensor_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                            int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
+                                            int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
+                                            const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                            jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
+                                            jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
+try {
+    if (!colour)
+        return jpeg_amd_decompress_tensor_placed_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h,
+                                                       filter, spec, h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views,
+                                                       h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
+                            h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views, h_orient_out, false, nullptr,
+                            nullptr, nullptr, colour);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decompress_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                                   int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                                   const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                                   const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const jpeg_amd_colour *colour,
+                                                   void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                                   float *h_matrices_out, int32_t *h_orient_out)
+try {
+    if (!colour)
+        return jpeg_amd_decompress_tensor_warped_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_orient, h_matrices, warp,
+                                                       out_w, out_h, spec, h_flip, d_dst, dst_stride, h_info, h_views, h_matrices_out,
+                                                       h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
+                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
+                            warp, h_matrices_out, colour);
 }
 JA_NOTHROW_TAIL

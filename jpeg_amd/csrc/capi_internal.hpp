@@ -125,11 +125,22 @@ int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
 // context, for the file calls, which judge a call before its planes exist (the images' pointers only have to be non-null):
 // of the first `judged` images of a call of n_images, in the mixed call's order; *taps: with judged == n_images the verdict on
 // the antialiasing filter's tap limit, which that call gives last (capi_view.hip).  h_orient: as in the *_oriented_mixed calls
-// (n_images values, or nullptr); place: as in the *_placed_mixed calls (or nullptr).
+// (n_images values, or nullptr); place: as in the *_placed_mixed calls (or nullptr); colour: as in the *_colour_mixed calls
+// (or nullptr).
 int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
                           bool tensor, const uint8_t *h_orient, const jpeg_amd_placement *place, void *d_dst, size_t dst_stride,
-                          int *taps, const float *h_view_matrices = nullptr, const jpeg_amd_warp *warp = nullptr, bool warped = false);
+                          int *taps, const float *h_view_matrices = nullptr, const jpeg_amd_warp *warp = nullptr, bool warped = false,
+                          const jpeg_amd_colour *colour = nullptr);
+// "colour stage": what the contract requires of a call's colour, judged with the target.
+inline int check_colour(const jpeg_amd_colour &c, int n_images)
+{
+    if (std::isnan(c.lo) || std::isnan(c.hi) || c.lo > c.hi) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && !c.h_matrices) return JPEG_AMD_EINVAL;
+    for (size_t k = 0; n_images > 0 && k < 12 * (size_t)n_images; ++k)
+        if (!std::isfinite(c.h_matrices[k]) || std::fabs(c.h_matrices[k]) > kColourMaxEntry) return JPEG_AMD_EINVAL;
+    return JPEG_AMD_OK;
+}
 // "warped resample": what the contract requires of one matrix.
 inline int check_warp_matrix(const float *m)
 {
@@ -143,7 +154,7 @@ inline int check_warp_matrix(const float *m)
 int decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                               const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
                               int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
-                              size_t dst_stride);
+                              size_t dst_stride, const jpeg_amd_colour *colour = nullptr);
 // "placed resample": what a placed call refuses of its placement as a whole, and of one image's window on its canvas.
 inline int check_placement(const jpeg_amd_placement &p, int n_images)
 {

@@ -539,6 +539,13 @@ struct ResampleTarget {
     const float *h_matrices = nullptr;
     const jpeg_amd_warp *warp = nullptr;
     bool warped = false;
+    // "colour stage": the call's colour, or nullptr, which is the call without one -- its records, its kernels.  With one,
+    // check() judges it with the target (a byte target has no colour stage), every record that is not a warp record is the
+    // PLACED one of its filter -- without a placement its window is the whole canvas, which "placed resample" makes the
+    // oriented and the stored call bit for bit -- and the ColourRecords go up behind the call's resample records, 16-byte
+    // aligned, in the same copy.
+    const jpeg_amd_colour *colour = nullptr;
+    int n_call = 0;          // the images of the call, of which launch() takes a part: check() sets it
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
     bool oriented = false;   // check() sets it
     std::vector<jpeg_amd_region> windows;   // of a placed call, per image: check() sizes it, window(i) fills it
@@ -549,10 +556,12 @@ struct ResampleTarget {
     int check(int n_images)
     {
         oriented = false;   // (not a verdict: which records the call writes)
+        n_call = std::max(n_images, 0);
         for (int i = 0; h_orient && i < n_images; ++i) oriented = oriented || h_orient[i] != 1;
         if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
         JA_TRY(tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride));
+        if (colour) JA_TRY(tensor ? check_colour(*colour, n_images) : JPEG_AMD_EINVAL);
         if (warped) {
             if (filter != JPEG_AMD_FILTER_BILINEAR || h_orient || place || !warp) return JPEG_AMD_EINVAL;
             if (warp->edge != JPEG_AMD_EDGE_FILL && warp->edge != JPEG_AMD_EDGE_REPLICATE) return JPEG_AMD_EINVAL;
@@ -584,7 +593,7 @@ struct ResampleTarget {
     size_t record_bytes() const
     {
         if (warped) return sizeof(WarpRecord);
-        if (place) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
+        if (place || colour) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
         if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
         return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
     }
@@ -614,16 +623,29 @@ struct ResampleTarget {
         std::memcpy(rec.data() + (size_t)at * record_bytes(), &r, record_bytes());
         return kx > max_scale() || ky > max_scale() ? JPEG_AMD_ENOSUP : JPEG_AMD_OK;
     }
-    // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards.
+    // What a call of n images uploads: their resample records, then ("colour stage") their ColourRecords at colour_at(n) --
+    // image i's twelve numbers as the caller wrote them.
+    size_t colour_at(int n) const { return ((size_t)n * record_bytes() + 15) & ~(size_t)15; }
+    size_t upload_bytes(int n) const { return colour ? colour_at(n) + (size_t)n * sizeof(ColourRecord) : (size_t)n * record_bytes(); }
+    void colour_records(std::vector<uint8_t> &rec, int n) const
+    {
+        if (colour && n > 0) std::memcpy(rec.data() + colour_at(n), colour->h_matrices, (size_t)n * sizeof(ColourRecord));
+    }
+    // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards, and ColourRecord i0 of the call's.
     hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
         const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
         const ResampleRecords kind = warped  ? ResampleRecords::Warped
-                                     : place ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
+                                     : place || colour ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
         ResampleLaunch l{filter, kind, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride, {0, 0, 0}};
         for (int c = 0; place && c < 3; ++c) l.fill[c] = place->fill[c];
         for (int c = 0; warped && c < 3; ++c) l.fill[c] = warp->fill[c];
+        if (colour) {
+            l.d_colour = static_cast<const uint8_t *>(d_rec) + colour_at(n_call) + (size_t)i0 * sizeof(ColourRecord);
+            l.lo = colour->lo;
+            l.hi = colour->hi;
+        }
         return launch_resample(stream, l);
     }
 };
@@ -641,7 +663,8 @@ struct ResizePlan {
 ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, const ResampleTarget &t)
 {
     ResizePlan plan;
-    plan.rec.resize((size_t)n_images * t.record_bytes());
+    plan.rec.resize(t.upload_bytes(n_images));
+    t.colour_records(plan.rec, n_images);
     for (int i0 = 0; i0 < n_images;) {
         int m = 0;
         size_t stride = 0;
@@ -687,7 +710,8 @@ int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t 
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     JA_TRY(t.check(n_images));
-    std::vector<uint8_t> rec((size_t)n_images * t.record_bytes());
+    std::vector<uint8_t> rec(t.upload_bytes(n_images));
+    t.colour_records(rec, n_images);
     int taps = JPEG_AMD_OK;   // the tap limit: judged last, by the first image over it
     if (n_images > 0) {
         if (!d_src || !h_extents) return JPEG_AMD_EINVAL;
@@ -943,9 +967,11 @@ int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_a
                                           const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
                                           const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient,
                                           const jpeg_amd_placement *place, void *d_dst, size_t dst_stride, int *taps,
-                                          const float *h_view_matrices, const jpeg_amd_warp *warp, bool warped)
+                                          const float *h_view_matrices, const jpeg_amd_warp *warp, bool warped,
+                                          const jpeg_amd_colour *colour)
 {
-    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place, nullptr, h_view_matrices, warp, warped};
+    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place, nullptr, h_view_matrices, warp, warped,
+                     colour};
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
@@ -1237,11 +1263,12 @@ JA_NOTHROW_TAIL
 int jpeg_amd::capi::decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
                                               jpeg_amd_color color, const jpeg_amd_view *h_views, const float *h_view_matrices,
                                               const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
-                                              const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride)
+                                              const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
+                                              const jpeg_amd_colour *colour)
 {
     return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
                          ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_view_matrices, warp, true});
+                                        nullptr, h_view_matrices, warp, true, colour});
 }
 
 namespace {
@@ -1251,7 +1278,7 @@ namespace {
 int warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                  const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out, float *h_matrices_out, void *d_dst,
-                 size_t dst_stride)
+                 size_t dst_stride, const jpeg_amd_colour *colour = nullptr)
 {
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_images || !h_matrices)) return JPEG_AMD_EINVAL;
@@ -1265,7 +1292,7 @@ int warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images
         if (h_matrices_out) std::memcpy(h_matrices_out + 6 * i, &view_matrices[6 * i], 6 * sizeof(float));
     }
     return decode_warped_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), view_matrices.data(), warp, out_w, out_h, tensor,
-                                     spec, h_flip, d_dst, dst_stride);
+                                     spec, h_flip, d_dst, dst_stride, colour);
 }
 
 }  // namespace
@@ -1288,5 +1315,67 @@ int jpeg_amd_decode_tensor_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const j
 try {
     return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
                         h_views_out, h_matrices_out, d_dst, dst_stride);
+}
+JA_NOTHROW_TAIL
+
+// ---- "colour stage" ----
+// The tensor calls with an affine map of (R, G, B) per image between the resample and the tensor output; with colour == nullptr
+// each is the call it is named after, by delegation.
+int jpeg_amd_resize_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                        const jpeg_amd_extent *h_extents, int32_t out_w, int32_t out_h, int filter,
+                                        const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient,
+                                        const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out,
+                                        const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+try {
+    if (!colour)
+        return jpeg_amd_resize_placed_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, spec, h_flip, h_orient,
+                                                   place, h_windows_out, d_dst, dst_stride);
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out, nullptr,
+                                        nullptr, false, colour});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_colour_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                        jpeg_amd_color color, const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h,
+                                        int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                        const uint8_t *h_orient, const jpeg_amd_placement *place,
+                                        jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst,
+                                        size_t dst_stride)
+try {
+    if (!colour)
+        return jpeg_amd_decode_tensor_placed_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, spec, h_flip,
+                                                   h_orient, place, h_windows_out, d_dst, dst_stride);
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out, nullptr,
+                                        nullptr, false, colour});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_warp_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                      const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                                      int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                      const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+try {
+    if (!colour)
+        return jpeg_amd_warp_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, h_matrices, warp, out_w, out_h, spec, h_flip, d_dst,
+                                          dst_stride);
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_matrices, warp, true, colour});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                               jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                               const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                               const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                                               float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+try {
+    if (!colour)
+        return jpeg_amd_decode_tensor_warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, spec,
+                                                   h_flip, h_views_out, h_matrices_out, d_dst, dst_stride);
+    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
+                        h_views_out, h_matrices_out, d_dst, dst_stride, colour);
 }
 JA_NOTHROW_TAIL

@@ -221,6 +221,14 @@ struct WarpRecord {
     int32_t  edge;
 };
 static_assert(sizeof(WarpRecord) == 48, "record layout");
+// Colour ("colour stage"): beside the resample record of a tensor launch, per image the affine map of (R, G, B) that stands
+// between the resample and the tensor output: row c is k[c][0 .. 2], the matrix row, and k[c][3], the offset.  The kernels read
+// it once per workgroup, through uniform loads in front of the walk.
+struct ColourRecord {
+    float k[3][4];   // finite, at most kColourMaxEntry in magnitude
+};
+static_assert(sizeof(ColourRecord) == 48, "record layout");
+constexpr float kColourMaxEntry = 1073741824.0f; // 2^30: three products of it with a byte and the offset stay finite
 constexpr int   kWarpMaxSourceSide = 1 << 24;    // (float)w and (float)h are exact
 constexpr float kWarpMaxEntry = 1073741824.0f;   // 2^30: with an output side of at most 2^30 no coordinate overflows
 constexpr int   kResizeMaxSide = 1 << 30;        // of the output: the kernels' pixel indices are int
@@ -245,6 +253,10 @@ struct ResampleLaunch {
     void *d_dst;
     size_t dst_stride;
     uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window; Warped: of a tap outside the image
+    // "colour stage": nullptr, or ColourRecord 0 of the launch (16-byte aligned) and the clamp's bounds, neither a NaN and
+    // lo <= hi; only with a spec and with Placed or Warped records (anything else: hipErrorInvalidValue)
+    const void *d_colour = nullptr;
+    float lo = 0.0f, hi = 0.0f;
 };
 hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l);
 

@@ -14,6 +14,10 @@
 //   end with the launch's fill.
 // k_warp_bytes, k_warp_tensor<T, CHW>: "warped resample" -- warp_walk (warp.hpp) over WarpRecords with the same two sinks and
 //   the placed kernels' arguments; no tables, no LDS.
+// k_resize_placed_tensor, k_tables_placed_tensor and k_warp_tensor carry a leading Colour flag: with it the sink is colour_sink
+//   ("colour stage": an affine map of (R, G, B) per image and a clamp, in front of the mean), the arguments end with the
+//   ColourRecords and the clamp's bounds, and nothing else differs.  These three express every record kind -- a whole-canvas
+//   window is the oriented and the stored call -- so the others have no colour form.
 // The byte kernels never flip (the records' flip is not read); the tensor kernels flip where the record says so, after the
 // orientation: the flip mirrors the OUTPUT columns.
 //
@@ -67,6 +71,14 @@ template <typename T, typename Record>
 struct PlacedTensorArgs : RecordTensorArgs<T, Record> {
     uint32_t fill;
 };
+// ... and with the "colour stage": the placed tensor kernels' (the warp's are those), then the records and the clamp.
+template <typename T, typename Record>
+struct ColourTensorArgs : PlacedTensorArgs<T, Record> {
+    const ColourRecord *colour;
+    float lo, hi;
+};
+template <bool Colour, typename T, typename Record>
+using PlacedSinkArgs = typename std::conditional<Colour, ColourTensorArgs<T, Record>, PlacedTensorArgs<T, Record>>::type;
 
 // Where the image of the workgroup goes, and the elements of one of its channels in CHW.
 template <typename Args>
@@ -213,14 +225,23 @@ __global__ __launch_bounds__(kThreads) void k_resize_placed_bytes(PlacedBytesArg
     resample_walk<true, true>(a, false, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); }, a.fill);
 }
 
-template <typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_resize_placed_tensor(PlacedTensorArgs<T, PlacedResizeRecord> a)
+// Colour: the image's ColourRecord, read here, once per workgroup and in front of the walk, and colour_sink in tensor_sink's
+// place; without it the kernel is the text it was.  The same in k_tables_placed_tensor and k_warp_tensor.
+template <bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_resize_placed_tensor(PlacedSinkArgs<Colour, T, PlacedResizeRecord> a)
 {
     T *dst = image_dst(a);
     const size_t plane = image_plane(a);
-    resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-    }, a.fill);
+    if constexpr (Colour) {
+        const ColourRecord k = a.colour[blockIdx.y];
+        resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
+        }, a.fill);
+    } else {
+        resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+        }, a.fill);
+    }
 }
 
 template <typename Filter>
@@ -230,14 +251,21 @@ __global__ __launch_bounds__(kThreads) void k_tables_placed_bytes(PlacedBytesArg
     antialias_walk<Filter>(a, a.tab_records, false, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); }, a.fill);
 }
 
-template <typename Filter, typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_tables_placed_tensor(PlacedTensorArgs<T, PlacedAntialiasRecord> a)
+template <bool Colour, typename Filter, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_tables_placed_tensor(PlacedSinkArgs<Colour, T, PlacedAntialiasRecord> a)
 {
     T *dst = image_dst(a);
     const size_t plane = image_plane(a);
-    antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-    }, a.fill);
+    if constexpr (Colour) {
+        const ColourRecord k = a.colour[blockIdx.y];
+        antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
+        }, a.fill);
+    } else {
+        antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+        }, a.fill);
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_warp_bytes(PlacedBytesArgs<WarpRecord> a)
@@ -246,14 +274,21 @@ __global__ __launch_bounds__(kThreads) void k_warp_bytes(PlacedBytesArgs<WarpRec
     warp_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
 }
 
-template <typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_warp_tensor(PlacedTensorArgs<T, WarpRecord> a)
+template <bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_warp_tensor(PlacedSinkArgs<Colour, T, WarpRecord> a)
 {
     T *dst = image_dst(a);
     const size_t plane = image_plane(a);
-    warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-        tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-    });
+    if constexpr (Colour) {
+        const ColourRecord k = a.colour[blockIdx.y];
+        warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
+        });
+    } else {
+        warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+        });
+    }
 }
 
 // ---- the launcher ----
@@ -271,6 +306,17 @@ hipError_t with_element(const jpeg_amd_tensor_spec &spec, F f)
     case JPEG_AMD_BF16: return in_layout(bf16_t{});
     default: return hipErrorInvalidValue;
     }
+}
+
+// The "colour stage" of the launch into the args that have one.
+template <typename Args>
+void set_colour(Args &, const ResampleLaunch &) {}
+template <typename T, typename Record>
+void set_colour(ColourTensorArgs<T, Record> &a, const ResampleLaunch &l)
+{
+    a.colour = static_cast<const ColourRecord *>(l.d_colour);
+    a.lo = l.lo;
+    a.hi = l.hi;
 }
 
 struct Bilinear;   // in place of a filter of antialias.hpp: resample_walk, whose records are ResampleArgs::records
@@ -291,6 +337,7 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
         a.dst = static_cast<decltype(a.dst)>(l.d_dst);
         a.dst_stride = l.dst_stride;
         if constexpr (placed || warped) a.fill = (uint32_t)l.fill[0] | (uint32_t)l.fill[1] << 8 | (uint32_t)l.fill[2] << 16;
+        set_colour(a, l);
         if constexpr (!std::is_same<decltype(a.dst), uint8_t *>::value) {
             for (int c = 0; c < 3; ++c) {
                 a.mean[c] = l.spec->mean[c];
@@ -300,15 +347,26 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, a);
         return hipGetLastError();
     };
+    if (l.d_colour && !(l.spec && (placed || warped))) return hipErrorInvalidValue;   // "colour stage": these kernels only
     if (l.spec) {
         return with_element(*l.spec, [&](auto t, auto chw) {
             using T = decltype(t);
+            if constexpr (placed || warped) {
+                if (l.d_colour) {
+                    if constexpr (warped)
+                        return run(k_warp_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
+                    else if constexpr (bilinear)
+                        return run(k_resize_placed_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
+                    else
+                        return run(k_tables_placed_tensor<true, Filter, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
+                }
+            }
             if constexpr (warped)
-                return run(k_warp_tensor<T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+                return run(k_warp_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (placed && bilinear)
-                return run(k_resize_placed_tensor<T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+                return run(k_resize_placed_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (placed)
-                return run(k_tables_placed_tensor<Filter, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+                return run(k_tables_placed_tensor<false, Filter, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (bilinear)
                 return run(k_resize_tensor<oriented, T, decltype(chw)::value>, ResizeTensorArgs<oriented, T>{});
             else

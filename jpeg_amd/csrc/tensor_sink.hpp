@@ -142,4 +142,40 @@ __device__ __forceinline__ void tensor_sink(const TensorArgs<T> &a, T *dst, size
     }
 }
 
+// The colour sink ("colour stage" of include/jpeg_amd.h): tensor_sink with image i's affine map of (R, G, B) and the clamp
+// between the byte and the mean.  Per channel c, every statement ONE binary32 operation:
+//     p = ((k[c][0] * r) + (k[c][1] * g)) + (k[c][2] * b);  q = p + k[c][3];  q = q < lo ? lo : q;  q = q > hi ? hi : q
+// then tensor_sink's t = q - mean[c], v = t * scale[c] and its conversion and stores.  The clamp is two compares and selects,
+// not v_max / v_min: those may return either zero for max(-0, +0), and the sign of q = -0 shows in q - mean where mean is 0.
+// There is no branch: the two infinities leave every q, which is finite, as it is.  k is the workgroup's record, read by the
+// kernel in front of the walk (blockIdx.y indexes it: scalar loads into SGPRs); lo and hi are kernel arguments.
+// The conversion loop and the stores repeat tensor_sink's text instead of sharing a helper with it, so that nothing of the
+// existing kernels' text moves (they are to stay the code they are): a change to one is made to the other.
+template <typename T, bool CHW>
+__device__ __forceinline__ void colour_sink(const TensorArgs<T> &a, const ColourRecord &k, float lo, float hi, T *dst, size_t plane,
+                                            const uint32_t (&o)[kRun][3], int y, int x, int npix)
+{
+    T e[CHW ? 3 : 1][CHW ? kRun : 3 * kRun];
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) {
+        const float r = (float)o[j][0], g = (float)o[j][1], b = (float)o[j][2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p = ((k.k[c][0] * r) + (k.k[c][1] * g)) + (k.k[c][2] * b);
+            float q = p + k.k[c][3];
+            q = q < lo ? lo : q;
+            q = q > hi ? hi : q;
+            const float d = q - a.mean[c];
+            e[CHW ? c : 0][CHW ? j : 3 * j + c] = to_element<T>(d * a.scale[c]);
+        }
+    }
+    const size_t at = (size_t)(uint32_t)y * (uint32_t)a.out_w + (uint32_t)x;
+    if constexpr (CHW) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) store_elems<T, kRun>(dst + c * plane + at, e[c], npix);
+    } else {
+        store_elems<T, 3 * kRun>(dst + 3 * at, e[0], 3 * npix);
+    }
+}
+
 }  // namespace jpeg_amd

@@ -1535,6 +1535,120 @@ int jpeg_amd_decompress_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, const uint
                                                    jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                    float *h_matrices_out, int32_t *h_orient_out);
 
+/* ---- projective resample: a 3 x 3 homography in the warp calls ---------------------------------------------------------------
+ *
+ * The warp calls take an affine map.  These take, per image, a matrix m[9] = (m00, m01, m02, m10, m11, m12, m20, m21, m22) of
+ * binary32, row by row: the INVERSE projective map from the centre of an OUTPUT pixel to a point of the SOURCE, in the
+ * continuous pixel coordinates of "warped resample".  It is torchvision's RandomPerspective and perspective(), the keystone
+ * correction of a photographed page, sign or number plate, the bird's-eye view of a road camera.  One launch writes every
+ * image of the call.
+ *
+ * THE CONTRACT.  A source of w x h pixels of 3 bytes, a target of out_w x out_h.  Every statement is ONE binary32 operation
+ * and nothing is contracted; xs, xc, yc are those of "warped resample":
+ *     nx = ((m00 * xc) + (m01 * yc)) + m02
+ *     ny = ((m10 * xc) + (m11 * yc)) + m12
+ *     nw = ((m20 * xc) + (m21 * yc)) + m22
+ *     rw = 1.0f / nw                                      (the correctly rounded binary32 quotient)
+ *     sx = nx * rw;   sx = sx - 0.5f;   sx = min(max(sx, -1.0f), (float)w)
+ *     sy = ny * rw;   sy = sy - 0.5f;   sy = min(max(sy, -1.0f), (float)h)
+ * and from fx0 = floorf(sx) on the contract is "warped resample" word for word: the four taps, JPEG_AMD_EDGE_FILL and
+ * JPEG_AMD_EDGE_REPLICATE of the same jpeg_amd_warp, the blend, the rounding to a byte, "tensor output" and the "colour stage"
+ * behind it.
+ *
+ * CONSEQUENCE.  With the last row (0, 0, 1): nw = (0 + 0) + 1 = 1, rw = 1 and sx = nx * 1 = nx exactly, so the call is
+ * jpeg_amd_warp_batch on m[0 .. 5] (or its tensor and colour forms), bit for bit.
+ *
+ * THE LIMITS, derived.  The entries are finite and at most 2^30 in magnitude, as a warp's.  The denominator is the affine
+ * form W(cx, cy) = m20 cx + m21 cy + m22 of the canvas point; with S = |m20| out_w + |m21| out_h + |m22|, |W| <= S on the
+ * canvas, and W, being affine, takes its minimum over the canvas at one of the four corners (0, 0), (out_w, 0), (0, out_h),
+ * (out_w, out_h).  A matrix is refused unless S >= 2^-30 and that minimum is at least S / 16.  Then at every pixel centre:
+ *   - the exact W is at least S / 16, and the computed nw differs from it by at most about 3 * 2^-24 * S (two products and two
+ *     sums, each rounded once, of terms that are at most S), that is by at most 3 * 2^-20 of W itself: nw is positive, at
+ *     least 2^-35 and at most 3 * 2^60, normal in binary32, and so is rw; the division meets no zero, no subnormal and no
+ *     infinity;
+ *   - |nx| and |ny| are below 3 * 2^60, so |nx * rw| is below 2^97: every coordinate is finite, no NaN arises, and the clamp
+ *     is defined;
+ *   - the foreshortening across the canvas, max W / min W, is at most 16 : 1, far beyond the distortion_scale = 0.5 of the
+ *     usual augmentation; the horizon W = 0 is never on the canvas.
+ *
+ * EINVAL, judged on the host in double before anything is enqueued, the context last: an entry that is not finite or exceeds
+ * 2^30 in magnitude; S < 2^-30; min W < S / 16 (a corner with W <= 0 is such a matrix); and whatever "warped resample"
+ * refuses otherwise.  n_images == 0 is OK.
+ *
+ * h_matrices is [n_images][9].  jpeg_amd_project_tensor_batch takes `colour` in front of the output pointer: NULL for none,
+ * else the "colour stage" as jpeg_amd_warp_colour_tensor_batch applies it -- one entry point, not two. */
+int jpeg_amd_project_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                           const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                           int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_project_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                  const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                                  int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                  const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+
+/* The view of an image that a projective map reads, and the matrix against that view: jpeg_amd_warp_view for a homography.
+ * Host only, pure, computed in double.  `m` is in the coordinates of the UPRIGHT image, as there.
+ *   1. The orientation is composed into the matrix, row by row (row k = (mk0, mk1, mk2); row 2 is the denominator's): with the
+ *      orientation's bits (T, fx, fy), T swaps rows 0 and 1; fx: row0 = W row2 - row0; fy: row1 = H row2 - row1.  The result
+ *      maps output centres to STORED coordinates, since W - nx / nw = (W nw - nx) / nw.
+ *   2. The denominator.  The Jacobian of (X, Y) = (nx, ny) / nw has the columns ((m00 - X m20) / nw, (m10 - Y m20) / nw) and
+ *      ((m01 - X m21) / nw, (m11 - Y m21) / nw): the source steps of one output column and of one output row.  They are taken
+ *      at the four canvas corners and at the canvas centre (out_w / 2, out_h / 2), and d is the largest of {8, 4, 2, 1} with
+ *      d * d <= the minimum of the ten squared column norms.  For a last row (0, 0, 1) this is jpeg_amd_warp_view's rule.  For
+ *      a true projective map the five points are a RULE, not a bound: the step varies over the canvas and may be smaller
+ *      between them.  Any d gives a result that the contract defines (image i is the project call on the view's pixels); d
+ *      decides only the cost and the sharpness.
+ *   3. Rows 0 and 1 times 1 / d (exact): the matrix against the scaled image of W' x H' (jpeg_amd_scaled_layout).
+ *   4. The footprint.  nw > 0 on the canvas, so the canvas maps onto the convex quadrilateral of its corners' images, and the
+ *      extremes xmin, xmax, ymin, ymax are those of the four corners, each divided in double.  The view's columns are
+ *      clamp(floor(xmin - 0.5) - 1, 0, W' - 1) ..= clamp(floor(xmax - 0.5) + 2, 0, W' - 1), its rows likewise; it is never
+ *      empty.  The margin of one pixel beyond the taps covers the binary32 rounding of the kernel's coordinate, which is
+ *      bounded as follows.  Let X be the exact coordinate against the view and A = (|m00 xc| + |m01 yc| + |m02|) / nw the sum
+ *      of the magnitudes of its three terms.  nx carries at most 3 * 2^-24 * A * nw (as nw's bound above), which is
+ *      3 * 2^-24 * A of X; nw carries 3 * 2^-20 of itself, the quotient, the product and the subtraction of 0.5 one rounding
+ *      each, together 51 * 2^-24 * |X|; and rounding m_view to binary32 adds at most 2^-24 * A from row 0 and 16 * 2^-24 * |X|
+ *      from row 2.  In all |error| <= 2^-24 * (67 |X| + 4 A).  With |X| <= 2^16, the largest side a JPEG can have, and
+ *      A <= 2^18 (terms that cancel from no more than four times that side: every rotation, shear and keystone about a point
+ *      of the image), this is 67 * 2^-8 + 4 * 2^-6 < 0.33 pixel: the one-pixel margin holds for every source a JPEG file can
+ *      hold, and is not widened.  A matrix whose terms cancel from further out loses bits in proportion, as an affine one
+ *      does in "warped resample"; the call remains defined by the view and m_view it returns.
+ *   5. m_view: row0 - x_view row2 and row1 - y_view row2, row 2 unchanged, rounded to binary32 ONCE.  It passes the contract's
+ *      own check, or the call is refused (an entry beyond 2^30 behind the subtraction).
+ * EINVAL: an orientation outside 1 .. 8, a matrix the contract refuses on this canvas, out_w or out_h outside 1 .. 2^30, a
+ * layout jpeg_amd_scaled_layout refuses, a null pointer. */
+int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h,
+                          jpeg_amd_view *view, float m_view[9]);
+
+/* The decode and file routes, by reference only: they define no arithmetic.  Each is the *_warped_mixed call of the same
+ * place with h_matrices and h_matrices_out of [n_images][9], jpeg_amd_project_view where that call has jpeg_amd_warp_view,
+ * and ONE project launch per chunk: image i is, bit for bit, jpeg_amd_project_batch (or the tensor form) applied to the pixels
+ * jpeg_amd_decode_view_batch defines for the view jpeg_amd_project_view returns, with the m_view it returns.  The tensor
+ * forms take `colour` in front of the output pointer, NULL for none.  The file calls honour JPEG_AMD_ORIENT_EXIF, and write
+ * h_info, h_views, h_matrices_out and h_orient_out as far as the files were judged. */
+int jpeg_amd_decode_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                    jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                    const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
+                                    float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride);
+int jpeg_amd_decode_tensor_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                           const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                           const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                           jpeg_amd_view *h_views_out, float *h_matrices_out,
+                                           const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_resized_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                                int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                                const uint8_t *h_orient, const float *h_matrices,
+                                                const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, uint8_t *d_pixels,
+                                                size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                                float *h_matrices_out, int32_t *h_orient_out);
+int jpeg_amd_decompress_tensor_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                               int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                               const uint8_t *h_orient, const float *h_matrices,
+                                               const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                               const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                               const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
+                                               jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                               float *h_matrices_out, int32_t *h_orient_out);
+
 #ifdef __cplusplus
 }
 #endif

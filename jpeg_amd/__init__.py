@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     transform, transform_quanta, view_denom, view_of_source, view_window,
     affine_matrix, decode_tensors_warped_mixed, decode_warped_mixed, warp, warp_tensor, warp_view,
     colour_matrix,
+    decode_projected_mixed, decode_tensors_projected_mixed, perspective_matrix, project, project_tensor, project_view,
 )
 
 __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangular",
@@ -23,4 +24,5 @@ __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangu
            "decode_views", "decode_views_mixed", "decompress_resized", "decompress_tensors", "default_context", "encode_tensors", "exif_orientation", "inspect", "orient_region", "place_window", "reduce", "reduce_layout",
            "region_window", "resize", "resize_tensor", "scaled_size", "tensor_pixels", "tensor_source", "tensor_spec", "transform", "transform_quanta", "view_denom",
            "view_of_source", "view_window", "affine_matrix", "decode_tensors_warped_mixed", "decode_warped_mixed", "warp", "warp_tensor",
-           "warp_view", "colour_matrix"]
+           "warp_view", "colour_matrix", "decode_projected_mixed", "decode_tensors_projected_mixed", "perspective_matrix", "project",
+           "project_tensor", "project_view"]

@@ -685,6 +685,73 @@ def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
     return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
 
 
+def _homographies(matrices, n: int) -> np.ndarray:
+    """matrices= of the project calls -> float32 [n, 9], contiguous."""
+    m = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, 9))
+    if m.shape[0] != n:
+        raise ValueError("matrices: one (m00, m01, m02, m10, m11, m12, m20, m21, m22) per image")
+    return m
+
+
+def _is_projective(matrices) -> bool:
+    """Whether warp= of the file calls holds 3 x 3 matrices ([n, 9] or [n, 3, 3]) rather than affine ones ([n, 6])."""
+    shape = np.shape(matrices)
+    return shape[-1:] == (9,) or shape[-2:] == (3, 3)
+
+
+def perspective_matrix(src_points, out_points) -> np.ndarray:
+    """The matrix of the project calls (include/jpeg_amd.h, "projective resample") that takes four points of the canvas,
+    out_points [(x, y)] * 4 in continuous pixel coordinates, to four points of the source, src_points: the INVERSE map of
+    torchvision's perspective(startpoints=src_points, endpoints=out_points), with m22 = 1.  The eight unknowns are solved in
+    float64 and returned as float64 [3, 3] (the calls round to float32); ValueError for a singular system (three points on a
+    line, or a map whose m22 would be 0).  Two axis-aligned rectangles, the corners in the same order, give exactly
+    (sx, 0, x0, 0, sy, y0, 0, 0, 1)."""
+    src = np.asarray(src_points, np.float64).reshape(-1, 2)
+    out = np.asarray(out_points, np.float64).reshape(-1, 2)
+    if src.shape != (4, 2) or out.shape != (4, 2) or not (np.isfinite(src).all() and np.isfinite(out).all()):
+        raise ValueError("perspective_matrix: four finite (x, y) points each")
+
+    def rectangle(p):   # corners in the order (x0, y0), (x1, y0), (x1, y1), (x0, y1) or (x0, y0), (x1, y0), (x0, y1), (x1, y1)
+        (ax, ay), (bx, by), (cx, cy), (dx, dy) = p.tolist()
+        if ay == by and ax != bx and bx == cx and cy == dy and dx == ax and cy != ay:
+            return ax, ay, bx, cy, 0
+        if ay == by and ax != bx and ax == cx and bx == dx and cy == dy and cy != ay:
+            return ax, ay, bx, cy, 1
+        return None
+
+    rs, ro = rectangle(src), rectangle(out)
+    if rs is not None and ro is not None and rs[4] == ro[4]:
+        sx, sy = (rs[2] - rs[0]) / (ro[2] - ro[0]), (rs[3] - rs[1]) / (ro[3] - ro[1])
+        return np.array([[sx, 0.0, rs[0] - sx * ro[0]], [0.0, sy, rs[1] - sy * ro[1]], [0.0, 0.0, 1.0]], np.float64)
+    a = np.zeros((8, 8), np.float64)
+    b = np.zeros(8, np.float64)
+    for k in range(4):
+        (x, y), (u, v) = out[k], src[k]
+        a[2 * k] = [x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y]
+        a[2 * k + 1] = [0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y]
+        b[2 * k], b[2 * k + 1] = u, v
+    scale = np.abs(a).max(axis=0)
+    if not (scale > 0.0).all() or np.linalg.cond(a / scale) > 1e12:
+        raise ValueError("perspective_matrix: the points do not determine a projective map")
+    h = np.linalg.solve(a / scale, b) / scale
+    if not np.isfinite(h).all():
+        raise ValueError("perspective_matrix: the points do not determine a projective map")
+    return np.append(h, 1.0).reshape(3, 3)
+
+
+def project_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
+    """The view that a projective map of an image of `size` (w, h) and `layout` reads, and the matrix against it
+    (jpeg_amd_project_view): `matrix` (9 values, or [3, 3]) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT
+    image, the stored image seen through `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [9])."""
+    m = _homographies(matrix, 1)
+    v = _lib.View()
+    mv = np.zeros(9, np.float32)
+    L = layout.c_layout(size)
+    _lib.check(_lib.lib().jpeg_amd_project_view(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]),
+                                                C.byref(v), mv.ctypes.data), "jpeg_amd_project_view")
+    return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
+
+
 _GREY = (0.2989, 0.587, 0.114)                     # torchvision's rgb_to_grayscale
 _RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.5959, -0.2746, -0.3213), (0.2115, -0.5227, 0.3112))
 
@@ -1362,6 +1429,48 @@ def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spe
     return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
 
 
+def _projected_mixed_args(ctx: Context, spectrals, matrices, orientations):
+    """The arguments the projected mixed calls share: _warped_mixed_args' with nine numbers per matrix."""
+    spectrals = list(spectrals)
+    n = len(spectrals)
+    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, np.zeros((n, 5), np.int32))
+    return n, h_images, h_views, _homographies(matrices, n), _orientations(orientations, n), np.zeros((n, 9), np.float32), keep
+
+
+def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
+                           edge="fill", fill=(0, 0, 0)):
+    """decode_warped_mixed through a 3 x 3 homography per image (jpeg_amd_decode_projected_mixed; include/jpeg_amd.h,
+    "projective resample"): matrices [n, 9] or [n, 3, 3] in the coordinates of the UPRIGHT full-size images (perspective_matrix
+    makes one from four point pairs).  project_view chooses each image's denominator and view, and image i is project() of
+    decode_views_mixed's pixels for that view with the matrix against it.
+    Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 9])."""
+    n, h_images, h_views, m, h_orient, m_out, keep = _projected_mixed_args(ctx, spectrals, matrices, orientations)
+    w = _warp(edge, fill)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    _lib.check(_lib.lib().jpeg_amd_decode_projected_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
+                                                          m.ctypes.data, C.byref(w), wt, ht, h_views, m_out.ctypes.data, out.data_ptr(),
+                                                          stride), "jpeg_amd_decode_projected_mixed", ctx.handle)
+    return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
+
+
+def decode_tensors_projected_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
+                                   cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None,
+                                   colour_clamp=None):
+    """decode_projected_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_projected_mixed); flips, spec,
+    colour and colour_clamp as in project_tensor.
+    Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 9])."""
+    n, h_images, h_views, m, h_orient, m_out, keep = _projected_mixed_args(ctx, spectrals, matrices, orientations)
+    w = _warp(edge, fill)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_decode_tensor_projected_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
+                                                                 m.ctypes.data, C.byref(w), wt, ht, C.byref(spec), h_flip, h_views,
+                                                                 m_out.ctypes.data, None if tint is None else C.byref(tint),
+                                                                 out.data_ptr(), stride),
+               "jpeg_amd_decode_tensor_projected_mixed", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
+
+
 def _file_args(sources, source_regions):
     """The arguments the file calls share: (n, c file pointers, c sizes, c source rectangles or None, room for the frame
     infos, room for the views, keep).  sources: paths or the files' bytes."""
@@ -1381,9 +1490,12 @@ def _file_args(sources, source_regions):
 
 
 def _warp_file_args(warp, n: int, source_regions, place, filter_code: int, edge, fill):
-    """warp=, edge=, fill= of the file calls -> (the matrices [n, 6], room for the applied ones, struct jpeg_amd_warp)."""
+    """warp=, edge=, fill= of the file calls -> (the matrices [n, 6], room for the applied ones, struct jpeg_amd_warp); of
+    3 x 3 matrices ([n, 9] or [n, 3, 3]: "projective resample") [n, 9] and room for as many."""
     if source_regions is not None or place is not None or filter_code != _lib.FILTER_BILINEAR:
         raise ValueError('warp: not together with source_regions, place or a filter other than "bilinear"')
+    if _is_projective(warp):
+        return _homographies(warp, n), np.zeros((n, 9), np.float32), _warp(edge, fill)
     return _matrices(warp, n), np.zeros((n, 6), np.float32), _warp(edge, fill)
 
 
@@ -1413,7 +1525,9 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     warp / edge / fill: per file a matrix [6] in the coordinates of its UPRIGHT full-size image, as in decode_warped_mixed
     (jpeg_amd_decompress_tensor_warped_mixed; include/jpeg_amd.h, "warped resample"); not together with source_regions, place
     or a filter other than "bilinear" (ValueError).  The views that come back are warp_view's, and the matrices applied to them
-    come back as the last item, float32 [n, 6].
+    come back as the last item, float32 [n, 6].  A warp of [n, 9] or [n, 3, 3] is a homography per file
+    (jpeg_amd_decompress_tensor_projected_mixed; "projective resample"): the views are project_view's and the matrices that
+    come back float32 [n, 9].
     colour / colour_clamp: as in resize_tensor, per file (jpeg_amd_decompress_tensor_colour_mixed, with `warp`
     jpeg_amd_decompress_tensor_warped_colour_mixed); what comes back is what the call without them returns."""
     code = _filter(filter)
@@ -1424,7 +1538,14 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
         m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
         wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
         applied = (C.c_int32 * max(n, 1))()
-        if tint is not None:
+        if m.shape[1] == 9:
+            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_projected_mixed(ctx.handle, ptrs, sizes, n, int(threads),
+                                                                             1 if cosite else 0, color.code, h_orient, m.ctypes.data,
+                                                                             C.byref(w), wt, ht, C.byref(spec), h_flip,
+                                                                             None if tint is None else C.byref(tint), out.data_ptr(),
+                                                                             stride, infos, h_views, m_out.ctypes.data, applied),
+                       "jpeg_amd_decompress_tensor_projected_mixed", ctx.handle)
+        elif tint is not None:
             _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_colour_mixed(ctx.handle, ptrs, sizes, n, int(threads),
                                                                                  1 if cosite else 0, color.code, h_orient, m.ctypes.data,
                                                                                  C.byref(w), wt, ht, C.byref(spec), h_flip, C.byref(tint),
@@ -1485,7 +1606,8 @@ def decompress_resized(ctx: Context, sources, out_size, source_regions=None, col
     (Wt, Ht) as bytes by `filter`; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
     place / anchor / fill: as there (jpeg_amd_decompress_resized_placed_mixed), the windows as a second item.
     warp / edge / fill: as there (jpeg_amd_decompress_resized_warped_mixed); with it the views (int32 [n, 5]) and the matrices
-    applied to them (float32 [n, 6]) come back as the last two items.
+    applied to them (float32 [n, 6]; of a [n, 9] or [n, 3, 3] warp, jpeg_amd_decompress_resized_projected_mixed, [n, 9]) come
+    back as the last two items.
     Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
@@ -1493,6 +1615,13 @@ def decompress_resized(ctx: Context, sources, out_size, source_regions=None, col
     if warp is not None:
         m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
         wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+        if m.shape[1] == 9:
+            _lib.check(_lib.lib().jpeg_amd_decompress_resized_projected_mixed(ctx.handle, ptrs, sizes, n, int(threads),
+                                                                              1 if cosite else 0, color.code, h_orient, m.ctypes.data,
+                                                                              C.byref(w), wt, ht, out.data_ptr(), stride, infos, h_views,
+                                                                              m_out.ctypes.data, None),
+                       "jpeg_amd_decompress_resized_projected_mixed", ctx.handle)
+            return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
         _lib.check(_lib.lib().jpeg_amd_decompress_resized_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
                                                                        color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
                                                                        out.data_ptr(), stride, infos, h_views, m_out.ctypes.data, None),
@@ -1596,6 +1725,39 @@ def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec,
     _lib.check(_lib.lib().jpeg_amd_warp_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt,
                                                      ht, C.byref(spec), h_flip, out.data_ptr(), stride),
                "jpeg_amd_warp_tensor_batch", ctx.handle)
+    return _tensor_view(out, n, wt, ht, spec)
+
+
+def project(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
+    """warp through a 3 x 3 homography per image (jpeg_amd_project_batch; include/jpeg_amd.h, "projective resample", holds the
+    contract): matrices [n, 9] or [n, 3, 3], row by row, the INVERSE projective map from the centres of output pixels to source
+    coordinates (perspective_matrix makes one from four point pairs).  The denominator m20 x + m21 y + m22 must stay positive
+    and within 16 : 1 over the canvas (the library judges it).  With the last row (0, 0, 1) this is warp on the first six
+    numbers, bit for bit.  Returns uint8 [n, Ht, Wt, 3]."""
+    images = list(images)
+    n = len(images)
+    m, w = _homographies(matrices, n), _warp(edge, fill)
+    src, src_stride, extents = _pack_images(ctx, images)
+    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
+    _lib.check(_lib.lib().jpeg_amd_project_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt, ht,
+                                                 out.data_ptr(), stride), "jpeg_amd_project_batch", ctx.handle)
+    return out.view(n, ht, wt, 3)
+
+
+def project_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
+                   colour=None, colour_clamp=None):
+    """project with the output stage of the tensor calls (jpeg_amd_project_tensor_batch): flips, spec, colour and colour_clamp
+    as in warp_tensor.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    images = list(images)
+    n = len(images)
+    m, w = _homographies(matrices, n), _warp(edge, fill)
+    tint, keep_colour = _colour(colour, colour_clamp, n)
+    src, src_stride, extents = _pack_images(ctx, images)
+    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
+    _lib.check(_lib.lib().jpeg_amd_project_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w),
+                                                        wt, ht, C.byref(spec), h_flip, None if tint is None else C.byref(tint),
+                                                        out.data_ptr(), stride),
+               "jpeg_amd_project_tensor_batch", ctx.handle)
     return _tensor_view(out, n, wt, ht, spec)
 
 

@@ -51,6 +51,7 @@ struct FilesDecode : FileBatch {
     bool warped = false;                       // "warped resample": pass 0's m_view per file go to the mixed call with the call's warp
     std::vector<float> matrices;
     const jpeg_amd_warp *warp = nullptr;
+    bool projective = false;                   // "projective resample": the matrices are m[9], jpeg_amd_project_view's
     const jpeg_amd_colour *colour = nullptr;   // "colour stage": the call's, of which a chunk takes its files' matrices
     void *d_dst;
     size_t dst_stride, elem_bytes;
@@ -138,7 +139,11 @@ int FilesDecode::submit(int k)
     const jpeg_amd_placement *place = placed ? &here : nullptr;
     const jpeg_amd_colour tint{colour ? colour->h_matrices + 12 * (size_t)ch.i0 : nullptr, colour ? colour->lo : 0.0f, colour ? colour->hi : 0.0f};
     const jpeg_amd_colour *chunk_colour = colour ? &tint : nullptr;   // (nullptr: the calls without a colour stage, as they stand)
-    if (warped)
+    if (warped && projective)
+        JA_TRY(decode_projected_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 9 * (size_t)ch.i0,
+                                            warp, out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride,
+                                            chunk_colour));
+    else if (warped)
         JA_TRY(decode_warped_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 6 * (size_t)ch.i0, warp,
                                          out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride, chunk_colour));
     else if (tensor)
@@ -168,7 +173,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                      const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
                      jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                      int32_t *h_orient_out, bool warped = false, const float *h_matrices = nullptr, const jpeg_amd_warp *warp = nullptr,
-                     float *h_matrices_out = nullptr, const jpeg_amd_colour *colour = nullptr)
+                     float *h_matrices_out = nullptr, const jpeg_amd_colour *colour = nullptr, bool projective = false)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
@@ -185,7 +190,8 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     if (warped) {
         d.warped = true;
         d.warp = warp;
-        d.matrices.assign(6 * (size_t)n_images, 0.0f);
+        d.projective = projective;
+        d.matrices.assign((projective ? 9 : 6) * (size_t)n_images, 0.0f);
     }
     if (place) {
         d.placed = true;
@@ -220,8 +226,11 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
             if (st == JPEG_AMD_OK && warped) {
                 // "warped resample": the matrix says what is read -- the view and the matrix against it are jpeg_amd_warp_view's
                 if (h_orient_out) h_orient_out[i] = o;
-                st = jpeg_amd_warp_view(&f.layout, o, h_matrices + 6 * (size_t)i, out_w, out_h, &f.view, &d.matrices[6 * (size_t)i]);
-                if (st == JPEG_AMD_OK && h_matrices_out) std::memcpy(h_matrices_out + 6 * (size_t)i, &d.matrices[6 * (size_t)i], 6 * sizeof(float));
+                // ("projective resample": jpeg_amd_project_view's, nine numbers each)
+                const size_t k = projective ? 9 : 6;
+                st = projective ? jpeg_amd_project_view(&f.layout, o, h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i])
+                                : jpeg_amd_warp_view(&f.layout, o, h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i]);
+                if (st == JPEG_AMD_OK && h_matrices_out) std::memcpy(h_matrices_out + k * (size_t)i, &d.matrices[k * (size_t)i], k * sizeof(float));
             } else if (st == JPEG_AMD_OK) {
                 if (h_orient) d.orient[(size_t)i] = (uint8_t)o;
                 if (h_orient_out) h_orient_out[i] = o;
@@ -254,9 +263,13 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     // ... then what the mixed call refuses of the files in front of that one, the target included; the tap limit last
     int taps = JPEG_AMD_OK;
     const jpeg_amd_placement judged{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {d.fill[0], d.fill[1], d.fill[2]}, 0};
-    JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
-                                 d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps,
-                                 d.matrices.data(), warp, warped, colour));
+    if (projective)
+        JA_TRY(check_projected_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, spec, tensor, d_dst,
+                                     dst_stride, d.matrices.data(), warp, colour));
+    else
+        JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
+                                     d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps,
+                                     d.matrices.data(), warp, warped, colour));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
@@ -453,5 +466,32 @@ try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
                             spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
                             warp, h_matrices_out, colour);
+}
+JA_NOTHROW_TAIL
+
+// The two file calls through a homography ("projective resample"): each file's view and matrix from jpeg_amd_project_view in
+// pass 0; the tensor form with the "colour stage", or colour == nullptr for none.
+int jpeg_amd_decompress_resized_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                                int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                                const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                                uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
+                                                jpeg_amd_view *h_views, float *h_matrices_out, int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false,
+                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out, true,
+                            h_matrices, warp, h_matrices_out, nullptr, true);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decompress_tensor_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                               int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                               const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                               const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const jpeg_amd_colour *colour,
+                                               void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                               float *h_matrices_out, int32_t *h_orient_out)
+try {
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
+                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
+                            warp, h_matrices_out, colour, true);
 }
 JA_NOTHROW_TAIL

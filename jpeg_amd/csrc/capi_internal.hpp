@@ -132,6 +132,12 @@ int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_imag
                           bool tensor, const uint8_t *h_orient, const jpeg_amd_placement *place, void *d_dst, size_t dst_stride,
                           int *taps, const float *h_view_matrices = nullptr, const jpeg_amd_warp *warp = nullptr, bool warped = false,
                           const jpeg_amd_colour *colour = nullptr);
+// The same of a call of the "projective resample": h_view_matrices [n_images][9], jpeg_amd_project_view's; no filter but the
+// bilinear, no orientations, no placement, and so no tap limit.
+int check_projected_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, bool tensor,
+                          void *d_dst, size_t dst_stride, const float *h_view_matrices, const jpeg_amd_warp *warp,
+                          const jpeg_amd_colour *colour);
 // "colour stage": what the contract requires of a call's colour, judged with the target.
 inline int check_colour(const jpeg_amd_colour &c, int n_images)
 {
@@ -149,12 +155,33 @@ inline int check_warp_matrix(const float *m)
         if (!std::isfinite(m[k]) || std::fabs(m[k]) > kWarpMaxEntry) return JPEG_AMD_EINVAL;
     return JPEG_AMD_OK;
 }
+// "projective resample": what the contract requires of one matrix m[9] on a canvas of out_w x out_h (both in 1 .. 2^30, judged
+// before): the entries as check_warp_matrix's, and the denominator W(cx, cy) = m20 cx + m21 cy + m22 at least S / 16 at the
+// four corners of the canvas, S = |m20| out_w + |m21| out_h + |m22| at least 2^-30.  In double: every product and sum is
+// rounded by at most 2^-53 of itself, so S and W are within 2^-50 S of their exact values, far inside the margin that the
+// header's derivation leaves (it counts 3 * 2^-24 S for the kernel's own rounding).
+inline int check_project_matrix(const float *m, int32_t out_w, int32_t out_h)
+{
+    if (!m) return JPEG_AMD_EINVAL;
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(m[k]) || std::fabs(m[k]) > kWarpMaxEntry) return JPEG_AMD_EINVAL;
+    const double w = out_w, h = out_h, m20 = m[6], m21 = m[7], m22 = m[8];
+    const double S = (std::fabs(m20) * w + std::fabs(m21) * h) + std::fabs(m22);
+    if (S < kProjectMinScale) return JPEG_AMD_EINVAL;
+    const double low = std::min(std::min(m22, m20 * w + m22), std::min(m21 * h + m22, (m20 * w + m21 * h) + m22));
+    return low < S / kProjectMaxForeshortening ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
+}
 // jpeg_amd_decode_warped_mixed (tensor: jpeg_amd_decode_tensor_warped_mixed) behind jpeg_amd_warp_view, for the file calls,
 // whose pass 0 has taken every file's view and m_view already: the views and the matrices against them (capi_view.hip).
 int decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                               const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
                               int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
                               size_t dst_stride, const jpeg_amd_colour *colour = nullptr);
+// The same behind jpeg_amd_project_view ("projective resample"): the matrices are [n_images][9].
+int decode_projected_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                                 const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
+                                 int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
+                                 size_t dst_stride, const jpeg_amd_colour *colour);
 // "placed resample": what a placed call refuses of its placement as a whole, and of one image's window on its canvas.
 inline int check_placement(const jpeg_amd_placement &p, int n_images)
 {

@@ -545,7 +545,10 @@ struct ResampleTarget {
     // oriented and the stored call bit for bit -- and the ColourRecords go up behind the call's resample records, 16-byte
     // aligned, in the same copy.
     const jpeg_amd_colour *colour = nullptr;
-    int n_call = 0;          // the images of the call, of which launch() takes a part: check() sets it
+    // "projective resample": with `warped`, h_matrices holds m[9] per image, a 3 x 3 homography; window(i) judges it on the
+    // canvas where it judges a warp's matrix, record(i) writes the ProjectRecord, and the launch is the project kernels'
+    bool projective = false;
+    int n_call = 0;         // the images of the call, of which launch() takes a part: check() sets it
     size_t elem_bytes = 1;   // of a tensor call: check() sets it
     bool oriented = false;   // check() sets it
     std::vector<jpeg_amd_region> windows;   // of a placed call, per image: check() sizes it, window(i) fills it
@@ -576,7 +579,9 @@ struct ResampleTarget {
     // Image i's window, w x h as it is STORED: judged behind its orientation (and behind check()), in front of record(i).
     int window(int i, int32_t w, int32_t h)
     {
-        if (warped) return w > kWarpMaxSourceSide || h > kWarpMaxSourceSide ? JPEG_AMD_EINVAL : check_warp_matrix(h_matrices + 6 * (size_t)i);
+        if (warped && (w > kWarpMaxSourceSide || h > kWarpMaxSourceSide)) return JPEG_AMD_EINVAL;
+        if (warped && projective) return check_project_matrix(h_matrices + 9 * (size_t)i, out_w, out_h);
+        if (warped) return check_warp_matrix(h_matrices + 6 * (size_t)i);
         if (!place) return JPEG_AMD_OK;
         const OrientedSource s = oriented_source(orientation(i), 0, w, h);
         JA_TRY(placed_window(*place, i, s.w, s.h, out_w, out_h, &windows[(size_t)i]));
@@ -592,13 +597,19 @@ struct ResampleTarget {
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
     size_t record_bytes() const
     {
-        if (warped) return sizeof(WarpRecord);
+        if (warped) return projective ? sizeof(ProjectRecord) : sizeof(WarpRecord);
         if (place || colour) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
         if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
         return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
     }
     int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
+        if (warped && projective) {
+            ProjectRecord r{offset, w, h, {}, h_flip && h_flip[i] ? 1u : 0u, warp->edge, 0u};
+            std::memcpy(r.m, h_matrices + 9 * (size_t)i, sizeof r.m);
+            std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
+            return JPEG_AMD_OK;
+        }
         if (warped) {
             WarpRecord r{offset, w, h, {}, h_flip && h_flip[i] ? 1u : 0u, warp->edge};
             std::memcpy(r.m, h_matrices + 6 * (size_t)i, sizeof r.m);
@@ -636,7 +647,7 @@ struct ResampleTarget {
     {
         uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
         const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
-        const ResampleRecords kind = warped  ? ResampleRecords::Warped
+        const ResampleRecords kind = warped  ? (projective ? ResampleRecords::Projected : ResampleRecords::Warped)
                                      : place || colour ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
         ResampleLaunch l{filter, kind, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride, {0, 0, 0}};
         for (int c = 0; place && c < 3; ++c) l.fill[c] = place->fill[c];
@@ -977,6 +988,18 @@ int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_a
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
     *taps = plan.status;
     return JPEG_AMD_OK;
+}
+
+int jpeg_amd::capi::check_projected_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
+                                          bool tensor, void *d_dst, size_t dst_stride, const float *h_view_matrices,
+                                          const jpeg_amd_warp *warp, const jpeg_amd_colour *colour)
+{
+    ResampleTarget t{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, nullptr, d_dst, dst_stride, nullptr, nullptr, nullptr,
+                     h_view_matrices, warp, true, colour, true};
+    ResizePlan plan;
+    std::vector<MixedPlan> plans;
+    return judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans);
 }
 
 int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
@@ -1377,5 +1400,153 @@ try {
                                                    h_flip, h_views_out, h_matrices_out, d_dst, dst_stride);
     return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
                         h_views_out, h_matrices_out, d_dst, dst_stride, colour);
+}
+JA_NOTHROW_TAIL
+
+// ---- "projective resample" ----
+int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h,
+                          jpeg_amd_view *view, float m_view[9])
+{
+    if (!view || !m_view || !orientation_valid(orientation)) return JPEG_AMD_EINVAL;
+    if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
+    JA_TRY(check_project_matrix(m, out_w, out_h));
+    JA_TRY(check_layout(layout, -1));
+    // 1. the orientation composed into the matrix: output centres to STORED coordinates, homogeneous
+    const Orientation b = orientation_bits(orientation);
+    const double W = layout->width, H = layout->height;
+    double s[9];
+    for (int k = 0; k < 3; ++k) {
+        s[k] = b.T ? m[3 + k] : m[k];
+        s[3 + k] = b.T ? m[k] : m[3 + k];
+        s[6 + k] = m[6 + k];
+    }
+    for (int k = 0; b.fx && k < 3; ++k) s[k] = W * s[6 + k] - s[k];
+    for (int k = 0; b.fy && k < 3; ++k) s[3 + k] = H * s[6 + k] - s[3 + k];
+    // 2. the denominator: the shorter column of the Jacobian at the corners and the centre of the canvas (of the upright map:
+    // the orientation permutes and negates its rows)
+    const double px[5] = {0.0, (double)out_w, 0.0, (double)out_w, 0.5 * (double)out_w};
+    const double py[5] = {0.0, 0.0, (double)out_h, (double)out_h, 0.5 * (double)out_h};
+    double step2 = 0.0;
+    for (int p = 0; p < 5; ++p) {
+        const double nw = ((double)m[6] * px[p] + (double)m[7] * py[p]) + (double)m[8];
+        const double X = (((double)m[0] * px[p] + (double)m[1] * py[p]) + (double)m[2]) / nw;
+        const double Y = (((double)m[3] * px[p] + (double)m[4] * py[p]) + (double)m[5]) / nw;
+        for (int c = 0; c < 2; ++c) {
+            const double jx = ((double)m[c] - X * (double)m[6 + c]) / nw, jy = ((double)m[3 + c] - Y * (double)m[6 + c]) / nw;
+            const double n2 = jx * jx + jy * jy;
+            step2 = p == 0 && c == 0 ? n2 : std::min(step2, n2);
+        }
+    }
+    int denom = 1;
+    for (int d = 8; d > 1; d /= 2)
+        if ((double)(d * d) <= step2) { denom = d; break; }
+    // 3. against the scaled image: the numerators' rows times 1 / d
+    jpeg_amd_layout S;
+    JA_TRY(jpeg_amd_scaled_layout(layout, denom, &S));
+    const double f = (double)(8 / denom) / 8.0;
+    for (int k = 0; k < 6; ++k) s[k] = s[k] * f;
+    // 4. the footprint of the canvas: the denominator is positive on it, so it maps onto the quadrilateral of its corners' images
+    const double cx[4] = {0.0, (double)out_w, 0.0, (double)out_w}, cy[4] = {0.0, 0.0, (double)out_h, (double)out_h};
+    double lo[2], hi[2];
+    for (int c = 0; c < 4; ++c) {
+        const double nw = (s[6] * cx[c] + s[7] * cy[c]) + s[8];
+        for (int a = 0; a < 2; ++a) {
+            const double v = ((s[3 * a] * cx[c] + s[3 * a + 1] * cy[c]) + s[3 * a + 2]) / nw;
+            lo[a] = c == 0 ? v : std::min(lo[a], v);
+            hi[a] = c == 0 ? v : std::max(hi[a], v);
+        }
+    }
+    const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
+    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
+    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
+    // 5. against the view: the view's origin times the denominator's row off the numerators' rows
+    float mv[9];
+    for (int k = 0; k < 3; ++k) {
+        mv[k] = (float)(s[k] - (double)x0 * s[6 + k]);
+        mv[3 + k] = (float)(s[3 + k] - (double)y0 * s[6 + k]);
+        mv[6 + k] = m[6 + k];
+    }
+    JA_TRY(check_project_matrix(mv, out_w, out_h));   // (an entry past 2^30 behind the subtraction)
+    *view = jpeg_amd_view{denom, jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1}};
+    std::memcpy(m_view, mv, sizeof mv);
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_project_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                           const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                           int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_matrices, warp, true, nullptr, true});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_project_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                  const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                                  int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                  const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+try {
+    return resize_images(ctx, n_images, d_src, src_stride, h_extents,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_matrices, warp, true, colour, true});
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd::capi::decode_projected_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                                 jpeg_amd_color color, const jpeg_amd_view *h_views, const float *h_view_matrices,
+                                                 const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
+                                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
+                                                 const jpeg_amd_colour *colour)
+{
+    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
+                                        nullptr, h_view_matrices, warp, true, colour, true});
+}
+
+namespace {
+
+// jpeg_amd_decode_projected_mixed and its tensor form: every image's view and m_view from jpeg_amd_project_view, then the
+// route of the resized mixed calls with project records.
+int projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                    const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                    bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                    float *h_matrices_out, void *d_dst, size_t dst_stride, const jpeg_amd_colour *colour)
+{
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images > 0 && (!h_images || !h_matrices)) return JPEG_AMD_EINVAL;
+    const size_t n = (size_t)n_images;
+    std::vector<jpeg_amd_view> views(n);
+    std::vector<float> view_matrices(9 * n);
+    for (size_t i = 0; i < n; ++i) {
+        JA_TRY(jpeg_amd_project_view(&h_images[i].layout, h_orient ? h_orient[i] : 1, h_matrices + 9 * i, out_w, out_h, &views[i],
+                                     &view_matrices[9 * i]));
+        if (h_views_out) h_views_out[i] = views[i];
+        if (h_matrices_out) std::memcpy(h_matrices_out + 9 * i, &view_matrices[9 * i], 9 * sizeof(float));
+    }
+    return decode_projected_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), view_matrices.data(), warp, out_w, out_h,
+                                        tensor, spec, h_flip, d_dst, dst_stride, colour);
+}
+
+}  // namespace
+
+int jpeg_amd_decode_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                    jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                    const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
+                                    float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
+try {
+    return projected_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, false, nullptr, nullptr,
+                           h_views_out, h_matrices_out, d_pixels, pixel_stride, nullptr);
+}
+JA_NOTHROW_TAIL
+
+int jpeg_amd_decode_tensor_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                           const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
+                                           const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                                           float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+try {
+    return projected_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
+                           h_views_out, h_matrices_out, d_dst, dst_stride, colour);
 }
 JA_NOTHROW_TAIL

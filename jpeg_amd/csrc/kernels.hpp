@@ -171,7 +171,8 @@ hipError_t launch_idct_scaled_plane(hipStream_t stream, int n_images, const int1
 // include/jpeg_amd.h: through one of three filters ("resized decode", "antialiased resample", "bicubic resample"), read as
 // stored or oriented ("oriented resample"), to bytes or to tensor elements ("tensor output").  One record per image, made on
 // the host; which of the six kinds follows from the filter and from whether the call is oriented or placed.  A seventh kind,
-// the WarpRecord ("warped resample"), takes the image through an affine map instead of a scale factor per axis.
+// the WarpRecord ("warped resample"), takes the image through an affine map instead of a scale factor per axis, and an eighth,
+// the ProjectRecord ("projective resample"), through a 3 x 3 homography.
 struct ResizeRecord {      // bilinear
     uint64_t offset;   // bytes from d_src
     int32_t  w, h;     // > 0
@@ -221,6 +222,17 @@ struct WarpRecord {
     int32_t  edge;
 };
 static_assert(sizeof(WarpRecord) == 48, "record layout");
+// Projected ("projective resample"): the WarpRecord with the third row of the matrix, a 3 x 3 homography whose denominator the
+// host has found positive and well conditioned over the whole canvas (check_project_matrix); padded to a cache-line half.
+struct ProjectRecord {
+    uint64_t offset;   // bytes from d_src
+    int32_t  w, h;     // > 0, at most kWarpMaxSourceSide
+    float    m[9];     // m00 ... m22, row by row: finite, at most kWarpMaxEntry in magnitude
+    uint32_t flip;     // as ResizeRecord's
+    int32_t  edge;
+    uint32_t reserved;
+};
+static_assert(sizeof(ProjectRecord) == 64, "record layout");
 // Colour ("colour stage"): beside the resample record of a tensor launch, per image the affine map of (R, G, B) that stands
 // between the resample and the tensor output: row c is k[c][0 .. 2], the matrix row, and k[c][3], the offset.  The kernels read
 // it once per workgroup, through uniform loads in front of the walk.
@@ -231,7 +243,9 @@ static_assert(sizeof(ColourRecord) == 48, "record layout");
 constexpr float kColourMaxEntry = 1073741824.0f; // 2^30: three products of it with a byte and the offset stay finite
 constexpr int   kWarpMaxSourceSide = 1 << 24;    // (float)w and (float)h are exact
 constexpr float kWarpMaxEntry = 1073741824.0f;   // 2^30: with an output side of at most 2^30 no coordinate overflows
-constexpr int   kResizeMaxSide = 1 << 30;        // of the output: the kernels' pixel indices are int
+constexpr double kProjectMinScale = 9.31322574615478515625e-10;   // 2^-30: of S, the scale of a homography's denominator row
+constexpr double kProjectMaxForeshortening = 16.0;               // S over the denominator's minimum on the canvas, at most
+constexpr int   kResizeMaxSide = 1 << 30;       // of the output: the kernels' pixel indices are int
 constexpr float kAntialiasMaxScale = 16.0f;
 constexpr int   kAntialiasMaxTaps = 33;          // the interval [c - s, c + s] rounded outwards: 2 s + 1
 constexpr float kBicubicMaxScale = 8.0f;         // "bicubic resample": [c - 2 s, c + 2 s], 4 s + 1 taps in the same tables
@@ -241,7 +255,7 @@ uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the la
 // (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted and stored in spec->layout.  A spec is
 // valid (jpeg_amd_tensor_extent).  hipErrorInvalidValue: an extent or a tile count past the limits above, null records, or a
 // filter, dtype or layout that no kernel exists for.
-enum class ResampleRecords : int { Stored, Oriented, Placed, Warped };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms; WarpRecord (bilinear only)
+enum class ResampleRecords : int { Stored, Oriented, Placed, Warped, Projected };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms; WarpRecord, ProjectRecord (bilinear only)
 struct ResampleLaunch {
     int filter;                        // JPEG_AMD_FILTER_*
     ResampleRecords records;           // the kind of every record of the launch
@@ -252,9 +266,9 @@ struct ResampleLaunch {
     int out_w, out_h;
     void *d_dst;
     size_t dst_stride;
-    uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window; Warped: of a tap outside the image
+    uint8_t fill[3];                   // Placed: the bytes of a canvas pixel outside the image's window; Warped, Projected: of a tap outside the image
     // "colour stage": nullptr, or ColourRecord 0 of the launch (16-byte aligned) and the clamp's bounds, neither a NaN and
-    // lo <= hi; only with a spec and with Placed or Warped records (anything else: hipErrorInvalidValue)
+    // lo <= hi; only with a spec and with Placed, Warped or Projected records (anything else: hipErrorInvalidValue)
     const void *d_colour = nullptr;
     float lo = 0.0f, hi = 0.0f;
 };

@@ -14,7 +14,9 @@
 //   end with the launch's fill.
 // k_warp_bytes, k_warp_tensor<T, CHW>: "warped resample" -- warp_walk (warp.hpp) over WarpRecords with the same two sinks and
 //   the placed kernels' arguments; no tables, no LDS.
-// k_resize_placed_tensor, k_tables_placed_tensor and k_warp_tensor carry a leading Colour flag: with it the sink is colour_sink
+// k_project_bytes, k_project_tensor<Colour, T, CHW>: "projective resample" -- project_walk (project.hpp) over ProjectRecords, the
+//   warp kernels with another walk: the same grid, arguments and sinks.
+// k_resize_placed_tensor, k_tables_placed_tensor, k_warp_tensor and k_project_tensor carry a leading Colour flag: with it the sink is colour_sink
 //   ("colour stage": an affine map of (R, G, B) per image and a clamp, in front of the mean), the arguments end with the
 //   ColourRecords and the clamp's bounds, and nothing else differs.  These three express every record kind -- a whole-canvas
 //   window is the oriented and the stored call -- so the others have no colour form.
@@ -34,6 +36,7 @@
 #include "antialias.hpp"
 #include "fused_common.hpp"
 #include "kernels.hpp"
+#include "project.hpp"
 #include "resample.hpp"
 #include "tensor_sink.hpp"
 #include "warp.hpp"
@@ -291,6 +294,29 @@ __global__ __launch_bounds__(kThreads) void k_warp_tensor(PlacedSinkArgs<Colour,
     }
 }
 
+__global__ __launch_bounds__(kThreads) void k_project_bytes(PlacedBytesArgs<ProjectRecord> a)
+{
+    uint8_t *dst = image_dst(a);
+    project_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+}
+
+template <bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_project_tensor(PlacedSinkArgs<Colour, T, ProjectRecord> a)
+{
+    T *dst = image_dst(a);
+    const size_t plane = image_plane(a);
+    if constexpr (Colour) {
+        const ColourRecord k = a.colour[blockIdx.y];
+        project_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
+        });
+    } else {
+        project_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+        });
+    }
+}
+
 // ---- the launcher ----
 
 // f(T{}, std::bool_constant<CHW>{}) for the element type and the layout of spec, or what no kernel exists for.
@@ -325,7 +351,8 @@ struct Bilinear;   // in place of a filter of antialias.hpp: resample_walk, whos
 template <typename Filter, typename Record>
 hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const ResampleArgs &head, dim3 grid)
 {
-    constexpr bool warped = std::is_same<Record, WarpRecord>::value;   // (the placed kernels' args: records in tab_records, a fill)
+    constexpr bool projected = std::is_same<Record, ProjectRecord>::value;   // (the warp kernels' args)
+    constexpr bool warped = std::is_same<Record, WarpRecord>::value || projected;   // (the placed kernels' args: records in tab_records, a fill)
     constexpr bool bilinear = std::is_same<Filter, Bilinear>::value, oriented = std::is_same<Record, OrientedResizeRecord>::value;
     constexpr bool placed = std::is_same<Record, PlacedResizeRecord>::value || std::is_same<Record, PlacedAntialiasRecord>::value;
     const auto run = [&](auto kernel, auto a) {   // a: the kernel's args, zeroed
@@ -353,7 +380,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
             using T = decltype(t);
             if constexpr (placed || warped) {
                 if (l.d_colour) {
-                    if constexpr (warped)
+                    if constexpr (projected)
+                        return run(k_project_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
+                    else if constexpr (warped)
                         return run(k_warp_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
                     else if constexpr (bilinear)
                         return run(k_resize_placed_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
@@ -361,7 +390,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
                         return run(k_tables_placed_tensor<true, Filter, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
                 }
             }
-            if constexpr (warped)
+            if constexpr (projected)
+                return run(k_project_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+            else if constexpr (warped)
                 return run(k_warp_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (placed && bilinear)
                 return run(k_resize_placed_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
@@ -373,7 +404,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
                 return run(k_tables_tensor<Filter, Record, T, decltype(chw)::value>, RecordTensorArgs<T, Record>{});
         });
     }
-    if constexpr (warped)
+    if constexpr (projected)
+        return run(k_project_bytes, PlacedBytesArgs<Record>{});
+    else if constexpr (warped)
         return run(k_warp_bytes, PlacedBytesArgs<Record>{});
     else if constexpr (placed && bilinear)
         return run(k_resize_placed_bytes, PlacedBytesArgs<Record>{});
@@ -414,6 +447,8 @@ hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l)
     if (const hipError_t e = resample_launch(l.n_images, l.d_src, nullptr, l.out_w, l.out_h, head, grid)) return e;
     if (l.records == ResampleRecords::Warped)   // "warped resample": the two-tap filter only
         return l.filter == JPEG_AMD_FILTER_BILINEAR ? launch_kernel<Bilinear, WarpRecord>(stream, l, head, grid) : hipErrorInvalidValue;
+    if (l.records == ResampleRecords::Projected)   // "projective resample": likewise
+        return l.filter == JPEG_AMD_FILTER_BILINEAR ? launch_kernel<Bilinear, ProjectRecord>(stream, l, head, grid) : hipErrorInvalidValue;
     switch (l.filter) {
     case JPEG_AMD_FILTER_BILINEAR: return launch_filter<Bilinear, ResizeRecord, OrientedResizeRecord, PlacedResizeRecord>(stream, l, head, grid);
     case JPEG_AMD_FILTER_ANTIALIAS: return launch_filter<TriangleFilter, AntialiasRecord, OrientedAntialiasRecord, PlacedAntialiasRecord>(stream, l, head, grid);

@@ -1382,12 +1382,14 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
                                 orientations=orientations, colour=colour, colour_clamp=colour_clamp), views
 
 
-def _warped_mixed_args(ctx: Context, spectrals, matrices, orientations):
-    """The arguments the warped mixed calls share, behind _mixed_args' (with placeholder views)."""
+def _mapped_mixed_args(ctx: Context, spectrals, matrices, orientations, k: int):
+    """The arguments the warped (k = 6 numbers per matrix) and the projected (k = 9) mixed calls share, behind _mixed_args'
+    (with placeholder views)."""
     spectrals = list(spectrals)
     n = len(spectrals)
     vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, np.zeros((n, 5), np.int32))
-    return n, h_images, h_views, _matrices(matrices, n), _orientations(orientations, n), np.zeros((n, 6), np.float32), keep
+    m = _homographies(matrices, n) if k == 9 else _matrices(matrices, n)
+    return n, h_images, h_views, m, _orientations(orientations, n), np.zeros((n, k), np.float32), keep
 
 
 def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
@@ -1397,7 +1399,7 @@ def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, 
     orientations[i], 1 .. 8; None: as stored).  warp_view chooses each image's denominator and view -- only the part the canvas
     maps into is decoded -- and image i is warp() of decode_views_mixed's pixels for that view with the matrix against it.
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 6])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _warped_mixed_args(ctx, spectrals, matrices, orientations)
+    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 6)
     w = _warp(edge, fill)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     _lib.check(_lib.lib().jpeg_amd_decode_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient, m.ctypes.data,
@@ -1411,7 +1413,7 @@ def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spe
     """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_mixed); flips, spec,
     colour and colour_clamp (jpeg_amd_decode_tensor_warped_colour_mixed) as in warp_tensor.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _warped_mixed_args(ctx, spectrals, matrices, orientations)
+    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 6)
     w = _warp(edge, fill)
     tint, keep_colour = _colour(colour, colour_clamp, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
@@ -1429,14 +1431,6 @@ def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spe
     return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
 
 
-def _projected_mixed_args(ctx: Context, spectrals, matrices, orientations):
-    """The arguments the projected mixed calls share: _warped_mixed_args' with nine numbers per matrix."""
-    spectrals = list(spectrals)
-    n = len(spectrals)
-    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, np.zeros((n, 5), np.int32))
-    return n, h_images, h_views, _homographies(matrices, n), _orientations(orientations, n), np.zeros((n, 9), np.float32), keep
-
-
 def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
                            edge="fill", fill=(0, 0, 0)):
     """decode_warped_mixed through a 3 x 3 homography per image (jpeg_amd_decode_projected_mixed; include/jpeg_amd.h,
@@ -1444,7 +1438,7 @@ def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RG
     makes one from four point pairs).  project_view chooses each image's denominator and view, and image i is project() of
     decode_views_mixed's pixels for that view with the matrix against it.
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 9])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _projected_mixed_args(ctx, spectrals, matrices, orientations)
+    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 9)
     w = _warp(edge, fill)
     wt, ht, out, stride = _bytes_out(ctx, n, out_size)
     _lib.check(_lib.lib().jpeg_amd_decode_projected_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
@@ -1459,7 +1453,7 @@ def decode_tensors_projected_mixed(ctx: Context, spectrals, matrices, out_size, 
     """decode_projected_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_projected_mixed); flips, spec,
     colour and colour_clamp as in project_tensor.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 9])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _projected_mixed_args(ctx, spectrals, matrices, orientations)
+    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 9)
     w = _warp(edge, fill)
     tint, keep_colour = _colour(colour, colour_clamp, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
@@ -1501,6 +1495,13 @@ def _warp_file_args(warp, n: int, source_regions, place, filter_code: int, edge,
 
 def _views_array(h_views, n) -> np.ndarray:
     return np.array([(v.denom, v.region.x, v.region.y, v.region.width, v.region.height) for v in h_views[:n]], np.int32).reshape(n, 5)
+
+
+def _files_result(out, n, wt, ht, spec, h_views, infos, h_orient=None, applied=None):
+    """What decompress_tensors returns of every call: (the tensor, the views, the frame infos), and with orientations given
+    the orientations applied."""
+    res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
+    return res if h_orient is None else res + (np.array(applied[:n], np.int32),)
 
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
@@ -1558,9 +1559,7 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
                                                                           C.byref(spec), h_flip, out.data_ptr(), stride, infos, h_views,
                                                                           m_out.ctypes.data, applied),
                        "jpeg_amd_decompress_tensor_warped_mixed", ctx.handle)
-        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
-        if h_orient is not None:
-            res += (np.array(applied[:n], np.int32),)
+        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
         return res + (m_out,)
     placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
     wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
@@ -1571,9 +1570,7 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
                                                                       None if placement is None else C.byref(placement), h_windows,
                                                                       C.byref(tint), out.data_ptr(), stride, infos, h_views, applied),
                    "jpeg_amd_decompress_tensor_colour_mixed", ctx.handle)
-        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
-        if h_orient is not None:
-            res += (np.array(applied[:n], np.int32),)
+        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
         return res if placement is None else res + (_windows_array(h_windows, n),)
     if placement is not None:
         applied = (C.c_int32 * max(n, 1))()
@@ -1582,21 +1579,19 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
                                                                       C.byref(placement), h_windows, out.data_ptr(), stride, infos,
                                                                       h_views, applied),
                    "jpeg_amd_decompress_tensor_placed_mixed", ctx.handle)
-        res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
-        if h_orient is not None:
-            res += (np.array(applied[:n], np.int32),)
+        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
         return res + (_windows_array(h_windows, n),)
     if h_orient is None:
         _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
                                                                regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
                                                                infos, h_views), "jpeg_amd_decompress_tensor_mixed", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n])
+        return _files_result(out, n, wt, ht, spec, h_views, infos)
     applied = (C.c_int32 * max(n, 1))()
     _lib.check(_lib.lib().jpeg_amd_decompress_tensor_oriented_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
                                                                     color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
                                                                     out.data_ptr(), stride, infos, h_views, applied),
                "jpeg_amd_decompress_tensor_oriented_mixed", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]), np.array(applied[:n], np.int32)
+    return _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,

@@ -37,24 +37,22 @@ struct FileChunk {
     size_t quanta_off, items_off, groups_off, sparse_off, dense_off, device_bytes, slot_bytes;
 };
 
+// The optional outputs of a file call, per file, each nullptr or the caller's array (four types: none can take another's place).
+struct FileOutputs {
+    jpeg_amd_frame_info *h_info = nullptr;
+    jpeg_amd_view *h_views = nullptr;
+    int32_t *h_orient_out = nullptr;
+    float *h_matrices_out = nullptr;
+};
+
 // One call behind its checks.
 struct FilesDecode : FileBatch {
-    int32_t out_w, out_h;
-    int filter;
-    bool tensor;
-    const jpeg_amd_tensor_spec *spec;
-    const uint8_t *h_flip;
-    std::vector<uint8_t> orient;               // per file, what the call applies; empty: the call names no orientations
-    bool placed = false;                       // "placed resample": `windows` per file, pass 0's, go to the mixed call as they are
-    std::vector<jpeg_amd_region> windows;
-    uint8_t fill[3] = {0, 0, 0};
-    bool warped = false;                       // "warped resample": pass 0's m_view per file go to the mixed call with the call's warp
-    std::vector<float> matrices;
-    const jpeg_amd_warp *warp = nullptr;
-    bool projective = false;                   // "projective resample": the matrices are m[9], jpeg_amd_project_view's
-    const jpeg_amd_colour *colour = nullptr;   // "colour stage": the call's, of which a chunk takes its files' matrices
-    void *d_dst;
-    size_t dst_stride, elem_bytes;
+    // what goes to the mixed call: the caller's request, with pass 0's per-file vectors in the place of the caller's arrays
+    ResampleRequest mixed;
+    std::vector<uint8_t> orient;               // per file, what the call applies; empty: no orientations reach the mixed call
+    std::vector<jpeg_amd_region> windows;      // "placed resample": per file, pass 0's, go to the mixed call as they are ...
+    jpeg_amd_placement in_windows;             // ... under this placement
+    std::vector<float> matrices;               // with a map: pass 0's m_view per file
     std::vector<FileSpec> files;               // (the threads write into it until the loop has stopped them)
     std::vector<FileChunk> chunks;
     std::vector<int> chunk_of;                 // per file
@@ -132,27 +130,8 @@ int FilesDecode::submit(int k)
                                     (uint32_t)acc, reinterpret_cast<const uint32_t *>(dev + ch.sparse_off)));
     std::vector<jpeg_amd_view> views((size_t)ch.m);
     for (int i = 0; i < ch.m; ++i) views[(size_t)i] = files[(size_t)(ch.i0 + i)].view;
-    void *d_out = static_cast<char *>(d_dst) + (size_t)ch.i0 * dst_stride * elem_bytes;
-    const uint8_t *h_orient = orient.empty() ? nullptr : orient.data() + ch.i0;   // (nullptr: the calls without orientations)
-    const jpeg_amd_placement here{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, placed ? windows.data() + ch.i0 : nullptr,
-                                  {fill[0], fill[1], fill[2]}, 0};
-    const jpeg_amd_placement *place = placed ? &here : nullptr;
-    const jpeg_amd_colour tint{colour ? colour->h_matrices + 12 * (size_t)ch.i0 : nullptr, colour ? colour->lo : 0.0f, colour ? colour->hi : 0.0f};
-    const jpeg_amd_colour *chunk_colour = colour ? &tint : nullptr;   // (nullptr: the calls without a colour stage, as they stand)
-    if (warped && projective)
-        JA_TRY(decode_projected_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 9 * (size_t)ch.i0,
-                                            warp, out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride,
-                                            chunk_colour));
-    else if (warped)
-        JA_TRY(decode_warped_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), matrices.data() + 6 * (size_t)ch.i0, warp,
-                                         out_w, out_h, tensor, spec, h_flip ? h_flip + ch.i0 : nullptr, d_out, dst_stride, chunk_colour));
-    else if (tensor)
-        JA_TRY(jpeg_amd_decode_tensor_colour_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec,
-                                                   h_flip ? h_flip + ch.i0 : nullptr, h_orient, place, nullptr, chunk_colour, d_out,
-                                                   dst_stride));
-    else
-        JA_TRY(jpeg_amd_decode_resized_placed_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), out_w, out_h, filter,
-                                                    h_orient, place, nullptr, static_cast<uint8_t *>(d_out), dst_stride));
+    ResampleRequest::Room room;
+    JA_TRY(decode_views_mixed(ctx, ch.m, images.data(), cosited, color, views.data(), mixed.images(ch.i0, ch.m, &room)));
     JA_HIP(ctx, hipEventRecord(ctx->file_decoded[slot], ctx->stream));
     JA_HIP(ctx, hipEventRecord(ctx->file_done[slot], ctx->stream));     // the tensor stays where it is: done when the kernels are
     return JPEG_AMD_OK;
@@ -168,36 +147,32 @@ int FilesDecode::run()
                       device([this](int k) { return submit(k); }));
 }
 
+// Every file call: the file arguments, what the caller asked of the resample (rq; with a map, rq.h_matrices against the upright
+// images) and where the per-file results go.
 int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads, int cosited,
-                     jpeg_amd_color color, const jpeg_amd_region *h_source_regions, int32_t out_w, int32_t out_h, int filter, bool tensor,
-                     const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const uint8_t *h_orient, const jpeg_amd_placement *place,
-                     jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
-                     int32_t *h_orient_out, bool warped = false, const float *h_matrices = nullptr, const jpeg_amd_warp *warp = nullptr,
-                     float *h_matrices_out = nullptr, const jpeg_amd_colour *colour = nullptr, bool projective = false)
+                     jpeg_amd_color color, const jpeg_amd_region *h_source_regions, const ResampleRequest &rq, const FileOutputs &out)
 {
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_jpeg || !nbytes)) return JPEG_AMD_EINVAL;
-    if (warped && n_images > 0 && !h_matrices) return JPEG_AMD_EINVAL;
+    const bool mapped = rq.has_map();
+    if (mapped && n_images > 0 && !rq.h_matrices) return JPEG_AMD_EINVAL;
+    const int32_t out_w = rq.out_w, out_h = rq.out_h;
+    const uint8_t *const h_orient = rq.h_orient;
+    const jpeg_amd_placement *const place = rq.place;
+    const size_t k = rq.matrix_floats();
     FilesDecode d;
     d.ctx = ctx; d.h_jpeg = h_jpeg; d.nbytes = nbytes; d.n_images = n_images; d.cosited = cosited; d.color = color;
-    d.out_w = out_w; d.out_h = out_h; d.filter = filter; d.tensor = tensor; d.spec = spec; d.h_flip = h_flip; d.d_dst = d_dst;
-    d.dst_stride = dst_stride;
-    d.colour = colour;
     d.files.resize((size_t)n_images);
-    // (1 behind a refused file: the mixed call's judgement stops in front of it; warped: the orientation goes into the matrix)
-    if (h_orient && !warped) d.orient.assign((size_t)n_images, 1);
-    if (warped) {
-        d.warped = true;
-        d.warp = warp;
-        d.projective = projective;
-        d.matrices.assign((projective ? 9 : 6) * (size_t)n_images, 0.0f);
-    }
-    if (place) {
-        d.placed = true;
-        d.windows.assign((size_t)n_images, jpeg_amd_region{0, 0, 0, 0});
-        for (int c = 0; c < 3; ++c) d.fill[c] = place->fill[c];
-    }
+    // (1 behind a refused file: the mixed call's judgement stops in front of it; mapped: the orientation goes into the matrix)
+    if (h_orient && !mapped) d.orient.assign((size_t)n_images, 1);
+    if (mapped) d.matrices.assign(k * (size_t)n_images, 0.0f);
+    if (place) d.windows.assign((size_t)n_images, jpeg_amd_region{0, 0, 0, 0});
+    d.in_windows = jpeg_amd_placement{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {0, 0, 0}, 0};
+    for (int c = 0; place && c < 3; ++c) d.in_windows.fill[c] = place->fill[c];
+    d.mixed = rq;
+    d.mixed.oriented(d.orient.empty() ? nullptr : d.orient.data()).placed(place ? &d.in_windows : nullptr, nullptr);
+    if (mapped) d.mixed.mapped(rq.map, d.matrices.data(), rq.warp);
     // ---- pass 0: the headers, file by file; the first file that is refused ends it
     int bad = n_images, bad_status = JPEG_AMD_OK;
     std::vector<jpeg_amd_image> images((size_t)n_images);
@@ -207,7 +182,7 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
         int st = h_jpeg[i] ? jpeg_amd_jpeg_inspect(h_jpeg[i], nbytes[i], &f.info) : JPEG_AMD_EINVAL;
         if (st == JPEG_AMD_OK && !jpeg_common(f.info.precision, f.info.ncomponents)) st = JPEG_AMD_ENOSUP;
         if (st == JPEG_AMD_OK) {
-            if (h_info) h_info[i] = f.info;
+            if (out.h_info) out.h_info[i] = f.info;
             f.layout = layout_of_info(f.info, f.info.ncomponents);
             // the orientation the call applies: the file's tag, or the caller's value; the source rectangle is one of the
             // ORIENTED image then, and `source` the stored rectangle that holds its pixels
@@ -223,17 +198,17 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
                 seen = h_source_regions ? h_source_regions[i] : jpeg_amd_region{0, 0, whole.w, whole.h};
                 st = jpeg_amd_orient_region(o, f.info.width, f.info.height, &seen, &source);
             }
-            if (st == JPEG_AMD_OK && warped) {
-                // "warped resample": the matrix says what is read -- the view and the matrix against it are jpeg_amd_warp_view's
-                if (h_orient_out) h_orient_out[i] = o;
-                // ("projective resample": jpeg_amd_project_view's, nine numbers each)
-                const size_t k = projective ? 9 : 6;
-                st = projective ? jpeg_amd_project_view(&f.layout, o, h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i])
-                                : jpeg_amd_warp_view(&f.layout, o, h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i]);
-                if (st == JPEG_AMD_OK && h_matrices_out) std::memcpy(h_matrices_out + k * (size_t)i, &d.matrices[k * (size_t)i], k * sizeof(float));
+            if (st == JPEG_AMD_OK && mapped) {
+                // the matrix says what is read -- the view and the matrix against it are jpeg_amd_warp_view's, or
+                // ("projective resample") jpeg_amd_project_view's, nine numbers each
+                if (out.h_orient_out) out.h_orient_out[i] = o;
+                const auto view_of = rq.map == ResampleMap::Projective ? jpeg_amd_project_view : jpeg_amd_warp_view;
+                st = view_of(&f.layout, o, rq.h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i]);
+                if (st == JPEG_AMD_OK && out.h_matrices_out)
+                    std::memcpy(out.h_matrices_out + k * (size_t)i, &d.matrices[k * (size_t)i], k * sizeof(float));
             } else if (st == JPEG_AMD_OK) {
                 if (h_orient) d.orient[(size_t)i] = (uint8_t)o;
-                if (h_orient_out) h_orient_out[i] = o;
+                if (out.h_orient_out) out.h_orient_out[i] = o;
                 // the data-loader call's view (decode_crops_tensor_mixed): the cheapest denominator, then the rectangle at it
                 // placed: the file's window, of the oriented rectangle's size; the denominator is chosen against it
                 jpeg_amd_region want{0, 0, out_w, out_h};
@@ -249,8 +224,8 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
             }
         }
         if (st != JPEG_AMD_OK) { bad = i; bad_status = st; break; }
-        if (h_views) h_views[i] = f.view;
-        if (place && h_windows_out) h_windows_out[i] = d.windows[(size_t)i];
+        if (out.h_views) out.h_views[i] = f.view;
+        if (place && rq.h_windows_out) rq.h_windows_out[i] = d.windows[(size_t)i];
         views[(size_t)i] = f.view;
         // (the planes do not exist yet: what the mixed call judges of a pointer is that it is there)
         jpeg_amd_image &im = images[(size_t)i];
@@ -262,19 +237,10 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
     }
     // ... then what the mixed call refuses of the files in front of that one, the target included; the tap limit last
     int taps = JPEG_AMD_OK;
-    const jpeg_amd_placement judged{JPEG_AMD_PLACE_WINDOWS, JPEG_AMD_ANCHOR_CENTRE, d.windows.data(), {d.fill[0], d.fill[1], d.fill[2]}, 0};
-    if (projective)
-        JA_TRY(check_projected_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, spec, tensor, d_dst,
-                                     dst_stride, d.matrices.data(), warp, colour));
-    else
-        JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), out_w, out_h, filter, spec, tensor,
-                                     d.orient.empty() ? nullptr : d.orient.data(), place ? &judged : nullptr, d_dst, dst_stride, &taps,
-                                     d.matrices.data(), warp, warped, colour));
+    JA_TRY(check_resampled_mixed(n_images, bad, images.data(), cosited, color, views.data(), d.mixed, &taps));
     JA_TRY(bad_status);
     JA_TRY(taps);
     if (n_images == 0) return JPEG_AMD_OK;   // nothing to do, and no context needed for it
-    d.elem_bytes = 1;
-    if (tensor) JA_TRY(jpeg_amd_tensor_extent(spec, out_w, out_h, &d.elem_bytes, nullptr));
 
     // ---- the windows, and the chunks: consecutive files, at most kChunkFiles and kChunkPlaneBytes of planes
     const size_t rec_bytes = expand_mixed_record_bytes();
@@ -345,8 +311,9 @@ int jpeg_amd_decompress_tensor_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_j
                                      int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
                                      size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, nullptr, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, nullptr);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride).through(filter),
+                            FileOutputs{h_info, h_views});
 }
 JA_NOTHROW_TAIL
 
@@ -355,8 +322,9 @@ int jpeg_amd_decompress_resized_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_
                                       int32_t out_h, int filter, uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
                                       jpeg_amd_view *h_views)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, nullptr);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride).through(filter),
+                            FileOutputs{h_info, h_views});
 }
 JA_NOTHROW_TAIL
 
@@ -367,8 +335,9 @@ int jpeg_amd_decompress_tensor_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t *
                                               const uint8_t *h_flip, const uint8_t *h_orient, void *d_dst, size_t dst_stride,
                                               jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride).through(filter).oriented(h_orient),
+                            FileOutputs{h_info, h_views, h_orient_out});
 }
 JA_NOTHROW_TAIL
 
@@ -378,8 +347,9 @@ int jpeg_amd_decompress_resized_oriented_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride).through(filter).oriented(h_orient),
+                            FileOutputs{h_info, h_views, h_orient_out});
 }
 JA_NOTHROW_TAIL
 
@@ -391,8 +361,10 @@ int jpeg_amd_decompress_tensor_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *co
                                             jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info,
                                             jpeg_amd_view *h_views, int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views, h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                .through(filter).oriented(h_orient).placed(place, h_windows_out),
+                            FileOutputs{h_info, h_views, h_orient_out});
 }
 JA_NOTHROW_TAIL
 
@@ -403,8 +375,10 @@ int jpeg_amd_decompress_resized_placed_mixed(jpeg_amd_ctx *ctx, const uint8_t *c
                                              size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                              int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, false,
-                            nullptr, nullptr, h_orient, place, h_windows_out, d_pixels, pixel_stride, h_info, h_views, h_orient_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                                .through(filter).oriented(h_orient).placed(place, h_windows_out),
+                            FileOutputs{h_info, h_views, h_orient_out});
 }
 JA_NOTHROW_TAIL
 
@@ -415,9 +389,10 @@ int jpeg_amd_decompress_resized_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *c
                                              uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                              float *h_matrices_out, int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false,
-                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out, true,
-                            h_matrices, warp, h_matrices_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
+                            ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                                .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp),
+                            FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL
 
@@ -428,13 +403,15 @@ int jpeg_amd_decompress_tensor_warped_mixed(jpeg_amd_ctx *ctx, const uint8_t *co
                                             jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
                                             int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
-                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
-                            warp, h_matrices_out);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp),
+                            FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL
 
-// The two file calls to a tensor with the "colour stage": with colour == nullptr each is the call it is named after.
+// The two file calls to a tensor with the "colour stage": with colour == nullptr each is the call it is named after, whose
+// request it then builds.
 int jpeg_amd_decompress_tensor_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
                                             int nthreads, int cosited, jpeg_amd_color color, const jpeg_amd_region *h_source_regions,
                                             int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
@@ -442,13 +419,10 @@ int jpeg_amd_decompress_tensor_colour_mixed(jpeg_amd_ctx *ctx, const uint8_t *co
                                             jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
                                             jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, int32_t *h_orient_out)
 try {
-    if (!colour)
-        return jpeg_amd_decompress_tensor_placed_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h,
-                                                       filter, spec, h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views,
-                                                       h_orient_out);
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions, out_w, out_h, filter, true, spec,
-                            h_flip, h_orient, place, h_windows_out, d_dst, dst_stride, h_info, h_views, h_orient_out, false, nullptr,
-                            nullptr, nullptr, colour);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_source_regions,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                .through(filter).oriented(h_orient).placed(place, h_windows_out).coloured(colour),
+                            FileOutputs{h_info, h_views, h_orient_out});
 }
 JA_NOTHROW_TAIL
 
@@ -459,13 +433,10 @@ int jpeg_amd_decompress_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, const uint
                                                    void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                    float *h_matrices_out, int32_t *h_orient_out)
 try {
-    if (!colour)
-        return jpeg_amd_decompress_tensor_warped_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_orient, h_matrices, warp,
-                                                       out_w, out_h, spec, h_flip, d_dst, dst_stride, h_info, h_views, h_matrices_out,
-                                                       h_orient_out);
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
-                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
-                            warp, h_matrices_out, colour);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp).coloured(colour),
+                            FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL
 
@@ -477,9 +448,10 @@ int jpeg_amd_decompress_resized_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t
                                                 uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
                                                 jpeg_amd_view *h_views, float *h_matrices_out, int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false,
-                            nullptr, nullptr, h_orient, nullptr, nullptr, d_pixels, pixel_stride, h_info, h_views, h_orient_out, true,
-                            h_matrices, warp, h_matrices_out, nullptr, true);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
+                            ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                                .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
+                            FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL
 
@@ -490,8 +462,9 @@ int jpeg_amd_decompress_tensor_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                float *h_matrices_out, int32_t *h_orient_out)
 try {
-    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true,
-                            spec, h_flip, h_orient, nullptr, nullptr, d_dst, dst_stride, h_info, h_views, h_orient_out, true, h_matrices,
-                            warp, h_matrices_out, colour, true);
+    return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
+                            ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
+                            FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL

@@ -1,5 +1,6 @@
 // capi_internal.hpp -- what the units of the C layer (capi*.hip) share: the context, the status macros, the layout checks,
-// the argument record of the batch decodes and the buffer and staging helpers.  The helpers are defined in capi.hip.
+// the argument record of the batch decodes and the buffer and staging helpers.  The helpers are defined in capi.hip.  The
+// request record of the resample calls, and the two internal routes that take it, are in resample_request.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 
 #include "interleave.hpp"
 #include "kernels.hpp"
+#include "resample_request.hpp"
 #include "sparse_format.hpp"
 #include "transform.hpp"
 #include "worker_pool.hpp"
@@ -121,23 +123,7 @@ int check_tensor_source(int n_images, const void *d_src, size_t src_stride, int3
 
 // What jpeg_amd_spectral_expand_mixed requires of one item; *groups: the workgroups it takes (capi.hip).
 int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
-// What jpeg_amd_decode_resized_filter_mixed (tensor: jpeg_amd_decode_tensor_filter_mixed) refuses before it looks at the
-// context, for the file calls, which judge a call before its planes exist (the images' pointers only have to be non-null):
-// of the first `judged` images of a call of n_images, in the mixed call's order; *taps: with judged == n_images the verdict on
-// the antialiasing filter's tap limit, which that call gives last (capi_view.hip).  h_orient: as in the *_oriented_mixed calls
-// (n_images values, or nullptr); place: as in the *_placed_mixed calls (or nullptr); colour: as in the *_colour_mixed calls
-// (or nullptr).
-int check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter, const jpeg_amd_tensor_spec *spec,
-                          bool tensor, const uint8_t *h_orient, const jpeg_amd_placement *place, void *d_dst, size_t dst_stride,
-                          int *taps, const float *h_view_matrices = nullptr, const jpeg_amd_warp *warp = nullptr, bool warped = false,
-                          const jpeg_amd_colour *colour = nullptr);
-// The same of a call of the "projective resample": h_view_matrices [n_images][9], jpeg_amd_project_view's; no filter but the
-// bilinear, no orientations, no placement, and so no tap limit.
-int check_projected_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, bool tensor,
-                          void *d_dst, size_t dst_stride, const float *h_view_matrices, const jpeg_amd_warp *warp,
-                          const jpeg_amd_colour *colour);
+// (check_resampled_mixed and decode_views_mixed, what the file calls use of the mixed resample calls: resample_request.hpp)
 // "colour stage": what the contract requires of a call's colour, judged with the target.
 inline int check_colour(const jpeg_amd_colour &c, int n_images)
 {
@@ -171,17 +157,6 @@ inline int check_project_matrix(const float *m, int32_t out_w, int32_t out_h)
     const double low = std::min(std::min(m22, m20 * w + m22), std::min(m21 * h + m22, (m20 * w + m21 * h) + m22));
     return low < S / kProjectMaxForeshortening ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
 }
-// jpeg_amd_decode_warped_mixed (tensor: jpeg_amd_decode_tensor_warped_mixed) behind jpeg_amd_warp_view, for the file calls,
-// whose pass 0 has taken every file's view and m_view already: the views and the matrices against them (capi_view.hip).
-int decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                              const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
-                              int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
-                              size_t dst_stride, const jpeg_amd_colour *colour = nullptr);
-// The same behind jpeg_amd_project_view ("projective resample"): the matrices are [n_images][9].
-int decode_projected_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                                 const jpeg_amd_view *h_views, const float *h_view_matrices, const jpeg_amd_warp *warp, int32_t out_w,
-                                 int32_t out_h, bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst,
-                                 size_t dst_stride, const jpeg_amd_colour *colour);
 // "placed resample": what a placed call refuses of its placement as a whole, and of one image's window on its canvas.
 inline int check_placement(const jpeg_amd_placement &p, int n_images)
 {

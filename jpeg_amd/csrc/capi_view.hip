@@ -514,58 +514,45 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
     return JPEG_AMD_OK;
 }
 
-// Where the resampled images of a call go, and through which filter: bytes or, in a tensor call, elements of `spec`
-// (launch_resample).  `tensor` is not `spec != nullptr`: a tensor call without a spec is jpeg_amd_tensor_extent's to refuse.  The records of a call are bytes on the host, record_bytes() per image:
-// ResizeRecord for the bilinear kernels, as ever, AntialiasRecord for the others (the bicubic filter fills the same one).
-// h_orient ("oriented resample"): per image an orientation in 1 .. 8, or nullptr.  A call in which it is nullptr or every
-// value is 1 is today's call -- today's records, today's kernels; in any other, check() sets `oriented`, every record is the
-// oriented one (orientation 1 included: base = offset, steps 3 and 3 w) and ONE launch of the oriented kernels takes them all.
-// place ("placed resample"): the call's placement, or nullptr, which is the oriented call -- its records, its kernels.  With
-// one, check() judges it with the target, window(i) judges and keeps image i's window (behind its orientation), every record
-// is the placed one of its filter, its scale factors the window's, and ONE launch of the placed kernels takes them all.
-struct ResampleTarget {
-    int32_t out_w, out_h;
-    int filter;              // JPEG_AMD_FILTER_*
-    bool tensor;
-    const jpeg_amd_tensor_spec *spec;
-    const uint8_t *h_flip;   // per image, or nullptr: none is mirrored
-    void *d_dst;
-    size_t stride;           // between images, in elements
-    const uint8_t *h_orient = nullptr;   // per image, or nullptr: every image as it is stored
-    const jpeg_amd_placement *place = nullptr;
-    jpeg_amd_region *h_windows_out = nullptr;   // per image, or nullptr: window(i) writes it
-    // "warped resample": `warped` makes the call one (bilinear, no orientations, no placement); per image the matrix m[6]
-    // against the image AS IT IS STORED at the launch's source (of a view: jpeg_amd_warp_view's m_view), and the call's warp
-    const float *h_matrices = nullptr;
-    const jpeg_amd_warp *warp = nullptr;
-    bool warped = false;
-    // "colour stage": the call's colour, or nullptr, which is the call without one -- its records, its kernels.  With one,
-    // check() judges it with the target (a byte target has no colour stage), every record that is not a warp record is the
-    // PLACED one of its filter -- without a placement its window is the whole canvas, which "placed resample" makes the
-    // oriented and the stored call bit for bit -- and the ColourRecords go up behind the call's resample records, 16-byte
-    // aligned, in the same copy.
-    const jpeg_amd_colour *colour = nullptr;
-    // "projective resample": with `warped`, h_matrices holds m[9] per image, a 3 x 3 homography; window(i) judges it on the
-    // canvas where it judges a warp's matrix, record(i) writes the ProjectRecord, and the launch is the project kernels'
-    bool projective = false;
-    int n_call = 0;         // the images of the call, of which launch() takes a part: check() sets it
-    size_t elem_bytes = 1;   // of a tensor call: check() sets it
-    bool oriented = false;   // check() sets it
-    std::vector<jpeg_amd_region> windows;   // of a placed call, per image: check() sizes it, window(i) fills it
+// A resample call behind its request (resample_request.hpp): what the caller asked for, and what check() derives of it.  The
+// records of a call are bytes on the host, record_bytes() per image, of the kind that check() decides ONCE:
+//   Stored    no orientations, or every one of them 1: ResizeRecord for the bilinear kernels, AntialiasRecord for the others
+//             (the bicubic filter fills the same one);
+//   Oriented  ("oriented resample") some orientation is not 1: every record is the oriented one (orientation 1 included: base =
+//             offset, steps 3 and 3 w) and ONE launch of the oriented kernels takes them all;
+//   Placed    ("placed resample") a placement: check() judges it with the target, window(i) judges and keeps image i's window
+//             (behind its orientation), every record is the placed one of its filter, its scale factors the window's, and ONE
+//             launch of the placed kernels takes them all.  Also ("colour stage") a colour without a placement: its window is
+//             the whole canvas, which "placed resample" makes the oriented and the stored call bit for bit;
+//   Warped, Projected  ("warped resample", "projective resample") a map: bilinear, no orientations, no placement; window(i)
+//             judges image i's matrix, record(i) writes the WarpRecord or the ProjectRecord.
+// With a colour, check() judges it with the target (a byte target has no colour stage), and the ColourRecords go up behind the
+// call's resample records, 16-byte aligned, in the same copy.
+struct ResampleTarget : ResampleRequest {
+    int n_call = 0;   // the images of the call, of which launch() takes a part: check() sets it
+    ResampleRecords kind = ResampleRecords::Stored;   // check() sets it
+    std::vector<jpeg_amd_region> windows;   // of a call with a placement, per image: check() sizes it, window(i) fills it
 
+    explicit ResampleTarget(const ResampleRequest &rq) : ResampleRequest(rq) {}
     bool bicubic() const { return filter == JPEG_AMD_FILTER_BICUBIC; }
     bool antialias() const { return filter == JPEG_AMD_FILTER_ANTIALIAS || bicubic(); }   // the kernels with tables: their records
     float max_scale() const { return bicubic() ? kBicubicMaxScale : kAntialiasMaxScale; }
     int check(int n_images)
     {
-        oriented = false;   // (not a verdict: which records the call writes)
         n_call = std::max(n_images, 0);
-        for (int i = 0; h_orient && i < n_images; ++i) oriented = oriented || h_orient[i] != 1;
+        bool turned = false;   // (not a verdict: which records the call writes)
+        for (int i = 0; h_orient && i < n_images; ++i) turned = turned || h_orient[i] != 1;
+        kind = map == ResampleMap::Projective ? ResampleRecords::Projected
+               : map == ResampleMap::Affine   ? ResampleRecords::Warped
+               : place || colour              ? ResampleRecords::Placed
+               : turned                       ? ResampleRecords::Oriented
+                                              : ResampleRecords::Stored;
         if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
+        size_t elem_bytes = 1;
         JA_TRY(tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride));
         if (colour) JA_TRY(tensor ? check_colour(*colour, n_images) : JPEG_AMD_EINVAL);
-        if (warped) {
+        if (has_map()) {
             if (filter != JPEG_AMD_FILTER_BILINEAR || h_orient || place || !warp) return JPEG_AMD_EINVAL;
             if (warp->edge != JPEG_AMD_EDGE_FILL && warp->edge != JPEG_AMD_EDGE_REPLICATE) return JPEG_AMD_EINVAL;
             return n_images > 0 && !h_matrices ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
@@ -575,14 +562,17 @@ struct ResampleTarget {
         windows.assign((size_t)std::max(n_images, 0), jpeg_amd_region{0, 0, 0, 0});
         return JPEG_AMD_OK;
     }
-    int orientation(int i) const { return place ? (h_orient ? h_orient[i] : 1) : oriented ? h_orient[i] : 1; }
+    int orientation(int i) const { return h_orient ? h_orient[i] : 1; }
     // Image i's window, w x h as it is STORED: judged behind its orientation (and behind check()), in front of record(i).
     int window(int i, int32_t w, int32_t h)
     {
-        if (warped && (w > kWarpMaxSourceSide || h > kWarpMaxSourceSide)) return JPEG_AMD_EINVAL;
-        if (warped && projective) return check_project_matrix(h_matrices + 9 * (size_t)i, out_w, out_h);
-        if (warped) return check_warp_matrix(h_matrices + 6 * (size_t)i);
-        if (!place) return JPEG_AMD_OK;
+        if (has_map() && (w > kWarpMaxSourceSide || h > kWarpMaxSourceSide)) return JPEG_AMD_EINVAL;
+        switch (kind) {
+        case ResampleRecords::Projected: return check_project_matrix(h_matrices + 9 * (size_t)i, out_w, out_h);
+        case ResampleRecords::Warped: return check_warp_matrix(h_matrices + 6 * (size_t)i);
+        case ResampleRecords::Placed: if (place) break;   // (a colour alone: the whole canvas)
+        default: return JPEG_AMD_OK;
+        }
         const OrientedSource s = oriented_source(orientation(i), 0, w, h);
         JA_TRY(placed_window(*place, i, s.w, s.h, out_w, out_h, &windows[(size_t)i]));
         if (h_windows_out) h_windows_out[i] = windows[(size_t)i];
@@ -590,28 +580,32 @@ struct ResampleTarget {
     }
     // Image i's orientation: judged with the image's other arguments, behind them, by the callers.  record(i) comes after it.
     int check_orientation(int i) const { return !h_orient || orientation_valid(h_orient[i]) ? JPEG_AMD_OK : JPEG_AMD_EINVAL; }
+    size_t record_bytes() const
+    {
+        switch (kind) {
+        case ResampleRecords::Projected: return sizeof(ProjectRecord);
+        case ResampleRecords::Warped: return sizeof(WarpRecord);
+        case ResampleRecords::Placed: return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
+        case ResampleRecords::Oriented: return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
+        default: return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
+        }
+    }
     // Image i of the call, w x h as it is STORED at `offset` bytes from the launch's source.  The scale factors of the
     // contract: divided here, in binary32, never on the device; of an oriented call they are the ORIENTED extent's.
     // ENOSUP: the tap limit of the filter the target carries, kx or ky above kAntialiasMaxScale (the bicubic filter, whose
     // record is the antialiasing one's: kBicubicMaxScale).  The record is written either way, and
     // the caller keeps the verdict of the first such image until everything else of the call has been judged.
-    size_t record_bytes() const
-    {
-        if (warped) return projective ? sizeof(ProjectRecord) : sizeof(WarpRecord);
-        if (place || colour) return antialias() ? sizeof(PlacedAntialiasRecord) : sizeof(PlacedResizeRecord);
-        if (oriented) return antialias() ? sizeof(OrientedAntialiasRecord) : sizeof(OrientedResizeRecord);
-        return antialias() ? sizeof(AntialiasRecord) : sizeof(ResizeRecord);
-    }
     int record(std::vector<uint8_t> &rec, int at, int i, uint64_t offset, int32_t w, int32_t h) const
     {
-        if (warped && projective) {
-            ProjectRecord r{offset, w, h, {}, h_flip && h_flip[i] ? 1u : 0u, warp->edge, 0u};
+        const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
+        if (kind == ResampleRecords::Projected) {
+            ProjectRecord r{offset, w, h, {}, flip, warp->edge, 0u};
             std::memcpy(r.m, h_matrices + 9 * (size_t)i, sizeof r.m);
             std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
             return JPEG_AMD_OK;
         }
-        if (warped) {
-            WarpRecord r{offset, w, h, {}, h_flip && h_flip[i] ? 1u : 0u, warp->edge};
+        if (kind == ResampleRecords::Warped) {
+            WarpRecord r{offset, w, h, {}, flip, warp->edge};
             std::memcpy(r.m, h_matrices + 6 * (size_t)i, sizeof r.m);
             std::memcpy(rec.data() + (size_t)at * sizeof r, &r, sizeof r);
             return JPEG_AMD_OK;
@@ -619,7 +613,6 @@ struct ResampleTarget {
         const OrientedSource s = oriented_source(orientation(i), offset, w, h);   // (1: the stored image)
         const jpeg_amd_region win = place ? windows[(size_t)i] : jpeg_amd_region{0, 0, out_w, out_h};   // (placed: the window's factors)
         const float kx = (float)s.w / (float)win.width, ky = (float)s.h / (float)win.height;
-        const uint32_t flip = h_flip && h_flip[i] ? 1u : 0u;
         if (!antialias()) {
             PlacedResizeRecord r{};
             static_cast<OrientedResizeRecord &>(r) = OrientedResizeRecord{{s.base, s.w, s.h, kx, ky, flip, 0u}, s.step_x, s.step_y};
@@ -645,13 +638,11 @@ struct ResampleTarget {
     // Images [i0, i0 + m) of the call, from their records: record i0 of d_rec onwards, and ColourRecord i0 of the call's.
     hipError_t launch(hipStream_t stream, int m, const uint8_t *d_src, const void *d_rec, int i0) const
     {
-        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * elem_bytes;
+        uint8_t *d_out = static_cast<uint8_t *>(d_dst) + (size_t)i0 * stride * element_bytes();
         const uint8_t *rec = static_cast<const uint8_t *>(d_rec) + (size_t)i0 * record_bytes();
-        const ResampleRecords kind = warped  ? (projective ? ResampleRecords::Projected : ResampleRecords::Warped)
-                                     : place || colour ? ResampleRecords::Placed : oriented ? ResampleRecords::Oriented : ResampleRecords::Stored;
         ResampleLaunch l{filter, kind, tensor ? spec : nullptr, m, d_src, rec, out_w, out_h, d_out, stride, {0, 0, 0}};
         for (int c = 0; place && c < 3; ++c) l.fill[c] = place->fill[c];
-        for (int c = 0; warped && c < 3; ++c) l.fill[c] = warp->fill[c];
+        for (int c = 0; has_map() && c < 3; ++c) l.fill[c] = warp->fill[c];
         if (colour) {
             l.d_colour = static_cast<const uint8_t *>(d_rec) + colour_at(n_call) + (size_t)i0 * sizeof(ColourRecord);
             l.lo = colour->lo;
@@ -716,8 +707,9 @@ int resample_chunks(jpeg_amd_ctx *ctx, const ResizePlan &plan, const ResampleTar
 
 // jpeg_amd_resize_batch and jpeg_amd_resize_tensor_batch, and their forms with a filter.
 int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride, const jpeg_amd_extent *h_extents,
-                  ResampleTarget t)
+                  const ResampleRequest &rq)
 {
+    ResampleTarget t(rq);
     // every argument first, the context last: nothing is enqueued, and the device is not touched, for a call that is refused
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     JA_TRY(t.check(n_images));
@@ -745,8 +737,9 @@ int resize_images(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t 
 }
 
 // jpeg_amd_decode_resized_batch and jpeg_amd_decode_tensor_batch, and their forms with a filter; c.d_pixels is t.d_dst, and its stride is not looked at.
-int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, ResampleTarget t)
+int decode_resampled(jpeg_amd_ctx *ctx, const DecodeCall &c, const jpeg_amd_view *h_views, const ResampleRequest &rq)
 {
+    ResampleTarget t(rq);
     // everything the view call refuses is refused here, before its first chunk is enqueued (the intermediate's stride is
     // ours and always large enough), then what the target refuses
     DecodeCall views = c;
@@ -793,7 +786,7 @@ int jpeg_amd_decode_resized(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const i
 {
     // as jpeg_amd_decode_view: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_pixels, 0}.check(1)));
+    JA_TRY(ResampleTarget(ResampleRequest::bytes(out_w, out_h, d_pixels, 0)).check(1));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -841,7 +834,7 @@ int jpeg_amd_decode_tensor(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, const in
 {
     // as jpeg_amd_decode_resized: what can be refused is refused before a table is staged
     JA_TRY(check_one_view(L, ntables, color, view));
-    JA_TRY((ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, nullptr, d_dst, 0}.check(1)));
+    JA_TRY(ResampleTarget(ResampleRequest::elements(out_w, out_h, spec, nullptr, d_dst, 0)).check(1));
     JA_TRY(bind(ctx));
     const uint16_t *d_q = nullptr;
     JA_TRY(stage_quanta(ctx, h_quanta, ntables, &d_q));
@@ -956,11 +949,14 @@ int judge_resized_mixed(int n_images, int judged, const jpeg_amd_image *h_images
     return JPEG_AMD_OK;
 }
 
-// jpeg_amd_decode_resized_mixed and jpeg_amd_decode_tensor_mixed: decode_resampled's route with the mixed view decode.
-int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                  const jpeg_amd_view *h_views, ResampleTarget t)
-{
+}  // namespace
+
+// The route of the mixed resample calls: decode_resampled's with the mixed view decode.
+int jpeg_amd::capi::decode_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                       jpeg_amd_color color, const jpeg_amd_view *h_views, const ResampleRequest &rq)
+try {
     // every argument first, the context last
+    ResampleTarget t(rq);
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, n_images, h_images, cosited, color, h_views, t, &plan, &plans));
@@ -971,35 +967,17 @@ int resized_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_image
         return run_mixed(ctx, h_images + k.i0, h_views + k.i0, k.m, plans[c], cosited, color, d_views, k.stride);
     });
 }
-
-}  // namespace
+JA_NOTHROW_TAIL
 
 int jpeg_amd::capi::check_resampled_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, int filter,
-                                          const jpeg_amd_tensor_spec *spec, bool tensor, const uint8_t *h_orient,
-                                          const jpeg_amd_placement *place, void *d_dst, size_t dst_stride, int *taps,
-                                          const float *h_view_matrices, const jpeg_amd_warp *warp, bool warped,
-                                          const jpeg_amd_colour *colour)
+                                          const jpeg_amd_view *h_views, const ResampleRequest &rq, int *taps)
 {
-    ResampleTarget t{out_w, out_h, filter, tensor, spec, nullptr, d_dst, dst_stride, h_orient, place, nullptr, h_view_matrices, warp, warped,
-                     colour};
+    ResampleTarget t(rq);
     ResizePlan plan;
     std::vector<MixedPlan> plans;
     JA_TRY(judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans));
     *taps = plan.status;
     return JPEG_AMD_OK;
-}
-
-int jpeg_amd::capi::check_projected_mixed(int n_images, int judged, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                                          const jpeg_amd_view *h_views, int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec,
-                                          bool tensor, void *d_dst, size_t dst_stride, const float *h_view_matrices,
-                                          const jpeg_amd_warp *warp, const jpeg_amd_colour *colour)
-{
-    ResampleTarget t{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, nullptr, d_dst, dst_stride, nullptr, nullptr, nullptr,
-                     h_view_matrices, warp, true, colour, true};
-    ResizePlan plan;
-    std::vector<MixedPlan> plans;
-    return judge_resized_mixed(n_images, judged, h_images, cosited, color, h_views, t, &plan, &plans);
 }
 
 int jpeg_amd_decode_view_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
@@ -1059,7 +1037,7 @@ int jpeg_amd_decode_resized_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layou
                                          int32_t out_w, int32_t out_h, int filter, uint8_t *d_pixels, size_t pixel_stride)
 try {
     return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color, d_pixels, 0},
-                            h_views, ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride});
+                            h_views, ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride).through(filter));
 }
 JA_NOTHROW_TAIL
 
@@ -1072,7 +1050,7 @@ int jpeg_amd_decode_tensor_filter_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout
 try {
     return decode_resampled(ctx, DecodeCall{L, n_images, d_coef, coef_stride, d_quanta, quanta_stride, ntables, cosited, color,
                                             static_cast<uint8_t *>(d_dst), 0},
-                            h_views, ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride});
+                            h_views, ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride).through(filter));
 }
 JA_NOTHROW_TAIL
 
@@ -1176,7 +1154,8 @@ int jpeg_amd_resize_placed_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t 
                                  uint8_t *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_dst, dst_stride, h_orient, place, h_windows_out});
+                         ResampleRequest::bytes(out_w, out_h, d_dst, dst_stride)
+                             .through(filter).oriented(h_orient).placed(place, h_windows_out));
 }
 JA_NOTHROW_TAIL
 
@@ -1187,7 +1166,8 @@ int jpeg_amd_resize_placed_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const u
                                         size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out});
+                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                             .through(filter).oriented(h_orient).placed(place, h_windows_out));
 }
 JA_NOTHROW_TAIL
 
@@ -1196,8 +1176,9 @@ int jpeg_amd_decode_resized_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const 
                                          int filter, const uint8_t *h_orient, const jpeg_amd_placement *place,
                                          jpeg_amd_region *h_windows_out, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, false, nullptr, nullptr, d_pixels, pixel_stride, h_orient, place, h_windows_out});
+    return decode_views_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                              ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                                  .through(filter).oriented(h_orient).placed(place, h_windows_out));
 }
 JA_NOTHROW_TAIL
 
@@ -1207,12 +1188,35 @@ int jpeg_amd_decode_tensor_placed_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         const uint8_t *h_orient, const jpeg_amd_placement *place,
                                         jpeg_amd_region *h_windows_out, void *d_dst, size_t dst_stride)
 try {
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out});
+    return decode_views_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                              ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                  .through(filter).oriented(h_orient).placed(place, h_windows_out));
 }
 JA_NOTHROW_TAIL
 
 // ---- "warped resample" ----
+namespace {
+
+// What jpeg_amd_warp_view and jpeg_amd_project_view share.  The denominator of a map whose shorter Jacobian column has the
+// squared length step2: the largest d of 8, 4, 2 with d * d <= step2, else 1.
+int map_denom(double step2)
+{
+    for (int d = 8; d > 1; d /= 2)
+        if ((double)(d * d) <= step2) return d;
+    return 1;
+}
+
+// The rectangle of the scaled image S that holds the taps of a canvas whose footprint spans lo[a] .. hi[a] on axis a, clamped.
+jpeg_amd_region footprint_view(const double lo[2], const double hi[2], const jpeg_amd_layout &S)
+{
+    const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
+    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
+    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
+    return jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1};
+}
+
+}  // namespace
+
 int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const float m[6], int32_t out_w, int32_t out_h,
                        jpeg_amd_view *view, float m_view[6])
 {
@@ -1233,9 +1237,7 @@ int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const flo
     // 2. the denominator
     const double m00 = m[0], m01 = m[1], m10 = m[3], m11 = m[4];
     const double step2 = std::min(m00 * m00 + m10 * m10, m01 * m01 + m11 * m11);
-    int denom = 1;
-    for (int d = 8; d > 1; d /= 2)
-        if ((double)(d * d) <= step2) { denom = d; break; }
+    const int denom = map_denom(step2);
     // 3. against the scaled image
     jpeg_amd_layout S;
     JA_TRY(jpeg_amd_scaled_layout(layout, denom, &S));
@@ -1251,13 +1253,11 @@ int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const flo
             hi[a] = c == 0 ? v : std::max(hi[a], v);
         }
     }
-    const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
-    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
-    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
-    *view = jpeg_amd_view{denom, jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1}};
+    const jpeg_amd_region r = footprint_view(lo, hi, S);
+    *view = jpeg_amd_view{denom, r};
     // 5. against the view
-    s[2] = s[2] - (double)x0;
-    s[5] = s[5] - (double)y0;
+    s[2] = s[2] - (double)r.x;
+    s[5] = s[5] - (double)r.y;
     for (int k = 0; k < 6; ++k) m_view[k] = (float)s[k];
     return JPEG_AMD_OK;
 }
@@ -1267,8 +1267,7 @@ int jpeg_amd_warp_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, s
                         int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_matrices, warp, true});
+                         ResampleRequest::bytes(out_w, out_h, d_dst, dst_stride).mapped(ResampleMap::Affine, h_matrices, warp));
 }
 JA_NOTHROW_TAIL
 
@@ -1278,44 +1277,34 @@ int jpeg_amd_warp_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d
                                void *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_matrices, warp, true});
+                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                             .mapped(ResampleMap::Affine, h_matrices, warp));
 }
 JA_NOTHROW_TAIL
 
-int jpeg_amd::capi::decode_warped_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
-                                              jpeg_amd_color color, const jpeg_amd_view *h_views, const float *h_view_matrices,
-                                              const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
-                                              const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
-                                              const jpeg_amd_colour *colour)
-{
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_view_matrices, warp, true, colour});
-}
-
 namespace {
 
-// jpeg_amd_decode_warped_mixed and its tensor form: every image's view and m_view from jpeg_amd_warp_view, then the route of
-// the resized mixed calls with warp records.
-int warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                 const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
-                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out, float *h_matrices_out, void *d_dst,
-                 size_t dst_stride, const jpeg_amd_colour *colour = nullptr)
+// The mixed calls through a map (jpeg_amd_decode_warped_mixed, jpeg_amd_decode_projected_mixed, their tensor forms): rq carries
+// the caller's matrices against the upright images and the orientations; every image's view and m_view from jpeg_amd_warp_view
+// or jpeg_amd_project_view, which take the orientation into the matrix, then the route of the mixed calls with those.
+int mapped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
+                 const ResampleRequest &rq, jpeg_amd_view *h_views_out, float *h_matrices_out)
 {
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    if (n_images > 0 && (!h_images || !h_matrices)) return JPEG_AMD_EINVAL;
-    const size_t n = (size_t)n_images;
+    if (n_images > 0 && (!h_images || !rq.h_matrices)) return JPEG_AMD_EINVAL;
+    const size_t n = (size_t)n_images, k = rq.matrix_floats();
+    const auto view_of = rq.map == ResampleMap::Projective ? jpeg_amd_project_view : jpeg_amd_warp_view;
     std::vector<jpeg_amd_view> views(n);
-    std::vector<float> view_matrices(6 * n);
+    std::vector<float> view_matrices(k * n);
     for (size_t i = 0; i < n; ++i) {
-        JA_TRY(jpeg_amd_warp_view(&h_images[i].layout, h_orient ? h_orient[i] : 1, h_matrices + 6 * i, out_w, out_h, &views[i],
-                                  &view_matrices[6 * i]));
+        JA_TRY(view_of(&h_images[i].layout, rq.h_orient ? rq.h_orient[i] : 1, rq.h_matrices + k * i, rq.out_w, rq.out_h, &views[i],
+                       &view_matrices[k * i]));
         if (h_views_out) h_views_out[i] = views[i];
-        if (h_matrices_out) std::memcpy(h_matrices_out + 6 * i, &view_matrices[6 * i], 6 * sizeof(float));
+        if (h_matrices_out) std::memcpy(h_matrices_out + k * i, &view_matrices[k * i], k * sizeof(float));
     }
-    return decode_warped_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), view_matrices.data(), warp, out_w, out_h, tensor,
-                                     spec, h_flip, d_dst, dst_stride, colour);
+    ResampleRequest behind = rq;
+    behind.oriented(nullptr).mapped(rq.map, view_matrices.data(), rq.warp);
+    return decode_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), behind);
 }
 
 }  // namespace
@@ -1325,8 +1314,10 @@ int jpeg_amd_decode_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd
                                  const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
                                  float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, false, nullptr, nullptr,
-                        h_views_out, h_matrices_out, d_pixels, pixel_stride);
+    return mapped_mixed(ctx, n_images, h_images, cosited, color,
+                        ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                            .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp),
+                        h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL
 
@@ -1336,8 +1327,10 @@ int jpeg_amd_decode_tensor_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
                                         float *h_matrices_out, void *d_dst, size_t dst_stride)
 try {
-    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
-                        h_views_out, h_matrices_out, d_dst, dst_stride);
+    return mapped_mixed(ctx, n_images, h_images, cosited, color,
+                        ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                            .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp),
+                        h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL
 
@@ -1350,12 +1343,9 @@ int jpeg_amd_resize_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const u
                                         const jpeg_amd_placement *place, jpeg_amd_region *h_windows_out,
                                         const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
-    if (!colour)
-        return jpeg_amd_resize_placed_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, out_w, out_h, filter, spec, h_flip, h_orient,
-                                                   place, h_windows_out, d_dst, dst_stride);
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out, nullptr,
-                                        nullptr, false, colour});
+                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                             .through(filter).oriented(h_orient).placed(place, h_windows_out).coloured(colour));
 }
 JA_NOTHROW_TAIL
 
@@ -1366,12 +1356,9 @@ int jpeg_amd_decode_tensor_colour_mixed(jpeg_amd_ctx *ctx, int n_images, const j
                                         jpeg_amd_region *h_windows_out, const jpeg_amd_colour *colour, void *d_dst,
                                         size_t dst_stride)
 try {
-    if (!colour)
-        return jpeg_amd_decode_tensor_placed_mixed(ctx, n_images, h_images, cosited, color, h_views, out_w, out_h, filter, spec, h_flip,
-                                                   h_orient, place, h_windows_out, d_dst, dst_stride);
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, filter, true, spec, h_flip, d_dst, dst_stride, h_orient, place, h_windows_out, nullptr,
-                                        nullptr, false, colour});
+    return decode_views_mixed(ctx, n_images, h_images, cosited, color, h_views,
+                              ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                                  .through(filter).oriented(h_orient).placed(place, h_windows_out).coloured(colour));
 }
 JA_NOTHROW_TAIL
 
@@ -1380,12 +1367,9 @@ int jpeg_amd_warp_colour_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uin
                                       int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
                                       const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
-    if (!colour)
-        return jpeg_amd_warp_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, h_matrices, warp, out_w, out_h, spec, h_flip, d_dst,
-                                          dst_stride);
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_matrices, warp, true, colour});
+                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                             .mapped(ResampleMap::Affine, h_matrices, warp).coloured(colour));
 }
 JA_NOTHROW_TAIL
 
@@ -1395,11 +1379,10 @@ int jpeg_amd_decode_tensor_warped_colour_mixed(jpeg_amd_ctx *ctx, int n_images, 
                                                const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
                                                float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
-    if (!colour)
-        return jpeg_amd_decode_tensor_warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, spec,
-                                                   h_flip, h_views_out, h_matrices_out, d_dst, dst_stride);
-    return warped_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
-                        h_views_out, h_matrices_out, d_dst, dst_stride, colour);
+    return mapped_mixed(ctx, n_images, h_images, cosited, color,
+                        ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                            .oriented(h_orient).mapped(ResampleMap::Affine, h_matrices, warp).coloured(colour),
+                        h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL
 
@@ -1437,9 +1420,7 @@ int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const 
             step2 = p == 0 && c == 0 ? n2 : std::min(step2, n2);
         }
     }
-    int denom = 1;
-    for (int d = 8; d > 1; d /= 2)
-        if ((double)(d * d) <= step2) { denom = d; break; }
+    const int denom = map_denom(step2);
     // 3. against the scaled image: the numerators' rows times 1 / d
     jpeg_amd_layout S;
     JA_TRY(jpeg_amd_scaled_layout(layout, denom, &S));
@@ -1456,18 +1437,16 @@ int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const 
             hi[a] = c == 0 ? v : std::max(hi[a], v);
         }
     }
-    const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
-    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
-    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
+    const jpeg_amd_region r = footprint_view(lo, hi, S);
     // 5. against the view: the view's origin times the denominator's row off the numerators' rows
     float mv[9];
     for (int k = 0; k < 3; ++k) {
-        mv[k] = (float)(s[k] - (double)x0 * s[6 + k]);
-        mv[3 + k] = (float)(s[3 + k] - (double)y0 * s[6 + k]);
+        mv[k] = (float)(s[k] - (double)r.x * s[6 + k]);
+        mv[3 + k] = (float)(s[3 + k] - (double)r.y * s[6 + k]);
         mv[6 + k] = m[6 + k];
     }
     JA_TRY(check_project_matrix(mv, out_w, out_h));   // (an entry past 2^30 behind the subtraction)
-    *view = jpeg_amd_view{denom, jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1}};
+    *view = jpeg_amd_view{denom, r};
     std::memcpy(m_view, mv, sizeof mv);
     return JPEG_AMD_OK;
 }
@@ -1477,8 +1456,7 @@ int jpeg_amd_project_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src
                            int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, false, nullptr, nullptr, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_matrices, warp, true, nullptr, true});
+                         ResampleRequest::bytes(out_w, out_h, d_dst, dst_stride).mapped(ResampleMap::Projective, h_matrices, warp));
 }
 JA_NOTHROW_TAIL
 
@@ -1488,55 +1466,20 @@ int jpeg_amd_project_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t
                                   const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, true, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_matrices, warp, true, colour, true});
+                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                             .mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour));
 }
 JA_NOTHROW_TAIL
-
-int jpeg_amd::capi::decode_projected_views_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
-                                                 jpeg_amd_color color, const jpeg_amd_view *h_views, const float *h_view_matrices,
-                                                 const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, bool tensor,
-                                                 const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, void *d_dst, size_t dst_stride,
-                                                 const jpeg_amd_colour *colour)
-{
-    return resized_mixed(ctx, n_images, h_images, cosited, color, h_views,
-                         ResampleTarget{out_w, out_h, JPEG_AMD_FILTER_BILINEAR, tensor, spec, h_flip, d_dst, dst_stride, nullptr, nullptr,
-                                        nullptr, h_view_matrices, warp, true, colour, true});
-}
-
-namespace {
-
-// jpeg_amd_decode_projected_mixed and its tensor form: every image's view and m_view from jpeg_amd_project_view, then the
-// route of the resized mixed calls with project records.
-int projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
-                    const uint8_t *h_orient, const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
-                    bool tensor, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
-                    float *h_matrices_out, void *d_dst, size_t dst_stride, const jpeg_amd_colour *colour)
-{
-    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
-    if (n_images > 0 && (!h_images || !h_matrices)) return JPEG_AMD_EINVAL;
-    const size_t n = (size_t)n_images;
-    std::vector<jpeg_amd_view> views(n);
-    std::vector<float> view_matrices(9 * n);
-    for (size_t i = 0; i < n; ++i) {
-        JA_TRY(jpeg_amd_project_view(&h_images[i].layout, h_orient ? h_orient[i] : 1, h_matrices + 9 * i, out_w, out_h, &views[i],
-                                     &view_matrices[9 * i]));
-        if (h_views_out) h_views_out[i] = views[i];
-        if (h_matrices_out) std::memcpy(h_matrices_out + 9 * i, &view_matrices[9 * i], 9 * sizeof(float));
-    }
-    return decode_projected_views_mixed(ctx, n_images, h_images, cosited, color, views.data(), view_matrices.data(), warp, out_w, out_h,
-                                        tensor, spec, h_flip, d_dst, dst_stride, colour);
-}
-
-}  // namespace
 
 int jpeg_amd_decode_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
                                     jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
                                     const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
                                     float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
 try {
-    return projected_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, false, nullptr, nullptr,
-                           h_views_out, h_matrices_out, d_pixels, pixel_stride, nullptr);
+    return mapped_mixed(ctx, n_images, h_images, cosited, color,
+                        ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
+                            .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
+                        h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL
 
@@ -1546,7 +1489,9 @@ int jpeg_amd_decode_tensor_projected_mixed(jpeg_amd_ctx *ctx, int n_images, cons
                                            const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
                                            float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
-    return projected_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, out_w, out_h, true, spec, h_flip,
-                           h_views_out, h_matrices_out, d_dst, dst_stride, colour);
+    return mapped_mixed(ctx, n_images, h_images, cosited, color,
+                        ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
+                            .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
+                        h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL

@@ -324,13 +324,15 @@ def test_a_null_colour_is_the_named_call(files):
 
 
 def test_a_colour_forced_through_a_byte_target_is_refused(tmp_path):
-    """tests/cpp/colour_byte_target_test.cpp lists the assertions: check_resampled_mixed and decode_warped_views_mixed with a
-    valid colour and tensor = false give EINVAL, for no images and for two; without the colour, or with tensor = true, the
-    same arguments are judged to the end (OK, and ENOSUP past the tap limit)."""
+    """tests/cpp/colour_byte_target_test.cpp lists the assertions: check_resampled_mixed and decode_views_mixed with a request
+    (csrc/resample_request.hpp) of a valid colour and a byte target give EINVAL, for no images and for two, without a map and
+    through either map; without the colour, or to a tensor, the same request is judged to the end (OK, and ENOSUP past the
+    tap limit)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "colour_byte_target_test")
     libdir = os.path.join(root, "jpeg_amd")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(root, "include"),
+                           "-I", os.path.join(root, "jpeg_amd", "csrc"),
                            os.path.join(root, "tests", "cpp", "colour_byte_target_test.cpp"), "-o", exe,
                            "-L", libdir, "-ljpeg_amd", "-Wl,-rpath," + libdir])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)

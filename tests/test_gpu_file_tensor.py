@@ -378,3 +378,48 @@ def test_python_api(ctx, torch, files, tmp_path):
         J.decompress_resized(ctx, sources[:2], OUT, source_regions=[regions[0], (0, 0, 500, 500)])
     with pytest.raises(ValueError):
         J.decompress_resized(ctx, sources[:2], OUT, source_regions=regions[:1])
+
+
+# ---- a call of two chunks carries every per-file array into its second chunk ---------------------------------------------------
+
+@pytest.fixture(scope="module")
+def files_33():
+    """33 small files, one more than a chunk holds: 4:2:0 and grey in turn, none larger than 48 x 32."""
+    sizes = [(48, 32), (31, 17), (16, 16), (9, 29), (40, 8)]
+    return [F.synthetic_file("420" if i % 2 else "y8", sizes[i % len(sizes)], 900 + i)[0].tobytes() for i in range(33)]
+
+
+@pytest.mark.parametrize("case", ["placed", "warped"])
+def test_a_call_of_two_chunks_is_its_chunks_side_by_side(ctx, torch, files_33, case):
+    """Orientations 1 .. 8 in turn, flips on the odd files and a colour per file, with (placed) a fitted window, the antialiasing
+    filter and a float16 CHW tensor, or (warped) an affine map per file: the call on all 33 files is, bit for bit and in every
+    per-file result it returns, the call on files [0, 32) and the call on file 32 alone."""
+    n = len(files_33)
+    rng = np.random.Generator(np.random.PCG64(33))
+    colour = np.tile(np.eye(3, 4, dtype=np.float32), (n, 1, 1)) + rng.uniform(-0.2, 0.2, (n, 3, 4)).astype(np.float32)
+    colour[:, :, 3] = rng.uniform(-20, 20, (n, 3))
+    orient = [1 + i % 8 for i in range(n)]
+    flips = [i % 2 for i in range(n)]
+    if case == "placed":
+        spec = spec_of("f16-chw")
+        kw = dict(filter="antialias", place="fit", fill=(9, 8, 7))
+    else:
+        spec = spec_of("f32-hwc")
+        angle = rng.uniform(-0.5, 0.5, n)
+        zoom = rng.uniform(0.8, 1.6, n)
+        warp = np.stack([zoom * np.cos(angle), -zoom * np.sin(angle), rng.uniform(-3, 3, n),
+                         zoom * np.sin(angle), zoom * np.cos(angle), rng.uniform(-3, 3, n)], axis=1).astype(np.float32)
+        kw = dict(edge="replicate")
+
+    def call(lo, hi):
+        more = dict(kw, warp=warp[lo:hi]) if case == "warped" else kw
+        got = J.decompress_tensors(ctx, files_33[lo:hi], OUT, spec, flips=flips[lo:hi], orientation=orient[lo:hi],
+                                   colour=colour[lo:hi], colour_clamp=(0.0, 255.0), threads=2, **more)
+        tensor, views, infos, applied, last = got                       # (last: the windows, or the matrices applied)
+        return tensor.contiguous().view(hi - lo, -1).view(torch.uint8).cpu().numpy(), views, applied, np.asarray(last)
+
+    whole, head, tail = call(0, n), call(0, 32), call(32, n)
+    for w, h, t in zip(whole, head, tail):
+        assert w.shape[0] == n and (w == np.concatenate([h, t])).all()
+    assert whole[2].tolist() == orient
+    assert len({tuple(v) for v in whole[1].tolist()}) > 1 and whole[0].any()

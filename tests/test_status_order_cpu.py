@@ -7,13 +7,19 @@ the argument handling of the C layer (jpeg_amd/csrc/capi*.hip) was gathered into
 checks shows here.  The six resample calls are there twice, without a filter argument and as their *_filter_* forms with the
 bilinear filter: the first forward to the second.  A second table holds calls that are wrong twice, in the view (ENOSUP) and
 in the target (EINVAL), and calls with an unknown filter: there the order between the checks shows, and what an empty call
-answers without a context."""
+answers without a context.  The oriented, placed, warped, colour and projected forms and the file calls
+(jpeg_amd_decompress_*_mixed, on one small in-memory file) stand in both tables as well; the second table holds them with a
+per-image argument that is wrong (an orientation of 9, an unknown placement mode, a non-finite matrix, a homography whose
+denominator changes sign on the canvas, a colour with lo > hi) next to a bad target, and again on a 12-bit image: the order
+between the image, the per-image argument and the target shows there."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from _calls import c_layout
+from _files import synthetic_file
 from jpeg_amd import _lib
 
 OK, EINVAL, ENOSUP = 0, -1, -5                                     # JPEG_AMD_OK, _EINVAL, _ENOSUP, as literals
@@ -40,12 +46,37 @@ class Args:
         self.region = _lib.Region(0, 0, 0 if bad else 4, 4)
         self.view = _lib.View(self.denom, _lib.Region(0, 0, 4, 4))
         self.extent = _lib.Extent(4, 4)
+        self.out = (8, 8)                                          # the canvas of the later forms
         self.r, self.v, self.e = C.byref(self.region), C.byref(self.view), C.byref(self.extent)
         self.spec = _lib.TensorSpec(_lib.F32, _lib.TENSOR_HWC, (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1))
         self.s = C.byref(self.spec)
         # the mixed calls: the layout lies inside the image, so "null layout" is a null image array there
         self.image = image(self.layout, self.p)
         self.im = None if case == "null layout" else C.byref(self.image)
+        # the per-image arguments of the later forms, all valid: an orientation, a placement, a warp with an affine and a
+        # projective matrix, a colour
+        self.orient = np.array([6], np.uint8)
+        self.o = self.orient.ctypes.data
+        self.placement = _lib.Placement(_lib.PLACE_FIT, _lib.ANCHOR_CENTRE, None, (C.c_uint8 * 3)(1, 2, 3), 0)
+        self.pl = C.byref(self.placement)
+        self.warp = _lib.Warp(_lib.EDGE_FILL, (C.c_uint8 * 3)(1, 2, 3))
+        self.w = C.byref(self.warp)
+        self.matrix6 = np.array([0.5, 0, 0, 0, 0.5, 0], np.float32)
+        self.matrix9 = np.array([0.5, 0, 0, 0, 0.5, 0, 0, 0, 1], np.float32)
+        self.m6, self.m9 = self.matrix6.ctypes.data, self.matrix9.ctypes.data
+        self.colour_matrix = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
+        self.colour = _lib.Colour(self.colour_matrix.ctypes.data, 0.0, 255.0)
+        self.c = C.byref(self.colour)
+        # the file calls: one file of 16 x 16, 4:2:0 ("null layout": no file array)
+        self.file = small_file()
+        self.jpeg = (C.c_void_p * 1)(self.file.ctypes.data)
+        self.nbytes = (C.c_size_t * 1)(self.file.size)
+        self.jp = None if case == "null layout" else self.jpeg
+
+
+@functools.lru_cache(maxsize=None)
+def small_file():
+    return synthetic_file("420", (16, 16), 1)[0]
 
 
 def image(layout, p):
@@ -56,6 +87,11 @@ def image(layout, p):
         im.d_coef[c] = p
     im.d_quanta, im.ntables = p, 2
     return im
+
+
+def files(a):
+    """The leading arguments of a file call behind the context."""
+    return a.jp, a.nbytes, a.n, 1, 0, RGB
 
 
 RGB = _lib.COLOR_RGB8
@@ -88,6 +124,52 @@ CALLS = {
         lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 8, 8, BILINEAR, a.s, None, a.p, 192),
     "jpeg_amd_decode_resized_filter_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, BILINEAR, a.p, 768),
     "jpeg_amd_decode_tensor_filter_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, 8, 8, BILINEAR, a.s, None, a.p, 192),
+    # ... with an orientation per image, a placement, an affine map, a colour and a homography
+    "jpeg_amd_resize_oriented_batch": lambda a: (a.n, a.p, 48, a.e, *a.out, BILINEAR, a.o, a.p, 192),
+    "jpeg_amd_resize_oriented_tensor_batch": lambda a: (a.n, a.p, 48, a.e, *a.out, BILINEAR, a.s, None, a.o, a.p, 192),
+    "jpeg_amd_decode_resized_oriented_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, *a.out, BILINEAR, a.o, a.p, 768),
+    "jpeg_amd_decode_tensor_oriented_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, *a.out, BILINEAR, a.s, None, a.o, a.p, 192),
+    "jpeg_amd_resize_placed_batch": lambda a: (a.n, a.p, 48, a.e, *a.out, BILINEAR, a.o, a.pl, None, a.p, 192),
+    "jpeg_amd_resize_placed_tensor_batch": lambda a: (a.n, a.p, 48, a.e, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.p, 192),
+    "jpeg_amd_decode_resized_placed_mixed": lambda a: (a.n, a.im, 0, RGB, a.v, *a.out, BILINEAR, a.o, a.pl, None, a.p, 768),
+    "jpeg_amd_decode_tensor_placed_mixed":
+        lambda a: (a.n, a.im, 0, RGB, a.v, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.p, 192),
+    "jpeg_amd_warp_batch": lambda a: (a.n, a.p, 48, a.e, a.m6, a.w, *a.out, a.p, 192),
+    "jpeg_amd_warp_tensor_batch": lambda a: (a.n, a.p, 48, a.e, a.m6, a.w, *a.out, a.s, None, a.p, 192),
+    "jpeg_amd_decode_warped_mixed": lambda a: (a.n, a.im, 0, RGB, a.o, a.m6, a.w, *a.out, None, None, a.p, 768),
+    "jpeg_amd_decode_tensor_warped_mixed": lambda a: (a.n, a.im, 0, RGB, a.o, a.m6, a.w, *a.out, a.s, None, None, None, a.p, 192),
+    "jpeg_amd_resize_colour_tensor_batch":
+        lambda a: (a.n, a.p, 48, a.e, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.c, a.p, 192),
+    "jpeg_amd_decode_tensor_colour_mixed":
+        lambda a: (a.n, a.im, 0, RGB, a.v, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.c, a.p, 192),
+    "jpeg_amd_warp_colour_tensor_batch": lambda a: (a.n, a.p, 48, a.e, a.m6, a.w, *a.out, a.s, None, a.c, a.p, 192),
+    "jpeg_amd_decode_tensor_warped_colour_mixed":
+        lambda a: (a.n, a.im, 0, RGB, a.o, a.m6, a.w, *a.out, a.s, None, None, None, a.c, a.p, 192),
+    "jpeg_amd_project_batch": lambda a: (a.n, a.p, 48, a.e, a.m9, a.w, *a.out, a.p, 192),
+    "jpeg_amd_project_tensor_batch": lambda a: (a.n, a.p, 48, a.e, a.m9, a.w, *a.out, a.s, None, a.c, a.p, 192),
+    "jpeg_amd_decode_projected_mixed": lambda a: (a.n, a.im, 0, RGB, a.o, a.m9, a.w, *a.out, None, None, a.p, 768),
+    "jpeg_amd_decode_tensor_projected_mixed":
+        lambda a: (a.n, a.im, 0, RGB, a.o, a.m9, a.w, *a.out, a.s, None, None, None, a.c, a.p, 192),
+    # the file calls: (files, sizes, n, one thread, centred, RGB), then the call's own; "empty region": the source rectangle's
+    "jpeg_amd_decompress_tensor_mixed": lambda a: (*files(a), a.r, *a.out, BILINEAR, a.s, None, a.p, 192, None, None),
+    "jpeg_amd_decompress_resized_mixed": lambda a: (*files(a), a.r, *a.out, BILINEAR, a.p, 192, None, None),
+    "jpeg_amd_decompress_tensor_oriented_mixed":
+        lambda a: (*files(a), a.r, *a.out, BILINEAR, a.s, None, a.o, a.p, 192, None, None, None),
+    "jpeg_amd_decompress_resized_oriented_mixed": lambda a: (*files(a), a.r, *a.out, BILINEAR, a.o, a.p, 192, None, None, None),
+    "jpeg_amd_decompress_tensor_placed_mixed":
+        lambda a: (*files(a), a.r, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.p, 192, None, None, None),
+    "jpeg_amd_decompress_resized_placed_mixed":
+        lambda a: (*files(a), a.r, *a.out, BILINEAR, a.o, a.pl, None, a.p, 192, None, None, None),
+    "jpeg_amd_decompress_resized_warped_mixed": lambda a: (*files(a), a.o, a.m6, a.w, *a.out, a.p, 192, None, None, None, None),
+    "jpeg_amd_decompress_tensor_warped_mixed":
+        lambda a: (*files(a), a.o, a.m6, a.w, *a.out, a.s, None, a.p, 192, None, None, None, None),
+    "jpeg_amd_decompress_tensor_colour_mixed":
+        lambda a: (*files(a), a.r, *a.out, BILINEAR, a.s, None, a.o, a.pl, None, a.c, a.p, 192, None, None, None),
+    "jpeg_amd_decompress_tensor_warped_colour_mixed":
+        lambda a: (*files(a), a.o, a.m6, a.w, *a.out, a.s, None, a.c, a.p, 192, None, None, None, None),
+    "jpeg_amd_decompress_resized_projected_mixed": lambda a: (*files(a), a.o, a.m9, a.w, *a.out, a.p, 192, None, None, None, None),
+    "jpeg_amd_decompress_tensor_projected_mixed":
+        lambda a: (*files(a), a.o, a.m9, a.w, *a.out, a.s, None, a.c, a.p, 192, None, None, None, None),
     "jpeg_amd_encode_batch": lambda a: (a.L, a.n, a.p, 768, RGB, a.p, 64, 2, a.pp, a.sz),
     "jpeg_amd_encode": lambda a: (a.L, a.p, RGB, a.p, 2, a.pp),
     "jpeg_amd_spectral_rectangular_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, 2, 0, a.p, 768),
@@ -139,6 +221,38 @@ EXPECTED = {
     "jpeg_amd_decode_tensor_filter_batch": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_decode_resized_filter_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
     "jpeg_amd_decode_tensor_filter_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_resize_oriented_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_resize_oriented_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_resized_oriented_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor_oriented_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_resize_placed_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_resize_placed_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_resized_placed_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_decode_tensor_placed_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_warp_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_warp_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_warped_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, _),
+    "jpeg_amd_decode_tensor_warped_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, _),
+    "jpeg_amd_resize_colour_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_tensor_colour_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, EINVAL),
+    "jpeg_amd_warp_colour_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_tensor_warped_colour_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, _),
+    "jpeg_amd_project_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_project_tensor_batch": (EINVAL, _, _, _, EINVAL, _),
+    "jpeg_amd_decode_projected_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, _),
+    "jpeg_amd_decode_tensor_projected_mixed": (EINVAL, EINVAL, ENOSUP, EINVAL, EINVAL, _),
+    "jpeg_amd_decompress_tensor_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_resized_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_tensor_oriented_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_resized_oriented_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_tensor_placed_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_resized_placed_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_resized_warped_mixed": (EINVAL, EINVAL, _, _, EINVAL, _),
+    "jpeg_amd_decompress_tensor_warped_mixed": (EINVAL, EINVAL, _, _, EINVAL, _),
+    "jpeg_amd_decompress_tensor_colour_mixed": (EINVAL, EINVAL, _, _, EINVAL, EINVAL),
+    "jpeg_amd_decompress_tensor_warped_colour_mixed": (EINVAL, EINVAL, _, _, EINVAL, _),
+    "jpeg_amd_decompress_resized_projected_mixed": (EINVAL, EINVAL, _, _, EINVAL, _),
+    "jpeg_amd_decompress_tensor_projected_mixed": (EINVAL, EINVAL, _, _, EINVAL, _),
     "jpeg_amd_encode_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
     "jpeg_amd_encode": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
     "jpeg_amd_spectral_rectangular_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
@@ -201,9 +315,77 @@ def call(name, case, args):
     return getattr(_lib.lib(), name)(None, *args(a))
 
 
+def orientation_9(a):
+    a.orient[0] = 9
+
+
+def unknown_placement_mode(a):
+    a.placement.mode = 7
+
+
+def non_finite_matrix(a):
+    a.matrix6[1] = np.inf
+
+
+def denominator_changes_sign(a):
+    a.matrix9[7] = -1.0                                            # 1 - cy: positive on the canvas's top edge, negative on its bottom
+
+
+def colour_lo_above_hi(a):
+    a.colour.lo = 300.0
+
+
+def wrong_with_bad_target(name, spoil, case="valid"):
+    """`name` with its per-image argument spoilt and a canvas of 0 x 8, on the image of `case`."""
+    a = Args(case)
+    a.out = (0, 8)
+    spoil(a)
+    return getattr(_lib.lib(), name)(None, *CALLS[name](a))
+
+
+# What is spoilt -> the calls that take it: over bytes in memory, over mixed images (those again on a 12-bit image), over files.
+SPOILT = {
+    "an orientation of 9":
+        (orientation_9, "jpeg_amd_resize_oriented_tensor_batch", "jpeg_amd_decode_tensor_oriented_mixed",
+         "jpeg_amd_decompress_tensor_oriented_mixed"),
+    "an unknown placement mode":
+        (unknown_placement_mode, "jpeg_amd_resize_placed_tensor_batch", "jpeg_amd_decode_tensor_placed_mixed",
+         "jpeg_amd_decompress_tensor_placed_mixed"),
+    "a non-finite warp matrix":
+        (non_finite_matrix, "jpeg_amd_warp_tensor_batch", "jpeg_amd_decode_tensor_warped_mixed",
+         "jpeg_amd_decompress_tensor_warped_mixed"),
+    "a denominator that changes sign":
+        (denominator_changes_sign, "jpeg_amd_project_tensor_batch", "jpeg_amd_decode_tensor_projected_mixed",
+         "jpeg_amd_decompress_tensor_projected_mixed"),
+    "a colour with lo > hi":
+        (colour_lo_above_hi, "jpeg_amd_resize_colour_tensor_batch", "jpeg_amd_decode_tensor_colour_mixed",
+         "jpeg_amd_decompress_tensor_colour_mixed"),
+}
+# ... and the statuses of the library before the change: (bytes, mixed, files, mixed on a 12-bit image)
+SPOILT_EXPECTED = {
+    "an orientation of 9": (EINVAL, EINVAL, EINVAL, ENOSUP),
+    "an unknown placement mode": (EINVAL, EINVAL, EINVAL, ENOSUP),
+    "a non-finite warp matrix": (EINVAL, EINVAL, EINVAL, EINVAL),
+    "a denominator that changes sign": (EINVAL, EINVAL, EINVAL, EINVAL),
+    "a colour with lo > hi": (EINVAL, EINVAL, EINVAL, ENOSUP),
+}
+
+
+def spoilt_rows():
+    rows = {}
+    for what, (spoil, in_memory, mixed, of_files) in SPOILT.items():
+        want = SPOILT_EXPECTED[what]
+        for name, case, status in ((in_memory, "valid", want[0]), (mixed, "valid", want[1]), (of_files, "valid", want[2]),
+                                   (mixed, T12, want[3])):
+            title = f"{name[len('jpeg_amd_'):]}, {what} and out_w = 0" + (", 12 bits" if case == T12 else "")
+            rows[title] = (lambda name=name, spoil=spoil, case=case: wrong_with_bad_target(name, spoil, case), status)
+    return rows
+
+
 # Calls that are wrong twice, and empty calls: description -> (the call, the status of the library before the change).
 T12 = "12-bit layout"
 TWICE = {
+    **spoilt_rows(),
     "resized batch, 12 bits and out_w = 0":
         (lambda: call("jpeg_amd_decode_resized_batch", T12, lambda a: (a.L, 1, a.pp, a.sz, a.p, 64, 2, 0, RGB, a.v, 0, 8, a.p, 768)), ENOSUP),
     "tensor batch, 12 bits and out_w = 0":

@@ -18,7 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
 SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_tile.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
-HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "warp.hpp", "project.hpp", "resample_request.hpp"]
+HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "warp.hpp", "project.hpp", "resample_request.hpp", "resample_chunks.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
 # Per-source flags.  The transform kernels are compiled WITHOUT the SLP vectoriser: it turns the float arithmetic of the 8-point

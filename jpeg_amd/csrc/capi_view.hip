@@ -4,6 +4,7 @@
 
 #include "capi_internal.hpp"
 #include "orient.hpp"
+#include "resample_chunks.hpp"
 #include "tile_staging.hpp"
 
 using namespace jpeg_amd;
@@ -481,8 +482,6 @@ int jpeg_amd_view_denom(int32_t src_w, int32_t src_h, int32_t want_w, int32_t wa
 
 namespace {
 
-constexpr size_t kResizeChunkBytes = (size_t)1 << 30;   // decoded views per chunk of the resized and tensor decodes
-
 // The records into the context's record buffer, one copy from a host buffer (pageable, so the copy has taken it when the call
 // returns -- as stage_quanta).
 int upload_records(jpeg_amd_ctx *ctx, const std::vector<uint8_t> &rec)
@@ -653,9 +652,8 @@ struct ResampleTarget : ResampleRequest {
 };
 
 // The chunks of the resized and tensor decodes: consecutive images, m images at a stride of the chunk's largest view, at most
-// kResizeChunkBytes in all; rec holds image i's record inside its chunk (the target's kind of record); need: the bytes the
-// largest chunk takes; status: what the target's record() says of the first image it refuses.
-struct ResizeChunk { int i0, m; size_t stride; };
+// kResizeChunkBytes in all (resample_chunks.hpp holds the rule); rec holds image i's record inside its chunk (the target's kind
+// of record); need: the bytes the largest chunk takes; status: what the target's record() says of the first image it refuses.
 struct ResizePlan {
     std::vector<ResizeChunk> chunks;
     std::vector<uint8_t> rec;
@@ -667,23 +665,14 @@ ResizePlan plan_resize_chunks(int n_images, const jpeg_amd_view *h_views, const 
     ResizePlan plan;
     plan.rec.resize(t.upload_bytes(n_images));
     t.colour_records(plan.rec, n_images);
-    for (int i0 = 0; i0 < n_images;) {
-        int m = 0;
-        size_t stride = 0;
-        for (; i0 + m < n_images; ++m) {
-            const jpeg_amd_region &r = h_views[i0 + m].region;
-            const size_t s = std::max(stride, (size_t)3 * r.width * r.height);
-            if (m > 0 && s * ((size_t)m + 1) > kResizeChunkBytes) break;
-            stride = s;
-        }
-        for (int j = 0; j < m; ++j) {
-            const jpeg_amd_region &r = h_views[i0 + j].region;
-            const int verdict = t.record(plan.rec, i0 + j, i0 + j, (uint64_t)j * stride, r.width, r.height);
+    plan.chunks = split_resize_chunks(n_images, h_views);
+    for (const ResizeChunk &k : plan.chunks) {
+        for (int j = 0; j < k.m; ++j) {
+            const jpeg_amd_region &r = h_views[k.i0 + j].region;
+            const int verdict = t.record(plan.rec, k.i0 + j, k.i0 + j, (uint64_t)j * k.stride, r.width, r.height);
             if (plan.status == JPEG_AMD_OK) plan.status = verdict;
         }
-        plan.chunks.push_back(ResizeChunk{i0, m, stride});
-        plan.need = std::max(plan.need, stride * (size_t)m);
-        i0 += m;
+        plan.need = std::max(plan.need, k.stride * (size_t)k.m);
     }
     return plan;
 }

@@ -194,9 +194,11 @@ def spectrals(ctx):
 
 
 def test_decode_tensors_mixed_with_colour_is_the_view_decode_and_the_resample(ctx, torch, spectrals):
-    """One chunk: the chunk limit of the resized decodes is 2^30 bytes of decoded views and the code offers no smaller one to
-    tests, so a call of two chunks is out of reach at test size; launch()'s offsets for a second chunk are exercised by the
-    file route below, whose chunks of 32 files each make one mixed call with the call's matrices offset by the chunk's first file."""
+    """One chunk: the chunk limit of the resized decodes is 2^30 bytes of decoded views, and these views are far below it.
+    Calls of two and three chunks -- launch()'s offsets for a chunk that is not the first, the colour records' among them --
+    are test_gpu_resample_chunks.py's: the limit counts stride x images, so one large view and a hundred small ones cross it.
+    (The file route below does not reach them: each of its chunks of 32 files makes a mixed call of its own, whose per-image
+    arrays begin at the chunk's first file.)"""
     spec = J.tensor_spec(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), layout="chw")
     n = len(DECODE)
     views = [(2, 3, 5, 60, 50), (1, 10, 20, 100, 200), (4, 1, 1, 60, 30), (8, 0, 0, 17, 33), (2, 0, 0, 75, 45)]

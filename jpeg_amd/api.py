@@ -543,7 +543,7 @@ def orient_region(orientation: int, size, region=None) -> Tuple[int, int, int, i
 
 
 def _orientations(orientations, n: int, exif: bool = False):
-    """orientations=... of the resample calls -> the c bytes for h_orient, or None (today's entry point).  exif: the file
+    """orientations=... of the resample calls -> the c bytes for h_orient, or None (every image as it is stored).  exif: the file
     calls, where "exif" (the whole call, or an entry of a sequence) is JPEG_AMD_ORIENT_EXIF."""
     if orientations is None:
         return None
@@ -579,7 +579,7 @@ def place_window(mode, src_size, out_size, anchor="centre") -> Tuple[int, int, i
 
 def _placement(place, anchor, fill, n: int):
     """place=, anchor=, fill= of the resample calls -> (struct jpeg_amd_placement, room for the applied windows, keep), or
-    (None, None, None) for place=None (today's entry point).  place: "fit", "fit-down" or one (x, y, width, height) per image."""
+    (None, None, None) for place=None.  place: "fit", "fit-down" or one (x, y, width, height) per image."""
     if place is None:
         return None, None, None
     p = _lib.Placement()
@@ -605,10 +605,6 @@ def _placement(place, anchor, fill, n: int):
     return p, (_lib.Region * max(n, 1))(), keep
 
 
-def _windows_array(h_windows, n) -> np.ndarray:
-    return np.array([(r.x, r.y, r.width, r.height) for r in h_windows[:n]], np.int32).reshape(n, 4)
-
-
 _EDGES = {"fill": _lib.EDGE_FILL, "replicate": _lib.EDGE_REPLICATE}
 
 
@@ -628,12 +624,24 @@ def _warp(edge, fill) -> "_lib.Warp":
     return w
 
 
-def _matrices(matrices, n: int) -> np.ndarray:
-    """matrices= of the warp calls -> float32 [n, 6], contiguous."""
-    m = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, 6))
+def _matrices(matrices, n: int, k: int = 6) -> np.ndarray:
+    """matrices= of the warp calls (k = 6 numbers each) and of the project calls (k = 9) -> float32 [n, k], contiguous."""
+    m = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, k))
     if m.shape[0] != n:
-        raise ValueError("matrices: one (m00, m01, m02, m10, m11, m12) per image")
+        raise ValueError("matrices: one (m00, m01, m02, m10, m11, m12%s) per image" % (", m20, m21, m22" if k == 9 else ""))
     return m
+
+
+def _map_view(k: int, size, layout: "Layout", matrix, out_size, orientation: int):
+    """warp_view (k = 6) and project_view (k = 9)."""
+    name = "jpeg_amd_project_view" if k == 9 else "jpeg_amd_warp_view"
+    m = _matrices(matrix, 1, k)
+    v = _lib.View()
+    mv = np.zeros(k, np.float32)
+    L = layout.c_layout(size)
+    _lib.check(getattr(_lib.lib(), name)(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]), C.byref(v),
+                                         mv.ctypes.data), name)
+    return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
 
 
 def _cos_sin_degrees(angle: float) -> Tuple[float, float]:
@@ -676,27 +684,7 @@ def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
     """The view that a warp of an image of `size` (w, h) and `layout` reads, and the matrix against it (jpeg_amd_warp_view):
     `matrix` (6 values) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT image, the stored image seen through
     `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [6])."""
-    m = _matrices(matrix, 1)
-    v = _lib.View()
-    mv = np.zeros(6, np.float32)
-    L = layout.c_layout(size)
-    _lib.check(_lib.lib().jpeg_amd_warp_view(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]),
-                                             C.byref(v), mv.ctypes.data), "jpeg_amd_warp_view")
-    return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
-
-
-def _homographies(matrices, n: int) -> np.ndarray:
-    """matrices= of the project calls -> float32 [n, 9], contiguous."""
-    m = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, 9))
-    if m.shape[0] != n:
-        raise ValueError("matrices: one (m00, m01, m02, m10, m11, m12, m20, m21, m22) per image")
-    return m
-
-
-def _is_projective(matrices) -> bool:
-    """Whether warp= of the file calls holds 3 x 3 matrices ([n, 9] or [n, 3, 3]) rather than affine ones ([n, 6])."""
-    shape = np.shape(matrices)
-    return shape[-1:] == (9,) or shape[-2:] == (3, 3)
+    return _map_view(6, size, layout, matrix, out_size, orientation)
 
 
 def perspective_matrix(src_points, out_points) -> np.ndarray:
@@ -743,13 +731,7 @@ def project_view(size, layout: "Layout", matrix, out_size, orientation: int = 1)
     """The view that a projective map of an image of `size` (w, h) and `layout` reads, and the matrix against it
     (jpeg_amd_project_view): `matrix` (9 values, or [3, 3]) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT
     image, the stored image seen through `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [9])."""
-    m = _homographies(matrix, 1)
-    v = _lib.View()
-    mv = np.zeros(9, np.float32)
-    L = layout.c_layout(size)
-    _lib.check(_lib.lib().jpeg_amd_project_view(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]),
-                                                C.byref(v), mv.ctypes.data), "jpeg_amd_project_view")
-    return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
+    return _map_view(9, size, layout, matrix, out_size, orientation)
 
 
 _GREY = (0.2989, 0.587, 0.114)                     # torchvision's rgb_to_grayscale
@@ -797,8 +779,8 @@ def colour_matrix(brightness: float = 1.0, contrast: float = 1.0, saturation: fl
 
 
 def _colour(colour, colour_clamp, n: int):
-    """colour=, colour_clamp= of the tensor calls -> (struct jpeg_amd_colour, keep), or (None, None) for colour=None (today's
-    entry point).  colour: [n, 3, 4] or [n, 12]; colour_clamp: (lo, hi) in byte units, None: no clamp."""
+    """colour=, colour_clamp= of the tensor calls -> (struct jpeg_amd_colour, keep), or (None, None) for colour=None.
+    colour: [n, 3, 4] or [n, 12]; colour_clamp: (lo, hi) in byte units, None: no clamp."""
     if colour is None:
         if colour_clamp is not None:
             raise ValueError("colour_clamp: only together with colour")
@@ -1038,8 +1020,7 @@ def view_denom(source_size, want_size) -> int:
 
 
 def _filter(filter) -> int:
-    """filter="bilinear" | "antialias" | "bicubic" of the resample calls -> the JPEG_AMD_FILTER_* code for the *_filter_*
-    entry points (with the bilinear code they are the entry points without a filter argument)."""
+    """filter="bilinear" | "antialias" | "bicubic" of the resample calls -> its JPEG_AMD_FILTER_* code."""
     codes = {"bilinear": _lib.FILTER_BILINEAR, "antialias": _lib.FILTER_ANTIALIAS, "bicubic": _lib.FILTER_BICUBIC}
     if filter not in codes:
         raise ValueError("filter: 'bilinear', 'antialias' or 'bicubic'")
@@ -1083,13 +1064,8 @@ def decode_resized(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     ("bicubic resample" there; what torch's interpolate(mode="bicubic", antialias=True) computes, within one level), which
     refuses a view more than 8 times the target on an axis.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
-    vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
-    n = vs.shape[0]
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                               code, out.data_ptr(), stride),
-               "jpeg_amd_decode_resized_filter_batch", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    source = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    return _resample_batch(source, color, cosite, _Resample(ctx, source[0].shape[0], out_size, code).target())
 
 
 def _crop_views(size, source_regions, out_size) -> np.ndarray:
@@ -1131,34 +1107,16 @@ def _pack_images(ctx: Context, images):
 
 def resize(ctx: Context, images, out_size, filter: str = "bilinear", orientations=None, place=None, anchor="centre", fill=(0, 0, 0)):
     """Bilinearly resample n device uint8 images [h_i, w_i, 3] of any sizes to out_size (Wt, Ht) in one launch
-    (jpeg_amd_resize_filter_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
+    (jpeg_amd_resize_placed_batch), or with filter="antialias" through the antialiasing filter (no image more than 16 times
     the target on an axis), or with filter="bicubic" through the bicubic one (no image more than 8 times; decode_resized says
     which filter that is).  The images are packed into one allocation first (torch copies).  orientations: per image an EXIF
-    orientation 1 .. 8 in which the image is read (jpeg_amd_resize_oriented_batch; include/jpeg_amd.h, "oriented resample").
-    place / anchor / fill: the image in a window of the out_size canvas and the
-    fill's three bytes around it (include/jpeg_amd.h, "placed resample"): place "fit" or "fit-down" (aspect-preserving, at
-    `anchor` "centre" or "top-left") or one window (x, y, width, height) per image; with it the windows applied come back as an
-    extra int32 [n, 4] item.
-    Returns uint8 [n, Ht, Wt, 3]."""
+    orientation 1 .. 8 in which the image is read (include/jpeg_amd.h, "oriented resample").  place / anchor / fill: the image
+    in a window of the out_size canvas and the fill's three bytes around it ("placed resample" there): place "fit" or "fit-down"
+    (aspect-preserving, at `anchor` "centre" or "top-left") or one window (x, y, width, height) per image; with it the windows
+    applied come back as an extra int32 [n, 4] item.  Returns uint8 [n, Ht, Wt, 3]."""
     code = _filter(filter)
     images = list(images)
-    n = len(images)
-    h_orient = _orientations(orientations, n)
-    placement, h_windows, keep = _placement(place, anchor, fill, n)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if placement is not None:
-        _lib.check(_lib.lib().jpeg_amd_resize_placed_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code, h_orient,
-                                                           C.byref(placement), h_windows, out.data_ptr(), stride),
-                   "jpeg_amd_resize_placed_batch", ctx.handle)
-        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_resize_filter_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                           out.data_ptr(), stride), "jpeg_amd_resize_filter_batch", ctx.handle)
-    else:
-        _lib.check(_lib.lib().jpeg_amd_resize_oriented_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code, h_orient,
-                                                             out.data_ptr(), stride), "jpeg_amd_resize_oriented_batch", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    return _resample_images(images, _Resample(ctx, len(images), out_size, code).oriented(orientations).placed(place, anchor, fill))
 
 
 def tensor_spec(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.TensorSpec:
@@ -1180,30 +1138,118 @@ def tensor_spec(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.Te
     return spec
 
 
-def _bytes_out(ctx: Context, n: int, out_size):
-    """-> (wt, ht, room for n byte images of out_size [n * 3 wt ht], its stride)."""
-    wt, ht = int(out_size[0]), int(out_size[1])
-    stride = 3 * max(wt, 0) * max(ht, 0)
-    return wt, ht, ctx.empty(n * stride, _torch().uint8), stride
+class _Resample:
+    """What a resample call was asked for, as one record (csrc/resample_request.hpp on this side).  A public function fills the
+    columns in the order in which it judges its keyword arguments, the target (bytes or elements) last; the record keeps alive
+    what the call points into, and a column the call does not carry is None, which the library takes as NULL."""
+
+    def __init__(self, ctx: Context, n: int, out_size, code: int = _lib.FILTER_BILINEAR):
+        self.ctx, self.n, self.out_size, self.code, self.k = ctx, n, out_size, code, 0   # k: the numbers of a matrix; 0: no map
+        self.h_orient = self.placement = self.h_windows = self.tint = self.spec = self.h_flip = None
+
+    def oriented(self, orientations, exif: bool = False):
+        self.h_orient = _orientations(orientations, self.n, exif)
+        return self
+
+    def placed(self, place, anchor, fill):
+        self.placement, self.h_windows, self._keep_windows = _placement(place, anchor, fill, self.n)
+        return self
+
+    def mapped(self, matrices, k: int, edge, fill, orientations=None):
+        """k = 6: the affine map, 9: the homography.  The mixed calls judge their orientations behind the matrices."""
+        self.k, self.m, self.m_out = k, _matrices(matrices, self.n, k), np.zeros((self.n, k), np.float32)
+        if orientations is not None:
+            self.oriented(orientations)
+        self.warp = _warp(edge, fill)
+        return self
+
+    def coloured(self, colour, colour_clamp):
+        self.tint, self._keep_colour = _colour(colour, colour_clamp, self.n)
+        return self
+
+    def target(self, tensor=None):
+        """The target, which comes last: room for n images of out_size, of bytes or with tensor = (spec, flips) of elements."""
+        torch = _torch()
+        self.wt, self.ht = int(self.out_size[0]), int(self.out_size[1])
+        self.stride = 3 * max(self.wt, 0) * max(self.ht, 0)                 # between the images, in elements
+        dtype = torch.uint8
+        if tensor is not None:
+            self.spec, flips = tensor
+            dtype = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}.get(self.spec.dtype, torch.float32)
+            if flips is not None:
+                f = np.ascontiguousarray(np.asarray(flips).reshape(-1) != 0, np.uint8)
+                if f.size != self.n:
+                    raise ValueError("flips: one flag per image")
+                self.h_flip = (C.c_uint8 * max(self.n, 1))(*f.tolist())
+        self.out = self.ctx.empty(self.n * self.stride, dtype)
+        return self
+
+    def call(self, cells, head, lead=(), written=(), outputs=(), columns=True):
+        """The one library call of the request: its cell (map x target) of a source's table, behind the source's `head`.  lead: the
+        views or source rectangles, with a map the orientations; written: where a mixed call writes views and matrices."""
+        target = () if self.spec is None else (C.byref(self.spec), self.h_flip)
+        colour = () if self.spec is None else (None if self.tint is None else C.byref(self.tint),)
+        if self.k:
+            args = lead + (self.m.ctypes.data, C.byref(self.warp), self.wt, self.ht) + target + written + colour
+        else:                                                # (the uniform batch has no columns)
+            place = None if self.placement is None else C.byref(self.placement)
+            args = lead + (self.wt, self.ht, self.code) + target + ((self.h_orient, place, self.h_windows) + colour if columns else ())
+        name = cells[self.k, self.spec is not None]
+        _lib.check(getattr(_lib.lib(), name)(self.ctx.handle, *head, *args, self.out.data_ptr(), self.stride, *outputs), name,
+                   self.ctx.handle)
+
+    def result(self, *written):
+        """The output tensor, then `written`, then with a placement the windows applied; one item comes back bare."""
+        chw = self.spec is not None and self.spec.layout == _lib.TENSOR_CHW
+        out = self.out.view(self.n, 3, self.ht, self.wt) if chw else self.out.view(self.n, self.ht, self.wt, 3)
+        if self.placement is not None:
+            written += (np.array([(r.x, r.y, r.width, r.height) for r in self.h_windows[:self.n]], np.int32).reshape(self.n, 4),)
+        return (out,) + written if written else out
 
 
-def _tensor_out(ctx: Context, n: int, out_size, spec: _lib.TensorSpec, flips):
-    """-> (wt, ht, the output tensor [n * 3 wt ht], its stride in elements, the flip bytes or None)."""
-    torch = _torch()
-    wt, ht = int(out_size[0]), int(out_size[1])
-    dtype = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}.get(spec.dtype, torch.float32)
-    stride = 3 * max(wt, 0) * max(ht, 0)
-    h_flip = None
-    if flips is not None:
-        f = np.ascontiguousarray(np.asarray(flips).reshape(-1) != 0, np.uint8)
-        if f.size != n:
-            raise ValueError("flips: one flag per image")
-        h_flip = (C.c_uint8 * max(n, 1))(*f.tolist())
-    return wt, ht, ctx.empty(n * stride, dtype), stride, h_flip
+# The widest entry point of every cell, source by source: (numbers of a matrix, tensor target) -> symbol (csrc/capi_*.hip).
+_BATCH_CELLS = {(0, False): "jpeg_amd_decode_resized_filter_batch", (0, True): "jpeg_amd_decode_tensor_filter_batch"}
+_IMAGE_CELLS = {(0, False): "jpeg_amd_resize_placed_batch", (0, True): "jpeg_amd_resize_colour_tensor_batch",
+                (6, False): "jpeg_amd_warp_batch", (6, True): "jpeg_amd_warp_colour_tensor_batch",
+                (9, False): "jpeg_amd_project_batch", (9, True): "jpeg_amd_project_tensor_batch"}
+_MIXED_CELLS = {(0, False): "jpeg_amd_decode_resized_placed_mixed", (0, True): "jpeg_amd_decode_tensor_colour_mixed",
+                (6, False): "jpeg_amd_decode_warped_mixed", (6, True): "jpeg_amd_decode_tensor_warped_colour_mixed",
+                (9, False): "jpeg_amd_decode_projected_mixed", (9, True): "jpeg_amd_decode_tensor_projected_mixed"}
+_FILE_CELLS = {(0, False): "jpeg_amd_decompress_resized_placed_mixed", (0, True): "jpeg_amd_decompress_tensor_colour_mixed",
+               (6, False): "jpeg_amd_decompress_resized_warped_mixed", (6, True): "jpeg_amd_decompress_tensor_warped_colour_mixed",
+               (9, False): "jpeg_amd_decompress_resized_projected_mixed", (9, True): "jpeg_amd_decompress_tensor_projected_mixed"}
 
 
-def _tensor_view(out, n, wt, ht, spec):
-    return out.view(n, 3, ht, wt) if spec.layout == _lib.TENSOR_CHW else out.view(n, ht, wt, 3)
+def _resample_batch(source, color, cosite: bool, rq: _Resample):
+    """The route of the uniform batch; source: what _view_batch_args returns."""
+    vs, head, keep, h_views = source
+    rq.call(_BATCH_CELLS, head + (1 if cosite else 0, color.code, h_views), columns=False)
+    return rq.result()
+
+
+def _resample_images(images, rq: _Resample, tensor=None):
+    """The route of device images, which are packed here, behind the request's other complaints and in front of its target's."""
+    src, src_stride, extents = _pack_images(rq.ctx, images)
+    rq.target(tensor).call(_IMAGE_CELLS, (rq.n, src.data_ptr(), src_stride, extents))
+    return rq.result()
+
+
+def _resample_mixed(source, color, cosite: bool, rq: _Resample):
+    """The route of Spectral images of mixed layouts; source: what _mixed_args returns (with a map: of placeholder views)."""
+    vs, h_images, h_views, keep = source
+    lead, written = ((rq.h_orient,), (h_views, rq.m_out.ctypes.data)) if rq.k else ((h_views,), ())
+    rq.call(_MIXED_CELLS, (rq.n, h_images, 1 if cosite else 0, color.code), lead, written)
+    return rq.result(_views_array(h_views, rq.n), rq.m_out) if rq.k else rq.result()
+
+
+def _resample_files(source, threads: int, color, cosite: bool, rq: _Resample):
+    """The route of files; source: what _file_args returns.  -> the orientations applied: the wide forms always have room."""
+    n, ptrs, sizes, regions, infos, h_views, keep = source
+    head = (ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code)
+    applied = (C.c_int32 * max(n, 1))()
+    lead, matrices = ((rq.h_orient,), (rq.m_out.ctypes.data,)) if rq.k else ((regions,), ())
+    rq.call(_FILE_CELLS, head, lead, outputs=(infos, h_views) + matrices + (applied,))
+    return np.array(applied[:n], np.int32)
 
 
 def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, out_size, spec: _lib.TensorSpec, flips=None,
@@ -1213,13 +1259,8 @@ def decode_tensors(ctx: Context, size, layout: Layout, planes, quanta, views, ou
     normalised by `spec` (tensor_spec) and stored in its dtype and layout; `filter` as in decode_resized.  Returns one tensor
     [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
-    vs, head, keep, h_views = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
-    n = vs.shape[0]
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_batch(ctx.handle, *head, 1 if cosite else 0, color.code, h_views, wt, ht,
-                                                              code, C.byref(spec), h_flip, out.data_ptr(), stride),
-               "jpeg_amd_decode_tensor_filter_batch", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec)
+    source = _view_batch_args(ctx, size, layout, planes, quanta, views, q)
+    return _resample_batch(source, color, cosite, _Resample(ctx, source[0].shape[0], out_size, code).target((spec, flips)))
 
 
 def decode_crops_tensor(ctx: Context, size, layout: Layout, planes, quanta, source_regions, out_size, spec: _lib.TensorSpec,
@@ -1271,73 +1312,28 @@ def decode_views_mixed(ctx: Context, spectrals, views, color=RGB, cosite: bool =
 
 def decode_resized_mixed(ctx: Context, spectrals, views, out_size, color=RGB, cosite: bool = False, filter: str = "bilinear",
                          orientations=None, place=None, anchor="centre", fill=(0, 0, 0)):
-    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_filter_mixed);
+    """decode_resized for images of different sizes and layouts in one call (jpeg_amd_decode_resized_placed_mixed);
     arguments as decode_views_mixed, `filter` as in decode_resized.  orientations: per image an EXIF orientation 1 .. 8 in which
-    its view's pixels are read (jpeg_amd_decode_resized_oriented_mixed); the views stay rectangles of the STORED scaled
-    images.  place / anchor / fill: as in resize (jpeg_amd_decode_resized_placed_mixed); "fit" fits the oriented view.
-    Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    its view's pixels are read; the views stay rectangles of the STORED scaled images.  place / anchor / fill: as in resize;
+    "fit" fits the oriented view.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
-    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
-    n = vs.shape[0]
-    h_orient = _orientations(orientations, n)
-    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if placement is not None:
-        _lib.check(_lib.lib().jpeg_amd_decode_resized_placed_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                   ht, code, h_orient, C.byref(placement), h_windows, out.data_ptr(),
-                                                                   stride), "jpeg_amd_decode_resized_placed_mixed", ctx.handle)
-        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_decode_resized_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                   ht, code, out.data_ptr(), stride),
-                   "jpeg_amd_decode_resized_filter_mixed", ctx.handle)
-    else:
-        _lib.check(_lib.lib().jpeg_amd_decode_resized_oriented_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views,
-                                                                     wt, ht, code, h_orient, out.data_ptr(), stride),
-                   "jpeg_amd_decode_resized_oriented_mixed", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    source = _mixed_args(ctx, spectrals, views)
+    rq = _Resample(ctx, source[0].shape[0], out_size, code).oriented(orientations).placed(place, anchor, fill)
+    return _resample_mixed(source, color, cosite, rq.target())
 
 
 def decode_tensors_mixed(ctx: Context, spectrals, views, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                          cosite: bool = False, filter: str = "bilinear", orientations=None, place=None, anchor="centre",
                          fill=(0, 0, 0), colour=None, colour_clamp=None):
-    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_filter_mixed); arguments
-    as decode_views_mixed, then as decode_tensors, `filter` ("bilinear" | "antialias" | "bicubic") included.  orientations: as in decode_resized_mixed
-    (jpeg_amd_decode_tensor_oriented_mixed); a flip mirrors the output after the orientation.
-    place / anchor / fill: as in resize (jpeg_amd_decode_tensor_placed_mixed); a flip mirrors the whole canvas.
-    colour / colour_clamp: as in resize_tensor (jpeg_amd_decode_tensor_colour_mixed).
+    """decode_tensors for images of different sizes and layouts in one call (jpeg_amd_decode_tensor_colour_mixed); arguments
+    as decode_views_mixed, then as decode_tensors, `filter` ("bilinear" | "antialias" | "bicubic") included.  orientations: as
+    in decode_resized_mixed; a flip mirrors the output after the orientation.  place / anchor / fill: as in resize; a flip
+    mirrors the whole canvas.  colour / colour_clamp: as in resize_tensor.
     Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
     code = _filter(filter)
-    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, views)
-    n = vs.shape[0]
-    h_orient = _orientations(orientations, n)
-    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if tint is not None:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_colour_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                  ht, code, C.byref(spec), h_flip, h_orient,
-                                                                  None if placement is None else C.byref(placement), h_windows,
-                                                                  C.byref(tint), out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_colour_mixed", ctx.handle)
-        res = _tensor_view(out, n, wt, ht, spec)
-        return res if placement is None else (res, _windows_array(h_windows, n))
-    if placement is not None:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_placed_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                  ht, code, C.byref(spec), h_flip, h_orient, C.byref(placement),
-                                                                  h_windows, out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_placed_mixed", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec), _windows_array(h_windows, n)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_filter_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views, wt,
-                                                                  ht, code, C.byref(spec), h_flip, out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_filter_mixed", ctx.handle)
-    else:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_oriented_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_views,
-                                                                    wt, ht, code, C.byref(spec), h_flip, h_orient, out.data_ptr(),
-                                                                    stride),
-                   "jpeg_amd_decode_tensor_oriented_mixed", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec)
+    source = _mixed_args(ctx, spectrals, views)
+    rq = _Resample(ctx, source[0].shape[0], out_size, code).oriented(orientations).placed(place, anchor, fill)
+    return _resample_mixed(source, color, cosite, rq.coloured(colour, colour_clamp).target((spec, flips)))
 
 
 def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
@@ -1358,38 +1354,33 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
     if orientations is not None and len(orientations) != len(spectrals):
         raise ValueError("orientations: one value in 1 .. 8 per image")
     views = np.empty((len(spectrals), 5), np.int32)
+    windows = None
     if place is not None:
         if isinstance(place, str):
             place = [place_window(place, regs[i, 2:], out_size, anchor) for i in range(len(spectrals))]
         windows = np.asarray(place, np.int64).reshape(-1, 4)
         if windows.shape[0] != len(spectrals):
             raise ValueError("place: one (x, y, width, height) per image")
-        for i, s in enumerate(spectrals):
-            denom = view_denom(regs[i, 2:], windows[i, 2:])
-            stored = regs[i].tolist() if orientations is None else orient_region(orientations[i], s.size, regs[i].tolist())
-            views[i] = (denom,) + view_of_source(s.size, denom, stored)
-        out, applied = decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
-                                            orientations=orientations, place=windows, anchor=anchor, fill=fill, colour=colour,
-                                            colour_clamp=colour_clamp)
-        return out, views, applied
     for i, s in enumerate(spectrals):
-        if orientations is None:
-            views[i] = _crop_views(s.size, regs[i:i + 1], out_size)[0]
-        else:
-            denom = view_denom(regs[i, 2:], out_size)
-            views[i] = (denom,) + view_of_source(s.size, denom, orient_region(orientations[i], s.size, regs[i].tolist()))
-    return decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
-                                orientations=orientations, colour=colour, colour_clamp=colour_clamp), views
+        denom = view_denom(regs[i, 2:], out_size if windows is None else windows[i, 2:])
+        stored = regs[i].tolist() if orientations is None else orient_region(orientations[i], s.size, regs[i].tolist())
+        views[i] = (denom,) + view_of_source(s.size, denom, stored)
+    res = decode_tensors_mixed(ctx, spectrals, views, out_size, spec, flips=flips, color=color, cosite=cosite, filter=filter,
+                               orientations=orientations, place=windows, anchor=anchor, fill=fill, colour=colour, colour_clamp=colour_clamp)
+    return (res, views) if windows is None else (res[0], views, res[1])
 
 
-def _mapped_mixed_args(ctx: Context, spectrals, matrices, orientations, k: int):
-    """The arguments the warped (k = 6 numbers per matrix) and the projected (k = 9) mixed calls share, behind _mixed_args'
-    (with placeholder views)."""
-    spectrals = list(spectrals)
-    n = len(spectrals)
-    vs, h_images, h_views, keep = _mixed_args(ctx, spectrals, np.zeros((n, 5), np.int32))
-    m = _homographies(matrices, n) if k == 9 else _matrices(matrices, n)
-    return n, h_images, h_views, m, _orientations(orientations, n), np.zeros((n, k), np.float32), keep
+def _resample_mapped(ctx: Context, sources, matrices, k: int, out_size, edge, fill, tensor=None, mixed=None):
+    """The warp (k = 6) and project (k = 9) calls of device images, or with mixed = (color, cosite, orientations) of Spectral
+    images.  tensor: None for bytes, or the (spec, flips, colour, colour_clamp) of the tensor forms."""
+    sources = list(sources)
+    source = mixed and _mixed_args(ctx, sources, np.zeros((len(sources), 5), np.int32))   # (placeholder views: the call writes them)
+    rq = _Resample(ctx, len(sources), out_size).mapped(matrices, k, edge, fill, mixed and mixed[2])
+    if tensor:
+        rq.coloured(*tensor[2:])
+    if not mixed:
+        return _resample_images(sources, rq, tensor and tensor[:2])
+    return _resample_mixed(source, mixed[0], mixed[1], rq.target(tensor and tensor[:2]))
 
 
 def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
@@ -1399,36 +1390,16 @@ def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, 
     orientations[i], 1 .. 8; None: as stored).  warp_view chooses each image's denominator and view -- only the part the canvas
     maps into is decoded -- and image i is warp() of decode_views_mixed's pixels for that view with the matrix against it.
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 6])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 6)
-    w = _warp(edge, fill)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_decode_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient, m.ctypes.data,
-                                                       C.byref(w), wt, ht, h_views, m_out.ctypes.data, out.data_ptr(), stride),
-               "jpeg_amd_decode_warped_mixed", ctx.handle)
-    return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
+    return _resample_mapped(ctx, spectrals, matrices, 6, out_size, edge, fill, None, (color, cosite, orientations))
 
 
 def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                                 cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None, colour_clamp=None):
-    """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_mixed); flips, spec,
-    colour and colour_clamp (jpeg_amd_decode_tensor_warped_colour_mixed) as in warp_tensor.
+    """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_colour_mixed); flips, spec,
+    colour and colour_clamp as in warp_tensor.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 6)
-    w = _warp(edge, fill)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if tint is not None:
-        _lib.check(_lib.lib().jpeg_amd_decode_tensor_warped_colour_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code,
-                                                                         h_orient, m.ctypes.data, C.byref(w), wt, ht, C.byref(spec),
-                                                                         h_flip, h_views, m_out.ctypes.data, C.byref(tint),
-                                                                         out.data_ptr(), stride),
-                   "jpeg_amd_decode_tensor_warped_colour_mixed", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_warped_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
-                                                              m.ctypes.data, C.byref(w), wt, ht, C.byref(spec), h_flip, h_views,
-                                                              m_out.ctypes.data, out.data_ptr(), stride),
-               "jpeg_amd_decode_tensor_warped_mixed", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
+    return _resample_mapped(ctx, spectrals, matrices, 6, out_size, edge, fill, (spec, flips, colour, colour_clamp),
+                            (color, cosite, orientations))
 
 
 def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
@@ -1438,13 +1409,7 @@ def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RG
     makes one from four point pairs).  project_view chooses each image's denominator and view, and image i is project() of
     decode_views_mixed's pixels for that view with the matrix against it.
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 9])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 9)
-    w = _warp(edge, fill)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_decode_projected_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
-                                                          m.ctypes.data, C.byref(w), wt, ht, h_views, m_out.ctypes.data, out.data_ptr(),
-                                                          stride), "jpeg_amd_decode_projected_mixed", ctx.handle)
-    return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
+    return _resample_mapped(ctx, spectrals, matrices, 9, out_size, edge, fill, None, (color, cosite, orientations))
 
 
 def decode_tensors_projected_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
@@ -1453,16 +1418,8 @@ def decode_tensors_projected_mixed(ctx: Context, spectrals, matrices, out_size, 
     """decode_projected_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_projected_mixed); flips, spec,
     colour and colour_clamp as in project_tensor.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 9])."""
-    n, h_images, h_views, m, h_orient, m_out, keep = _mapped_mixed_args(ctx, spectrals, matrices, orientations, 9)
-    w = _warp(edge, fill)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_decode_tensor_projected_mixed(ctx.handle, n, h_images, 1 if cosite else 0, color.code, h_orient,
-                                                                 m.ctypes.data, C.byref(w), wt, ht, C.byref(spec), h_flip, h_views,
-                                                                 m_out.ctypes.data, None if tint is None else C.byref(tint),
-                                                                 out.data_ptr(), stride),
-               "jpeg_amd_decode_tensor_projected_mixed", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), m_out
+    return _resample_mapped(ctx, spectrals, matrices, 9, out_size, edge, fill, (spec, flips, colour, colour_clamp),
+                            (color, cosite, orientations))
 
 
 def _file_args(sources, source_regions):
@@ -1483,205 +1440,85 @@ def _file_args(sources, source_regions):
     return n, ptrs, sizes, regions, (_lib.FrameInfo * max(n, 1))(), (_lib.View * max(n, 1))(), files
 
 
-def _warp_file_args(warp, n: int, source_regions, place, filter_code: int, edge, fill):
-    """warp=, edge=, fill= of the file calls -> (the matrices [n, 6], room for the applied ones, struct jpeg_amd_warp); of
-    3 x 3 matrices ([n, 9] or [n, 3, 3]: "projective resample") [n, 9] and room for as many."""
-    if source_regions is not None or place is not None or filter_code != _lib.FILTER_BILINEAR:
+def _file_columns(rq: _Resample, warp, edge, source_regions, place, anchor, fill) -> _Resample:
+    """warp=, edge=, fill= of the file calls, or without a warp their place=, anchor=, fill=."""
+    if warp is None:
+        return rq.placed(place, anchor, fill)
+    if source_regions is not None or place is not None or rq.code != _lib.FILTER_BILINEAR:
         raise ValueError('warp: not together with source_regions, place or a filter other than "bilinear"')
-    if _is_projective(warp):
-        return _homographies(warp, n), np.zeros((n, 9), np.float32), _warp(edge, fill)
-    return _matrices(warp, n), np.zeros((n, 6), np.float32), _warp(edge, fill)
+    shape = np.shape(warp)                                   # [n, 9] or [n, 3, 3]: the homography; else the affine map [n, 6]
+    return rq.mapped(warp, 9 if shape[-1:] == (9,) or shape[-2:] == (3, 3) else 6, edge, fill)
 
 
 def _views_array(h_views, n) -> np.ndarray:
     return np.array([(v.denom, v.region.x, v.region.y, v.region.width, v.region.height) for v in h_views[:n]], np.int32).reshape(n, 5)
 
 
-def _files_result(out, n, wt, ht, spec, h_views, infos, h_orient=None, applied=None):
-    """What decompress_tensors returns of every call: (the tensor, the views, the frame infos), and with orientations given
-    the orientations applied."""
-    res = (_tensor_view(out, n, wt, ht, spec), _views_array(h_views, n), list(infos[:n]))
-    return res if h_orient is None else res + (np.array(applied[:n], np.int32),)
-
-
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
                        cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None, place=None,
                        anchor="centre", fill=(0, 0, 0), warp=None, edge="fill", colour=None, colour_clamp=None):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
-    and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_mixed; include/jpeg_amd.h, "files to
+    and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_colour_mixed, with `warp`
+    jpeg_amd_decompress_tensor_warped_colour_mixed or jpeg_amd_decompress_tensor_projected_mixed; include/jpeg_amd.h, "files to
     tensors").  Image i is what decode_crops_tensor_mixed gives for Spectral.decompress of file i: per file a rectangle
     (x, y, width, height) of its full-size image (source_regions; None: the whole images), decoded at the cheapest denominator
     that is still no smaller than out_size (Wt, Ht), resampled by `filter` ("bilinear" | "antialias" | "bicubic", as in
-    decode_resized), mirrored where flips[i] is set, normalised by
-    `spec` (tensor_spec).  The files are entropy-decoded on `threads` host threads (0: all cores) into the sparse form, and
-    only the parts of the coefficient planes that the views read are rebuilt on the device.
+    decode_resized), mirrored where flips[i] is set, normalised by `spec` (tensor_spec).  The files are entropy-decoded on
+    `threads` host threads (0: all cores) into the sparse form, and only the parts of the coefficient planes that the views read
+    are rebuilt on the device.
     orientation: None (the images as they are stored), "exif" (every file in the orientation its EXIF segment names:
-    exif_orientation) or a sequence of 1 .. 8 or "exif" per file (jpeg_amd_decompress_tensor_oriented_mixed; include/jpeg_amd.h,
-    "oriented resample").  With it, source_regions are rectangles of the ORIENTED images -- the images a viewer shows -- while the
-    views that come back stay in stored scaled coordinates.
+    exif_orientation) or a sequence of 1 .. 8 or "exif" per file ("oriented resample" there).  With it, source_regions are
+    rectangles of the ORIENTED images -- the images a viewer shows -- while the views that come back stay in stored scaled
+    coordinates.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5] of (denom, x, y, width, height), the files'
     frame infos), and with `orientation` given a fourth item, the orientations applied as int32 [n].
-    place / anchor / fill: as in resize (jpeg_amd_decompress_tensor_placed_mixed); "fit" fits the (oriented) source rectangle,
-    and the denominator is chosen against the window; with `place` the windows applied come back as the last item.
+    place / anchor / fill: as in resize; "fit" fits the (oriented) source rectangle, and the denominator is chosen against the
+    window; with `place` the windows applied come back as the last item.
     warp / edge / fill: per file a matrix [6] in the coordinates of its UPRIGHT full-size image, as in decode_warped_mixed
-    (jpeg_amd_decompress_tensor_warped_mixed; include/jpeg_amd.h, "warped resample"); not together with source_regions, place
-    or a filter other than "bilinear" (ValueError).  The views that come back are warp_view's, and the matrices applied to them
-    come back as the last item, float32 [n, 6].  A warp of [n, 9] or [n, 3, 3] is a homography per file
-    (jpeg_amd_decompress_tensor_projected_mixed; "projective resample"): the views are project_view's and the matrices that
+    ("warped resample" there); not together with source_regions, place or a filter other than "bilinear" (ValueError).  The
+    views that come back are warp_view's, and the matrices applied to them come back as the last item, float32 [n, 6].  A warp
+    of [n, 9] or [n, 3, 3] is a homography per file ("projective resample"): the views are project_view's and the matrices that
     come back float32 [n, 9].
-    colour / colour_clamp: as in resize_tensor, per file (jpeg_amd_decompress_tensor_colour_mixed, with `warp`
-    jpeg_amd_decompress_tensor_warped_colour_mixed); what comes back is what the call without them returns."""
+    colour / colour_clamp: as in resize_tensor, per file; what comes back is what the call without them returns."""
     code = _filter(filter)
-    n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
-    h_orient = _orientations(orientation, n, exif=True)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    if warp is not None:
-        m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
-        wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-        applied = (C.c_int32 * max(n, 1))()
-        if m.shape[1] == 9:
-            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_projected_mixed(ctx.handle, ptrs, sizes, n, int(threads),
-                                                                             1 if cosite else 0, color.code, h_orient, m.ctypes.data,
-                                                                             C.byref(w), wt, ht, C.byref(spec), h_flip,
-                                                                             None if tint is None else C.byref(tint), out.data_ptr(),
-                                                                             stride, infos, h_views, m_out.ctypes.data, applied),
-                       "jpeg_amd_decompress_tensor_projected_mixed", ctx.handle)
-        elif tint is not None:
-            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_colour_mixed(ctx.handle, ptrs, sizes, n, int(threads),
-                                                                                 1 if cosite else 0, color.code, h_orient, m.ctypes.data,
-                                                                                 C.byref(w), wt, ht, C.byref(spec), h_flip, C.byref(tint),
-                                                                                 out.data_ptr(), stride, infos, h_views,
-                                                                                 m_out.ctypes.data, applied),
-                       "jpeg_amd_decompress_tensor_warped_colour_mixed", ctx.handle)
-        else:
-            _lib.check(_lib.lib().jpeg_amd_decompress_tensor_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                          color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
-                                                                          C.byref(spec), h_flip, out.data_ptr(), stride, infos, h_views,
-                                                                          m_out.ctypes.data, applied),
-                       "jpeg_amd_decompress_tensor_warped_mixed", ctx.handle)
-        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
-        return res + (m_out,)
-    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if tint is not None:
-        applied = (C.c_int32 * max(n, 1))()
-        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_colour_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                      color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
-                                                                      None if placement is None else C.byref(placement), h_windows,
-                                                                      C.byref(tint), out.data_ptr(), stride, infos, h_views, applied),
-                   "jpeg_amd_decompress_tensor_colour_mixed", ctx.handle)
-        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
-        return res if placement is None else res + (_windows_array(h_windows, n),)
-    if placement is not None:
-        applied = (C.c_int32 * max(n, 1))()
-        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_placed_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                      color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
-                                                                      C.byref(placement), h_windows, out.data_ptr(), stride, infos,
-                                                                      h_views, applied),
-                   "jpeg_amd_decompress_tensor_placed_mixed", ctx.handle)
-        res = _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
-        return res + (_windows_array(h_windows, n),)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_decompress_tensor_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
-                                                               regions, wt, ht, code, C.byref(spec), h_flip, out.data_ptr(), stride,
-                                                               infos, h_views), "jpeg_amd_decompress_tensor_mixed", ctx.handle)
-        return _files_result(out, n, wt, ht, spec, h_views, infos)
-    applied = (C.c_int32 * max(n, 1))()
-    _lib.check(_lib.lib().jpeg_amd_decompress_tensor_oriented_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                    color.code, regions, wt, ht, code, C.byref(spec), h_flip, h_orient,
-                                                                    out.data_ptr(), stride, infos, h_views, applied),
-               "jpeg_amd_decompress_tensor_oriented_mixed", ctx.handle)
-    return _files_result(out, n, wt, ht, spec, h_views, infos, h_orient, applied)
+    source = _file_args(sources, source_regions)
+    n, infos, h_views = source[0], source[4], source[5]
+    rq = _Resample(ctx, n, out_size, code).oriented(orientation, exif=True).coloured(colour, colour_clamp)
+    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill).target((spec, flips))
+    applied = _resample_files(source, threads, color, cosite, rq)
+    written = (_views_array(h_views, n), list(infos[:n])) + (() if rq.h_orient is None else (applied,))
+    return rq.result(*written, *((rq.m_out,) if rq.k else ()))
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
                        filter: str = "bilinear", threads: int = 0, orientation=None, place=None, anchor="centre", fill=(0, 0, 0),
                        warp=None, edge="fill"):
-    """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_mixed): the files' views resampled to out_size
-    (Wt, Ht) as bytes by `filter`; `orientation` as there (jpeg_amd_decompress_resized_oriented_mixed).
-    place / anchor / fill: as there (jpeg_amd_decompress_resized_placed_mixed), the windows as a second item.
-    warp / edge / fill: as there (jpeg_amd_decompress_resized_warped_mixed); with it the views (int32 [n, 5]) and the matrices
-    applied to them (float32 [n, 6]; of a [n, 9] or [n, 3, 3] warp, jpeg_amd_decompress_resized_projected_mixed, [n, 9]) come
-    back as the last two items.
-    Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_placed_mixed, with `warp`
+    jpeg_amd_decompress_resized_warped_mixed or jpeg_amd_decompress_resized_projected_mixed): the files' views resampled to
+    out_size (Wt, Ht) as bytes by `filter`; `orientation` as there.  place / anchor / fill: as there, the windows as a second
+    item.  warp / edge / fill: as there; with it the views (int32 [n, 5]) and the matrices applied to them (float32 [n, 6]; of a
+    [n, 9] or [n, 3, 3] warp [n, 9]) come back as the last two items.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
-    n, ptrs, sizes, regions, infos, h_views, keep = _file_args(sources, source_regions)
-    h_orient = _orientations(orientation, n, exif=True)
-    if warp is not None:
-        m, m_out, w = _warp_file_args(warp, n, source_regions, place, code, edge, fill)
-        wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-        if m.shape[1] == 9:
-            _lib.check(_lib.lib().jpeg_amd_decompress_resized_projected_mixed(ctx.handle, ptrs, sizes, n, int(threads),
-                                                                              1 if cosite else 0, color.code, h_orient, m.ctypes.data,
-                                                                              C.byref(w), wt, ht, out.data_ptr(), stride, infos, h_views,
-                                                                              m_out.ctypes.data, None),
-                       "jpeg_amd_decompress_resized_projected_mixed", ctx.handle)
-            return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
-        _lib.check(_lib.lib().jpeg_amd_decompress_resized_warped_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                       color.code, h_orient, m.ctypes.data, C.byref(w), wt, ht,
-                                                                       out.data_ptr(), stride, infos, h_views, m_out.ctypes.data, None),
-                   "jpeg_amd_decompress_resized_warped_mixed", ctx.handle)
-        return out.view(n, ht, wt, 3), _views_array(h_views, n), m_out
-    placement, h_windows, keep_windows = _placement(place, anchor, fill, n)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    if placement is not None:
-        _lib.check(_lib.lib().jpeg_amd_decompress_resized_placed_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                       color.code, regions, wt, ht, code, h_orient, C.byref(placement),
-                                                                       h_windows, out.data_ptr(), stride, infos, h_views, None),
-                   "jpeg_amd_decompress_resized_placed_mixed", ctx.handle)
-        return out.view(n, ht, wt, 3), _windows_array(h_windows, n)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_decompress_resized_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0, color.code,
-                                                                regions, wt, ht, code, out.data_ptr(), stride, infos, h_views),
-                   "jpeg_amd_decompress_resized_mixed", ctx.handle)
-    else:
-        _lib.check(_lib.lib().jpeg_amd_decompress_resized_oriented_mixed(ctx.handle, ptrs, sizes, n, int(threads), 1 if cosite else 0,
-                                                                         color.code, regions, wt, ht, code, h_orient, out.data_ptr(),
-                                                                         stride, infos, h_views, None),
-                   "jpeg_amd_decompress_resized_oriented_mixed", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    source = _file_args(sources, source_regions)
+    rq = _Resample(ctx, source[0], out_size, code).oriented(orientation, exif=True)
+    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill).target()
+    _resample_files(source, threads, color, cosite, rq)
+    return rq.result(_views_array(source[5], rq.n), rq.m_out) if rq.k else rq.result()
 
 
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None,
                   place=None, anchor="centre", fill=(0, 0, 0), colour=None, colour_clamp=None):
-    """The resample and the output stage alone (jpeg_amd_resize_filter_tensor_batch; `filter` as in resize): n device uint8 images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or
-    [n, Ht, Wt, 3] of spec's dtype, in one launch.  orientations: as in resize (jpeg_amd_resize_oriented_tensor_batch); a flip
-    mirrors the output after the orientation.  place / anchor / fill: as in resize (jpeg_amd_resize_placed_tensor_batch); a
-    padded element is the fill byte through `spec`, and a flip mirrors the whole canvas, window position included.
+    """The resample and the output stage alone (jpeg_amd_resize_colour_tensor_batch; `filter` as in resize): n device uint8
+    images [h_i, w_i, 3] of any sizes to one tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3] of spec's dtype, in one launch.
+    orientations: as in resize; a flip mirrors the output after the orientation.  place / anchor / fill: as in resize; a padded
+    element is the fill byte through `spec`, and a flip mirrors the whole canvas, window position included.
     colour / colour_clamp: per image a matrix [3, 4] (colour_matrix makes one; [n, 3, 4] or [n, 12]) applied to every pixel's
     (R, G, B), fill pixels included, in front of spec's mean, then clamped to colour_clamp = (lo, hi) in byte units (None: no
-    clamp), in the same launch (jpeg_amd_resize_colour_tensor_batch; include/jpeg_amd.h, "colour stage")."""
+    clamp), in the same launch (include/jpeg_amd.h, "colour stage")."""
     code = _filter(filter)
     images = list(images)
-    n = len(images)
-    h_orient = _orientations(orientations, n)
-    placement, h_windows, keep = _placement(place, anchor, fill, n)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if tint is not None:
-        _lib.check(_lib.lib().jpeg_amd_resize_colour_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                                  C.byref(spec), h_flip, h_orient,
-                                                                  None if placement is None else C.byref(placement), h_windows,
-                                                                  C.byref(tint), out.data_ptr(), stride),
-                   "jpeg_amd_resize_colour_tensor_batch", ctx.handle)
-        res = _tensor_view(out, n, wt, ht, spec)
-        return res if placement is None else (res, _windows_array(h_windows, n))
-    if placement is not None:
-        _lib.check(_lib.lib().jpeg_amd_resize_placed_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                                  C.byref(spec), h_flip, h_orient, C.byref(placement), h_windows,
-                                                                  out.data_ptr(), stride),
-                   "jpeg_amd_resize_placed_tensor_batch", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec), _windows_array(h_windows, n)
-    if h_orient is None:
-        _lib.check(_lib.lib().jpeg_amd_resize_filter_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                                  C.byref(spec), h_flip, out.data_ptr(), stride),
-                   "jpeg_amd_resize_filter_tensor_batch", ctx.handle)
-    else:
-        _lib.check(_lib.lib().jpeg_amd_resize_oriented_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, wt, ht, code,
-                                                                    C.byref(spec), h_flip, h_orient, out.data_ptr(), stride),
-                   "jpeg_amd_resize_oriented_tensor_batch", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec)
+    rq = _Resample(ctx, len(images), out_size, code).oriented(orientations).placed(place, anchor, fill).coloured(colour, colour_clamp)
+    return _resample_images(images, rq, (spec, flips))
 
 
 def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
@@ -1690,37 +1527,15 @@ def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
     m11, m12), the INVERSE map from the centres of output pixels to source coordinates (affine_matrix makes one from an angle,
     a scale and a shear).  edge: "fill" (a tap outside the image has the `fill` bytes: grid_sample's "zeros") or "replicate"
     (its index is clamped: "border").  Returns uint8 [n, Ht, Wt, 3]."""
-    images = list(images)
-    n = len(images)
-    m, w = _matrices(matrices, n), _warp(edge, fill)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_warp_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt, ht,
-                                              out.data_ptr(), stride), "jpeg_amd_warp_batch", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill)
 
 
 def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
                 colour=None, colour_clamp=None):
-    """warp with the output stage of the tensor calls (jpeg_amd_warp_tensor_batch): the warped image mirrored along x where
-    flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  colour / colour_clamp: as
-    in resize_tensor (jpeg_amd_warp_colour_tensor_batch).  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
-    images = list(images)
-    n = len(images)
-    m, w = _matrices(matrices, n), _warp(edge, fill)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    if tint is not None:
-        _lib.check(_lib.lib().jpeg_amd_warp_colour_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data,
-                                                                C.byref(w), wt, ht, C.byref(spec), h_flip, C.byref(tint),
-                                                                out.data_ptr(), stride),
-                   "jpeg_amd_warp_colour_tensor_batch", ctx.handle)
-        return _tensor_view(out, n, wt, ht, spec)
-    _lib.check(_lib.lib().jpeg_amd_warp_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt,
-                                                     ht, C.byref(spec), h_flip, out.data_ptr(), stride),
-               "jpeg_amd_warp_tensor_batch", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec)
+    """warp with the output stage of the tensor calls (jpeg_amd_warp_colour_tensor_batch): the warped image mirrored along x
+    where flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  colour /
+    colour_clamp: as in resize_tensor.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill, (spec, flips, colour, colour_clamp))
 
 
 def project(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
@@ -1729,31 +1544,14 @@ def project(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0
     coordinates (perspective_matrix makes one from four point pairs).  The denominator m20 x + m21 y + m22 must stay positive
     and within 16 : 1 over the canvas (the library judges it).  With the last row (0, 0, 1) this is warp on the first six
     numbers, bit for bit.  Returns uint8 [n, Ht, Wt, 3]."""
-    images = list(images)
-    n = len(images)
-    m, w = _homographies(matrices, n), _warp(edge, fill)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride = _bytes_out(ctx, n, out_size)
-    _lib.check(_lib.lib().jpeg_amd_project_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w), wt, ht,
-                                                 out.data_ptr(), stride), "jpeg_amd_project_batch", ctx.handle)
-    return out.view(n, ht, wt, 3)
+    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill)
 
 
 def project_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
                    colour=None, colour_clamp=None):
     """project with the output stage of the tensor calls (jpeg_amd_project_tensor_batch): flips, spec, colour and colour_clamp
     as in warp_tensor.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
-    images = list(images)
-    n = len(images)
-    m, w = _homographies(matrices, n), _warp(edge, fill)
-    tint, keep_colour = _colour(colour, colour_clamp, n)
-    src, src_stride, extents = _pack_images(ctx, images)
-    wt, ht, out, stride, h_flip = _tensor_out(ctx, n, out_size, spec, flips)
-    _lib.check(_lib.lib().jpeg_amd_project_tensor_batch(ctx.handle, n, src.data_ptr(), src_stride, extents, m.ctypes.data, C.byref(w),
-                                                        wt, ht, C.byref(spec), h_flip, None if tint is None else C.byref(tint),
-                                                        out.data_ptr(), stride),
-               "jpeg_amd_project_tensor_batch", ctx.handle)
-    return _tensor_view(out, n, wt, ht, spec)
+    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill, (spec, flips, colour, colour_clamp))
 
 
 def tensor_source(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.TensorSource:

@@ -346,7 +346,8 @@ __global__ __launch_bounds__(kGThreads, (generic_waves_per_simd<COUNT>())) void 
                         // value as the truncation of V / (SX SY) + 1/2 (exact as well; the conversion truncates).  Six operations per
                         // pixel and plane where the literal sequence takes fourteen; the pixels at a plane's edge keep the literal one.
                         // (This is arithmetic on exactly representable values, not a proof by exhaustion: it holds for every
-                        // precision up to 16 bits.  tests/soak_generic.py compares with the literal sequence, evaluated on the CPU.)
+                        // precision up to 16 bits.  tests/test_gpu_generic_shapes.py -- collected -- and tests/soak_generic.py compare with
+                        // the literal sequence, evaluated on the CPU.)
                         constexpr float SXW = KIND == 0 ? 4.0f : KIND == 1 ? 2.0f : 1.0f;      // horizontal weights sum to this
                         // vertical: t = clamp(f / c) with c a power of two up to 8 (this path is only taken then): weights f and c - f
                         const float SYW = P.fcy;

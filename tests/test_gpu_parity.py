@@ -150,7 +150,8 @@ def test_staged_decode_unusual_layouts(J, ctx, case, cosite):
     rect = planar.interleaved(cosite=cosite).host_values()
     want = O.interleave(planar_o, factors, layout.scale, size, cosited=cosite)
     assert (rect == want).all(), f"{(rect != want).sum()} samples differ"
-    # the same in one call (jpeg_amd_spectral_rectangular: k_generic_fused where every factor is 1 | 2, staged otherwise)
+    # the same in one call (jpeg_amd_spectral_rectangular: k_generic_fused where every plane is an integer fraction of the scale -- 1, 1/2,
+    # 1/3, 1/4 --, staged otherwise; here on one tile, on several in tests/test_gpu_generic_shapes.py)
     assert (spectral.rectangular(cosite=cosite).host_values() == want).all()
     if precision == 8 and len(comps) in (1, 3):
         for color, unpack in ((J.RGB, O.unpack_rgb8), (J.YCbCr, O.unpack_ycc8)):
@@ -492,7 +493,9 @@ def test_cosited_through_the_fused_entry_point_parity_unpinned_no_reference_gold
 
 
 GENERIC_FUSED = [
-    # (size, precision, factors, cosite): layouts k_generic_fused takes (every factor 1 | 2 under a scale <= 2), sizes of several tiles
+    # (size, precision, factors, cosite): the layouts with every factor 1 | 2 under a scale <= 2 among those k_generic_fused takes, sizes
+    # of several tiles.  (It takes every plane that is an integer fraction of the scale: the layouts with a factor of 3 or 4, on
+    # several tiles as well, are in tests/test_gpu_generic_shapes.py.)
     ((700, 333), 12, [(2, 2), (1, 1), (1, 1)], False),
     ((700, 333), 12, [(2, 2), (1, 1), (1, 1)], True),
     ((513, 129), 12, [(2, 2), (2, 2), (2, 2), (1, 1)], False),     # examples/custom-color/main.swift:150-158: rgba12

@@ -1435,7 +1435,8 @@ int jpeg_amd_warp_view(const jpeg_amd_layout *layout, int orientation, const flo
  * jpeg_amd_decompress_resized_warped_mixed / jpeg_amd_decompress_tensor_warped_mixed: their file front end, as "files to
  * tensors" is of the mixed calls: h_orient as in the *_oriented_mixed file calls (JPEG_AMD_ORIENT_EXIF = the file's own tag),
  * each file's view from jpeg_amd_warp_view; h_info, h_views, h_matrices_out and h_orient_out are written as far as the files
- * were judged.  There are no source rectangles (the matrix says what is read), no placement and no filter but the bilinear. */
+ * were judged.  There are no source rectangles (the matrix says what is read), no placement and no filter but the bilinear
+ * (the projective calls have the bicubic one: "bicubic warp"). */
 int jpeg_amd_decode_warped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
                                  jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
                                  const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
@@ -1648,6 +1649,97 @@ int jpeg_amd_decompress_tensor_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
                                                jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                float *h_matrices_out, int32_t *h_orient_out);
+
+/* ---- bicubic warp: the bicubic filter in the projective calls ----------------------------------------------------------------
+ *
+ * "warped resample" and "projective resample" blend four taps.  These calls take `int filter` behind `warp` (the view:
+ * behind `m`): with JPEG_AMD_FILTER_BILINEAR each is, bit for bit and status for status, the call of "projective resample" it
+ * is named after; with JPEG_AMD_FILTER_BICUBIC the 4 x 4 taps of the Keys cubic with a = -0.5 stand in the blend's place.  It
+ * is the polynomial of "bicubic resample" with the same operation order, over FOUR FIXED taps per axis: NOT widened by the
+ * scale (there is no one scale under a map) and NOT renormalised (the weights sum to 1 up to rounding, and nothing is clipped:
+ * the edge modes supply the taps outside).  This is PIL's BICUBIC kernel as Image.transform / rotate and torchvision's
+ * RandomRotation, RandomAffine and RandomPerspective with interpolation=BICUBIC apply it.  torch's
+ * grid_sample(mode="bicubic") uses a = -0.75 and is a different filter, as "bicubic resample" says of its interpolate.
+ * Only the projective forms take a filter: a last row (0, 0, 1) is the affine warp (below), and one division per pixel is
+ * nothing beside 16 taps -- one entry point, not two.
+ *
+ * THE CONTRACT.  Every statement is ONE binary32 operation and nothing is contracted; xs, xc, yc, nx, ny, nw, rw are those
+ * of "projective resample", then
+ *     sx = nx * rw;   sx = sx - 0.5f;   sx = min(max(sx, -2.0f), (float)w + 1.0f)        (likewise sy with h)
+ *     fx0 = floorf(sx);   x0 = (int)fx0;   fx = sx - fx0                                   (x0 in -2 .. w + 1; likewise y0, fy)
+ *     columns x0 - 1, x0, x0 + 1, x0 + 2 at the distances  fx + 1.0f,  fx,  1.0f - fx,  2.0f - fx
+ *     the weight of a distance x:   x < 1:  ((1.5f * x - 2.5f) * x) * x + 1.0f
+ *                                   x < 2:  ((((x - 5.0f) * x + 8.0f) * x) - 4.0f) * -0.5f
+ *                                   else 0.0f                                  ("bicubic resample"'s two lines, word for word)
+ *     rows y0 - 1 .. y0 + 2 the same with fy
+ *     per row j and channel:  r_j = ((wx0 * t_j0 + wx1 * t_j1) + wx2 * t_j2) + wx3 * t_j3   (a product, then a sum, ascending)
+ *     v = ((wy0 * r_0 + wy1 * r_1) + wy2 * r_2) + wy3 * r_3
+ *     out = (uint8)(int)(min(max(v, 0.0f), 255.0f) + 0.5f)
+ * A tap outside the image is (float)fill[c] under JPEG_AMD_EDGE_FILL; under JPEG_AMD_EDGE_REPLICATE its indices are clamped
+ * into the image -- of the same jpeg_amd_warp.  "tensor output" and the "colour stage" act on this byte.
+ *
+ * THE LIMITS and refusals are those of "projective resample": the source side is at most 2^24, the conditioning of the
+ * denominator is unchanged.  There is no tap limit and no ENOSUP.  Under a map JPEG_AMD_FILTER_ANTIALIAS and every other
+ * value of `filter` is EINVAL -- there is no widening under a map -- judged where the edge mode is judged.
+ *
+ * CONSEQUENCES.
+ *   - Identity.  The identity at out = (w, h) gives the source bytes: sx = x exactly, fx = 0, the weights are exactly
+ *     0, 1, 0, 0 (the cubic is 0 at 1 and at 2) and the sums add zeros.
+ *   - Integer translation.  An integer translation gives the shifted bytes, and the fill or the replicated edge where they
+ *     came from outside.
+ *   - Quarter turn.  (0, 1, 0, -1, 0, h, 0, 0, 1) to (h, w) is the quarter turn, as a permutation of bytes.
+ *   - Far outside under FILL.  A pixel none of whose 16 taps lies inside is the fill byte: the weights' sum differs from 1 by
+ *     a few ulp and the fill is an integer of at most 255, so v rounds to it.  Where the clamp binds, the fraction is 0, the
+ *     weights are exactly 0, 1, 0, 0 and the one tap that counts (column -2 or w + 1, row -2 or h + 1) is outside: the same
+ *     byte.  The kernels load nothing for such pixels.
+ *   - A last row (0, 0, 1): rw = 1 and sx = nx exactly, so the map is the affine one of m[0 .. 5] -- the bicubic affine warp.
+ *   - filter = JPEG_AMD_FILTER_BILINEAR through these entry points is the existing call, bit for bit and status for status;
+ *     the entry points of "projective resample" ARE these with that value. */
+int jpeg_amd_project_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                  const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
+                                  int filter, int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride);
+int jpeg_amd_project_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                         const jpeg_amd_extent *h_extents, const float *h_matrices,
+                                         const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                         const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                         const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+
+/* jpeg_amd_project_view for a filter.  With JPEG_AMD_FILTER_BILINEAR it returns exactly what jpeg_amd_project_view returns.
+ * With JPEG_AMD_FILTER_BICUBIC the footprint's margin (step 4) is one pixel wider on each side, since the taps reach
+ * x0 - 1 .. x0 + 2: the view's columns are clamp(floor(xmin - 0.5) - 2, 0, W' - 1) ..= clamp(floor(xmax - 0.5) + 3, 0, W' - 1),
+ * its rows likewise.  The denominator rule (step 2) and everything else are unchanged, and the one-pixel margin beyond the
+ * taps covers the same rounding.  Any other filter is EINVAL. */
+int jpeg_amd_project_filter_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int filter, int32_t out_w,
+                                 int32_t out_h, jpeg_amd_view *view, float m_view[9]);
+
+/* The decode and file routes, by reference only: each is the *_projected_mixed call of the same place with views from
+ * jpeg_amd_project_filter_view, and image i is, bit for bit, jpeg_amd_project_filter_batch (or the tensor form) applied to the
+ * pixels jpeg_amd_decode_view_batch defines for the view jpeg_amd_project_filter_view returns, with the m_view it returns. */
+int jpeg_amd_decode_projected_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                           const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                           jpeg_amd_view *h_views_out, float *h_matrices_out, uint8_t *d_pixels,
+                                           size_t pixel_stride);
+int jpeg_amd_decode_tensor_projected_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                                  jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                                  const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                                  jpeg_amd_view *h_views_out, float *h_matrices_out,
+                                                  const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride);
+int jpeg_amd_decompress_resized_projected_filter_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                                       int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                                       const uint8_t *h_orient, const float *h_matrices,
+                                                       const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                                       uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
+                                                       jpeg_amd_view *h_views, float *h_matrices_out, int32_t *h_orient_out);
+int jpeg_amd_decompress_tensor_projected_filter_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                                      int n_images, int nthreads, int cosited, jpeg_amd_color color,
+                                                      const uint8_t *h_orient, const float *h_matrices,
+                                                      const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                                      const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                                      const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
+                                                      jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
+                                                      float *h_matrices_out, int32_t *h_orient_out);
 
 #ifdef __cplusplus
 }

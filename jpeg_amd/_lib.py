@@ -207,6 +207,19 @@ SIGNATURES = {
                                                               C.c_int32, _p, C.c_size_t, _p, _p, _p, _p]),
     "jpeg_amd_decompress_tensor_projected_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int32,
                                                              C.c_int32, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, _p]),
+    # "bicubic warp": the projective calls with `int filter` behind the warp (the view: behind the matrix)
+    "jpeg_amd_project_filter_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, _p, _p, C.c_int, C.c_int32, C.c_int32, _p, C.c_size_t]),
+    "jpeg_amd_project_filter_tensor_batch": (C.c_int, [_p, C.c_int, _p, C.c_size_t, _p, _p, _p, C.c_int, C.c_int32, C.c_int32, _p, _p,
+                                                       _p, _p, C.c_size_t]),
+    "jpeg_amd_project_filter_view": (C.c_int, [_L, C.c_int, _p, C.c_int, C.c_int32, C.c_int32, _p, _p]),
+    "jpeg_amd_decode_projected_filter_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int, C.c_int32, C.c_int32,
+                                                         _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decode_tensor_projected_filter_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int, C.c_int32,
+                                                                C.c_int32, _p, _p, _p, _p, _p, _p, C.c_size_t]),
+    "jpeg_amd_decompress_resized_projected_filter_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int,
+                                                                     C.c_int32, C.c_int32, _p, C.c_size_t, _p, _p, _p, _p]),
+    "jpeg_amd_decompress_tensor_projected_filter_mixed": (C.c_int, [_p, _pp, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int,
+                                                                    C.c_int32, C.c_int32, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, _p]),
     "jpeg_amd_warp_view": (C.c_int, [_L, C.c_int, _p, C.c_int32, C.c_int32, _p, _p]),
     "jpeg_amd_decode_warped_mixed": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p,
                                                C.c_size_t]),

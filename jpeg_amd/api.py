@@ -632,15 +632,29 @@ def _matrices(matrices, n: int, k: int = 6) -> np.ndarray:
     return m
 
 
-def _map_view(k: int, size, layout: "Layout", matrix, out_size, orientation: int):
-    """warp_view (k = 6) and project_view (k = 9)."""
-    name = "jpeg_amd_project_view" if k == 9 else "jpeg_amd_warp_view"
+def _pad_affine(m: np.ndarray) -> np.ndarray:
+    """[n, 6] affine matrices as [n, 9] homographies with the last row (0, 0, 1): the same map ("bicubic warp")."""
+    return np.ascontiguousarray(np.concatenate([m, np.tile(np.array([0.0, 0.0, 1.0], np.float32), (m.shape[0], 1))], axis=1))
+
+
+def _map_view(k: int, size, layout: "Layout", matrix, out_size, orientation: int, filter: str = "bilinear"):
+    """warp_view (k = 6) and project_view (k = 9); with the bicubic filter both through jpeg_amd_project_filter_view."""
+    code = _map_filter(filter)
     m = _matrices(matrix, 1, k)
     v = _lib.View()
-    mv = np.zeros(k, np.float32)
     L = layout.c_layout(size)
-    _lib.check(getattr(_lib.lib(), name)(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]), C.byref(v),
-                                         mv.ctypes.data), name)
+    if code == _lib.FILTER_BILINEAR:
+        name = "jpeg_amd_project_view" if k == 9 else "jpeg_amd_warp_view"
+        mv = np.zeros(k, np.float32)
+        _lib.check(getattr(_lib.lib(), name)(C.byref(L), int(orientation), m.ctypes.data, int(out_size[0]), int(out_size[1]), C.byref(v),
+                                             mv.ctypes.data), name)
+    else:
+        name = "jpeg_amd_project_filter_view"
+        m = m if k == 9 else _pad_affine(m)
+        mv = np.zeros(9, np.float32)
+        _lib.check(getattr(_lib.lib(), name)(C.byref(L), int(orientation), m.ctypes.data, code, int(out_size[0]), int(out_size[1]),
+                                             C.byref(v), mv.ctypes.data), name)
+        mv = mv[:k].copy()
     return (v.denom, v.region.x, v.region.y, v.region.width, v.region.height), mv
 
 
@@ -680,11 +694,13 @@ def affine_matrix(src_size, out_size, angle: float = 0.0, scale: float = 1.0, sh
     return np.array([v + 0.0 for v in m], np.float64).astype(np.float32)
 
 
-def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
+def warp_view(size, layout: "Layout", matrix, out_size, orientation: int = 1, filter: str = "bilinear"):
     """The view that a warp of an image of `size` (w, h) and `layout` reads, and the matrix against it (jpeg_amd_warp_view):
     `matrix` (6 values) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT image, the stored image seen through
-    `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [6])."""
-    return _map_view(6, size, layout, matrix, out_size, orientation)
+    `orientation` 1 .. 8.  filter: "bilinear", or "bicubic" for the view of warp(filter="bicubic"), one pixel wider on each
+    side (jpeg_amd_project_filter_view on the matrix with the last row (0, 0, 1)).
+    Returns ((denom, x, y, width, height), float32 [6])."""
+    return _map_view(6, size, layout, matrix, out_size, orientation, filter)
 
 
 def perspective_matrix(src_points, out_points) -> np.ndarray:
@@ -727,11 +743,12 @@ def perspective_matrix(src_points, out_points) -> np.ndarray:
     return np.append(h, 1.0).reshape(3, 3)
 
 
-def project_view(size, layout: "Layout", matrix, out_size, orientation: int = 1):
+def project_view(size, layout: "Layout", matrix, out_size, orientation: int = 1, filter: str = "bilinear"):
     """The view that a projective map of an image of `size` (w, h) and `layout` reads, and the matrix against it
     (jpeg_amd_project_view): `matrix` (9 values, or [3, 3]) maps the centres of the out_size (Wt, Ht) canvas into the UPRIGHT
-    image, the stored image seen through `orientation` 1 .. 8.  Returns ((denom, x, y, width, height), float32 [9])."""
-    return _map_view(9, size, layout, matrix, out_size, orientation)
+    image, the stored image seen through `orientation` 1 .. 8.  filter: as in warp_view (jpeg_amd_project_filter_view).
+    Returns ((denom, x, y, width, height), float32 [9])."""
+    return _map_view(9, size, layout, matrix, out_size, orientation, filter)
 
 
 _GREY = (0.2989, 0.587, 0.114)                     # torchvision's rgb_to_grayscale
@@ -1027,6 +1044,14 @@ def _filter(filter) -> int:
     return codes[filter]
 
 
+def _map_filter(filter) -> int:
+    """filter="bilinear" | "bicubic" of the calls through a map ("bicubic warp": nothing is widened under a map, so no "antialias")."""
+    codes = {"bilinear": _lib.FILTER_BILINEAR, "bicubic": _lib.FILTER_BICUBIC}
+    if filter not in codes:
+        raise ValueError("filter: 'bilinear' or 'bicubic' (a map has no 'antialias')")
+    return codes[filter]
+
+
 def _view_batch_args(ctx: Context, size, layout: Layout, planes, quanta, views, q):
     """The arguments decode_views, decode_resized and decode_tensors share: (vs [n, 5], head and keep of _batch_args, c views)."""
     vs, h_views = _views(views)
@@ -1145,6 +1170,7 @@ class _Resample:
 
     def __init__(self, ctx: Context, n: int, out_size, code: int = _lib.FILTER_BILINEAR):
         self.ctx, self.n, self.out_size, self.code, self.k = ctx, n, out_size, code, 0   # k: the numbers of a matrix; 0: no map
+        self.map_code, self.k_given = _lib.FILTER_BILINEAR, 0   # the filter of a map, and the numbers of a matrix as the caller gave it
         self.h_orient = self.placement = self.h_windows = self.tint = self.spec = self.h_flip = None
 
     def oriented(self, orientations, exif: bool = False):
@@ -1155,13 +1181,23 @@ class _Resample:
         self.placement, self.h_windows, self._keep_windows = _placement(place, anchor, fill, self.n)
         return self
 
-    def mapped(self, matrices, k: int, edge, fill, orientations=None):
-        """k = 6: the affine map, 9: the homography.  The mixed calls judge their orientations behind the matrices."""
-        self.k, self.m, self.m_out = k, _matrices(matrices, self.n, k), np.zeros((self.n, k), np.float32)
+    def mapped(self, matrices, k: int, edge, fill, orientations=None, filter: str = "bilinear"):
+        """k = 6: the affine map, 9: the homography.  The mixed calls judge their orientations behind the matrices.  filter:
+        "bilinear", or "bicubic" ("bicubic warp"), which the projective calls alone carry: an affine map goes as the
+        homography with the last row (0, 0, 1), and the matrices that come back are [n, 6] again (matrices_out)."""
+        self.map_code = _map_filter(filter)
+        self.k_given, m = k, _matrices(matrices, self.n, k)
+        if self.map_code != _lib.FILTER_BILINEAR and k == 6:
+            k, m = 9, _pad_affine(m)
+        self.k, self.m, self.m_out = k, m, np.zeros((self.n, k), np.float32)
         if orientations is not None:
             self.oriented(orientations)
         self.warp = _warp(edge, fill)
         return self
+
+    def matrices_out(self) -> np.ndarray:
+        """The matrices a mixed or file call applied to its views, in the caller's form."""
+        return self.m_out if self.k_given == self.k else np.ascontiguousarray(self.m_out[:, :self.k_given])
 
     def coloured(self, colour, colour_clamp):
         self.tint, self._keep_colour = _colour(colour, colour_clamp, self.n)
@@ -1190,11 +1226,14 @@ class _Resample:
         target = () if self.spec is None else (C.byref(self.spec), self.h_flip)
         colour = () if self.spec is None else (None if self.tint is None else C.byref(self.tint),)
         if self.k:
-            args = lead + (self.m.ctypes.data, C.byref(self.warp), self.wt, self.ht) + target + written + colour
+            code = () if self.map_code == _lib.FILTER_BILINEAR else (self.map_code,)   # (the *_filter_* forms: behind the warp)
+            args = lead + (self.m.ctypes.data, C.byref(self.warp)) + code + (self.wt, self.ht) + target + written + colour
         else:                                                # (the uniform batch has no columns)
             place = None if self.placement is None else C.byref(self.placement)
             args = lead + (self.wt, self.ht, self.code) + target + ((self.h_orient, place, self.h_windows) + colour if columns else ())
         name = cells[self.k, self.spec is not None]
+        if self.k and self.map_code != _lib.FILTER_BILINEAR:
+            name = _FILTER_CELLS[name]
         _lib.check(getattr(_lib.lib(), name)(self.ctx.handle, *head, *args, self.out.data_ptr(), self.stride, *outputs), name,
                    self.ctx.handle)
 
@@ -1220,6 +1259,15 @@ _FILE_CELLS = {(0, False): "jpeg_amd_decompress_resized_placed_mixed", (0, True)
                (9, False): "jpeg_amd_decompress_resized_projected_mixed", (9, True): "jpeg_amd_decompress_tensor_projected_mixed"}
 
 
+# ... and of the projective cells the form with a filter ("bicubic warp"), which a map with another filter than the bilinear takes.
+_FILTER_CELLS = {"jpeg_amd_project_batch": "jpeg_amd_project_filter_batch",
+                 "jpeg_amd_project_tensor_batch": "jpeg_amd_project_filter_tensor_batch",
+                 "jpeg_amd_decode_projected_mixed": "jpeg_amd_decode_projected_filter_mixed",
+                 "jpeg_amd_decode_tensor_projected_mixed": "jpeg_amd_decode_tensor_projected_filter_mixed",
+                 "jpeg_amd_decompress_resized_projected_mixed": "jpeg_amd_decompress_resized_projected_filter_mixed",
+                 "jpeg_amd_decompress_tensor_projected_mixed": "jpeg_amd_decompress_tensor_projected_filter_mixed"}
+
+
 def _resample_batch(source, color, cosite: bool, rq: _Resample):
     """The route of the uniform batch; source: what _view_batch_args returns."""
     vs, head, keep, h_views = source
@@ -1239,7 +1287,7 @@ def _resample_mixed(source, color, cosite: bool, rq: _Resample):
     vs, h_images, h_views, keep = source
     lead, written = ((rq.h_orient,), (h_views, rq.m_out.ctypes.data)) if rq.k else ((h_views,), ())
     rq.call(_MIXED_CELLS, (rq.n, h_images, 1 if cosite else 0, color.code), lead, written)
-    return rq.result(_views_array(h_views, rq.n), rq.m_out) if rq.k else rq.result()
+    return rq.result(_views_array(h_views, rq.n), rq.matrices_out()) if rq.k else rq.result()
 
 
 def _resample_files(source, threads: int, color, cosite: bool, rq: _Resample):
@@ -1370,12 +1418,13 @@ def decode_crops_tensor_mixed(ctx: Context, spectrals, source_regions, out_size,
     return (res, views) if windows is None else (res[0], views, res[1])
 
 
-def _resample_mapped(ctx: Context, sources, matrices, k: int, out_size, edge, fill, tensor=None, mixed=None):
+def _resample_mapped(ctx: Context, sources, matrices, k: int, out_size, edge, fill, tensor=None, mixed=None, filter: str = "bilinear"):
     """The warp (k = 6) and project (k = 9) calls of device images, or with mixed = (color, cosite, orientations) of Spectral
-    images.  tensor: None for bytes, or the (spec, flips, colour, colour_clamp) of the tensor forms."""
+    images.  tensor: None for bytes, or the (spec, flips, colour, colour_clamp) of the tensor forms.  filter: of the map."""
+    _map_filter(filter)
     sources = list(sources)
     source = mixed and _mixed_args(ctx, sources, np.zeros((len(sources), 5), np.int32))   # (placeholder views: the call writes them)
-    rq = _Resample(ctx, len(sources), out_size).mapped(matrices, k, edge, fill, mixed and mixed[2])
+    rq = _Resample(ctx, len(sources), out_size).mapped(matrices, k, edge, fill, mixed and mixed[2], filter)
     if tensor:
         rq.coloured(*tensor[2:])
     if not mixed:
@@ -1384,42 +1433,45 @@ def _resample_mapped(ctx: Context, sources, matrices, k: int, out_size, edge, fi
 
 
 def decode_warped_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
-                        edge="fill", fill=(0, 0, 0)):
+                        edge="fill", fill=(0, 0, 0), filter: str = "bilinear"):
     """The warp from Spectral images of different sizes and layouts in one call (jpeg_amd_decode_warped_mixed; include/jpeg_amd.h,
     "warped resample"): per image a matrix [6] in the coordinates of its UPRIGHT full-size image (the stored image seen through
     orientations[i], 1 .. 8; None: as stored).  warp_view chooses each image's denominator and view -- only the part the canvas
     maps into is decoded -- and image i is warp() of decode_views_mixed's pixels for that view with the matrix against it.
+    filter: "bilinear" or "bicubic", as in warp; the views are warp_view's with that filter.
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 6])."""
-    return _resample_mapped(ctx, spectrals, matrices, 6, out_size, edge, fill, None, (color, cosite, orientations))
+    return _resample_mapped(ctx, spectrals, matrices, 6, out_size, edge, fill, None, (color, cosite, orientations), filter)
 
 
 def decode_tensors_warped_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
-                                cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None, colour_clamp=None):
+                                cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None, colour_clamp=None,
+                                filter: str = "bilinear"):
     """decode_warped_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_warped_colour_mixed); flips, spec,
-    colour and colour_clamp as in warp_tensor.
+    colour and colour_clamp as in warp_tensor, filter as in decode_warped_mixed.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 6])."""
     return _resample_mapped(ctx, spectrals, matrices, 6, out_size, edge, fill, (spec, flips, colour, colour_clamp),
-                            (color, cosite, orientations))
+                            (color, cosite, orientations), filter)
 
 
 def decode_projected_mixed(ctx: Context, spectrals, matrices, out_size, color=RGB, cosite: bool = False, orientations=None,
-                           edge="fill", fill=(0, 0, 0)):
+                           edge="fill", fill=(0, 0, 0), filter: str = "bilinear"):
     """decode_warped_mixed through a 3 x 3 homography per image (jpeg_amd_decode_projected_mixed; include/jpeg_amd.h,
     "projective resample"): matrices [n, 9] or [n, 3, 3] in the coordinates of the UPRIGHT full-size images (perspective_matrix
     makes one from four point pairs).  project_view chooses each image's denominator and view, and image i is project() of
-    decode_views_mixed's pixels for that view with the matrix against it.
+    decode_views_mixed's pixels for that view with the matrix against it.  filter: "bilinear" or "bicubic", as in project
+    (jpeg_amd_decode_projected_filter_mixed; the views are project_view's with that filter).
     Returns (uint8 [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices applied to them as float32 [n, 9])."""
-    return _resample_mapped(ctx, spectrals, matrices, 9, out_size, edge, fill, None, (color, cosite, orientations))
+    return _resample_mapped(ctx, spectrals, matrices, 9, out_size, edge, fill, None, (color, cosite, orientations), filter)
 
 
 def decode_tensors_projected_mixed(ctx: Context, spectrals, matrices, out_size, spec: _lib.TensorSpec, flips=None, color=RGB,
                                    cosite: bool = False, orientations=None, edge="fill", fill=(0, 0, 0), colour=None,
-                                   colour_clamp=None):
+                                   colour_clamp=None, filter: str = "bilinear"):
     """decode_projected_mixed with the output stage of the tensor calls (jpeg_amd_decode_tensor_projected_mixed); flips, spec,
-    colour and colour_clamp as in project_tensor.
+    colour and colour_clamp as in project_tensor, filter as in decode_projected_mixed.
     Returns (tensor [n, 3, Ht, Wt] or [n, Ht, Wt, 3], the views as int32 [n, 5], the matrices as float32 [n, 9])."""
     return _resample_mapped(ctx, spectrals, matrices, 9, out_size, edge, fill, (spec, flips, colour, colour_clamp),
-                            (color, cosite, orientations))
+                            (color, cosite, orientations), filter)
 
 
 def _file_args(sources, source_regions):
@@ -1440,14 +1492,17 @@ def _file_args(sources, source_regions):
     return n, ptrs, sizes, regions, (_lib.FrameInfo * max(n, 1))(), (_lib.View * max(n, 1))(), files
 
 
-def _file_columns(rq: _Resample, warp, edge, source_regions, place, anchor, fill) -> _Resample:
-    """warp=, edge=, fill= of the file calls, or without a warp their place=, anchor=, fill=."""
+def _file_columns(rq: _Resample, warp, edge, source_regions, place, anchor, fill, warp_filter=None) -> _Resample:
+    """warp=, edge=, fill=, warp_filter= of the file calls, or without a warp their place=, anchor=, fill=."""
     if warp is None:
+        if warp_filter is not None:
+            raise ValueError("warp_filter: only together with warp")
         return rq.placed(place, anchor, fill)
     if source_regions is not None or place is not None or rq.code != _lib.FILTER_BILINEAR:
         raise ValueError('warp: not together with source_regions, place or a filter other than "bilinear"')
     shape = np.shape(warp)                                   # [n, 9] or [n, 3, 3]: the homography; else the affine map [n, 6]
-    return rq.mapped(warp, 9 if shape[-1:] == (9,) or shape[-2:] == (3, 3) else 6, edge, fill)
+    return rq.mapped(warp, 9 if shape[-1:] == (9,) or shape[-2:] == (3, 3) else 6, edge, fill,
+                     filter="bilinear" if warp_filter is None else warp_filter)
 
 
 def _views_array(h_views, n) -> np.ndarray:
@@ -1456,7 +1511,7 @@ def _views_array(h_views, n) -> np.ndarray:
 
 def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, source_regions=None, flips=None, color=RGB,
                        cosite: bool = False, filter: str = "bilinear", threads: int = 0, orientation=None, place=None,
-                       anchor="centre", fill=(0, 0, 0), warp=None, edge="fill", colour=None, colour_clamp=None):
+                       anchor="centre", fill=(0, 0, 0), warp=None, edge="fill", colour=None, colour_clamp=None, warp_filter=None):
     """The data-loader call from FILES: n JPEG files (paths or bytes) of any mix of sizes, of 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, grey
     and progressive, to one normalised tensor in one call (jpeg_amd_decompress_tensor_colour_mixed, with `warp`
     jpeg_amd_decompress_tensor_warped_colour_mixed or jpeg_amd_decompress_tensor_projected_mixed; include/jpeg_amd.h, "files to
@@ -1478,32 +1533,35 @@ def decompress_tensors(ctx: Context, sources, out_size, spec: _lib.TensorSpec, s
     ("warped resample" there); not together with source_regions, place or a filter other than "bilinear" (ValueError).  The
     views that come back are warp_view's, and the matrices applied to them come back as the last item, float32 [n, 6].  A warp
     of [n, 9] or [n, 3, 3] is a homography per file ("projective resample"): the views are project_view's and the matrices that
-    come back float32 [n, 9].
+    come back float32 [n, 9].  warp_filter: the filter of the warp, "bilinear" (None) or "bicubic" as in warp ("bicubic warp";
+    the views are then one pixel wider on each side); only together with `warp` (ValueError).  `filter` is the resize's and
+    stays "bilinear" with a warp.
     colour / colour_clamp: as in resize_tensor, per file; what comes back is what the call without them returns."""
     code = _filter(filter)
     source = _file_args(sources, source_regions)
     n, infos, h_views = source[0], source[4], source[5]
     rq = _Resample(ctx, n, out_size, code).oriented(orientation, exif=True).coloured(colour, colour_clamp)
-    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill).target((spec, flips))
+    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill, warp_filter).target((spec, flips))
     applied = _resample_files(source, threads, color, cosite, rq)
     written = (_views_array(h_views, n), list(infos[:n])) + (() if rq.h_orient is None else (applied,))
-    return rq.result(*written, *((rq.m_out,) if rq.k else ()))
+    return rq.result(*written, *((rq.matrices_out(),) if rq.k else ()))
 
 
 def decompress_resized(ctx: Context, sources, out_size, source_regions=None, color=RGB, cosite: bool = False,
                        filter: str = "bilinear", threads: int = 0, orientation=None, place=None, anchor="centre", fill=(0, 0, 0),
-                       warp=None, edge="fill"):
+                       warp=None, edge="fill", warp_filter=None):
     """decompress_tensors without the tensor stage (jpeg_amd_decompress_resized_placed_mixed, with `warp`
     jpeg_amd_decompress_resized_warped_mixed or jpeg_amd_decompress_resized_projected_mixed): the files' views resampled to
     out_size (Wt, Ht) as bytes by `filter`; `orientation` as there.  place / anchor / fill: as there, the windows as a second
     item.  warp / edge / fill: as there; with it the views (int32 [n, 5]) and the matrices applied to them (float32 [n, 6]; of a
-    [n, 9] or [n, 3, 3] warp [n, 9]) come back as the last two items.  Returns one uint8 tensor [n, Ht, Wt, 3]."""
+    [n, 9] or [n, 3, 3] warp [n, 9]) come back as the last two items; warp_filter: as there.
+    Returns one uint8 tensor [n, Ht, Wt, 3]."""
     code = _filter(filter)
     source = _file_args(sources, source_regions)
     rq = _Resample(ctx, source[0], out_size, code).oriented(orientation, exif=True)
-    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill).target()
+    rq = _file_columns(rq, warp, edge, source_regions, place, anchor, fill, warp_filter).target()
     _resample_files(source, threads, color, cosite, rq)
-    return rq.result(_views_array(source[5], rq.n), rq.m_out) if rq.k else rq.result()
+    return rq.result(_views_array(source[5], rq.n), rq.matrices_out()) if rq.k else rq.result()
 
 
 def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=None, filter: str = "bilinear", orientations=None,
@@ -1521,37 +1579,40 @@ def resize_tensor(ctx: Context, images, out_size, spec: _lib.TensorSpec, flips=N
     return _resample_images(images, rq, (spec, flips))
 
 
-def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
+def warp(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0), filter: str = "bilinear"):
     """n device uint8 images [h_i, w_i, 3] of any sizes through an affine map each, to out_size (Wt, Ht), in one launch
     (jpeg_amd_warp_batch; include/jpeg_amd.h, "warped resample", holds the contract).  matrices: [n, 6] of (m00, m01, m02, m10,
     m11, m12), the INVERSE map from the centres of output pixels to source coordinates (affine_matrix makes one from an angle,
     a scale and a shear).  edge: "fill" (a tap outside the image has the `fill` bytes: grid_sample's "zeros") or "replicate"
-    (its index is clamped: "border").  Returns uint8 [n, Ht, Wt, 3]."""
-    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill)
+    (its index is clamped: "border").  filter: "bilinear", or "bicubic" (include/jpeg_amd.h, "bicubic warp": 4 x 4 fixed taps
+    of the Keys cubic with a = -0.5, PIL's BICUBIC under a rotation; through jpeg_amd_project_filter_batch with the last row
+    (0, 0, 1)); "antialias" is a ValueError: nothing is widened under a map.  Returns uint8 [n, Ht, Wt, 3]."""
+    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill, filter=filter)
 
 
 def warp_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
-                colour=None, colour_clamp=None):
+                colour=None, colour_clamp=None, filter: str = "bilinear"):
     """warp with the output stage of the tensor calls (jpeg_amd_warp_colour_tensor_batch): the warped image mirrored along x
     where flips[i] is set, normalised by `spec` (fill pixels included) and stored in its dtype and layout.  colour /
-    colour_clamp: as in resize_tensor.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
-    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill, (spec, flips, colour, colour_clamp))
+    colour_clamp: as in resize_tensor; filter: as in warp.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    return _resample_mapped(ctx, images, matrices, 6, out_size, edge, fill, (spec, flips, colour, colour_clamp), filter=filter)
 
 
-def project(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0)):
+def project(ctx: Context, images, matrices, out_size, edge="fill", fill=(0, 0, 0), filter: str = "bilinear"):
     """warp through a 3 x 3 homography per image (jpeg_amd_project_batch; include/jpeg_amd.h, "projective resample", holds the
     contract): matrices [n, 9] or [n, 3, 3], row by row, the INVERSE projective map from the centres of output pixels to source
     coordinates (perspective_matrix makes one from four point pairs).  The denominator m20 x + m21 y + m22 must stay positive
     and within 16 : 1 over the canvas (the library judges it).  With the last row (0, 0, 1) this is warp on the first six
-    numbers, bit for bit.  Returns uint8 [n, Ht, Wt, 3]."""
-    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill)
+    numbers, bit for bit.  filter: "bilinear" or "bicubic", as in warp (jpeg_amd_project_filter_batch).
+    Returns uint8 [n, Ht, Wt, 3]."""
+    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill, filter=filter)
 
 
 def project_tensor(ctx: Context, images, matrices, out_size, spec: _lib.TensorSpec, flips=None, edge="fill", fill=(0, 0, 0),
-                   colour=None, colour_clamp=None):
+                   colour=None, colour_clamp=None, filter: str = "bilinear"):
     """project with the output stage of the tensor calls (jpeg_amd_project_tensor_batch): flips, spec, colour and colour_clamp
-    as in warp_tensor.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
-    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill, (spec, flips, colour, colour_clamp))
+    as in warp_tensor, filter as in project.  Returns one tensor [n, 3, Ht, Wt] ("chw") or [n, Ht, Wt, 3] ("hwc")."""
+    return _resample_mapped(ctx, images, matrices, 9, out_size, edge, fill, (spec, flips, colour, colour_clamp), filter=filter)
 
 
 def tensor_source(mean=None, std=None, dtype=None, layout: str = "chw") -> _lib.TensorSource:

@@ -200,10 +200,9 @@ int decompress_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const siz
             }
             if (st == JPEG_AMD_OK && mapped) {
                 // the matrix says what is read -- the view and the matrix against it are jpeg_amd_warp_view's, or
-                // ("projective resample") jpeg_amd_project_view's, nine numbers each
+                // ("projective resample", "bicubic warp") jpeg_amd_project_filter_view's at the request's filter, nine numbers each
                 if (out.h_orient_out) out.h_orient_out[i] = o;
-                const auto view_of = rq.map == ResampleMap::Projective ? jpeg_amd_project_view : jpeg_amd_warp_view;
-                st = view_of(&f.layout, o, rq.h_matrices + k * (size_t)i, out_w, out_h, &f.view, &d.matrices[k * (size_t)i]);
+                st = map_view(rq, &f.layout, o, rq.h_matrices + k * (size_t)i, &f.view, &d.matrices[k * (size_t)i]);
                 if (st == JPEG_AMD_OK && out.h_matrices_out)
                     std::memcpy(out.h_matrices_out + k * (size_t)i, &d.matrices[k * (size_t)i], k * sizeof(float));
             } else if (st == JPEG_AMD_OK) {
@@ -440,17 +439,29 @@ try {
 }
 JA_NOTHROW_TAIL
 
-// The two file calls through a homography ("projective resample"): each file's view and matrix from jpeg_amd_project_view in
-// pass 0; the tensor form with the "colour stage", or colour == nullptr for none.
+// The two file calls through a homography ("projective resample", "bicubic warp"): each file's view and matrix from
+// jpeg_amd_project_filter_view in pass 0; the tensor form with the "colour stage", or colour == nullptr for none.  The forms
+// without a filter argument are these with JPEG_AMD_FILTER_BILINEAR.
 int jpeg_amd_decompress_resized_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
                                                 int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
                                                 const float *h_matrices, const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
                                                 uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
                                                 jpeg_amd_view *h_views, float *h_matrices_out, int32_t *h_orient_out)
+{
+    return jpeg_amd_decompress_resized_projected_filter_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_orient, h_matrices, warp,
+                                                              JPEG_AMD_FILTER_BILINEAR, out_w, out_h, d_pixels, pixel_stride, h_info, h_views,
+                                                              h_matrices_out, h_orient_out);
+}
+
+int jpeg_amd_decompress_resized_projected_filter_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                                       int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                                       const float *h_matrices, const jpeg_amd_warp *warp, int filter, int32_t out_w,
+                                                       int32_t out_h, uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *h_info,
+                                                       jpeg_amd_view *h_views, float *h_matrices_out, int32_t *h_orient_out)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
                             ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
-                                .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
+                                .through(filter).oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
                             FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL
@@ -461,10 +472,23 @@ int jpeg_amd_decompress_tensor_projected_mixed(jpeg_amd_ctx *ctx, const uint8_t 
                                                const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, const jpeg_amd_colour *colour,
                                                void *d_dst, size_t dst_stride, jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views,
                                                float *h_matrices_out, int32_t *h_orient_out)
+{
+    return jpeg_amd_decompress_tensor_projected_filter_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_orient, h_matrices, warp,
+                                                             JPEG_AMD_FILTER_BILINEAR, out_w, out_h, spec, h_flip, colour, d_dst, dst_stride,
+                                                             h_info, h_views, h_matrices_out, h_orient_out);
+}
+
+int jpeg_amd_decompress_tensor_projected_filter_mixed(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images,
+                                                      int nthreads, int cosited, jpeg_amd_color color, const uint8_t *h_orient,
+                                                      const float *h_matrices, const jpeg_amd_warp *warp, int filter, int32_t out_w,
+                                                      int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                                      const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride,
+                                                      jpeg_amd_frame_info *h_info, jpeg_amd_view *h_views, float *h_matrices_out,
+                                                      int32_t *h_orient_out)
 try {
     return decompress_mixed(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr,
                             ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
-                                .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
+                                .through(filter).oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
                             FileOutputs{h_info, h_views, h_orient_out, h_matrices_out});
 }
 JA_NOTHROW_TAIL

@@ -523,8 +523,9 @@ int check_tensor_target(int n_images, int32_t out_w, int32_t out_h, const jpeg_a
 //             (behind its orientation), every record is the placed one of its filter, its scale factors the window's, and ONE
 //             launch of the placed kernels takes them all.  Also ("colour stage") a colour without a placement: its window is
 //             the whole canvas, which "placed resample" makes the oriented and the stored call bit for bit;
-//   Warped, Projected  ("warped resample", "projective resample") a map: bilinear, no orientations, no placement; window(i)
-//             judges image i's matrix, record(i) writes the WarpRecord or the ProjectRecord.
+//   Warped, Projected  ("warped resample", "projective resample") a map: bilinear, or ("bicubic warp") the bicubic filter with
+//             a projective map; no orientations, no placement; window(i) judges image i's matrix, record(i) writes the
+//             WarpRecord or the ProjectRecord -- the same one for either filter.
 // With a colour, check() judges it with the target (a byte target has no colour stage), and the ColourRecords go up behind the
 // call's resample records, 16-byte aligned, in the same copy.
 struct ResampleTarget : ResampleRequest {
@@ -546,13 +547,15 @@ struct ResampleTarget : ResampleRequest {
                : place || colour              ? ResampleRecords::Placed
                : turned                       ? ResampleRecords::Oriented
                                               : ResampleRecords::Stored;
-        if (filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
+        if (!has_map() && filter != JPEG_AMD_FILTER_BILINEAR && !antialias()) return JPEG_AMD_EINVAL;
         size_t elem_bytes = 1;
         JA_TRY(tensor ? check_tensor_target(n_images, out_w, out_h, spec, d_dst, stride, &elem_bytes)
                       : check_resize_target(n_images, out_w, out_h, d_dst, stride));
         if (colour) JA_TRY(tensor ? check_colour(*colour, n_images) : JPEG_AMD_EINVAL);
         if (has_map()) {
-            if (filter != JPEG_AMD_FILTER_BILINEAR || h_orient || place || !warp) return JPEG_AMD_EINVAL;
+            // the filter of a map is judged here, with the edge mode: nothing is widened under a map, so no antialiasing
+            const bool filtered = filter == JPEG_AMD_FILTER_BILINEAR || (bicubic() && map == ResampleMap::Projective);
+            if (!filtered || h_orient || place || !warp) return JPEG_AMD_EINVAL;
             if (warp->edge != JPEG_AMD_EDGE_FILL && warp->edge != JPEG_AMD_EDGE_REPLICATE) return JPEG_AMD_EINVAL;
             return n_images > 0 && !h_matrices ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
         }
@@ -1196,13 +1199,19 @@ int map_denom(double step2)
 }
 
 // The rectangle of the scaled image S that holds the taps of a canvas whose footprint spans lo[a] .. hi[a] on axis a, clamped.
-jpeg_amd_region footprint_view(const double lo[2], const double hi[2], const jpeg_amd_layout &S)
+// wider: the pixels that the filter's taps reach beyond the two-tap filter's on each side ("bicubic warp": 1).
+jpeg_amd_region footprint_view(const double lo[2], const double hi[2], const jpeg_amd_layout &S, int wider = 0)
 {
     const auto clamp = [](double v, double last) { return (int32_t)std::min(std::max(v, 0.0), last); };
-    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - 1.0, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + 2.0, S.width - 1);
-    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - 1.0, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + 2.0, S.height - 1);
+    const double before = 1.0 + (double)wider, after = 2.0 + (double)wider;
+    const int32_t x0 = clamp(std::floor(lo[0] - 0.5) - before, S.width - 1), x1 = clamp(std::floor(hi[0] - 0.5) + after, S.width - 1);
+    const int32_t y0 = clamp(std::floor(lo[1] - 0.5) - before, S.height - 1), y1 = clamp(std::floor(hi[1] - 0.5) + after, S.height - 1);
     return jpeg_amd_region{x0, y0, x1 - x0 + 1, y1 - y0 + 1};
 }
+
+// jpeg_amd_project_filter_view behind the verdict on its filter: `wider` as footprint_view's.
+int project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h, int wider,
+                 jpeg_amd_view *view, float m_view[9]);
 
 }  // namespace
 
@@ -1274,20 +1283,18 @@ JA_NOTHROW_TAIL
 namespace {
 
 // The mixed calls through a map (jpeg_amd_decode_warped_mixed, jpeg_amd_decode_projected_mixed, their tensor forms): rq carries
-// the caller's matrices against the upright images and the orientations; every image's view and m_view from jpeg_amd_warp_view
-// or jpeg_amd_project_view, which take the orientation into the matrix, then the route of the mixed calls with those.
+// the caller's matrices against the upright images and the orientations; every image's view and m_view from map_view, which
+// takes the orientation into the matrix, then the route of the mixed calls with those.
 int mapped_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited, jpeg_amd_color color,
                  const ResampleRequest &rq, jpeg_amd_view *h_views_out, float *h_matrices_out)
 {
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images > 0 && (!h_images || !rq.h_matrices)) return JPEG_AMD_EINVAL;
     const size_t n = (size_t)n_images, k = rq.matrix_floats();
-    const auto view_of = rq.map == ResampleMap::Projective ? jpeg_amd_project_view : jpeg_amd_warp_view;
     std::vector<jpeg_amd_view> views(n);
     std::vector<float> view_matrices(k * n);
     for (size_t i = 0; i < n; ++i) {
-        JA_TRY(view_of(&h_images[i].layout, rq.h_orient ? rq.h_orient[i] : 1, rq.h_matrices + k * i, rq.out_w, rq.out_h, &views[i],
-                       &view_matrices[k * i]));
+        JA_TRY(map_view(rq, &h_images[i].layout, rq.h_orient ? rq.h_orient[i] : 1, rq.h_matrices + k * i, &views[i], &view_matrices[k * i]));
         if (h_views_out) h_views_out[i] = views[i];
         if (h_matrices_out) std::memcpy(h_matrices_out + k * i, &view_matrices[k * i], k * sizeof(float));
     }
@@ -1375,9 +1382,11 @@ try {
 }
 JA_NOTHROW_TAIL
 
-// ---- "projective resample" ----
-int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h,
-                          jpeg_amd_view *view, float m_view[9])
+// ---- "projective resample" and "bicubic warp" ----
+namespace {
+
+int project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h, int wider,
+                 jpeg_amd_view *view, float m_view[9])
 {
     if (!view || !m_view || !orientation_valid(orientation)) return JPEG_AMD_EINVAL;
     if (out_w < 1 || out_h < 1 || out_w > kResizeMaxSide || out_h > kResizeMaxSide) return JPEG_AMD_EINVAL;
@@ -1426,7 +1435,7 @@ int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const 
             hi[a] = c == 0 ? v : std::max(hi[a], v);
         }
     }
-    const jpeg_amd_region r = footprint_view(lo, hi, S);
+    const jpeg_amd_region r = footprint_view(lo, hi, S, wider);
     // 5. against the view: the view's origin times the denominator's row off the numerators' rows
     float mv[9];
     for (int k = 0; k < 3; ++k) {
@@ -1440,12 +1449,47 @@ int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const 
     return JPEG_AMD_OK;
 }
 
+}  // namespace
+
+// The view that the map of `rq` reads of an image, and the matrix against it: jpeg_amd_warp_view's, or jpeg_amd_project_filter_view's
+// at the request's filter -- whose verdict is not given here but with the edge mode's (ResampleTarget::check): any filter
+// but the bicubic one has the two-tap footprint.
+int jpeg_amd::capi::map_view(const ResampleRequest &rq, const jpeg_amd_layout *layout, int orientation, const float *m, jpeg_amd_view *view,
+                             float *m_view)
+{
+    if (rq.map != ResampleMap::Projective) return jpeg_amd_warp_view(layout, orientation, m, rq.out_w, rq.out_h, view, m_view);
+    return project_view(layout, orientation, m, rq.out_w, rq.out_h, rq.filter == JPEG_AMD_FILTER_BICUBIC ? 1 : 0, view, m_view);
+}
+
+int jpeg_amd_project_filter_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int filter, int32_t out_w, int32_t out_h,
+                                 jpeg_amd_view *view, float m_view[9])
+{
+    if (filter != JPEG_AMD_FILTER_BILINEAR && filter != JPEG_AMD_FILTER_BICUBIC) return JPEG_AMD_EINVAL;
+    return project_view(layout, orientation, m, out_w, out_h, filter == JPEG_AMD_FILTER_BICUBIC ? 1 : 0, view, m_view);
+}
+
+int jpeg_amd_project_view(const jpeg_amd_layout *layout, int orientation, const float m[9], int32_t out_w, int32_t out_h,
+                          jpeg_amd_view *view, float m_view[9])
+{
+    return jpeg_amd_project_filter_view(layout, orientation, m, JPEG_AMD_FILTER_BILINEAR, out_w, out_h, view, m_view);
+}
+
+// The existing projective calls are the calls with a filter at JPEG_AMD_FILTER_BILINEAR.
 int jpeg_amd_project_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
                            const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
                            int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_project_filter_batch(ctx, n_images, d_src, src_stride, h_extents, h_matrices, warp, JPEG_AMD_FILTER_BILINEAR, out_w, out_h,
+                                         d_dst, dst_stride);
+}
+
+int jpeg_amd_project_filter_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                  const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp, int filter,
+                                  int32_t out_w, int32_t out_h, uint8_t *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
-                         ResampleRequest::bytes(out_w, out_h, d_dst, dst_stride).mapped(ResampleMap::Projective, h_matrices, warp));
+                         ResampleRequest::bytes(out_w, out_h, d_dst, dst_stride)
+                             .through(filter).mapped(ResampleMap::Projective, h_matrices, warp));
 }
 JA_NOTHROW_TAIL
 
@@ -1453,10 +1497,19 @@ int jpeg_amd_project_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t
                                   const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp,
                                   int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
                                   const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_project_filter_tensor_batch(ctx, n_images, d_src, src_stride, h_extents, h_matrices, warp, JPEG_AMD_FILTER_BILINEAR, out_w,
+                                                out_h, spec, h_flip, colour, d_dst, dst_stride);
+}
+
+int jpeg_amd_project_filter_tensor_batch(jpeg_amd_ctx *ctx, int n_images, const uint8_t *d_src, size_t src_stride,
+                                         const jpeg_amd_extent *h_extents, const float *h_matrices, const jpeg_amd_warp *warp, int filter,
+                                         int32_t out_w, int32_t out_h, const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip,
+                                         const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
     return resize_images(ctx, n_images, d_src, src_stride, h_extents,
                          ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
-                             .mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour));
+                             .through(filter).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour));
 }
 JA_NOTHROW_TAIL
 
@@ -1464,10 +1517,19 @@ int jpeg_amd_decode_projected_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_
                                     jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
                                     const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h, jpeg_amd_view *h_views_out,
                                     float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
+{
+    return jpeg_amd_decode_projected_filter_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp, JPEG_AMD_FILTER_BILINEAR,
+                                                  out_w, out_h, h_views_out, h_matrices_out, d_pixels, pixel_stride);
+}
+
+int jpeg_amd_decode_projected_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                           jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                           const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                           jpeg_amd_view *h_views_out, float *h_matrices_out, uint8_t *d_pixels, size_t pixel_stride)
 try {
     return mapped_mixed(ctx, n_images, h_images, cosited, color,
                         ResampleRequest::bytes(out_w, out_h, d_pixels, pixel_stride)
-                            .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
+                            .through(filter).oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp),
                         h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL
@@ -1477,10 +1539,21 @@ int jpeg_amd_decode_tensor_projected_mixed(jpeg_amd_ctx *ctx, int n_images, cons
                                            const jpeg_amd_warp *warp, int32_t out_w, int32_t out_h,
                                            const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
                                            float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
+{
+    return jpeg_amd_decode_tensor_projected_filter_mixed(ctx, n_images, h_images, cosited, color, h_orient, h_matrices, warp,
+                                                         JPEG_AMD_FILTER_BILINEAR, out_w, out_h, spec, h_flip, h_views_out, h_matrices_out,
+                                                         colour, d_dst, dst_stride);
+}
+
+int jpeg_amd_decode_tensor_projected_filter_mixed(jpeg_amd_ctx *ctx, int n_images, const jpeg_amd_image *h_images, int cosited,
+                                                  jpeg_amd_color color, const uint8_t *h_orient, const float *h_matrices,
+                                                  const jpeg_amd_warp *warp, int filter, int32_t out_w, int32_t out_h,
+                                                  const jpeg_amd_tensor_spec *spec, const uint8_t *h_flip, jpeg_amd_view *h_views_out,
+                                                  float *h_matrices_out, const jpeg_amd_colour *colour, void *d_dst, size_t dst_stride)
 try {
     return mapped_mixed(ctx, n_images, h_images, cosited, color,
                         ResampleRequest::elements(out_w, out_h, spec, h_flip, d_dst, dst_stride)
-                            .oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
+                            .through(filter).oriented(h_orient).mapped(ResampleMap::Projective, h_matrices, warp).coloured(colour),
                         h_views_out, h_matrices_out);
 }
 JA_NOTHROW_TAIL

@@ -255,7 +255,7 @@ uint64_t   resize_tiles(int out_w, int out_h);   // workgroups per image; the la
 // (image, row, flip ? out_w - 1 - x : x, channel), minus mean, times scale, converted and stored in spec->layout.  A spec is
 // valid (jpeg_amd_tensor_extent).  hipErrorInvalidValue: an extent or a tile count past the limits above, null records, or a
 // filter, dtype or layout that no kernel exists for.
-enum class ResampleRecords : int { Stored, Oriented, Placed, Warped, Projected };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms; WarpRecord, ProjectRecord (bilinear only)
+enum class ResampleRecords : int { Stored, Oriented, Placed, Warped, Projected };   // ResizeRecord / AntialiasRecord, their Oriented*, their Placed* forms; WarpRecord (bilinear only), ProjectRecord (bilinear, or bicubic: "bicubic warp")
 struct ResampleLaunch {
     int filter;                        // JPEG_AMD_FILTER_*
     ResampleRecords records;           // the kind of every record of the launch

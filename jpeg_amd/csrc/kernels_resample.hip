@@ -16,6 +16,9 @@
 //   the placed kernels' arguments; no tables, no LDS.
 // k_project_bytes, k_project_tensor<Colour, T, CHW>: "projective resample" -- project_walk (project.hpp) over ProjectRecords, the
 //   warp kernels with another walk: the same grid, arguments and sinks.
+// k_project_cubic_bytes, k_project_cubic_tensor<Colour, T, CHW>: "bicubic warp" -- project_cubic_walk (project_cubic.hpp) over the
+//   same ProjectRecords: the project kernels with 4 x 4 taps of the Keys cubic and a fetch of their own, the same grid,
+//   arguments and sinks.
 // k_resize_placed_tensor, k_tables_placed_tensor, k_warp_tensor and k_project_tensor carry a leading Colour flag: with it the sink is colour_sink
 //   ("colour stage": an affine map of (R, G, B) per image and a clamp, in front of the mean), the arguments end with the
 //   ColourRecords and the clamp's bounds, and nothing else differs.  These three express every record kind -- a whole-canvas
@@ -37,6 +40,7 @@
 #include "fused_common.hpp"
 #include "kernels.hpp"
 #include "project.hpp"
+#include "project_cubic.hpp"
 #include "resample.hpp"
 #include "tensor_sink.hpp"
 #include "warp.hpp"
@@ -317,6 +321,29 @@ __global__ __launch_bounds__(kThreads) void k_project_tensor(PlacedSinkArgs<Colo
     }
 }
 
+__global__ __launch_bounds__(kThreads) void k_project_cubic_bytes(PlacedBytesArgs<ProjectRecord> a)
+{
+    uint8_t *dst = image_dst(a);
+    project_cubic_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+}
+
+template <bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_project_cubic_tensor(PlacedSinkArgs<Colour, T, ProjectRecord> a)
+{
+    T *dst = image_dst(a);
+    const size_t plane = image_plane(a);
+    if constexpr (Colour) {
+        const ColourRecord k = a.colour[blockIdx.y];
+        project_cubic_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
+        });
+    } else {
+        project_cubic_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
+            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
+        });
+    }
+}
+
 // ---- the launcher ----
 
 // f(T{}, std::bool_constant<CHW>{}) for the element type and the layout of spec, or what no kernel exists for.
@@ -355,6 +382,7 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
     constexpr bool warped = std::is_same<Record, WarpRecord>::value || projected;   // (the placed kernels' args: records in tab_records, a fill)
     constexpr bool bilinear = std::is_same<Filter, Bilinear>::value, oriented = std::is_same<Record, OrientedResizeRecord>::value;
     constexpr bool placed = std::is_same<Record, PlacedResizeRecord>::value || std::is_same<Record, PlacedAntialiasRecord>::value;
+    constexpr bool cubic = projected && !bilinear;   // "bicubic warp": BicubicFilter names the filter, the walk is project_cubic_walk
     const auto run = [&](auto kernel, auto a) {   // a: the kernel's args, zeroed
         static_cast<ResampleArgs &>(a) = head;
         if constexpr (bilinear && !warped)
@@ -380,7 +408,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
             using T = decltype(t);
             if constexpr (placed || warped) {
                 if (l.d_colour) {
-                    if constexpr (projected)
+                    if constexpr (cubic)
+                        return run(k_project_cubic_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
+                    else if constexpr (projected)
                         return run(k_project_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
                     else if constexpr (warped)
                         return run(k_warp_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
@@ -390,7 +420,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
                         return run(k_tables_placed_tensor<true, Filter, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
                 }
             }
-            if constexpr (projected)
+            if constexpr (cubic)
+                return run(k_project_cubic_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
+            else if constexpr (projected)
                 return run(k_project_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
             else if constexpr (warped)
                 return run(k_warp_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
@@ -404,7 +436,9 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
                 return run(k_tables_tensor<Filter, Record, T, decltype(chw)::value>, RecordTensorArgs<T, Record>{});
         });
     }
-    if constexpr (projected)
+    if constexpr (cubic)
+        return run(k_project_cubic_bytes, PlacedBytesArgs<Record>{});
+    else if constexpr (projected)
         return run(k_project_bytes, PlacedBytesArgs<Record>{});
     else if constexpr (warped)
         return run(k_warp_bytes, PlacedBytesArgs<Record>{});
@@ -447,8 +481,10 @@ hipError_t launch_resample(hipStream_t stream, const ResampleLaunch &l)
     if (const hipError_t e = resample_launch(l.n_images, l.d_src, nullptr, l.out_w, l.out_h, head, grid)) return e;
     if (l.records == ResampleRecords::Warped)   // "warped resample": the two-tap filter only
         return l.filter == JPEG_AMD_FILTER_BILINEAR ? launch_kernel<Bilinear, WarpRecord>(stream, l, head, grid) : hipErrorInvalidValue;
-    if (l.records == ResampleRecords::Projected)   // "projective resample": likewise
+    if (l.records == ResampleRecords::Projected) {   // "projective resample", or "bicubic warp" over the same records
+        if (l.filter == JPEG_AMD_FILTER_BICUBIC) return launch_kernel<BicubicFilter, ProjectRecord>(stream, l, head, grid);
         return l.filter == JPEG_AMD_FILTER_BILINEAR ? launch_kernel<Bilinear, ProjectRecord>(stream, l, head, grid) : hipErrorInvalidValue;
+    }
     switch (l.filter) {
     case JPEG_AMD_FILTER_BILINEAR: return launch_filter<Bilinear, ResizeRecord, OrientedResizeRecord, PlacedResizeRecord>(stream, l, head, grid);
     case JPEG_AMD_FILTER_ANTIALIAS: return launch_filter<TriangleFilter, AntialiasRecord, OrientedAntialiasRecord, PlacedAntialiasRecord>(stream, l, head, grid);

@@ -17,7 +17,7 @@ enum class ResampleMap { None, Affine, Projective };
 
 struct ResampleRequest {
     int32_t out_w = 0, out_h = 0;                     // the canvas
-    int filter = JPEG_AMD_FILTER_BILINEAR;            // JPEG_AMD_FILTER_*
+    int filter = JPEG_AMD_FILTER_BILINEAR;            // JPEG_AMD_FILTER_*; with a map ("bicubic warp"): bilinear, or bicubic with a projective one
     // the target: bytes, or the elements of a tensor.  `tensor` is not `spec != nullptr`: a tensor call without a spec is
     // jpeg_amd_tensor_extent's to refuse
     bool tensor = false;
@@ -29,7 +29,7 @@ struct ResampleRequest {
     const jpeg_amd_placement *place = nullptr;        // or nullptr: every image fills the canvas
     jpeg_amd_region *h_windows_out = nullptr;         // per image, or nullptr: where a placed call writes its windows
     // with a map: per image matrix_floats() numbers against the image AS IT IS STORED at the launch's source (of a view:
-    // jpeg_amd_warp_view's or jpeg_amd_project_view's m_view), and the call's warp
+    // map_view's m_view), and the call's warp
     ResampleMap map = ResampleMap::None;
     const float *h_matrices = nullptr;
     const jpeg_amd_warp *warp = nullptr;
@@ -105,6 +105,9 @@ struct ResampleRequest {
 };
 
 
+// The view that the map of `rq` reads of one image, and the matrix against it: jpeg_amd_warp_view's, or
+// jpeg_amd_project_filter_view's at the request's filter.  For the mixed calls and for pass 0 of the file calls (capi_view.hip).
+int map_view(const ResampleRequest &rq, const jpeg_amd_layout *layout, int orientation, const float *m, jpeg_amd_view *view, float *m_view);
 // What the mixed resample calls (jpeg_amd_decode_resized_placed_mixed, jpeg_amd_decode_tensor_colour_mixed, ...) refuse of the
 // request `rq` before they look at the context, for the file calls, which judge a call before its planes exist (the images'
 // pointers only have to be non-null): of the first `judged` images of a call of n_images, in the mixed call's order; *taps:

@@ -18,7 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
 SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_tile.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
-HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "warp.hpp", "project.hpp", "project_cubic.hpp", "resample_request.hpp", "resample_chunks.hpp"]
+HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "mapped_walk.hpp", "resample_request.hpp", "resample_chunks.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
 # Per-source flags.  The transform kernels are compiled WITHOUT the SLP vectoriser: it turns the float arithmetic of the 8-point
@@ -40,15 +40,14 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
 # must not leave a user without a library).  k_resize_bilinear counts nothing, but it is small (54 VGPRs) and every lane streams
 # bytes: a spill there is a mistake in the source, so it is held to the strict rule; k_resize_tensor<false, ...> (the stored
 # images'), the same walk with another store, likewise; k_tensor_pixels, smaller still (26 VGPRs), likewise; k_expand_mixed, an
-# entry walk and one store, likewise; k_warp_bytes and k_warp_tensor (52 to 57 VGPRs, no LDS), whose every lane computes its own
-# tap addresses, likewise; the kernels with the colour stage (a leading template flag: ILb1E; those of k_warp_tensor stand
-# under k_warp_), which keep twelve more numbers in SGPRs and nine more operations per pixel in flight, likewise; k_project_bytes and
-# k_project_tensor, the warp kernels with a third row of the matrix and a division per pixel, likewise; k_project_cubic_bytes and
-# k_project_cubic_tensor ("bicubic warp": 98 to 100 VGPRs, twelve dwords of taps per pixel in flight), which the same fragment
-# k_project_ names, likewise.  A source
+# entry walk and one store, likewise; k_mapped_bytes and k_mapped_tensor (mapped_walk.hpp: no LDS, every lane computes its own tap
+# addresses; 52 to 57 VGPRs with TwoTaps, the projective map's third row and division included, 98 to 100 with CubicTaps and its
+# twelve dwords of taps per pixel in flight), likewise, with their colour forms; the placed kernels with the colour stage (a
+# leading template flag: ILb1E), which keep twelve more numbers in SGPRs and nine more operations per pixel in flight,
+# likewise.  A source
 # may stand in both tables, with other fragments.
 NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused",
-              "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E", "k_warp_", "k_project_", "k_resize_placed_tensorILb1E",
+              "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E", "k_mapped_", "k_resize_placed_tensorILb1E",
                                        "k_tables_placed_tensorILb1E"),
               "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",

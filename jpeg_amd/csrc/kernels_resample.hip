@@ -1,8 +1,8 @@
 // kernels_resample.hip -- the resample kernels: pixel images to one target size through one of three filters, read as they are
 // stored or in one of the eight EXIF orientations, to bytes or to normalised tensor elements.  The contracts are in
 // include/jpeg_amd.h ("resized decode", "antialiased resample", "bicubic resample", "oriented resample", "tensor output"); the
-// walks, the filters and the stores are resample.hpp's, antialias.hpp's and tensor_sink.hpp's.  Filter, record kind and sink
-// are three parameters; a kernel is a walk with a sink:
+// walks, the filters and the stores are resample.hpp's, antialias.hpp's, mapped_walk.hpp's and tensor_sink.hpp's.  Filter,
+// record kind and sink are three parameters; a kernel is a walk with a sink:
 //
 // k_resize_bilinear: bilinear, stored, bytes -- resample_walk written out with the packing inside the tap loop (below).
 // k_resize_oriented_bytes: bilinear, oriented, bytes -- resample_walk<true> with byte_sink.
@@ -12,17 +12,13 @@
 // k_resize_placed_bytes, k_resize_placed_tensor<T, CHW>, k_tables_placed_bytes<Filter>, k_tables_placed_tensor<Filter, T, CHW>:
 //   the same walks over PlacedResizeRecords / PlacedAntialiasRecords ("placed resample") with the same sinks; their arguments
 //   end with the launch's fill.
-// k_warp_bytes, k_warp_tensor<T, CHW>: "warped resample" -- warp_walk (warp.hpp) over WarpRecords with the same two sinks and
-//   the placed kernels' arguments; no tables, no LDS.
-// k_project_bytes, k_project_tensor<Colour, T, CHW>: "projective resample" -- project_walk (project.hpp) over ProjectRecords, the
-//   warp kernels with another walk: the same grid, arguments and sinks.
-// k_project_cubic_bytes, k_project_cubic_tensor<Colour, T, CHW>: "bicubic warp" -- project_cubic_walk (project_cubic.hpp) over the
-//   same ProjectRecords: the project kernels with 4 x 4 taps of the Keys cubic and a fetch of their own, the same grid,
-//   arguments and sinks.
-// k_resize_placed_tensor, k_tables_placed_tensor, k_warp_tensor and k_project_tensor carry a leading Colour flag: with it the sink is colour_sink
+// k_mapped_bytes<Map, Taps>, k_mapped_tensor<Map, Taps, Colour, T, CHW>: mapped_walk (mapped_walk.hpp) with the same two sinks and
+//   the placed kernels' arguments; no tables, no LDS.  AffineMap over WarpRecords with TwoTaps is "warped resample";
+//   ProjectiveMap over ProjectRecords is "projective resample" with TwoTaps and "bicubic warp" with CubicTaps.
+// k_resize_placed_tensor, k_tables_placed_tensor and k_mapped_tensor carry a Colour flag: with it the sink is colour_sink
 //   ("colour stage": an affine map of (R, G, B) per image and a clamp, in front of the mean), the arguments end with the
-//   ColourRecords and the clamp's bounds, and nothing else differs.  These three express every record kind -- a whole-canvas
-//   window is the oriented and the stored call -- so the others have no colour form.
+//   ColourRecords and the clamp's bounds, and nothing else differs (walk_to_tensor).  These three express every record kind
+//   -- a whole-canvas window is the oriented and the stored call -- so the others have no colour form.
 // The byte kernels never flip (the records' flip is not read); the tensor kernels flip where the record says so, after the
 // orientation: the flip mirrors the OUTPUT columns.
 //
@@ -39,11 +35,9 @@
 #include "antialias.hpp"
 #include "fused_common.hpp"
 #include "kernels.hpp"
-#include "project.hpp"
-#include "project_cubic.hpp"
+#include "mapped_walk.hpp"
 #include "resample.hpp"
 #include "tensor_sink.hpp"
-#include "warp.hpp"
 
 namespace jpeg_amd {
 
@@ -232,23 +226,28 @@ __global__ __launch_bounds__(kThreads) void k_resize_placed_bytes(PlacedBytesArg
     resample_walk<true, true>(a, false, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); }, a.fill);
 }
 
-// Colour: the image's ColourRecord, read here, once per workgroup and in front of the walk, and colour_sink in tensor_sink's
-// place; without it the kernel is the text it was.  The same in k_tables_placed_tensor and k_warp_tensor.
-template <bool Colour, typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_resize_placed_tensor(PlacedSinkArgs<Colour, T, PlacedResizeRecord> a)
+// walk(sink) with the sink of a tensor kernel that carries a Colour flag.  Colour: the image's ColourRecord, read here, once
+// per workgroup and in front of the walk, and colour_sink in tensor_sink's place.  Handed the walk as a generic lambda, all
+// kernels are the instructions they were when each spelled this block out, but for the three bicubic k_mapped_tensor<...,
+// false, T, true>: one address computation in front of their row loop stands two instructions later (measured:
+// profiles/mapped_walk_refactor.txt).
+template <bool Colour, typename T, bool CHW, typename Args, typename Walk>
+__device__ __forceinline__ void walk_to_tensor(const Args &a, Walk walk)
 {
     T *dst = image_dst(a);
     const size_t plane = image_plane(a);
     if constexpr (Colour) {
         const ColourRecord k = a.colour[blockIdx.y];
-        resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
-        }, a.fill);
+        walk([&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix); });
     } else {
-        resample_walk<true, true>(a, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-        }, a.fill);
+        walk([&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix); });
     }
+}
+
+template <bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_resize_placed_tensor(PlacedSinkArgs<Colour, T, PlacedResizeRecord> a)
+{
+    walk_to_tensor<Colour, T, CHW>(a, [&](auto sink) { resample_walk<true, true>(a, true, sink, a.fill); });
 }
 
 template <typename Filter>
@@ -261,87 +260,20 @@ __global__ __launch_bounds__(kThreads) void k_tables_placed_bytes(PlacedBytesArg
 template <bool Colour, typename Filter, typename T, bool CHW>
 __global__ __launch_bounds__(kThreads) void k_tables_placed_tensor(PlacedSinkArgs<Colour, T, PlacedAntialiasRecord> a)
 {
-    T *dst = image_dst(a);
-    const size_t plane = image_plane(a);
-    if constexpr (Colour) {
-        const ColourRecord k = a.colour[blockIdx.y];
-        antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
-        }, a.fill);
-    } else {
-        antialias_walk<Filter>(a, a.tab_records, true, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-        }, a.fill);
-    }
+    walk_to_tensor<Colour, T, CHW>(a, [&](auto sink) { antialias_walk<Filter>(a, a.tab_records, true, sink, a.fill); });
 }
 
-__global__ __launch_bounds__(kThreads) void k_warp_bytes(PlacedBytesArgs<WarpRecord> a)
+template <typename Map, typename Taps>
+__global__ __launch_bounds__(kThreads) void k_mapped_bytes(PlacedBytesArgs<typename Map::Record> a)
 {
     uint8_t *dst = image_dst(a);
-    warp_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
+    mapped_walk<Map, Taps>(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
 }
 
-template <bool Colour, typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_warp_tensor(PlacedSinkArgs<Colour, T, WarpRecord> a)
+template <typename Map, typename Taps, bool Colour, typename T, bool CHW>
+__global__ __launch_bounds__(kThreads) void k_mapped_tensor(PlacedSinkArgs<Colour, T, typename Map::Record> a)
 {
-    T *dst = image_dst(a);
-    const size_t plane = image_plane(a);
-    if constexpr (Colour) {
-        const ColourRecord k = a.colour[blockIdx.y];
-        warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
-        });
-    } else {
-        warp_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-        });
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_project_bytes(PlacedBytesArgs<ProjectRecord> a)
-{
-    uint8_t *dst = image_dst(a);
-    project_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
-}
-
-template <bool Colour, typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_project_tensor(PlacedSinkArgs<Colour, T, ProjectRecord> a)
-{
-    T *dst = image_dst(a);
-    const size_t plane = image_plane(a);
-    if constexpr (Colour) {
-        const ColourRecord k = a.colour[blockIdx.y];
-        project_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
-        });
-    } else {
-        project_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-        });
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_project_cubic_bytes(PlacedBytesArgs<ProjectRecord> a)
-{
-    uint8_t *dst = image_dst(a);
-    project_cubic_walk(a, a.tab_records, false, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) { byte_sink(dst, a.out_w, o, y, x, npix); });
-}
-
-template <bool Colour, typename T, bool CHW>
-__global__ __launch_bounds__(kThreads) void k_project_cubic_tensor(PlacedSinkArgs<Colour, T, ProjectRecord> a)
-{
-    T *dst = image_dst(a);
-    const size_t plane = image_plane(a);
-    if constexpr (Colour) {
-        const ColourRecord k = a.colour[blockIdx.y];
-        project_cubic_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            colour_sink<T, CHW>(a, k, a.lo, a.hi, dst, plane, o, y, x, npix);
-        });
-    } else {
-        project_cubic_walk(a, a.tab_records, true, a.fill, [&](const uint32_t (&o)[kRun][3], int y, int x, int npix) {
-            tensor_sink<T, CHW>(a, dst, plane, o, y, x, npix);
-        });
-    }
+    walk_to_tensor<Colour, T, CHW>(a, [&](auto sink) { mapped_walk<Map, Taps>(a, a.tab_records, true, a.fill, sink); });
 }
 
 // ---- the launcher ----
@@ -372,18 +304,25 @@ void set_colour(ColourTensorArgs<T, Record> &a, const ResampleLaunch &l)
     a.hi = l.hi;
 }
 
+// The args of a kernel, zeroed.
+template <typename Args>
+Args kernel_args(void (*)(Args)) { return Args{}; }
+
 struct Bilinear;   // in place of a filter of antialias.hpp: resample_walk, whose records are ResampleArgs::records
 
-// The launch of one filter and record kind: `run` fills the args of either sink, the rest names the kernel and its args.
+// The launch of one filter and record kind: `run` fills the args of a kernel, whatever its sink, the rest names the kernel.
 template <typename Filter, typename Record>
 hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const ResampleArgs &head, dim3 grid)
 {
-    constexpr bool projected = std::is_same<Record, ProjectRecord>::value;   // (the warp kernels' args)
-    constexpr bool warped = std::is_same<Record, WarpRecord>::value || projected;   // (the placed kernels' args: records in tab_records, a fill)
+    constexpr bool projected = std::is_same<Record, ProjectRecord>::value;
+    constexpr bool warped = std::is_same<Record, WarpRecord>::value || projected;   // (mapped_walk; the placed kernels' args: records in tab_records, a fill)
     constexpr bool bilinear = std::is_same<Filter, Bilinear>::value, oriented = std::is_same<Record, OrientedResizeRecord>::value;
     constexpr bool placed = std::is_same<Record, PlacedResizeRecord>::value || std::is_same<Record, PlacedAntialiasRecord>::value;
-    constexpr bool cubic = projected && !bilinear;   // "bicubic warp": BicubicFilter names the filter, the walk is project_cubic_walk
-    const auto run = [&](auto kernel, auto a) {   // a: the kernel's args, zeroed
+    constexpr bool cubic = projected && !bilinear;   // "bicubic warp": BicubicFilter names the filter, the taps are CubicTaps
+    using Map = typename std::conditional<projected, ProjectiveMap, AffineMap>::type;   // (warped: mapped_walk's map and taps)
+    using Taps = typename std::conditional<cubic, CubicTaps, TwoTaps>::type;
+    const auto run = [&](auto kernel) {
+        auto a = kernel_args(kernel);
         static_cast<ResampleArgs &>(a) = head;
         if constexpr (bilinear && !warped)
             a.records = static_cast<const Record *>(l.d_records);
@@ -402,56 +341,42 @@ hipError_t launch_kernel(hipStream_t stream, const ResampleLaunch &l, const Resa
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, a);
         return hipGetLastError();
     };
+    // The kernel with the tensor sink for elements of t in the layout chw; colour: with the "colour stage", where there is one.
+    const auto tensor_kernel = [](auto colour, auto t, auto chw) {
+        using T = decltype(t);
+        constexpr bool Colour = decltype(colour)::value, CHW = decltype(chw)::value;
+        if constexpr (warped)
+            return k_mapped_tensor<Map, Taps, Colour, T, CHW>;
+        else if constexpr (placed && bilinear)
+            return k_resize_placed_tensor<Colour, T, CHW>;
+        else if constexpr (placed)
+            return k_tables_placed_tensor<Colour, Filter, T, CHW>;
+        else if constexpr (bilinear)
+            return k_resize_tensor<oriented, T, CHW>;
+        else
+            return k_tables_tensor<Filter, Record, T, CHW>;
+    };
     if (l.d_colour && !(l.spec && (placed || warped))) return hipErrorInvalidValue;   // "colour stage": these kernels only
     if (l.spec) {
         return with_element(*l.spec, [&](auto t, auto chw) {
-            using T = decltype(t);
             if constexpr (placed || warped) {
-                if (l.d_colour) {
-                    if constexpr (cubic)
-                        return run(k_project_cubic_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
-                    else if constexpr (projected)
-                        return run(k_project_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
-                    else if constexpr (warped)
-                        return run(k_warp_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
-                    else if constexpr (bilinear)
-                        return run(k_resize_placed_tensor<true, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
-                    else
-                        return run(k_tables_placed_tensor<true, Filter, T, decltype(chw)::value>, ColourTensorArgs<T, Record>{});
-                }
+                if (l.d_colour) return run(tensor_kernel(std::true_type{}, t, chw));
             }
-            if constexpr (cubic)
-                return run(k_project_cubic_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
-            else if constexpr (projected)
-                return run(k_project_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
-            else if constexpr (warped)
-                return run(k_warp_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
-            else if constexpr (placed && bilinear)
-                return run(k_resize_placed_tensor<false, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
-            else if constexpr (placed)
-                return run(k_tables_placed_tensor<false, Filter, T, decltype(chw)::value>, PlacedTensorArgs<T, Record>{});
-            else if constexpr (bilinear)
-                return run(k_resize_tensor<oriented, T, decltype(chw)::value>, ResizeTensorArgs<oriented, T>{});
-            else
-                return run(k_tables_tensor<Filter, Record, T, decltype(chw)::value>, RecordTensorArgs<T, Record>{});
+            return run(tensor_kernel(std::false_type{}, t, chw));
         });
     }
-    if constexpr (cubic)
-        return run(k_project_cubic_bytes, PlacedBytesArgs<Record>{});
-    else if constexpr (projected)
-        return run(k_project_bytes, PlacedBytesArgs<Record>{});
-    else if constexpr (warped)
-        return run(k_warp_bytes, PlacedBytesArgs<Record>{});
+    if constexpr (warped)
+        return run(k_mapped_bytes<Map, Taps>);
     else if constexpr (placed && bilinear)
-        return run(k_resize_placed_bytes, PlacedBytesArgs<Record>{});
+        return run(k_resize_placed_bytes);
     else if constexpr (placed)
-        return run(k_tables_placed_bytes<Filter>, PlacedBytesArgs<Record>{});
+        return run(k_tables_placed_bytes<Filter>);
     else if constexpr (!bilinear)
-        return run(k_tables_bytes<Filter, Record>, BytesArgs<Record>{});
+        return run(k_tables_bytes<Filter, Record>);
     else if constexpr (oriented)
-        return run(k_resize_oriented_bytes, BytesArgs<Record>{});
+        return run(k_resize_oriented_bytes);
     else
-        return run(k_resize_bilinear, ResizeArgs{});
+        return run(k_resize_bilinear);
 }
 
 template <typename Filter, typename Stored, typename Oriented, typename Placed>

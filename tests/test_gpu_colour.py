@@ -1,4 +1,4 @@
-"""The colour stage on the MI355X (the six *_colour_* calls; k_resize_placed_tensor, k_tables_placed_tensor and k_warp_tensor with
+"""The colour stage on the MI355X (the six *_colour_* calls; k_resize_placed_tensor, k_tables_placed_tensor and k_mapped_tensor with
 the Colour flag): every output is compared element for element, as a bit pattern, with the numpy mirror of the contract
 (_colour_ref) on the bytes of the existing mirrors, and where the contract ties into an existing call, with that call on the GPU.
 The canvas is 70 x 37 -- two tiles across and two down, the last ones partial, an odd width so that runs of 4 straddle out_w --

@@ -1,5 +1,5 @@
 """The projective resample on the MI355X (jpeg_amd_project_batch, _project_tensor_batch, the *_projected_mixed decode and file
-calls; k_project_bytes and k_project_tensor): every output is compared byte for byte, or element for element as a bit
+calls; k_mapped_bytes and k_mapped_tensor over ProjectiveMap and TwoTaps): every output is compared byte for byte, or element for element as a bit
 pattern, with the numpy mirror of the contract (_project_ref) -- which is what holds the kernel's division to the correctly
 rounded one -- and where the contract ties into an existing call, with that call on the GPU.  The canvas is 70 x 37: two tiles
 across and two down, the last ones partial, with an odd width so that runs of 4 straddle out_w.  Every raw call writes into a

@@ -1,5 +1,5 @@
 """The bicubic warp on the MI355X (jpeg_amd_project_filter_batch, _project_filter_tensor_batch, the *_projected_filter_mixed
-decode and file calls; k_project_cubic_bytes and k_project_cubic_tensor): every output is compared byte for byte, or element
+decode and file calls; k_mapped_bytes and k_mapped_tensor over ProjectiveMap and CubicTaps): every output is compared byte for byte, or element
 for element as a bit pattern, with the numpy mirror of the contract (_project_cubic_ref), and where the contract ties into an
 existing call, with that call on the GPU.  The canvas is 70 x 37: two tiles across and two down, the last ones partial, with an
 odd width so that runs of 4 straddle out_w.  Every raw call writes into a sentinel-filled buffer whose bytes in front of,

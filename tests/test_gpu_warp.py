@@ -1,5 +1,5 @@
 """The warped resample on the MI355X (jpeg_amd_warp_batch, _warp_tensor_batch, the *_warped_mixed decode and file calls;
-k_warp_bytes and k_warp_tensor): every output is compared byte for byte, or element for element as a bit pattern, with the
+k_mapped_bytes and k_mapped_tensor over AffineMap and TwoTaps): every output is compared byte for byte, or element for element as a bit pattern, with the
 numpy mirror of the contract (_warp_ref), and where the contract ties into an existing call, with that call on the GPU.  The
 canvas is 70 x 37 -- two tiles across and two down, the last ones partial, with an odd width so that runs of 4 straddle out_w.
 Every raw call writes into a sentinel-filled buffer whose bytes in front of, between and behind the images are checked.

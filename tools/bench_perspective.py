@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_perspective.py -- the projective resample (k_project_tensor over ProjectRecords; include/jpeg_amd.h, "projective
+"""tools/bench_perspective.py -- the projective resample (k_mapped_tensor<ProjectiveMap, TwoTaps> over ProjectRecords; include/jpeg_amd.h, "projective
 resample") against the affine warp on identical matrices and against the route a caller has today to a perspective crop,
 alternating in one process.
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_warp.py -- the warped resample (k_warp_tensor over WarpRecords; include/jpeg_amd.h, "warped resample") against
+"""tools/bench_warp.py -- the warped resample (k_mapped_tensor<AffineMap, TwoTaps> over WarpRecords; include/jpeg_amd.h, "warped resample") against
 the bilinear kernels on the same views and against the route a caller has today to a rotated crop, alternating in one process.
 
     python tools/bench_warp.py [--steps 10] [--warmup 2] [--rounds 5] [--ring 2] [--out profiles/warp.txt]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_warp_cubic.py -- the bicubic warp (k_project_cubic_tensor over ProjectRecords; include/jpeg_amd.h, "bicubic warp")
+"""tools/bench_warp_cubic.py -- the bicubic warp (k_mapped_tensor<ProjectiveMap, CubicTaps> over ProjectRecords; include/jpeg_amd.h, "bicubic warp")
 against the bilinear warp on the same views and matrices and against the route a caller has today to a bicubic rotation,
 alternating in one process.
 

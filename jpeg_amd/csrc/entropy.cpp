@@ -17,7 +17,6 @@
 #include <cstring>
 #include <new>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
@@ -345,6 +344,69 @@ struct SparseOut {
 };
 int16_t g_sparse_sentinel[1];   // what Component::coef points at in a sparse decode (never dereferenced)
 
+// ---- one scan: what its header says, parsed once (Decoder::plan_scan) ----
+struct ScanComp { Component *c; int td, ta; };
+struct Slot { Component *c; int td, ta, bx, by; };   // one block of an MCU: its component and tables, its place in the MCU
+enum class BlockKind { Sequential, DcFirst, DcRefine, AcFirst, AcRefine };
+struct ScanPlan {
+    int ns = 0;
+    ScanComp sc[4];
+    int ss = 0, se = 63, ah = 0, al = 0;
+    bool progressive = false;
+    BlockKind kind = BlockKind::Sequential;
+    Slot slots[16];
+    int nslots = 0;
+    int mcux = 0, mcuy = 0;
+    long total = 0, ri = 0, nintervals = 0;   // MCUs of the scan, MCUs of a restart interval (the whole scan without one)
+};
+
+// Where the block of slot `sl` of MCU (mx, my) lies in its component's plane.
+struct BlockAt { int x, y; };
+inline BlockAt block_at(const ScanPlan &plan, const Slot &sl, int mx, int my)
+{
+    return plan.ns > 1 ? BlockAt{mx * sl.c->fx + sl.bx, my * sl.c->fy + sl.by} : BlockAt{mx, my};
+}
+
+// Where the restart intervals of the entropy-coded segment [ecs, end) start: its first byte, then the byte behind every RSTn.
+// As many entries as the scan has intervals only when every marker is where it should be.
+inline std::vector<const uint8_t *> find_interval_starts(const uint8_t *ecs, const uint8_t *end, long nintervals)
+{
+    std::vector<const uint8_t *> starts{ecs};
+    if (nintervals > 1)
+        for (const uint8_t *q = ecs; q + 1 < end;) {
+            q = static_cast<const uint8_t *>(std::memchr(q, 0xff, (size_t)(end - 1 - q)));
+            if (!q) break;
+            if (q[1] >= 0xd0 && q[1] <= 0xd7) starts.push_back(q + 2);
+            q += q[1] == 0xff ? 1 : 2;          // 0xFF fill bytes may precede a marker
+        }
+    return starts;
+}
+
+// work(0) ... work(t_n - 1), each once: up to t_n - 1 of them on threads of their own, index 0 -- and every index whose thread
+// could not be started -- on this thread; nothing is left joinable.  An exception inside work(t) becomes
+// status[t] = JPEG_AMD_ENOMEM where a status array (t_n entries or more) is given, and never leaves its thread.
+template <class Work>
+void run_on_threads(int t_n, const Work &work, int *status = nullptr)
+{
+    auto guarded = [&](int t) {
+        try {
+            work(t);
+        } catch (...) {
+            if (status) status[t] = JPEG_AMD_ENOMEM;
+        }
+    };
+    std::vector<std::thread> pool;
+    int started = 1;
+    try {
+        pool.reserve((size_t)t_n);
+        for (int t = 1; t < t_n; ++t) { pool.emplace_back(guarded, t); ++started; }
+    } catch (...) {
+    }
+    for (int t = started; t < t_n; ++t) guarded(t);
+    guarded(0);
+    for (std::thread &th : pool) th.join();
+}
+
 struct Decoder {
     const uint8_t *data;
     size_t n;
@@ -398,20 +460,11 @@ struct Decoder {
         const size_t piece = (size_t)4 << 20;
         const int t_n = (int)std::min<size_t>((size_t)nthreads, bytes / piece);
         if (t_n < 2) { std::memset(p, 0, bytes); return; }
-        std::vector<std::thread> pool;
         const size_t per = (bytes / t_n + 63) & ~(size_t)63;
-        auto clear = [=](int t) {
+        run_on_threads(t_n, [=](int t) {
             const size_t lo = std::min(bytes, per * t), hi = t + 1 == t_n ? bytes : std::min(bytes, per * (t + 1));
             std::memset(reinterpret_cast<char *>(p) + lo, 0, hi - lo);
-        };
-        int started = 0;   // a thread that cannot be started leaves its piece to this one; nothing is left joinable
-        try {
-            pool.reserve((size_t)t_n);
-            for (int t = 0; t < t_n; ++t) { pool.emplace_back(clear, t); ++started; }
-        } catch (...) {
-        }
-        for (int t = started; t < t_n; ++t) clear(t);
-        for (std::thread &th : pool) th.join();
+        });
     }
 
     // Height 0 in the frame header: the real height follows the FIRST scan in a DNL segment
@@ -479,439 +532,10 @@ struct Decoder {
         return JPEG_AMD_OK;
     }
 
-    // ---- one scan ----
-    struct ScanComp { Component *c; int td, ta; };
-
-    int decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, const uint8_t *end, uint16_t (*quanta_out)[64])
-    {
-        if (hlen < 1) return JPEG_AMD_EINVAL;
-        const int ns = hdr[0];
-        if (ns < 1 || ns > 4 || hlen < 4 + 2 * (size_t)ns) return JPEG_AMD_EINVAL;
-        ScanComp sc[4];
-        for (int j = 0; j < ns; ++j) {
-            const int cid = hdr[1 + 2 * j], tt = hdr[2 + 2 * j];
-            Component *c = nullptr;
-            for (Component &x : comps) if (x.id == cid) c = &x;
-            if (!c) return JPEG_AMD_EINVAL;
-            sc[j] = {c, tt >> 4, tt & 15};
-            if (sc[j].td > 3 || sc[j].ta > 3) return JPEG_AMD_EINVAL;
-        }
-        const int ss = hdr[1 + 2 * ns], se = hdr[2 + 2 * ns], ah = hdr[3 + 2 * ns] >> 4, al = hdr[3 + 2 * ns] & 15;
-        const bool progressive = info.process == 2;
-        if (se > 63 || ss > se) return JPEG_AMD_EINVAL;
-        if (progressive && ss > 0 && ns != 1) return JPEG_AMD_EINVAL;
-        if (!progressive && (ss != 0 || se != 63 || ah != 0 || al != 0)) {
-            // tolerate odd headers of sequential scans the way libjpeg does: treat as full band
-        }
-        // bind quantisation tables at the component's first scan
-        if (ah == 0 && ss == 0) {
-            for (int j = 0; j < ns; ++j) {
-                Component *c = sc[j].c;
-                if (!qdefined[c->tq]) return JPEG_AMD_EINVAL;
-                if (quanta_out) std::memcpy(quanta_out[c - comps.data()], qslots[c->tq], 128);
-                c->bound = true;
-            }
-        }
-        if (!comps[0].coef) return JPEG_AMD_OK;   // inspect-only pass
-
-        // MCU geometry
-        int mcux, mcuy;
-        struct Slot { Component *c; int td, ta, bx, by; };
-        Slot slots[16];
-        int nslots = 0;
-        if (ns > 1) {
-            mcux = units(info.width, 8 * info.scale_x);
-            mcuy = units(info.height, 8 * info.scale_y);
-            for (int j = 0; j < ns; ++j)
-                for (int by = 0; by < sc[j].c->fy; ++by)
-                    for (int bx = 0; bx < sc[j].c->fx; ++bx) {
-                        if (nslots >= 16) return JPEG_AMD_ENOSUP;
-                        slots[nslots++] = {sc[j].c, sc[j].td, sc[j].ta, bx, by};
-                    }
-        } else {
-            mcux = sc[0].c->ux; mcuy = sc[0].c->uy;
-            slots[nslots++] = {sc[0].c, sc[0].td, sc[0].ta, 0, 0};
-        }
-        const long total = (long)mcux * mcuy;
-        const long ri = restart_interval ? restart_interval : total;
-
-        // One restart interval (or the whole scan): MCUs [mcu0, mcu1) from `br`, predictors and
-        // the EOB run starting from zero (T.81 E.2.4).  Intervals touch disjoint blocks.
-        auto run_interval = [&](BitReader &br, long mcu0, long mcu1) -> int {
-        int pred[4] = {0, 0, 0, 0};
-        int eobrun = 0;
-        int16_t dummy[64];
-        int my = (int)(mcu0 / mcux), mx = (int)(mcu0 - (long)my * mcux) - 1;
-        for (long mcu = mcu0; mcu < mcu1; ++mcu) {
-            if (++mx == mcux) { mx = 0; ++my; }
-            if (!progressive && (mx == 0 || mcu == mcu0)) {
-                // sequential: the blocks of this MCU row that belong to the interval are cleared here, a row at a time -- large
-                // enough for the library's wide memset, small enough to still be in cache when they are filled (clearing the
-                // whole plane up front costs a quarter of the decode time; clearing block by block, 128 bytes at a time, a third)
-                const long span = std::min<long>(mcux - mx, mcu1 - mcu);     // MCUs of this row inside the interval
-                for (int j = 0; j < ns; ++j) {
-                    Component *c = sc[j].c;
-                    const int fx = ns > 1 ? c->fx : 1, fy = ns > 1 ? c->fy : 1;
-                    const int x0 = std::min(mx * fx, c->ux), x1 = (int)std::min<long>((mx + span) * fx, c->ux);
-                    for (int y = my * fy; y < std::min(my * fy + fy, c->uy); ++y)
-                        if (x1 > x0) std::memset(c->coef + (size_t)64 * ((size_t)c->ux * y + x0), 0, (size_t)128 * (x1 - x0));
-                }
-            }
-            for (int si = 0; si < nslots; ++si) {
-                const Slot &sl = slots[si];
-                Component *c = sl.c;
-                const int x = ns > 1 ? mx * c->fx + sl.bx : mx, y = ns > 1 ? my * c->fy + sl.by : my;
-                const bool inside = x < c->ux && y < c->uy;
-                int16_t *blk = inside ? c->coef + (size_t)64 * ((size_t)c->ux * y + x) : dummy;
-                const int ci = (int)(c - comps.data());
-                if (!inside) std::memset(dummy, 0, sizeof dummy);
-                if (!progressive) {
-                    // sequential: T.81 F.2.2.  The block is cleared here, while it is in cache,
-                    // instead of with the whole plane up front (a quarter of the decode time).
-                    if (!dc[sl.td].defined || !ac[sl.ta].defined) return JPEG_AMD_EINVAL;
-                    if (br.nbits < 32) br.refill();
-                    int diff;
-                    const int32_t ed = dc[sl.td].look_dc[br.peek(10)];
-                    if (ed) {                                           // code and difference in one lookup
-                        br.skip(ed & 31);
-                        diff = ed >> 8;
-                    } else {
-                        const int t = br.decode(dc[sl.td]);
-                        if (t < 0 || t > 16) return JPEG_AMD_EINVAL;
-                        diff = extend((int)br.get(t), t);
-                    }
-                    pred[ci] += diff;
-                    blk[0] = (int16_t)pred[ci];
-                    const Huffman &h = ac[sl.ta];
-                    for (int k = 1; k < 64;) {
-                        if (br.nbits < 32) br.refill();
-                        const uint32_t e = h.look_ac[br.peek(10)];
-                        if (e) {                                        // run, size and value -- or EOB / ZRL -- in one lookup
-                            br.skip((int)(e & 31));
-                            const int adv = (int)(e >> 5) & 31;
-                            if (adv == 0) break;                        // EOB
-                            k += adv;
-                            if ((e & 1024) && k <= 64) blk[k - 1] = (int16_t)(e >> 16);
-                            continue;
-                        }
-                        const int rs = br.decode(h);
-                        if (rs < 0) return JPEG_AMD_EINVAL;
-                        const int r = rs >> 4, sz = rs & 15;
-                        if (sz == 0) {
-                            if (r == 15) { k += 16; continue; }
-                            break;
-                        }
-                        k += r;
-                        const int v = extend((int)br.get(sz), sz);
-                        if (k < 64) blk[k] = (int16_t)v;
-                        ++k;
-                    }
-                } else if (ss == 0) {
-                    if (ah == 0) {   // DC first: T.81 G.1.2.1
-                        if (!dc[sl.td].defined) return JPEG_AMD_EINVAL;
-                        const int t = br.decode(dc[sl.td]);
-                        if (t < 0 || t > 16) return JPEG_AMD_EINVAL;
-                        pred[ci] += extend((int)br.get(t), t);
-                        blk[0] = (int16_t)(pred[ci] * (1 << al));
-                    } else if (br.get(1)) {
-                        blk[0] = (int16_t)(blk[0] | (1 << al));
-                    }
-                } else if (ah == 0) {   // AC first: T.81 G.1.2.2
-                    if (eobrun > 0) { --eobrun; continue; }
-                    if (!ac[sl.ta].defined) return JPEG_AMD_EINVAL;
-                    const Huffman &h = ac[sl.ta];
-                    for (int k = ss; k <= se;) {
-                        const int rs = br.decode(h);
-                        if (rs < 0) return JPEG_AMD_EINVAL;
-                        const int r = rs >> 4, s = rs & 15;
-                        if (s == 0) {
-                            if (r < 15) { eobrun = (1 << r) - 1; if (r) eobrun += (int)br.get(r); break; }
-                            k += 16;
-                            continue;
-                        }
-                        k += r;
-                        const int v = extend((int)br.get(s), s);
-                        if (k <= se) blk[k] = (int16_t)(v * (1 << al));
-                        ++k;
-                    }
-                } else {   // AC refinement: T.81 G.1.2.3
-                    if (!ac[sl.ta].defined) return JPEG_AMD_EINVAL;
-                    const Huffman &h = ac[sl.ta];
-                    const int p1 = 1 << al, m1 = -(1 << al);
-                    int k = ss;
-                    auto refine = [&](int16_t &cf) {
-                        if (br.get(1) && (cf & p1) == 0) cf = (int16_t)(cf >= 0 ? cf + p1 : cf + m1);
-                    };
-                    if (eobrun == 0) {
-                        for (; k <= se; ++k) {
-                            const int rs = br.decode(h);
-                            if (rs < 0) return JPEG_AMD_EINVAL;
-                            int r = rs >> 4;
-                            const int s = rs & 15;
-                            int val = 0;
-                            if (s) {
-                                val = br.get(1) ? p1 : m1;
-                            } else if (r < 15) {
-                                eobrun = 1 << r;
-                                if (r) eobrun += (int)br.get(r);
-                                break;
-                            }
-                            for (; k <= se; ++k) {
-                                if (blk[k] != 0) refine(blk[k]);
-                                else if (--r < 0) break;
-                            }
-                            if (s && k <= se) blk[k] = (int16_t)val;
-                        }
-                    }
-                    if (eobrun > 0) {
-                        for (; k <= se; ++k)
-                            if (blk[k] != 0) refine(blk[k]);
-                        --eobrun;
-                    }
-                }
-            }
-        }
-        return JPEG_AMD_OK;
-        };   // run_interval
-
-        // Sequential scans whose restart markers are all in place (or that have none): one restart interval from its own
-        // bytes [b, e), on a copy without stuffing.  A block is decoded into a local buffer (zero, then its few coefficients)
-        // and copied out whole, so the plane is written once, front to back, and never read.
-        const bool fast_sequential = !progressive && max_scans == 0x7fffffff;
-        if (sparse && !fast_sequential) return JPEG_AMD_ENOSUP;
-        std::vector<uint64_t> pair_tables;
-        std::vector<uint32_t> dc_tables;
-        const uint64_t *pair_of[16];
-        const uint32_t *dcx_of[16];
-        if (fast_sequential) {
-            for (int si = 0; si < nslots; ++si)
-                if (!dc[slots[si].td].defined || !ac[slots[si].ta].defined) return JPEG_AMD_EINVAL;
-            pair_tables.resize((size_t)kChainSize * 4);
-            dc_tables.resize((size_t)kChainSize * 16);
-            bool have_pair[4] = {false, false, false, false}, have_dcx[16] = {};
-            for (int si = 0; si < nslots; ++si) {
-                const int td = slots[si].td, ta = slots[si].ta, both = td * 4 + ta;
-                if (!have_pair[ta]) { build_chain_table(ac[ta], pair_tables.data() + (size_t)kChainSize * ta); have_pair[ta] = true; }
-                if (!have_dcx[both]) { build_dc_table(dc[td], ac[ta], dc_tables.data() + (size_t)kChainSize * both); have_dcx[both] = true; }
-                pair_of[si] = pair_tables.data() + (size_t)kChainSize * ta;
-                dcx_of[si] = dc_tables.data() + (size_t)kChainSize * both;
-            }
-        }
-        // One restart interval in flight: where its reader is, and which block comes next.
-        struct Walk {
-            CleanReader br{nullptr, nullptr};
-            int pred[4] = {0, 0, 0, 0};
-            long mcu = 0, mcu1 = 0;
-            int mx = 0, my = 0, si = 0;
-            bool streaming = false;
-            uint32_t *ent = nullptr, *ent_end = nullptr;   // sparse output: the next entry, the end of the arena
-            alignas(64) int16_t tmp[128];      // [64, 128): where the stores of a damaged stream land that run past the block
-        };
-        auto begin_walk = [&](Walk &w, const uint8_t *b, const uint8_t *e, long mcu0, long mcu1, std::vector<uint8_t> &scratch) {
-            const uint8_t *clean_end = unstuff(b, e, scratch);
-            w.br = CleanReader{scratch.data(), clean_end + 8};
-            size_t plane_bytes = 0;
-            w.streaming = true;
-            for (int j = 0; j < ns; ++j) {
-                w.streaming = w.streaming && (reinterpret_cast<uintptr_t>(sc[j].c->coef) & 15) == 0;
-                plane_bytes += (size_t)128 * sc[j].c->ux * sc[j].c->uy;
-            }
-            w.streaming = w.streaming && plane_bytes >= ((size_t)1 << 20);     // smaller planes stay in this core's cache
-            std::memset(w.tmp, 0, sizeof w.tmp);
-            w.mcu = mcu0; w.mcu1 = mcu1;
-            w.my = (int)(mcu0 / mcux); w.mx = (int)(mcu0 - (long)w.my * mcux);
-            w.si = 0;
-        };
-        // the next block of a walk (slot w.si of MCU w.mcu)
-        auto next_block = [&](Walk &w, auto sparse_kind) __attribute__((always_inline)) -> int {
-            constexpr bool SPARSE = decltype(sparse_kind)::value;
-            uint32_t *const ent0 = w.ent;
-            if constexpr (SPARSE) {
-                if (w.ent + jpeg_amd::kSparseDecoderHeadroom > w.ent_end) return JPEG_AMD_ENOSUP;      // the arena is full: the caller decodes this file densely
-            }
-            const Slot &sl = slots[w.si];
-            Component *c = sl.c;
-            const int x = ns > 1 ? w.mx * c->fx + sl.bx : w.mx, y = ns > 1 ? w.my * c->fy + sl.by : w.my;
-            const int ci = (int)(c - comps.data());
-            // ---- DC (T.81 F.2.2.1), together with an EOB right behind it where both fit the window ----
-            w.br.refill();
-            const uint32_t ed = dcx_of[w.si][w.br.acc >> (64 - kChainBits)];
-            bool done = false;
-            int budget = 0;                                      // valid bits a lookup may still count on
-            if (ed & 15) {
-                w.br.skip((int)(ed & 15));
-                budget = 56 - (int)(ed & 15);
-                w.pred[ci] += (int32_t)ed >> 16;
-                done = (ed & 64) != 0;
-            } else {
-                const int t = w.br.symbol(dc[sl.td]);
-                if (t > 16) return JPEG_AMD_EINVAL;
-                if (t) w.pred[ci] += w.br.magnitude(t);
-            }
-            if constexpr (SPARSE) *w.ent++ = sparse_fmt::make((uint16_t)(int16_t)w.pred[ci], 0);
-            else w.tmp[0] = (int16_t)w.pred[ci];
-            // ---- AC (T.81 F.2.2.2) ----
-            int k = 1;
-            if (!done) {
-                const Huffman &h = ac[sl.ta];
-                const uint64_t *chains = pair_of[w.si];
-                while (k < 64) {
-                    if (budget < kChainBits) { w.br.refill(); budget = 56; }
-                    uint64_t en = chains[w.br.acc >> (64 - kChainBits)];
-                    if (__builtin_expect(k + (int)((en >> 26) & 63) > 63, 0)) {
-                        // a symbol in the middle of the entry would complete the block: one symbol at a time
-                        const uint32_t e1 = h.look_ac[w.br.peek10()];
-                        const uint64_t n1 = (e1 >> 5) & 31;
-                        en = e1 == 0 ? 0 : (uint64_t)(e1 & 31) | (n1 << 18) | (n1 ? 0 : 1ull << 25)
-                             | (e1 & 1024 ? ((n1 - 1) << 4) | ((n1 - 1) << 11) | ((uint64_t)(e1 >> 16) << 32) | ((uint64_t)(e1 >> 16) << 48) : 0);
-                    }
-                    const int n = (int)(en & 15);
-                    if (__builtin_expect(n == 0, 0)) {           // a code + magnitude longer than 10 bits: the long way
-                        w.br.refill();
-                        budget = 0;
-                        const int rs = w.br.symbol(h);
-                        const int r = rs >> 4, sz = rs & 15;
-                        if (sz == 0) {
-                            if (r != 15) break;
-                            k += 16;
-                            continue;
-                        }
-                        k += r;
-                        if constexpr (SPARSE) *w.ent++ = sparse_fmt::make((uint16_t)(int16_t)w.br.magnitude(sz), (uint32_t)k);
-                        else w.tmp[k] = (int16_t)w.br.magnitude(sz);  // k <= 63 + 15
-                        ++k;
-                        continue;
-                    }
-                    w.br.skip(n);
-                    budget -= n;
-                    if constexpr (SPARSE) {
-                        // the entry's two stores: both written, the cursor advanced by the number that are real (a
-                        // coefficient is never zero; an entry without one has value 0, one with a single one repeats it)
-                        const uint32_t a1 = (uint32_t)(en >> 4) & 127, a2 = (uint32_t)(en >> 11) & 127;
-                        const uint32_t v1 = (uint32_t)(en >> 32) & 0xffffu, v2 = (uint32_t)(en >> 48);
-                        w.ent[0] = sparse_fmt::make(v1, (uint32_t)k + a1);
-                        w.ent[1] = sparse_fmt::make(v2, (uint32_t)k + a2);
-                        w.ent += (v1 != 0) + (a1 != a2);
-                    } else {
-                        w.tmp[k + ((en >> 4) & 127)] = (int16_t)(en >> 32);
-                        w.tmp[k + ((en >> 11) & 127)] = (int16_t)(en >> 48);
-                    }
-                    k += (int)(en >> 18) & 127;
-                    if (en & (1ull << 25)) break;
-                }
-            }
-            if constexpr (SPARSE) {
-                if (x < c->ux && y < c->uy) {
-                    if (__builtin_expect(k > 64, 0)) {                   // a damaged stream ran past the block: drop what lies beyond
-                        uint32_t *keep = ent0;
-                        for (const uint32_t *q = ent0; q < w.ent; ++q)
-                            if ((*q >> sparse_fmt::kZigzagShift) < 64) *keep++ = *q;   // (the whole index: no flag is set yet)
-                        w.ent = keep;                                    // (the DC entry is always kept)
-                    }
-                    w.ent[-1] |= sparse_fmt::kLast;
-                    sparse->desc[c->first_block + (size_t)c->ux * y + x] = (uint32_t)(ent0 - sparse->entries);
-                } else {
-                    w.ent = ent0;                                        // decoded and dropped (decode.swift:1459-1475)
-                }
-            } else {
-                if (x < c->ux && y < c->uy) store_block(c->coef + (size_t)64 * ((size_t)c->ux * y + x), w.tmp, w.streaming);
-                std::memset(w.tmp, 0, 128);
-            }
-            if (++w.si == nslots) {
-                w.si = 0;
-                ++w.mcu;
-                if (++w.mx == mcux) { w.mx = 0; ++w.my; }
-            }
-            return JPEG_AMD_OK;
-        };
-        auto end_walk = [&](Walk &w) {
-#if JA_X86_STREAMING
-            if (w.streaming) _mm_sfence();
-#else
-            (void)w;
-#endif
-        };
-        auto seq_interval = [&](const uint8_t *b, const uint8_t *e, long mcu0, long mcu1, std::vector<uint8_t> &scratch) -> int {
-            Walk w;
-            begin_walk(w, b, e, mcu0, mcu1, scratch);
-            if (sparse) {                                                // (one interval after the other: the arena is shared)
-                w.ent = sparse->entries + sparse->n;
-                w.ent_end = sparse->entries + sparse->capacity;
-                while (w.mcu < w.mcu1) {
-                    const int st = next_block(w, std::true_type{});
-                    if (st != JPEG_AMD_OK) return st;
-                }
-                sparse->n = (size_t)(w.ent - sparse->entries);
-                return JPEG_AMD_OK;
-            }
-            while (w.mcu < w.mcu1) {
-                const int st = next_block(w, std::false_type{});
-                if (st != JPEG_AMD_OK) return st;
-            }
-            end_walk(w);
-            return JPEG_AMD_OK;
-        };
-        const long nintervals = (total + ri - 1) / ri;
-        // a thread is worth starting for a few thousand blocks, not less
-        const long useful = std::min<long>(nthreads, std::min<long>(nintervals, auto_threads ? total * nslots / 4096 : nintervals));
-        if (useful > 1 || fast_sequential) {
-            // Restart-interval-parallel decoding: the intervals of a scan are
-            // independent bit streams separated by RSTn markers.  Only when every marker is
-            // where it should be; a damaged stream takes the careful path below, which
-            // resynchronises like the reference.
-            std::vector<const uint8_t *> starts{ecs};
-            if (nintervals > 1)
-                for (const uint8_t *q = ecs; q + 1 < end;) {
-                    q = static_cast<const uint8_t *>(std::memchr(q, 0xff, (size_t)(end - 1 - q)));
-                    if (!q) break;
-                    if (q[1] >= 0xd0 && q[1] <= 0xd7) starts.push_back(q + 2);
-                    q += q[1] == 0xff ? 1 : 2;          // 0xFF fill bytes may precede a marker
-                }
-            if ((long)starts.size() == nintervals) {
-                std::vector<int> status((size_t)nintervals, JPEG_AMD_OK);
-                const int t_n = (int)std::max<long>(1, useful);
-                auto work = [&](int t) {
-                    try {
-                        std::vector<uint8_t> scratch;
-                        auto first = [&](long i) { return starts[(size_t)i]; };
-                        auto last = [&](long i) { return i + 1 < nintervals ? starts[(size_t)i + 1] - 2 : end; };
-                        long k = t;
-                        for (; k < nintervals; k += t_n) {
-                            const uint8_t *b = first(k), *e = last(k);
-                            const long mcu0 = k * ri, mcu1 = std::min(total, (k + 1) * ri);
-                            if (fast_sequential) status[(size_t)k] = seq_interval(b, e, mcu0, mcu1, scratch);
-                            else {
-                                BitReader br(b, e);
-                                status[(size_t)k] = run_interval(br, mcu0, mcu1);
-                            }
-                        }
-                    } catch (...) {
-                        status[(size_t)t] = JPEG_AMD_ENOMEM;   // (t < t_n <= nintervals)
-                    }
-                };
-                std::vector<std::thread> pool;
-                int started = 1;
-                try {
-                    pool.reserve((size_t)t_n);
-                    for (int t = 1; t < t_n; ++t) { pool.emplace_back(work, t); ++started; }
-                } catch (...) {
-                }
-                for (int t = started; t < t_n; ++t) work(t);
-                work(0);
-                for (std::thread &th : pool) th.join();
-                for (int st : status) if (st != JPEG_AMD_OK) return st;
-                return JPEG_AMD_OK;
-            }
-        }
-        if (sparse) return JPEG_AMD_ENOSUP;          // a restart marker is missing: the resynchronising reader writes planes
-        BitReader br(ecs, end);
-        for (long k = 0; k < nintervals; ++k) {
-            if (k) br.restart();
-            const int st = run_interval(br, k * ri, std::min(total, (k + 1) * ri));
-            if (st != JPEG_AMD_OK) return st;
-        }
-        return JPEG_AMD_OK;
-    }
+    // ---- one scan (defined below, behind the readers it is made of) ----
+    int plan_scan(const uint8_t *hdr, size_t hlen, ScanPlan *plan);
+    int bind_tables(const ScanPlan &plan, uint16_t (*quanta_out)[64]);
+    int decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, const uint8_t *end, uint16_t (*quanta_out)[64]);
 
     // Walk the whole file.  coef == nullptr: headers only (fills info, counts scans).
     // Resumable: `pos`, `have_frame` and all tables live in the object.  With `streaming` set the
@@ -924,6 +548,46 @@ struct Decoder {
     bool have_frame = false, streaming = false, finished = false;
     std::vector<std::vector<int16_t>> own_planes;       // streaming: the decoder owns the planes
     uint16_t own_quanta[JPEG_AMD_MAX_PLANES][64];
+
+    // The frame header is in.  The stream decoder OWNS the planes: an attacker-chosen frame size must not make it allocate
+    // tens of gigabytes from a 20-byte header.  32 Mi blocks (4 GiB of coefficients, e.g. a 4:2:0 image of 37 000 x 37 000)
+    // is the cap; larger frames go through the one-shot entry points, where the caller allocates.
+    int own_the_planes()
+    {
+        long long blocks = 0;
+        for (int c = 0; c < info.ncomponents; ++c) blocks += (long long)comps[c].ux * comps[c].uy;
+        if (blocks > kStreamMaxBlocks) return JPEG_AMD_ENOMEM;
+        have_frame = true;
+        own_planes.assign((size_t)info.ncomponents, {});
+        for (int c = 0; c < info.ncomponents; ++c) {
+            own_planes[c].assign((size_t)64 * comps[c].ux * comps[c].uy, 0);
+            comps[c].coef = own_planes[c].data();
+            for (int z = 0; z < 64; ++z) own_quanta[c][z] = 1;
+        }
+        return JPEG_AMD_OK;
+    }
+    // The frame header is in, one-shot decode: the caller's planes, or the sparse record, become the components' output
+    // (neither: an inspect-only pass).
+    int bind_output(int16_t *const coef[])
+    {
+        have_frame = true;
+        if (sparse) {
+            if (info.process == 2) return JPEG_AMD_ENOSUP;      // progressive scans add to a block: planes only
+            size_t frame_blocks = 0;
+            for (const Component &c : comps) frame_blocks += (size_t)c.ux * c.uy;
+            if (frame_blocks > sparse->ndesc || frame_blocks >= sparse_fmt::kAbsent) return JPEG_AMD_EINVAL;   // the caller's array is too small
+            std::memset(sparse->desc, 0xff, frame_blocks * sizeof(uint32_t));
+            for (int c = 0; c < info.ncomponents; ++c) comps[c].coef = g_sparse_sentinel;
+        } else if (coef)
+            for (int c = 0; c < info.ncomponents; ++c) {
+                if (!coef[c]) return JPEG_AMD_EINVAL;
+                comps[c].coef = coef[c];
+                // progressive scans only add to a block; sequential ones clear it themselves
+                if (info.process == 2 || max_scans != 0x7fffffff)
+                    zero_plane(coef[c], (size_t)128 * comps[c].ux * comps[c].uy);
+            }
+        return JPEG_AMD_OK;
+    }
 
     int run(int16_t *const coef[], uint16_t (*quanta_out)[64])
     {
@@ -962,39 +626,7 @@ struct Decoder {
                     if (st == JPEG_AMD_OK)
                         for (int c = 0; c < info.ncomponents; ++c)     // the bound the device ABI puts on a plane (check_layout)
                             if ((long long)comps[c].ux * comps[c].uy > (1LL << 30)) return JPEG_AMD_EINVAL;
-                    if (st == JPEG_AMD_OK && streaming) {
-                        // the stream decoder OWNS the planes: an attacker-chosen frame size must not make it allocate
-                        // tens of gigabytes from a 20-byte header.  32 Mi blocks (4 GiB of coefficients, e.g. a 4:2:0
-                        // image of 37 000 x 37 000) is the cap; larger frames go through the one-shot entry points,
-                        // where the caller allocates.
-                        long long blocks = 0;
-                        for (int c = 0; c < info.ncomponents; ++c) blocks += (long long)comps[c].ux * comps[c].uy;
-                        if (blocks > kStreamMaxBlocks) return JPEG_AMD_ENOMEM;
-                        have_frame = true;
-                        own_planes.assign((size_t)info.ncomponents, {});
-                        for (int c = 0; c < info.ncomponents; ++c) {
-                            own_planes[c].assign((size_t)64 * comps[c].ux * comps[c].uy, 0);
-                            comps[c].coef = own_planes[c].data();
-                            for (int z = 0; z < 64; ++z) own_quanta[c][z] = 1;
-                        }
-                    } else if (st == JPEG_AMD_OK) {
-                        have_frame = true;
-                        if (sparse) {
-                            if (info.process == 2) return JPEG_AMD_ENOSUP;      // progressive scans add to a block: planes only
-                            size_t frame_blocks = 0;
-                            for (const Component &c : comps) frame_blocks += (size_t)c.ux * c.uy;
-                            if (frame_blocks > sparse->ndesc || frame_blocks >= sparse_fmt::kAbsent) return JPEG_AMD_EINVAL;   // the caller's array is too small
-                            std::memset(sparse->desc, 0xff, frame_blocks * sizeof(uint32_t));
-                            for (int c = 0; c < info.ncomponents; ++c) comps[c].coef = g_sparse_sentinel;
-                        } else if (coef)
-                            for (int c = 0; c < info.ncomponents; ++c) {
-                                if (!coef[c]) return JPEG_AMD_EINVAL;
-                                comps[c].coef = coef[c];
-                                // progressive scans only add to a block; sequential ones clear it themselves
-                                if (info.process == 2 || max_scans != 0x7fffffff)
-                                    zero_plane(coef[c], (size_t)128 * comps[c].ux * comps[c].uy);
-                            }
-                    }
+                    if (st == JPEG_AMD_OK) st = streaming ? own_the_planes() : bind_output(coef);
                     break;
                 case 0xc3: case 0xc5: case 0xc6: case 0xc7: case 0xc9: case 0xca: case 0xcb:
                 case 0xcd: case 0xce: case 0xcf:
@@ -1043,6 +675,502 @@ struct Decoder {
         return JPEG_AMD_OK;
     }
 };
+
+// ---- the careful reader: any scan, byte by byte ------------------------------------------------------------------------
+// One restart interval (or the whole scan): MCUs [mcu0, mcu1) from `br`, predictors and the EOB run starting from zero
+// (T.81 E.2.4).  Intervals touch disjoint blocks.  The Huffman tables are checked block by block: a scan that names an
+// undefined table fails at its first block.
+struct CarefulInterval {
+    const Decoder &d;
+    const ScanPlan &plan;
+    int pred[4] = {0, 0, 0, 0};
+    int eobrun = 0;
+    int16_t dummy[64];      // where the blocks go that an interleaved scan addresses beyond the plane
+
+    // sequential: the blocks of this MCU row that belong to the interval (`span` MCUs from mx) are cleared here, a row at a
+    // time -- large enough for the library's wide memset, small enough to still be in cache when they are filled (clearing the
+    // whole plane up front costs a quarter of the decode time; clearing block by block, 128 bytes at a time, a third)
+    void clear_mcu_row(int mx, int my, long span) const
+    {
+        for (int j = 0; j < plan.ns; ++j) {
+            Component *c = plan.sc[j].c;
+            const int fx = plan.ns > 1 ? c->fx : 1, fy = plan.ns > 1 ? c->fy : 1;
+            const int x0 = std::min(mx * fx, c->ux), x1 = (int)std::min<long>((mx + span) * fx, c->ux);
+            for (int y = my * fy; y < std::min(my * fy + fy, c->uy); ++y)
+                if (x1 > x0) std::memset(c->coef + (size_t)64 * ((size_t)c->ux * y + x0), 0, (size_t)128 * (x1 - x0));
+        }
+    }
+
+    // sequential: T.81 F.2.2, into a block that clear_mcu_row has cleared
+    int sequential_block(BitReader &br, const Slot &sl, int16_t *blk, int &pred_c) const
+    {
+        if (!d.dc[sl.td].defined || !d.ac[sl.ta].defined) return JPEG_AMD_EINVAL;
+        if (br.nbits < 32) br.refill();
+        int diff;
+        const int32_t ed = d.dc[sl.td].look_dc[br.peek(10)];
+        if (ed) {                                           // code and difference in one lookup
+            br.skip(ed & 31);
+            diff = ed >> 8;
+        } else {
+            const int t = br.decode(d.dc[sl.td]);
+            if (t < 0 || t > 16) return JPEG_AMD_EINVAL;
+            diff = extend((int)br.get(t), t);
+        }
+        pred_c += diff;
+        blk[0] = (int16_t)pred_c;
+        const Huffman &h = d.ac[sl.ta];
+        for (int k = 1; k < 64;) {
+            if (br.nbits < 32) br.refill();
+            const uint32_t e = h.look_ac[br.peek(10)];
+            if (e) {                                        // run, size and value -- or EOB / ZRL -- in one lookup
+                br.skip((int)(e & 31));
+                const int adv = (int)(e >> 5) & 31;
+                if (adv == 0) break;                        // EOB
+                k += adv;
+                if ((e & 1024) && k <= 64) blk[k - 1] = (int16_t)(e >> 16);
+                continue;
+            }
+            const int rs = br.decode(h);
+            if (rs < 0) return JPEG_AMD_EINVAL;
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz == 0) {
+                if (r == 15) { k += 16; continue; }
+                break;
+            }
+            k += r;
+            const int v = extend((int)br.get(sz), sz);
+            if (k < 64) blk[k] = (int16_t)v;
+            ++k;
+        }
+        return JPEG_AMD_OK;
+    }
+
+    // DC first: T.81 G.1.2.1
+    int dc_first(BitReader &br, const Slot &sl, int16_t *blk, int &pred_c) const
+    {
+        if (!d.dc[sl.td].defined) return JPEG_AMD_EINVAL;
+        const int t = br.decode(d.dc[sl.td]);
+        if (t < 0 || t > 16) return JPEG_AMD_EINVAL;
+        pred_c += extend((int)br.get(t), t);
+        blk[0] = (int16_t)(pred_c * (1 << plan.al));
+        return JPEG_AMD_OK;
+    }
+
+    // DC refinement: one bit per block
+    void dc_refine(BitReader &br, int16_t *blk) const
+    {
+        if (br.get(1)) blk[0] = (int16_t)(blk[0] | (1 << plan.al));
+    }
+
+    // AC first: T.81 G.1.2.2
+    int ac_first(BitReader &br, const Slot &sl, int16_t *blk)
+    {
+        if (eobrun > 0) { --eobrun; return JPEG_AMD_OK; }
+        if (!d.ac[sl.ta].defined) return JPEG_AMD_EINVAL;
+        const Huffman &h = d.ac[sl.ta];
+        const int se = plan.se, al = plan.al;
+        for (int k = plan.ss; k <= se;) {
+            const int rs = br.decode(h);
+            if (rs < 0) return JPEG_AMD_EINVAL;
+            const int r = rs >> 4, s = rs & 15;
+            if (s == 0) {
+                if (r < 15) { eobrun = (1 << r) - 1; if (r) eobrun += (int)br.get(r); break; }
+                k += 16;
+                continue;
+            }
+            k += r;
+            const int v = extend((int)br.get(s), s);
+            if (k <= se) blk[k] = (int16_t)(v * (1 << al));
+            ++k;
+        }
+        return JPEG_AMD_OK;
+    }
+
+    // AC refinement: T.81 G.1.2.3
+    int ac_refine(BitReader &br, const Slot &sl, int16_t *blk)
+    {
+        if (!d.ac[sl.ta].defined) return JPEG_AMD_EINVAL;
+        const Huffman &h = d.ac[sl.ta];
+        const int se = plan.se, p1 = 1 << plan.al, m1 = -(1 << plan.al);
+        int k = plan.ss;
+        auto refine = [&](int16_t &cf) {
+            if (br.get(1) && (cf & p1) == 0) cf = (int16_t)(cf >= 0 ? cf + p1 : cf + m1);
+        };
+        if (eobrun == 0) {
+            for (; k <= se; ++k) {
+                const int rs = br.decode(h);
+                if (rs < 0) return JPEG_AMD_EINVAL;
+                int r = rs >> 4;
+                const int s = rs & 15;
+                int val = 0;
+                if (s) {
+                    val = br.get(1) ? p1 : m1;
+                } else if (r < 15) {
+                    eobrun = 1 << r;
+                    if (r) eobrun += (int)br.get(r);
+                    break;
+                }
+                for (; k <= se; ++k) {
+                    if (blk[k] != 0) refine(blk[k]);
+                    else if (--r < 0) break;
+                }
+                if (s && k <= se) blk[k] = (int16_t)val;
+            }
+        }
+        if (eobrun > 0) {
+            for (; k <= se; ++k)
+                if (blk[k] != 0) refine(blk[k]);
+            --eobrun;
+        }
+        return JPEG_AMD_OK;
+    }
+
+    int run(BitReader &br, long mcu0, long mcu1)
+    {
+        const int mcux = plan.mcux;
+        int my = (int)(mcu0 / mcux), mx = (int)(mcu0 - (long)my * mcux) - 1;
+        for (long mcu = mcu0; mcu < mcu1; ++mcu) {
+            if (++mx == mcux) { mx = 0; ++my; }
+            if (!plan.progressive && (mx == 0 || mcu == mcu0))
+                clear_mcu_row(mx, my, std::min<long>(mcux - mx, mcu1 - mcu));     // MCUs of this row inside the interval
+            for (int si = 0; si < plan.nslots; ++si) {
+                const Slot &sl = plan.slots[si];
+                Component *c = sl.c;
+                const BlockAt at = block_at(plan, sl, mx, my);
+                const bool inside = at.x < c->ux && at.y < c->uy;
+                int16_t *blk = inside ? c->coef + (size_t)64 * ((size_t)c->ux * at.y + at.x) : dummy;
+                const int ci = (int)(c - d.comps.data());
+                if (!inside) std::memset(dummy, 0, sizeof dummy);
+                int st = JPEG_AMD_OK;
+                switch (plan.kind) {
+                    case BlockKind::Sequential: st = sequential_block(br, sl, blk, pred[ci]); break;
+                    case BlockKind::DcFirst: st = dc_first(br, sl, blk, pred[ci]); break;
+                    case BlockKind::DcRefine: dc_refine(br, blk); break;
+                    case BlockKind::AcFirst: st = ac_first(br, sl, blk); break;
+                    case BlockKind::AcRefine: st = ac_refine(br, sl, blk); break;
+                }
+                if (st != JPEG_AMD_OK) return st;
+            }
+        }
+        return JPEG_AMD_OK;
+    }
+};
+
+// ---- the fast reader: sequential scans whose restart markers are all in place (or that have none) -------------------------
+// The chain and DC tables of a scan's slots, built once per scan.
+struct FastTables {
+    std::vector<uint64_t> pair_tables;
+    std::vector<uint32_t> dc_tables;
+    const uint64_t *pair_of[16];
+    const uint32_t *dcx_of[16];
+
+    int build(const Decoder &d, const ScanPlan &plan)
+    {
+        for (int si = 0; si < plan.nslots; ++si)
+            if (!d.dc[plan.slots[si].td].defined || !d.ac[plan.slots[si].ta].defined) return JPEG_AMD_EINVAL;
+        pair_tables.resize((size_t)kChainSize * 4);
+        dc_tables.resize((size_t)kChainSize * 16);
+        bool have_pair[4] = {false, false, false, false}, have_dcx[16] = {};
+        for (int si = 0; si < plan.nslots; ++si) {
+            const int td = plan.slots[si].td, ta = plan.slots[si].ta, both = td * 4 + ta;
+            if (!have_pair[ta]) { build_chain_table(d.ac[ta], pair_tables.data() + (size_t)kChainSize * ta); have_pair[ta] = true; }
+            if (!have_dcx[both]) { build_dc_table(d.dc[td], d.ac[ta], dc_tables.data() + (size_t)kChainSize * both); have_dcx[both] = true; }
+            pair_of[si] = pair_tables.data() + (size_t)kChainSize * ta;
+            dcx_of[si] = dc_tables.data() + (size_t)kChainSize * both;
+        }
+        return JPEG_AMD_OK;
+    }
+};
+
+// What every interval of such a scan reads.  One restart interval comes from its own bytes [b, e), on a copy without
+// stuffing.  A block is decoded into a local buffer (zero, then its few coefficients) and copied out whole, so the plane is
+// written once, front to back, and never read -- or its coefficients go to the sparse record as entries.
+struct FastScan {
+    const Decoder &d;
+    const ScanPlan &plan;
+    const FastTables &tables;
+
+    int interval(const uint8_t *b, const uint8_t *e, long mcu0, long mcu1, std::vector<uint8_t> &scratch) const;
+};
+
+// One restart interval in flight: where its reader is, and which block comes next.
+struct Walk {
+    CleanReader br{nullptr, nullptr};
+    int pred[4] = {0, 0, 0, 0};
+    long mcu = 0, mcu1 = 0;
+    int mx = 0, my = 0, si = 0;
+    bool streaming = false;
+    uint32_t *ent = nullptr, *ent_end = nullptr;   // sparse output: the next entry, the end of the arena
+    alignas(64) int16_t tmp[128];      // [64, 128): where the stores of a damaged stream land that run past the block
+
+    Walk(const FastScan &fs, const uint8_t *b, const uint8_t *e, long mcu0, long mcu_end, std::vector<uint8_t> &scratch)
+    {
+        const uint8_t *clean_end = unstuff(b, e, scratch);
+        br = CleanReader{scratch.data(), clean_end + 8};
+        size_t plane_bytes = 0;
+        streaming = true;
+        for (int j = 0; j < fs.plan.ns; ++j) {
+            const Component *c = fs.plan.sc[j].c;
+            streaming = streaming && (reinterpret_cast<uintptr_t>(c->coef) & 15) == 0;
+            plane_bytes += (size_t)128 * c->ux * c->uy;
+        }
+        streaming = streaming && plane_bytes >= ((size_t)1 << 20);     // smaller planes stay in this core's cache
+        std::memset(tmp, 0, sizeof tmp);
+        mcu = mcu0; mcu1 = mcu_end;
+        my = (int)(mcu0 / fs.plan.mcux); mx = (int)(mcu0 - (long)my * fs.plan.mcux);
+        si = 0;
+    }
+
+    // the next block of the walk (slot si of MCU mcu)
+    template <bool SPARSE>
+    __attribute__((always_inline)) int next(const FastScan &fs)
+    {
+        uint32_t *const ent0 = ent;
+        if constexpr (SPARSE) {
+            if (ent + jpeg_amd::kSparseDecoderHeadroom > ent_end) return JPEG_AMD_ENOSUP;      // the arena is full: the caller decodes this file densely
+        }
+        const Slot &sl = fs.plan.slots[si];
+        Component *c = sl.c;
+        const BlockAt at = block_at(fs.plan, sl, mx, my);
+        const int x = at.x, y = at.y;
+        const int ci = (int)(c - fs.d.comps.data());
+        // ---- DC (T.81 F.2.2.1), together with an EOB right behind it where both fit the window ----
+        br.refill();
+        const uint32_t ed = fs.tables.dcx_of[si][br.acc >> (64 - kChainBits)];
+        bool done = false;
+        int budget = 0;                                      // valid bits a lookup may still count on
+        if (ed & 15) {
+            br.skip((int)(ed & 15));
+            budget = 56 - (int)(ed & 15);
+            pred[ci] += (int32_t)ed >> 16;
+            done = (ed & 64) != 0;
+        } else {
+            const int t = br.symbol(fs.d.dc[sl.td]);
+            if (t > 16) return JPEG_AMD_EINVAL;
+            if (t) pred[ci] += br.magnitude(t);
+        }
+        if constexpr (SPARSE) *ent++ = sparse_fmt::make((uint16_t)(int16_t)pred[ci], 0);
+        else tmp[0] = (int16_t)pred[ci];
+        // ---- AC (T.81 F.2.2.2) ----
+        int k = 1;
+        if (!done) {
+            const Huffman &h = fs.d.ac[sl.ta];
+            const uint64_t *chains = fs.tables.pair_of[si];
+            while (k < 64) {
+                if (budget < kChainBits) { br.refill(); budget = 56; }
+                uint64_t en = chains[br.acc >> (64 - kChainBits)];
+                if (__builtin_expect(k + (int)((en >> 26) & 63) > 63, 0)) {
+                    // a symbol in the middle of the entry would complete the block: one symbol at a time
+                    const uint32_t e1 = h.look_ac[br.peek10()];
+                    const uint64_t n1 = (e1 >> 5) & 31;
+                    en = e1 == 0 ? 0 : (uint64_t)(e1 & 31) | (n1 << 18) | (n1 ? 0 : 1ull << 25)
+                         | (e1 & 1024 ? ((n1 - 1) << 4) | ((n1 - 1) << 11) | ((uint64_t)(e1 >> 16) << 32) | ((uint64_t)(e1 >> 16) << 48) : 0);
+                }
+                const int n = (int)(en & 15);
+                if (__builtin_expect(n == 0, 0)) {           // a code + magnitude longer than 10 bits: the long way
+                    br.refill();
+                    budget = 0;
+                    const int rs = br.symbol(h);
+                    const int r = rs >> 4, sz = rs & 15;
+                    if (sz == 0) {
+                        if (r != 15) break;
+                        k += 16;
+                        continue;
+                    }
+                    k += r;
+                    if constexpr (SPARSE) *ent++ = sparse_fmt::make((uint16_t)(int16_t)br.magnitude(sz), (uint32_t)k);
+                    else tmp[k] = (int16_t)br.magnitude(sz);  // k <= 63 + 15
+                    ++k;
+                    continue;
+                }
+                br.skip(n);
+                budget -= n;
+                if constexpr (SPARSE) {
+                    // the entry's two stores: both written, the cursor advanced by the number that are real (a
+                    // coefficient is never zero; an entry without one has value 0, one with a single one repeats it)
+                    const uint32_t a1 = (uint32_t)(en >> 4) & 127, a2 = (uint32_t)(en >> 11) & 127;
+                    const uint32_t v1 = (uint32_t)(en >> 32) & 0xffffu, v2 = (uint32_t)(en >> 48);
+                    ent[0] = sparse_fmt::make(v1, (uint32_t)k + a1);
+                    ent[1] = sparse_fmt::make(v2, (uint32_t)k + a2);
+                    ent += (v1 != 0) + (a1 != a2);
+                } else {
+                    tmp[k + ((en >> 4) & 127)] = (int16_t)(en >> 32);
+                    tmp[k + ((en >> 11) & 127)] = (int16_t)(en >> 48);
+                }
+                k += (int)(en >> 18) & 127;
+                if (en & (1ull << 25)) break;
+            }
+        }
+        if constexpr (SPARSE) {
+            if (x < c->ux && y < c->uy) {
+                if (__builtin_expect(k > 64, 0)) {                   // a damaged stream ran past the block: drop what lies beyond
+                    uint32_t *keep = ent0;
+                    for (const uint32_t *q = ent0; q < ent; ++q)
+                        if ((*q >> sparse_fmt::kZigzagShift) < 64) *keep++ = *q;   // (the whole index: no flag is set yet)
+                    ent = keep;                                      // (the DC entry is always kept)
+                }
+                ent[-1] |= sparse_fmt::kLast;
+                fs.d.sparse->desc[c->first_block + (size_t)c->ux * y + x] = (uint32_t)(ent0 - fs.d.sparse->entries);
+            } else {
+                ent = ent0;                                          // decoded and dropped (decode.swift:1459-1475)
+            }
+        } else {
+            if (x < c->ux && y < c->uy) store_block(c->coef + (size_t)64 * ((size_t)c->ux * y + x), tmp, streaming);
+            std::memset(tmp, 0, 128);
+        }
+        if (++si == fs.plan.nslots) {
+            si = 0;
+            ++mcu;
+            if (++mx == fs.plan.mcux) { mx = 0; ++my; }
+        }
+        return JPEG_AMD_OK;
+    }
+
+    void end() const
+    {
+#if JA_X86_STREAMING
+        if (streaming) _mm_sfence();
+#endif
+    }
+};
+
+int FastScan::interval(const uint8_t *b, const uint8_t *e, long mcu0, long mcu1, std::vector<uint8_t> &scratch) const
+{
+    Walk w(*this, b, e, mcu0, mcu1, scratch);
+    if (SparseOut *sparse = d.sparse) {                          // (one interval after the other: the arena is shared)
+        w.ent = sparse->entries + sparse->n;
+        w.ent_end = sparse->entries + sparse->capacity;
+        while (w.mcu < w.mcu1) {
+            const int st = w.next<true>(*this);
+            if (st != JPEG_AMD_OK) return st;
+        }
+        sparse->n = (size_t)(w.ent - sparse->entries);
+        return JPEG_AMD_OK;
+    }
+    while (w.mcu < w.mcu1) {
+        const int st = w.next<false>(*this);
+        if (st != JPEG_AMD_OK) return st;
+    }
+    w.end();
+    return JPEG_AMD_OK;
+}
+
+// ---- one scan ----------------------------------------------------------------------------------------------------------
+// The scan header into `plan`.  EINVAL: the header is malformed.  ENOSUP: more than 16 blocks in an MCU -- the geometry's
+// verdict, which decode_scan holds back behind the table binding and the inspect-only return.
+int Decoder::plan_scan(const uint8_t *hdr, size_t hlen, ScanPlan *plan)
+{
+    if (hlen < 1) return JPEG_AMD_EINVAL;
+    const int ns = plan->ns = hdr[0];
+    if (ns < 1 || ns > 4 || hlen < 4 + 2 * (size_t)ns) return JPEG_AMD_EINVAL;
+    ScanComp *sc = plan->sc;
+    for (int j = 0; j < ns; ++j) {
+        const int cid = hdr[1 + 2 * j], tt = hdr[2 + 2 * j];
+        Component *c = nullptr;
+        for (Component &x : comps) if (x.id == cid) c = &x;
+        if (!c) return JPEG_AMD_EINVAL;
+        sc[j] = {c, tt >> 4, tt & 15};
+        if (sc[j].td > 3 || sc[j].ta > 3) return JPEG_AMD_EINVAL;
+    }
+    const int ss = plan->ss = hdr[1 + 2 * ns], se = plan->se = hdr[2 + 2 * ns];
+    const int ah = plan->ah = hdr[3 + 2 * ns] >> 4;
+    plan->al = hdr[3 + 2 * ns] & 15;
+    const bool progressive = plan->progressive = info.process == 2;
+    if (se > 63 || ss > se) return JPEG_AMD_EINVAL;
+    if (progressive && ss > 0 && ns != 1) return JPEG_AMD_EINVAL;
+    // (a sequential scan is decoded as the full band whatever its header says of ss, se, ah and al)
+    plan->kind = !progressive ? BlockKind::Sequential
+               : ss == 0 ? (ah == 0 ? BlockKind::DcFirst : BlockKind::DcRefine)
+               : (ah == 0 ? BlockKind::AcFirst : BlockKind::AcRefine);
+
+    // MCU geometry
+    plan->nslots = 0;
+    if (ns > 1) {
+        plan->mcux = units(info.width, 8 * info.scale_x);
+        plan->mcuy = units(info.height, 8 * info.scale_y);
+        for (int j = 0; j < ns; ++j)
+            for (int by = 0; by < sc[j].c->fy; ++by)
+                for (int bx = 0; bx < sc[j].c->fx; ++bx) {
+                    if (plan->nslots >= 16) return JPEG_AMD_ENOSUP;
+                    plan->slots[plan->nslots++] = {sc[j].c, sc[j].td, sc[j].ta, bx, by};
+                }
+    } else {
+        plan->mcux = sc[0].c->ux; plan->mcuy = sc[0].c->uy;
+        plan->slots[plan->nslots++] = {sc[0].c, sc[0].td, sc[0].ta, 0, 0};
+    }
+    plan->total = (long)plan->mcux * plan->mcuy;
+    plan->ri = restart_interval ? restart_interval : plan->total;
+    plan->nintervals = (plan->total + plan->ri - 1) / plan->ri;
+    return JPEG_AMD_OK;
+}
+
+// Quantisation tables are bound at a component's first scan, from whatever the DQT slot holds then.
+int Decoder::bind_tables(const ScanPlan &plan, uint16_t (*quanta_out)[64])
+{
+    if (plan.ah != 0 || plan.ss != 0) return JPEG_AMD_OK;
+    for (int j = 0; j < plan.ns; ++j) {
+        Component *c = plan.sc[j].c;
+        if (!qdefined[c->tq]) return JPEG_AMD_EINVAL;
+        if (quanta_out) std::memcpy(quanta_out[c - comps.data()], qslots[c->tq], 128);
+        c->bound = true;
+    }
+    return JPEG_AMD_OK;
+}
+
+int Decoder::decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, const uint8_t *end, uint16_t (*quanta_out)[64])
+{
+    ScanPlan plan;
+    const int planned = plan_scan(hdr, hlen, &plan);
+    if (planned == JPEG_AMD_EINVAL) return planned;
+    const int bound = bind_tables(plan, quanta_out);
+    if (bound != JPEG_AMD_OK) return bound;
+    if (!comps[0].coef) return JPEG_AMD_OK;   // inspect-only pass
+    if (planned != JPEG_AMD_OK) return planned;
+
+    const bool fast_sequential = !plan.progressive && max_scans == 0x7fffffff;
+    if (sparse && !fast_sequential) return JPEG_AMD_ENOSUP;
+    FastTables tables;
+    if (fast_sequential) {
+        const int st = tables.build(*this, plan);
+        if (st != JPEG_AMD_OK) return st;
+    }
+    const FastScan fast{*this, plan, tables};
+    const long total = plan.total, ri = plan.ri, nintervals = plan.nintervals;
+    // a thread is worth starting for a few thousand blocks, not less
+    const long useful = std::min<long>(nthreads, std::min<long>(nintervals, auto_threads ? total * plan.nslots / 4096 : nintervals));
+    if (useful > 1 || fast_sequential) {
+        // Restart-interval-parallel decoding: the intervals of a scan are independent bit streams separated
+        // by RSTn markers.  Only when every marker is where it should be; a damaged stream takes the careful path below,
+        // which resynchronises like the reference.
+        const std::vector<const uint8_t *> starts = find_interval_starts(ecs, end, nintervals);
+        if ((long)starts.size() == nintervals) {
+            std::vector<int> status((size_t)nintervals, JPEG_AMD_OK);
+            const int t_n = (int)std::max<long>(1, useful);
+            run_on_threads(t_n, [&](int t) {             // (t < t_n <= nintervals: status[t] exists)
+                std::vector<uint8_t> scratch;
+                for (long k = t; k < nintervals; k += t_n) {
+                    const uint8_t *b = starts[(size_t)k], *e = k + 1 < nintervals ? starts[(size_t)k + 1] - 2 : end;
+                    const long mcu0 = k * ri, mcu1 = std::min(total, (k + 1) * ri);
+                    if (fast_sequential) status[(size_t)k] = fast.interval(b, e, mcu0, mcu1, scratch);
+                    else {
+                        BitReader br(b, e);
+                        status[(size_t)k] = CarefulInterval{*this, plan}.run(br, mcu0, mcu1);
+                    }
+                }
+            }, status.data());
+            for (int st : status) if (st != JPEG_AMD_OK) return st;
+            return JPEG_AMD_OK;
+        }
+    }
+    if (sparse) return JPEG_AMD_ENOSUP;          // a restart marker is missing: the resynchronising reader writes planes
+    BitReader br(ecs, end);
+    for (long k = 0; k < nintervals; ++k) {
+        if (k) br.restart();
+        const int st = CarefulInterval{*this, plan}.run(br, k * ri, std::min(total, (k + 1) * ri));
+        if (st != JPEG_AMD_OK) return st;
+    }
+    return JPEG_AMD_OK;
+}
 
 }  // namespace
 

@@ -23,6 +23,21 @@ def test_entropy_coder_is_clean_under_asan_and_ubsan(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])
 
 
+def test_entropy_decoder_threads_are_clean_under_tsan(tmp_path):
+    """The same program under ThreadSanitizer on the fixtures with restart markers, the files whose intervals the decoder
+    shares among threads (csrc/entropy.cpp, run_on_threads: the 4-thread decode of the intact file, the 3-thread decode of
+    every other damaged copy, the shared clearing of a plane); built and run as the two tests below."""
+    exe = str(tmp_path / "entropy_tsan")
+    src = [os.path.join(ROOT, "tests", "cpp", "entropy_sanitize.cpp"),
+           os.path.join(ROOT, "jpeg_amd", "csrc", "entropy.cpp"), os.path.join(ROOT, "jpeg_amd", "csrc", "entropy_encode.cpp")]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I", os.path.join(ROOT, "include"), *src,
+                           "-o", exe, "-lpthread"])
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "decode", "*-restart.jpg")))
+    assert len(files) >= 3
+    r = subprocess.run(["setarch", platform.machine(), "-R", exe, *files], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-800:], r.stderr[-2000:])
+
+
 def test_worker_pool_is_clean_under_tsan(tmp_path):
     """The host thread pool of the batch file paths (csrc/worker_pool.hpp) under ThreadSanitizer: regions of every size and
     thread limit on pools of 1, 2, 5 and 16 threads -- every item exactly once, never more threads than the region was given,

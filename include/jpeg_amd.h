@@ -303,11 +303,29 @@ int jpeg_amd_jpeg_decode_sparse(const uint8_t *data, size_t nbytes, uint32_t *h_
 /* Sparse coefficients -> Spectral planes on the device (the other half of jpeg_amd_jpeg_decode_sparse): image i reads its
  * descriptors at d_desc + i * desc_stride and its entries at d_entries + i * entries_stride (elements) and has every block
  * of its planes d_coef[p] + i * coef_stride[p] written; d_skip (optional, one byte per image): nonzero = the image's planes
- * are left as they are.  Asynchronous on the context's stream. */
+ * are left as they are.  Asynchronous on the context's stream.  JPEG_AMD_EINVAL for a frame of 2^32 - 1 blocks or more
+ * (descriptors are 32-bit indices, and 0xFFFFFFFF means no block). */
 int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
                                    const uint32_t *d_desc, size_t desc_stride, const uint32_t *d_entries,
                                    size_t entries_stride, const uint8_t *d_skip, int16_t *const d_coef[],
                                    const size_t coef_stride[]);
+
+/* Spectral planes -> sparse coefficients on the device, the way back (what the batch compress calls run in front of
+ * jpeg_amd_jpeg_encode_sparse): image i reads its planes at d_coef[p] + i * coef_stride[p] and writes its descriptors at
+ * d_desc + i * desc_stride and its entries into the arena of `capacity` entries at d_entries + i * entries_stride (elements).
+ * Per block, planes in frame order: an entry for index 0 always, then one for every nonzero coefficient in ascending zigzag
+ * order, the last one flagged; the rows of the blocks lie in the arena in no particular order -- the descriptors say where.
+ *   d_count[i] is image i's entry count, whether the entries fit or not.
+ *   d_count[i] <= capacity: every descriptor of image i is written, and the rows tile [0, d_count[i]) of its arena, without
+ *     holes and without overlap; nothing behind them is written.
+ *   d_count[i] > capacity: the descriptors and entries of image i are unspecified, but nothing outside [0, capacity) of its
+ *     arena is written.
+ * Asynchronous on the context's stream.  JPEG_AMD_EINVAL for a frame of 2^26 blocks or more: the count is kept in 32 bits
+ * and takes up to 64 per block. */
+int jpeg_amd_spectral_sparsify_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *layout, int n_images,
+                                     const int16_t *const d_coef[], const size_t coef_stride[], uint32_t *d_desc,
+                                     size_t desc_stride, uint32_t *d_entries, size_t entries_stride, uint32_t capacity,
+                                     uint32_t *d_count);
 
 typedef struct jpeg_amd_stream jpeg_amd_stream;
 jpeg_amd_stream *jpeg_amd_stream_create(void);

@@ -89,6 +89,7 @@ SIGNATURES = {
     "jpeg_amd_jpeg_decode_spectral_mt": (C.c_int, [_p, C.c_size_t, _pp, _p, _p, C.c_int]),
     "jpeg_amd_jpeg_decode_spectral_partial": (C.c_int, [_p, C.c_size_t, _pp, _p, _p, C.c_int, C.c_int]),
     "jpeg_amd_spectral_expand_batch": (C.c_int, [_p, _L, C.c_int, _p, C.c_size_t, _p, C.c_size_t, _p, _pp, _szp]),
+    "jpeg_amd_spectral_sparsify_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, _p, C.c_size_t, C.c_uint32, _p]),
     "jpeg_amd_jpeg_decode_sparse": (C.c_int, [_p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p]),
     "jpeg_amd_stream_create": (C.c_void_p, []),
     "jpeg_amd_stream_destroy": (None, [_p]),

@@ -489,9 +489,27 @@ int jpeg_amd_spectral_expand_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, 
     if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
     if (n_images == 0) return JPEG_AMD_OK;
     if (!d_desc || !d_entries || !d_coef || !coef_stride) return JPEG_AMD_EINVAL;
+    JA_TRY(check_sparse_blocks(*L));
     PlaneSetMut cs;
     JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
     JA_HIP(ctx, launch_expand_sparse(ctx->stream, n_images, *L, d_desc, desc_stride, d_entries, entries_stride, d_skip, cs));
+    return JPEG_AMD_OK;
+}
+
+int jpeg_amd_spectral_sparsify_batch(jpeg_amd_ctx *ctx, const jpeg_amd_layout *L, int n_images, const int16_t *const d_coef[],
+                                     const size_t coef_stride[], uint32_t *d_desc, size_t desc_stride, uint32_t *d_entries,
+                                     size_t entries_stride, uint32_t capacity, uint32_t *d_count)
+{
+    JA_TRY(bind(ctx));
+    JA_TRY(check_layout(L, -1));
+    if (n_images < 0 || n_images > 65535) return JPEG_AMD_EINVAL;
+    if (n_images == 0) return JPEG_AMD_OK;
+    if (!d_coef || !coef_stride || !d_desc || !d_entries || !d_count) return JPEG_AMD_EINVAL;
+    // (the stricter of the two limits: a frame that check_sparse_blocks refuses is refused here)
+    if (!sparsify_count_fits(sparse_budget(*L).blocks)) return JPEG_AMD_EINVAL;   // d_count[i] would not be the entry count
+    PlaneSet cs;
+    JA_TRY(plane_set(L, d_coef, coef_stride, true, &cs));
+    JA_HIP(ctx, launch_sparsify(ctx->stream, n_images, *L, cs, d_desc, desc_stride, d_entries, entries_stride, capacity, d_count));
     return JPEG_AMD_OK;
 }
 
@@ -503,15 +521,13 @@ int check_expand_item(const jpeg_amd_expand_item &it, uint64_t *groups)
 {
     JA_TRY(check_layout(&it.layout, -1));
     if (it.head != 1 && it.head != 4 && it.head != 8) return JPEG_AMD_EINVAL;
-    uint64_t blocks = 0;
     for (int p = 0; p < it.layout.nplanes; ++p) {
         if (!it.d_coef[p] || reinterpret_cast<uintptr_t>(it.d_coef[p]) % 16 != 0) return JPEG_AMD_EINVAL;
         const jpeg_amd_region &w = it.window[p];
         if (w.x < 0 || w.y < 0 || w.width < 0 || w.height < 0) return JPEG_AMD_EINVAL;
         if ((long long)w.x + w.width > it.layout.units_x[p] || (long long)w.y + w.height > it.layout.units_y[p]) return JPEG_AMD_EINVAL;
-        blocks += (uint64_t)it.layout.units_x[p] * (uint64_t)it.layout.units_y[p];
     }
-    if (blocks >= sparse::kAbsent) return JPEG_AMD_EINVAL;   // descriptors are 32-bit indices, and one value means no block
+    JA_TRY(check_sparse_blocks(it.layout));
     *groups = expand_mixed_groups(it);
     return JPEG_AMD_OK;
 }

@@ -701,7 +701,8 @@ int compress_batch_impl(jpeg_amd_ctx *ctx, jpeg_amd_frame_info *frame, const uin
     // (jpeg_amd_jpeg_encode_sparse); a picture whose entries do not fit its arena comes down as planes, like every picture of a
     // progressive frame, or of a frame too large for 32-bit descriptors (sparse_budget).
     e.sb = sparse_budget(e.L);
-    e.sparse_down = frame->process != 2 && e.sb.ok;
+    // (... or of 2^26 blocks or more: k_sparsify's uint32 cursor could wrap, and the host would read a small count)
+    e.sparse_down = frame->process != 2 && e.sb.ok && sparsify_count_fits(e.sb.blocks);
     // slot layout (pinned and device alike): [pixels x chunk][coef plane 0 x chunk][plane 1 x chunk][plane 2 x chunk][sparse x chunk][counts]
     e.at.px_off = e.at.take(npx * e.chunk);
     for (int c = 0; c < nc; ++c) e.at.coef_off[c] = e.at.take(e.plane[c] * 2 * e.chunk);

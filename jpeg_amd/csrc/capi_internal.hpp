@@ -121,6 +121,16 @@ int reduce_n(int denom);   // (capi_spectral.hip)
 int check_tensor_source(int n_images, const void *d_src, size_t src_stride, int32_t w, int32_t h,
                         const jpeg_amd_tensor_source *src, size_t *elem_bytes);
 
+// What the calls that take or write a sparse record require of a frame's block count, summed in 64 bits: descriptors are
+// 32-bit indices, and one value means no block.
+inline int check_sparse_blocks(const jpeg_amd_layout &L)
+{
+    return sparse_budget(L).blocks >= sparse::kAbsent ? JPEG_AMD_EINVAL : JPEG_AMD_OK;
+}
+// k_sparsify's per-image cursor is a uint32 that takes up to 64 entries per block, fitting or not: only below 2^26 blocks is
+// the count it leaves the image's entry count.
+inline bool sparsify_count_fits(size_t blocks) { return 64 * (uint64_t)blocks < ((uint64_t)1 << 32); }
+
 // What jpeg_amd_spectral_expand_mixed requires of one item; *groups: the workgroups it takes (capi.hip).
 int check_expand_item(const jpeg_amd_expand_item &item, uint64_t *groups);
 // (check_resampled_mixed and decode_views_mixed, what the file calls use of the mixed resample calls: resample_request.hpp)

@@ -181,6 +181,7 @@ CALLS = {
     "jpeg_amd_spectral_reduce_batch": lambda a: (a.L, a.n, a.denom, a.pp, a.sz, a.p, 64, 2, None, a.pp, a.sz),
     "jpeg_amd_spectral_reduce": lambda a: (a.L, a.denom, a.pp, a.p, 2, None, a.pp),
     "jpeg_amd_spectral_expand_batch": lambda a: (a.L, a.n, a.p, 64, a.p, 64, None, a.pp, a.sz),
+    "jpeg_amd_spectral_sparsify_batch": lambda a: (a.L, a.n, a.pp, a.sz, a.p, 64, a.p, 64, 64, a.p),
     # the stages
     "jpeg_amd_idct_plane": lambda a: (a.p, 2, 2, a.p, a.precision, a.p),
     "jpeg_amd_spectral_idct": lambda a: (a.L, a.pp, a.p, 2, a.pp),
@@ -264,6 +265,7 @@ EXPECTED = {
     "jpeg_amd_spectral_reduce_batch": BIND_FIRST,
     "jpeg_amd_spectral_reduce": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),
     "jpeg_amd_spectral_expand_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
+    "jpeg_amd_spectral_sparsify_batch": (EINVAL, EINVAL, EINVAL, EINVAL, EINVAL, _),
     "jpeg_amd_idct_plane": (EINVAL, _, EINVAL, _, _, _),
     "jpeg_amd_spectral_idct": (EINVAL, EINVAL, EINVAL, EINVAL, _, _),
     "jpeg_amd_spectral_idct_scaled": (EINVAL, EINVAL, EINVAL, EINVAL, _, EINVAL),

@@ -83,6 +83,15 @@ int         jpeg_amd_device_count(int *count);
  * the device's default stream).  With JPEG_AMD_CTX_OWN_STREAM in flags, `stream` is
  * ignored and the ctx creates (and later destroys) a private non-blocking stream. */
 #define JPEG_AMD_CTX_OWN_STREAM 1
+/* With JPEG_AMD_CTX_DEVICE_ENTROPY in flags, the batch file calls (jpeg_amd_decompress_batch, _batch_device and every
+ * jpeg_amd_decompress_*_mixed call) ask jpeg_amd_jpeg_plan_intervals about each file first: a file it takes, whose
+ * entropy-coded bytes, tables and interval list fit the staging of its coefficient planes (of its first plane in the calls of
+ * one geometry; about 6 kB of that are Huffman tables, so images of a few blocks stay on the host), is uploaded as
+ * those bytes and Huffman-decoded on the device (k_huffman_intervals) in front of the chunk's other kernels; every other file
+ * takes the host route in the same chunk.  Results are the same either way.  A device file whose status is not OK ends the call
+ * with that status, as a file that proves damaged after the call has started does.  jpeg_amd_decompress (one file) and
+ * jpeg_amd_decompress_rectangular decode on the host whatever the flag says. */
+#define JPEG_AMD_CTX_DEVICE_ENTROPY 2
 int         jpeg_amd_ctx_create(int device, void *stream, int flags, jpeg_amd_ctx **ctx);
 int         jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx);
 int         jpeg_amd_ctx_synchronize(jpeg_amd_ctx *ctx);
@@ -299,6 +308,47 @@ int jpeg_amd_jpeg_decode_spectral_partial(const uint8_t *h_jpeg, size_t nbytes, 
 int jpeg_amd_jpeg_decode_sparse(const uint8_t *data, size_t nbytes, uint32_t *h_desc, size_t ndesc,
                                 uint32_t *h_entries, size_t capacity, size_t *nentries,
                                 uint16_t h_quanta[][64], jpeg_amd_frame_info *info);
+
+/* ---- entropy decoding on the device: one restart interval per work-item ------------------------------------------------
+ * The restart intervals of a sequential scan are independent bit streams (T.81 E.2.4): k_huffman_intervals decodes one per
+ * work-item, from the file's entropy-coded bytes in device memory into Spectral planes in device memory.  The decoder is
+ * csrc/huffman_interval.hpp, one statement for the kernel and for the host.
+ *
+ * jpeg_amd_jpeg_plan_intervals: whether a file takes that route, judged on the host from its headers and marker positions
+ * alone, and how much work it is (*nscans scans, *nintervals intervals in all; a file without DRI is one interval per scan).
+ *   JPEG_AMD_OK      a sequential Huffman frame, every scan of it sequential (interleaved or not), with every restart marker
+ *                    where DRI says it is -- the files jpeg_amd_jpeg_decode_sparse takes, however dense
+ *   JPEG_AMD_ENOSUP  a progressive frame; a missing or surplus restart marker; more than 16 blocks in an MCU; more than
+ *                    JPEG_AMD_MAX_DEVICE_INTERVALS intervals in the file; a component that two scans write (the device
+ *                    decodes all scans at once, and the later scan has to win)
+ *   JPEG_AMD_EINVAL  what jpeg_amd_jpeg_inspect and the entropy decoder call malformed, a scan that names an undefined
+ *                    Huffman table or an unbound quantisation table included
+ * Host only. */
+#define JPEG_AMD_MAX_DEVICE_INTERVALS (1 << 20)
+int jpeg_amd_jpeg_plan_intervals(const uint8_t *h_jpeg, size_t nbytes, jpeg_amd_frame_info *info, int32_t *nscans,
+                                 int64_t *nintervals);
+/* The host instantiation of the same decoder over the same work list, one interval after the other, into host planes: what
+ * the kernel computes, without a device.  Planes, tables and status are jpeg_amd_jpeg_decode_spectral's for every file the
+ * planner takes (the planner's status otherwise, with nothing written); the planes need no alignment. */
+int jpeg_amd_jpeg_decode_intervals_host(const uint8_t *h_jpeg, size_t nbytes, int16_t *const h_coef[],
+                                        uint16_t h_quanta[][64], jpeg_amd_frame_info *info);
+/* n_images files of ANY mix of geometries, entropy-decoded on the device.  File i writes whole planes d_coef[i][c] (device
+ * memory, int16 [units_y][units_x][64] zigzag, sized from jpeg_amd_jpeg_inspect, 16-byte aligned): byte for byte the planes
+ * of jpeg_amd_jpeg_decode_spectral, every block of every plane written.  h_quanta[i][c] and h_info[i] receive what that call
+ * gives; h_status[i] the file's status, the first that is not OK among its intervals in file order.
+ * Judged before anything is enqueued, the context last: a null pointer (EINVAL; of d_coef[i] the first ncomponents entries
+ * count) or a misaligned plane (EINVAL), a file the planner refuses (its status, for the whole call, nothing written).
+ * n_images == 0 is OK.  One upload (the entropy-coded bytes, the tables and the work list), one launch; the call waits and
+ * returns the first h_status[i] that is not OK.  The planes of a file whose status is not OK are unspecified. */
+int jpeg_amd_jpeg_decode_spectral_device(jpeg_amd_ctx *ctx, int n_images, const uint8_t *const h_jpeg[], const size_t nbytes[],
+                                         int16_t *const d_coef[][JPEG_AMD_MAX_PLANES],
+                                         uint16_t h_quanta[][JPEG_AMD_MAX_PLANES][64], jpeg_amd_frame_info *h_info,
+                                         int32_t *h_status);
+/* How many files the context has entropy-decoded on the device since it was made: those of
+ * jpeg_amd_jpeg_decode_spectral_device, and those that took the device route of the batch file calls. */
+int jpeg_amd_ctx_device_entropy_files(const jpeg_amd_ctx *ctx, int64_t *count);
+/* ... and the time k_huffman_intervals itself has taken for them, in milliseconds (HIP events around every launch). */
+int jpeg_amd_ctx_device_entropy_kernel_ms(const jpeg_amd_ctx *ctx, double *ms);
 
 /* Sparse coefficients -> Spectral planes on the device (the other half of jpeg_amd_jpeg_decode_sparse): image i reads its
  * descriptors at d_desc + i * desc_stride and its entries at d_entries + i * entries_stride (elements) and has every block

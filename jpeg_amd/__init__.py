@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     transform, transform_quanta, view_denom, view_of_source, view_window,
     affine_matrix, decode_tensors_warped_mixed, decode_warped_mixed, warp, warp_tensor, warp_view,
     colour_matrix,
+    decompress_spectrals, plan_intervals,
     decode_projected_mixed, decode_tensors_projected_mixed, perspective_matrix, project, project_tensor, project_view,
 )
 
@@ -25,4 +26,4 @@ __all__ = ["RGB", "YCbCr", "Component", "Context", "Layout", "Planar", "Rectangu
            "region_window", "resize", "resize_tensor", "scaled_size", "tensor_pixels", "tensor_source", "tensor_spec", "transform", "transform_quanta", "view_denom",
            "view_of_source", "view_window", "affine_matrix", "decode_tensors_warped_mixed", "decode_warped_mixed", "warp", "warp_tensor",
            "warp_view", "colour_matrix", "decode_projected_mixed", "decode_tensors_projected_mixed", "perspective_matrix", "project",
-           "project_tensor", "project_view"]
+           "project_tensor", "project_view", "decompress_spectrals", "plan_intervals"]

@@ -13,6 +13,7 @@ MAX_PLANES = 4
 OK, EINVAL, ENOMEM, EHIP, ENODEV, ENOSUP = 0, -1, -2, -3, -4, -5
 COLOR_YCC8, COLOR_RGB8 = 0, 1
 CTX_OWN_STREAM = 1
+CTX_DEVICE_ENTROPY = 2
 
 
 class JpegAmdError(RuntimeError):
@@ -91,6 +92,11 @@ SIGNATURES = {
     "jpeg_amd_spectral_expand_batch": (C.c_int, [_p, _L, C.c_int, _p, C.c_size_t, _p, C.c_size_t, _p, _pp, _szp]),
     "jpeg_amd_spectral_sparsify_batch": (C.c_int, [_p, _L, C.c_int, _pp, _szp, _p, C.c_size_t, _p, C.c_size_t, C.c_uint32, _p]),
     "jpeg_amd_jpeg_decode_sparse": (C.c_int, [_p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_jpeg_plan_intervals": (C.c_int, [_p, C.c_size_t, _p, _p, _p]),
+    "jpeg_amd_jpeg_decode_intervals_host": (C.c_int, [_p, C.c_size_t, _pp, _p, _p]),
+    "jpeg_amd_jpeg_decode_spectral_device": (C.c_int, [_p, C.c_int, _pp, _szp, _p, _p, _p, _p]),
+    "jpeg_amd_ctx_device_entropy_files": (C.c_int, [_p, _p]),
+    "jpeg_amd_ctx_device_entropy_kernel_ms": (C.c_int, [_p, _p]),
     "jpeg_amd_stream_create": (C.c_void_p, []),
     "jpeg_amd_stream_destroy": (None, [_p]),
     "jpeg_amd_stream_push": (C.c_int, [_p, _p, C.c_size_t, _p, _p]),

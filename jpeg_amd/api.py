@@ -43,7 +43,7 @@ def _torch():
 class Context:
     """One jpeg_amd_ctx bound to a device and to torch's current stream on it."""
 
-    def __init__(self, device: int = 0, stream: Optional[int] = None, own_stream: bool = False):
+    def __init__(self, device: int = 0, stream: Optional[int] = None, own_stream: bool = False, device_entropy: bool = False):
         torch = _torch()
         if not torch.cuda.is_available():
             raise RuntimeError("jpeg_amd needs a GPU: torch.cuda.is_available() is False "
@@ -53,13 +53,20 @@ class Context:
         if stream is None:
             stream = torch.cuda.current_stream(self.torch_device).cuda_stream
         self._h = C.c_void_p()
-        flags = _lib.CTX_OWN_STREAM if own_stream else 0
+        flags = (_lib.CTX_OWN_STREAM if own_stream else 0) | (_lib.CTX_DEVICE_ENTROPY if device_entropy else 0)
         _lib.check(_lib.lib().jpeg_amd_ctx_create(self.device, C.c_void_p(stream), flags,
                                                  C.byref(self._h)), "jpeg_amd_ctx_create")
 
     @property
     def handle(self):
         return self._h
+
+    @property
+    def device_entropy_files(self) -> int:
+        """Files this context has entropy-decoded on the GPU so far (jpeg_amd_ctx_device_entropy_files)."""
+        n = C.c_int64()
+        _lib.check(_lib.lib().jpeg_amd_ctx_device_entropy_files(self._h, C.byref(n)), "jpeg_amd_ctx_device_entropy_files")
+        return n.value
 
     def synchronize(self):
         _lib.check(_lib.lib().jpeg_amd_ctx_synchronize(self._h), "synchronize", self._h)
@@ -423,13 +430,8 @@ class Spectral:
         t = self.transform(0, (0, 0, w, h))
         self.size, self.planes = t.size, t.planes
 
-    @classmethod
-    def decompress(cls, ctx: Context, source, scans: int = 0) -> "Spectral":
-        """Spectral.decompress(stream:) / decompress(path:) -- decode.swift:3728, os.swift:309.
-        source: a path or the file's bytes.  The entropy-coded segments are decoded on the host
-        by the library (csrc/entropy.cpp); the coefficient planes land in HBM."""
-        data = _file_bytes(source)
-        info, planes, quanta = _decode_spectral(data, scans)   # scans > 0: the image after that many scans
+    @staticmethod
+    def _file_layout(info) -> Layout:
         n = info.ncomponents
         if info.precision == 8 and n == 1:
             fmt = "y8"
@@ -437,8 +439,25 @@ class Spectral:
             fmt = "ycc8"
         else:
             fmt = ("custom", info.precision, n)
-        layout = Layout(fmt, {info.id[c]: Component((info.factor_x[c], info.factor_y[c]), c) for c in range(n)})
-        return cls.from_host(ctx, (info.width, info.height), layout, planes, [quanta[c] for c in range(n)],
+        return Layout(fmt, {info.id[c]: Component((info.factor_x[c], info.factor_y[c]), c) for c in range(n)})
+
+    @classmethod
+    def decompress(cls, ctx: Context, source, scans: int = 0, entropy: str = "host") -> "Spectral":
+        """Spectral.decompress(stream:) / decompress(path:) -- decode.swift:3728, os.swift:309.
+        source: a path or the file's bytes.  entropy="host": the entropy-coded segments are decoded on the host by the
+        library (csrc/entropy.cpp) and the coefficient planes uploaded; entropy="device": the file's bytes go up and its
+        restart intervals are decoded on the GPU (jpeg_amd_jpeg_decode_spectral_device; sequential files whose restart
+        markers are all in place -- plan_intervals says which)."""
+        if entropy == "device":
+            if scans:
+                raise ValueError("entropy='device' decodes whole files")
+            return decompress_spectrals(ctx, [source])[0]
+        if entropy != "host":
+            raise ValueError("entropy is 'host' or 'device'")
+        data = _file_bytes(source)
+        info, planes, quanta = _decode_spectral(data, scans)   # scans > 0: the image after that many scans
+        n = info.ncomponents
+        return cls.from_host(ctx, (info.width, info.height), cls._file_layout(info), planes, [quanta[c] for c in range(n)],
                              q=list(range(n)))
 
 
@@ -522,6 +541,40 @@ def inspect(source) -> _lib.FrameInfo:
     info = _lib.FrameInfo()
     _lib.check(_lib.lib().jpeg_amd_jpeg_inspect(data.ctypes.data, data.size, C.byref(info)), "jpeg_amd_jpeg_inspect")
     return info
+
+
+def plan_intervals(source):
+    """Whether a file's entropy decoding can run on the GPU, and how much work it is (jpeg_amd_jpeg_plan_intervals):
+    -> (info, nscans, nintervals), or raises with the planner's status (ENOSUP: the host decodes this file)."""
+    data = _file_bytes(source)
+    info, nscans, nintervals = _lib.FrameInfo(), C.c_int32(), C.c_int64()
+    _lib.check(_lib.lib().jpeg_amd_jpeg_plan_intervals(data.ctypes.data, data.size, C.byref(info), C.byref(nscans), C.byref(nintervals)),
+               "jpeg_amd_jpeg_plan_intervals")
+    return info, nscans.value, nintervals.value
+
+
+def decompress_spectrals(ctx: "Context", sources) -> List["Spectral"]:
+    """Files of any mix of sizes and layouts -> Spectral images, entropy-decoded on the GPU in one launch
+    (jpeg_amd_jpeg_decode_spectral_device).  Raises if the planner refuses any of the files, with nothing decoded."""
+    torch = _torch()
+    files = [_file_bytes(s) for s in sources]
+    n = len(files)
+    if n == 0:
+        return []
+    infos = [inspect(f) for f in files]
+    planes = [[torch.empty((i.units_y[c], i.units_x[c], 64), dtype=torch.int16, device=ctx.torch_device) for c in range(i.ncomponents)]
+              for i in infos]
+    coef = (C.c_void_p * (MAX_PLANES * n))()
+    for k, ps in enumerate(planes):
+        for c, t in enumerate(ps):
+            coef[MAX_PLANES * k + c] = t.data_ptr()
+    quanta = np.zeros((n, MAX_PLANES, 64), np.uint16)
+    out_info, status = (_lib.FrameInfo * n)(), (C.c_int32 * n)()
+    _lib.check(_lib.lib().jpeg_amd_jpeg_decode_spectral_device(
+        ctx.handle, n, (C.c_void_p * n)(*[f.ctypes.data for f in files]), (C.c_size_t * n)(*[f.size for f in files]), coef,
+        quanta.ctypes.data, out_info, status), "jpeg_amd_jpeg_decode_spectral_device", ctx.handle)
+    return [Spectral(ctx, (i.width, i.height), Spectral._file_layout(i), planes[k], [quanta[k][c] for c in range(i.ncomponents)],
+                     q=list(range(i.ncomponents))) for k, i in enumerate(out_info)]
 
 
 def exif_orientation(source) -> int:

@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libjpeg_amd.so")
 
-SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_tile.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "entropy.cpp", "entropy_encode.cpp"]
-HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "mapped_walk.hpp", "resample_request.hpp", "resample_chunks.hpp"]
+SOURCES = ["kernels_stage.hip", "kernels_fused.hip", "kernels_quad.hip", "kernels_encode.hip", "kernels_generic.hip", "kernels_transform.hip", "kernels_tile.hip", "kernels_resample.hip", "kernels_reduce.hip", "kernels_pixels.hip", "kernels_expand.hip", "kernels_entropy.hip", "capi.hip", "capi_view.hip", "capi_host.hip", "capi_file.hip", "capi_files.hip", "capi_spectral.hip", "capi_tensor.hip", "capi_entropy.hip", "entropy.cpp", "entropy_encode.cpp"]
+HEADERS = ["dct.hpp", "kernels.hpp", "upsample.hpp", "fused_common.hpp", "quantise.hpp", "worker_pool.hpp", "capi_internal.hpp", "transform.hpp", "interleave.hpp", "tile_decode.hpp", "tile_staging.hpp", "resample.hpp", "tensor_sink.hpp", "antialias.hpp", "tensor_source.hpp", "sparse_format.hpp", "orient.hpp", "mapped_walk.hpp", "resample_request.hpp", "resample_chunks.hpp", "huffman_interval.hpp", "interval_plan.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-command-line-argument"]
 # Per-source flags.  The transform kernels are compiled WITHOUT the SLP vectoriser: it turns the float arithmetic of the 8-point
@@ -49,7 +49,9 @@ EXTRA_FLAGS = {"kernels_generic.hip": _NO_SLP, "kernels_encode.hip": _NO_SLP, "k
 NO_SCRATCH = {"kernels_quad.hip": "k_quad420", "kernels_fused.hip": "k_luma_fused",
               "kernels_resample.hip": ("k_resize_bilinear", "k_resize_tensorILb0E", "k_mapped_", "k_resize_placed_tensorILb1E",
                                        "k_tables_placed_tensorILb1E"),
-              "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed"}
+              "kernels_pixels.hip": "k_tensor_pixels", "kernels_expand.hip": "k_expand_mixed",
+              # k_huffman_intervals indexes a block's 64 coefficients by the stream: they go to the plane, never to a private array
+              "kernels_entropy.hip": "k_huffman_intervals"}
 WARN_SCRATCH = {"kernels_encode.hip": "k_encode_fused", "kernels_generic.hip": "k_generic_fused",
                 "kernels_transform.hip": "k_spectral_transform",
                 "kernels_tile.hip": ("k_region_decode", "k_scaled_decode", "k_view_decode"),

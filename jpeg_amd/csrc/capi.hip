@@ -244,6 +244,7 @@ int jpeg_amd_ctx_create(int device, void *stream, int flags, jpeg_amd_ctx **out)
     jpeg_amd_ctx *ctx = new (std::nothrow) jpeg_amd_ctx();
     if (!ctx) return JPEG_AMD_ENOMEM;
     ctx->device = device;
+    ctx->flags = flags;
     int status = JPEG_AMD_OK;
     do {
         if (hipSetDevice(device) != hipSuccess) { status = JPEG_AMD_ENODEV; break; }
@@ -274,8 +275,10 @@ int jpeg_amd_ctx_destroy(jpeg_amd_ctx *ctx)
     ctx->workers.reset();
     ctx->copiers.reset();
     for (DeviceBuffer *buf : {&ctx->scratch, &ctx->region, &ctx->resize_src, &ctx->resize_rec, &ctx->mixed, &ctx->tensor_px, &ctx->expand,
-                              &ctx->file_planes})
+                              &ctx->file_planes, &ctx->entropy})
         if (buf->ptr) (void)hipFree(buf->ptr);
+    for (hipEvent_t ev : ctx->entropy_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (ctx->d_qstage) (void)hipFree(ctx->d_qstage);
     if (ctx->d_walk) (void)hipFree(ctx->d_walk);
     if (ctx->d_flag) (void)hipFree(ctx->d_flag);

@@ -118,6 +118,28 @@ try {
     *dense = true;
     if (!data) return JPEG_AMD_EINVAL;
     jpeg_amd_frame_info seen{};
+    if (to.device) to.device->on = false;
+    if ((ctx->flags & JPEG_AMD_CTX_DEVICE_ENTROPY) && to.device) {
+        namespace iv = jpeg_amd::interval;
+        iv::FilePlan plan;
+        const int ps = iv::plan_file(data, nbytes[file], &plan);
+        if (ps != JPEG_AMD_OK && ps != JPEG_AMD_ENOSUP) return ps;          // malformed: the host decoder says the same
+        if (ps == JPEG_AMD_OK) {
+            if (!same_frame(plan.info, frame)) return JPEG_AMD_EINVAL;
+            const iv::FileBlock b = iv::file_block(plan);
+            bool fits = b.size <= to.room;                                   // (or its bytes and list exceed its plane: the host route)
+            for (const iv::IntervalWork &w : plan.work) fits = fits && iv::work_fits(w, plan.scans[w.scan], nbytes[file]);
+            if (fits) {
+                iv::write_file_block(plan, b, data, reinterpret_cast<char *>(to.planes[0]));
+                for (int c = 0; c < plan.info.ncomponents; ++c) std::memcpy(to.quanta[c], plan.quanta[c], 128);
+                int16_t *const none[JPEG_AMD_MAX_PLANES] = {nullptr, nullptr, nullptr, nullptr};
+                to.device->record = iv::file_record(plan, b, 0, none);
+                to.device->bytes = b.size;
+                to.device->on = true;
+                return JPEG_AMD_OK;                                          // (*dense: the expand leaves its planes alone)
+            }
+        }
+    }
     // Sparse first, without a look at the headers beforehand: the decoder itself refuses a frame with more blocks than the
     // descriptor array holds and never writes past the arena, so a file of another geometry is caught afterwards.
     if (sb.ok) {
@@ -219,6 +241,13 @@ struct HostPlanes {
 }  // namespace
 
 // ---- JPEG bytes -> pixels (host entropy decode + the fused device path) ----------------------
+namespace {
+// (defined with the batch pipeline below; device_route: whether JPEG_AMD_CTX_DEVICE_ENTROPY applies to this call)
+int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads,
+                          int cosited, jpeg_amd_color color, uint8_t *h_pixels, uint8_t *d_pixels_out, size_t pixel_stride,
+                          jpeg_amd_frame_info *info_out, bool device_route);
+}  // namespace
+
 int jpeg_amd_decompress(jpeg_amd_ctx *ctx, const uint8_t *h_jpeg, size_t nbytes, int cosited,
                         jpeg_amd_color color, uint8_t *h_pixels, size_t pixel_capacity,
                         jpeg_amd_frame_info *info_out)
@@ -233,7 +262,8 @@ try {
     if (!h_pixels || pixel_capacity < need) return JPEG_AMD_EINVAL;
     // a batch of one: pinned staging kept in the context, restart intervals and the copy-out on
     // host threads (their number left to the library)
-    return jpeg_amd_decompress_batch(ctx, &h_jpeg, &nbytes, 1, 0, cosited, color, h_pixels, need, nullptr);
+    // (one file stays on the host route whatever the context's flags say: a lone stream is a lone lane on the device)
+    return decompress_batch_impl(ctx, &h_jpeg, &nbytes, 1, 0, cosited, color, h_pixels, nullptr, need, nullptr, false);
 }
 JA_NOTHROW_TAIL
 
@@ -280,7 +310,8 @@ struct BatchDecode : FileBatch {
     int nc, chunk, nchunks;
     SparseBudget sb;
     SlotLayout at;
-    bool to_host, direct_out, copies_out;
+    bool to_host, direct_out, copies_out, device_route;
+    std::vector<DeviceEntropyFile> device_files;   // per file (JPEG_AMD_CTX_DEVICE_ENTROPY)
 
     int images(int k) const { return std::min(chunk, n_images - k * chunk); }
     int decode_file(int file, std::vector<uint32_t> &record);
@@ -295,6 +326,8 @@ int BatchDecode::decode_file(int file, std::vector<uint32_t> &record)
     char *host = static_cast<char *>(ctx->file_pinned[k & 1]);
     Into to{k & 1, m, reinterpret_cast<uint32_t *>(host + at.sparse_off), reinterpret_cast<uint16_t(*)[64]>(host + at.quanta_off + (size_t)i * kQSlotElems * 2), {}};
     for (int c = 0; c < nc; ++c) to.planes[c] = reinterpret_cast<int16_t *>(host + at.coef_off[c]) + plane[c] * i;
+    to.room = plane[0] * 2;
+    to.device = device_route ? &device_files[(size_t)file] : nullptr;
     // spare threads only help a file that has restart intervals, and the sparse form is written by one thread per file: with
     // fewer files than threads a batch of such files travels as planes
     SparseBudget mine = sb;
@@ -319,15 +352,22 @@ int BatchDecode::submit(int k)
     int16_t *d_coef[JPEG_AMD_MAX_PLANES] = {};
     for (int c = 0; c < nc; ++c) d_coef[c] = reinterpret_cast<int16_t *>(dev + at.coef_off[c]);
     bool any_sparse = false;
+    std::vector<DeviceEntropyJob> jobs;
     for (int i = 0; i < m; ++i) {
         any_sparse = any_sparse || !skip[i];
-        if (skip[i])                                 // planes, this image only (progressive, damaged, too dense)
+        const DeviceEntropyFile &df = device_files[(size_t)(base + i)];
+        if (df.on) {                                 // its planes are produced on the device, from its block
+            DeviceEntropyJob job{&df, host + at.coef_off[0] + plane[0] * 2 * i, {}};
+            for (int c = 0; c < nc; ++c) job.d_planes[c] = d_coef[c] + plane[c] * i;
+            jobs.push_back(job);
+        } else if (skip[i])                          // planes, this image only (progressive, damaged, too dense)
             for (int c = 0; c < nc; ++c)
                 JA_HIP(ctx, hipMemcpyAsync(dev + at.coef_off[c] + plane[c] * 2 * i, host + at.coef_off[c] + plane[c] * 2 * i, plane[c] * 2,
                                            hipMemcpyHostToDevice, ctx->stream));
     }
     // tables, flags, record offsets and the packed records: one copy
     JA_HIP(ctx, hipMemcpyAsync(dev + at.quanta_off, host + at.quanta_off, at.sparse_off - at.quanta_off + loop.packed_end[slot].load() * 4, hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(decode_blocks_on_device(ctx, jobs.data(), (int)jobs.size()));
     if (any_sparse) {
         PlaneSetMut cs{};
         for (int c = 0; c < nc; ++c) { cs.ptr[c] = d_coef[c]; cs.stride[c] = plane[c]; }
@@ -385,7 +425,7 @@ int BatchDecode::run()
 // Files -> pixels, in host memory (h_pixels) or left on the device (d_pixels_out): see jpeg_amd_decompress_batch[_device].
 int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], const size_t nbytes[], int n_images, int nthreads,
                           int cosited, jpeg_amd_color color, uint8_t *h_pixels, uint8_t *d_pixels_out, size_t pixel_stride,
-                          jpeg_amd_frame_info *info_out)
+                          jpeg_amd_frame_info *info_out, bool device_route)
 {
     JA_TRY(bind(ctx));
     if (!h_jpeg || !nbytes || (!h_pixels && !d_pixels_out) || n_images < 0) return JPEG_AMD_EINVAL;
@@ -424,6 +464,8 @@ int decompress_batch_impl(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], cons
     d.at.px_off = d.at.take(d.to_host ? d.npx * d.chunk : 0);
     JA_TRY(ensure_file_staging(ctx, d.at.slot_bytes, d.at.slot_bytes));
     d.nthreads = host_threads(nthreads, &d.auto_threads);
+    d.device_route = device_route;
+    d.device_files.resize((size_t)n_images);
 
     d.nchunks = (n_images + d.chunk - 1) / d.chunk;
     // a caller whose pixel buffer is page-locked gets the download straight into it: no copy out of the pinned slot
@@ -439,7 +481,7 @@ int jpeg_amd_decompress_batch(jpeg_amd_ctx *ctx, const uint8_t *const h_jpeg[], 
                               uint8_t *h_pixels, size_t pixel_stride, jpeg_amd_frame_info *info_out)
 try {
     if (!h_pixels) return JPEG_AMD_EINVAL;
-    return decompress_batch_impl(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_pixels, nullptr, pixel_stride, info_out);
+    return decompress_batch_impl(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, h_pixels, nullptr, pixel_stride, info_out, true);
 }
 JA_NOTHROW_TAIL
 
@@ -448,7 +490,7 @@ int jpeg_amd_decompress_batch_device(jpeg_amd_ctx *ctx, const uint8_t *const h_j
                                      uint8_t *d_pixels, size_t pixel_stride, jpeg_amd_frame_info *info_out)
 try {
     if (!d_pixels) return JPEG_AMD_EINVAL;
-    return decompress_batch_impl(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, d_pixels, pixel_stride, info_out);
+    return decompress_batch_impl(ctx, h_jpeg, nbytes, n_images, nthreads, cosited, color, nullptr, d_pixels, pixel_stride, info_out, true);
 }
 JA_NOTHROW_TAIL
 

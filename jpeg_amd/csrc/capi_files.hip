@@ -29,6 +29,7 @@ struct FileSpec {
     // written by the thread that decodes the file, read by the directing thread once the file's chunk is complete
     uint64_t where;                                 // its record [descriptors][entries] in the slot's packed records, elements
     bool dense;                                     // decoded into planes: uploaded whole, not expanded
+    DeviceEntropyFile device;                       // ... or produced on the device from its block (JPEG_AMD_CTX_DEVICE_ENTROPY)
 };
 
 // A chunk: files [i0, i0 + m), and where the parts of its staging slot begin.  [quanta .. packed records] goes up in one copy.
@@ -76,6 +77,8 @@ int FilesDecode::decode_file(int file, std::vector<uint32_t> &record)
         to.planes[c] = reinterpret_cast<int16_t *>(host + ch.dense_off + at);
         at += align256(plane_samples(&f.layout, c) * 2);
     }
+    to.room = at - f.dense_off;                      // (a file's planes lie in a row here: a block may take them all)
+    to.device = &f.device;
     return decode_to_slot(file, to, f.info, f.sb, false, record, &f.where, &f.dense);   // (what pass 0 saw, headers included)
 }
 
@@ -95,6 +98,7 @@ int FilesDecode::submit(int k)
     uint32_t *groups = reinterpret_cast<uint32_t *>(host + ch.groups_off);
     int n_items = 0;
     uint64_t acc = 0;
+    std::vector<DeviceEntropyJob> jobs;
     for (int i = 0; i < ch.m; ++i) {
         const FileSpec &f = files[(size_t)(ch.i0 + i)];
         jpeg_amd_image &im = images[(size_t)i];
@@ -109,11 +113,16 @@ int FilesDecode::submit(int k)
             item.d_coef[c] = reinterpret_cast<int16_t *>(d_planes + f.plane_off[c]);
             im.d_coef[c] = item.d_coef[c];
             item.window[c] = f.window[c];
-            if (f.dense) {
+            if (f.dense && !f.device.on) {
                 const size_t bytes = plane_samples(&f.layout, c) * 2;
                 JA_HIP(ctx, hipMemcpyAsync(item.d_coef[c], host + ch.dense_off + at, bytes, hipMemcpyHostToDevice, ctx->stream));
                 at += align256(bytes);
             }
+        }
+        if (f.device.on) {                           // its planes are produced on the device, from its block
+            DeviceEntropyJob job{&f.device, host + ch.dense_off + f.dense_off, {}};
+            for (int c = 0; c < f.layout.nplanes; ++c) job.d_planes[c] = item.d_coef[c];
+            jobs.push_back(job);
         }
         if (f.dense) continue;
         item.head = f.head;
@@ -126,6 +135,7 @@ int FilesDecode::submit(int k)
     groups[n_items] = (uint32_t)acc;
     JA_HIP(ctx, hipMemcpyAsync(dev + ch.quanta_off, host + ch.quanta_off, ch.sparse_off - ch.quanta_off + loop.packed_end[slot].load() * 4,
                                hipMemcpyHostToDevice, ctx->stream));
+    JA_TRY(decode_blocks_on_device(ctx, jobs.data(), (int)jobs.size()));
     JA_HIP(ctx, launch_expand_mixed(ctx->stream, n_items, dev + ch.items_off, reinterpret_cast<const uint32_t *>(dev + ch.groups_off),
                                     (uint32_t)acc, reinterpret_cast<const uint32_t *>(dev + ch.sparse_off)));
     std::vector<jpeg_amd_view> views((size_t)ch.m);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "interleave.hpp"
+#include "interval_plan.hpp"
 #include "kernels.hpp"
 #include "resample_request.hpp"
 #include "sparse_format.hpp"
@@ -34,6 +35,7 @@ struct DeviceBuffer {
 
 struct jpeg_amd_ctx {
     int device = 0;
+    int flags = 0;                 // jpeg_amd_ctx_create's
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -57,6 +59,12 @@ struct jpeg_amd_ctx {
     // the file calls to tensors (capi_files.hip): the coefficient planes of a chunk's files.  Only the heads of the blocks of
     // the views' windows are ever written: nothing else of it may be read.
     DeviceBuffer file_planes;
+    // jpeg_amd_jpeg_decode_spectral_device and the batch file paths under JPEG_AMD_CTX_DEVICE_ENTROPY: the files' records and
+    // blocks of a launch of k_huffman_intervals, and its statuses.
+    DeviceBuffer entropy;
+    int64_t device_entropy_files = 0;   // files whose entropy decoding ran on the device, since the context was made
+    hipEvent_t entropy_ev[2] = {nullptr, nullptr};   // around every launch of k_huffman_intervals (made on first use)
+    double device_entropy_kernel_ms = 0;              // their sum
     int qslot = 0;
     int last_hip = 0;
     // staging of the batch file paths (jpeg_amd_decompress_batch, jpeg_amd_decompress_tensor_mixed, jpeg_amd_compress_batch), kept
@@ -208,6 +216,24 @@ struct SlotLayout {
         return at;
     }
 };
+// A file of a chunk whose planes k_huffman_intervals produces (JPEG_AMD_CTX_DEVICE_ENTROPY): its block (interval_plan.hpp) lies
+// in the pinned slot where its first plane would lie, `bytes` long; `record` counts from the block's first byte and names no
+// planes yet.  Written by the thread that decodes the file, read by the directing thread once the chunk is complete.
+struct DeviceEntropyFile {
+    bool on = false;
+    interval::IntervalFile record{};
+    size_t bytes = 0;
+};
+// ... and what submit(k) hands to decode_blocks_on_device for it: where the block lies (pinned) and the planes to write.
+struct DeviceEntropyJob {
+    const DeviceEntropyFile *file;
+    const char *h_block;
+    int16_t *d_planes[JPEG_AMD_MAX_PLANES];
+};
+// The blocks up (a copy each, on the context's stream), one launch of k_huffman_intervals, the statuses back; waits for them and
+// returns the first that is not OK, in job and interval order.  (capi_entropy.hip)
+int decode_blocks_on_device(jpeg_amd_ctx *ctx, const DeviceEntropyJob *jobs, int n);
+
 // One call of a batch decode of files behind its checks: what the two pipelines share of it.
 struct FileBatch {
     jpeg_amd_ctx *ctx;
@@ -225,11 +251,15 @@ struct FileBatch {
         uint32_t *packed;
         uint16_t (*quanta)[64];
         int16_t *planes[JPEG_AMD_MAX_PLANES];
+        size_t room = 0;                       // bytes of planes[0]: what a device file's block may take
+        DeviceEntropyFile *device = nullptr;   // where to note that the file took the device route (nullptr: it may not)
     };
     // One file, on a thread of the file queue: sparse into the thread's own record, then packed behind the records already in
     // the slot (one fetch_add on loop.packed_end[slot]; *where: its offset in `packed`, elements); where the sparse decoder says
     // ENOSUP, or sb.ok is false, into the planes on nthreads / m threads (*dense).  `frame`: what the file must be;
     // inspect_dense: look at the headers of a file that goes into planes, because nobody has yet.
+    // Under JPEG_AMD_CTX_DEVICE_ENTROPY, and with to.device, the planner is asked first: a file it takes, whose block fits
+    // to.room, is a dense file (*dense) whose planes the device produces -- only its block and its tables are written.
     int decode_to_slot(int file, const Into &to, const jpeg_amd_frame_info &frame, const SparseBudget &sb, bool inspect_dense,
                        std::vector<uint32_t> &record, uint64_t *where, bool *dense);
     // The loop's device side on the context's stream and events, around the pipeline's submit(k).

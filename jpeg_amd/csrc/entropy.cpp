@@ -28,6 +28,7 @@
 
 #include "../../include/jpeg_amd.h"
 #include "sparse_format.hpp"
+#include "interval_plan.hpp"
 
 namespace sparse_fmt = jpeg_amd::sparse;   // (Decoder::sparse is the output of a sparse decode)
 
@@ -420,6 +421,11 @@ struct Decoder {
     bool auto_threads = false;   // nthreads chosen by the library: only where a thread pays off
     int max_scans = 0x7fffffff;  // stop after this many scans (progressive previews, JPEG.Context-style)
     SparseOut *sparse = nullptr; // entries instead of planes (sequential scans with every restart marker in place only)
+    // the planner of the device entropy decoder: nothing is decoded, every scan adds to the work list instead.  `refused`:
+    // the file is well formed as far as the walk has come, but not for the device (the walk goes on: what is malformed
+    // further on still decides)
+    jpeg_amd::interval::FilePlan *intervals = nullptr;
+    bool refused = false, scanned[JPEG_AMD_MAX_PLANES] = {false, false, false, false};
     int nscans = 0;
 
     static int units(int size, int stride) { return size / stride + (size % stride != 0 ? 1 : 0); }
@@ -536,6 +542,7 @@ struct Decoder {
     int plan_scan(const uint8_t *hdr, size_t hlen, ScanPlan *plan);
     int bind_tables(const ScanPlan &plan, uint16_t (*quanta_out)[64]);
     int decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, const uint8_t *end, uint16_t (*quanta_out)[64]);
+    int plan_intervals(const ScanPlan &plan, int planned, const uint8_t *ecs, const uint8_t *end);
 
     // Walk the whole file.  coef == nullptr: headers only (fills info, counts scans).
     // Resumable: `pos`, `have_frame` and all tables live in the object.  With `streaming` set the
@@ -1124,6 +1131,7 @@ int Decoder::decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, co
     if (planned == JPEG_AMD_EINVAL) return planned;
     const int bound = bind_tables(plan, quanta_out);
     if (bound != JPEG_AMD_OK) return bound;
+    if (intervals) return plan_intervals(plan, planned, ecs, end);
     if (!comps[0].coef) return JPEG_AMD_OK;   // inspect-only pass
     if (planned != JPEG_AMD_OK) return planned;
 
@@ -1172,7 +1180,77 @@ int Decoder::decode_scan(const uint8_t *hdr, size_t hlen, const uint8_t *ecs, co
     return JPEG_AMD_OK;
 }
 
+// ---- the planner of the device entropy decoder ---------------------------------------------------------------------------
+// One scan of a file that is planned, not decoded: its record, the tables it names as they stand now, and one work item per
+// restart interval.  What decode_scan refuses as malformed is refused here with the same status; what it would decode, but the
+// device route does not take, sets `refused` and lets the walk go on.
+int Decoder::plan_intervals(const ScanPlan &plan, int planned, const uint8_t *ecs, const uint8_t *end)
+{
+    namespace iv = jpeg_amd::interval;
+    if (planned != JPEG_AMD_OK || plan.progressive) { refused = true; return JPEG_AMD_OK; }
+    for (int si = 0; si < plan.nslots; ++si)
+        if (!dc[plan.slots[si].td].defined || !ac[plan.slots[si].ta].defined) return JPEG_AMD_EINVAL;
+    if (refused) return JPEG_AMD_OK;
+    // a component that a second scan writes again: the host decodes the scans one after the other, the device all at once
+    for (int j = 0; j < plan.ns; ++j) {
+        const int ci = (int)(plan.sc[j].c - comps.data());
+        if (scanned[ci]) { refused = true; return JPEG_AMD_OK; }
+        scanned[ci] = true;
+    }
+    if (plan.nintervals > (long)JPEG_AMD_MAX_DEVICE_INTERVALS - (long)intervals->work.size()) { refused = true; return JPEG_AMD_OK; }
+    const std::vector<const uint8_t *> starts = find_interval_starts(ecs, end, plan.nintervals);
+    if ((long)starts.size() != plan.nintervals) { refused = true; return JPEG_AMD_OK; }   // a restart marker is missing, or one too many
+
+    auto table_of = [&](const Huffman &h) {
+        iv::IntervalTable t;
+        std::memset(&t, 0, sizeof t);
+        std::memcpy(t.fast, h.fast, sizeof t.fast);
+        std::memcpy(t.maxcode + 1, h.maxcode + 1, sizeof(int32_t) * 17);      // ([0] is never set, nor read)
+        std::memcpy(t.mincode + 1, h.mincode + 1, sizeof(int32_t) * 16);
+        std::memcpy(t.valptr + 1, h.valptr + 1, sizeof(int32_t) * 16);
+        const int nsyms = h.valptr[16] + (h.maxcode[16] >= 0 ? h.maxcode[16] - h.mincode[16] + 1 : 0);
+        std::memcpy(t.symbols, h.symbols, (size_t)std::min(std::max(nsyms, 0), 256));
+        for (size_t k = 0; k < intervals->tables.size(); ++k)
+            if (std::memcmp(&intervals->tables[k], &t, sizeof t) == 0) return (int32_t)k;
+        intervals->tables.push_back(t);
+        return (int32_t)(intervals->tables.size() - 1);
+    };
+    iv::IntervalScan s{};
+    s.ns = plan.ns;
+    s.mcux = plan.mcux;
+    s.mcus = (int32_t)plan.total;
+    for (int j = 0; j < plan.ns; ++j) {
+        const Component *c = plan.sc[j].c;
+        s.c[j] = iv::IntervalComp{(int32_t)(c - comps.data()), table_of(dc[plan.sc[j].td]), table_of(ac[plan.sc[j].ta]),
+                                  plan.ns > 1 ? c->fx : 1, plan.ns > 1 ? c->fy : 1, c->ux, c->uy};
+    }
+    const uint32_t scan = (uint32_t)intervals->scans.size();
+    intervals->scans.push_back(s);
+    intervals->bytes.push_back(iv::ScanBytes{(size_t)(ecs - data), (size_t)(end - data)});
+    for (long k = 0; k < plan.nintervals; ++k) {
+        const uint8_t *b = starts[(size_t)k], *e = k + 1 < plan.nintervals ? starts[(size_t)k + 1] - 2 : end;
+        intervals->work.push_back(iv::IntervalWork{scan, (uint32_t)(k * plan.ri), (uint32_t)std::min(plan.total, (k + 1) * plan.ri), 0,
+                                                   (uint64_t)(b - data), (uint64_t)(e - data)});
+    }
+    return JPEG_AMD_OK;
+}
+
 }  // namespace
+
+int jpeg_amd::interval::plan_file(const uint8_t *data, size_t nbytes, FilePlan *plan)
+{
+    *plan = FilePlan{};
+    Decoder d{data, nbytes};
+    d.nthreads = 1;
+    d.intervals = plan;
+    const int st = d.run(nullptr, plan->quanta);
+    if (st != JPEG_AMD_OK) return st;
+    for (const Component &c : d.comps)
+        if (!c.bound) return JPEG_AMD_EINVAL;   // a component no scan ever touched
+    if (d.refused) return JPEG_AMD_ENOSUP;
+    plan->info = d.info;
+    return JPEG_AMD_OK;
+}
 
 extern "C" {
 
@@ -1418,6 +1496,61 @@ int jpeg_amd_jpeg_decode_sparse(const uint8_t *data, size_t nbytes, uint32_t *h_
     *nentries = out.n;
     if (info) *info = d.info;
     return JPEG_AMD_OK;
+    JA_NOTHROW_END
+}
+
+int jpeg_amd_jpeg_plan_intervals(const uint8_t *data, size_t nbytes, jpeg_amd_frame_info *info, int32_t *nscans, int64_t *nintervals)
+{
+    if (!data || !info || !nscans || !nintervals) return JPEG_AMD_EINVAL;
+    JA_NOTHROW_BEGIN
+    jpeg_amd::interval::FilePlan plan;
+    const int st = jpeg_amd::interval::plan_file(data, nbytes, &plan);
+    if (st != JPEG_AMD_OK) return st;
+    *info = plan.info;
+    *nscans = (int32_t)plan.scans.size();
+    *nintervals = (int64_t)plan.work.size();
+    return JPEG_AMD_OK;
+    JA_NOTHROW_END
+}
+
+// The host instantiation of huffman_interval.hpp over the planner's work list, one interval after the other, straight from
+// the file's bytes: what k_huffman_intervals computes, without a device.
+int jpeg_amd_jpeg_decode_intervals_host(const uint8_t *data, size_t nbytes, int16_t *const h_coef[], uint16_t h_quanta[][64],
+                                        jpeg_amd_frame_info *info)
+{
+    if (!data || !h_coef || !h_quanta) return JPEG_AMD_EINVAL;
+    JA_NOTHROW_BEGIN
+    namespace iv = jpeg_amd::interval;
+    iv::FilePlan plan;
+    const int st = iv::plan_file(data, nbytes, &plan);
+    if (st != JPEG_AMD_OK) return st;
+    int16_t *planes[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int c = 0; c < plan.info.ncomponents; ++c) {
+        if (!h_coef[c]) return JPEG_AMD_EINVAL;
+        planes[c] = h_coef[c];
+        std::memcpy(h_quanta[c], plan.quanta[c], 128);
+    }
+    if (info) *info = plan.info;
+    // the file's block exactly as a launch uploads it (write_file_block: only the entropy-coded bytes, the intervals' ranges
+    // rebased onto them), in an allocation of exactly its size, and every interval decoded from there
+    for (const iv::IntervalWork &w : plan.work)
+        if (!iv::work_fits(w, plan.scans[w.scan], nbytes)) return JPEG_AMD_EINVAL;
+    const iv::FileBlock b = iv::file_block(plan);
+    std::vector<char> block(b.size);
+    iv::write_file_block(plan, b, data, block.data());
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(block.data() + b.bytes_at);
+    int first = JPEG_AMD_OK;
+    for (size_t k = 0; k < plan.work.size(); ++k) {
+        iv::IntervalWork w;
+        std::memcpy(&w, block.data() + b.work_at + k * sizeof w, sizeof w);
+        iv::IntervalScan s;
+        std::memcpy(&s, block.data() + b.scans_at + w.scan * sizeof s, sizeof s);
+        if (!iv::work_fits(w, s, b.nbytes)) return JPEG_AMD_EINVAL;
+        const int is = iv::decode_interval(s, reinterpret_cast<const iv::IntervalTable *>(block.data() + b.tables_at), planes,
+                                           bytes + w.begin, bytes + w.end, w.mcu0, w.mcu1);
+        if (is != JPEG_AMD_OK && first == JPEG_AMD_OK) first = is;
+    }
+    return first;
     JA_NOTHROW_END
 }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/jpeg_amd.h"
+#include "huffman_interval.hpp"
 
 namespace jpeg_amd {
 
@@ -71,6 +72,22 @@ uint64_t   expand_mixed_groups(const jpeg_amd_expand_item &item);   // workgroup
 void       expand_mixed_record(void *dst, const jpeg_amd_expand_item &item);
 hipError_t launch_expand_mixed(hipStream_t stream, int n_images, const void *d_items, const uint32_t *d_groups, uint32_t nwg,
                                const uint32_t *d_records);
+
+// ---- entropy decoding on the device (kernels_entropy.hip) -----------------------------------------------
+// One launch of k_huffman_intervals: a work-item per restart interval.  `base`: a buffer in device memory, 16-byte aligned,
+// of base_bytes bytes, that holds the files' blocks (interval_plan.hpp); `files`: a record per file, with its whole planes
+// (16-byte aligned) and where its block lies behind `base`; first[f]: the intervals of the files before f, first[nfiles] ==
+// nwork, the launch's work-items; status: one word per interval, in that order.  The host has checked every interval
+// (interval_plan.hpp, work_fits); the kernel checks what it takes from device memory once more.
+struct IntervalLaunch {
+    const uint8_t *base;
+    const interval::IntervalFile *files;
+    const uint32_t *first;
+    int32_t *status;
+    uint64_t base_bytes;
+    uint32_t nfiles, nwork;
+};
+hipError_t launch_huffman_intervals(hipStream_t stream, const IntervalLaunch &launch);
 
 // a9 (+ a11/a12): upsample + interleave, written as Rectangular uint16, or colour-converted
 // straight to YCbCr / RGB bytes.  Planes are uint16 (or uint8 when planes_u8).
